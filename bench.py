@@ -6,7 +6,13 @@ Default mode (`--mode frame`): a "step" is one frame of the render hot path: tha
 mapping, seed 1, followed by the tonemapped read-out into device memory and (N > 1) the gather of the row
 stripes.  Scene, BVH and film are resident in HBM before the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run does what the headline needs and nothing else: set-up, W warm-up steps, the K timed steps, the result line.
+--full adds everything else the line can carry (the objects listed under "Extra objects" below, the `strong` / `c5` groups,
+gather_ms_rank0, and in --mode dropin the halves, kernel time, wavefront A/B and CPU oracle).  --dump-outputs DIR writes what
+the last timed step computed as DIR/<name>.npy (see write_outputs); inputs are fixed (scene, seed 1), so two builds can be
+compared output for output.
 
 N > 1 started WITHOUT a launcher (no WORLD_SIZE in the environment) launches itself: the parent — before it imports
 torch or touches the GPU — starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
@@ -21,12 +27,12 @@ torch or touches the GPU — starts `python -m torch.distributed.run --nnodes=1 
                             a step is trace_frame_additive() + get_tonemapped_pixels(); metric = primary rays/s,
                             the reference's own stats.rs:27 definition.  N = 1 only.
 
-Rank 0 prints ONE JSON line (see the repo instructions for the contract).  The default run (weak, c4) carries three result
+Rank 0 prints ONE JSON line.  A --full run (weak, c4) carries three result
 groups: the line itself (weak scaling: what the driver's scaling curve is made of), `strong` (the fixed 1080p x 64 frame
 dealt to the N ranks) and `c5` (BASELINE config 5, the fixed 3840x2160 x 256 frame dealt to the N ranks), each with its own
 ms_per_step, gather_ms_rank0, gather_path ("none" | "library_rccl" | "torch_all_gather"), rccl_ranks (what ncclCommCount
 returned) and gather_error (null unless the library's RCCL path was refused and torch's all_gather stood in).
-Extra objects of the line:
+Extra objects of the line (--full only):
   roofline      dominant kernel = trace_kernel (closest-hit traversal), secondary launches.  It is bound by the CU's VECTOR MEMORY
                 PIPE (texture addresser / L1 / data return: TA busy 0.91, TD busy 0.95 of its cycles), not by HBM (the 1.5 MB scene
                 is cache-resident), not by VALU issue (12 % fewer instructions in the hot block change nothing, one more divergent
@@ -84,8 +90,8 @@ def parse_args(argv=None):
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child passes (roofline PMC fields become null)")
-    ap.add_argument("--no-groups", action="store_true", help="default run only: skip the `strong` and `c5` result groups")
-    ap.add_argument("--no-dropin", action="store_true", help="default N = 1 run only: skip the `dropin` object")
+    ap.add_argument("--no-groups", action="store_true", help="--full weak c4 run only: skip the `strong` and `c5` result groups")
+    ap.add_argument("--no-dropin", action="store_true", help="--full N = 1 run only: skip the `dropin` object")
     ap.add_argument("--native-gather", choices=["auto", "on", "off"], default="auto",
                     help="N > 1: gather the stripes with the library's own RCCL path (on), torch.distributed (off), or try native first")
     ap.add_argument("--stripe-rows", type=int, default=0, help="rows per stripe of the deal over ranks (and of the blocks dealt to the frame slices); 0: the default")
@@ -96,6 +102,11 @@ def parse_args(argv=None):
                     help="v = idx / width instead of the reference's idx / height (SURVEY.md 8d: reported next to the headline, never as it)")
     ap.add_argument("--slices", type=int, default=0, help="concurrent frame slices of the timed frames (0: library default)")
     ap.add_argument("--spawn", action="store_true", help="launch the rank processes from here even for N = 1 (what N > 1 without a launcher does)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline (with its rocprofv3 --pmc child passes), other semantics, "
+                         "strong / c5 groups, gather time, drop-in object, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
     if args.stripe_rows > 0:
@@ -233,6 +244,37 @@ def oracle_build_flags(ge):
     return None
 
 
+DUMP_BYTES = 64 * 10**6
+
+
+def write_outputs(path, width, height, frame, film, counts):
+    """--dump-outputs: what the last timed step computed, as DIR/<name>.npy.
+      frame_rgb     [pixels, 3] float32  the packed 0xAARRGGBB pixels the caller receives, as R, G, B in 0..255 (alpha is always 255)
+      film_sum      [pixels, 3] float32  the film the step left: per-pixel radiance sums ...
+      film_samples  [pixels]    float32  ... and sample counts (rows another rank owns hold zeros)
+      ray_counts    [5]         float64  primary, bounce, shadow, primary_culled, shadow_skipped of one step
+    Pixels are in row-major order.  When the per-pixel arrays of the whole frame would exceed DUMP_BYTES, they hold a fixed
+    seeded sample of the pixels instead, listed (ascending) in pixel_index.npy (float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = width * height
+    frame = np.asarray(frame).view(np.uint32).reshape(n)
+    sums, _, samples = film
+    if n * 28 <= DUMP_BYTES:
+        idx = None
+        sel = slice(None)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES // 40, replace=False))       # 28 B per pixel + 8 B of index + headers
+        sel = idx
+    out = {"frame_rgb": np.stack([(frame[sel] >> s) & 0xFF for s in (16, 8, 0)], axis=1).astype(np.float32),
+           "film_sum": np.asarray(sums[sel], np.float32), "film_samples": samples[sel].astype(np.float32),
+           "ray_counts": np.asarray(counts, np.float64)}
+    if idx is not None:
+        out["pixel_index"] = idx.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 class Ctx:
     """what every result group needs: the package, the scene, the process group"""
@@ -326,9 +368,6 @@ class FrameSetup:
         if not same:
             raise SystemExit("bench: a queued frame traced other rays than the synchronous one: %s vs %s" % (c.as_dict(), ref.as_dict()))
         tot = [float(steps * c.primary), float(steps * c.bounce), float(steps * c.shadow), float(steps * c.primary_culled), float(steps * c.shadow_skipped)]
-        for _ in range(2):                                              # the gather timed on its own (render excluded)
-            self.step(time_gather=True)
-        self.sync()
         stats = torch.tensor([elapsed] + tot, dtype=torch.float64, device="cuda")
         dist = self.ctx.dist
         if dist is not None:
@@ -338,6 +377,25 @@ class FrameSetup:
         else:
             vals = [float(x) for x in stats[1:]]
         return elapsed, vals, step_ms
+
+    def time_gather(self):
+        """two more frames, the gather timed on its own (render excluded) -> gather_ms_rank0 of summary()"""
+        for _ in range(2):
+            self.step(time_gather=True)
+        self.sync()
+
+    def dump_outputs(self, path, vals, steps):
+        """--dump-outputs right after timed(): the frame the last timed step delivered and the film it left (rank 0)"""
+        import numpy as np
+        if self.native is not None:                                     # collective: the same film tonemapped and gathered once more
+            frame = np.zeros(self.width * self.height, np.uint32) if self.ctx.rank == 0 else None
+            self.rt.comm_gather_frame(0, frame)
+        else:
+            self.sync()
+            frame = self.fg.frame.cpu().numpy()
+        if self.ctx.rank == 0:
+            write_outputs(path, self.width, self.height, frame, self.rt.film.pixel_datas(), [v / steps for v in vals])
+        self.sync()
 
     def summary(self, workload, scaling, steps, warmup, elapsed, vals):
         primary, bounce, shadow, culled, skipped = vals
@@ -368,12 +426,13 @@ def workload_text(args, width, height, spp, base_spp, world, scaling, c5=False):
 
 
 def extra_group(ctx, name, sem_flag):
-    """the `strong` / `c5` result groups of the default run: the fixed frame dealt to the ranks, a few frames"""
+    """the `strong` / `c5` result groups of the --full run: the fixed frame dealt to the ranks, a few frames"""
     args = ctx.args
     width, height, spp = (3840, 2160, 256) if name == "c5" else (WIDTH, HEIGHT, SPP)
     steps, warmup = (3, 1) if name == "c5" else (min(args.steps, 5), 1)
     fs = FrameSetup(ctx, width, height, spp, sem_flag)
     elapsed, vals, _ = fs.timed(steps, warmup)
+    fs.time_gather()
     out = fs.summary(workload_text(args, width, height, spp, spp, ctx.world, "strong", c5=name == "c5"), "strong", steps, warmup, elapsed, vals)
     fs.close()
     return out
@@ -409,7 +468,7 @@ def main(argv=None):
 
     # counter passes first: this process has not initialised the GPU yet, so the children have the device to themselves
     pmc, pmc_gather, pmc_note = {}, {}, ("skipped (--no-pmc)" if args.no_pmc else "skipped (N > 1)")
-    if not args.no_pmc and world == 1:
+    if args.full and not args.no_pmc and world == 1:
         main_kernel = "fused_pass_kernel" if args.mode == "dropin" else "trace_kernel<false, false"
         both, pmc_note = run_pmc_passes(args, [main_kernel, "gather_rate_kernel"])
         pmc, pmc_gather = both.get(main_kernel, {}), both.get("gather_rate_kernel", {})
@@ -437,7 +496,7 @@ def main(argv=None):
     scene_io = importlib.import_module("raytracer_rs_amd.scene_io")
     scene = scene_io.load_scene_file(os.path.join(ge.SCENES, args.scene + ".scene"))
     if args.mode == "dropin":
-        out = dropin_measure(args, ge, pkg, scene, pmc, pmc_note, full=True)
+        out = dropin_measure(args, ge, pkg, scene, pmc, pmc_note, line=True)
         emit(out)
         return
 
@@ -452,47 +511,55 @@ def main(argv=None):
     fs = FrameSetup(ctx, width, height, spp, sem_flag)
     rt, base_flags = fs.rt, fs.base_flags
 
-    # instrumented frame (untimed): nodes visited / triangles tested per ray, useful-lane fractions of the two sections,
-    # and the clock the trace waves run at (s_memtime against s_memrealtime, stamped by the instrumented build only)
-    rt.set_flags(base_flags | pkg.FLAG_COUNT_STEPS)
-    rt.film.clear()
-    c = rt.render(max(1, min(4, spp)))
-    inst_rays = max(1, c.primary - c.primary_culled + c.bounce + c.shadow - c.shadow_skipped)       # traced rays
-    nodes_per_ray = c.nodes_visited / inst_rays
-    tris_per_ray = c.tris_tested / inst_rays
-    lane_inner = c.nodes_visited / (64.0 * c.inner_execs) if c.inner_execs else None
-    lane_leaf = c.tris_tested / (64.0 * c.leaf_execs) if c.leaf_execs else None
-    observed_mhz = c.shader_clock_mhz or None
-    rt.set_flags(base_flags)
+    if args.full:
+        # instrumented frame (untimed): nodes visited / triangles tested per ray, useful-lane fractions of the two sections,
+        # and the clock the trace waves run at (s_memtime against s_memrealtime, stamped by the instrumented build only)
+        rt.set_flags(base_flags | pkg.FLAG_COUNT_STEPS)
+        rt.film.clear()
+        c = rt.render(max(1, min(4, spp)))
+        inst_rays = max(1, c.primary - c.primary_culled + c.bounce + c.shadow - c.shadow_skipped)       # traced rays
+        nodes_per_ray = c.nodes_visited / inst_rays
+        tris_per_ray = c.tris_tested / inst_rays
+        lane_inner = c.nodes_visited / (64.0 * c.inner_execs) if c.inner_execs else None
+        lane_leaf = c.tris_tested / (64.0 * c.leaf_execs) if c.leaf_execs else None
+        observed_mhz = c.shader_clock_mhz or None
+        rt.set_flags(base_flags)
 
     elapsed, vals, step_ms = fs.timed(args.steps, args.warmup)
     primary, bounce, shadow, culled, skipped = vals
     total_rays = primary + bounce + shadow
 
-    # Kernel-timing loop for the roofline: the same frames again with ONE slice and HIP events around every
-    # trace launch (on the stream it is launched on).  The frames above run several slices concurrently:
-    # their kernels share the chip and have no individual duration, so the per-launch time is taken here.
-    rt.set_slices(1)
-    rt.set_flags(base_flags | pkg.FLAG_TIME_KERNELS)
-    fs.step()
-    ksteps = max(1, min(args.steps, 3))
-    fs.sync()
-    t1 = time.perf_counter()
-    k = dict(rays=0, sec_rays=0, trace_ms=0.0, sec_ms=0.0, launches=0, sec_launches=0)
-    for _ in range(ksteps):
-        c = fs.step()
-        k["rays"] += c.primary - c.primary_culled + c.bounce + c.shadow - c.shadow_skipped; k["sec_rays"] += c.bounce + c.shadow - c.shadow_skipped      # rays the launches actually trace
-        k["trace_ms"] += c.trace_ms; k["sec_ms"] += c.trace_secondary_ms
-        k["launches"] += c.trace_launches; k["sec_launches"] += c.trace_secondary_launches
-    fs.sync()
-    serial_ms_per_step = (time.perf_counter() - t1) / ksteps * 1e3
-    rt.set_flags(base_flags)
-    gather = None
-    if rank == 0:
-        try:
-            gather = rt.debug_gather_rate(48000, 2000)              # 1.5 MB table: L2-resident like the scene
-        except Exception as e:                                      # noqa: BLE001 — the line then carries a null peak
-            gather = None
+    if args.dump_outputs:
+        fs.dump_outputs(args.dump_outputs, vals, args.steps)
+
+    if args.full:
+        fs.time_gather()
+
+        # Kernel-timing loop for the roofline: the same frames again with ONE slice and HIP events around every
+        # trace launch (on the stream it is launched on).  The frames above run several slices concurrently:
+        # their kernels share the chip and have no individual duration, so the per-launch time is taken here.
+        rt.set_slices(1)
+        rt.set_flags(base_flags | pkg.FLAG_TIME_KERNELS)
+        fs.step()
+        ksteps = max(1, min(args.steps, 3))
+        fs.sync()
+        t1 = time.perf_counter()
+        k = dict(rays=0, sec_rays=0, trace_ms=0.0, sec_ms=0.0, launches=0, sec_launches=0)
+        for _ in range(ksteps):
+            c = fs.step()
+            k["rays"] += c.primary - c.primary_culled + c.bounce + c.shadow - c.shadow_skipped; k["sec_rays"] += c.bounce + c.shadow - c.shadow_skipped      # rays the launches actually trace
+            k["trace_ms"] += c.trace_ms; k["sec_ms"] += c.trace_secondary_ms
+            k["launches"] += c.trace_launches; k["sec_launches"] += c.trace_secondary_launches
+        fs.sync()
+        serial_ms_per_step = (time.perf_counter() - t1) / ksteps * 1e3
+        rt.set_flags(base_flags)
+        gather = None
+        if rank == 0:
+            try:
+                gather = rt.debug_gather_rate(48000, 2000)              # 1.5 MB table: L2-resident like the scene
+            except Exception as e:                                      # noqa: BLE001 — the line then carries a null peak
+                gather = None
+
     main_group = fs.summary(workload_text(args, width, height, spp, base_spp, world, args.scaling, c5=args.config == "c5"), args.scaling, args.steps, args.warmup, elapsed, vals)
     acc = rt.accel_stats()
     build_info = rt.bvh_build_info()
@@ -501,7 +568,7 @@ def main(argv=None):
 
     # the other intersector semantics on the same frame (short: 1 warm + 3 timed frames), for the record in the line
     other = None
-    if world == 1:
+    if args.full and world == 1:
         oflag = (0 if args.true_closest_hit else pkg.FLAG_TRUE_CLOSEST_HIT) | (pkg.FLAG_DEVICE_LBVH if args.device_lbvh else 0)
         rt2 = pkg.create_raytracer_from_arrays(scene, pkg.DEFAULT_TRIANGLES_PER_LEAF, width, height, seed=1, device=local_rank, stripe_rows=STRIPE_ROWS, flags=oflag)
         rt2.set_flags(oflag | (pkg.FLAG_FIX_ROW_INDEX if args.fix_row_index else 0))
@@ -516,13 +583,13 @@ def main(argv=None):
                  "ms_per_step": round(dt2 / 3 * 1e3, 3), "mrays_per_s": round(r2 / dt2 / 1e6, 2)}
         del rt2
 
-    # the other two result groups of the default run (collective: every rank takes part)
+    # the other two result groups of the --full run (collective: every rank takes part)
     groups = {}
-    if args.scaling == "weak" and args.config == "c4" and not args.no_groups and not args.spp:
+    if args.full and args.scaling == "weak" and args.config == "c4" and not args.no_groups and not args.spp:
         for name in ("strong", "c5"):
             groups[name] = extra_group(ctx, name, sem_flag)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         node_bytes = acc["node_bytes"] / max(acc["nodes"], 1)
         bytes_per_ray = node_bytes * nodes_per_ray + 48.0 * tris_per_ray + 96.0
         prim_launches = k["launches"] - k["sec_launches"]
@@ -603,6 +670,7 @@ def main(argv=None):
             roof["hbm"] = {"bytes_per_launch": round(per_launch, 1), "bytes_per_secondary_ray": round(per_ray, 2), "gbs": round(per_launch / sec_launch_s / 1e9, 1) if sec_launch_s > 0 else None,
                            "frac_of_hbm_peak": round(per_launch / sec_launch_s / 1e9 / HBM_PEAK_GBS, 4) if sec_launch_s > 0 else None,
                            "formula": "(2 x FETCH_SIZE + WRITE_SIZE) x 1024 / secondary rays of the child's frames x secondary rays per launch"}
+    if rank == 0:
         out = {
             "metric": "Mrays/s (whole node) + ms/frame, 1920x1080x64spp thai2.dae",
             "value": main_group["value"],
@@ -625,16 +693,16 @@ def main(argv=None):
                            "the primary samples of chunks the culling skipped without tracing (%.1f %% of the primary samples) and the shadow rays the lights' depth maps proved "
                            "free (%.1f %% of the shadow rays): work whose outcome was known" % (100.0 * culled / max(primary, 1), 100.0 * skipped / max(shadow, 1)),
             "rays_per_frame": {"primary": primary / args.steps, "bounce": bounce / args.steps, "shadow": shadow / args.steps, "primary_culled": culled / args.steps, "shadow_skipped": skipped / args.steps},
-            "other_semantics": other,
-            "roofline": roof,
             "accel": dict(acc, builder=("device LBVH (MI355RT_FLAG_DEVICE_LBVH)" if build_info["on_device"] else "host binned SAH"),
                           device_build_ms=build_info["device_ms"]),
         }
+        if args.full:
+            out.update(other_semantics=other, roofline=roof)
         out.update(groups)
-        if world == 1 and not args.no_dropin and args.scaling == "weak" and args.config == "c4":
-            d = dropin_measure(args, ge, pkg, scene, {}, "not collected in frame mode", full=False)
+        if args.full and world == 1 and not args.no_dropin and args.scaling == "weak" and args.config == "c4":
+            d = dropin_measure(args, ge, pkg, scene, {}, "not collected in frame mode", line=False)
             out["dropin"] = d
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(ge, scene, width, height, args.fix_row_index)
         emit(out)
     if dist is not None:
@@ -643,14 +711,15 @@ def main(argv=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-def dropin_measure(args, ge, pkg, scene, pmc, pmc_note, full):
+def dropin_measure(args, ge, pkg, scene, pmc, pmc_note, line):
     """The reference binary's loop (main.rs:197-207) at its defaults: thai2, 1024x768; one step = trace_frame_additive()
     (50 rows x 1 sample = 51 200 primary rays) + get_tonemapped_pixels() (a fresh copy of the whole frame in host memory).
-    full: the whole --mode dropin line (args.steps steps); else the short `dropin` object of the frame-mode line."""
+    line: the --mode dropin line (args.steps steps; without --full the timed loop only); else the short `dropin` object of
+    the frame-mode --full line."""
     import numpy as np
     import torch
     w, h = 1024, 768
-    steps, warmup = (args.steps, args.warmup) if full else (500, 50)
+    steps, warmup = (args.steps, args.warmup) if line else (500, 50)
     extra = {"stripe_rows": args.stripe_rows} if args.stripe_rows > 0 else {}
     rt = pkg.create_raytracer_from_arrays(scene, pkg.DEFAULT_TRIANGLES_PER_LEAF, w, h, seed=1, **extra)
     buf = np.empty(w * h, np.uint32)
@@ -669,6 +738,22 @@ def dropin_measure(args, ge, pkg, scene, pmc, pmc_note, full):
         primary += step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if line:
+        out = {
+            "metric": "primary rays/s of the reference binary's loop: trace_frame_additive() + get_tonemapped_pixels(), thai2 1024x768 (main.rs:13-15,197-207)",
+            "value": round(primary / elapsed, 1), "unit": "primary rays/s",
+            "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "%s 1024x768, 50 rows x 1 sample per call (51 200 primary rays), whole-frame u32 read-out into host memory per call" % args.scene,
+                       "scene": args.scene, "width": w, "height": h, "seed": 1},
+            "fps": round(steps / elapsed, 1),
+            "hbm_allocated_bytes": rt.hbm_allocated_bytes(),
+        }
+        if args.dump_outputs:
+            c = rt.last_counts()
+            write_outputs(args.dump_outputs, w, h, buf, rt.film.pixel_datas(), [c.primary, c.bounce, c.shadow, c.primary_culled, c.shadow_skipped])
+        if not args.full:
+            return out
     # the two halves on their own
     t1 = time.perf_counter()
     for _ in range(steps):
@@ -693,7 +778,7 @@ def dropin_measure(args, ge, pkg, scene, pmc, pmc_note, full):
         O = ge.load_oracle()
         orc = O.Oracle(scene, w, h, seed=1)                              # the reference's default intersector (octree, 70 per leaf)
         t = time.perf_counter(); calls = 0; prim = 0
-        budget, cap = (12.0, 400) if full else (4.0, 30)
+        budget, cap = (12.0, 400) if line else (4.0, 30)
         while time.perf_counter() - t < budget and calls < cap:
             prim += orc.trace_frame_additive(); orc.get_tonemapped_pixels(); calls += 1
         dt = time.perf_counter() - t
@@ -702,7 +787,7 @@ def dropin_measure(args, ge, pkg, scene, pmc, pmc_note, full):
                "sample": "%d calls of oracle_trace_frame_additive + oracle_get_tonemapped on 1 thread (%.1f s): the reference's loop is serial "
                          "(mod.rs:80-117); octree oracle at 70 triangles per leaf" % (calls, dt),
                "ms_per_step": round(dt / calls * 1e3, 2), "cpu_model": model, "physical_cores": phys, "build_flags": oracle_build_flags(ge)}
-    if not full:
+    if not line:
         return {"what": "the loop the reference binary runs (raytracer/src/main.rs:197-207) at its defaults: thai2 1024x768; one step = trace_frame_additive() "
                         "(50 rows x 1 sample = 51 200 primary rays, ONE launch of fused_pass_kernel) + get_tonemapped_pixels() (whole frame as u32 in host memory)",
                 "steps": steps, "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 4), "primary_rays_per_s": round(primary / elapsed, 1),
@@ -737,20 +822,13 @@ def dropin_measure(args, ge, pkg, scene, pmc, pmc_note, full):
         roof["traffic"] = round((2.0 * f / max(nf, 1) + wv / max(nw, 1)) * 1024.0, 1)
     if "SQ_INSTS_VALU" in pmc:
         roof["pmc"]["valu_winst_per_launch"] = round(pmc["SQ_INSTS_VALU"][0] / max(pmc["SQ_INSTS_VALU"][1], 1), 1)
-    out = {
-        "metric": "primary rays/s of the reference binary's loop: trace_frame_additive() + get_tonemapped_pixels(), thai2 1024x768 (main.rs:13-15,197-207)",
-        "value": round(primary / elapsed, 1), "unit": "primary rays/s",
-        "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "%s 1024x768, 50 rows x 1 sample per call (51 200 primary rays), whole-frame u32 read-out into host memory per call" % args.scene,
-                   "scene": args.scene, "width": w, "height": h, "seed": 1},
-        "fps": round(steps / elapsed, 1),
+    out.update({
         "ms_trace_frame_additive_only": round(trace_only * 1e3, 4), "ms_get_tonemapped_pixels_clean": round(copy_only * 1e3, 4),
         "ms_per_step_wavefront_rounds": round(wavefront_ms, 4),
         "total_mrays_per_s": round(rays / kcalls / (elapsed / steps) / 1e6, 2),
         "hbm_allocated_bytes": rt.hbm_allocated_bytes(),
         "roofline": roof,
-    }
+    })
     if cpu is not None:
         out["cpu_baseline"] = cpu
     return out

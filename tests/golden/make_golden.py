@@ -2,8 +2,8 @@
 """Regenerates the committed fixtures under tests/golden/.
 
   scenes/*.scene   flat scene containers made by the product's COLLADA ingest
-                   (raytracer-rs_amd/bin/dae2scene) from the reference's bundled data files
-                   /root/reference/data/*.dae (+ blender_cycles_ico3.png).  Data only: triangle
+                   (raytracer-rs_amd/bin/dae2scene) from the reference's bundled data files, stored
+                   here as collada/*.dae.xz (+ blender_cycles_ico3.png).  Data only: triangle
                    soup, materials, light, camera matrix, texture bytes.
   render_*.npz     outputs of the CPU oracle (oracle/oracle.c — our C restatement; NOT of the Rust
                    reference, which cannot be built here): 64x64, 4 spp, seed 1, for the octree
@@ -13,9 +13,12 @@
 
 Run from the repo root in the build container:  python tests/golden/make_golden.py
 """
+import lzma
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
@@ -23,7 +26,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
-REF_DATA = "/root/reference/data"
 HERE = os.path.dirname(os.path.abspath(__file__))
 SCENES = ["4boxes", "ico2", "thai2", "ico3_tex"]
 
@@ -31,11 +33,14 @@ SCENES = ["4boxes", "ico2", "thai2", "ico3_tex"]
 def main():
     ge.build()
     tool = os.path.join(ge.PKG_DIR, "bin", "dae2scene")
-    if os.path.isdir(REF_DATA):
+    collada = os.path.join(HERE, "collada")
+    with tempfile.TemporaryDirectory() as tmp:
+        shutil.copy(os.path.join(collada, "blender_cycles_ico3.png"), tmp)
         for s in SCENES:
-            subprocess.check_call([tool, os.path.join(REF_DATA, s + ".dae"), os.path.join(HERE, "scenes", s + ".scene")])
-    else:
-        print("no %s: keeping the committed scene files" % REF_DATA)
+            dae = os.path.join(tmp, s + ".dae")
+            with lzma.open(os.path.join(collada, s + ".dae.xz")) as f, open(dae, "wb") as g:
+                g.write(f.read())
+            subprocess.check_call([tool, dae, os.path.join(HERE, "scenes", s + ".scene")])
     pkg = ge.load_package()
     import importlib
     sio = importlib.import_module("raytracer_rs_amd.scene_io")

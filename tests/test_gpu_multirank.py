@@ -77,7 +77,7 @@ def _bench(argv, env_extra=None, timeout=600):
 def test_bench_self_launch_with_one_rank():
     """`bench.py --gpus 1 --spawn`: the parent starts torch.distributed.run, which starts the one rank; the line carries the
     three result groups (weak = the line itself, `strong`, `c5`), each with its gather fields, and the drop-in object."""
-    d = _bench(["--gpus", "1", "--spawn", "--steps", "2", "--warmup", "1", "--no-pmc", "--no-cpu-baseline"])
+    d = _bench(["--gpus", "1", "--spawn", "--steps", "2", "--warmup", "1", "--full", "--no-pmc", "--no-cpu-baseline"])
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["scaling"] == "weak" and d["unit"] == "Mrays/s"
     assert d["gather_path"] == "none" and d["rccl_ranks"] == 0 and d["gather_error"] is None
     assert d["hbm_allocated_bytes"] > 0 and d["ms_per_step"] > 0
@@ -94,10 +94,35 @@ def test_bench_two_ranks_share_the_gpu_and_report_the_fallback():
     """N = 2 rehearsal on the one GPU of the box (gloo, MI355RT_BENCH_SHARE_GPU): the library's RCCL path is asked for, RCCL
     refuses two ranks on one device, every rank agrees on that, and the line SAYS so: gather_path torch_all_gather with a
     non-null gather_error — in every result group."""
-    d = _bench(["--gpus", "2", "--steps", "1", "--warmup", "1", "--no-pmc", "--no-cpu-baseline", "--spp", "2"], {"MI355RT_BENCH_SHARE_GPU": "1"})
+    d = _bench(["--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--no-pmc", "--no-cpu-baseline", "--spp", "2"], {"MI355RT_BENCH_SHARE_GPU": "1"})
     assert d["n_gpus"] == 2 and d["gather_path"] in ("torch_all_gather", "library_rccl")
     if d["gather_path"] == "torch_all_gather":
         assert d["gather_error"] and d["rccl_ranks"] == 0
     else:
         assert d["gather_error"] is None and d["rccl_ranks"] == 2
     assert d["gather_ms_rank0"] is not None
+
+
+def test_bench_plain_run_carries_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line is the headline only; --dump-outputs writes the last timed step's frame, film and ray
+    counters as float32 / float64 arrays, within 64 MB — in frame mode and in --mode dropin."""
+    d = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--spp", "4", "--dump-outputs", str(tmp_path / "frame")])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "Mrays/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["gather_ms_rank0"] is None
+    for k in ("roofline", "other_semantics", "strong", "c5", "dropin", "cpu_baseline"):
+        assert k not in d, k
+    out = {f[:-4]: np.load(tmp_path / "frame" / f) for f in os.listdir(tmp_path / "frame")}
+    assert sorted(out) == ["film_samples", "film_sum", "frame_rgb", "ray_counts"]
+    assert sum(os.path.getsize(tmp_path / "frame" / (k + ".npy")) for k in out) <= 64 * 10**6
+    n = 1920 * 1080
+    assert out["frame_rgb"].shape == (n, 3) and out["frame_rgb"].dtype == np.float32 and out["film_sum"].shape == (n, 3)
+    assert out["frame_rgb"].max() <= 255 and out["frame_rgb"].max() > 0 and np.array_equal(out["frame_rgb"], np.round(out["frame_rgb"]))
+    assert (out["film_samples"] == 4).all()                                  # film cleared every step: one frame of 4 spp
+    rc = out["ray_counts"]
+    assert rc.dtype == np.float64 and rc[0] == n * 4 == d["rays_per_frame"]["primary"] and rc[1] == d["rays_per_frame"]["bounce"]
+    d = _bench(["--gpus", "1", "--mode", "dropin", "--steps", "20", "--warmup", "2", "--dump-outputs", str(tmp_path / "dropin")])
+    assert d["steps"] == 20 and d["ms_per_step"] > 0 and d["unit"] == "primary rays/s" and "roofline" not in d and "cpu_baseline" not in d
+    frame = np.load(tmp_path / "dropin" / "frame_rgb.npy")
+    samples = np.load(tmp_path / "dropin" / "film_samples.npy")
+    assert frame.shape == (1024 * 768, 3) and samples.sum() == 22 * 50 * 1024   # 22 calls of 50 rows x 1 sample
+    assert np.load(tmp_path / "dropin" / "ray_counts.npy")[0] == 50 * 1024

@@ -5,7 +5,7 @@ out=gpurun_out/${1:-overlap}; mkdir -p $out
 cd $GRAFT_REPO_ROOT
 run() {  # label, env...
   local label=$1; shift
-  env "$@" timeout -k 10 200 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-pmc --slices $sl > $out/b_${sl}_${label}.json 2>> $out/err.txt || { echo "failed $sl $label"; exit 1; }
+  env "$@" timeout -k 10 200 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-pmc --slices $sl > $out/b_${sl}_${label}.json 2>> $out/err.txt || { echo "failed $sl $label"; exit 1; }
   python3 -c "
 import json; d=json.load(open('$out/b_${sl}_${label}.json')); print('slices $sl $label: frame', d['ms_per_step'], 'ms | tch', d['other_semantics']['ms_per_step'])"
 }

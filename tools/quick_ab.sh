@@ -11,9 +11,9 @@ for r in csv.DictReader(open(f)):
     if float(r["Percentage"]) > 0.4:
         print("%-58s calls %4s avg %8.1f us  %5.1f%%" % (r["Name"].replace("mi355rt::", "")[:58], r["Calls"], float(r["AverageNs"]) / 1e3, float(r["Percentage"])))
 PY
-timeout -k 10 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-pmc > $out/bench.json 2>> $out/err.txt
+timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-pmc > $out/bench.json 2>> $out/err.txt
 python3 -c "
 import json; d=json.load(open('$out/bench.json')); print('frame', d['ms_per_step'], 'ms', d['value'], 'Mrays/s | other', d['other_semantics'])"
-timeout -k 10 200 python bench.py --mode dropin --no-cpu-baseline --no-pmc > $out/dropin.json 2>> $out/err.txt
+timeout -k 10 200 python bench.py --full --mode dropin --no-cpu-baseline --no-pmc > $out/dropin.json 2>> $out/err.txt
 python3 -c "
 import json; d=json.load(open('$out/dropin.json')); print('dropin', d['ms_per_step'], 'ms/step kernel', d['roofline']['avg_launch_ms'])"
