@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 #include "bvh.hpp"
+#include "device_buffer.hpp"
 
 namespace mi355rt {
 namespace {
@@ -178,13 +179,6 @@ __global__ __launch_bounds__(kLbvhBlock) void lbvh_emit_tris_kernel(int n, const
     tris[j] = r;
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16) == hipSuccess; }
-    template <class T> T* as() const { return (T*)p; }
-};
-
 }  // namespace
 
 // Builds `out` on the current device.  Returns false (with `why`) when the device path cannot serve the scene — fewer
@@ -211,32 +205,33 @@ bool build_bvh_device(const float* tri_verts, const uint32_t* tri_geom, uint32_t
 
     const int n = (int)ntri, n_inner = n - 1;
     const unsigned grid_n = (unsigned)((n + kLbvhBlock - 1) / kLbvhBlock), grid_i = (unsigned)((n_inner + kLbvhBlock - 1) / kLbvhBlock);
-    DevBuf d_verts, d_geom, d_boxes, d_keys0, d_keys1, d_vals0, d_order, d_child, d_range, d_pin, d_pleaf, d_lboxes, d_nboxes, d_height, d_flags, d_survive, d_newidx, d_nodes, d_tris, d_tmp;
-    if (!d_verts.alloc((size_t)n * 36) || !d_geom.alloc((size_t)n * 4) || !d_boxes.alloc((size_t)n * sizeof(Box6)) || !d_keys0.alloc((size_t)n * 8) || !d_keys1.alloc((size_t)n * 8)
-        || !d_vals0.alloc((size_t)n * 4) || !d_order.alloc((size_t)n * 4) || !d_child.alloc((size_t)n_inner * 8) || !d_range.alloc((size_t)n_inner * 8) || !d_pin.alloc((size_t)n_inner * 4)
-        || !d_pleaf.alloc((size_t)n * 4) || !d_lboxes.alloc((size_t)n * sizeof(Box6)) || !d_nboxes.alloc((size_t)n_inner * sizeof(Box6)) || !d_height.alloc((size_t)n_inner * 4)
-        || !d_flags.alloc((size_t)n_inner * 4) || !d_survive.alloc((size_t)n_inner * 4) || !d_newidx.alloc((size_t)n_inner * 4) || !d_nodes.alloc((size_t)n_inner * sizeof(BvhNode))
-        || !d_tris.alloc((size_t)n * sizeof(BvhTri))) { why = "hipMalloc failed"; (void)hipGetLastError(); return false; }
+    DeviceBuffer<float> d_verts; DeviceBuffer<uint32_t> d_geom, d_vals0, d_order, d_pin, d_pleaf, d_height, d_flags, d_survive, d_newidx; DeviceBuffer<unsigned long long> d_keys0, d_keys1;
+    DeviceBuffer<Box6> d_boxes, d_lboxes, d_nboxes; DeviceBuffer<uint2> d_child, d_range; DeviceBuffer<BvhNode> d_nodes; DeviceBuffer<BvhTri> d_tris; DeviceBuffer<> d_tmp;   // n > kBvhMaxLeaf: none is empty
+    if (d_verts.alloc((size_t)n * 36) != hipSuccess || d_geom.alloc((size_t)n * 4) != hipSuccess || d_boxes.alloc((size_t)n * sizeof(Box6)) != hipSuccess || d_keys0.alloc((size_t)n * 8) != hipSuccess
+        || d_keys1.alloc((size_t)n * 8) != hipSuccess || d_vals0.alloc((size_t)n * 4) != hipSuccess || d_order.alloc((size_t)n * 4) != hipSuccess || d_child.alloc((size_t)n_inner * 8) != hipSuccess
+        || d_range.alloc((size_t)n_inner * 8) != hipSuccess || d_pin.alloc((size_t)n_inner * 4) != hipSuccess || d_pleaf.alloc((size_t)n * 4) != hipSuccess || d_lboxes.alloc((size_t)n * sizeof(Box6)) != hipSuccess
+        || d_nboxes.alloc((size_t)n_inner * sizeof(Box6)) != hipSuccess || d_height.alloc((size_t)n_inner * 4) != hipSuccess || d_flags.alloc((size_t)n_inner * 4) != hipSuccess || d_survive.alloc((size_t)n_inner * 4) != hipSuccess
+        || d_newidx.alloc((size_t)n_inner * 4) != hipSuccess || d_nodes.alloc((size_t)n_inner * sizeof(BvhNode)) != hipSuccess || d_tris.alloc((size_t)n * sizeof(BvhTri)) != hipSuccess) { why = "device allocation failed"; (void)hipGetLastError(); return false; }
     size_t sort_bytes = 0, scan_bytes = 0;
-    if (rocprim::radix_sort_pairs(nullptr, sort_bytes, d_keys0.as<unsigned long long>(), d_keys1.as<unsigned long long>(), d_vals0.as<uint32_t>(), d_order.as<uint32_t>(), (size_t)n, 0, 63, 0) != hipSuccess
-        || rocprim::exclusive_scan(nullptr, scan_bytes, d_survive.as<uint32_t>(), d_newidx.as<uint32_t>(), 0u, (size_t)n_inner, rocprim::plus<uint32_t>(), 0) != hipSuccess
-        || !d_tmp.alloc(std::max(sort_bytes, scan_bytes))) { why = "rocprim temporary storage"; (void)hipGetLastError(); return false; }
+    if (rocprim::radix_sort_pairs(nullptr, sort_bytes, d_keys0.get(), d_keys1.get(), d_vals0.get(), d_order.get(), (size_t)n, 0, 63, 0) != hipSuccess
+        || rocprim::exclusive_scan(nullptr, scan_bytes, d_survive.get(), d_newidx.get(), 0u, (size_t)n_inner, rocprim::plus<uint32_t>(), 0) != hipSuccess
+        || d_tmp.alloc(std::max<size_t>({ sort_bytes, scan_bytes, 16 })) != hipSuccess) { why = "rocprim temporary storage"; (void)hipGetLastError(); return false; }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { why = "hipEventCreate failed"; return false; }
     auto fail = [&](const char* what) { why = std::string(what) + ": " + hipGetErrorString(hipGetLastError()); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return false; };
-    if (hipMemcpy(d_verts.p, tri_verts, (size_t)n * 36, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_geom.p, tri_geom, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("upload");
+    if (hipMemcpy(d_verts.get(), tri_verts, (size_t)n * 36, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_geom.get(), tri_geom, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("upload");
     (void)hipEventRecord(e0, 0);
-    hipLaunchKernelGGL(lbvh_prim_kernel, dim3(grid_n), dim3(kLbvhBlock), 0, 0, d_verts.as<float>(), (uint32_t)n, dmin, dinv, d_boxes.as<Box6>(), d_keys0.as<unsigned long long>(), d_vals0.as<uint32_t>());
-    if (rocprim::radix_sort_pairs(d_tmp.p, sort_bytes, d_keys0.as<unsigned long long>(), d_keys1.as<unsigned long long>(), d_vals0.as<uint32_t>(), d_order.as<uint32_t>(), (size_t)n, 0, 63, 0) != hipSuccess) return fail("radix sort");
-    hipLaunchKernelGGL(lbvh_hierarchy_kernel, dim3(grid_i), dim3(kLbvhBlock), 0, 0, d_keys1.as<unsigned long long>(), n, d_child.as<uint2>(), d_range.as<uint2>(), d_pin.as<uint32_t>(), d_pleaf.as<uint32_t>());
-    (void)hipMemsetAsync(d_flags.p, 0, (size_t)n_inner * 4, 0);
-    hipLaunchKernelGGL(lbvh_refit_kernel, dim3(grid_n), dim3(kLbvhBlock), 0, 0, n, max_leaf, d_order.as<uint32_t>(), d_boxes.as<Box6>(), d_child.as<uint2>(), d_range.as<uint2>(),
-                       d_pin.as<uint32_t>(), d_pleaf.as<uint32_t>(), d_lboxes.as<Box6>(), d_nboxes.as<Box6>(), d_height.as<uint32_t>(), d_flags.as<uint32_t>());
-    hipLaunchKernelGGL(lbvh_survive_kernel, dim3(grid_i), dim3(kLbvhBlock), 0, 0, n_inner, max_leaf, d_range.as<uint2>(), d_survive.as<uint32_t>());
-    if (rocprim::exclusive_scan(d_tmp.p, scan_bytes, d_survive.as<uint32_t>(), d_newidx.as<uint32_t>(), 0u, (size_t)n_inner, rocprim::plus<uint32_t>(), 0) != hipSuccess) return fail("scan");
-    hipLaunchKernelGGL(lbvh_emit_nodes_kernel, dim3(grid_i), dim3(kLbvhBlock), 0, 0, n_inner, pad, d_child.as<uint2>(), d_range.as<uint2>(), d_survive.as<uint32_t>(), d_newidx.as<uint32_t>(),
-                       d_lboxes.as<Box6>(), d_nboxes.as<Box6>(), d_nodes.as<BvhNode>());
-    hipLaunchKernelGGL(lbvh_emit_tris_kernel, dim3(grid_n), dim3(kLbvhBlock), 0, 0, n, d_order.as<uint32_t>(), d_verts.as<float>(), d_geom.as<uint32_t>(), d_tris.as<BvhTri>());
+    hipLaunchKernelGGL(lbvh_prim_kernel, dim3(grid_n), dim3(kLbvhBlock), 0, 0, d_verts.get(), (uint32_t)n, dmin, dinv, d_boxes.get(), d_keys0.get(), d_vals0.get());
+    if (rocprim::radix_sort_pairs(d_tmp.get(), sort_bytes, d_keys0.get(), d_keys1.get(), d_vals0.get(), d_order.get(), (size_t)n, 0, 63, 0) != hipSuccess) return fail("radix sort");
+    hipLaunchKernelGGL(lbvh_hierarchy_kernel, dim3(grid_i), dim3(kLbvhBlock), 0, 0, d_keys1.get(), n, d_child.get(), d_range.get(), d_pin.get(), d_pleaf.get());
+    (void)hipMemsetAsync(d_flags.get(), 0, (size_t)n_inner * 4, 0);
+    hipLaunchKernelGGL(lbvh_refit_kernel, dim3(grid_n), dim3(kLbvhBlock), 0, 0, n, max_leaf, d_order.get(), d_boxes.get(), d_child.get(), d_range.get(),
+                       d_pin.get(), d_pleaf.get(), d_lboxes.get(), d_nboxes.get(), d_height.get(), d_flags.get());
+    hipLaunchKernelGGL(lbvh_survive_kernel, dim3(grid_i), dim3(kLbvhBlock), 0, 0, n_inner, max_leaf, d_range.get(), d_survive.get());
+    if (rocprim::exclusive_scan(d_tmp.get(), scan_bytes, d_survive.get(), d_newidx.get(), 0u, (size_t)n_inner, rocprim::plus<uint32_t>(), 0) != hipSuccess) return fail("scan");
+    hipLaunchKernelGGL(lbvh_emit_nodes_kernel, dim3(grid_i), dim3(kLbvhBlock), 0, 0, n_inner, pad, d_child.get(), d_range.get(), d_survive.get(), d_newidx.get(),
+                       d_lboxes.get(), d_nboxes.get(), d_nodes.get());
+    hipLaunchKernelGGL(lbvh_emit_tris_kernel, dim3(grid_n), dim3(kLbvhBlock), 0, 0, n, d_order.get(), d_verts.get(), d_geom.get(), d_tris.get());
     (void)hipEventRecord(e1, 0);
     if (hipEventSynchronize(e1) != hipSuccess || hipGetLastError() != hipSuccess) return fail("build kernels");
     float dev_ms = 0.0f;
@@ -245,14 +240,14 @@ bool build_bvh_device(const float* tri_verts, const uint32_t* tri_geom, uint32_t
     // read back: how many nodes survived, the root's height, then the arrays (the renderer keeps a host copy for the culling
     // boxes and the statistics, like the host build's)
     uint32_t last_idx = 0, last_flag = 0, root_height = 0;
-    if (hipMemcpy(&last_idx, d_newidx.as<uint32_t>() + (n_inner - 1), 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&last_flag, d_survive.as<uint32_t>() + (n_inner - 1), 4, hipMemcpyDeviceToHost) != hipSuccess
-        || hipMemcpy(&root_height, d_height.p, 4, hipMemcpyDeviceToHost) != hipSuccess) { why = "read-back failed"; return false; }
+    if (hipMemcpy(&last_idx, d_newidx.get() + (n_inner - 1), 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&last_flag, d_survive.get() + (n_inner - 1), 4, hipMemcpyDeviceToHost) != hipSuccess
+        || hipMemcpy(&root_height, d_height.get(), 4, hipMemcpyDeviceToHost) != hipSuccess) { why = "read-back failed"; return false; }
     const uint32_t nnodes = last_idx + last_flag;
     if (root_height > kBvhMaxDepth) { why = "Morton-order tree deeper than the traversal stack (" + std::to_string(root_height) + " levels)"; return false; }
     if (nnodes == 0) { why = "internal: no surviving node"; return false; }
     out.nodes.resize(nnodes); out.tris.resize((size_t)n);
-    if (hipMemcpy(out.nodes.data(), d_nodes.p, (size_t)nnodes * sizeof(BvhNode), hipMemcpyDeviceToHost) != hipSuccess
-        || hipMemcpy(out.tris.data(), d_tris.p, (size_t)n * sizeof(BvhTri), hipMemcpyDeviceToHost) != hipSuccess) { why = "read-back failed"; return false; }
+    if (hipMemcpy(out.nodes.data(), d_nodes.get(), (size_t)nnodes * sizeof(BvhNode), hipMemcpyDeviceToHost) != hipSuccess
+        || hipMemcpy(out.tris.data(), d_tris.get(), (size_t)n * sizeof(BvhTri), hipMemcpyDeviceToHost) != hipSuccess) { why = "read-back failed"; return false; }
     out.root = 0; out.max_depth = root_height;
     for (const BvhNode& nd : out.nodes)
         for (int32_t c : { nd.child0, nd.child1 })

@@ -38,15 +38,19 @@ bool Renderer::bind()
     return true;
 }
 
+template <class T> bool Renderer::upload(DeviceBuffer<T>& buf, const void* src, size_t bytes)
+{
+    HIP_TRY(buf.alloc(bytes ? bytes : 16, &hbm_bytes_));
+    if (bytes && src) HIP_TRY(hipMemcpy(buf.get(), src, bytes, hipMemcpyHostToDevice));
+    else if (bytes) HIP_TRY(hipMemset(buf.get(), 0, bytes));
+    return true;
+}
+
 template <class T> bool Renderer::upload(T*& dptr, const void* src, size_t bytes)
 {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, bytes ? bytes : 16));
-    allocs_.push_back(p);
-    alloc_bytes_ += bytes ? bytes : 16;
-    if (bytes && src) HIP_TRY(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
-    else if (bytes) HIP_TRY(hipMemset(p, 0, bytes));
-    dptr = static_cast<T*>(p);
+    scene_bufs_.emplace_back();
+    if (!upload(scene_bufs_.back(), src, bytes)) return false;
+    dptr = static_cast<T*>(scene_bufs_.back().get());
     return true;
 }
 
@@ -307,8 +311,8 @@ bool Renderer::init(const SceneData& scene, std::string& err, int& code)
     if (!upload(d_owned_rows_, owned_rows.data(), owned_rows.size() * 4)) return bail();
     if (!upload(d_tmp_rows_, nullptr, 64 * 4)) return bail();
     if (!upload(d_counters_, nullptr, sizeof(DCounters) * kShards)) return bail();
-    if (hipHostMalloc((void**)&h_counters_, sizeof(DCounters) * kShards, hipHostMallocDefault) != hipSuccess) { err = "hipHostMalloc failed"; return false; }
-    std::memset(h_counters_, 0, sizeof(DCounters) * kShards);
+    if (h_counters_.alloc(sizeof(DCounters) * kShards) != hipSuccess) { err = "pinned host allocation failed"; return false; }
+    std::memset(h_counters_.get(), 0, sizeof(DCounters) * kShards);
     slices_[0].stream = stream_;
     if (hipStreamCreateWithFlags(&trace_stream_, hipStreamNonBlocking) != hipSuccess) { err = "hipStreamCreate failed"; return false; }
     for (uint32_t i = 0; i < kMaxSlices; ++i) {
@@ -349,24 +353,17 @@ Renderer::~Renderer()
         if (slices_[i].ev_traced) (void)hipEventDestroy(slices_[i].ev_traced);
     }
     if (trace_stream_) { (void)hipStreamSynchronize(trace_stream_); (void)hipStreamDestroy(trace_stream_); }
-    for (void* p : allocs_) (void)hipFree(p);
-    if (d_tile_ofs_) (void)hipFree(d_tile_ofs_);
-    if (d_tile_entries_) (void)hipFree(d_tile_entries_);
-    if (h_ldr_) (void)hipHostFree(h_ldr_);
-    if (h_counters_) (void)hipHostFree(h_counters_);
     comm_destroy();
-    if (d_gather_) (void)hipFree(d_gather_);
     if (ev_tonemap_) (void)hipEventDestroy(ev_tonemap_);
     if (read_stream_) (void)hipStreamDestroy(read_stream_);
     if (ev_call_done_) (void)hipEventDestroy(ev_call_done_);
     if (ev_spec_done_) (void)hipEventDestroy(ev_spec_done_);
-    if (h_counters_spec_) (void)hipHostFree(h_counters_spec_);
     if (ev_gather_) (void)hipEventDestroy(ev_gather_);
-    free_pass_buffers();
     for (hipEvent_t e : ev_pool_) (void)hipEventDestroy(e);
     if (ev_begin_) (void)hipEventDestroy(ev_begin_);
     if (ev_end_) (void)hipEventDestroy(ev_end_);
     if (stream_) (void)hipStreamDestroy(stream_);
+    // the DeviceBuffer / PinnedBuffer members free their memory after this body: behind the synchronisations above
 }
 
 // The (padded, half-precision) boxes of the top BVH subtrees, at most kCullRects of them: the boxes the
@@ -455,7 +452,7 @@ bool Renderer::refresh_cull_mask(DCamera& c, const double inv[3][3], double pad,
     std::vector<float> key(c.rot, c.rot + 16);
     key.insert(key.end(), c.origin, c.origin + 3); key.push_back(c.max_x); key.push_back(c.max_y);
     if (key == mask_key_) {
-        if (mask_valid_) { c.cull_mask = d_cull_mask_; c.mask_x0 = mask_dom_[0]; c.mask_y0 = mask_dom_[1]; c.mask_inv_cx = mask_dom_[2]; c.mask_inv_cy = mask_dom_[3]; }
+        if (mask_valid_) { c.cull_mask = d_cull_mask_.get(); c.mask_x0 = mask_dom_[0]; c.mask_y0 = mask_dom_[1]; c.mask_inv_cx = mask_dom_[2]; c.mask_inv_cy = mask_dom_[3]; }
         return true;
     }
     // A 50-row frame of the drop-in loop (0.3 ms) is not worth a rebuild (1.5 ms) when the camera has just moved — the reference's loop moves it between
@@ -479,15 +476,15 @@ bool Renderer::refresh_cull_mask(DCamera& c, const double inv[3][3], double pad,
         for (long j = j0; j <= j1; ++j) for (long i = i0; i <= i1; ++i) bits[(size_t)j * wpr + (size_t)(i >> 5)] |= 1u << (i & 31);
     }
     if (!bind()) return false;
-    if (!d_cull_mask_) { if (hipMalloc((void**)&d_cull_mask_, bits.size() * 4) != hipSuccess) { d_cull_mask_ = nullptr; return true; } allocs_.push_back(d_cull_mask_); }
+    if (!d_cull_mask_ && d_cull_mask_.alloc(bits.size() * 4, &hbm_bytes_) != hipSuccess) return true;
     // kernels of earlier calls may still read the old mask: wait for them, then replace it (camera changes are rare and clear the film anyway, main.rs:116-169)
     (void)hipStreamSynchronize(stream_);
     if (trace_stream_) (void)hipStreamSynchronize(trace_stream_);
     for (Slice& sl : slices_) if (sl.stream) (void)hipStreamSynchronize(sl.stream);
-    if (hipMemcpy(d_cull_mask_, bits.data(), bits.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return true;
+    if (hipMemcpy(d_cull_mask_.get(), bits.data(), bits.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return true;
     mask_dom_[0] = (float)X0; mask_dom_[1] = (float)Y0; mask_dom_[2] = (float)icx; mask_dom_[3] = (float)icy;
     mask_valid_ = true;
-    c.cull_mask = d_cull_mask_; c.mask_x0 = mask_dom_[0]; c.mask_y0 = mask_dom_[1]; c.mask_inv_cx = mask_dom_[2]; c.mask_inv_cy = mask_dom_[3];
+    c.cull_mask = d_cull_mask_.get(); c.mask_x0 = mask_dom_[0]; c.mask_y0 = mask_dom_[1]; c.mask_inv_cx = mask_dom_[2]; c.mask_inv_cy = mask_dom_[3];
     if (getenv("MI355RT_DEBUG_CULL")) { size_t n = 0; for (uint32_t w : bits) n += (size_t)__builtin_popcount(w); fprintf(stderr, "[mi355rt] cull mask: %zu of %u cells set, domain x [%g, %g] y [%g, %g]\n", n, kCullGrid * kCullGrid, X0, X1, Y0, Y1); }
     return true;
 }
@@ -517,7 +514,7 @@ bool Renderer::refresh_tile_bins(DCamera& c, const double inv[3][3], double pad,
     key.insert(key.end(), c.origin, c.origin + 3); key.push_back(c.max_x); key.push_back(c.max_y);
     key.push_back((float)cols); key.push_back((float)rg); key.push_back(fix_row ? 1.0f : 0.0f);
     const uint32_t nblocks = W / cols, ngroups = (H + rg - 1) / rg;
-    auto publish = [&]() { c.tile_ofs = d_tile_ofs_; c.tile_entries = d_tile_entries_; c.tile_cols = cols; c.tile_rg = rg; c.tile_nblocks = nblocks; };
+    auto publish = [&]() { c.tile_ofs = d_tile_ofs_.get(); c.tile_entries = d_tile_entries_.get(); c.tile_cols = cols; c.tile_rg = rg; c.tile_nblocks = nblocks; };
     if (key == bins_key_) { if (bins_valid_) publish(); return true; }
     bins_key_ = key; bins_valid_ = false;
     const auto t_begin = std::chrono::steady_clock::now();
@@ -581,10 +578,10 @@ bool Renderer::refresh_tile_bins(DCamera& c, const double inv[3][3], double pad,
     (void)hipStreamSynchronize(stream_);
     if (trace_stream_) (void)hipStreamSynchronize(trace_stream_);
     for (Slice& sl : slices_) if (sl.stream) (void)hipStreamSynchronize(sl.stream);
-    if (ofs.size() > tile_ofs_cap_) { if (d_tile_ofs_) (void)hipFree(d_tile_ofs_); d_tile_ofs_ = nullptr; tile_ofs_cap_ = 0; if (hipMalloc((void**)&d_tile_ofs_, ofs.size() * sizeof(uint2)) != hipSuccess) { d_tile_ofs_ = nullptr; BINS_OUT(9); } tile_ofs_cap_ = ofs.size(); }
-    if (entries.size() > tile_entries_cap_) { if (d_tile_entries_) (void)hipFree(d_tile_entries_); d_tile_entries_ = nullptr; tile_entries_cap_ = 0; const size_t cap = entries.size() + entries.size() / 4; if (hipMalloc((void**)&d_tile_entries_, cap * sizeof(uint2)) != hipSuccess) { d_tile_entries_ = nullptr; BINS_OUT(10); } tile_entries_cap_ = cap; }
-    if (hipMemcpy(d_tile_ofs_, ofs.data(), ofs.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess) BINS_OUT(11);
-    if (hipMemcpy(d_tile_entries_, entries.data(), entries.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess) BINS_OUT(12);
+    if (ofs.size() * sizeof(uint2) > d_tile_ofs_.bytes() && d_tile_ofs_.alloc(ofs.size() * sizeof(uint2), &hbm_bytes_) != hipSuccess) BINS_OUT(9);
+    if (entries.size() * sizeof(uint2) > d_tile_entries_.bytes() && d_tile_entries_.alloc((entries.size() + entries.size() / 4) * sizeof(uint2), &hbm_bytes_) != hipSuccess) BINS_OUT(10);    // 1/4 slack
+    if (hipMemcpy(d_tile_ofs_.get(), ofs.data(), ofs.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess) BINS_OUT(11);
+    if (hipMemcpy(d_tile_entries_.get(), entries.data(), entries.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess) BINS_OUT(12);
     bins_valid_ = true; bins_entries_ = refs.size();
     bins_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     publish();
@@ -656,20 +653,7 @@ DCamera Renderer::device_camera(const DPass* layout, const std::vector<uint32_t>
 
 void Renderer::free_pass_buffers()
 {
-    for (Slice& sl : slices_) {
-        for (int i = 0; i < 2; ++i) {
-            if (sl.d_queue[i]) { (void)hipFree(sl.d_queue[i]); sl.d_queue[i] = nullptr; }
-            if (sl.d_chunk_counts[i]) { (void)hipFree(sl.d_chunk_counts[i]); sl.d_chunk_counts[i] = nullptr; }
-        }
-        if (sl.d_slot_L) { (void)hipFree(sl.d_slot_L); sl.d_slot_L = nullptr; }
-        if (sl.d_sample_slot) { (void)hipFree(sl.d_sample_slot); sl.d_sample_slot = nullptr; }
-        if (sl.d_live) { (void)hipFree(sl.d_live); sl.d_live = nullptr; }
-        if (sl.d_block_culled) { (void)hipFree(sl.d_block_culled); sl.d_block_culled = nullptr; sl.block_culled_cap = 0; sl.cull_key.clear(); }
-        if (sl.d_slot_ps) { (void)hipFree(sl.d_slot_ps); sl.d_slot_ps = nullptr; }
-        if (sl.d_hits) { (void)hipFree(sl.d_hits); sl.d_hits = nullptr; }
-        if (sl.d_hit_prim) { (void)hipFree(sl.d_hit_prim); sl.d_hit_prim = nullptr; }
-        sl.capacity = 0; sl.bytes = 0; sl.guards.clear();
-    }
+    for (Slice& sl : slices_) { sl.release_pass_buffers(); sl.d_block_culled.reset(); sl.cull_key.clear(); }
 }
 
 bool Renderer::ensure_pass_capacity(Slice& sl, size_t nsamples)
@@ -677,13 +661,7 @@ bool Renderer::ensure_pass_capacity(Slice& sl, size_t nsamples)
     alloc_failed_ = false;
     if (nsamples <= sl.capacity) return true;
     for (Slice& o : slices_) if (o.stream) HIP_TRY(hipStreamSynchronize(o.stream));
-    if (sl.capacity) {          // grow: release this slice's buffers only
-        for (int i = 0; i < 2; ++i) { (void)hipFree(sl.d_queue[i]); sl.d_queue[i] = nullptr; (void)hipFree(sl.d_chunk_counts[i]); sl.d_chunk_counts[i] = nullptr; }
-        (void)hipFree(sl.d_slot_L); sl.d_slot_L = nullptr; (void)hipFree(sl.d_sample_slot); sl.d_sample_slot = nullptr;
-        (void)hipFree(sl.d_slot_ps); sl.d_slot_ps = nullptr; (void)hipFree(sl.d_live); sl.d_live = nullptr;
-        (void)hipFree(sl.d_hits); sl.d_hits = nullptr; (void)hipFree(sl.d_hit_prim); sl.d_hit_prim = nullptr;
-        sl.capacity = 0; sl.bytes = 0; sl.guards.clear();
-    }
+    sl.release_pass_buffers();          // grow: release this slice's buffers only
     const size_t nchunks = (nsamples + chunk_ - 1) / chunk_;
     const size_t records = nchunks * chunk_ * records_per_sample_;
     // the kernels index records, light-term floats and hit flags with 32 bits (byte offsets are 64-bit)
@@ -695,26 +673,19 @@ bool Renderer::ensure_pass_capacity(Slice& sl, size_t nsamples)
     // MI355RT_DEBUG_GUARD: every pass buffer gets a 256-byte tail filled with 0xA5 that check_guards() reads back
     // (tests/test_gpu_dropin.py: no launch may write past the sizes computed here)
     const size_t guard = getenv("MI355RT_DEBUG_GUARD") ? kGuardBytes : 0;
-    sl.guards.clear();
-    auto pass_alloc = [&](void** p, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(p, bytes + guard);
-        if (e == hipSuccess && guard) { e = hipMemset((char*)*p + bytes, 0xA5, guard); sl.guards.push_back((const uint8_t*)*p + bytes); }
-        return e;
-    };
     for (int i = 0; i < 2; ++i) {
-        HIP_ALLOC(pass_alloc(&sl.d_queue[i], records * kRayRecordBytes));
-        HIP_ALLOC(pass_alloc((void**)&sl.d_chunk_counts[i], count_entries * 8));
+        HIP_ALLOC(sl.d_queue[i].alloc(records * kRayRecordBytes, &hbm_bytes_, guard));
+        HIP_ALLOC(sl.d_chunk_counts[i].alloc(count_entries * 8, &hbm_bytes_, guard));
     }
-    HIP_ALLOC(pass_alloc(&sl.d_hits, records * 16));
-    HIP_ALLOC(pass_alloc((void**)&sl.d_hit_prim, records * 4));
-    HIP_ALLOC(pass_alloc((void**)&sl.d_slot_L, nchunks * chunk_ * nodes_per_sample * std::max(nlights_, 1u) * 12));
-    HIP_ALLOC(pass_alloc((void**)&sl.d_sample_slot, nchunks * chunk_ * 4));
-    HIP_ALLOC(pass_alloc((void**)&sl.d_slot_ps, nchunks * chunk_ * 8));
-    HIP_ALLOC(pass_alloc((void**)&sl.d_live, (nchunks + kMaxCursors) * 4));
+    HIP_ALLOC(sl.d_hits.alloc(records * 16, &hbm_bytes_, guard));
+    HIP_ALLOC(sl.d_hit_prim.alloc(records * 4, &hbm_bytes_, guard));
+    HIP_ALLOC(sl.d_slot_L.alloc(nchunks * chunk_ * nodes_per_sample * std::max(nlights_, 1u) * 12, &hbm_bytes_, guard));
+    HIP_ALLOC(sl.d_sample_slot.alloc(nchunks * chunk_ * 4, &hbm_bytes_, guard));
+    HIP_ALLOC(sl.d_slot_ps.alloc(nchunks * chunk_ * 8, &hbm_bytes_, guard));
+    HIP_ALLOC(sl.d_live.alloc((nchunks + kMaxCursors) * 4, &hbm_bytes_, guard));
     sl.capacity = nsamples;
     sl.queue_records = records;
     sl.count_entries = count_entries;
-    sl.bytes = 2 * (records * kRayRecordBytes + count_entries * 8) + records * 20 + nchunks * chunk_ * ((size_t)nodes_per_sample * std::max(nlights_, 1u) * 12 + 12);
     return true;
 }
 
@@ -727,7 +698,7 @@ bool Renderer::assign_slice_rows(uint32_t nslices)
     for (Slice& o : slices_) { o.rows.clear(); o.cull_key.clear(); }       // other rows: other pixel blocks, other verdicts
     for (size_t i = 0; i < owned_rows.size(); ++i) slices_[(i / cfg.stripe_rows) % nslices].rows.push_back(owned_rows[i]);
     for (uint32_t s = 0; s < nslices; ++s)
-        if (!slices_[s].rows.empty()) HIP_TRY(hipMemcpy(slices_[s].d_rows, slices_[s].rows.data(), slices_[s].rows.size() * 4, hipMemcpyHostToDevice));
+        if (!slices_[s].rows.empty()) HIP_TRY(hipMemcpy(slices_[s].d_rows.get(), slices_[s].rows.data(), slices_[s].rows.size() * 4, hipMemcpyHostToDevice));
     rows_assigned_for_ = nslices;
     return true;
 }
@@ -764,7 +735,7 @@ void Renderer::describe_pass(DPass& ps, const Slice& sl, const uint32_t* d_rows,
     std::memcpy(ps.level_first, level_first, sizeof ps.level_first);
     ps.use_explicit = explicit_sample ? 1u : 0u; ps.explicit_pixel = epixel; ps.explicit_sampleno = esample;
     ps.chunk = chunk; ps.nchunks = (uint32_t)((nsamples + chunk - 1) / chunk); ps.region = chunk * records_per_sample_;
-    ps.hit_prim = sl.d_hit_prim; ps.qstride = sl.queue_records; ps.slot_ps = (uint2*)sl.d_slot_ps;
+    ps.hit_prim = sl.d_hit_prim.get(); ps.qstride = sl.queue_records; ps.slot_ps = (uint2*)sl.d_slot_ps.get();
     ps.stack_depth = traversal_rows(); ps.list_cap = chunk * max_level_nodes_;
     ps.leaf_threshold = leaf_threshold_;
     ps.refill_threshold = 24; if (const char* e = getenv("MI355RT_REFILL")) { int v = atoi(e); if (v >= 1 && v <= 64) ps.refill_threshold = (uint32_t)v; }
@@ -782,8 +753,8 @@ void Renderer::describe_pass(DPass& ps, const Slice& sl, const uint32_t* d_rows,
     // Not with the direct octree walk: its trace launch strides over ALL chunks, and the ray counts of the chunks the shade launches no longer visit
     // are whatever an earlier pass left there.
     ps.live = nullptr; ps.live_count = nullptr; ps.live_cap = 0;
-    if (ps.pull_mode == 4u && ps.pull_group == 1u && chunk == chunk_ && sl.d_live != nullptr && !explicit_sample && mode_ != kModeOctreeWalk && !getenv("MI355RT_NO_LIVE")) {
-        ps.live = sl.d_live; ps.live_count = sl.d_ctrl; ps.live_cap = (ps.nchunks + ps.ncursors - 1u) / ps.ncursors;
+    if (ps.pull_mode == 4u && ps.pull_group == 1u && chunk == chunk_ && sl.d_live && !explicit_sample && mode_ != kModeOctreeWalk && !getenv("MI355RT_NO_LIVE")) {
+        ps.live = sl.d_live.get(); ps.live_count = sl.d_ctrl.get(); ps.live_cap = (ps.nchunks + ps.ncursors - 1u) / ps.ncursors;
     }
 }
 
@@ -800,7 +771,7 @@ bool Renderer::pass_begin(PassRun& run, Slice& sl, const uint32_t* d_rows, uint3
     if (!ensure_pass_capacity(sl, nsamples)) return false;
     describe_pass(run.ps, sl, d_rows, row0, row_wrap, npix, nsamples, chunk_, explicit_sample, epixel, esample);
     // the tile bins of the primary rays need a pass that walks the slice's whole row list (render(); not the odd row windows of the other callers)
-    const bool whole = !explicit_sample && d_rows == sl.d_rows && row0 == 0 && nrows == sl.rows.size() && row_wrap == 0xFFFFFFFFu;
+    const bool whole = !explicit_sample && d_rows == sl.d_rows.get() && row0 == 0 && nrows == sl.rows.size() && row_wrap == 0xFFFFFFFFu;
     run.cam = device_camera(whole ? &run.ps : nullptr, whole ? &sl.rows : nullptr);
     // culling verdicts per pixel block, computed once per camera and layout (DPass::block_culled) instead of per launch and chunk
     run.ps.block_culled = nullptr; run.ps.cull_blocks = 0;
@@ -812,23 +783,22 @@ bool Renderer::pass_begin(PassRun& run, Slice& sl, const uint32_t* d_rows, uint3
         key.insert(key.end(), run.cam.origin, run.cam.origin + 3); key.push_back(run.cam.max_x); key.push_back(run.cam.max_y);
         key.push_back((float)nrows); key.push_back((float)run.ps.chunk); key.push_back((float)run.ps.sample_group); key.push_back((float)run.ps.row_group);
         key.push_back((float)(run.ps.flags & 1u)); key.push_back(run.cam.cull_mask ? 1.0f : 0.0f); key.push_back((float)nblocks);
-        if (nblocks > sl.block_culled_cap) {
+        if (nblocks * 4 > sl.d_block_culled.bytes()) {
             HIP_TRY(hipStreamSynchronize(sl.stream));
-            if (sl.d_block_culled) { (void)hipFree(sl.d_block_culled); sl.d_block_culled = nullptr; sl.block_culled_cap = 0; }
-            if (hipMalloc((void**)&sl.d_block_culled, nblocks * 4) == hipSuccess) sl.block_culled_cap = nblocks; else { (void)hipGetLastError(); sl.d_block_culled = nullptr; }
+            if (sl.d_block_culled.alloc(nblocks * 4, &hbm_bytes_) != hipSuccess) (void)hipGetLastError();
             sl.cull_key.clear();
         }
         if (sl.d_block_culled) {
             if (key != sl.cull_key) {          // stream-ordered behind the launches that read the old verdicts
-                HIP_TRY(launch_cull_blocks(sl.stream, run.cam, run.ps, (uint32_t)nblocks, sl.d_block_culled));
+                HIP_TRY(launch_cull_blocks(sl.stream, run.cam, run.ps, (uint32_t)nblocks, sl.d_block_culled.get()));
                 sl.cull_key = key;
             }
-            run.ps.block_culled = sl.d_block_culled; run.ps.cull_blocks = (uint32_t)nblocks;
+            run.ps.block_culled = sl.d_block_culled.get(); run.ps.cull_blocks = (uint32_t)nblocks;
         }
     }
     run.rounds = cfg.recursions + 2;
     // the work cursors: zeroed at creation and again by the resolve kernel of every pass that ran to its end (pass_end)
-    if (!sl.ctrl_clean) HIP_TRY(hipMemsetAsync(sl.d_ctrl, 0, kMaxRounds * kCtrlWordsPerRound * 4, sl.stream));
+    if (!sl.ctrl_clean) HIP_TRY(hipMemsetAsync(sl.d_ctrl.get(), 0, kMaxRounds * kCtrlWordsPerRound * 4, sl.stream));
     sl.ctrl_clean = false;
     run.live = true;
     return true;
@@ -850,8 +820,8 @@ bool Renderer::pass_round(PassRun& run, uint32_t r, hipStream_t trace_stream, in
     const bool confirm_round = mode_ == kModeConfirm && !dscene_.oct_single_leaf;
     const char* sw_env = getenv("MI355RT_SHADE_WALK");
     const bool fuse_primary = r == 0 && cam.tile_ofs != nullptr && mode_ != kModeOctreeWalk && (!confirm_round || !sw_env || atoi(sw_env) >= 1) && !getenv("MI355RT_NO_FUSE_PRIMARY");
-    const void* in_q = r == 0 ? nullptr : sl.d_queue[(r - 1) & 1];
-    const void* in_c = r == 0 ? nullptr : sl.d_chunk_counts[(r - 1) & 1];
+    const void* in_q = r == 0 ? nullptr : sl.d_queue[(r - 1) & 1].get();
+    const void* in_c = r == 0 ? nullptr : sl.d_chunk_counts[(r - 1) & 1].get();
     const bool balance_dbg = !fuse_primary && count && getenv("MI355RT_DEBUG_UTIL") && mode_ != kModeOctreeWalk;
     if (!fuse_primary) {
     if (tst != st) { HIP_TRY(hipEventRecord(sl.ev_ready, st)); HIP_TRY(hipStreamWaitEvent(tst, sl.ev_ready, 0)); }
@@ -864,19 +834,19 @@ bool Renderer::pass_round(PassRun& run, uint32_t r, hipStream_t trace_stream, in
     }
     if (balance_dbg) {       // load-balance diagnostics of this launch (debug only: synchronises)
         DCounters init{};
-        HIP_TRY(hipMemcpy(&init, d_counters_, sizeof init, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&init, d_counters_.get(), sizeof init, hipMemcpyDeviceToHost));
         init.t_first_end = ~0ull; init.t_start = ~0ull; init.t_last_end = 0; init.t_sum_end = 0; init.n_waves = 0;
-        HIP_TRY(hipMemcpy(d_counters_, &init, sizeof init, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_counters_.get(), &init, sizeof init, hipMemcpyHostToDevice));
     }
     if (mode_ == kModeOctreeWalk)
-        HIP_TRY(launch_trace_octree(tst, num_cus_, r == 0, dscene_, cam, ps, in_q, in_c, sl.d_hits, sl.d_slot_L, d_film_n_));
+        HIP_TRY(launch_trace_octree(tst, num_cus_, r == 0, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_slot_L.get(), d_film_n_.get()));
     else {
         DPass pr = ps;
         if (r == 0) pr.refill_threshold = refill_primary_;             // primary rays: see describe_pass
         if (r == 0 && cam.tile_ofs != nullptr)                         // the primary rays' closest hits from the screen-space triangle bins instead of the tree
-            HIP_TRY(launch_raster(tst, num_cus_, count, mode_ == kModeConfirm, dscene_, cam, ps, sl.d_hits, sl.d_ctrl + r * kCtrlWordsPerRound, d_film_n_, d_counters_));
+            HIP_TRY(launch_raster(tst, num_cus_, count, mode_ == kModeConfirm, dscene_, cam, ps, sl.d_hits.get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound, d_film_n_.get(), d_counters_.get()));
         else
-        HIP_TRY(launch_trace(tst, num_cus_, trace_blocks_per_cu, r == 0, count, mode_ == kModeConfirm, dscene_, cam, pr, in_q, in_c, sl.d_hits, sl.d_ctrl + r * kCtrlWordsPerRound, sl.d_slot_L, d_film_n_, d_counters_));
+        HIP_TRY(launch_trace(tst, num_cus_, trace_blocks_per_cu, r == 0, count, mode_ == kModeConfirm, dscene_, cam, pr, in_q, in_c, sl.d_hits.get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound, sl.d_slot_L.get(), d_film_n_.get(), d_counters_.get()));
     }
     if (timed) { HIP_TRY(hipEventRecord(ev_pool_[ev_used_ + 1], tst)); ev_used_ += 2; }
     ++launches_;
@@ -890,14 +860,14 @@ bool Renderer::pass_round(PassRun& run, uint32_t r, hipStream_t trace_stream, in
     const int sw_mode = sw ? atoi(sw) : 2;
     const bool shade_walks = confirm_here && r <= cfg.recursions && (r == 0 ? sw_mode >= 1 : sw_mode >= 2);
     if (confirm_here && !(shade_walks && r == 0))
-        HIP_TRY(launch_confirm(st, num_cus_, r == 0, shade_walks, dscene_, cam, ps, in_q, in_c, sl.d_hits, sl.d_ctrl + r * kCtrlWordsPerRound + kConfirmCursorOffset, sl.d_slot_L, d_film_n_));
+        HIP_TRY(launch_confirm(st, num_cus_, r == 0, shade_walks, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound + kConfirmCursorOffset, sl.d_slot_L.get(), d_film_n_.get()));
     if (balance_dbg) {
         DCounters c0{};
         HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(&c0, d_counters_, sizeof c0, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&c0, d_counters_.get(), sizeof c0, hipMemcpyDeviceToHost));
         {   // lane census of the launch (summed over the counter shards; cumulative over the call's launches: print differences)
             DCounters sh[kShards], t{};
-            HIP_TRY(hipMemcpy(sh, d_counters_, sizeof sh, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(sh, d_counters_.get(), sizeof sh, hipMemcpyDeviceToHost));
             for (const DCounters& x : sh) { t.lanes_inner += x.lanes_inner; t.lanes_leaf += x.lanes_leaf; t.lanes_done += x.lanes_done; t.lane_samples += x.lane_samples;
                                             t.refills += x.refills; t.refill_passes += x.refill_passes; t.refill_rays += x.refill_rays; t.inner_execs += x.inner_execs; t.leaf_execs += x.leaf_execs; }
             static DCounters prev{};
@@ -915,7 +885,7 @@ bool Renderer::pass_round(PassRun& run, uint32_t r, hipStream_t trace_stream, in
                     (double)c0.t_sum_end / c0.n_waves / 100.0, (double)(c0.t_first_end - c0.t_start) / 100.0, (double)(c0.t_last_end - c0.t_start) / 100.0);
     }
     if (r <= cfg.recursions)
-        HIP_TRY(launch_shade(st, num_cus_, r == 0, shade_walks, dscene_, cam, ps, r, in_q, in_c, sl.d_hits, sl.d_queue[r & 1], sl.d_chunk_counts[r & 1], sl.d_ctrl + r * kCtrlWordsPerRound + kShadeCursorOffset, sl.d_slot_L, sl.d_sample_slot, d_film_n_, d_counters_, fuse_primary));
+        HIP_TRY(launch_shade(st, num_cus_, r == 0, shade_walks, dscene_, cam, ps, r, in_q, in_c, sl.d_hits.get(), sl.d_queue[r & 1].get(), sl.d_chunk_counts[r & 1].get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound + kShadeCursorOffset, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_n_.get(), d_counters_.get(), fuse_primary));
     return true;
 }
 
@@ -923,7 +893,7 @@ bool Renderer::pass_end(PassRun& run)
 {
     if (!run.live) return true;
     Slice& sl = *run.sl;
-    HIP_TRY(launch_resolve(sl.stream, run.ps, cfg.width, nlights_, sl.d_slot_L, sl.d_sample_slot, d_film_sum_, d_film_sumsq_, d_film_n_, d_debug_color_, sl.d_ctrl));
+    HIP_TRY(launch_resolve(sl.stream, run.ps, cfg.width, nlights_, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_debug_color_.get(), sl.d_ctrl.get()));
     sl.ctrl_clean = true;
     run.live = false;
     return true;
@@ -944,7 +914,7 @@ bool Renderer::begin_call()
     call_done_valid_ = false;
     ev_used_ = 0; launches_ = 0;
     counts_pending_ = false;
-    HIP_TRY(hipMemsetAsync(d_counters_, 0, sizeof(DCounters) * kShards, stream_));
+    HIP_TRY(hipMemsetAsync(d_counters_.get(), 0, sizeof(DCounters) * kShards, stream_));
     HIP_TRY(hipEventRecord(ev_begin_, stream_));
     active_slices_ = 1;
     return true;
@@ -954,7 +924,7 @@ bool Renderer::begin_call()
 bool Renderer::fetch_counts(uint64_t primary, bool timed_call)
 {
     DCounters c{};
-    const DCounters* shard = h_counters_;          // pinned; filled by the asynchronous copy queue_counts_copy() put behind the call's kernels
+    const DCounters* shard = h_counters_.get();          // pinned; filled by the asynchronous copy queue_counts_copy() put behind the call's kernels
     for (uint32_t i = 0; i < kShards; ++i) {
         const DCounters& s = shard[i];
         c.bounce += s.bounce; c.shadow += s.shadow; c.primary_hits += s.primary_hits;
@@ -994,7 +964,7 @@ bool Renderer::fetch_counts(uint64_t primary, bool timed_call)
 // the call's device counters -> the pinned host mirror, stream-ordered behind the call's kernels (one wait serves both)
 bool Renderer::queue_counts_copy()
 {
-    HIP_TRY(hipMemcpyAsync(h_counters_, d_counters_, sizeof(DCounters) * kShards, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(h_counters_.get(), d_counters_.get(), sizeof(DCounters) * kShards, hipMemcpyDeviceToHost, stream_));
     return true;
 }
 
@@ -1068,7 +1038,7 @@ uint32_t Renderer::trace_frame_additive()
         if (!begin_call()) return 0;
         for (uint32_t done = 0; done < win.total; done += nown) {
             const uint32_t n = std::min(nown, win.total - done);
-            if (!run_pass(slices_[0], d_owned_rows_, (win.first + done) % nown, n, 1, false, 0, 0, nown)) return 0;
+            if (!run_pass(slices_[0], d_owned_rows_.get(), (win.first + done) % nown, n, 1, false, 0, 0, nown)) return 0;
         }
         current_row = win.next_row;
         mark_dirty_window(win.first, win.total);
@@ -1092,7 +1062,7 @@ uint32_t Renderer::trace_frame_additive()
         } else if (!settle_speculation()) return 0;
     }
     if (!adopted) {
-        if (hipMemsetAsync(d_counters_, 0, sizeof(DCounters) * kShards, stream_) != hipSuccess) { last_error = "hipMemsetAsync failed"; return 0; }
+        if (hipMemsetAsync(d_counters_.get(), 0, sizeof(DCounters) * kShards, stream_) != hipSuccess) { last_error = "hipMemsetAsync failed"; return 0; }
         for (uint32_t done = 0; done < win.total; done += nown) {
             const uint32_t n = std::min(nown, win.total - done);
             if (timed) {
@@ -1100,7 +1070,7 @@ uint32_t Renderer::trace_frame_additive()
                 (void)hipEventRecord(ev_pool_[ev_used_], stream_);
                 ev_secondary_.resize(ev_pool_.size() / 2); ev_secondary_[ev_used_ / 2] = false;
             }
-            if (!launch_fused_window((win.first + done) % nown, n, cam, d_counters_)) return 0;
+            if (!launch_fused_window((win.first + done) % nown, n, cam, d_counters_.get())) return 0;
             if (timed) { (void)hipEventRecord(ev_pool_[ev_used_ + 1], stream_); ev_used_ += 2; }
             ++launches_;
         }
@@ -1118,20 +1088,22 @@ uint32_t Renderer::trace_frame_additive()
     const FrameWindow nxt = frame_window(current_row, cfg.height, cfg.stripe_rows, cfg.stripe_world, cfg.stripe_rank, owned_rows);
     if (!no_spec && !timed && cfg.stripe_world <= 1 && ev_call_done_ && read_stream_ && win.total <= nown && nxt.total != 0 && win.total + nxt.total <= nown) {
         const size_t bk = (size_t)50 * cfg.width;
-        if (!d_bk_sum_) {
-            if (hipMalloc((void**)&d_bk_sum_, bk * 12) != hipSuccess || hipMalloc((void**)&d_bk_sumsq_, bk * 12) != hipSuccess || hipMalloc((void**)&d_bk_n_, bk * 4) != hipSuccess
-                || hipMalloc((void**)&d_counters_spec_, sizeof(DCounters) * kShards) != hipSuccess || hipHostMalloc((void**)&h_counters_spec_, sizeof(DCounters) * kShards, hipHostMallocDefault) != hipSuccess) {
+        if (!d_bk_sum_) {          // all five or none: the next call takes a non-null d_bk_sum_ for the whole set
+            DeviceBuffer<float> sum, sumsq; DeviceBuffer<uint32_t> n; DeviceBuffer<DCounters> dc; PinnedBuffer<DCounters> hc;
+            if (sum.alloc(bk * 12, &hbm_bytes_) != hipSuccess || sumsq.alloc(bk * 12, &hbm_bytes_) != hipSuccess || n.alloc(bk * 4, &hbm_bytes_) != hipSuccess
+                || dc.alloc(sizeof(DCounters) * kShards, &hbm_bytes_) != hipSuccess || hc.alloc(sizeof(DCounters) * kShards) != hipSuccess) {
                 (void)hipGetLastError(); return 50u * cfg.width;            // no room to speculate: the frame asked for is queued all the same
             }
-            allocs_.push_back(d_bk_sum_); allocs_.push_back(d_bk_sumsq_); allocs_.push_back(d_bk_n_); allocs_.push_back(d_counters_spec_);
+            d_bk_sum_ = std::move(sum); d_bk_sumsq_ = std::move(sumsq); d_bk_n_ = std::move(n); d_counters_spec_ = std::move(dc); h_counters_spec_ = std::move(hc);
         }
-        bool ok = launch_film_rows_copy(stream_, d_owned_rows_, nxt.first, nxt.total, nown, cfg.width, d_film_sum_, d_film_sumsq_, d_film_n_, d_bk_sum_, d_bk_sumsq_, d_bk_n_, false) == hipSuccess
-                  && hipMemsetAsync(d_counters_spec_, 0, sizeof(DCounters) * kShards, stream_) == hipSuccess
-                  && launch_fused_window(nxt.first, nxt.total, cam, d_counters_spec_)
-                  && hipMemcpyAsync(h_counters_spec_, d_counters_spec_, sizeof(DCounters) * kShards, hipMemcpyDeviceToHost, stream_) == hipSuccess
+        const bool backed_up = launch_film_rows_copy(stream_, d_owned_rows_.get(), nxt.first, nxt.total, nown, cfg.width, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_bk_sum_.get(), d_bk_sumsq_.get(), d_bk_n_.get(), false) == hipSuccess;
+        bool ok = backed_up
+                  && hipMemsetAsync(d_counters_spec_.get(), 0, sizeof(DCounters) * kShards, stream_) == hipSuccess
+                  && launch_fused_window(nxt.first, nxt.total, cam, d_counters_spec_.get())
+                  && hipMemcpyAsync(h_counters_spec_.get(), d_counters_spec_.get(), sizeof(DCounters) * kShards, hipMemcpyDeviceToHost, stream_) == hipSuccess
                   && hipEventRecord(ev_spec_done_, stream_) == hipSuccess;
-        if (!ok) { (void)hipGetLastError(); HIP_TRY(hipStreamSynchronize(stream_));        // what was queued of it ran; put the rows back and go on without
-                   (void)launch_film_rows_copy(stream_, d_owned_rows_, nxt.first, nxt.total, nown, cfg.width, d_film_sum_, d_film_sumsq_, d_film_n_, d_bk_sum_, d_bk_sumsq_, d_bk_n_, true); }
+        if (!ok) { (void)hipGetLastError(); HIP_TRY(hipStreamSynchronize(stream_));        // what was queued of it ran; put the rows back (if they were saved) and go on without
+                   if (backed_up) (void)launch_film_rows_copy(stream_, d_owned_rows_.get(), nxt.first, nxt.total, nown, cfg.width, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_bk_sum_.get(), d_bk_sumsq_.get(), d_bk_n_.get(), true); }
         else { spec_.valid = true; spec_.row = current_row; spec_.first = nxt.first; spec_.total = nxt.total; spec_.next_row = nxt.next_row; spec_.cam_key = cam_key; spec_.seed = cfg.seed; spec_.flags = cfg.flags; ++spec_launched_; }
     }
     return 50u * cfg.width;
@@ -1147,10 +1119,10 @@ bool Renderer::launch_fused_window(uint32_t first, uint32_t total, const DCamera
     DPass ps;
     uint32_t fchunk = 32u;                                            // samples per wave (a 4x8 pixel tile): 64 / 32 / 16 measure 0.303 / 0.266 / 0.277 ms per launch
     if (const char* e = getenv("MI355RT_FUSED_CHUNK")) { int v = atoi(e); if (v == 16 || v == 32 || v == 64) fchunk = (uint32_t)v; }   // <= 64: the LDS lists hold one row per record of a sample; >= kMinChunk: the counts arrays
-    describe_pass(ps, sl, d_owned_rows_, first, nown, (uint32_t)nsamples, nsamples, fchunk, false, 0, 0);
+    describe_pass(ps, sl, d_owned_rows_.get(), first, nown, (uint32_t)nsamples, nsamples, fchunk, false, 0, 0);
     if (ps.nchunks > sl.count_entries || (size_t)ps.nchunks * ps.region > sl.queue_records) { last_error = "internal: fused pass does not fit the pass buffers"; return false; }
-    hipError_t e = launch_fused_pass(stream_, num_cus_, mode_ == kModeConfirm, dscene_, cam, ps, max_level_nodes_, records_per_sample_, sl.d_queue[0], sl.d_queue[1],
-                                     sl.d_hits, sl.d_slot_L, sl.d_sample_slot, d_film_sum_, d_film_sumsq_, d_film_n_, dcounters);
+    hipError_t e = launch_fused_pass(stream_, num_cus_, mode_ == kModeConfirm, dscene_, cam, ps, max_level_nodes_, records_per_sample_, sl.d_queue[0].get(), sl.d_queue[1].get(),
+                                     sl.d_hits.get(), sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), dcounters);
     if (e != hipSuccess) return fail(e, "fused pass launch");
     return true;
 }
@@ -1161,7 +1133,7 @@ bool Renderer::settle_speculation()
     if (!spec_.valid) return true;
     spec_.valid = false;
     if (!bind()) return false;
-    HIP_TRY(launch_film_rows_copy(stream_, d_owned_rows_, spec_.first, spec_.total, (uint32_t)owned_rows.size(), cfg.width, d_film_sum_, d_film_sumsq_, d_film_n_, d_bk_sum_, d_bk_sumsq_, d_bk_n_, true));
+    HIP_TRY(launch_film_rows_copy(stream_, d_owned_rows_.get(), spec_.first, spec_.total, (uint32_t)owned_rows.size(), cfg.width, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_bk_sum_.get(), d_bk_sumsq_.get(), d_bk_n_.get(), true));
     return true;
 }
 
@@ -1233,8 +1205,8 @@ bool Renderer::render(uint32_t spp, bool wait)
                 if (p >= plan[s].size()) continue;
                 any = true;
                 const PassDesc& d = plan[s][p];
-                if (!pipelined) { if (!run_pass(slices_[s], slices_[s].d_rows, d.r0, d.nr, d.kk, false, 0, 0)) return false; continue; }
-                if (!pass_begin(run[s], slices_[s], slices_[s].d_rows, d.r0, d.nr, d.kk, false, 0, 0, 0xFFFFFFFFu)) return false;
+                if (!pipelined) { if (!run_pass(slices_[s], slices_[s].d_rows.get(), d.r0, d.nr, d.kk, false, 0, 0)) return false; continue; }
+                if (!pass_begin(run[s], slices_[s], slices_[s].d_rows.get(), d.r0, d.nr, d.kk, false, 0, 0, 0xFFFFFFFFu)) return false;
                 rounds = std::max(rounds, run[s].rounds);
             }
             if (!any) break;
@@ -1257,7 +1229,7 @@ bool Renderer::get_tonemapped(uint32_t* out, size_t n)
     if (!bind()) return false;
     const size_t npix = (size_t)cfg.width * cfg.height;
     if (n < npix || !out) { last_error = "output buffer too small"; return false; }
-    if (!h_ldr_) HIP_TRY(hipHostMalloc((void**)&h_ldr_, npix * 4, hipHostMallocDefault));
+    if (!h_ldr_) HIP_TRY(h_ldr_.alloc(npix * 4));
     // A speculative frame may be changing rows right now (trace_frame_additive).  Rows it touches that have to be read (everything is dirty after a
     // clear) would show samples the caller has not asked for yet: then the speculation is given up.  Otherwise the read-out runs beside it, on its own
     // stream, behind the frame the caller did ask for.
@@ -1273,12 +1245,12 @@ bool Renderer::get_tonemapped(uint32_t* out, size_t n)
         if (!ldr_dirty_[r]) { ++r; continue; }
         uint32_t e = r;
         while (e < cfg.height && ldr_dirty_[e]) ldr_dirty_[e++] = 0;
-        HIP_TRY(launch_tonemap(rs, nullptr, r, e - r, cfg.width, false, d_film_sum_, d_film_n_, d_ldr_));
-        HIP_TRY(hipMemcpyAsync(h_ldr_ + (size_t)r * cfg.width, d_ldr_ + (size_t)r * cfg.width, (size_t)(e - r) * cfg.width * 4, hipMemcpyDeviceToHost, rs));
+        HIP_TRY(launch_tonemap(rs, nullptr, r, e - r, cfg.width, false, d_film_sum_.get(), d_film_n_.get(), d_ldr_.get()));
+        HIP_TRY(hipMemcpyAsync(h_ldr_.get() + (size_t)r * cfg.width, d_ldr_.get() + (size_t)r * cfg.width, (size_t)(e - r) * cfg.width * 4, hipMemcpyDeviceToHost, rs));
         r = e;
     }
     HIP_TRY(hipStreamSynchronize(rs));
-    std::memcpy(out, h_ldr_, npix * 4);
+    std::memcpy(out, h_ldr_.get(), npix * 4);
     return true;
 }
 
@@ -1294,13 +1266,13 @@ bool Renderer::tonemap_owned_rows_device(uint32_t* device_out, size_t n, hipStre
     if (caller_stream) {
         HIP_TRY(hipEventRecord(slices_[0].done, stream_));
         HIP_TRY(hipStreamWaitEvent(caller_stream, slices_[0].done, 0));
-        HIP_TRY(launch_tonemap(caller_stream, d_owned_rows_, 0, (uint32_t)owned_rows.size(), cfg.width, true, d_film_sum_, d_film_n_, device_out));
+        HIP_TRY(launch_tonemap(caller_stream, d_owned_rows_.get(), 0, (uint32_t)owned_rows.size(), cfg.width, true, d_film_sum_.get(), d_film_n_.get(), device_out));
         // later work of this handle (film.clear, the next frame) must not overtake the read of the film
         HIP_TRY(hipEventRecord(ev_tonemap_, caller_stream));
         HIP_TRY(hipStreamWaitEvent(stream_, ev_tonemap_, 0));
         return true;
     }
-    HIP_TRY(launch_tonemap(stream_, d_owned_rows_, 0, (uint32_t)owned_rows.size(), cfg.width, true, d_film_sum_, d_film_n_, device_out));
+    HIP_TRY(launch_tonemap(stream_, d_owned_rows_.get(), 0, (uint32_t)owned_rows.size(), cfg.width, true, d_film_sum_.get(), d_film_n_.get(), device_out));
     HIP_TRY(hipStreamSynchronize(stream_));
     return true;
 }
@@ -1321,20 +1293,13 @@ long Renderer::check_guards()
     std::vector<uint8_t> h(kGuardBytes);
     for (Slice& sl : slices_) {
         if (sl.stream && hipStreamSynchronize(sl.stream) != hipSuccess) return -1;
-        for (const uint8_t* g : sl.guards) {
-            if (hipMemcpy(h.data(), g, kGuardBytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-            for (uint8_t b : h) bad += b != 0xA5;
-        }
+        sl.for_each_pass_buffer([&](const auto& buf) {
+            if (bad < 0 || !buf.guard()) return;
+            if (hipMemcpy(h.data(), buf.guard(), kGuardBytes, hipMemcpyDeviceToHost) != hipSuccess) bad = -1;
+            else for (uint8_t b : h) bad += b != 0xA5;
+        });
     }
     return bad;
-}
-
-size_t Renderer::hbm_allocated_bytes() const
-{
-    size_t b = alloc_bytes_;
-    for (const Slice& sl : slices_) b += sl.bytes;
-    if (d_gather_) b += (size_t)slot_rows() * cfg.width * 4 * (gather_is_root_ ? cfg.stripe_world : 1);
-    return b;
 }
 
 // ---- multi-GPU gather ------------------------------------------------------------------------------------------
@@ -1353,9 +1318,9 @@ bool Renderer::gather_prepare(bool root)
 {
     if (!bind()) return false;
     if (d_gather_ && gather_is_root_ == root) return true;
-    if (d_gather_) { HIP_TRY(hipStreamSynchronize(stream_)); (void)hipFree(d_gather_); d_gather_ = nullptr; }
+    if (d_gather_) HIP_TRY(hipStreamSynchronize(stream_));             // kernels of earlier calls may still use the old slots
     const size_t slot = (size_t)slot_rows() * cfg.width * 4;
-    HIP_TRY(hipMalloc((void**)&d_gather_, slot * (root ? cfg.stripe_world : 1)));
+    HIP_TRY(d_gather_.alloc(slot * (root ? cfg.stripe_world : 1), &hbm_bytes_));
     gather_is_root_ = root;
     return true;
 }
@@ -1363,7 +1328,7 @@ bool Renderer::tonemap_to_gather_slot()
 {
     if (!bind()) return false;
     if (!settle_speculation()) return false;
-    HIP_TRY(launch_tonemap(stream_, d_owned_rows_, 0, (uint32_t)owned_rows.size(), cfg.width, true, d_film_sum_, d_film_n_, gather_slot(cfg.stripe_rank)));
+    HIP_TRY(launch_tonemap(stream_, d_owned_rows_.get(), 0, (uint32_t)owned_rows.size(), cfg.width, true, d_film_sum_.get(), d_film_n_.get(), gather_slot(cfg.stripe_rank)));
     return true;
 }
 bool Renderer::finish_gather(uint32_t* host_out, size_t n)
@@ -1371,12 +1336,12 @@ bool Renderer::finish_gather(uint32_t* host_out, size_t n)
     if (!bind()) return false;
     const size_t npix = (size_t)cfg.width * cfg.height;
     if (host_out && n < npix) { last_error = "output buffer too small"; return false; }
-    HIP_TRY(launch_place_stripes(stream_, d_gather_, d_ldr_, cfg.width, cfg.height, cfg.stripe_rows, cfg.stripe_world, slot_rows()));
+    HIP_TRY(launch_place_stripes(stream_, d_gather_.get(), d_ldr_.get(), cfg.width, cfg.height, cfg.stripe_rows, cfg.stripe_world, slot_rows()));
     if (host_out) {
-        if (!h_ldr_) HIP_TRY(hipHostMalloc((void**)&h_ldr_, npix * 4, hipHostMallocDefault));
-        HIP_TRY(hipMemcpyAsync(h_ldr_, d_ldr_, npix * 4, hipMemcpyDeviceToHost, stream_));
+        if (!h_ldr_) HIP_TRY(h_ldr_.alloc(npix * 4));
+        HIP_TRY(hipMemcpyAsync(h_ldr_.get(), d_ldr_.get(), npix * 4, hipMemcpyDeviceToHost, stream_));
         HIP_TRY(hipStreamSynchronize(stream_));
-        std::memcpy(host_out, h_ldr_, npix * 4);
+        std::memcpy(host_out, h_ldr_.get(), npix * 4);
     }
     return true;
 }
@@ -1387,9 +1352,9 @@ bool Renderer::film_get(float* sum, float* sumsq, uint32_t* n)
     if (!settle_speculation()) return false;
     const size_t npix = (size_t)cfg.width * cfg.height;
     HIP_TRY(hipStreamSynchronize(stream_));
-    if (sum) HIP_TRY(hipMemcpy(sum, d_film_sum_, npix * 12, hipMemcpyDeviceToHost));
-    if (sumsq) HIP_TRY(hipMemcpy(sumsq, d_film_sumsq_, npix * 12, hipMemcpyDeviceToHost));
-    if (n) HIP_TRY(hipMemcpy(n, d_film_n_, npix * 4, hipMemcpyDeviceToHost));
+    if (sum) HIP_TRY(hipMemcpy(sum, d_film_sum_.get(), npix * 12, hipMemcpyDeviceToHost));
+    if (sumsq) HIP_TRY(hipMemcpy(sumsq, d_film_sumsq_.get(), npix * 12, hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(hipMemcpy(n, d_film_n_.get(), npix * 4, hipMemcpyDeviceToHost));
     return true;
 }
 
@@ -1402,12 +1367,12 @@ bool Renderer::film_clear()
     if (cfg.stripe_world > 1) {
         // a striped handle only ever writes its own rows (the others stay as created: zero): one launch over them instead of three
         // whole-film memsets — 20 us of a 3.3 ms frame on one rank of eight
-        HIP_TRY(launch_film_clear_rows(stream_, d_owned_rows_, (uint32_t)owned_rows.size(), cfg.width, d_film_sum_, d_film_sumsq_, d_film_n_));
+        HIP_TRY(launch_film_clear_rows(stream_, d_owned_rows_.get(), (uint32_t)owned_rows.size(), cfg.width, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get()));
         return true;
     }
-    HIP_TRY(hipMemsetAsync(d_film_sum_, 0, npix * 12, stream_));
-    HIP_TRY(hipMemsetAsync(d_film_sumsq_, 0, npix * 12, stream_));
-    HIP_TRY(hipMemsetAsync(d_film_n_, 0, npix * 4, stream_));
+    HIP_TRY(hipMemsetAsync(d_film_sum_.get(), 0, npix * 12, stream_));
+    HIP_TRY(hipMemsetAsync(d_film_sumsq_.get(), 0, npix * 12, stream_));
+    HIP_TRY(hipMemsetAsync(d_film_n_.get(), 0, npix * 4, stream_));
     return true;            // stream-ordered: every later call on this handle starts on the same stream
 }
 
@@ -1417,43 +1382,38 @@ bool Renderer::intersect(const float* rays6, size_t n, float* tuv, uint32_t* pri
     if (n == 0) return true;
     if (n > 0x7FFFFFFFull / 24) { last_error = "too many rays in one batch"; return false; }
     const bool shadow = blocked != nullptr;
-    float* d_rays = nullptr; float* d_tuv = nullptr; uint32_t* d_prim = nullptr; uint8_t* d_blocked = nullptr;
-    bool ok = true;
-    auto chk = [&](hipError_t e, const char* w) { if (ok && e != hipSuccess) { ok = fail(e, w); } };
-    chk(hipMalloc((void**)&d_rays, n * 24), "hipMalloc rays");
-    chk(hipMalloc((void**)&d_tuv, n * 12), "hipMalloc tuv");
-    chk(hipMalloc((void**)&d_prim, n * 4), "hipMalloc prim");
-    chk(hipMalloc((void**)&d_blocked, n), "hipMalloc blocked");
-    if (ok) chk(hipMemcpyAsync(d_rays, rays6, n * 24, hipMemcpyHostToDevice, stream_), "upload rays");
-    if (ok && !shadow) chk(hipMemcpyAsync(d_tuv, tuv, n * 12, hipMemcpyHostToDevice, stream_), "upload tuv");   // misses stay untouched
-    if (ok) chk(launch_intersect(stream_, dscene_, traversal_rows(), mode_ == kModeConfirm ? 0 : mode_ == kModeOctreeWalk ? 1 : 2, d_rays, (uint32_t)n, shadow, d_tuv, d_prim, d_blocked), "intersect kernel");
-    if (ok && shadow) chk(hipMemcpyAsync(blocked, d_blocked, n, hipMemcpyDeviceToHost, stream_), "download blocked");
-    if (ok && !shadow) {
-        chk(hipMemcpyAsync(tuv, d_tuv, n * 12, hipMemcpyDeviceToHost, stream_), "download tuv");
-        chk(hipMemcpyAsync(prim, d_prim, n * 4, hipMemcpyDeviceToHost, stream_), "download prim");
+    DeviceBuffer<float> d_rays, d_tuv; DeviceBuffer<uint32_t> d_prim; DeviceBuffer<uint8_t> d_blocked;
+    HIP_TRY(d_rays.alloc(n * 24));
+    HIP_TRY(d_tuv.alloc(n * 12));
+    HIP_TRY(d_prim.alloc(n * 4));
+    HIP_TRY(d_blocked.alloc(n));
+    HIP_TRY(hipMemcpyAsync(d_rays.get(), rays6, n * 24, hipMemcpyHostToDevice, stream_));
+    if (!shadow) HIP_TRY(hipMemcpyAsync(d_tuv.get(), tuv, n * 12, hipMemcpyHostToDevice, stream_));   // misses stay untouched
+    HIP_TRY(launch_intersect(stream_, dscene_, traversal_rows(), mode_ == kModeConfirm ? 0 : mode_ == kModeOctreeWalk ? 1 : 2, d_rays.get(), (uint32_t)n, shadow, d_tuv.get(), d_prim.get(), d_blocked.get()));
+    if (shadow) HIP_TRY(hipMemcpyAsync(blocked, d_blocked.get(), n, hipMemcpyDeviceToHost, stream_));
+    else {
+        HIP_TRY(hipMemcpyAsync(tuv, d_tuv.get(), n * 12, hipMemcpyDeviceToHost, stream_));
+        HIP_TRY(hipMemcpyAsync(prim, d_prim.get(), n * 4, hipMemcpyDeviceToHost, stream_));
     }
-    if (ok) chk(hipStreamSynchronize(stream_), "sync");
-    (void)hipFree(d_rays); (void)hipFree(d_tuv); (void)hipFree(d_prim); (void)hipFree(d_blocked);
-    return ok;
+    HIP_TRY(hipStreamSynchronize(stream_));
+    return true;
 }
 
 bool Renderer::debug_numerics(const float* a, const float* b, size_t n, float* q, float* r, float* p)
 {
     if (!bind()) return false;
     if (n == 0) return true;
-    float* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, n * 4 * 5));
-    bool ok = true;
-    auto chk = [&](hipError_t e, const char* w) { if (ok && e != hipSuccess) ok = fail(e, w); };
-    chk(hipMemcpyAsync(d, a, n * 4, hipMemcpyHostToDevice, stream_), "upload a");
-    chk(hipMemcpyAsync(d + n, b, n * 4, hipMemcpyHostToDevice, stream_), "upload b");
-    if (ok) chk(launch_numerics(stream_, d, d + n, (uint32_t)n, d + 2 * n, d + 3 * n, d + 4 * n), "numerics kernel");
-    chk(hipMemcpyAsync(q, d + 2 * n, n * 4, hipMemcpyDeviceToHost, stream_), "download q");
-    chk(hipMemcpyAsync(r, d + 3 * n, n * 4, hipMemcpyDeviceToHost, stream_), "download r");
-    chk(hipMemcpyAsync(p, d + 4 * n, n * 4, hipMemcpyDeviceToHost, stream_), "download p");
-    chk(hipStreamSynchronize(stream_), "sync");
-    (void)hipFree(d);
-    return ok;
+    DeviceBuffer<float> buf;
+    HIP_TRY(buf.alloc(n * 4 * 5));
+    float* d = buf.get();
+    HIP_TRY(hipMemcpyAsync(d, a, n * 4, hipMemcpyHostToDevice, stream_));
+    HIP_TRY(hipMemcpyAsync(d + n, b, n * 4, hipMemcpyHostToDevice, stream_));
+    HIP_TRY(launch_numerics(stream_, d, d + n, (uint32_t)n, d + 2 * n, d + 3 * n, d + 4 * n));
+    HIP_TRY(hipMemcpyAsync(q, d + 2 * n, n * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(r, d + 3 * n, n * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(p, d + 4 * n, n * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    return true;
 }
 
 // mi355rt_debug_gather_rate: the divergent-gather rate of this device's vector memory pipe (kernels.hip, gather_rate_kernel).
@@ -1466,24 +1426,21 @@ bool Renderer::debug_gather_rate(uint32_t table_nodes, uint32_t steps, double ou
     std::vector<uint32_t> host((size_t)table_nodes * 8);
     uint32_t x = 12345u;
     for (uint32_t& v : host) { x = x * 1664525u + 1013904223u; v = x >> 8; }
-    void* d = nullptr; uint32_t* sink = nullptr;
-    HIP_TRY(hipMalloc(&d, host.size() * 4));
-    bool ok = true;
-    auto chk = [&](hipError_t e, const char* w) { if (ok && e != hipSuccess) ok = fail(e, w); };
-    chk(hipMalloc((void**)&sink, 4), "hipMalloc");
-    chk(hipMemcpy(d, host.data(), host.size() * 4, hipMemcpyHostToDevice), "upload table");
+    DeviceBuffer<> d; DeviceBuffer<uint32_t> sink;
+    HIP_TRY(d.alloc(host.size() * 4));
+    HIP_TRY(sink.alloc(4));
+    HIP_TRY(hipMemcpy(d.get(), host.data(), host.size() * 4, hipMemcpyHostToDevice));
     float best = 0.0f;
-    for (int rep = 0; ok && rep < 3; ++rep) {                          // first launch warms the caches and the clocks
-        chk(hipEventRecord(ev_begin_, stream_), "event");
-        chk(launch_gather_rate(stream_, num_cus_, d, table_nodes, steps, sink), "gather kernel");
-        chk(hipEventRecord(ev_end_, stream_), "event");
-        chk(hipStreamSynchronize(stream_), "sync");
+    for (int rep = 0; rep < 3; ++rep) {                                // first launch warms the caches and the clocks
+        HIP_TRY(hipEventRecord(ev_begin_, stream_));
+        HIP_TRY(launch_gather_rate(stream_, num_cus_, d.get(), table_nodes, steps, sink.get()));
+        HIP_TRY(hipEventRecord(ev_end_, stream_));
+        HIP_TRY(hipStreamSynchronize(stream_));
         float ms = 0.0f;
-        if (ok) chk(hipEventElapsedTime(&ms, ev_begin_, ev_end_), "elapsed");
+        HIP_TRY(hipEventElapsedTime(&ms, ev_begin_, ev_end_));
         if (rep > 0 && (best == 0.0f || ms < best)) best = ms;
     }
-    (void)hipFree(d); if (sink) (void)hipFree(sink);
-    if (!ok || best <= 0.0f) return false;
+    if (best <= 0.0f) return false;
     const double wave_steps = (double)num_cus_ * 8.0 * 4.0 * steps;
     out[0] = wave_steps * 128.0 / (best * 1e-3); out[1] = best; out[2] = wave_steps * 64.0 / (best * 1e-3);
     return true;
@@ -1494,19 +1451,17 @@ bool Renderer::debug_slab(const float* inv_rays6, const float* cubes6, size_t n,
     if (!bind()) return false;
     if (n == 0) return true;
     if (n > (1u << 24)) { last_error = "too many slab tests in one batch"; return false; }
-    float* d = nullptr; uint8_t* dh = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, n * 4 * 13));
-    bool ok = true;
-    auto chk = [&](hipError_t e, const char* w) { if (ok && e != hipSuccess) ok = fail(e, w); };
-    chk(hipMalloc((void**)&dh, n), "hipMalloc");
-    chk(hipMemcpyAsync(d, inv_rays6, n * 24, hipMemcpyHostToDevice, stream_), "upload rays");
-    chk(hipMemcpyAsync(d + 6 * n, cubes6, n * 24, hipMemcpyHostToDevice, stream_), "upload cubes");
-    if (ok) chk(launch_slab(stream_, d, d + 6 * n, (uint32_t)n, dh, d + 12 * n), "slab kernel");
-    chk(hipMemcpyAsync(hit, dh, n, hipMemcpyDeviceToHost, stream_), "download hit");
-    chk(hipMemcpyAsync(tmin, d + 12 * n, n * 4, hipMemcpyDeviceToHost, stream_), "download tmin");
-    chk(hipStreamSynchronize(stream_), "sync");
-    (void)hipFree(d); if (dh) (void)hipFree(dh);
-    return ok;
+    DeviceBuffer<float> buf; DeviceBuffer<uint8_t> dh;
+    HIP_TRY(buf.alloc(n * 4 * 13));
+    HIP_TRY(dh.alloc(n));
+    float* d = buf.get();
+    HIP_TRY(hipMemcpyAsync(d, inv_rays6, n * 24, hipMemcpyHostToDevice, stream_));
+    HIP_TRY(hipMemcpyAsync(d + 6 * n, cubes6, n * 24, hipMemcpyHostToDevice, stream_));
+    HIP_TRY(launch_slab(stream_, d, d + 6 * n, (uint32_t)n, dh.get(), d + 12 * n));
+    HIP_TRY(hipMemcpyAsync(hit, dh.get(), n, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(tmin, d + 12 * n, n * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    return true;
 }
 
 // Film::get_pixels / get_estimated_variances computed on the device, downloaded as width*height*3 floats
@@ -1515,15 +1470,12 @@ bool Renderer::film_stat(bool variances, float* rgb)
     if (!bind()) return false;
     if (!settle_speculation()) return false;
     const size_t npix = (size_t)cfg.width * cfg.height;
-    float* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, npix * 12));
-    bool ok = true;
-    auto chk = [&](hipError_t e, const char* w) { if (ok && e != hipSuccess) ok = fail(e, w); };
-    chk(launch_film_stat(stream_, variances, npix, d_film_sum_, d_film_sumsq_, d_film_n_, d), "film_stat kernel");
-    chk(hipMemcpyAsync(rgb, d, npix * 12, hipMemcpyDeviceToHost, stream_), "download");
-    chk(hipStreamSynchronize(stream_), "sync");
-    (void)hipFree(d);
-    return ok;
+    DeviceBuffer<float> d;
+    HIP_TRY(d.alloc(npix * 12));
+    HIP_TRY(launch_film_stat(stream_, variances, npix, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d.get()));
+    HIP_TRY(hipMemcpyAsync(rgb, d.get(), npix * 12, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    return true;
 }
 
 bool Renderer::debug_sample(uint32_t pixel, uint32_t sampleno, float* color3, float* node_L, size_t nodes)
@@ -1532,19 +1484,19 @@ bool Renderer::debug_sample(uint32_t pixel, uint32_t sampleno, float* color3, fl
     if (nodes < nodes_per_sample || pixel >= cfg.width * cfg.height) { last_error = "bad debug_sample arguments"; return false; }
     if (!settle_speculation()) return false;
     call_done_valid_ = false;
-    HIP_TRY(hipMemsetAsync(d_counters_, 0, sizeof(DCounters) * kShards, stream_));
+    HIP_TRY(hipMemsetAsync(d_counters_.get(), 0, sizeof(DCounters) * kShards, stream_));
     ev_used_ = 0; counts_pending_ = false;
     if (!run_pass(slices_[0], nullptr, 0, 1, 1, true, pixel, sampleno)) return false;
     HIP_TRY(hipStreamSynchronize(stream_));
     const uint32_t nl = std::max(nlights_, 1u);
     std::vector<float> raw((size_t)nodes_per_sample * nl * 3);
     uint32_t sl = 0xFFFFFFFFu;
-    HIP_TRY(hipMemcpy(&sl, slices_[0].d_sample_slot, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&sl, slices_[0].d_sample_slot.get(), 4, hipMemcpyDeviceToHost));
     std::fill(raw.begin(), raw.end(), 0.0f);
     if (sl != 0xFFFFFFFFu)         // slot_L is node-major: plane q = node * nlights + light, chunk_ slots in this one-sample pass
         for (size_t q = 0; q < (size_t)nodes_per_sample * nl; ++q)
-            HIP_TRY(hipMemcpy(raw.data() + 3 * q, slices_[0].d_slot_L + 3 * (q * chunk_ + sl), 12, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(color3, d_debug_color_, 12, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(raw.data() + 3 * q, slices_[0].d_slot_L.get() + 3 * (q * chunk_ + sl), 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(color3, d_debug_color_.get(), 12, hipMemcpyDeviceToHost));
     for (uint32_t nd = 0; nd < nodes_per_sample; ++nd) {
         float acc[3] = { 0.0f, 0.0f, 0.0f };
         for (uint32_t li = 0; li < nlights_; ++li)

@@ -9,6 +9,7 @@
 #include "../../include/mi355rt.h"
 #include "bvh.hpp"
 #include "camera.hpp"
+#include "device_buffer.hpp"
 #include "device_types.hpp"
 #include "scene.hpp"
 
@@ -35,7 +36,7 @@ public:
     uint32_t slot_rows() const;                                         // rows of one rank's slot: ceil(stripes / world) * stripe_rows
     uint32_t rows_of_rank(uint32_t rank) const;
     bool gather_prepare(bool root);                                     // root: world slots, others: their own slot
-    uint32_t* gather_slot(uint32_t rank) { return d_gather_ ? d_gather_ + (gather_is_root_ ? (size_t)rank : 0) * slot_rows() * cfg.width : nullptr; }
+    uint32_t* gather_slot(uint32_t rank) { return d_gather_ ? d_gather_.get() + (gather_is_root_ ? (size_t)rank : 0) * slot_rows() * cfg.width : nullptr; }
     bool tonemap_to_gather_slot();                                      // own rows, packed, into the own slot (on the handle's stream)
     bool finish_gather(uint32_t* host_out, size_t n);                   // root: slots -> frame (+ copy to the host when host_out != null)
     hipStream_t stream() const { return stream_; }
@@ -46,7 +47,7 @@ public:
     void comm_destroy();
     uint32_t comm_ranks();                                              // ncclCommCount of the live communicator, 0 without one
     long check_guards();                                                // MI355RT_DEBUG_GUARD: corrupted guard bytes behind the pass buffers
-    size_t hbm_allocated_bytes() const;                                 // device memory this handle holds (scene, film, pass buffers, gather slots)
+    size_t hbm_allocated_bytes() const { return hbm_bytes_; }           // device memory this handle holds: every DeviceBuffer that counts into hbm_bytes_
     bool debug_gather_rate(uint32_t table_nodes, uint32_t steps, double out[3]);
     bool debug_slab(const float* inv_rays6, const float* cubes6, size_t n, uint8_t* hit, float* tmin);
     bool film_stat(bool variances, float* rgb);
@@ -69,12 +70,12 @@ public:
     uint32_t nodes_per_sample = 1;
     uint32_t level_first[kMaxLevels + 1] = { 0 };
     std::vector<std::array<float, 6>> cull_boxes_;   // top BVH subtree boxes for primary-chunk culling
-    uint32_t* d_cull_mask_ = nullptr;    // kCullGrid x kCullGrid coverage bits (device_types.hpp), rebuilt when the camera changes
+    size_t hbm_bytes_ = 0;               // device bytes held by the DeviceBuffers below (declared before them: they count into it until they are destroyed)
+    DeviceBuffer<uint32_t> d_cull_mask_; // kCullGrid x kCullGrid coverage bits (device_types.hpp), rebuilt when the camera changes
     std::vector<float> mask_key_;        // the camera the mask on the device was built for (rot, origin, max_x, max_y); empty: none
     float mask_dom_[4] = { 0, 0, 0, 0 }; // its domain: x0, y0, 1 / cell width, 1 / cell height
     bool mask_valid_ = false;
-    uint2* d_tile_ofs_ = nullptr; uint2* d_tile_entries_ = nullptr;     // screen-space triangle bins of the primary rays (device_types.hpp), rebuilt with the mask
-    size_t tile_entries_cap_ = 0, tile_ofs_cap_ = 0;
+    DeviceBuffer<uint2> d_tile_ofs_, d_tile_entries_;     // screen-space triangle bins of the primary rays (device_types.hpp), rebuilt with the mask
     std::vector<float> bins_key_;        // camera + layout the bins on the device were built for
     uint32_t bins_layout_[3] = { 0, 0, 0 };   // tile_cols, tile_rg, tile_nblocks
     bool bins_valid_ = false;
@@ -103,25 +104,25 @@ private:
         hipEvent_t done = nullptr;
         hipEvent_t ev_ready = nullptr, ev_traced = nullptr;   // slice stream -> trace stream -> slice stream, per round (render())
         std::vector<uint32_t> rows;              // this slice's rows (host copy of d_rows)
-        uint32_t* d_rows = nullptr;
-        uint32_t* d_ctrl = nullptr;              // per round: chunk cursors
+        DeviceBuffer<uint32_t> d_rows;
+        DeviceBuffer<uint32_t> d_ctrl;           // per round: chunk cursors
         bool ctrl_clean = true;                  // the cursors are zero (creation, or the last pass's resolve kernel left them so)
-        void* d_queue[2] = { nullptr, nullptr };
-        uint32_t* d_chunk_counts[2] = { nullptr, nullptr };   // rays per chunk in each queue
-        void* d_hits = nullptr;
-        uint32_t* d_hit_prim = nullptr;          // hit records of the round being processed (16 B per queue record)
-        float* d_slot_L = nullptr;
-        void* d_slot_ps = nullptr;               // light-term slot -> (pixel, sample number) of its sample (uint2)
-        uint32_t* d_sample_slot = nullptr;       // primary sample -> slot of its light terms (0xFFFFFFFF: the primary ray missed)
-        uint32_t* d_live = nullptr;              // live-chunk lists of the pass, one per work cursor (DPass::live)
-        uint32_t* d_block_culled = nullptr;      // cached culling verdicts of the pass's pixel blocks (DPass::block_culled) for the camera / layout of cull_key
-        size_t block_culled_cap = 0;
+        // the pass buffers, sized for `capacity` samples (ensure_pass_capacity)
+        DeviceBuffer<> d_queue[2];
+        DeviceBuffer<uint32_t> d_chunk_counts[2];   // rays per chunk in each queue
+        DeviceBuffer<> d_hits;
+        DeviceBuffer<uint32_t> d_hit_prim;       // hit records of the round being processed (16 B per queue record)
+        DeviceBuffer<float> d_slot_L;
+        DeviceBuffer<> d_slot_ps;                // light-term slot -> (pixel, sample number) of its sample (uint2)
+        DeviceBuffer<uint32_t> d_sample_slot;    // primary sample -> slot of its light terms (0xFFFFFFFF: the primary ray missed)
+        DeviceBuffer<uint32_t> d_live;           // live-chunk lists of the pass, one per work cursor (DPass::live)
+        DeviceBuffer<uint32_t> d_block_culled;   // cached culling verdicts of the pass's pixel blocks (DPass::block_culled) for the camera / layout of cull_key
         std::vector<float> cull_key;
         size_t capacity = 0;                     // samples
         size_t queue_records = 0;
         size_t count_entries = 0;                // entries of each d_chunk_counts array
-        size_t bytes = 0;                        // device memory of this slice's pass buffers
-        std::vector<const uint8_t*> guards;      // MI355RT_DEBUG_GUARD: the 0xA5-filled tails of the pass buffers
+        template <class F> void for_each_pass_buffer(F f) { f(d_queue[0]); f(d_queue[1]); f(d_chunk_counts[0]); f(d_chunk_counts[1]); f(d_hits); f(d_hit_prim); f(d_slot_L); f(d_slot_ps); f(d_sample_slot); f(d_live); }
+        void release_pass_buffers() { for_each_pass_buffer([](auto& b) { b.reset(); }); capacity = 0; }
     };
     bool ensure_pass_capacity(Slice& sl, size_t nsamples);
     void free_pass_buffers();
@@ -149,7 +150,8 @@ private:
     bool rects_ok_ = false;
     void collect_cull_boxes();
     void build_sample_table(std::vector<float>& table4);
-    template <class T> bool upload(T*& dptr, const void* src, size_t bytes);
+    template <class T> bool upload(DeviceBuffer<T>& buf, const void* src, size_t bytes);
+    template <class T> bool upload(T*& dptr, const void* src, size_t bytes);     // a scene array: owned by scene_bufs_
 
     int num_cus_ = 0;
     hipStream_t trace_stream_ = nullptr;         // the trace launches of a multi-slice frame, round by round
@@ -158,38 +160,37 @@ private:
     std::vector<hipEvent_t> ev_pool_;
     size_t ev_used_ = 0;
     std::vector<uint8_t> ev_secondary_;  // per event pair: the launch traced secondary rays (rounds >= 1)
-    std::vector<void*> allocs_;
-    size_t alloc_bytes_ = 0;             // bytes behind allocs_ (scene, acceleration structures, film, row lists, cursors)
+    std::vector<DeviceBuffer<>> scene_bufs_;   // scene and acceleration structures (dscene_ points into them)
 
     DScene dscene_{};
-    float* d_film_sum_ = nullptr; float* d_film_sumsq_ = nullptr; uint32_t* d_film_n_ = nullptr;
-    uint32_t* d_owned_rows_ = nullptr; uint32_t* d_all_rows_ = nullptr; uint32_t* d_tmp_rows_ = nullptr;
-    uint32_t* d_ldr_ = nullptr;
-    uint32_t* h_ldr_ = nullptr;          // pinned host mirror of d_ldr_ (get_tonemapped_pixels)
+    DeviceBuffer<float> d_film_sum_, d_film_sumsq_; DeviceBuffer<uint32_t> d_film_n_;
+    DeviceBuffer<uint32_t> d_owned_rows_, d_all_rows_, d_tmp_rows_;
+    DeviceBuffer<uint32_t> d_ldr_;
+    PinnedBuffer<uint32_t> h_ldr_;       // host mirror of d_ldr_ (get_tonemapped_pixels)
     std::vector<uint8_t> ldr_dirty_;     // per row: film changed since the row was last tone-mapped into d_ldr_ / h_ldr_
     hipEvent_t ev_tonemap_ = nullptr, ev_gather_ = nullptr;
-    uint32_t* d_gather_ = nullptr;       // gather slots (see gather_prepare)
+    DeviceBuffer<uint32_t> d_gather_;    // gather slots (see gather_prepare)
     bool gather_is_root_ = false;
     void* comm_ = nullptr;               // ncclComm_t
     bool counts_pending_ = false;        // the last call was an asynchronous 50-row frame: counters not fetched yet
     uint64_t pending_primary_ = 0;
     bool pending_timed_ = false;         // the pending call was a whole frame: its HIP-event time is read with the counters
-    DCounters* d_counters_ = nullptr;
+    DeviceBuffer<DCounters> d_counters_;
     // Speculation of the drop-in loop (trace_frame_additive): the NEXT 50-row frame is launched right behind the one just asked for, so that the device
     // traces it while the host reads out the current one (main.rs:197-207 alternates the two calls; one frame keeps the chip busy for 0.25 ms of latency,
     // not of work).  The rows it changes are backed up first; a next call that is not the predicted one (camera moved, film cleared, anything else
     // touched) puts them back.  Read-outs of the finished frame run on read_stream_, beside the speculative launch.
     struct Speculation { bool valid = false; uint32_t row = 0, first = 0, total = 0, next_row = 0; std::vector<float> cam_key; uint64_t seed = 0; uint32_t flags = 0; } spec_;
-    DCounters* d_counters_spec_ = nullptr; DCounters* h_counters_spec_ = nullptr;
-    float* d_bk_sum_ = nullptr; float* d_bk_sumsq_ = nullptr; uint32_t* d_bk_n_ = nullptr;
+    DeviceBuffer<DCounters> d_counters_spec_; PinnedBuffer<DCounters> h_counters_spec_;
+    DeviceBuffer<float> d_bk_sum_, d_bk_sumsq_; DeviceBuffer<uint32_t> d_bk_n_;
     hipStream_t read_stream_ = nullptr;
     hipEvent_t ev_call_done_ = nullptr, ev_spec_done_ = nullptr;      // behind the kernel (and the counters' copy) of the frame last asked for / of the speculative one
     bool call_done_valid_ = false;        // ev_call_done_ marks the last 50-row frame: read-outs wait for it, not for the stream
     uint64_t spec_launched_ = 0, spec_adopted_ = 0;
     bool settle_speculation();            // put the speculative frame's rows back (if one is out)
     bool launch_fused_window(uint32_t first, uint32_t total, const DCamera& cam, DCounters* dcounters);
-    DCounters* h_counters_ = nullptr;    // pinned host mirror (queue_counts_copy)
-    float* d_debug_color_ = nullptr;
+    PinnedBuffer<DCounters> h_counters_; // host mirror (queue_counts_copy)
+    DeviceBuffer<float> d_debug_color_;
     static constexpr uint32_t kMaxSlices = 8;
     Slice slices_[kMaxSlices];
     uint32_t rows_assigned_for_ = 0;     // number of slices the row lists were last split into

@@ -370,6 +370,35 @@ def test_no_launch_writes_past_a_pass_buffer(pkg, scenes, monkeypatch):
     assert rt.debug_check_guards() == 0
 
 
+def test_hbm_allocated_bytes_counts_every_buffer_the_handle_keeps(pkg, scenes, monkeypatch):
+    """hbm_allocated_bytes is the device memory the handle holds.  Of two handles that run the same three 50-row frames, the one that
+    speculated also holds the backups of the next frame's rows (sum, sum of squares, count: 28 B per pixel) and a second set of
+    counters.  The temporaries of the one-shot calls are neither counted nor kept."""
+    w, h = 1024, 768
+    handles = []
+    for speculate in (True, False):
+        if speculate:
+            monkeypatch.delenv("MI355RT_NO_SPECULATE", raising=False)
+        else:
+            monkeypatch.setenv("MI355RT_NO_SPECULATE", "1")        # read on every call: set while this handle's frames run
+        rt = make(pkg, scenes, "thai2", w, h, seed=2)
+        for _ in range(3):
+            assert rt.trace_frame_additive() == 50 * w
+        rt.last_counts()
+        handles.append(rt)
+    monkeypatch.delenv("MI355RT_NO_SPECULATE")
+    spec, plain = handles
+    assert spec.debug_speculation()[0] > 0 and plain.debug_speculation() == (0, 0)
+    held = spec.hbm_allocated_bytes()
+    assert held - plain.hbm_allocated_bytes() >= 50 * w * 28
+    rng = np.random.default_rng(5)
+    rays = np.concatenate([rng.uniform(-1, 1, (4096, 3)), rng.normal(size=(4096, 3))], axis=1).astype(np.float32)
+    spec.intersect_rays(rays)
+    spec.film.get_pixels()
+    spec.debug_slab([[2, 0, 0] + inv([-1, 0.1, 0.1])], [CUBE])
+    assert spec.hbm_allocated_bytes() == held
+
+
 def test_render_async_is_the_same_frame_queued(pkg, scenes):
     """mi355rt_render_async queues the frame and returns; last_counts / any read-out waits.  Two queued frames + a read-out give the
     film and the counters of two synchronous frames, bit for bit; a queued frame followed by film.clear() and another queued frame
