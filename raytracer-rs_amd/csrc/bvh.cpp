@@ -24,8 +24,7 @@ struct Box {
 
 struct TmpNode { Box box; int32_t left = -1, right = -1; uint32_t first = 0, count = 0; uint32_t depth = 0; };
 
-static uint32_t g_max_leaf = kBvhMaxLeaf;
-static float g_trav_cost = 0.5f;
+constexpr float kTravCost = 0.5f;       // SAH cost of a traversal step, in triangle tests; with kBvhMaxLeaf, measured: smaller leaves win (profiles/r01_notes.md)
 
 struct Builder {
     const float* verts;
@@ -37,7 +36,7 @@ struct Builder {
     static uint32_t levels_needed(uint32_t n)
     {
         uint32_t l = 0;
-        while ((g_max_leaf << l) < n) ++l;
+        while ((kBvhMaxLeaf << l) < n) ++l;
         return l;
     }
 
@@ -76,10 +75,10 @@ struct Builder {
                 }
             }
         }
-        if (count <= g_max_leaf) {
+        if (count <= kBvhMaxLeaf) {
             // leaf unless the split is clearly cheaper (traversal step ~ 1.5 triangle tests)
             float leaf_cost = node.box.half_area() * (float)count;
-            float split_cost = best_axis >= 0 ? best_cost + g_trav_cost * node.box.half_area() : 3.4e38f;
+            float split_cost = best_axis >= 0 ? best_cost + kTravCost * node.box.half_area() : 3.4e38f;
             if (!(split_cost < leaf_cost)) return idx;
         }
         uint32_t mid;
@@ -224,23 +223,10 @@ uint32_t half_bits_directed(float x, bool up)
     }
     return b;
 }
-// experiment knob (profiles/r02_notes.md): MI355RT_BOX_EXTRA_ULPS=n moves every bound n more half-precision steps outward —
-// how much do the node visits per ray depend on the quantisation of the boxes?
-uint32_t step_outward(uint32_t b, bool up, int n)
-{
-    for (int i = 0; i < n; ++i) {
-        if ((b & 0x7FFFu) >= 0x7BFFu) break;
-        if ((b & 0x7FFFu) == 0) b = up ? 0x0001u : 0x8001u;
-        else if (((b & 0x8000u) == 0) == up) b += 1;
-        else b -= 1;
-    }
-    return b;
-}
 void pack_box(const Box& box, float pad, uint32_t out[3])
 {
-    static const int extra = [] { const char* e = getenv("MI355RT_BOX_EXTRA_ULPS"); return e ? atoi(e) : 0; }();
     for (int a = 0; a < 3; ++a)
-        out[a] = step_outward(half_bits_directed(box.mn[a] - pad, false), false, extra) | (step_outward(half_bits_directed(box.mx[a] + pad, true), true, extra) << 16);
+        out[a] = half_bits_directed(box.mn[a] - pad, false) | (half_bits_directed(box.mx[a] + pad, true) << 16);
 }
 
 }  // namespace
@@ -248,9 +234,6 @@ void pack_box(const Box& box, float pad, uint32_t out[3])
 void build_bvh(const float* tri_verts, const uint32_t* tri_geom, uint32_t ntri, Bvh& out)
 {
     out = Bvh();
-    g_max_leaf = kBvhMaxLeaf; g_trav_cost = 0.5f;   // measured: smaller leaves win (profiles/r01_notes.md)
-    if (const char* e = std::getenv("MI355RT_MAX_LEAF")) { int v = std::atoi(e); if (v >= 1 && v <= 8) g_max_leaf = (uint32_t)v; }
-    if (const char* e = std::getenv("MI355RT_TRAV_COST")) { float v = (float)std::atof(e); if (v >= 0.0f) g_trav_cost = v; }
     if (ntri == 0) {
         // one empty leaf is not representable (count >= 1): a degenerate triangle that can never
         // be hit (|det| < EPSILON) keeps the kernels free of an "empty scene" special case
@@ -295,29 +278,16 @@ void build_bvh(const float* tri_verts, const uint32_t* tri_geom, uint32_t ntri, 
     float pad = std::max(diag * 2e-5f, 1e-6f);
 
     // Numbering of the inner nodes = their place in memory: breadth-first (the top of the tree has the lowest indices).
-    // MI355RT_NODE_LAYOUT=area numbers them by descending box surface instead (a priority queue from the root: the first N nodes are
-    // the N a ray most probably visits).  Measured for the trace kernels (profiles/r03_notes.md): by surface +0.2 ms per frame, a treelet
+    // Measured for the trace kernels (profiles/r03_notes.md): numbering by descending box surface +0.2 ms per frame, a treelet
     // layout (parent / children / grandchild in one 128-byte line) +-0 — which lines a fetch touches is not what bounds them.
     std::vector<int32_t> inner_index(b.tmp.size(), -1);
     std::vector<int32_t> bfs;                       // layout order: tmp-node per slot
-    const char* layout_env = std::getenv("MI355RT_NODE_LAYOUT");
-    const bool by_area = layout_env && std::strcmp(layout_env, "area") == 0;
-    if (b.tmp[root].left >= 0 && !by_area) {
+    if (b.tmp[root].left >= 0) {
         std::queue<int32_t> q; q.push(root);
         while (!q.empty()) {
             int32_t n = q.front(); q.pop();
             inner_index[n] = (int32_t)bfs.size(); bfs.push_back(n);
             for (int32_t c : { b.tmp[n].left, b.tmp[n].right }) if (b.tmp[c].left >= 0) q.push(c);
-        }
-    } else if (b.tmp[root].left >= 0) {
-        auto surface = [&](int32_t n) { const Box& x = b.tmp[n].box; const float dx = x.mx[0] - x.mn[0], dy = x.mx[1] - x.mn[1], dz = x.mx[2] - x.mn[2]; return dx * dy + dy * dz + dz * dx; };
-        typedef std::pair<float, int32_t> Item;                           // (surface, -node): ties in creation order
-        std::priority_queue<Item> q;
-        q.push(Item(surface(root), -root));
-        while (!q.empty()) {
-            const int32_t n = -q.top().second; q.pop();
-            inner_index[n] = (int32_t)bfs.size(); bfs.push_back(n);
-            for (int32_t c : { b.tmp[n].left, b.tmp[n].right }) if (b.tmp[c].left >= 0) q.push(Item(surface(c), -c));
         }
     }
     auto emit_leaf = [&](const TmpNode& n) -> int32_t {

@@ -66,7 +66,7 @@ struct DCamera {
     // screen rectangle of some triangle touches it.  A chunk whose footprint touches no set cell cannot hit anything.  null: first stage only.
     const uint32_t* cull_mask;
     float mask_x0, mask_y0, mask_inv_cx, mask_inv_cy;      // cell (i, j) = floor((dir_x - mask_x0) * mask_inv_cx), floor((dir_y - mask_y0) * mask_inv_cy)
-    // Screen-space triangle bins for the primary rays (round 3; kernels.hip, raster_kernel): the 64 samples a wave takes together are a tile of
+    // Screen-space triangle bins for the primary rays (round 3; kernels.hip, raster_tile): the 64 samples a wave takes together are a tile of
     // tile_cols columns x tile_rg rows; tile (row / tile_rg) * tile_nblocks + column / tile_cols lists every triangle a primary ray of the tile can
     // hit, nearest first.  null: no bins (the primary rays walk the BVH).
     const uint2* tile_ofs;        // per tile: x = first entry, y = number of entries
@@ -100,17 +100,11 @@ struct DPass {
     uint32_t nchunks;         // ceil(nsamples / chunk)
     uint32_t region;          // queue records reserved per chunk = chunk * worst-case records per sample
     uint32_t stack_depth;     // traversal stack rows in LDS (BVH max depth + 1)
-    uint32_t leaf_threshold;  // trace kernel: run the triangle code once this many lanes wait at a leaf
-    uint32_t refill_threshold; // trace kernel: refill idle lanes once this many are idle
-    uint32_t ncursors;        // trace kernel: number of work cursors (pull mode 4)
-    uint32_t pull_group;      // pull mode 4: consecutive chunks handed out per atomic
-    uint32_t pull_mode;       // work distribution: 4 = cursors (default), 2 = static striding, 0 = one cursor
     uint32_t list_cap;        // shade kernel: LDS hit-list entries per wave (max radiance rays per chunk)
-    uint32_t tail_chunks;     // trace kernel: the last tail_chunks chunks of every cursor's sequence are handed out in parts (host: chunks per wave; the launcher scales it by the waves per cursor)
-    uint32_t tail_split_shift; // log2 of the parts a tail chunk is handed out in (0: whole chunks everywhere)
+    uint32_t tail_chunks;     // trace kernel: the last tail_chunks chunks of every cursor's sequence are handed out in parts (set by the launcher: 2 per wave of the grid)
     // Live chunks (round 3).  Most chunks of a pass hold no ray after the primary round (thai2: 70 % — culled, or nothing hit), and every later launch
     // paid a pull, a count load and a loop set-up for each of them (1.35 ms per frame with every chunk empty).  The primary shade launch appends
-    // every chunk it leaves rays in to the list of cursor (chunk % ncursors): live[k * live_cap ...], length in live_count[k * 16384 + kLiveCountOffset];
+    // every chunk it leaves rays in to the list of cursor (chunk % kMaxCursors): live[k * live_cap ...], length in live_count[k * 16384 + kLiveCountOffset];
     // the launches of the later rounds hand out list entries instead of chunk numbers (pull_chunk).  null: every launch walks all chunks.
     // Cached culling verdicts (round 3): whether a chunk is culled depends on its pixels, not on its sample numbers, and a pass whose sample groups are
     // whole numbers of chunks repeats the same pixel blocks in every group.  block_culled[chunk % cull_blocks] != 0: the chunk's primary samples all miss

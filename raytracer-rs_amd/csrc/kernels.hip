@@ -47,85 +47,60 @@ typedef const uint32_t __attribute__((address_space(4))) * const_u1_ptr;    // c
 constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / 64;
 constexpr uint32_t kMiss = 0xFFFFFFFFu;
-#ifndef MI355RT_FUSED_FENCE_AGENT
-#define MI355RT_FUSED_FENCE_AGENT 0
-#endif
-#ifndef MI355RT_PRIMARY_BLOCKS
-#define MI355RT_PRIMARY_BLOCKS 7                // blocks per CU the primary trace kernel is compiled for: 69 VGPRs; 8 blocks = 64 VGPRs + 20 B of scratch, measured in profiles/r03_notes.md
-#endif
+constexpr int kPrimaryBlocks = 7;              // blocks per CU the primary trace kernel is compiled for: 69 VGPRs; 8 blocks = 64 VGPRs + 20 B of scratch, measured in profiles/r03_notes.md
 #ifndef MI355RT_WIDE_BLOCKS
 #define MI355RT_WIDE_BLOCKS 5                   // blocks per CU the trace kernels are compiled for when they walk the 4-wide tree (deeper stacks: ~32 LDS rows per block)
 #endif
-#ifndef MI355RT_CONFIRM_BLOCKS
-#define MI355RT_CONFIRM_BLOCKS 5               // blocks per CU the confirm kernel is compiled for (A/B knob, profiles/r02_notes.md)
-#endif
-#ifndef MI355RT_SHADE_P_BLOCKS
-#define MI355RT_SHADE_P_BLOCKS 5               // blocks per CU the shade kernels are compiled for and launched with (A/B knobs)
-#endif
-#ifndef MI355RT_SHADE_PW_BLOCKS
-#define MI355RT_SHADE_PW_BLOCKS 4              // primary shade kernel with the confirm walk inside: 128 VGPRs, no scratch (5 blocks: 80 B of scratch, 5 % slower)
-#endif
-#ifndef MI355RT_SHADE_SW_BLOCKS
-#define MI355RT_SHADE_SW_BLOCKS 5              // secondary shade kernel with the confirm walk of the radiance hits inside
-#endif
-#ifndef MI355RT_SHADE_S_BLOCKS
-#define MI355RT_SHADE_S_BLOCKS 7
-#endif
-#ifndef MI355RT_SHADE_PULL
-#define MI355RT_SHADE_PULL 0                   // 0: like the trace kernel (ps.pull_mode); 2: static striding
-#endif
-constexpr uint32_t kShadePullMode = MI355RT_SHADE_PULL;
-#ifndef MI355RT_CONFIRM_PULL
-#define MI355RT_CONFIRM_PULL 0                 // 0: like the trace kernel (ps.pull_mode); 2: static striding (A/B knob)
-#endif
-constexpr uint32_t kConfirmPullMode = MI355RT_CONFIRM_PULL;
-constexpr bool kFusedFenceAgent = MI355RT_FUSED_FENCE_AGENT != 0;      // A/B knob of the build (see phase_fence)
-#ifndef MI355RT_INNER_STEPS
-#define MI355RT_INNER_STEPS 2
-#endif
-constexpr int kInnerStepsPerIteration = MI355RT_INNER_STEPS;     // measured: 1 -> 2 takes 9 % off the trace kernel, 3 and 4 add nothing
+constexpr int kConfirmBlocks = 5;              // blocks per CU the confirm kernel is compiled for (profiles/r02_notes.md)
+// blocks per CU the shade kernels are compiled for and launched with: P / S primary / secondary, W with the confirm walk inside
+constexpr int kShadePBlocks = 5;
+constexpr int kShadePWBlocks = 4;              // 128 VGPRs, no scratch (5 blocks: 80 B of scratch, 5 % slower)
+constexpr int kShadeSWBlocks = 5;
+constexpr int kShadeSBlocks = 7;
+constexpr int kInnerStepsPerIteration = 2;     // measured: 1 -> 2 takes 9 % off the trace kernel, 3 and 4 add nothing
+// trace kernels: run the triangle code once this many lanes of the wave wait at a leaf (profiles/r02_notes.md)
+constexpr uint32_t kLeafThreshold = 16;
+// trace kernels: refill idle lanes once this many are idle (profiles/r01_notes.md: 16 -> 24 idle lanes, trace 19.4 -> 19.1 ms).  The primary launch
+// refills later: its rays are neighbours on the screen, and the more of them start together the more lanes of a quad share the lines they fetch
+// (cache-line accesses of the launch at 8 / 24 / 48 / 64 idle lanes: 1.48 / 1.21 / 1.03 / 0.94e10 per 7 frames, profiles/r03_notes.md); secondary
+// rays do not gain from it (5.8e10 at 24 and at 48).  The fused 50-row kernel refills at kRefillThreshold in every round.
+constexpr uint32_t kRefillThreshold = 24;
+constexpr uint32_t kRefillPrimary = 48;
 
 // One device word sustains only ~88 atomics/us on this chip: the statistics counters that every wave
 // flushes into exist in kShards copies (the host adds them up), and the work cursor is touched
 // sparingly (pull_chunk).
 __device__ __forceinline__ uint32_t global_wave_id() { return blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); }
 
-// Pull the next chunk for this wave (wave-uniform).
-//   mode 4 (default): dynamic, ps.ncursors (64) cursors that lie 64 KiB apart.  Cursor k hands out the
-//     chunks k, k + ncursors, ... (every cursor sees a uniform sample of the image, so they run dry
-//     together); a wave starts on cursor (wave % ncursors) and moves on to the next one when its own is
-//     dry, at most 8 of them.  Returning atomics to ONE word — or to several words in one cache line, or
-//     256 B apart — serialise at ~88/us for the whole chip: with one cursor the 131 072 chunk pulls of a
-//     launch put a 1.5 ms floor under every trace launch.
-//   mode 2: static striding, no atomics (wave w takes chunks w, w + nwaves, ...).  Measured on thai2:
-//     mean wave busy 2.56 ms but last wave done at 3.89 ms — a third of the machine idles on imbalance.
-//   mode 0: one cursor (kept for the A/B in profiles/r01_notes.md).
+// Pull the next chunk for this wave (wave-uniform): dynamic, kMaxCursors (64) cursors that lie 64 KiB apart.  Cursor k hands out
+// the chunks k, k + 64, ... (every cursor sees a uniform sample of the image, so they run dry together); a wave starts on cursor
+// (wave % 64) and moves on to the next one when its own is dry, at most 8 of them.  Returning atomics to ONE word — or to several
+// words in one cache line, or 256 B apart — serialise at ~88/us for the whole chip: with one cursor the 131 072 chunk pulls of a
+// launch put a 1.5 ms floor under every trace launch.  Static striding (no atomics) measured on thai2: mean wave busy 2.56 ms but
+// last wave done at 3.89 ms — a third of the machine idles on imbalance (profiles/r01_notes.md).
 // Tried and dropped: a relaxed agent-scope load in front of the atomic (2.5x slower), 3/4 static + a
 // dynamic rest, several chunks per pull, draining more than 8 cursors, heaviest-chunks-first order.
 constexpr uint32_t kCursorStride = kCtrlWordsPerRound / kMaxCursors;   // u32 words between cursors (64 KiB): atomics to nearby lines serialise on one memory channel
+constexpr uint32_t kMaxTries = 8u;                                     // cursors a wave drains before it stops
 static_assert(kCursorStride == 16384 && kShadeCursorOffset == 2 * kConfirmCursorOffset && kLiveCountOffset == 3 * kConfirmCursorOffset, "cursor layout (device_types.hpp) and the reset loop of resolve_kernel");
-struct PullState { bool first = true; uint32_t shard = 0u, tries = 0u, left = 0u, part = 0xFFFFFFFFu; };
-// the live-chunk lists of a pass (DPass::live): cursor k hands out the entries of list k instead of the chunk numbers k, k + ncursors, ...
+struct PullState { bool first = true; uint32_t shard = 0u, tries = 0u, part = 0xFFFFFFFFu; };
+// the live-chunk lists of a pass (DPass::live): cursor k hands out the entries of list k instead of the chunk numbers k, k + 64, ...
 struct LiveLists { const uint32_t* list = nullptr; const uint32_t* count = nullptr; uint32_t cap = 0u; };
-// (the build knobs that make the shade / confirm launches stride over ALL chunks switch the lists off for every launch: a launch that visits chunks the
-// others skipped would read ray counts nobody wrote)
-constexpr bool kLiveListsOk = kShadePullMode == 0u && kConfirmPullMode == 0u;
-__device__ __forceinline__ LiveLists live_lists(const DPass& ps) { LiveLists l; if (kLiveListsOk) { l.list = ps.live; l.count = ps.live_count; l.cap = ps.live_cap; } return l; }
+__device__ __forceinline__ LiveLists live_lists(const DPass& ps) { LiveLists l; l.list = ps.live; l.count = ps.live_count; l.cap = ps.live_cap; return l; }
 constexpr uint32_t kWholeChunk = 0xFFFFFFFFu;
 
-// tail / split (trace kernels only; 0 / 1 elsewhere): the LAST `tail` chunks of every cursor's sequence are handed out in `split`
-// parts (st.part = 0 .. split-1; kWholeChunk otherwise), several waves sharing a chunk.  A persistent launch ends when its slowest
+// tail (trace kernels only; 0 elsewhere): the LAST `tail` chunks of every cursor's sequence are handed out in 1 << kTailSplitShift
+// parts (st.part = 0 .. 3; kWholeChunk otherwise), several waves sharing a chunk.  A persistent launch ends when its slowest
 // wave does, and with whole chunks the waves run out of work up to ~1.5 chunk durations apart — a fifth of a launch of 8 chunks per
 // wave (one rank's share of a strong-scaled frame), a tenth of a full-size one (profiles/r03_notes.md).  Splitting only the tail keeps
 // the per-pull cost (count load, culling test, a colder start) off the bulk of the chunks.
-__device__ __forceinline__ bool pull_chunk(uint32_t* cursor, uint32_t nchunks, uint32_t mode, uint32_t ncursors, uint32_t group, PullState& st, uint32_t& chunk,
-                                           uint32_t tail = 0u, uint32_t split_shift = 0u, const LiveLists live = LiveLists())
+constexpr uint32_t kTailSplitShift = 2;
+__device__ __forceinline__ bool pull_chunk(uint32_t* cursor, uint32_t nchunks, PullState& st, uint32_t& chunk, uint32_t tail = 0u, const LiveLists live = LiveLists())
 {
-    if (mode == 4u && live.list != nullptr) {
+    if (live.list != nullptr) {
         // live lists: cursor k's sequence is list k (filled by the primary shade launch); otherwise as below
-        if (st.first) { st.first = false; st.shard = global_wave_id() % ncursors; }
-        const uint32_t max_tries = ncursors < 8u ? ncursors : 8u;
-        while (st.tries < max_tries) {
+        if (st.first) { st.first = false; st.shard = global_wave_id() % kMaxCursors; }
+        while (st.tries < kMaxTries) {
             // (lists and counts were written by an EARLIER launch: wave-uniform addresses, read through the scalar cache, which every launch starts with empty)
             const uint32_t len = ((const_u1_ptr)(uintptr_t)live.count)[(size_t)st.shard * kCursorStride + kLiveCountOffset];
             uint32_t v = 0xFFFFFFFFu;
@@ -133,55 +108,39 @@ __device__ __forceinline__ bool pull_chunk(uint32_t* cursor, uint32_t nchunks, u
             uint32_t j = v; st.part = kWholeChunk;
             if (tail != 0u && v != 0xFFFFFFFFu) {
                 const uint32_t head = len - (tail < len ? tail : len);
-                if (v >= head) { const uint32_t jj = v - head; j = head + (jj >> split_shift); st.part = jj & ((1u << split_shift) - 1u); }
+                if (v >= head) { const uint32_t jj = v - head; j = head + (jj >> kTailSplitShift); st.part = jj & ((1u << kTailSplitShift) - 1u); }
             }
             if (j < len) { chunk = ((const_u1_ptr)(uintptr_t)live.list)[(size_t)st.shard * live.cap + j]; return true; }
-            st.shard = (st.shard + 1u) % ncursors;      // dry for good
+            st.shard = (st.shard + 1u) % kMaxCursors;      // dry for good
             ++st.tries;
         }
         return false;
     }
-    if (mode == 4u) {
-        if (st.first) { st.first = false; st.shard = global_wave_id() % ncursors; }
-        else if (st.left > 0u && chunk + 1u < nchunks) { --st.left; ++chunk; return true; }     // rest of the group pulled last time
-        const uint32_t max_tries = ncursors < 8u ? ncursors : 8u;
-        while (st.tries < max_tries) {
-            uint32_t v = 0u;
-            if (lane_id() == 0) v = atomicAdd(&cursor[(size_t)st.shard * kCursorStride], 1u);
-            v = bcast_first(v);
-            if (tail != 0u && group == 1u) {
-                const uint32_t len = st.shard < nchunks ? (nchunks - st.shard + ncursors - 1u) / ncursors : 0u;     // chunks of this cursor
-                const uint32_t head = len - (tail < len ? tail : len);
-                uint32_t j = v; st.part = kWholeChunk;
-                if (v >= head) { const uint32_t jj = v - head; j = head + (jj >> split_shift); st.part = jj & ((1u << split_shift) - 1u); }
-                if (j < len) { chunk = st.shard + j * ncursors; return true; }
-            } else {
-                const uint32_t c = (st.shard + v * ncursors) * group;
-                if (c < nchunks) { chunk = c; st.left = group - 1u; return true; }
-            }
-            st.shard = (st.shard + 1u) % ncursors;      // dry for good
-            ++st.tries;
+    if (st.first) { st.first = false; st.shard = global_wave_id() % kMaxCursors; }
+    while (st.tries < kMaxTries) {
+        uint32_t v = 0u;
+        if (lane_id() == 0) v = atomicAdd(&cursor[(size_t)st.shard * kCursorStride], 1u);
+        v = bcast_first(v);
+        if (tail != 0u) {
+            const uint32_t len = st.shard < nchunks ? (nchunks - st.shard + kMaxCursors - 1u) / kMaxCursors : 0u;     // chunks of this cursor
+            const uint32_t head = len - (tail < len ? tail : len);
+            uint32_t j = v; st.part = kWholeChunk;
+            if (v >= head) { const uint32_t jj = v - head; j = head + (jj >> kTailSplitShift); st.part = jj & ((1u << kTailSplitShift) - 1u); }
+            if (j < len) { chunk = st.shard + j * kMaxCursors; return true; }
+        } else {
+            const uint32_t c = st.shard + v * kMaxCursors;
+            if (c < nchunks) { chunk = c; return true; }
         }
-        return false;
+        st.shard = (st.shard + 1u) % kMaxCursors;      // dry for good
+        ++st.tries;
     }
-    if (mode == 2u) {
-        if (st.first) { st.first = false; chunk = global_wave_id(); }
-        else chunk += gridDim.x * kWavesPerBlock;
-        return chunk < nchunks;
-    }
-    uint32_t v = 0u;
-    if (lane_id() == 0) v = atomicAdd(cursor, 1u);
-    chunk = bcast_first(v);
-    return chunk < nchunks;
+    return false;
 }
 
 // Streamed data (ray records, hit records, slot bookkeeping: written once, read once, gigabytes per pass) can be marked
-// non-temporal so that it does not evict the BVH from the L2.  MI355RT_NT is a build knob (bit 0: ray-record loads of the
-// trace kernel, 1: its hit stores, 2: the shade kernel's streams, 3: the confirm kernel's loads); see profiles/r02_notes.md.
-#ifndef MI355RT_NT
-#define MI355RT_NT 4
-#endif
-constexpr uint32_t kNT = MI355RT_NT;
+// non-temporal so that it does not evict the BVH from the L2.  kNT bit 0: ray-record loads of the trace kernel, 1: its hit
+// stores, 2: the shade kernel's streams, 3: the confirm kernel's loads.  Only the shade kernel's pay off (profiles/r02_notes.md).
+constexpr uint32_t kNT = 4;
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 template <uint32_t BIT> __device__ __forceinline__ float4 ld4(const float4* p)
 {
@@ -436,10 +395,10 @@ __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam,
     for (;;) {
         // ---- refill idle lanes from the current chunk (pull a new chunk when it runs dry)
         // A refill makes the wave wait for ray records that come from HBM, so it is done only when
-        // at least ps.refill_threshold lanes are idle (or nothing is left to do): the other waves of
+        // at least kRefillThreshold lanes are idle (or nothing is left to do): the other waves of
         // the SIMD then have enough work to cover the wait.
         unsigned long long idle = __ballot(rs.node <= kNodeFin);        // no ray, or a finished one (the two most negative codes)
-        if ((uint32_t)__popcll(idle) < ps.refill_threshold && idle != ~0ull) idle = 0ull;
+        if ((uint32_t)__popcll(idle) < (PRIMARY && !SINGLE ? kRefillPrimary : kRefillThreshold) && idle != ~0ull) idle = 0ull;
         if (COUNT && idle != 0ull) ++acc_rf;
         if (idle != 0ull) {
             if (rs.node == kNodeFin) {     // ---- results of the rays that ended since the last refill (they waited in their lanes: one store section per refill, well filled)
@@ -474,7 +433,7 @@ __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam,
                     if (!w_pull.first) { exhausted = true; break; }
                     w_pull.first = false; c = single_chunk;
                 }
-                else if (!pull_chunk(cursor, ps.nchunks, ps.pull_mode, ps.ncursors, ps.pull_group, w_pull, c, ps.tail_chunks, ps.tail_split_shift, PRIMARY ? LiveLists() : live_lists(ps))) { exhausted = true; break; }
+                else if (!pull_chunk(cursor, ps.nchunks, w_pull, c, ps.tail_chunks, PRIMARY ? LiveLists() : live_lists(ps))) { exhausted = true; break; }
                 // bcast_first: these are wave-uniform by construction; saying so keeps them in SGPRs
                 w_chunk = bcast_first(c); w_next = 0u;
                 if (PRIMARY) {
@@ -486,7 +445,7 @@ __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam,
                 else if (SINGLE) { w_nrad = single_nrad; w_ntot = single_nrad + single_nshadow; }      // from the shade phase, in registers
                 else { const uint2 n = in_counts[w_chunk]; w_nrad = bcast_first(n.x); w_ntot = w_nrad + bcast_first(n.y); }
                 if (!SINGLE && w_pull.part != kWholeChunk) {       // a part of a tail chunk: rays [part * per, (part + 1) * per) of it, per a multiple of 64
-                    const uint32_t per = ((w_ntot + (64u << ps.tail_split_shift) - 1u) >> (6u + ps.tail_split_shift)) << 6;
+                    const uint32_t per = ((w_ntot + (64u << kTailSplitShift) - 1u) >> (6u + kTailSplitShift)) << 6;
                     w_next = bcast_first(min(w_pull.part * per, w_ntot));
                     w_ntot = bcast_first(min(w_next + per, w_ntot));
                 }
@@ -521,20 +480,6 @@ __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam,
                     } else { o = mk3(r0.x, r0.y, r0.z); d = mk3(r0.w, r1.x, r1.y); }
                 }
                 ray_init(rs, o, d, shadow, sc.root);
-#ifdef MI355RT_EXP_NOSHADOW      // timing experiment (wrong results): shadow rays are not traced at all — what do they cost?
-                if (shadow) rs.node = kNodeFin;
-#endif
-#ifdef MI355RT_EXP_PATHLOADS     // timing experiment (same results): what would reading a 13-slot path record per secondary ray ADD?  Rays that start within 0.01 of each other read the same record
-                if (!PRIMARY) {
-                    const uint32_t hx = (uint32_t)(int)floorf(o.x * 100.0f) * 73856093u ^ (uint32_t)(int)floorf(o.y * 100.0f) * 19349663u ^ (uint32_t)(int)floorf(o.z * 100.0f) * 83492791u;
-                    const uint4* __restrict__ t4 = (const uint4*)sc.tris;
-                    const uint32_t b0 = hx % (sc.ntri * 3u - 16u);
-                    uint4 acc = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-                    for (uint32_t k = 0; k < 13u; ++k) { const uint4 q = t4[b0 + k]; acc.x ^= q.x; acc.y ^= q.y; acc.z ^= q.z; acc.w ^= q.w; }
-                    asm volatile("" : : "v"(acc.x), "v"(acc.y), "v"(acc.z), "v"(acc.w));
-                }
-#endif
             }
             w_next += min((uint32_t)__popcll(idle), avail);
             idle = __ballot(rs.node == kNodeIdle);
@@ -558,11 +503,8 @@ __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam,
                 if (__ballot(rs.sp >= (int)ps.stack_depth) != 0ull && lane_id() == 0) atomicOr(&counters->overflow, 2u);
             }
         }
-#ifdef MI355RT_EXP_REDESCEND     // timing experiment (same results): a secondary ray that reaches its FIRST leaf starts over at the root — what does the first descent cost, in place?
-        if (!PRIMARY) { const bool at_leaf = lane_at_leaf(rs); const bool redo = at_leaf & (rs.tri == 0u); rs.tri = at_leaf ? 1u : rs.tri; if (redo) { rs.node = sc.root; rs.sp = 0; } }
-#endif
         const unsigned long long m_leaf = __ballot(lane_at_leaf(rs));
-        if (m_leaf != 0ull && ((uint32_t)__popcll(m_leaf) >= ps.leaf_threshold || __ballot(lane_at_inner(rs)) == 0ull))
+        if (m_leaf != 0ull && ((uint32_t)__popcll(m_leaf) >= kLeafThreshold || __ballot(lane_at_inner(rs)) == 0ull))
             { leaf_pred<COUNT, CONFIRM || PRIMARY>(sc, rs, stack, kBlock, acc_tris); if (COUNT) ++acc_le; }
     }
     if (COUNT) {
@@ -586,7 +528,7 @@ __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam,
 }
 
 template <bool PRIMARY, bool COUNT, bool CONFIRM>
-__global__ __launch_bounds__(kBlock, MI355RT_WIDE ? MI355RT_WIDE_BLOCKS : PRIMARY ? MI355RT_PRIMARY_BLOCKS : 8) void trace_kernel(DScene sc, DCamera cam, DPass ps,
+__global__ __launch_bounds__(kBlock, MI355RT_WIDE ? MI355RT_WIDE_BLOCKS : PRIMARY ? kPrimaryBlocks : 8) void trace_kernel(DScene sc, DCamera cam, DPass ps,
                                                       const float4* __restrict__ in_q, const uint2* __restrict__ in_counts,
                                                       float4* __restrict__ hits, uint32_t* cursor,
                                                       float* __restrict__ slot_L, const uint32_t* __restrict__ film_n,
@@ -602,7 +544,6 @@ __global__ __launch_bounds__(kBlock, MI355RT_WIDE ? MI355RT_WIDE_BLOCKS : PRIMAR
 // through the scalar cache into SGPRs, the vector memory pipe that bounds the tree walk is not used at all, and what is left is the
 // reference's own Moller-Trumbore arithmetic (intersect.rs:62-98: same operations, same order, same tie rule as leaf_pred) at one triangle per ~70
 // vector instructions for 64 rays.  A list ends early once every lane holds a hit nearer than anything the rest of the list can offer.
-// Output: what trace_kernel<PRIMARY> writes — hit flags and hit records of the chunk's region; culled chunks are skipped alike.
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 typedef const u32x4_t __attribute__((address_space(4))) * const_u4_ptr;    // constant address space: a wave-uniform address loads through the scalar cache
@@ -653,32 +594,6 @@ __device__ __forceinline__ uint32_t raster_tile(const DScene& sc, const DCamera&
     if (sc.oct_single_leaf && bprim != kMiss &&
         !cube_contains(mk3(sc.oct_root[0], sc.oct_root[1], sc.oct_root[2]), mk3(sc.oct_root[3], sc.oct_root[4], sc.oct_root[5]), add3(o, vscale(d, bt)))) bprim = kMiss;
     return tested;
-}
-
-template <bool COUNT, bool CONFIRM>
-__global__ __launch_bounds__(kBlock) void raster_kernel(DScene sc, DCamera cam, DPass ps, float4* __restrict__ hits, uint32_t* cursor,
-                                                        const uint32_t* __restrict__ film_n, DCounters* counters)
-{
-    const int lane = lane_id();
-    unsigned long long acc_tris = 0;
-    PullState pull; uint32_t chunk = 0u;
-    while (pull_chunk(cursor, ps.nchunks, ps.pull_mode, ps.ncursors, ps.pull_group, pull, chunk)) {
-        const uint32_t n = min(ps.chunk, ps.nsamples - chunk * ps.chunk);
-        if (chunk_culled(cam, ps, chunk, n)) continue;               // the shade kernel makes the same decision
-        for (uint32_t i0 = 0; i0 < n; i0 += 64u) {
-            const uint32_t i = i0 + (uint32_t)lane;
-            const bool valid = i < n;
-            f3 o, d; float bt, bu, bv; uint32_t bprim;
-            const uint32_t tested = raster_tile(sc, cam, ps, film_n, chunk, i0, valid, o, d, bt, bu, bv, bprim);
-            if (COUNT) acc_tris += (unsigned long long)tested * (unsigned long long)__popcll(__ballot(valid));
-            if (valid) {
-                const uint32_t rec = chunk * ps.region + i;
-                st1<1>((uint32_t*)((char*)ps.hit_prim + ((size_t)rec << 2)), bprim);
-                if (bprim != kMiss) st4<1>((float4*)((char*)hits + ((size_t)rec << 4)), make_float4(bt, bu, bv, __uint_as_float(bprim)));
-            }
-        }
-    }
-    if (COUNT && lane == 0 && acc_tris) atomicAdd(&counters[global_wave_id() % kShards].tris_tested, acc_tris);
 }
 
 // ---- trace with the reference-exact octree intersector (parity path, MI355RT_FLAG_OCTREE_SEMANTICS) ----
@@ -748,9 +663,7 @@ __device__ __forceinline__ void confirm_record(const DScene& sc, const DCamera& 
     const float4 h = ld4<3>(&hits[r]);
     float t = h.x, u = h.y, v = h.z; uint32_t prim = __float_as_uint(h.w);
     const uint32_t prim_in = prim;
-#ifndef MI355RT_EXP_NOWALK          // timing experiment (wrong results): the confirm kernel's gathers and stores without the walk
     confirm_walk(sc, o, d, t, u, v, prim);
-#endif
     if (!shadow) {
         if (prim != prim_in) {
             ps.hit_prim[r] = prim;
@@ -796,7 +709,7 @@ __device__ __forceinline__ void confirm_chunk(const DScene& sc, const DCamera& c
 // batch of 64 lanes of every chunk would be mostly empty.  So a wave collects the hit records of its chunks in ONE LDS
 // list and walks 64 of them whenever it has 64 — across chunk borders (the writes are per record, in place).
 template <bool PRIMARY>
-__global__ __launch_bounds__(kBlock, MI355RT_CONFIRM_BLOCKS) void confirm_kernel(DScene sc, DCamera cam, DPass ps, const float4* __restrict__ in_q, const uint2* __restrict__ in_counts,
+__global__ __launch_bounds__(kBlock, kConfirmBlocks) void confirm_kernel(DScene sc, DCamera cam, DPass ps, const float4* __restrict__ in_q, const uint2* __restrict__ in_counts,
                                                          float4* __restrict__ hits, uint32_t* cursor, float* __restrict__ slot_L, const uint32_t* __restrict__ film_n, uint32_t shadow_only)
 {
     __shared__ uint32_t s_list[kWavesPerBlock][2][128];   // per wave: up to 127 pending entries of { record index | shadow << 31, sample index }
@@ -806,7 +719,7 @@ __global__ __launch_bounds__(kBlock, MI355RT_CONFIRM_BLOCKS) void confirm_kernel
     uint32_t cnt = 0u;                                // < 64 between the steps below
     // chunks are pulled like the trace kernel pulls them (the hits sit in a part of the image: static striding leaves waves idle)
     PullState pull; uint32_t chunk = 0u;
-    while (pull_chunk(cursor, ps.nchunks, kConfirmPullMode ? kConfirmPullMode : ps.pull_mode, ps.ncursors, ps.pull_group, pull, chunk, 0u, 0u, PRIMARY ? LiveLists() : live_lists(ps))) {
+    while (pull_chunk(cursor, ps.nchunks, pull, chunk, 0u, PRIMARY ? LiveLists() : live_lists(ps))) {
         uint32_t n_rad = 0u, n_sh = 0u;
         if (PRIMARY) {
             n_rad = min(ps.chunk, ps.nsamples - chunk * ps.chunk);
@@ -859,18 +772,8 @@ __device__ __forceinline__ void hemisphere_walk(const float4* __restrict__ table
     }
 }
 
-#ifndef MI355RT_SORT_BINS
-#define MI355RT_SORT_BINS 8                    // reflection rays of a shading batch grouped by direction: 0 off, 8 octants, 24 octant x dominant axis (A/B knob, profiles/r03_notes.md)
-#endif
-constexpr uint32_t kSortBins = MI355RT_SORT_BINS;
-__device__ __forceinline__ uint32_t dir_bin(const f3 d)
-{
-    const uint32_t oct = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
-    if (kSortBins <= 8u) return oct;
-    const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
-    const uint32_t major = ax >= ay ? (ax >= az ? 0u : 2u) : (ay >= az ? 1u : 2u);
-    return oct * 3u + major;
-}
+constexpr uint32_t kSortBins = 8;              // reflection rays of a shading batch grouped by the octant of their direction (profiles/r03_notes.md)
+__device__ __forceinline__ uint32_t dir_bin(const f3 d) { return (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u); }
 
 // Is the way from the shaded point to light li provably free?  l = light - hp (mod.rs:215).  The shadow ray of mod.rs:224-225 starts at hp + 0.01 l and
 // is searched on t in [0, 1): from 0.99 |l| in front of the light, through it, to 0.01 |l| behind it — every point of it in the direction -l (or +l)
@@ -954,11 +857,7 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
             // stores of a round — one node level — fill whole cache lines instead of 12 B of every 60)
             // The planes of node 0 (one per light) are not zeroed here: this wave writes every one of their entries itself below — the term, or the zero.
             const uint32_t planes = ps.nodes_per_sample * sc.nlights, total = cnt * 3u;
-#ifdef MI355RT_EXP_SHADE_NOZERO
-            for (uint32_t q = planes; q < planes; ++q) {
-#else
             for (uint32_t q = sc.nlights; q < planes; ++q) {
-#endif
                 float* z = slot_L + 3ull * ((size_t)q * ps.nslots + (size_t)chunk * ps.chunk);     // 16-byte aligned: nslots and ps.chunk are multiples of 4
                 float4* z4 = (float4*)z;
                 for (uint32_t k = (uint32_t)lane; k < total / 4u; k += 64u) st4<2>(&z4[k], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
@@ -989,9 +888,7 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
                 if (PRIMARY && level < ps.recursions) ps.slot_ps[slot] = make_uint2(pixel, sampleno);   // what the deeper levels hash with
                 if (WALK) {
                     float wt = h.x, wu = h.y, wv = h.z; uint32_t wprim = __float_as_uint(h.w);
-#ifndef MI355RT_EXP_SHADE_NOWALK     // timing experiments (wrong picture): what do the parts of the shade kernels cost?
                     confirm_walk(sc, o, d, wt, wu, wv, wprim);
-#endif
                     h = make_float4(wt, wu, wv, __uint_as_float(wprim));
                     active = wprim != kMiss;
                 }
@@ -1025,9 +922,6 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
                     }
                 }
                 uint32_t n_new;
-#ifdef MI355RT_EXP_SHADE_NOLIGHT
-                want = false;
-#endif
                 // a shadow ray the light's depth map proves free is never made: its term stands as written
                 const bool ray = want && !is_free;
                 skipped += (uint32_t)__popcll(__ballot(want && is_free));
@@ -1044,11 +938,7 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
                 }
             }
             // ---- reflection rays, mod.rs:146-158 + 178-196
-#ifdef MI355RT_EXP_SHADE_NOREFL
-            if (false) {
-#else
             if (level < ps.recursions) {
-#endif
                 const uint32_t k = ps.spread * (ps.recursions - level);                // num_sub_rays, mod.rs:150
                 const uint32_t index_in_level = node - ps.level_first[level];
                 // children in pairs: both first table entries are in flight before either walk starts (the walks are chains of
@@ -1068,25 +958,8 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
                             jx1 = __umulhi(b0, 65535u);
                         }
                         float4 tv0 = table[jx0], tv1 = table[jx1];
-#if defined(MI355RT_EXP_DIRCOH) && MI355RT_EXP_DIRCOH == 1      // timing experiment (wrong picture): every reflection ray of a chunk starts its table walk at the same entry
-                        jx0 = (chunk * 2654435761u) >> 17; jx1 = jx0 + 7u; tv0 = table[jx0]; tv1 = table[jx1];
-#endif
                         hemisphere_walk(table, n, jx0, tv0);
                         if (two) hemisphere_walk(table, n, jx1, tv1);
-#if defined(MI355RT_EXP_DIRCOH) && MI355RT_EXP_DIRCOH == 2      // timing experiment (wrong picture): every reflection ray of a chunk points into ONE octant (that of the first lane's normal): what would sorting a chunk's rays by octant buy at best?
-                        {
-                            const uint32_t oct = (uint32_t)__builtin_amdgcn_readfirstlane((int)((n.x < 0.0f ? 1u : 0u) | (n.y < 0.0f ? 2u : 0u) | (n.z < 0.0f ? 4u : 0u)));
-                            for (int w = 0; w < 2; ++w) {
-                                uint32_t& jx = w ? jx1 : jx0; float4& tv = w ? tv1 : tv0;
-                                for (uint32_t g = 0; g < 400u; ++g) {
-                                    const uint32_t o2 = (tv.x < 0.0f ? 1u : 0u) | (tv.y < 0.0f ? 2u : 0u) | (tv.z < 0.0f ? 4u : 0u);
-                                    if (o2 == oct && tv.x * n.x + tv.y * n.y + tv.z * n.z > 0.0f) break;
-                                    jx = jx + 1u == kSampleMax ? 0u : jx + 1u; tv = table[jx];
-                                }
-                                if (!(tv.x * n.x + tv.y * n.y + tv.z * n.z > 0.0f)) hemisphere_walk(table, n, jx, tv);
-                            }
-                        }
-#endif
                         bd0 = mk3(tv0.x, tv0.y, tv0.z); bo0 = add3(hp, sscale(0.00001f, bd0));   // mod.rs:192-193
                         bd1 = mk3(tv1.x, tv1.y, tv1.z); bo1 = add3(hp, sscale(0.00001f, bd1));
                     }
@@ -1096,23 +969,18 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
                     // (profiles/r03_notes.md: all rays of a chunk in one octant would take 14 % off the secondary trace launches).  Eight ballots per child;
                     // the order of the records inside a region means nothing to anyone else.
                     uint32_t pos[2] = { 0u, 0u };
-                    if (kSortBins != 0u) {
-                        const uint32_t key0 = active ? dir_bin(bd0) : kSortBins, key1 = (active && two) ? dir_bin(bd1) : kSortBins;
-                        uint32_t run = out_front;
-                        for (uint32_t b = 0; b < kSortBins; ++b) {
-                            const unsigned long long m0 = __ballot(key0 == b), m1 = __ballot(key1 == b);
-                            if (key0 == b) pos[0] = run + (uint32_t)__popcll(m0 & lanemask_lt());
-                            run += (uint32_t)__popcll(m0);
-                            if (key1 == b) pos[1] = run + (uint32_t)__popcll(m1 & lanemask_lt());
-                            run += (uint32_t)__popcll(m1);
-                        }
-                        out_front = run;
+                    const uint32_t key0 = active ? dir_bin(bd0) : kSortBins, key1 = (active && two) ? dir_bin(bd1) : kSortBins;
+                    for (uint32_t b = 0; b < kSortBins; ++b) {
+                        const unsigned long long m0 = __ballot(key0 == b), m1 = __ballot(key1 == b);
+                        if (key0 == b) pos[0] = out_front + (uint32_t)__popcll(m0 & lanemask_lt());
+                        out_front += (uint32_t)__popcll(m0);
+                        if (key1 == b) pos[1] = out_front + (uint32_t)__popcll(m1 & lanemask_lt());
+                        out_front += (uint32_t)__popcll(m1);
                     }
                     for (uint32_t w = 0; w < (two ? 2u : 1u); ++w) {
                         const f3 bo = w ? bo1 : bo0, bd = w ? bd1 : bd0;
                         const uint32_t child_node = w ? child1 : child0;
-                        uint32_t n_new;
-                        const uint32_t oi = kSortBins != 0u ? pos[w] : wave_append(active, out_front, n_new);
+                        const uint32_t oi = pos[w];
                         if (active && oi + out_back < ps.region + 0u) {
                             const size_t r = base + oi;
                             st4<2>(&out_q[r], make_float4(bo.x, bo.y, bo.z, bd.x));
@@ -1143,7 +1011,7 @@ __device__ __forceinline__ void flush_shade_counters(DCounters* counters, uint32
 }
 
 template <bool PRIMARY, bool WALK, bool RASTER = false>
-__global__ __launch_bounds__(kBlock, PRIMARY ? (WALK ? MI355RT_SHADE_PW_BLOCKS : MI355RT_SHADE_P_BLOCKS) : (WALK ? MI355RT_SHADE_SW_BLOCKS : MI355RT_SHADE_S_BLOCKS)) void shade_kernel(DScene sc, DCamera cam, DPass ps, uint32_t level,
+__global__ __launch_bounds__(kBlock, PRIMARY ? (WALK ? kShadePWBlocks : kShadePBlocks) : (WALK ? kShadeSWBlocks : kShadeSBlocks)) void shade_kernel(DScene sc, DCamera cam, DPass ps, uint32_t level,
                                                       const float4* __restrict__ in_q, const uint2* __restrict__ in_counts,
                                                       const float4* __restrict__ hits,
                                                       float4* __restrict__ out_q, uint2* __restrict__ out_counts, uint32_t* cursor,
@@ -1157,13 +1025,13 @@ __global__ __launch_bounds__(kBlock, PRIMARY ? (WALK ? MI355RT_SHADE_PW_BLOCKS :
     unsigned long long acc_bounce = 0, acc_shadow = 0, acc_hits = 0, acc_tris = 0;
     // chunks are pulled from the round's cursors: the hits sit in a part of the image, culled / empty chunks cost nothing
     PullState pull; uint32_t chunk = 0u;
-    while (pull_chunk(cursor, ps.nchunks, kShadePullMode ? kShadePullMode : ps.pull_mode, ps.ncursors, ps.pull_group, pull, chunk, 0u, 0u, PRIMARY ? LiveLists() : live_lists(ps))) {
+    while (pull_chunk(cursor, ps.nchunks, pull, chunk, 0u, PRIMARY ? LiveLists() : live_lists(ps))) {
         uint32_t o_rad, o_sh;
         shade_chunk<PRIMARY, LinearList, WALK, RASTER>(sc, cam, ps, level, chunk, list, in_q, PRIMARY ? 0u : in_counts[chunk].x, o_rad, o_sh, hits, out_q, out_counts, slot_L, sample_slot, film_n, counters, acc_bounce, acc_shadow, acc_hits,
                                                        lds_hits, (RASTER && (ps.flags & 2u)) ? &acc_tris : nullptr);      // flags & 2: MI355RT_FLAG_COUNT_STEPS
         // a chunk that leaves the primary round with rays goes on the live list of its cursor: the later launches of the pass visit only those (DPass::live)
-        if (PRIMARY && kLiveListsOk && ps.live != nullptr && (o_rad | o_sh) != 0u && lane_id() == 0) {
-            const uint32_t k = chunk % ps.ncursors;
+        if (PRIMARY && ps.live != nullptr && (o_rad | o_sh) != 0u && lane_id() == 0) {
+            const uint32_t k = chunk % kMaxCursors;
             const uint32_t at = atomicAdd(&ps.live_count[(size_t)k * kCursorStride + kLiveCountOffset], 1u);
             ps.live[(size_t)k * ps.live_cap + at] = chunk;
         }
@@ -1268,11 +1136,7 @@ __global__ __launch_bounds__(256) void resolve_kernel(DPass ps, uint32_t width, 
 // is exactly that on gfx950 (the waves of a workgroup share the CU's cache, which stores write through): a wait, no
 // L2 write-back / invalidate.  An agent-scope fence here flushes and invalidates the XCD's whole L2 eight times per
 // wave — it made this kernel 3.5x slower (0.35 ms -> see profiles/r02_notes.md), evicting the BVH each time.
-__device__ __forceinline__ void phase_fence()
-{
-    if (kFusedFenceAgent) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-    else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-}
+__device__ __forceinline__ void phase_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
 
 __device__ __forceinline__ void resolve_chunk_1spp(const DPass& ps, uint32_t width, uint32_t nlights, uint32_t chunk, const float* slot_L, const uint32_t* sample_slot,
                                                    float* film_sum, float* film_sumsq, uint32_t* film_n)
@@ -1298,11 +1162,9 @@ __device__ __forceinline__ void resolve_chunk_1spp(const DPass& ps, uint32_t wid
     }
 }
 
-#ifndef MI355RT_FUSED_BLOCKS
-#define MI355RT_FUSED_BLOCKS 1                 // blocks per CU the fused 50-row kernel is compiled for (A/B knob: 4 = 128 VGPRs)
-#endif
+constexpr int kFusedBlocks = 1;                // blocks per CU the fused 50-row kernel is compiled for (4 blocks = 128 VGPRs)
 template <bool CONFIRM>
-__global__ __launch_bounds__(kBlock, MI355RT_FUSED_BLOCKS) void fused_pass_kernel(DScene sc, DCamera cam, DPass ps, float4* q0, float4* q1,
+__global__ __launch_bounds__(kBlock, kFusedBlocks) void fused_pass_kernel(DScene sc, DCamera cam, DPass ps, float4* q0, float4* q1,
                                                             float4* hits, float* slot_L, uint32_t* sample_slot,
                                                             float* film_sum, float* film_sumsq, uint32_t* film_n, DCounters* counters)
 {
@@ -1509,31 +1371,29 @@ static int trace_blocks_per_cu(size_t lds)
 }
 
 template <bool P, bool C, bool F>
-static hipError_t launch_trace_variant(hipStream_t stream, int num_cus, int blocks_per_cu_cap, const DScene& sc, const DCamera& cam, const DPass& ps,
+static hipError_t launch_trace_variant(hipStream_t stream, int num_cus, const DScene& sc, const DCamera& cam, const DPass& ps,
                                        const void* in_q, const void* in_counts, void* hits, uint32_t* cursor,
                                        float* slot_L, const uint32_t* film_n, DCounters* counters)
 {
     // persistent grid: as many blocks as the chip holds; waves pull chunks from `cursor`
     const size_t lds = stack_bytes(ps.stack_depth);
     const int per_cu = trace_blocks_per_cu<P, C, F>(lds);
-    int use_per_cu = per_cu;
-    if (blocks_per_cu_cap > 0 && blocks_per_cu_cap < use_per_cu) use_per_cu = blocks_per_cu_cap;      // leave room for another stream's kernels
-    if (const char* e = getenv("MI355RT_BLOCKS_PER_CU")) { int v = atoi(e); if (v >= 1 && v <= per_cu) use_per_cu = v; }   // occupancy experiment
-    // tail of every cursor's chunk sequence that is handed out in parts (pull_chunk): ps.tail_chunks comes in as "chunks per WAVE"
+    // tail of every cursor's chunk sequence that is handed out in parts (pull_chunk): kTailChunksPerWave chunks per WAVE
+    constexpr uint32_t kTailChunksPerWave = 2;
     DPass pt = ps;
-    const uint32_t waves_per_cursor = ((uint32_t)(num_cus * use_per_cu) * kWavesPerBlock + ps.ncursors - 1u) / ps.ncursors;
-    pt.tail_chunks = (ps.pull_mode == 4u && ps.pull_group == 1u && ps.tail_split_shift != 0u) ? ps.tail_chunks * waves_per_cursor : 0u;
-    hipLaunchKernelGGL((trace_kernel<P, C, F>), dim3((unsigned)(num_cus * use_per_cu)), dim3(kBlock), lds, stream, sc, cam, pt,
+    const uint32_t waves_per_cursor = ((uint32_t)(num_cus * per_cu) * kWavesPerBlock + kMaxCursors - 1u) / kMaxCursors;
+    pt.tail_chunks = kTailChunksPerWave * waves_per_cursor;
+    hipLaunchKernelGGL((trace_kernel<P, C, F>), dim3((unsigned)(num_cus * per_cu)), dim3(kBlock), lds, stream, sc, cam, pt,
                        (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, cursor, slot_L, film_n, counters);
     return hipGetLastError();
 }
 
 // confirm: the octree confirm step follows (reference-default semantics); primary rays are radiance rays either way
-hipError_t launch_trace(hipStream_t stream, int num_cus, int blocks_per_cu_cap, bool primary, bool count, bool confirm, const DScene& sc, const DCamera& cam, const DPass& ps,
+hipError_t launch_trace(hipStream_t stream, int num_cus, bool primary, bool count, bool confirm, const DScene& sc, const DCamera& cam, const DPass& ps,
                         const void* in_q, const void* in_counts, void* hits, uint32_t* cursor,
                         float* slot_L, const uint32_t* film_n, DCounters* counters)
 {
-#define MI355RT_TRACE_ARGS stream, num_cus, blocks_per_cu_cap, sc, cam, ps, in_q, in_counts, hits, cursor, slot_L, film_n, counters
+#define MI355RT_TRACE_ARGS stream, num_cus, sc, cam, ps, in_q, in_counts, hits, cursor, slot_L, film_n, counters
     if (primary) return count ? launch_trace_variant<true, true, true>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true>(MI355RT_TRACE_ARGS);
     if (confirm) return count ? launch_trace_variant<false, true, true>(MI355RT_TRACE_ARGS) : launch_trace_variant<false, false, true>(MI355RT_TRACE_ARGS);
     return count ? launch_trace_variant<false, true, false>(MI355RT_TRACE_ARGS) : launch_trace_variant<false, false, false>(MI355RT_TRACE_ARGS);
@@ -1558,18 +1418,6 @@ hipError_t launch_cull_blocks(hipStream_t stream, const DCamera& cam, const DPas
     return hipGetLastError();
 }
 
-hipError_t launch_raster(hipStream_t stream, int num_cus, bool count, bool confirm, const DScene& sc, const DCamera& cam, const DPass& ps,
-                         void* hits, uint32_t* cursor, const uint32_t* film_n, DCounters* counters)
-{
-    // persistent grid like the trace launch; no LDS, few registers: 8 blocks per CU
-    const dim3 grid((unsigned)(num_cus * 8)), block(kBlock);
-    if (confirm) { if (count) hipLaunchKernelGGL((raster_kernel<true, true>), grid, block, 0, stream, sc, cam, ps, (float4*)hits, cursor, film_n, counters);
-                   else hipLaunchKernelGGL((raster_kernel<false, true>), grid, block, 0, stream, sc, cam, ps, (float4*)hits, cursor, film_n, counters); }
-    else { if (count) hipLaunchKernelGGL((raster_kernel<true, false>), grid, block, 0, stream, sc, cam, ps, (float4*)hits, cursor, film_n, counters);
-           else hipLaunchKernelGGL((raster_kernel<false, false>), grid, block, 0, stream, sc, cam, ps, (float4*)hits, cursor, film_n, counters); }
-    return hipGetLastError();
-}
-
 hipError_t launch_trace_octree(hipStream_t stream, int num_cus, bool primary, const DScene& sc, const DCamera& cam, const DPass& ps,
                                const void* in_q, const void* in_counts, void* hits, float* slot_L, const uint32_t* film_n)
 {
@@ -1590,7 +1438,7 @@ hipError_t launch_shade(hipStream_t stream, int num_cus, bool primary, bool walk
     // raster (primary round only): the kernel finds the primary rays' closest hits itself, through the tile bins (cam.tile_ofs), and keeps them in LDS
     const size_t lds = (size_t)ps.list_cap * kWavesPerBlock * sizeof(uint32_t) + (raster ? (size_t)ps.chunk * kWavesPerBlock * sizeof(float4) : 0);
     unsigned blocks = (ps.nchunks + kWavesPerBlock - 1) / kWavesPerBlock;
-    const unsigned cap = (unsigned)num_cus * (primary ? (walk ? MI355RT_SHADE_PW_BLOCKS : MI355RT_SHADE_P_BLOCKS) : (walk ? MI355RT_SHADE_SW_BLOCKS : MI355RT_SHADE_S_BLOCKS));    // what the chip holds at once
+    const unsigned cap = (unsigned)num_cus * (primary ? (walk ? kShadePWBlocks : kShadePBlocks) : (walk ? kShadeSWBlocks : kShadeSBlocks));    // what the chip holds at once
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     dim3 grid(blocks), block(kBlock);
@@ -1609,15 +1457,12 @@ hipError_t launch_resolve(hipStream_t stream, const DPass& ps, uint32_t width, u
                           float* film_sum, float* film_sumsq, uint32_t* film_n, float* debug_color, uint32_t* ctrl)
 {
     const uint32_t spp = ps.npix ? ps.nsamples / ps.npix : 1u;
-    uint32_t lanes = spp <= 32u ? 2u : (spp <= 96u ? 4u : 8u);
-    if (const char* e = getenv("MI355RT_RESOLVE_LANES")) { int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) lanes = (uint32_t)v; }
+    const uint32_t lanes = spp <= 32u ? 2u : (spp <= 96u ? 4u : 8u);
     dim3 block(256), grid((unsigned)(((size_t)ps.npix * lanes + 255) / 256));
 #define MI355RT_RESOLVE_ARGS grid, block, 0, stream, ps, width, nlights, slot_L, sample_slot, film_sum, film_sumsq, film_n, debug_color, ctrl
     switch (lanes) {
-        case 1: hipLaunchKernelGGL(resolve_kernel<1>, MI355RT_RESOLVE_ARGS); break;
         case 2: hipLaunchKernelGGL(resolve_kernel<2>, MI355RT_RESOLVE_ARGS); break;
         case 4: hipLaunchKernelGGL(resolve_kernel<4>, MI355RT_RESOLVE_ARGS); break;
-        case 16: hipLaunchKernelGGL(resolve_kernel<16>, MI355RT_RESOLVE_ARGS); break;
         default: hipLaunchKernelGGL(resolve_kernel<8>, MI355RT_RESOLVE_ARGS); break;
     }
 #undef MI355RT_RESOLVE_ARGS
@@ -1733,7 +1578,7 @@ hipError_t launch_confirm(hipStream_t stream, int num_cus, bool primary, bool sh
 {
     const size_t lds = 0;                                  // the pending lists are static LDS (128 entries per wave)
     unsigned blocks = (ps.nchunks + kWavesPerBlock - 1) / kWavesPerBlock;
-    const unsigned cap = (unsigned)num_cus * MI355RT_CONFIRM_BLOCKS;   // several chunks per wave, so that batches fill up across chunks
+    const unsigned cap = (unsigned)num_cus * kConfirmBlocks;   // several chunks per wave, so that batches fill up across chunks
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     if (primary) hipLaunchKernelGGL(confirm_kernel<true>, dim3(blocks), dim3(kBlock), lds, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, cursor, slot_L, film_n, 0u);

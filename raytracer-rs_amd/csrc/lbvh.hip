@@ -188,8 +188,7 @@ bool build_bvh_device(const float* tri_verts, const uint32_t* tri_geom, uint32_t
 {
     const auto t_wall = std::chrono::steady_clock::now();
     ms[0] = ms[1] = 0.0;
-    uint32_t max_leaf = 1;        // measured (profiles/r02_notes.md): Morton-order subtrees make poor leaves — thai2 28.0 / 28.2 / 29.0 / 30.4 ms per frame at 1 / 2 / 3 / 4
-    if (const char* e = std::getenv("MI355RT_MAX_LEAF")) { int v = std::atoi(e); if (v >= 1 && v <= 8) max_leaf = (uint32_t)v; }     // the host builder's knob
+    constexpr uint32_t max_leaf = 1;        // measured (profiles/r02_notes.md): Morton-order subtrees make poor leaves — thai2 28.0 / 28.2 / 29.0 / 30.4 ms per frame at 1 / 2 / 3 / 4
     if (ntri <= kBvhMaxLeaf) { why = "scene fits one leaf"; return false; }
     if (ntri >= (1u << 26)) { why = "too many triangles"; return false; }
     out = Bvh();

@@ -210,10 +210,8 @@ bool Renderer::init(const SceneData& scene, std::string& err, int& code)
           for (int a = 0; a < 3; ++a) diag2 += ((double)mx[a] - mn[a]) * ((double)mx[a] - mn[a]); }
         const double pad = 2e-4 * std::sqrt(diag2) + 1e-7;
         uint32_t res = 512;
-        if (const char* e = getenv("MI355RT_LIGHT_MAP_RES")) { int v = atoi(e); if (v >= 16 && v <= 2048) res = (uint32_t)v; }
         while (res > 16 && (size_t)6 * res * res * 4 * scene.lights.size() > ((size_t)64 << 20)) res /= 2;
-        uint64_t work_cap = 4ull << 20;
-        if (const char* e = getenv("MI355RT_LIGHT_MAP_WORK")) { long long v = atoll(e); if (v >= 1024) work_cap = (uint64_t)v; }
+        const uint64_t work_cap = 4ull << 20;
         for (const LightData& l : scene.lights) while (res > 16 && light_map_work(scene.tri_verts.data(), ntri, l.pos, res) > work_cap) res /= 2;
         std::vector<float> all; all.reserve((size_t)6 * res * res * scene.lights.size());
         bool finite = true;
@@ -314,11 +312,9 @@ bool Renderer::init(const SceneData& scene, std::string& err, int& code)
     if (h_counters_.alloc(sizeof(DCounters) * kShards) != hipSuccess) { err = "pinned host allocation failed"; return false; }
     std::memset(h_counters_.get(), 0, sizeof(DCounters) * kShards);
     slices_[0].stream = stream_;
-    if (hipStreamCreateWithFlags(&trace_stream_, hipStreamNonBlocking) != hipSuccess) { err = "hipStreamCreate failed"; return false; }
     for (uint32_t i = 0; i < kMaxSlices; ++i) {
         if (i && hipStreamCreateWithFlags(&slices_[i].stream, hipStreamNonBlocking) != hipSuccess) { err = "hipStreamCreate failed"; return false; }
-        if (hipEventCreateWithFlags(&slices_[i].done, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&slices_[i].ev_ready, hipEventDisableTiming) != hipSuccess
-            || hipEventCreateWithFlags(&slices_[i].ev_traced, hipEventDisableTiming) != hipSuccess) { err = "hipEventCreate failed"; return false; }
+        if (hipEventCreateWithFlags(&slices_[i].done, hipEventDisableTiming) != hipSuccess) { err = "hipEventCreate failed"; return false; }
         if (!upload(slices_[i].d_ctrl, nullptr, kMaxRounds * kCtrlWordsPerRound * 4)) return bail();
         if (!upload(slices_[i].d_rows, nullptr, (size_t)cfg.height * 4)) return bail();
     }
@@ -334,9 +330,6 @@ bool Renderer::init(const SceneData& scene, std::string& err, int& code)
     }
     max_level_nodes_ = 1;
     for (uint32_t l = 0; l <= cfg.recursions; ++l) max_level_nodes_ = std::max(max_level_nodes_, level_first[l + 1] - level_first[l]);
-    chunk_ = 256;
-    if (const char* e = getenv("MI355RT_LEAF_THRESHOLD")) { int v = atoi(e); if (v >= 1 && v <= 64) leaf_threshold_ = (uint32_t)v; }
-    if (const char* e = getenv("MI355RT_CHUNK")) { int v = atoi(e); if (v >= 64 && v <= 65536) chunk_ = (uint32_t)v; }
     code = MI355RT_OK;
     return true;
 }
@@ -349,10 +342,7 @@ Renderer::~Renderer()
     for (uint32_t i = 0; i < kMaxSlices; ++i) {
         if (i && slices_[i].stream) { (void)hipStreamSynchronize(slices_[i].stream); (void)hipStreamDestroy(slices_[i].stream); }
         if (slices_[i].done) (void)hipEventDestroy(slices_[i].done);
-        if (slices_[i].ev_ready) (void)hipEventDestroy(slices_[i].ev_ready);
-        if (slices_[i].ev_traced) (void)hipEventDestroy(slices_[i].ev_traced);
     }
-    if (trace_stream_) { (void)hipStreamSynchronize(trace_stream_); (void)hipStreamDestroy(trace_stream_); }
     comm_destroy();
     if (ev_tonemap_) (void)hipEventDestroy(ev_tonemap_);
     if (read_stream_) (void)hipStreamDestroy(read_stream_);
@@ -479,7 +469,6 @@ bool Renderer::refresh_cull_mask(DCamera& c, const double inv[3][3], double pad,
     if (!d_cull_mask_ && d_cull_mask_.alloc(bits.size() * 4, &hbm_bytes_) != hipSuccess) return true;
     // kernels of earlier calls may still read the old mask: wait for them, then replace it (camera changes are rare and clear the film anyway, main.rs:116-169)
     (void)hipStreamSynchronize(stream_);
-    if (trace_stream_) (void)hipStreamSynchronize(trace_stream_);
     for (Slice& sl : slices_) if (sl.stream) (void)hipStreamSynchronize(sl.stream);
     if (hipMemcpy(d_cull_mask_.get(), bits.data(), bits.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return true;
     mask_dom_[0] = (float)X0; mask_dom_[1] = (float)Y0; mask_dom_[2] = (float)icx; mask_dom_[3] = (float)icy;
@@ -489,7 +478,7 @@ bool Renderer::refresh_cull_mask(DCamera& c, const double inv[3][3], double pad,
     return true;
 }
 
-// Screen-space triangle bins for the primary rays (device_types.hpp, kernels.hip raster_kernel).  The 64 consecutive samples a wave takes are
+// Screen-space triangle bins for the primary rays (device_types.hpp, kernels.hip raster_tile).  The 64 consecutive samples a wave takes are
 // 64 / sample_group pixels: tile_cols columns x row_group rows of one row group (kernels.hip, pass_column).  When every group of the pass's row list
 // is row_group CONSECUTIVE image rows starting at a multiple of row_group (always, for whole images and power-of-two stripes) a tile is a fixed
 // block of the image, and every triangle whose padded screen rectangle (the culling mask's) meets the tile's (dir_x, dir_y) footprint — computed
@@ -576,7 +565,6 @@ bool Renderer::refresh_tile_bins(DCamera& c, const double inv[3][3], double pad,
     if (!bind()) return false;
     // kernels of earlier calls may still read the old bins (as with the mask): wait, then replace
     (void)hipStreamSynchronize(stream_);
-    if (trace_stream_) (void)hipStreamSynchronize(trace_stream_);
     for (Slice& sl : slices_) if (sl.stream) (void)hipStreamSynchronize(sl.stream);
     if (ofs.size() * sizeof(uint2) > d_tile_ofs_.bytes() && d_tile_ofs_.alloc(ofs.size() * sizeof(uint2), &hbm_bytes_) != hipSuccess) BINS_OUT(9);
     if (entries.size() * sizeof(uint2) > d_tile_entries_.bytes() && d_tile_entries_.alloc((entries.size() + entries.size() / 4) * sizeof(uint2), &hbm_bytes_) != hipSuccess) BINS_OUT(10);    // 1/4 slack
@@ -662,14 +650,14 @@ bool Renderer::ensure_pass_capacity(Slice& sl, size_t nsamples)
     if (nsamples <= sl.capacity) return true;
     for (Slice& o : slices_) if (o.stream) HIP_TRY(hipStreamSynchronize(o.stream));
     sl.release_pass_buffers();          // grow: release this slice's buffers only
-    const size_t nchunks = (nsamples + chunk_ - 1) / chunk_;
-    const size_t records = nchunks * chunk_ * records_per_sample_;
+    const size_t nchunks = (nsamples + kChunk - 1) / kChunk;
+    const size_t records = nchunks * kChunk * records_per_sample_;
     // the kernels index records, light-term floats and hit flags with 32 bits (byte offsets are 64-bit)
-    if (nsamples > 0x7FFFFFFFull || records > 0x3FFFFFFFull || nchunks * chunk_ * nodes_per_sample * std::max(nlights_, 1u) * 3ull > 0xFFFFFFFFull) {
+    if (nsamples > 0x7FFFFFFFull || records > 0x3FFFFFFFull || nchunks * kChunk * nodes_per_sample * std::max(nlights_, 1u) * 3ull > 0xFFFFFFFFull) {
         last_error = "pass too large"; alloc_failed_ = true; return false;     // the caller retries with a smaller pass
     }
     // (n_radiance, n_shadow) per chunk: the fused 50-row launch cuts the same samples into chunks as small as kMinChunk
-    const size_t count_entries = nchunks * chunk_ / std::min(chunk_, kMinChunk);
+    const size_t count_entries = nchunks * kChunk / std::min(kChunk, kMinChunk);
     // MI355RT_DEBUG_GUARD: every pass buffer gets a 256-byte tail filled with 0xA5 that check_guards() reads back
     // (tests/test_gpu_dropin.py: no launch may write past the sizes computed here)
     const size_t guard = getenv("MI355RT_DEBUG_GUARD") ? kGuardBytes : 0;
@@ -679,9 +667,9 @@ bool Renderer::ensure_pass_capacity(Slice& sl, size_t nsamples)
     }
     HIP_ALLOC(sl.d_hits.alloc(records * 16, &hbm_bytes_, guard));
     HIP_ALLOC(sl.d_hit_prim.alloc(records * 4, &hbm_bytes_, guard));
-    HIP_ALLOC(sl.d_slot_L.alloc(nchunks * chunk_ * nodes_per_sample * std::max(nlights_, 1u) * 12, &hbm_bytes_, guard));
-    HIP_ALLOC(sl.d_sample_slot.alloc(nchunks * chunk_ * 4, &hbm_bytes_, guard));
-    HIP_ALLOC(sl.d_slot_ps.alloc(nchunks * chunk_ * 8, &hbm_bytes_, guard));
+    HIP_ALLOC(sl.d_slot_L.alloc(nchunks * kChunk * nodes_per_sample * std::max(nlights_, 1u) * 12, &hbm_bytes_, guard));
+    HIP_ALLOC(sl.d_sample_slot.alloc(nchunks * kChunk * 4, &hbm_bytes_, guard));
+    HIP_ALLOC(sl.d_slot_ps.alloc(nchunks * kChunk * 8, &hbm_bytes_, guard));
     HIP_ALLOC(sl.d_live.alloc((nchunks + kMaxCursors) * 4, &hbm_bytes_, guard));
     sl.capacity = nsamples;
     sl.queue_records = records;
@@ -715,9 +703,7 @@ void Renderer::describe_pass(DPass& ps, const Slice& sl, const uint32_t* d_rows,
     // 1 / 2 / 4 / 8 / 16 / 64, one rank's share of eight 3.27 / 3.24 / 3.30 / 3.34 / 3.40 / 3.63 ms (profiles/r03_notes.md); the largest divisor of spp <= the wish.
     // With the primary rays going through the tile bins (a wave's tile is 64 / group pixels: shorter lists for smaller tiles) and most shadow rays
     // never made: 15.5 / 15.4 / 15.1 / 15.5 ms at 2 / 4 / 8 / 16 — 8 since.
-    uint32_t group = 8u;
-    if (const char* e = getenv("MI355RT_SAMPLE_GROUP")) { int v = atoi(e); if (v >= 1) group = (uint32_t)v; }
-    group = std::max(1u, std::min(group, ps.spp));
+    uint32_t group = std::max(1u, std::min(8u, ps.spp));
     while (ps.spp % group) --group;
     // a power of two by preference (12 spp: 4, not 6): the tile bins and the cached culling verdicts need the group to divide a wave's 64 samples
     if (64u % group) { uint32_t p2 = 8u; while (p2 > 1u && (p2 > group || ps.spp % p2)) p2 >>= 1; group = p2; }
@@ -737,52 +723,38 @@ void Renderer::describe_pass(DPass& ps, const Slice& sl, const uint32_t* d_rows,
     ps.chunk = chunk; ps.nchunks = (uint32_t)((nsamples + chunk - 1) / chunk); ps.region = chunk * records_per_sample_;
     ps.hit_prim = sl.d_hit_prim.get(); ps.qstride = sl.queue_records; ps.slot_ps = (uint2*)sl.d_slot_ps.get();
     ps.stack_depth = traversal_rows(); ps.list_cap = chunk * max_level_nodes_;
-    ps.leaf_threshold = leaf_threshold_;
-    ps.refill_threshold = 24; if (const char* e = getenv("MI355RT_REFILL")) { int v = atoi(e); if (v >= 1 && v <= 64) ps.refill_threshold = (uint32_t)v; }
-    // the primary launch refills later: its rays are neighbours on the screen, and the more of them start together the more lanes of a quad
-    // share the lines they fetch (cache-line accesses of the launch at 8 / 24 / 48 / 64 idle lanes: 1.48 / 1.21 / 1.03 / 0.94e10 per 7 frames,
-    // profiles/r03_notes.md); secondary rays do not gain from it (5.8e10 at 24 and at 48)
-    refill_primary_ = 48; if (const char* e = getenv("MI355RT_REFILL_PRIMARY")) { int v = atoi(e); if (v >= 1 && v <= 64) refill_primary_ = (uint32_t)v; }
-    ps.pull_mode = 4u;                  // 64 interleaved cursors (see pull_chunk in kernels.hip)
-    if (const char* e = getenv("MI355RT_PULL")) ps.pull_mode = (uint32_t)atoi(e);
-    ps.pull_group = 1; if (const char* e = getenv("MI355RT_GROUP")) { int v = atoi(e); if (v >= 1 && v <= 64) ps.pull_group = (uint32_t)v; }
-    ps.tail_chunks = 2; if (const char* e = getenv("MI355RT_TAIL_CHUNKS")) { int v = atoi(e); if (v >= 0 && v <= 64) ps.tail_chunks = (uint32_t)v; }
-    ps.tail_split_shift = 2; if (const char* e = getenv("MI355RT_TAIL_SPLIT")) { int v = atoi(e); if (v >= 0 && v <= 4) ps.tail_split_shift = (uint32_t)v; }
-    ps.ncursors = 64; if (const char* e = getenv("MI355RT_CURSORS")) { int v = atoi(e); if (v >= 1 && v <= (int)kMaxCursors) ps.ncursors = (uint32_t)v; }
-    // live-chunk lists (device_types.hpp): with the cursor scheme the wavefront launches use by default, and the chunk size the buffers were sized for.
+    // live-chunk lists (device_types.hpp): with the chunk size the buffers were sized for.
     // Not with the direct octree walk: its trace launch strides over ALL chunks, and the ray counts of the chunks the shade launches no longer visit
     // are whatever an earlier pass left there.
     ps.live = nullptr; ps.live_count = nullptr; ps.live_cap = 0;
-    if (ps.pull_mode == 4u && ps.pull_group == 1u && chunk == chunk_ && sl.d_live && !explicit_sample && mode_ != kModeOctreeWalk && !getenv("MI355RT_NO_LIVE")) {
-        ps.live = sl.d_live.get(); ps.live_count = sl.d_ctrl.get(); ps.live_cap = (ps.nchunks + ps.ncursors - 1u) / ps.ncursors;
+    if (chunk == kChunk && sl.d_live && !explicit_sample && mode_ != kModeOctreeWalk) {
+        ps.live = sl.d_live.get(); ps.live_count = sl.d_ctrl.get(); ps.live_cap = (ps.nchunks + kMaxCursors - 1u) / kMaxCursors;
     }
 }
 
-// A wavefront pass in three steps, so that a frame can interleave the rounds of its slices (render()):
-// pass_begin: buffers, descriptor, cursors; pass_round(r): trace (+ confirm) (+ shade) of round r; pass_end: resolve.
-// The trace launch of a round goes to `trace_stream` when one is given — ordered after the slice's own stream and before
-// what the slice queues next — everything else to the slice's stream.
-bool Renderer::pass_begin(PassRun& run, Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t nrows, uint32_t spp, bool explicit_sample, uint32_t epixel, uint32_t esample, uint32_t row_wrap)
+// A wavefront pass: buffers, descriptor and cursors; then round by round trace (+ confirm) (+ shade); then resolve.  Every launch goes
+// to the slice's stream.
+bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t nrows, uint32_t spp, bool explicit_sample, uint32_t epixel, uint32_t esample, uint32_t row_wrap)
 {
-    run.sl = &sl; run.live = false;
     const uint32_t npix = explicit_sample ? 1u : nrows * cfg.width;
     const size_t nsamples = (size_t)npix * spp;
     if (nsamples == 0) return true;
     if (!ensure_pass_capacity(sl, nsamples)) return false;
-    describe_pass(run.ps, sl, d_rows, row0, row_wrap, npix, nsamples, chunk_, explicit_sample, epixel, esample);
+    DPass ps;
+    describe_pass(ps, sl, d_rows, row0, row_wrap, npix, nsamples, kChunk, explicit_sample, epixel, esample);
     // the tile bins of the primary rays need a pass that walks the slice's whole row list (render(); not the odd row windows of the other callers)
     const bool whole = !explicit_sample && d_rows == sl.d_rows.get() && row0 == 0 && nrows == sl.rows.size() && row_wrap == 0xFFFFFFFFu;
-    run.cam = device_camera(whole ? &run.ps : nullptr, whole ? &sl.rows : nullptr);
+    const DCamera cam = device_camera(whole ? &ps : nullptr, whole ? &sl.rows : nullptr);
     // culling verdicts per pixel block, computed once per camera and layout (DPass::block_culled) instead of per launch and chunk
-    run.ps.block_culled = nullptr; run.ps.cull_blocks = 0;
+    ps.block_culled = nullptr; ps.cull_blocks = 0;
     // (needs chunks that hold whole pixels — the sample group divides the chunk — and sample groups that are whole numbers of chunks: then every sample of a pixel
     // lies in chunks of ONE block)
-    if (whole && run.cam.cull_valid != 0 && mode_ != kModeOctreeWalk && run.ps.chunk % run.ps.sample_group == 0 && ((size_t)run.ps.npix * run.ps.sample_group) % run.ps.chunk == 0 && !getenv("MI355RT_NO_CULL_CACHE")) {
-        const size_t nblocks = (size_t)run.ps.npix * run.ps.sample_group / run.ps.chunk;
-        std::vector<float> key(run.cam.rot, run.cam.rot + 16);
-        key.insert(key.end(), run.cam.origin, run.cam.origin + 3); key.push_back(run.cam.max_x); key.push_back(run.cam.max_y);
-        key.push_back((float)nrows); key.push_back((float)run.ps.chunk); key.push_back((float)run.ps.sample_group); key.push_back((float)run.ps.row_group);
-        key.push_back((float)(run.ps.flags & 1u)); key.push_back(run.cam.cull_mask ? 1.0f : 0.0f); key.push_back((float)nblocks);
+    if (whole && cam.cull_valid != 0 && mode_ != kModeOctreeWalk && ps.chunk % ps.sample_group == 0 && ((size_t)ps.npix * ps.sample_group) % ps.chunk == 0 && !getenv("MI355RT_NO_CULL_CACHE")) {
+        const size_t nblocks = (size_t)ps.npix * ps.sample_group / ps.chunk;
+        std::vector<float> key(cam.rot, cam.rot + 16);
+        key.insert(key.end(), cam.origin, cam.origin + 3); key.push_back(cam.max_x); key.push_back(cam.max_y);
+        key.push_back((float)nrows); key.push_back((float)ps.chunk); key.push_back((float)ps.sample_group); key.push_back((float)ps.row_group);
+        key.push_back((float)(ps.flags & 1u)); key.push_back(cam.cull_mask ? 1.0f : 0.0f); key.push_back((float)nblocks);
         if (nblocks * 4 > sl.d_block_culled.bytes()) {
             HIP_TRY(hipStreamSynchronize(sl.stream));
             if (sl.d_block_culled.alloc(nblocks * 4, &hbm_bytes_) != hipSuccess) (void)hipGetLastError();
@@ -790,121 +762,82 @@ bool Renderer::pass_begin(PassRun& run, Slice& sl, const uint32_t* d_rows, uint3
         }
         if (sl.d_block_culled) {
             if (key != sl.cull_key) {          // stream-ordered behind the launches that read the old verdicts
-                HIP_TRY(launch_cull_blocks(sl.stream, run.cam, run.ps, (uint32_t)nblocks, sl.d_block_culled.get()));
+                HIP_TRY(launch_cull_blocks(sl.stream, cam, ps, (uint32_t)nblocks, sl.d_block_culled.get()));
                 sl.cull_key = key;
             }
-            run.ps.block_culled = sl.d_block_culled.get(); run.ps.cull_blocks = (uint32_t)nblocks;
+            ps.block_culled = sl.d_block_culled.get(); ps.cull_blocks = (uint32_t)nblocks;
         }
     }
-    run.rounds = cfg.recursions + 2;
-    // the work cursors: zeroed at creation and again by the resolve kernel of every pass that ran to its end (pass_end)
-    if (!sl.ctrl_clean) HIP_TRY(hipMemsetAsync(sl.d_ctrl.get(), 0, kMaxRounds * kCtrlWordsPerRound * 4, sl.stream));
+    // the work cursors: zeroed at creation and again by the resolve kernel of every pass that ran to its end
+    hipStream_t st = sl.stream;
+    if (!sl.ctrl_clean) HIP_TRY(hipMemsetAsync(sl.d_ctrl.get(), 0, kMaxRounds * kCtrlWordsPerRound * 4, st));
     sl.ctrl_clean = false;
-    run.live = true;
-    return true;
-}
-
-// round r: trace the rays of level r (+ the shadow rays emitted by level r-1), then shade level r
-bool Renderer::pass_round(PassRun& run, uint32_t r, hipStream_t trace_stream, int trace_blocks_per_cu)
-{
-    if (!run.live || r >= run.rounds) return true;
-    Slice& sl = *run.sl;
-    const DPass& ps = run.ps;
-    const DCamera& cam = run.cam;
-    hipStream_t st = sl.stream;             // confirm / shade launches of this pass go to the slice's stream
-    hipStream_t tst = trace_stream ? trace_stream : st;
     const bool count = (cfg.flags & MI355RT_FLAG_COUNT_STEPS) != 0;
     const bool timed = (cfg.flags & MI355RT_FLAG_TIME_KERNELS) != 0;
-    // Primary round with tile bins: the shade launch finds the closest hits itself (kernels.hip, shade_chunk<RASTER>) — no trace launch at all —
-    // whenever that launch also does what else the round needs (the octree confirm step of its hits, or nothing to confirm).
-    const bool confirm_round = mode_ == kModeConfirm && !dscene_.oct_single_leaf;
-    const char* sw_env = getenv("MI355RT_SHADE_WALK");
-    const bool fuse_primary = r == 0 && cam.tile_ofs != nullptr && mode_ != kModeOctreeWalk && (!confirm_round || !sw_env || atoi(sw_env) >= 1) && !getenv("MI355RT_NO_FUSE_PRIMARY");
-    const void* in_q = r == 0 ? nullptr : sl.d_queue[(r - 1) & 1].get();
-    const void* in_c = r == 0 ? nullptr : sl.d_chunk_counts[(r - 1) & 1].get();
-    const bool balance_dbg = !fuse_primary && count && getenv("MI355RT_DEBUG_UTIL") && mode_ != kModeOctreeWalk;
-    if (!fuse_primary) {
-    if (tst != st) { HIP_TRY(hipEventRecord(sl.ev_ready, st)); HIP_TRY(hipStreamWaitEvent(tst, sl.ev_ready, 0)); }
-    if (timed) {
-        if (ev_used_ + 2 > ev_pool_.size()) {
-            for (int k = 0; k < 2; ++k) { hipEvent_t ev; HIP_TRY(hipEventCreate(&ev)); ev_pool_.push_back(ev); }
-        }
-        HIP_TRY(hipEventRecord(ev_pool_[ev_used_], tst));
-        ev_secondary_.resize(ev_pool_.size() / 2); ev_secondary_[ev_used_ / 2] = r > 0;
-    }
-    if (balance_dbg) {       // load-balance diagnostics of this launch (debug only: synchronises)
-        DCounters init{};
-        HIP_TRY(hipMemcpy(&init, d_counters_.get(), sizeof init, hipMemcpyDeviceToHost));
-        init.t_first_end = ~0ull; init.t_start = ~0ull; init.t_last_end = 0; init.t_sum_end = 0; init.n_waves = 0;
-        HIP_TRY(hipMemcpy(d_counters_.get(), &init, sizeof init, hipMemcpyHostToDevice));
-    }
-    if (mode_ == kModeOctreeWalk)
-        HIP_TRY(launch_trace_octree(tst, num_cus_, r == 0, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_slot_L.get(), d_film_n_.get()));
-    else {
-        DPass pr = ps;
-        if (r == 0) pr.refill_threshold = refill_primary_;             // primary rays: see describe_pass
-        if (r == 0 && cam.tile_ofs != nullptr)                         // the primary rays' closest hits from the screen-space triangle bins instead of the tree
-            HIP_TRY(launch_raster(tst, num_cus_, count, mode_ == kModeConfirm, dscene_, cam, ps, sl.d_hits.get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound, d_film_n_.get(), d_counters_.get()));
-        else
-        HIP_TRY(launch_trace(tst, num_cus_, trace_blocks_per_cu, r == 0, count, mode_ == kModeConfirm, dscene_, cam, pr, in_q, in_c, sl.d_hits.get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound, sl.d_slot_L.get(), d_film_n_.get(), d_counters_.get()));
-    }
-    if (timed) { HIP_TRY(hipEventRecord(ev_pool_[ev_used_ + 1], tst)); ev_used_ += 2; }
-    ++launches_;
-    if (tst != st) { HIP_TRY(hipEventRecord(sl.ev_traced, tst)); HIP_TRY(hipStreamWaitEvent(st, sl.ev_traced, 0)); }
-    }
-    // true closest hits -> the reference intersector's answers; settles the shadow rays of this round.  One-leaf octrees: done in the
+    // true closest hits -> the reference intersector's answers; settles the shadow rays of a round.  One-leaf octrees: done in the
     // trace kernel.  Radiance hits: confirmed by the round's SHADE kernel, which loads the ray and the hit record anyway (primary
     // round: no confirm launch at all; secondary rounds: the confirm launch handles the shadow records only).  24.3 -> 23.3 ms per frame.
     const bool confirm_here = mode_ == kModeConfirm && !dscene_.oct_single_leaf;
-    const char* sw = getenv("MI355RT_SHADE_WALK");                 // experiment knob: 0 = confirm launches only, 1 = the primary round's shade kernel walks, 2 (default) = every shade kernel walks its radiance hits
-    const int sw_mode = sw ? atoi(sw) : 2;
-    const bool shade_walks = confirm_here && r <= cfg.recursions && (r == 0 ? sw_mode >= 1 : sw_mode >= 2);
-    if (confirm_here && !(shade_walks && r == 0))
-        HIP_TRY(launch_confirm(st, num_cus_, r == 0, shade_walks, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound + kConfirmCursorOffset, sl.d_slot_L.get(), d_film_n_.get()));
-    if (balance_dbg) {
-        DCounters c0{};
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(&c0, d_counters_.get(), sizeof c0, hipMemcpyDeviceToHost));
-        {   // lane census of the launch (summed over the counter shards; cumulative over the call's launches: print differences)
-            DCounters sh[kShards], t{};
-            HIP_TRY(hipMemcpy(sh, d_counters_.get(), sizeof sh, hipMemcpyDeviceToHost));
-            for (const DCounters& x : sh) { t.lanes_inner += x.lanes_inner; t.lanes_leaf += x.lanes_leaf; t.lanes_done += x.lanes_done; t.lane_samples += x.lane_samples;
-                                            t.refills += x.refills; t.refill_passes += x.refill_passes; t.refill_rays += x.refill_rays; t.inner_execs += x.inner_execs; t.leaf_execs += x.leaf_execs; }
-            static DCounters prev{};
-            if (t.lane_samples < prev.lane_samples) prev = DCounters{};
-            const double it = (double)(t.lane_samples - prev.lane_samples);
-            if (it > 0)
-                fprintf(stderr, "[mi355rt] trace round %u census: iterations %.0f, lanes at inner %.1f / at leaf %.1f / idle-or-finished %.1f per iteration; inner execs %.2f, leaf execs %.2f per iteration; refills %llu, passes %llu, rays per refill %.1f\n",
-                        r, it, (t.lanes_inner - prev.lanes_inner) / it, (t.lanes_leaf - prev.lanes_leaf) / it, (t.lanes_done - prev.lanes_done) / it,
-                        (t.inner_execs - prev.inner_execs) / it, (t.leaf_execs - prev.leaf_execs) / it,
-                        t.refills - prev.refills, t.refill_passes - prev.refill_passes, (double)(t.refill_rays - prev.refill_rays) / std::max<double>(1.0, (double)(t.refills - prev.refills)));
-            prev = t;
+    // round r: trace the rays of level r (+ the shadow rays emitted by level r-1), then shade level r
+    for (uint32_t r = 0; r < cfg.recursions + 2; ++r) {
+        // Primary round with tile bins: the shade launch finds the closest hits itself (kernels.hip, shade_chunk<RASTER>) — no trace launch at all.
+        const bool fuse_primary = r == 0 && cam.tile_ofs != nullptr && mode_ != kModeOctreeWalk;
+        const void* in_q = r == 0 ? nullptr : sl.d_queue[(r - 1) & 1].get();
+        const void* in_c = r == 0 ? nullptr : sl.d_chunk_counts[(r - 1) & 1].get();
+        const bool balance_dbg = !fuse_primary && count && getenv("MI355RT_DEBUG_UTIL") && mode_ != kModeOctreeWalk;
+        if (!fuse_primary) {
+            if (timed) {
+                if (ev_used_ + 2 > ev_pool_.size()) {
+                    for (int k = 0; k < 2; ++k) { hipEvent_t ev; HIP_TRY(hipEventCreate(&ev)); ev_pool_.push_back(ev); }
+                }
+                HIP_TRY(hipEventRecord(ev_pool_[ev_used_], st));
+                ev_secondary_.resize(ev_pool_.size() / 2); ev_secondary_[ev_used_ / 2] = r > 0;
+            }
+            if (balance_dbg) {       // load-balance diagnostics of this launch (debug only: synchronises)
+                DCounters init{};
+                HIP_TRY(hipMemcpy(&init, d_counters_.get(), sizeof init, hipMemcpyDeviceToHost));
+                init.t_first_end = ~0ull; init.t_start = ~0ull; init.t_last_end = 0; init.t_sum_end = 0; init.n_waves = 0;
+                HIP_TRY(hipMemcpy(d_counters_.get(), &init, sizeof init, hipMemcpyHostToDevice));
+            }
+            if (mode_ == kModeOctreeWalk)
+                HIP_TRY(launch_trace_octree(st, num_cus_, r == 0, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_slot_L.get(), d_film_n_.get()));
+            else
+                HIP_TRY(launch_trace(st, num_cus_, r == 0, count, mode_ == kModeConfirm, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound, sl.d_slot_L.get(), d_film_n_.get(), d_counters_.get()));
+            if (timed) { HIP_TRY(hipEventRecord(ev_pool_[ev_used_ + 1], st)); ev_used_ += 2; }
+            ++launches_;
         }
-        if (c0.n_waves)
-            fprintf(stderr, "[mi355rt] trace round %u: %llu waves, mean wave busy %.1f us, first wave out of work at %.1f us, last at %.1f us\n", r, c0.n_waves,
-                    (double)c0.t_sum_end / c0.n_waves / 100.0, (double)(c0.t_first_end - c0.t_start) / 100.0, (double)(c0.t_last_end - c0.t_start) / 100.0);
+        const bool shade_walks = confirm_here && r <= cfg.recursions;
+        if (confirm_here && r != 0)         // (the primary round's shade kernel confirms its hits, and there are no shadow rays yet)
+            HIP_TRY(launch_confirm(st, num_cus_, false, shade_walks, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound + kConfirmCursorOffset, sl.d_slot_L.get(), d_film_n_.get()));
+        if (balance_dbg) {
+            DCounters c0{};
+            HIP_TRY(hipStreamSynchronize(st));
+            HIP_TRY(hipMemcpy(&c0, d_counters_.get(), sizeof c0, hipMemcpyDeviceToHost));
+            {   // lane census of the launch (summed over the counter shards; cumulative over the call's launches: print differences)
+                DCounters sh[kShards], t{};
+                HIP_TRY(hipMemcpy(sh, d_counters_.get(), sizeof sh, hipMemcpyDeviceToHost));
+                for (const DCounters& x : sh) { t.lanes_inner += x.lanes_inner; t.lanes_leaf += x.lanes_leaf; t.lanes_done += x.lanes_done; t.lane_samples += x.lane_samples;
+                                                t.refills += x.refills; t.refill_passes += x.refill_passes; t.refill_rays += x.refill_rays; t.inner_execs += x.inner_execs; t.leaf_execs += x.leaf_execs; }
+                static DCounters prev{};
+                if (t.lane_samples < prev.lane_samples) prev = DCounters{};
+                const double it = (double)(t.lane_samples - prev.lane_samples);
+                if (it > 0)
+                    fprintf(stderr, "[mi355rt] trace round %u census: iterations %.0f, lanes at inner %.1f / at leaf %.1f / idle-or-finished %.1f per iteration; inner execs %.2f, leaf execs %.2f per iteration; refills %llu, passes %llu, rays per refill %.1f\n",
+                            r, it, (t.lanes_inner - prev.lanes_inner) / it, (t.lanes_leaf - prev.lanes_leaf) / it, (t.lanes_done - prev.lanes_done) / it,
+                            (t.inner_execs - prev.inner_execs) / it, (t.leaf_execs - prev.leaf_execs) / it,
+                            t.refills - prev.refills, t.refill_passes - prev.refill_passes, (double)(t.refill_rays - prev.refill_rays) / std::max<double>(1.0, (double)(t.refills - prev.refills)));
+                prev = t;
+            }
+            if (c0.n_waves)
+                fprintf(stderr, "[mi355rt] trace round %u: %llu waves, mean wave busy %.1f us, first wave out of work at %.1f us, last at %.1f us\n", r, c0.n_waves,
+                        (double)c0.t_sum_end / c0.n_waves / 100.0, (double)(c0.t_first_end - c0.t_start) / 100.0, (double)(c0.t_last_end - c0.t_start) / 100.0);
+        }
+        if (r <= cfg.recursions)
+            HIP_TRY(launch_shade(st, num_cus_, r == 0, shade_walks, dscene_, cam, ps, r, in_q, in_c, sl.d_hits.get(), sl.d_queue[r & 1].get(), sl.d_chunk_counts[r & 1].get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound + kShadeCursorOffset, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_n_.get(), d_counters_.get(), fuse_primary));
     }
-    if (r <= cfg.recursions)
-        HIP_TRY(launch_shade(st, num_cus_, r == 0, shade_walks, dscene_, cam, ps, r, in_q, in_c, sl.d_hits.get(), sl.d_queue[r & 1].get(), sl.d_chunk_counts[r & 1].get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound + kShadeCursorOffset, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_n_.get(), d_counters_.get(), fuse_primary));
-    return true;
-}
-
-bool Renderer::pass_end(PassRun& run)
-{
-    if (!run.live) return true;
-    Slice& sl = *run.sl;
-    HIP_TRY(launch_resolve(sl.stream, run.ps, cfg.width, nlights_, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_debug_color_.get(), sl.d_ctrl.get()));
+    HIP_TRY(launch_resolve(st, ps, cfg.width, nlights_, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_debug_color_.get(), sl.d_ctrl.get()));
     sl.ctrl_clean = true;
-    run.live = false;
     return true;
-}
-
-bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t nrows, uint32_t spp, bool explicit_sample, uint32_t epixel, uint32_t esample, uint32_t row_wrap)
-{
-    PassRun run;
-    if (!pass_begin(run, sl, d_rows, row0, nrows, spp, explicit_sample, epixel, esample, row_wrap)) return false;
-    for (uint32_t r = 0; r < run.rounds; ++r) if (!pass_round(run, r, nullptr, 0)) return false;
-    return pass_end(run);
 }
 
 bool Renderer::begin_call()
@@ -1189,32 +1122,19 @@ bool Renderer::render(uint32_t spp, bool wait)
         for (uint32_t s = 1; s < nsl; ++s) HIP_TRY(hipStreamWaitEvent(slices_[s].stream, ev_begin_, 0));
         active_slices_ = nsl;
         // Enqueue the passes round-robin so that no stream waits for the host: every slice's whole pass on its own stream.
-        // Measured alternative (MI355RT_PIPELINE=1, profiles/r02_notes.md): all trace launches on ONE stream, round by round,
-        // so that a slice's confirm / shade / resolve launches (memory latency) run beside the NEXT slice's trace (VALU issue).
-        // The schedule comes out as planned, but a trace kernel with a streaming kernel beside it runs 20-25 % longer and the
-        // frame loses 2 ms against the slices left to themselves (which fall into lockstep: 3 traces, then 3 shades).
-        const bool pipelined = nsl > 1 && getenv("MI355RT_PIPELINE");
-        int tcap = 0;
-        if (const char* e = getenv("MI355RT_PIPE_BLOCKS")) { int v = atoi(e); if (v >= 0) tcap = v; }
-        if (pipelined) HIP_TRY(hipStreamWaitEvent(trace_stream_, ev_begin_, 0));
+        // Measured alternative (profiles/r02_notes.md): all trace launches on ONE stream, round by round, so that a slice's
+        // confirm / shade / resolve launches (memory latency) run beside the NEXT slice's trace (VALU issue).  The schedule
+        // comes out as planned, but a trace kernel with a streaming kernel beside it runs 20-25 % longer and the frame loses
+        // 2 ms against the slices left to themselves (which fall into lockstep: 3 traces, then 3 shades).
         for (size_t p = 0;; ++p) {
             bool any = false;
-            PassRun run[kMaxSlices];
-            uint32_t rounds = 0;
             for (uint32_t s = 0; s < nsl; ++s) {
                 if (p >= plan[s].size()) continue;
                 any = true;
                 const PassDesc& d = plan[s][p];
-                if (!pipelined) { if (!run_pass(slices_[s], slices_[s].d_rows.get(), d.r0, d.nr, d.kk, false, 0, 0)) return false; continue; }
-                if (!pass_begin(run[s], slices_[s], slices_[s].d_rows.get(), d.r0, d.nr, d.kk, false, 0, 0, 0xFFFFFFFFu)) return false;
-                rounds = std::max(rounds, run[s].rounds);
+                if (!run_pass(slices_[s], slices_[s].d_rows.get(), d.r0, d.nr, d.kk, false, 0, 0)) return false;
             }
             if (!any) break;
-            if (!pipelined) continue;
-            for (uint32_t r = 0; r < rounds; ++r)
-                for (uint32_t s = 0; s < nsl; ++s)
-                    if (!pass_round(run[s], r, trace_stream_, tcap)) return false;
-            for (uint32_t s = 0; s < nsl; ++s) if (!pass_end(run[s])) return false;
         }
     }
     for (uint32_t r : owned_rows) ldr_dirty_[r] = 1;
@@ -1493,9 +1413,9 @@ bool Renderer::debug_sample(uint32_t pixel, uint32_t sampleno, float* color3, fl
     uint32_t sl = 0xFFFFFFFFu;
     HIP_TRY(hipMemcpy(&sl, slices_[0].d_sample_slot.get(), 4, hipMemcpyDeviceToHost));
     std::fill(raw.begin(), raw.end(), 0.0f);
-    if (sl != 0xFFFFFFFFu)         // slot_L is node-major: plane q = node * nlights + light, chunk_ slots in this one-sample pass
+    if (sl != 0xFFFFFFFFu)         // slot_L is node-major: plane q = node * nlights + light, kChunk slots in this one-sample pass
         for (size_t q = 0; q < (size_t)nodes_per_sample * nl; ++q)
-            HIP_TRY(hipMemcpy(raw.data() + 3 * q, slices_[0].d_slot_L.get() + 3 * (q * chunk_ + sl), 12, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(raw.data() + 3 * q, slices_[0].d_slot_L.get() + 3 * (q * kChunk + sl), 12, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(color3, d_debug_color_.get(), 12, hipMemcpyDeviceToHost));
     for (uint32_t nd = 0; nd < nodes_per_sample; ++nd) {
         float acc[3] = { 0.0f, 0.0f, 0.0f };

@@ -102,7 +102,6 @@ private:
     struct Slice {
         hipStream_t stream = nullptr;            // slice 0 runs on the renderer's main stream
         hipEvent_t done = nullptr;
-        hipEvent_t ev_ready = nullptr, ev_traced = nullptr;   // slice stream -> trace stream -> slice stream, per round (render())
         std::vector<uint32_t> rows;              // this slice's rows (host copy of d_rows)
         DeviceBuffer<uint32_t> d_rows;
         DeviceBuffer<uint32_t> d_ctrl;           // per round: chunk cursors
@@ -127,10 +126,6 @@ private:
     bool ensure_pass_capacity(Slice& sl, size_t nsamples);
     void free_pass_buffers();
     bool assign_slice_rows(uint32_t nslices);
-    struct PassRun { Slice* sl = nullptr; DPass ps; DCamera cam; uint32_t rounds = 0; bool live = false; };
-    bool pass_begin(PassRun& run, Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t nrows, uint32_t spp, bool explicit_sample, uint32_t epixel, uint32_t esample, uint32_t row_wrap);
-    bool pass_round(PassRun& run, uint32_t r, hipStream_t trace_stream, int trace_blocks_per_cu);
-    bool pass_end(PassRun& run);
     bool run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t nrows, uint32_t spp, bool explicit_sample, uint32_t epixel, uint32_t esample, uint32_t row_wrap = 0xFFFFFFFFu);
     void describe_pass(DPass& ps, const Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t row_wrap, uint32_t npix, size_t nsamples, uint32_t chunk,
                        bool explicit_sample, uint32_t epixel, uint32_t esample) const;
@@ -154,7 +149,6 @@ private:
     template <class T> bool upload(T*& dptr, const void* src, size_t bytes);     // a scene array: owned by scene_bufs_
 
     int num_cus_ = 0;
-    hipStream_t trace_stream_ = nullptr;         // the trace launches of a multi-slice frame, round by round
     hipStream_t stream_ = nullptr;
     hipEvent_t ev_begin_ = nullptr, ev_end_ = nullptr;
     std::vector<hipEvent_t> ev_pool_;
@@ -195,12 +189,12 @@ private:
     Slice slices_[kMaxSlices];
     uint32_t rows_assigned_for_ = 0;     // number of slices the row lists were last split into
     uint32_t active_slices_ = 1;         // slices used by the call in flight (begin_call .. end_call)
-    uint32_t chunk_ = 256;               // primary samples per work chunk
+    // primary samples per work chunk of the wavefront passes: 256 / 128 / 64 -> 23.1 / 24.6 / 28.4 ms per frame, smaller chunks cost more per chunk than
+    // they balance (profiles/r03_notes.md)
+    static constexpr uint32_t kChunk = 256;
     static constexpr size_t kGuardBytes = 256;
     static constexpr uint32_t kMinChunk = 16;   // smallest chunk any launcher cuts a pass into (the fused 50-row launch: 16 / 32 / 64)
     uint32_t max_level_nodes_ = 1;
-    uint32_t leaf_threshold_ = 16;
-    mutable uint32_t refill_primary_ = 48;   // refill threshold of the primary trace launch (describe_pass)
     bool alloc_failed_ = false;          // the last ensure_pass_capacity failure was an out-of-memory
     uint32_t records_per_sample_ = 1;
     uint32_t nlights_ = 0;

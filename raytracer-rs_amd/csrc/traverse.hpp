@@ -286,9 +286,6 @@ __device__ __forceinline__ void inner_pred(const DScene& sc, RayState& s, int* s
     const uint32_t off = pred ? (uint32_t)s.node << 5 : 0u;           // 32-byte nodes, unsigned 32-bit byte offset
     const char* __restrict__ base = (const char*)sc.nodes;
     const uint4 q0 = *(const uint4*)(base + off), q1 = *(const uint4*)(base + off + 16u);
-#ifdef MI355RT_EXP_EXTRALOAD     // timing experiment (same results): one more divergent 16-byte load per inner step, its value unused — is the step bound by the vector memory pipe?  (yes: +22 % trace time, profiles/r03_notes.md)
-    { const uint4 qx = *(const uint4*)((const char*)sc.tris + off); asm volatile("" : : "v"(qx.x), "v"(qx.y), "v"(qx.z), "v"(qx.w)); }
-#endif
     float tn0, tf0, tn1, tf1;
     slab_child(q0, s, tn0, tf0);
     slab_child(q1, s, tn1, tf1);
@@ -505,9 +502,6 @@ __device__ inline void confirm_walk(const DScene& sc, f3 o, f3 d, float& t, floa
             }
             mn = mk3(px ? a.x : -b.x, py ? a.y : -b.y, pz ? a.z : -b.z);
             mx = mk3(px ? b.x : -a.x, py ? b.y : -a.y, pz ? b.z : -a.z);
-#ifdef MI355RT_EXP_FASTONLY      // timing experiment (wrong results): what the walk costs when nothing ever leaves the fast descent
-            return;
-#endif
         }
         if (info.x < 0) {
             // ---- leaf (reached => not skippable): what does intersect_leaf_triangles + contains give?

@@ -22,7 +22,7 @@ for i in range(n):
         fz.one_case(pkg, O, scenes, rng, verbose=False)
     except AssertionError as e:
         print("case %d fails: %s" % (i, str(e)[:300]), flush=True)
-        for sw in ("MI355RT_NO_RASTER", "MI355RT_NO_CULL_MASK", "MI355RT_NO_LIGHT_MAP", "MI355RT_NO_SPECULATE", "MI355RT_NO_FUSED", "MI355RT_NO_LIVE", "MI355RT_NO_CULL_CACHE", "MI355RT_NO_CULL", "MI355RT_NO_FUSE_PRIMARY"):
+        for sw in ("MI355RT_NO_RASTER", "MI355RT_NO_CULL_MASK", "MI355RT_NO_LIGHT_MAP", "MI355RT_NO_SPECULATE", "MI355RT_NO_FUSED", "MI355RT_NO_CULL_CACHE", "MI355RT_NO_CULL"):
             os.environ[sw] = "1"
             r = np.random.default_rng(0); r.bit_generator.state = copy.deepcopy(state)
             try:
