@@ -176,6 +176,52 @@ int mi355rt_render_async(mi355rt_handle* h, uint32_t spp);
 /* counters of the last trace_frame_additive / render call (waits for an asynchronous call to finish) */
 int mi355rt_last_counts(mi355rt_handle* h, mi355rt_ray_counts* counts);
 
+/* ---- adaptive sampling: render until every tile's noise meets a target (no reference counterpart).
+ * The image is cut into image-aligned tiles of MI355RT_ADAPTIVE_TILE x MI355RT_ADAPTIVE_TILE pixels (clipped at the right and
+ * bottom edges).  A tile's owned pixels are those of the handle's owned rows ((row / stripe_rows) % stripe_world == stripe_rank).
+ * With n = film_n, s = film_sum[c], q = film_sumsq[c] a pixel is SETTLED when n >= 2, n >= min_spp and, for each of the three
+ * channels c, the test below holds, evaluated in f32, unfused, in exactly this order (a NaN does not pass):
+ *     fn  = (float)n
+ *     lhs = fn*q - s*s
+ *     m   = max(s, abs_floor*fn)
+ *     rhs = (rel_error*rel_error) * ((fn - 1.0f) * (m*m))
+ *     pass iff lhs <= rhs
+ * i.e. "standard error of the mean <= rel_error * max(mean, abs_floor)" with the divisions multiplied out.
+ * A tile is ACTIVE when some owned pixel of it is not settled AND (max n over its owned pixels) + batch_spp <= max_spp.
+ * One round: compute the active tiles from the current film; stop if none is active or max_rounds rounds were rendered; otherwise
+ * add exactly batch_spp samples (sample numbers film_n + s, as mi355rt_render numbers them) to every owned pixel of every active
+ * tile and to no other pixel — no ray of any kind is traced for a pixel outside the active tiles.  The call's counters
+ * (mi355rt_last_counts) are summed over the rounds and count the added samples only (primary == samples_added).
+ * The call is synchronous; a queued mi355rt_render_async or drop-in speculation is settled first.  Device groups
+ * (config.device_count > 1) are not supported: MI355RT_E_INVALID. */
+#define MI355RT_ADAPTIVE_TILE 8u
+typedef struct mi355rt_adaptive_config {
+    uint32_t min_spp;     /* >= 2: a pixel with fewer samples is never settled */
+    uint32_t max_spp;     /* >= min_spp: no round pushes a pixel beyond this */
+    uint32_t batch_spp;   /* >= 1: samples added per round to each owned pixel of an active tile */
+    uint32_t max_rounds;  /* 0: until no tile is active */
+    float rel_error;      /* >= 0, finite */
+    float abs_floor;      /* >= 0, finite: means below this are judged against it (dark pixels) */
+} mi355rt_adaptive_config;
+
+typedef struct mi355rt_adaptive_stats {
+    uint32_t rounds;               /* passes rendered */
+    uint32_t tiles;                /* tiles with >= 1 owned pixel */
+    uint32_t tiles_active_first;   /* active at the first verdict of the call */
+    uint32_t tiles_active_last;    /* active at the last verdict (0: everything settled or capped) */
+    uint64_t samples_added;        /* increase of the sum of film_n over the call */
+} mi355rt_adaptive_stats;
+
+/* min 16, max 64, batch 16, max_rounds 0, rel_error 0.05, abs_floor 0.02 (measured choice: DESIGN.md §3c) */
+void mi355rt_adaptive_default_config(mi355rt_adaptive_config* cfg);
+/* Rounds as above until no tile is active (or max_rounds).  An invalid config returns MI355RT_E_INVALID, names the field in
+ * mi355rt_last_error and leaves the film untouched.  stats may be NULL. */
+int mi355rt_render_adaptive(mi355rt_handle* h, const mi355rt_adaptive_config* cfg, mi355rt_adaptive_stats* stats);
+/* The verdict the next round would use, without rendering: out[ty * tiles_x + tx] = 1 if the tile is active, else 0
+ * (tiles_x = ceil(width / MI355RT_ADAPTIVE_TILE), ntiles >= tiles_x * ceil(height / MI355RT_ADAPTIVE_TILE)).
+ * Returns the number of active tiles, or a negative error code. */
+int mi355rt_adaptive_tile_mask(mi355rt_handle* h, const mi355rt_adaptive_config* cfg, uint8_t* out, size_t ntiles);
+
 /* RayTracer::get_tonemapped_pixels, mod.rs:120-128: width*height u32 0xAARRGGBB (A = 255). */
 int mi355rt_get_tonemapped_pixels(mi355rt_handle* h, uint32_t* out, size_t n);
 /* Same, written to DEVICE memory on the handle's device (e.g. a buffer owned by the caller's

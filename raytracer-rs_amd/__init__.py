@@ -90,6 +90,22 @@ class RayCounts(C.Structure):
         return d
 
 
+ADAPTIVE_TILE = 8          # MI355RT_ADAPTIVE_TILE: adaptive sampling decides per image tile of 8 x 8 pixels
+
+
+class AdaptiveConfig(C.Structure):
+    _fields_ = [("min_spp", C.c_uint32), ("max_spp", C.c_uint32), ("batch_spp", C.c_uint32), ("max_rounds", C.c_uint32),
+                ("rel_error", C.c_float), ("abs_floor", C.c_float)]
+
+
+class AdaptiveStats(C.Structure):
+    _fields_ = [("rounds", C.c_uint32), ("tiles", C.c_uint32), ("tiles_active_first", C.c_uint32), ("tiles_active_last", C.c_uint32),
+                ("samples_added", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 # every symbol include/mi355rt.h declares: (name, restype, argtypes)
 _H = C.c_void_p
 _F = C.POINTER(C.c_float)
@@ -106,6 +122,9 @@ ABI = [
     ("mi355rt_render", C.c_int, [_H, C.c_uint32, C.POINTER(RayCounts)]),
     ("mi355rt_render_async", C.c_int, [_H, C.c_uint32]),
     ("mi355rt_last_counts", C.c_int, [_H, C.POINTER(RayCounts)]),
+    ("mi355rt_adaptive_default_config", None, [C.POINTER(AdaptiveConfig)]),
+    ("mi355rt_render_adaptive", C.c_int, [_H, C.POINTER(AdaptiveConfig), C.POINTER(AdaptiveStats)]),
+    ("mi355rt_adaptive_tile_mask", C.c_int, [_H, C.POINTER(AdaptiveConfig), C.POINTER(C.c_uint8), C.c_size_t]),
     ("mi355rt_get_tonemapped_pixels", C.c_int, [_H, _U, C.c_size_t]),
     ("mi355rt_tonemap_owned_rows_device", C.c_int, [_H, C.c_void_p, C.c_size_t]),
     ("mi355rt_tonemap_owned_rows_device_on_stream", C.c_int, [_H, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -195,6 +214,17 @@ def default_config(width=1024, height=768, **kw):
     for k, v in kw.items():
         if not hasattr(cfg, k):
             raise TypeError("unknown config field %r" % k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+def adaptive_config(**kw):
+    """mi355rt_adaptive_default_config with the given fields replaced (min_spp, max_spp, batch_spp, max_rounds, rel_error, abs_floor)"""
+    cfg = AdaptiveConfig()
+    lib().mi355rt_adaptive_default_config(C.byref(cfg))
+    for k, v in kw.items():
+        if not hasattr(cfg, k):
+            raise TypeError("unknown adaptive config field %r" % k)
         setattr(cfg, k, v)
     return cfg
 
@@ -309,6 +339,27 @@ class RayTracer:
         rc = RayCounts()
         self._check(lib().mi355rt_last_counts(self._h, C.byref(rc)))
         return rc
+
+    def render_adaptive(self, **cfg):
+        """Adaptive sampling (include/mi355rt.h, mi355rt_render_adaptive): rounds of batch_spp samples in the tiles whose noise is above the
+        target until none is left.  Fields not given keep mi355rt_adaptive_default_config's values.  Returns the stats as a dict;
+        last_counts() holds the call's ray counters."""
+        c = adaptive_config(**cfg)
+        st = AdaptiveStats()
+        self._check(lib().mi355rt_render_adaptive(self._h, C.byref(c), C.byref(st)))
+        return st.as_dict()
+
+    def adaptive_tile_mask(self, **cfg):
+        """the verdict the next adaptive round would use: uint8[tiles_y, tiles_x], 1 = active"""
+        c = adaptive_config(**cfg)
+        tx = (self.width + ADAPTIVE_TILE - 1) // ADAPTIVE_TILE
+        ty = (self.height + ADAPTIVE_TILE - 1) // ADAPTIVE_TILE
+        out = np.zeros((ty, tx), np.uint8)
+        rc = lib().mi355rt_adaptive_tile_mask(self._h, C.byref(c), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size)
+        if rc < 0:
+            self._check(rc)
+        assert rc == int(out.sum())
+        return out
 
     def set_seed(self, seed):
         self._check(lib().mi355rt_set_seed(self._h, seed))

@@ -4,9 +4,12 @@
 // (main.rs:197-216: trace_frame_additive -> get_tonemapped_pixels -> print stats), with the window
 // replaced by an optional image file.  Additions: --spp N (whole frames of N samples per pixel through
 // mi355rt_render instead of the 50-row calls), --seed S, --gpus N (a device group: the N GPUs of this process share the
-// rows, mi355rt_config.device_count), --out file.ppm | file.png, --fix-row-index.
+// rows, mi355rt_config.device_count), --out file.ppm | file.png, --fix-row-index, and adaptive sampling in place of --spp:
+// --adaptive REL (mi355rt_render_adaptive with rel_error REL) with --abs-floor F, --min-spp N, --max-spp N, --batch N (defaults:
+// mi355rt_adaptive_default_config).
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <zlib.h>
@@ -63,6 +66,10 @@ int main(int argc, char** argv)
     size_t frame_iterations = 0, spp = 0, seed = 1, gpus = 1;
     bool have_iterations = false, fix_row = false, share_device = false, device_lbvh = false;
     std::string out;
+    bool adaptive = false;
+    mi355rt_adaptive_config acfg;
+    mi355rt_adaptive_default_config(&acfg);
+    auto parse_float = [](const char* s, float& out) { if (!s || !*s) return false; char* end = nullptr; const float f = std::strtof(s, &end); if (*end != '\0' || !std::isfinite(f)) return false; out = f; return true; };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
@@ -79,15 +86,21 @@ int main(int argc, char** argv)
         else if (a == "--out") { if (v) out = take(); }
         else if (a == "--fix-row-index") fix_row = true;
         else if (a == "--device-lbvh") device_lbvh = true;
+        else if (a == "--adaptive") { float f; if (parse_float(take(), f)) { acfg.rel_error = f; adaptive = true; } }
+        else if (a == "--abs-floor") { float f; if (parse_float(take(), f)) acfg.abs_floor = f; }
+        else if (a == "--min-spp") { size_t t; if (parse_usize(take(), t)) acfg.min_spp = (uint32_t)t; }
+        else if (a == "--max-spp") { size_t t; if (parse_usize(take(), t)) acfg.max_spp = (uint32_t)t; }
+        else if (a == "--batch") { size_t t; if (parse_usize(take(), t)) acfg.batch_spp = (uint32_t)t; }
         else if (a == "-h" || a == "--help") {
             std::printf("raytracer-rs (MI355X) 0.1.0\nusage: raytracer [-f COLLADA_FILENAME] [-m MAX_TRIS] [-i FRAME_ITERATIONS] [--width W] [--height H]\n"
-                        "                 [--spp N] [--seed S] [--gpus N] [--out image.ppm|image.png] [--fix-row-index] [--device-lbvh]\n");
+                        "                 [--spp N] [--seed S] [--gpus N] [--out image.ppm|image.png] [--fix-row-index] [--device-lbvh]\n"
+                        "                 [--adaptive REL [--abs-floor F] [--min-spp N] [--max-spp N] [--batch N]]\n");
             return 0;
         }
     }
     std::printf("max triangles per leaf: %zu\n", max_triangles);      // main.rs:66
     if (have_iterations) std::printf("will quit after %zu frame iterations\n", frame_iterations);   // main.rs:73
-    if (!have_iterations) { frame_iterations = spp ? 1 : (height + 49) / 50; }   // headless: one sweep of the frame
+    if (!have_iterations) { frame_iterations = (spp || adaptive) ? 1 : (height + 49) / 50; }   // headless: one sweep of the frame
 
     try {
         mi355rt_config cfg = raytracer_lib::make_config(max_triangles, width, height);
@@ -103,7 +116,14 @@ int main(int argc, char** argv)
         std::vector<uint32_t> ldr;
         for (size_t it = 0; it < frame_iterations; ++it) {
             uint32_t num_primary_rays;
-            if (spp) {
+            if (adaptive) {
+                const mi355rt_adaptive_stats st = rt.render_adaptive(acfg);
+                const mi355rt_ray_counts c = rt.last_counts();
+                num_primary_rays = (uint32_t)c.primary;
+                std::printf("adaptive: %u rounds, %u of %u tiles active at the first verdict, %u at the last, %llu samples added (%.2f per owned pixel)  %.3f ms\n",
+                            st.rounds, st.tiles_active_first, st.tiles, st.tiles_active_last, (unsigned long long)st.samples_added,
+                            (double)st.samples_added / ((double)mi355rt_owned_rows(rt.handle()) * (double)width), c.total_ms);
+            } else if (spp) {
                 mi355rt_ray_counts c = rt.render((uint32_t)spp);
                 num_primary_rays = (uint32_t)c.primary;
                 std::printf("frame: %.3f ms  rays: %llu primary %llu bounce %llu shadow -> %.1f Mrays/s\n", c.total_ms,

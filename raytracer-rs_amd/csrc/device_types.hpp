@@ -115,6 +115,17 @@ struct DPass {
     uint32_t* live;
     uint32_t* live_count;
     uint32_t live_cap;
+    // Adaptive sampling: one byte per image tile of kAdaptiveTile x kAdaptiveTile pixels, tile (row / 8) * tiles_x + x / 8; a sample
+    // whose pixel lies in a tile whose byte is 0 is not rendered at all (no ray, no film update).  null: every pixel is active.
+    const uint8_t* tile_active;
+    uint32_t tiles_x;
+};
+constexpr uint32_t kAdaptiveTile = 8;      // MI355RT_ADAPTIVE_TILE
+struct AdaptiveArgs {         // adaptive_tiles_kernel: the image, the handle's stripe ownership and the config of the call
+    uint32_t width, height, tiles_x, tiles_y;
+    uint32_t stripe_rows, stripe_world, stripe_rank;
+    uint32_t min_spp, max_spp, batch_spp;
+    float rel_error, abs_floor;
 };
 
 struct DCounters {            // one set per render call, zeroed at its start

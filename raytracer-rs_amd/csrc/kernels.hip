@@ -317,9 +317,32 @@ __device__ __forceinline__ bool chunk_is_culled(const DCamera& cam, const DPass&
     return __ballot(word != 0u) == 0ull;
 }
 
-// the verdict, cached per pixel block of the pass when the host had it computed (DPass::block_culled), else computed here
+// Adaptive sampling (DPass::tile_active): is this pixel's tile rendered in this pass?
+__device__ __forceinline__ bool pixel_active(const DPass& ps, uint32_t width, uint32_t pixel)
+{
+    if (ps.tile_active == nullptr) return true;
+    const uint32_t row = pixel / width, x = pixel - row * width;
+    return ps.tile_active[(row / kAdaptiveTile) * ps.tiles_x + x / kAdaptiveTile] != 0u;
+}
+// the samples of a chunk whose pixel is active (n without a tile mask); wave-uniform control flow: one ballot per 64 samples
+__device__ __forceinline__ uint32_t chunk_active_samples(const DCamera& cam, const DPass& ps, uint32_t chunk, uint32_t n)
+{
+    if (ps.tile_active == nullptr || ps.use_explicit) return n;
+    uint32_t cnt = 0u;
+    for (uint32_t it = 0; it < n; it += 64u) {
+        const uint32_t i = it + (uint32_t)lane_id();
+        bool on = false;
+        if (i < n) { uint32_t s, p; sample_of(ps, chunk * ps.chunk + i, s, p); on = pixel_active(ps, cam.width, pass_pixel(ps, cam.width, p)); }
+        cnt += (uint32_t)__popcll(__ballot(on));
+    }
+    return cnt;
+}
+
+// the verdict, cached per pixel block of the pass when the host had it computed (DPass::block_culled), else computed here.  A chunk without a sample
+// in an active tile (adaptive sampling) is treated as culled by every launch: no rays, no slots, never on a live list.
 __device__ __forceinline__ bool chunk_culled(const DCamera& cam, const DPass& ps, uint32_t chunk, uint32_t n)
 {
+    if (ps.tile_active != nullptr && chunk_active_samples(cam, ps, chunk, n) == 0u) return true;
     if (ps.block_culled != nullptr) return ((const_u1_ptr)(uintptr_t)ps.block_culled)[chunk % ps.cull_blocks] != 0u;
     return chunk_is_culled(cam, ps, chunk, n);
 }
@@ -458,10 +481,12 @@ __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam,
                 const uint32_t i = w_next + rank;
                 f3 o, d;
                 bool shadow = false;
+                int start = sc.root;
                 if (PRIMARY) {
                     uint32_t pixel, sampleno;
                     primary_sample(cam, ps, film_n, w_chunk * ps.chunk + i, pixel, sampleno, o, d);
                     rec = w_chunk * ps.region + i;
+                    if (!pixel_active(ps, cam.width, pixel)) start = kNodeFin;    // adaptive sampling: finished at once, a miss that was never traced
                 } else {
                     // record index in 32 bits, byte offsets in 64 (a whole 1080p x 64 spp frame in ONE pass is 531 M records of 16 B per plane);
                     // the planes of the queue are wave-uniform base pointers
@@ -479,7 +504,7 @@ __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam,
                         if (!CONFIRM || sc.oct_single_leaf) rec = __float_as_uint(r0.w);           // float index of its light term in slot_L (shade kernel)
                     } else { o = mk3(r0.x, r0.y, r0.z); d = mk3(r0.w, r1.x, r1.y); }
                 }
-                ray_init(rs, o, d, shadow, sc.root);
+                ray_init(rs, o, d, shadow, start);
             }
             w_next += min((uint32_t)__popcll(idle), avail);
             idle = __ballot(rs.node == kNodeIdle);
@@ -611,18 +636,20 @@ __global__ __launch_bounds__(kBlock) void trace_octree_kernel(DScene sc, DCamera
         for (uint32_t i = (uint32_t)lane_id(); i < n_tot; i += 64u) {
             f3 o, d;
             size_t r = 0;
+            bool on = true;
             if (PRIMARY) {
                 uint32_t pixel, sampleno;
                 primary_sample(cam, ps, film_n, chunk * ps.chunk + i, pixel, sampleno, o, d);
                 r = (size_t)chunk * ps.region + i;
+                on = pixel_active(ps, cam.width, pixel);          // adaptive sampling: an inactive pixel's sample is a miss that is never traced
             } else {
                 r = record_index(ps, chunk, i, n_rad);
                 const float4 r0 = in_q[r];
                 if (i < n_rad) { const float4 r1 = in_q[ps.qstride + r]; o = mk3(r0.x, r0.y, r0.z); d = mk3(r0.w, r1.x, r1.y); }
                 else shadow_ray_of(sc, ps, r0, o, d);
             }
-            float t, u, v; uint32_t prim;
-            octree_intersect(sc, o, d, t, u, v, prim);
+            float t, u, v; uint32_t prim = kMiss;
+            if (on) octree_intersect(sc, o, d, t, u, v, prim);
             if (i < n_rad) {
                 ps.hit_prim[r] = prim;
                 if (prim != kMiss) hits[r] = make_float4(t, u, v, __uint_as_float(prim));
@@ -826,7 +853,8 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
         if (PRIMARY && chunk_culled(cam, ps, chunk, n_rad)) {
             // no hit records were written for this chunk: every sample is a miss (with cached verdicts the resolve launch knows that too and reads no slot)
             if (ps.block_culled == nullptr) for (uint32_t i = (uint32_t)lane; i < n_rad; i += 64u) sample_slot[chunk * ps.chunk + i] = kMiss;
-            acc_hits += (unsigned long long)n_rad << 32;         // high half: primary samples skipped by the frustum culling
+            // high half: primary samples skipped by the frustum culling (adaptive sampling: only those of active tiles — the others are not samples of the call)
+            acc_hits += (unsigned long long)chunk_active_samples(cam, ps, chunk, n_rad) << 32;
             n_rad = 0u;
         }
         // ---- compact the rays that hit something (wave64 ballot + prefix popcount into LDS)
@@ -837,9 +865,12 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
             float4 found = make_float4(0, 0, 0, 0);
             if (RASTER) {
                 f3 ro, rd; float bt, bu, bv; uint32_t bprim;
-                const uint32_t tested = raster_tile(sc, cam, ps, film_n, chunk, it, i < n_rad, ro, rd, bt, bu, bv, bprim);
-                if (acc_tris) *acc_tris += (unsigned long long)tested * (unsigned long long)__popcll(__ballot(i < n_rad));
-                valid = i < n_rad && bprim != kMiss;
+                // adaptive sampling: a lane whose pixel is inactive is out of range — no ray, a miss, counted nowhere
+                bool in = i < n_rad;
+                if (ps.tile_active != nullptr && in) { uint32_t s, p; sample_of(ps, chunk * ps.chunk + i, s, p); in = pixel_active(ps, cam.width, pass_pixel(ps, cam.width, p)); }
+                const uint32_t tested = raster_tile(sc, cam, ps, film_n, chunk, it, in, ro, rd, bt, bu, bv, bprim);
+                if (acc_tris) *acc_tris += (unsigned long long)tested * (unsigned long long)__popcll(__ballot(in));
+                valid = in && bprim != kMiss;
                 found = make_float4(bt, bu, bv, __uint_as_float(bprim));
             } else valid = i < n_rad && ld1<2>(&ps.hit_prim[base + i]) != kMiss;
             uint32_t n_new;
@@ -1094,8 +1125,11 @@ __global__ __launch_bounds__(256) void resolve_kernel(DPass ps, uint32_t width, 
     const int group_lane0 = lane_id() & ~(int)(kResolveLanes - 1u);
     // every sample of a pixel in a culled block is a miss: no slot to look up (the primary shade launch wrote none)
     const bool dead = ps.block_culled != nullptr && ps.block_culled[(uint32_t)(sample_index(ps, 0u, p) / ps.chunk) % ps.cull_blocks] != 0u;
+    // adaptive sampling: an inactive pixel's slots may be stale (a skipped chunk with a cached verdict writes none) and its film is not written at all;
+    // its lanes still run the exchange loop below with the rest of the wave
+    const bool on = ps.use_explicit || pixel_active(ps, width, pixel);
     for (uint32_t s0 = 0; s0 < spp; s0 += kResolveLanes) {
-        const uint32_t sl = (s0 + j < spp && !dead) ? sample_slot[sample_index(ps, s0 + j, p)] : 0xFFFFFFFFu;
+        const uint32_t sl = (s0 + j < spp && !dead && on) ? sample_slot[sample_index(ps, s0 + j, p)] : 0xFFFFFFFFu;
         const float* L = slot_L + 3ull * (size_t)sl;       // the slot's entry of plane 0; plane q is 3 * q * nslots floats further
         f3 c = mk3(0.0f, 0.0f, 0.0f);                                   // primary miss: RGB::black(), mod.rs:100
         if (sl != 0xFFFFFFFFu) switch (ps.recursions) {
@@ -1116,7 +1150,7 @@ __global__ __launch_bounds__(256) void resolve_kernel(DPass ps, uint32_t width, 
             }
         }
     }
-    if (!ps.use_explicit && live && j == 0u) {
+    if (!ps.use_explicit && live && on && j == 0u) {
         film_sum[3ull * pixel] = sum.x; film_sum[3ull * pixel + 1] = sum.y; film_sum[3ull * pixel + 2] = sum.z;
         film_sumsq[3ull * pixel] = sumsq.x; film_sumsq[3ull * pixel + 1] = sumsq.y; film_sumsq[3ull * pixel + 2] = sumsq.z;
         film_n[pixel] = n;
@@ -1336,6 +1370,53 @@ hipError_t launch_film_stat(hipStream_t stream, bool variances, size_t npix, con
 {
     if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(film_stat_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, variances ? 1 : 0, npix, film_sum, film_sumsq, film_n, out);
+    return hipGetLastError();
+}
+
+// ---- adaptive sampling: the verdict of every tile (include/mi355rt.h) ----------------------------------------------
+// One wave per tile of kAdaptiveTile x kAdaptiveTile pixels, one lane per pixel.  out[tile] = 1 when some owned pixel is not settled and the
+// round's batch keeps every owned pixel within max_spp; *count += (owned pixels of the tile << 32) | 1 per active tile (one atomic per wave).
+__global__ __launch_bounds__(kBlock) void adaptive_tiles_kernel(AdaptiveArgs a, const float* __restrict__ film_sum, const float* __restrict__ film_sumsq,
+                                                                const uint32_t* __restrict__ film_n, uint8_t* __restrict__ out, unsigned long long* count)
+{
+    static_assert(kAdaptiveTile * kAdaptiveTile == 64, "one lane per pixel of a tile");
+    const uint32_t tile = global_wave_id();
+    if (tile >= a.tiles_x * a.tiles_y) return;                        // whole waves
+    const uint32_t lane = (uint32_t)lane_id(), ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+    const uint32_t x = tx * kAdaptiveTile + (lane % kAdaptiveTile), y = ty * kAdaptiveTile + lane / kAdaptiveTile;
+    const bool owned = x < a.width && y < a.height && (y / a.stripe_rows) % a.stripe_world == a.stripe_rank;
+    uint32_t n = 0u;
+    bool unsettled = false;
+    if (owned) {
+        const size_t p = (size_t)y * a.width + x;
+        n = film_n[p];
+        bool settled = n >= 2u && n >= a.min_spp;
+        // the criterion of include/mi355rt.h, f32, unfused (-ffp-contract=off), in this order; a NaN fails the comparison
+        const float fn = (float)n, rel2 = a.rel_error * a.rel_error;
+        for (int c = 0; c < 3; ++c) {
+            const float s = film_sum[3 * p + c], q = film_sumsq[3 * p + c];
+            const float lhs = fn * q - s * s;
+            const float m = fmaxf(s, a.abs_floor * fn);
+            const float rhs = rel2 * ((fn - 1.0f) * (m * m));
+            settled = settled && lhs <= rhs;
+        }
+        unsettled = !settled;
+    }
+    const unsigned long long busy = __ballot(unsettled), own = __ballot(owned);
+    uint32_t max_n = n;
+    for (int off = 32; off > 0; off >>= 1) max_n = max(max_n, (uint32_t)__shfl_xor((int)max_n, off, 64));
+    const bool active = busy != 0ull && (uint64_t)max_n + a.batch_spp <= (uint64_t)a.max_spp;
+    if (lane == 0u) {
+        out[tile] = active ? 1u : 0u;
+        if (active) atomicAdd(count, ((unsigned long long)__popcll(own) << 32) | 1ull);
+    }
+}
+hipError_t launch_adaptive_tiles(hipStream_t stream, const AdaptiveArgs& a, const float* film_sum, const float* film_sumsq, const uint32_t* film_n,
+                                 uint8_t* out, unsigned long long* count)
+{
+    const size_t ntiles = (size_t)a.tiles_x * a.tiles_y;
+    if (ntiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(adaptive_tiles_kernel, dim3((unsigned)((ntiles + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, stream, a, film_sum, film_sumsq, film_n, out, count);
     return hipGetLastError();
 }
 

@@ -41,6 +41,9 @@ hipError_t launch_film_clear_rows(hipStream_t stream, const uint32_t* rows, uint
 hipError_t launch_film_rows_copy(hipStream_t stream, const uint32_t* rows, uint32_t first, uint32_t total, uint32_t nown, uint32_t width,
                                  float* film_sum, float* film_sumsq, uint32_t* film_n, float* bk_sum, float* bk_sumsq, uint32_t* bk_n, bool restore);
 hipError_t launch_slab(hipStream_t stream, const float* inv_rays6, const float* cubes6, uint32_t n, uint8_t* hit, float* tmin);
+// adaptive sampling: out[tile] = the tile is active; *count (zeroed by the caller) += (owned pixels << 32) | 1 per active tile
+hipError_t launch_adaptive_tiles(hipStream_t stream, const AdaptiveArgs& a, const float* film_sum, const float* film_sumsq, const uint32_t* film_n,
+                                 uint8_t* out, unsigned long long* count);
 hipError_t launch_film_stat(hipStream_t stream, bool variances, size_t npix, const float* film_sum, const float* film_sumsq, const uint32_t* film_n, float* out);
 // the gather microbenchmark behind bench.py's roofline: num_cus * 8 blocks walk `steps` random nodes of `table` each
 hipError_t launch_gather_rate(hipStream_t stream, int num_cus, const void* table, uint32_t nnodes, uint32_t steps, uint32_t* sink);

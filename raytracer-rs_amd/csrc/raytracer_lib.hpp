@@ -75,6 +75,19 @@ public:
         if (mi355rt_render(h_, spp, &c) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
         return c;
     }
+    // adaptive sampling (include/mi355rt.h): rounds of cfg.batch_spp samples in the tiles whose noise is above the target until none is left
+    mi355rt_adaptive_stats render_adaptive(const mi355rt_adaptive_config& cfg)
+    {
+        mi355rt_adaptive_stats st{};
+        if (mi355rt_render_adaptive(h_, &cfg, &st) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+        return st;
+    }
+    mi355rt_ray_counts last_counts()
+    {
+        mi355rt_ray_counts c{};
+        if (mi355rt_last_counts(h_, &c) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+        return c;
+    }
     mi355rt_handle* handle() const { return h_; }
 private:
     mi355rt_handle* h_;

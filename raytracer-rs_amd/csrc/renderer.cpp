@@ -734,7 +734,8 @@ void Renderer::describe_pass(DPass& ps, const Slice& sl, const uint32_t* d_rows,
 
 // A wavefront pass: buffers, descriptor and cursors; then round by round trace (+ confirm) (+ shade); then resolve.  Every launch goes
 // to the slice's stream.
-bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t nrows, uint32_t spp, bool explicit_sample, uint32_t epixel, uint32_t esample, uint32_t row_wrap)
+bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t nrows, uint32_t spp, bool explicit_sample, uint32_t epixel, uint32_t esample, uint32_t row_wrap,
+                        const uint8_t* tile_active)
 {
     const uint32_t npix = explicit_sample ? 1u : nrows * cfg.width;
     const size_t nsamples = (size_t)npix * spp;
@@ -742,6 +743,7 @@ bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32
     if (!ensure_pass_capacity(sl, nsamples)) return false;
     DPass ps;
     describe_pass(ps, sl, d_rows, row0, row_wrap, npix, nsamples, kChunk, explicit_sample, epixel, esample);
+    ps.tile_active = tile_active; ps.tiles_x = tiles_x();
     // the tile bins of the primary rays need a pass that walks the slice's whole row list (render(); not the odd row windows of the other callers)
     const bool whole = !explicit_sample && d_rows == sl.d_rows.get() && row0 == 0 && nrows == sl.rows.size() && row_wrap == 0xFFFFFFFFu;
     const DCamera cam = device_camera(whole ? &ps : nullptr, whole ? &sl.rows : nullptr);
@@ -904,13 +906,19 @@ bool Renderer::queue_counts_copy()
 // wait == false (mi355rt_render_async): everything is queued — the slices joined on the main stream, the counters' copy behind them —
 // and the call returns; mi355rt_last_counts / mi355rt_synchronize wait.  Consecutive frames then run back to back on the device
 // instead of one host round trip apart (a few % of a 3 ms frame: one rank's share of a strong-scaled frame).
-bool Renderer::end_call(uint64_t primary, bool wait)
+bool Renderer::join_slices()
 {
     for (uint32_t i = 1; i < active_slices_; ++i) {          // join the slices on the main stream
         HIP_TRY(hipEventRecord(slices_[i].done, slices_[i].stream));
         HIP_TRY(hipStreamWaitEvent(stream_, slices_[i].done, 0));
     }
     active_slices_ = 1;
+    return true;
+}
+
+bool Renderer::end_call(uint64_t primary, bool wait)
+{
+    if (!join_slices()) return false;
     HIP_TRY(hipEventRecord(ev_end_, stream_));
     if (!queue_counts_copy()) return false;
     if (!wait) { counts_pending_ = true; pending_primary_ = primary; pending_timed_ = true; return true; }
@@ -1073,6 +1081,15 @@ bool Renderer::settle_speculation()
 bool Renderer::render(uint32_t spp, bool wait)
 {
     if (!begin_call()) return false;
+    if (!enqueue_frame(spp, ev_begin_, nullptr)) return false;
+    for (uint32_t r : owned_rows) ldr_dirty_[r] = 1;
+    return end_call((uint64_t)owned_rows.size() * cfg.width * spp, wait);
+}
+
+// The body of a frame: plan the passes of every slice (halving them while the device cannot hold their buffers) and queue them, each slice on its
+// own stream, forked behind `fork` on the main stream.  render() runs one; render_adaptive() one per round, with the round's tile mask.
+bool Renderer::enqueue_frame(uint32_t spp, hipEvent_t fork, const uint8_t* tile_active)
+{
     const uint32_t nrows = (uint32_t)owned_rows.size();
     if (nrows && spp) {
         // concurrent frame slices: worth their extra launches from ~32 Mi samples per slice on (measured on one rank's share of a
@@ -1119,7 +1136,7 @@ bool Renderer::render(uint32_t spp, bool wait)
             target /= 2;
         }
         // fork: the other slices start after everything already queued on the main stream
-        for (uint32_t s = 1; s < nsl; ++s) HIP_TRY(hipStreamWaitEvent(slices_[s].stream, ev_begin_, 0));
+        for (uint32_t s = 1; s < nsl; ++s) HIP_TRY(hipStreamWaitEvent(slices_[s].stream, fork, 0));
         active_slices_ = nsl;
         // Enqueue the passes round-robin so that no stream waits for the host: every slice's whole pass on its own stream.
         // Measured alternative (profiles/r02_notes.md): all trace launches on ONE stream, round by round, so that a slice's
@@ -1132,13 +1149,68 @@ bool Renderer::render(uint32_t spp, bool wait)
                 if (p >= plan[s].size()) continue;
                 any = true;
                 const PassDesc& d = plan[s][p];
-                if (!run_pass(slices_[s], slices_[s].d_rows.get(), d.r0, d.nr, d.kk, false, 0, 0)) return false;
+                if (!run_pass(slices_[s], slices_[s].d_rows.get(), d.r0, d.nr, d.kk, false, 0, 0, 0xFFFFFFFFu, tile_active)) return false;
             }
             if (!any) break;
         }
     }
+    return true;
+}
+
+// ---- adaptive sampling (include/mi355rt.h) ----------------------------------------------------------------------------
+// The verdict of the current film into d_tile_active_; tiles = active tiles, pixels = owned pixels in them.  The one host wait of a round: 8 bytes.
+bool Renderer::adaptive_verdict(const mi355rt_adaptive_config& ac, uint32_t& tiles, uint64_t& pixels)
+{
+    const size_t ntiles = (size_t)tiles_x() * tiles_y();
+    if (!d_tile_active_) HIP_TRY(d_tile_active_.alloc(ntiles, &hbm_bytes_));
+    if (!d_tile_count_) HIP_TRY(d_tile_count_.alloc(sizeof(unsigned long long), &hbm_bytes_));
+    AdaptiveArgs a{};
+    a.width = cfg.width; a.height = cfg.height; a.tiles_x = tiles_x(); a.tiles_y = tiles_y();
+    a.stripe_rows = cfg.stripe_rows; a.stripe_world = std::max(1u, cfg.stripe_world); a.stripe_rank = cfg.stripe_world > 1 ? cfg.stripe_rank : 0u;
+    a.min_spp = ac.min_spp; a.max_spp = ac.max_spp; a.batch_spp = ac.batch_spp; a.rel_error = ac.rel_error; a.abs_floor = ac.abs_floor;
+    HIP_TRY(hipMemsetAsync(d_tile_count_.get(), 0, sizeof(unsigned long long), stream_));
+    HIP_TRY(launch_adaptive_tiles(stream_, a, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_tile_active_.get(), d_tile_count_.get()));
+    unsigned long long c = 0;
+    HIP_TRY(hipMemcpyAsync(&c, d_tile_count_.get(), sizeof c, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    tiles = (uint32_t)(c & 0xFFFFFFFFull); pixels = c >> 32;
+    return true;
+}
+
+bool Renderer::adaptive_tile_mask(const mi355rt_adaptive_config& ac, uint8_t* out, uint32_t& active)
+{
+    if (!bind()) return false;
+    if (!settle_speculation()) return false;
+    uint64_t pixels = 0;
+    if (!adaptive_verdict(ac, active, pixels)) return false;
+    HIP_TRY(hipMemcpy(out, d_tile_active_.get(), (size_t)tiles_x() * tiles_y(), hipMemcpyDeviceToHost));
+    return true;
+}
+
+bool Renderer::render_adaptive(const mi355rt_adaptive_config& ac, mi355rt_adaptive_stats& st)
+{
+    st = mi355rt_adaptive_stats{};
+    std::vector<uint8_t> tile_row(tiles_y(), 0);                       // tiles with an owned pixel: whole tile rows
+    for (uint32_t r : owned_rows) tile_row[r / kAdaptiveTile] = 1;
+    for (uint8_t t : tile_row) st.tiles += t ? tiles_x() : 0u;
+    if (!begin_call()) return false;
+    uint64_t added = 0;
+    for (;;) {
+        uint32_t active = 0; uint64_t pixels = 0;
+        if (!adaptive_verdict(ac, active, pixels)) return false;
+        if (st.rounds == 0) st.tiles_active_first = active;
+        st.tiles_active_last = active;
+        if (active == 0 || (ac.max_rounds && st.rounds >= ac.max_rounds)) break;
+        // the round's passes fork behind its verdict (slice 0 runs on the main stream; its `done` event is free here)
+        HIP_TRY(hipEventRecord(slices_[0].done, stream_));
+        if (!enqueue_frame(ac.batch_spp, slices_[0].done, d_tile_active_.get())) return false;
+        if (!join_slices()) return false;                             // the next verdict reads what every slice wrote
+        ++st.rounds;
+        added += pixels * ac.batch_spp;
+    }
+    st.samples_added = added;
     for (uint32_t r : owned_rows) ldr_dirty_[r] = 1;
-    return end_call((uint64_t)nrows * cfg.width * spp, wait);
+    return end_call(added, true);
 }
 
 // get_tonemapped_pixels, mod.rs:120-128.  The reference maps the whole film on every call although one

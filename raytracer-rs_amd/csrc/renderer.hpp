@@ -22,6 +22,11 @@ public:
 
     uint32_t trace_frame_additive();                                   // mod.rs:80-117
     bool render(uint32_t spp, bool wait = true);                        // wait == false: queued only (mi355rt_render_async)
+    // adaptive sampling: rounds of ac.batch_spp samples in the active tiles until none is left; ac is validated by the caller
+    bool render_adaptive(const mi355rt_adaptive_config& ac, mi355rt_adaptive_stats& st);
+    bool adaptive_tile_mask(const mi355rt_adaptive_config& ac, uint8_t* out, uint32_t& active);     // the next round's verdict, tiles_x() * tiles_y() bytes
+    uint32_t tiles_x() const { return (cfg.width + kAdaptiveTile - 1) / kAdaptiveTile; }
+    uint32_t tiles_y() const { return (cfg.height + kAdaptiveTile - 1) / kAdaptiveTile; }
     bool get_tonemapped(uint32_t* out, size_t n);                       // mod.rs:120-128
     bool tonemap_owned_rows_device(uint32_t* device_out, size_t n, hipStream_t caller_stream = nullptr);
     bool last_counts(mi355rt_ray_counts& out);
@@ -126,7 +131,14 @@ private:
     bool ensure_pass_capacity(Slice& sl, size_t nsamples);
     void free_pass_buffers();
     bool assign_slice_rows(uint32_t nslices);
-    bool run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t nrows, uint32_t spp, bool explicit_sample, uint32_t epixel, uint32_t esample, uint32_t row_wrap = 0xFFFFFFFFu);
+    bool run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t nrows, uint32_t spp, bool explicit_sample, uint32_t epixel, uint32_t esample, uint32_t row_wrap = 0xFFFFFFFFu,
+                  const uint8_t* tile_active = nullptr);
+    // the owned rows x spp as wavefront passes on the slices (pass planning, OOM halving), forked behind `fork` on the main stream; tile_active: DPass::tile_active
+    bool enqueue_frame(uint32_t spp, hipEvent_t fork, const uint8_t* tile_active);
+    bool join_slices();                                                 // the main stream waits for the slices of the call in flight
+    bool adaptive_verdict(const mi355rt_adaptive_config& ac, uint32_t& tiles, uint64_t& pixels);    // d_tile_active_ <- the verdict of the current film
+    DeviceBuffer<uint8_t> d_tile_active_;                               // adaptive sampling: one byte per tile (DPass::tile_active)
+    DeviceBuffer<unsigned long long> d_tile_count_;                     // (owned pixels of the active tiles << 32) + active tiles
     void describe_pass(DPass& ps, const Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t row_wrap, uint32_t npix, size_t nsamples, uint32_t chunk,
                        bool explicit_sample, uint32_t epixel, uint32_t esample) const;
     bool begin_call();
