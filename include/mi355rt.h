@@ -222,6 +222,57 @@ int mi355rt_render_adaptive(mi355rt_handle* h, const mi355rt_adaptive_config* cf
  * Returns the number of active tiles, or a negative error code. */
 int mi355rt_adaptive_tile_mask(mi355rt_handle* h, const mi355rt_adaptive_config* cfg, uint8_t* out, size_t ntiles);
 
+/* ---- denoised read-out: an edge-stopping a-trous wavelet filter over the film means, guided by the variance of each mean and by the
+ * primary hit of each pixel (no reference counterpart).  It only reads: the film, the counters and every other output stay
+ * as they are (a speculative 50-row frame is settled first).  Device groups (config.device_count > 1) and striped handles
+ * (stripe_world > 1) are not supported: MI355RT_E_INVALID.
+ *
+ * GUIDES.  Pixel p of the width x height image has u = p % width and v = p / height (v = p / width with MI355RT_FLAG_FIX_ROW_INDEX: the
+ * pixel -> ray mapping of the film itself), and its guide ray is mi355rt_camera_get_ray(u, v, 0.5, 0.5), intersected as
+ * mi355rt_intersect_rays would.  A hit stores prim (global triangle index), depth = t, normal = the triangle normal shading uses
+ * (mod.rs:198-205) and albedo = shade()'s diffuse colour (mod.rs:242-248: the material colour, or its texture at the hit's (u, v)).  A miss
+ * stores prim 0xFFFFFFFF, depth 0 and a zero normal and albedo.  The guides are kept on the device and rebuilt only when the camera or the
+ * FIX_ROW_INDEX flag changes.
+ *
+ * FILTER.  Everything is f32, unfused, in the order written; pos(x) = x > 0 ? x : 0 (NaN -> 0).  From the film (n, s[3], q[3]), fn = (float)n:
+ *     n == 0 : the pixel is EMPTY: never a tap, and its output is the film mean as it stands (NaN: white once packed)
+ *     c      = s * (1.0f / fn)                                                  per channel (mi355rt_film_get_pixels)
+ *     n >= 2 : v_ch = pos(fn*q - s*s) / ((fn*fn) * (fn - 1.0f)) per channel, var = (v_r + v_g) + v_b  (the variance of the mean)
+ *     n == 1 : the variance is UNKNOWN, var = 0
+ * Iteration i = 0 .. iterations-1, step h = 1 << i, reads the previous iteration's (c, var); for every non-empty pixel p at (x, y):
+ *     W = 0, S = (0, 0, 0), V = 0
+ *     for dy = -2..2, for dx = -2..2: tap q at (x + dx*h, y + dy*h); skip it when outside the image or empty
+ *         k = K1[dx+2] * K1[dy+2], K1 = (0.0625, 0.25, 0.375, 0.25, 0.0625)
+ *         q == p: w = k
+ *         else: skip the tap when exactly one of p, q is a miss;  both miss: g = 1;  both hit:
+ *             d  = (Np.x*Nq.x + Np.y*Nq.y) + Np.z*Nq.z;  wn = pos(d), squared normal_power_log2 times
+ *             rz = |tp - tq| / (sigma_depth * tp);   wz = 1.0f / (1.0f + rz*rz)
+ *             ra = ((|Ap.r-Aq.r| + |Ap.g-Aq.g|) + |Ap.b-Aq.b|) / sigma_albedo;  wa = 1.0f / (1.0f + ra*ra)
+ *             g  = (wn * wz) * wa
+ *           wl = 1 when p or q has unknown variance, else, with L(c) = (0.2126f*c.r + 0.7152f*c.g) + 0.0722f*c.b, dl = L(cp) - L(cq):
+ *             wl = 1.0f / (1.0f + (dl*dl) / ((sigma_luminance*sigma_luminance) * (varp + varq) + 1e-12f))
+ *           w = pos((k * g) * wl)
+ *         S += w * cq (per channel);  W += w;  V += (w*w) * varq
+ *     c' = S / W (per channel), var' = V / (W*W)
+ * rgb = c after the last iteration; packed = that c mapped as mi355rt_get_tonemapped_pixels maps a film mean (c/(1+c), to u8, 0xAARRGGBB).
+ * iterations = 0 returns exactly mi355rt_film_get_pixels and mi355rt_get_tonemapped_pixels.
+ * Device memory, allocated on the first call that needs it and counted in mi355rt_hbm_allocated_bytes: 32 bytes per pixel for the guides,
+ * 52 more per pixel on the first denoised read-out. */
+typedef struct mi355rt_denoise_config {
+    uint32_t iterations;          /* 0..10; 0 = the film means unchanged */
+    uint32_t normal_power_log2;   /* 0..10 */
+    float sigma_luminance;        /* > 0, finite */
+    float sigma_depth;            /* > 0, finite */
+    float sigma_albedo;           /* > 0, finite */
+} mi355rt_denoise_config;
+/* iterations 5, normal_power_log2 7, sigma_luminance 1, sigma_depth 0.1, sigma_albedo 0.1 (measured choice: DESIGN.md §3d) */
+void mi355rt_denoise_default_config(mi355rt_denoise_config* cfg);
+/* rgb: npix*3 floats, packed: npix u32 (either may be NULL, not both); npix >= width*height.  An invalid config returns MI355RT_E_INVALID,
+ * names the field in mi355rt_last_error and writes nothing. */
+int mi355rt_get_denoised_pixels(mi355rt_handle* h, const mi355rt_denoise_config* cfg, float* rgb, uint32_t* packed, size_t npix);
+/* the guide buffers above, width*height entries each (normal3, albedo3: 3 floats per pixel); any pointer may be NULL */
+int mi355rt_get_guides(mi355rt_handle* h, float* depth, float* normal3, float* albedo3, uint32_t* prim, size_t npix);
+
 /* RayTracer::get_tonemapped_pixels, mod.rs:120-128: width*height u32 0xAARRGGBB (A = 255). */
 int mi355rt_get_tonemapped_pixels(mi355rt_handle* h, uint32_t* out, size_t n);
 /* Same, written to DEVICE memory on the handle's device (e.g. a buffer owned by the caller's

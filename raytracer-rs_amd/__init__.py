@@ -106,6 +106,11 @@ class AdaptiveStats(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class DenoiseConfig(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32),
+                ("sigma_luminance", C.c_float), ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float)]
+
+
 # every symbol include/mi355rt.h declares: (name, restype, argtypes)
 _H = C.c_void_p
 _F = C.POINTER(C.c_float)
@@ -125,6 +130,9 @@ ABI = [
     ("mi355rt_adaptive_default_config", None, [C.POINTER(AdaptiveConfig)]),
     ("mi355rt_render_adaptive", C.c_int, [_H, C.POINTER(AdaptiveConfig), C.POINTER(AdaptiveStats)]),
     ("mi355rt_adaptive_tile_mask", C.c_int, [_H, C.POINTER(AdaptiveConfig), C.POINTER(C.c_uint8), C.c_size_t]),
+    ("mi355rt_denoise_default_config", None, [C.POINTER(DenoiseConfig)]),
+    ("mi355rt_get_denoised_pixels", C.c_int, [_H, C.POINTER(DenoiseConfig), _F, _U, C.c_size_t]),
+    ("mi355rt_get_guides", C.c_int, [_H, _F, _F, _F, _U, C.c_size_t]),
     ("mi355rt_get_tonemapped_pixels", C.c_int, [_H, _U, C.c_size_t]),
     ("mi355rt_tonemap_owned_rows_device", C.c_int, [_H, C.c_void_p, C.c_size_t]),
     ("mi355rt_tonemap_owned_rows_device_on_stream", C.c_int, [_H, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -225,6 +233,17 @@ def adaptive_config(**kw):
     for k, v in kw.items():
         if not hasattr(cfg, k):
             raise TypeError("unknown adaptive config field %r" % k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+def denoise_config(**kw):
+    """mi355rt_denoise_default_config with the given fields replaced (iterations, normal_power_log2, sigma_luminance, sigma_depth, sigma_albedo)"""
+    cfg = DenoiseConfig()
+    lib().mi355rt_denoise_default_config(C.byref(cfg))
+    for k, v in kw.items():
+        if not hasattr(cfg, k):
+            raise TypeError("unknown denoise config field %r" % k)
         setattr(cfg, k, v)
     return cfg
 
@@ -360,6 +379,24 @@ class RayTracer:
             self._check(rc)
         assert rc == int(out.sum())
         return out
+
+    def get_denoised_pixels(self, rgb=True, packed=True, **cfg):
+        """The denoised read-out of the film (include/mi355rt.h, mi355rt_get_denoised_pixels).  Fields not given keep
+        mi355rt_denoise_default_config's values.  Returns (rgb float32[npix, 3] or None, packed uint32[npix] or None)."""
+        c = denoise_config(**cfg)
+        n = self.width * self.height
+        out_rgb = np.zeros((n, 3), np.float32) if rgb else None
+        out_packed = np.zeros(n, np.uint32) if packed else None
+        self._check(lib().mi355rt_get_denoised_pixels(self._h, C.byref(c), _fp(out_rgb) if rgb else None,
+                                                      _up(out_packed) if packed else None, n))
+        return out_rgb, out_packed
+
+    def guides(self):
+        """the denoiser's guide buffers: dict(depth float32[npix], normal float32[npix, 3], albedo float32[npix, 3], prim uint32[npix])"""
+        n = self.width * self.height
+        g = dict(depth=np.zeros(n, np.float32), normal=np.zeros((n, 3), np.float32), albedo=np.zeros((n, 3), np.float32), prim=np.zeros(n, np.uint32))
+        self._check(lib().mi355rt_get_guides(self._h, _fp(g["depth"]), _fp(g["normal"]), _fp(g["albedo"]), _up(g["prim"]), n))
+        return g
 
     def set_seed(self, seed):
         self._check(lib().mi355rt_set_seed(self._h, seed))

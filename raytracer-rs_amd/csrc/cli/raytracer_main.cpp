@@ -6,7 +6,8 @@
 // mi355rt_render instead of the 50-row calls), --seed S, --gpus N (a device group: the N GPUs of this process share the
 // rows, mi355rt_config.device_count), --out file.ppm | file.png, --fix-row-index, and adaptive sampling in place of --spp:
 // --adaptive REL (mi355rt_render_adaptive with rel_error REL) with --abs-floor F, --min-spp N, --max-spp N, --batch N (defaults:
-// mi355rt_adaptive_default_config).
+// mi355rt_adaptive_default_config), and --denoise: --out receives the denoised read-out of the film (mi355rt_get_denoised_pixels,
+// mi355rt_denoise_default_config) instead of get_tonemapped_pixels.
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -66,7 +67,7 @@ int main(int argc, char** argv)
     size_t frame_iterations = 0, spp = 0, seed = 1, gpus = 1;
     bool have_iterations = false, fix_row = false, share_device = false, device_lbvh = false;
     std::string out;
-    bool adaptive = false;
+    bool adaptive = false, denoise = false;
     mi355rt_adaptive_config acfg;
     mi355rt_adaptive_default_config(&acfg);
     auto parse_float = [](const char* s, float& out) { if (!s || !*s) return false; char* end = nullptr; const float f = std::strtof(s, &end); if (*end != '\0' || !std::isfinite(f)) return false; out = f; return true; };
@@ -86,6 +87,7 @@ int main(int argc, char** argv)
         else if (a == "--out") { if (v) out = take(); }
         else if (a == "--fix-row-index") fix_row = true;
         else if (a == "--device-lbvh") device_lbvh = true;
+        else if (a == "--denoise") denoise = true;
         else if (a == "--adaptive") { float f; if (parse_float(take(), f)) { acfg.rel_error = f; adaptive = true; } }
         else if (a == "--abs-floor") { float f; if (parse_float(take(), f)) acfg.abs_floor = f; }
         else if (a == "--min-spp") { size_t t; if (parse_usize(take(), t)) acfg.min_spp = (uint32_t)t; }
@@ -94,7 +96,7 @@ int main(int argc, char** argv)
         else if (a == "-h" || a == "--help") {
             std::printf("raytracer-rs (MI355X) 0.1.0\nusage: raytracer [-f COLLADA_FILENAME] [-m MAX_TRIS] [-i FRAME_ITERATIONS] [--width W] [--height H]\n"
                         "                 [--spp N] [--seed S] [--gpus N] [--out image.ppm|image.png] [--fix-row-index] [--device-lbvh]\n"
-                        "                 [--adaptive REL [--abs-floor F] [--min-spp N] [--max-spp N] [--batch N]]\n");
+                        "                 [--adaptive REL [--abs-floor F] [--min-spp N] [--max-spp N] [--batch N]] [--denoise]\n");
             return 0;
         }
     }
@@ -136,6 +138,11 @@ int main(int argc, char** argv)
             std::printf("%s\n", stats.stats(num_primary_rays).c_str());  // main.rs:213
         }
         std::printf("%s\n\n\n", stats.mean_stats().c_str());             // main.rs:216
+        if (denoise) {                                                    // the denoised read-out of the film the loop left (default config)
+            mi355rt_denoise_config dcfg;
+            mi355rt_denoise_default_config(&dcfg);
+            ldr = rt.get_denoised_pixels(dcfg);
+        }
         if (!out.empty()) {
             const bool png = out.size() > 4 && out.compare(out.size() - 4, 4, ".png") == 0;
             if (png) {

@@ -127,6 +127,15 @@ struct AdaptiveArgs {         // adaptive_tiles_kernel: the image, the handle's 
     uint32_t min_spp, max_spp, batch_spp;
     float rel_error, abs_floor;
 };
+// Denoised read-out (include/mi355rt.h).  Guides: two float4 per pixel, (normal.xyz, t) and (albedo.rgb, prim bits); per-pixel
+// flags of one read-out: kDnHit (the guide ray hit), kDnEmpty (n == 0), kDnUnknown (n == 1: unknown variance).
+constexpr uint32_t kDnHit = 1u, kDnEmpty = 2u, kDnUnknown = 4u;
+struct DenoiseArgs {
+    uint32_t width, height;
+    uint32_t step;                // h = 1 << iteration
+    uint32_t normal_power_log2;
+    float sigma_luminance, sigma_depth, sigma_albedo;
+};
 
 struct DCounters {            // one set per render call, zeroed at its start
     unsigned long long bounce, shadow, primary_hits, nodes_visited, tris_tested;

@@ -233,6 +233,20 @@ __device__ __forceinline__ size_t sample_index(const DPass& ps, uint32_t s, uint
     return ((size_t)g * ps.npix + p) * G + (s - g * G);
 }
 
+// pixel + jitter -> ray, mod.rs:93-96 + camera.rs:80-90 (flags bit 0: MI355RT_FLAG_FIX_ROW_INDEX)
+__device__ __forceinline__ void pixel_ray(const DCamera& cam, uint32_t flags, uint32_t pixel, float xi1, float xi2, f3& o, f3& d)
+{
+    const uint32_t cu = pixel % cam.width;
+    const uint32_t cv = (flags & 1u) ? pixel / cam.width : pixel / cam.height;   // reference: idx / height
+    const float dir_x = -cam.max_x + 2.0f * cam.max_x * div_rn((float)cu + xi1, (float)cam.width);
+    const float dir_y = -cam.max_y + 2.0f * cam.max_y * div_rn((float)cv + xi2, (float)cam.height);
+    const float vx = dir_x, vy = -dir_y, vz = 1.0f, vw = 1.0f;
+    d.x = vx * cam.rot[0] + vy * cam.rot[4] + vz * cam.rot[8] + vw * cam.rot[12];
+    d.y = vx * cam.rot[1] + vy * cam.rot[5] + vz * cam.rot[9] + vw * cam.rot[13];
+    d.z = vx * cam.rot[2] + vy * cam.rot[6] + vz * cam.rot[10] + vw * cam.rot[14];
+    o = mk3(cam.origin[0], cam.origin[1], cam.origin[2]);
+}
+
 // pixel -> primary ray, mod.rs:93-96 + camera.rs:80-90.  gi = index of the primary sample in the pass.
 __device__ __forceinline__ void primary_sample(const DCamera& cam, const DPass& ps, const uint32_t* __restrict__ film_n, uint32_t gi,
                                                uint32_t& pixel, uint32_t& sampleno, f3& o, f3& d)
@@ -246,15 +260,7 @@ __device__ __forceinline__ void primary_sample(const DCamera& cam, const DPass& 
     }
     uint32_t h0 = pixel, h1 = sampleno, h2 = 0u, h3 = ps.seed;
     pcg4d(h0, h1, h2, h3);
-    const uint32_t cu = pixel % cam.width;
-    const uint32_t cv = (ps.flags & 1u) ? pixel / cam.width : pixel / cam.height;   // reference: idx / height
-    const float dir_x = -cam.max_x + 2.0f * cam.max_x * div_rn((float)cu + u01(h0), (float)cam.width);
-    const float dir_y = -cam.max_y + 2.0f * cam.max_y * div_rn((float)cv + u01(h1), (float)cam.height);
-    const float vx = dir_x, vy = -dir_y, vz = 1.0f, vw = 1.0f;
-    d.x = vx * cam.rot[0] + vy * cam.rot[4] + vz * cam.rot[8] + vw * cam.rot[12];
-    d.y = vx * cam.rot[1] + vy * cam.rot[5] + vz * cam.rot[9] + vw * cam.rot[13];
-    d.z = vx * cam.rot[2] + vy * cam.rot[6] + vz * cam.rot[10] + vw * cam.rot[14];
-    o = mk3(cam.origin[0], cam.origin[1], cam.origin[2]);
+    pixel_ray(cam, ps.flags, pixel, u01(h0), u01(h1), o, d);
 }
 
 // Frustum culling of a whole chunk of primary samples.  The samples of a chunk are a run of columns of one
@@ -1257,6 +1263,17 @@ __global__ __launch_bounds__(256) void tonemap_kernel(const uint32_t* __restrict
 // ---- batched Intersector seam (accel_intersect.rs:10-13) --------------------------------------
 // mode 0: BVH true closest hit + octree confirm (reference-default semantics); 1: the reference's octree walked
 // directly (cross-check path); 2: BVH true closest hit only (NoAccelerationIntersector semantics)
+// The hit of one radiance ray in the handle's semantics (mode as above); prim = kMiss on a miss.  stack: this lane's column of the LDS stack.
+__device__ __forceinline__ void closest_hit(const DScene& sc, const f3 o, const f3 d, int mode, int* stack, float& t, float& u, float& v, uint32_t& prim)
+{
+    if (mode == 1) { octree_intersect(sc, o, d, t, u, v, prim); return; }     // reference-exact intersector, walked directly
+    RayState rs;
+    uint32_t a = 0, b = 0;
+    ray_init(rs, o, d, false, sc.root);
+    ray_run<false>(sc, rs, stack, kBlock, a, b);
+    t = rs.t; u = rs.u; v = rs.v; prim = rs.prim;
+    if (mode == 0 && prim != kMiss) confirm_walk(sc, o, d, t, u, v, prim);   // the reference's octree decides what it would have returned
+}
 __global__ __launch_bounds__(kBlock) void intersect_kernel(DScene sc, const float* __restrict__ rays6, uint32_t n, int shadow_mode, int mode,
                                                           float* tuv, uint32_t* prim, uint8_t* blocked)
 {
@@ -1265,39 +1282,156 @@ __global__ __launch_bounds__(kBlock) void intersect_kernel(DScene sc, const floa
     if (i >= n) return;
     const f3 o = mk3(rays6[6ull * i], rays6[6ull * i + 1], rays6[6ull * i + 2]);
     const f3 d = mk3(rays6[6ull * i + 3], rays6[6ull * i + 4], rays6[6ull * i + 5]);
-    if (mode == 1) {             // reference-exact intersector, walked directly
+    if (!shadow_mode) {
+        float t, u, v; uint32_t p;
+        closest_hit(sc, o, d, mode, &s_stack[threadIdx.x], t, u, v, p);
+        prim[i] = p;
+        if (p != kMiss) { tuv[3ull * i] = t; tuv[3ull * i + 1] = u; tuv[3ull * i + 2] = v; }
+        return;
+    }
+    if (mode == 1) {
         float t, u, v; uint32_t p;
         octree_intersect(sc, o, d, t, u, v, p);
-        if (shadow_mode) blocked[i] = (p != kMiss && t > 0.01f && t < 1.0f) ? 1 : 0;
-        else {
-            prim[i] = p;
-            if (p != kMiss) { tuv[3ull * i] = t; tuv[3ull * i + 1] = u; tuv[3ull * i + 2] = v; }
-        }
+        blocked[i] = (p != kMiss && t > 0.01f && t < 1.0f) ? 1 : 0;
         return;
     }
     RayState rs;
     uint32_t a = 0, b = 0;
     if (mode == 0) {
-        // closest hit (shadow rays: on [0, 1)), then the reference's octree decides what it would have returned
+        // closest hit on [0, 1), then the reference's octree decides what it would have returned
         ray_init(rs, o, d, false, sc.root);
-        if (shadow_mode) rs.tlimit = 0x1.fffffep-1f;
+        rs.tlimit = 0x1.fffffep-1f;
         ray_run<false>(sc, rs, &s_stack[threadIdx.x], kBlock, a, b);
         float t = rs.t, u = rs.u, v = rs.v; uint32_t p = rs.prim;
         if (p != kMiss) confirm_walk(sc, o, d, t, u, v, p);
-        if (shadow_mode) blocked[i] = (p != kMiss && t > 0.01f && t < 1.0f) ? 1 : 0;
-        else {
-            prim[i] = p;
-            if (p != kMiss) { tuv[3ull * i] = t; tuv[3ull * i + 1] = u; tuv[3ull * i + 2] = v; }
-        }
+        blocked[i] = (p != kMiss && t > 0.01f && t < 1.0f) ? 1 : 0;
         return;
     }
-    ray_init(rs, o, d, shadow_mode != 0, sc.root);
+    ray_init(rs, o, d, true, sc.root);
     ray_run<false>(sc, rs, &s_stack[threadIdx.x], kBlock, a, b);
-    if (shadow_mode) blocked[i] = rs.occ == 1 ? 1 : 0;
-    else {
-        prim[i] = rs.prim;
-        if (rs.prim != kMiss) { tuv[3ull * i] = rs.t; tuv[3ull * i + 1] = rs.u; tuv[3ull * i + 2] = rs.v; }
+    blocked[i] = rs.occ == 1 ? 1 : 0;
+}
+
+// ---- denoised read-out (include/mi355rt.h) ------------------------------------------------------------------------
+// Guides: the primary hit of each pixel's centre ray, pixel_ray(p, 0.5, 0.5) through closest_hit, as mi355rt_intersect_rays returns it.
+// g0[p] = (normal, t), g1[p] = (albedo, prim bits); a miss: zeros and prim 0xFFFFFFFF.
+__global__ __launch_bounds__(kBlock) void guides_kernel(DScene sc, DCamera cam, uint32_t flags, int mode, uint32_t npix, float4* __restrict__ g0, float4* __restrict__ g1)
+{
+    extern __shared__ int s_stack[];
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    f3 o, d;
+    pixel_ray(cam, flags, p, 0.5f, 0.5f, o, d);
+    float t = 0.0f, u = 0.0f, v = 0.0f; uint32_t prim = kMiss;
+    closest_hit(sc, o, d, mode, &s_stack[threadIdx.x], t, u, v, prim);
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kMiss)), n = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (prim != kMiss) {
+        const float4 nn = ((const float4*)sc.normals)[prim];                   // calc_normal, mod.rs:198-205 (precomputed)
+        const DMaterial m = sc.materials[__float_as_uint(nn.w)];
+        f3 diffuse = mk3(m.r, m.g, m.b);                                         // mod.rs:242-248
+        if (m.kind_tex & 0x80000000u) diffuse = fetch_texel(sc, m.kind_tex & 0x7FFFFFFFu, u, v);
+        n = make_float4(nn.x, nn.y, nn.z, t);
+        a = make_float4(diffuse.x, diffuse.y, diffuse.z, __uint_as_float(prim));
     }
+    g0[p] = n; g1[p] = a;
+}
+
+__device__ __forceinline__ float pos0(float x) { return x > 0.0f ? x : 0.0f; }        // NaN -> 0
+
+// the read-out of one pixel: rgb (3 floats) and the packed tone-mapped value (tonemap_kernel); either may be null
+__device__ __forceinline__ void denoise_store(uint32_t p, const float4 c, float* __restrict__ rgb, uint32_t* __restrict__ packed)
+{
+    if (rgb) { rgb[3ull * p] = c.x; rgb[3ull * p + 1] = c.y; rgb[3ull * p + 2] = c.z; }
+    if (packed) {
+        const uint32_t R = to_u8(div_rn(c.x, 1.0f + c.x)), G = to_u8(div_rn(c.y, 1.0f + c.y)), B = to_u8(div_rn(c.z, 1.0f + c.z));
+        packed[p] = B | (G << 8) | (R << 16) | (255u << 24);
+    }
+}
+
+// film -> (c, var) and the pixel's flags; with no iteration to follow it also writes the read-out
+__global__ __launch_bounds__(256) void denoise_init_kernel(uint32_t npix, const float* __restrict__ film_sum, const float* __restrict__ film_sumsq,
+                                                          const uint32_t* __restrict__ film_n, const float4* __restrict__ g1, float4* __restrict__ col,
+                                                          uint32_t* __restrict__ flags, float* __restrict__ rgb, uint32_t* __restrict__ packed)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    const uint32_t n = film_n[p];
+    const float fn = (float)n, inv = div_rn(1.0f, fn);                          // film.rs:46
+    float c[3], var = 0.0f;
+    for (int k = 0; k < 3; ++k) c[k] = film_sum[3ull * p + k] * inv;
+    if (n >= 2u) {
+        float v[3];
+        for (int k = 0; k < 3; ++k) {
+            const float s = film_sum[3ull * p + k], q = film_sumsq[3ull * p + k];
+            v[k] = div_rn(pos0(fn * q - s * s), (fn * fn) * (fn - 1.0f));
+        }
+        var = (v[0] + v[1]) + v[2];
+    }
+    const float4 cv = make_float4(c[0], c[1], c[2], var);
+    col[p] = cv;
+    flags[p] = (__float_as_uint(g1[p].w) != kMiss ? kDnHit : 0u) | (n == 0u ? kDnEmpty : 0u) | (n == 1u ? kDnUnknown : 0u);
+    if (rgb || packed) denoise_store(p, cv, rgb, packed);
+}
+
+// One a-trous iteration (step a.step).  A block is 64 x 4 pixels, one image row per wave: each tap of a wave is one contiguous 1 KiB load
+// per buffer.  The last iteration (rgb or packed non-null) also writes the read-out.
+__global__ __launch_bounds__(256) void denoise_iter_kernel(DenoiseArgs a, const float4* __restrict__ g0, const float4* __restrict__ g1,
+                                                          const uint32_t* __restrict__ flags, const float4* __restrict__ in, float4* __restrict__ out,
+                                                          float* __restrict__ rgb, uint32_t* __restrict__ packed)
+{
+    const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
+    if (x >= a.width || y >= a.height) return;
+    const uint32_t p = y * a.width + x;
+    const uint32_t fp = flags[p];
+    const float4 cp = in[p];
+    float4 r = cp;
+    if (!(fp & kDnEmpty)) {
+        constexpr float K1[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
+        const float4 np = g0[p], ap = g1[p];
+        const float lp = (0.2126f * cp.x + 0.7152f * cp.y) + 0.0722f * cp.z;
+        const float sl2 = a.sigma_luminance * a.sigma_luminance, sz = a.sigma_depth * np.w;
+        float W = 0.0f, Sr = 0.0f, Sg = 0.0f, Sb = 0.0f, V = 0.0f;
+        for (int dy = -2; dy <= 2; ++dy) {
+            const int qy = (int)y + dy * (int)a.step;
+            if (qy < 0 || qy >= (int)a.height) continue;
+            for (int dx = -2; dx <= 2; ++dx) {
+                const int qx = (int)x + dx * (int)a.step;
+                if (qx < 0 || qx >= (int)a.width) continue;
+                const uint32_t q = (uint32_t)qy * a.width + (uint32_t)qx;
+                const uint32_t fq = flags[q];
+                if (fq & kDnEmpty) continue;
+                const float k = K1[dx + 2] * K1[dy + 2];
+                const float4 cq = in[q];
+                float w = k;
+                if (q != p) {
+                    if ((fp ^ fq) & kDnHit) continue;
+                    float g = 1.0f;
+                    if (fp & kDnHit) {
+                        const float4 nq = g0[q], aq = g1[q];
+                        float wn = pos0((np.x * nq.x + np.y * nq.y) + np.z * nq.z);
+                        for (uint32_t e = 0; e < a.normal_power_log2; ++e) wn = wn * wn;
+                        const float rz = div_rn(fabsf(np.w - nq.w), sz);
+                        const float wz = div_rn(1.0f, 1.0f + rz * rz);
+                        const float ra = div_rn((fabsf(ap.x - aq.x) + fabsf(ap.y - aq.y)) + fabsf(ap.z - aq.z), a.sigma_albedo);
+                        const float wa = div_rn(1.0f, 1.0f + ra * ra);
+                        g = (wn * wz) * wa;
+                    }
+                    float wl = 1.0f;
+                    if (!((fp | fq) & kDnUnknown)) {
+                        const float dl = lp - ((0.2126f * cq.x + 0.7152f * cq.y) + 0.0722f * cq.z);
+                        wl = div_rn(1.0f, 1.0f + div_rn(dl * dl, sl2 * (cp.w + cq.w) + 1e-12f));
+                    }
+                    w = pos0((k * g) * wl);
+                }
+                Sr = Sr + w * cq.x; Sg = Sg + w * cq.y; Sb = Sb + w * cq.z;
+                W = W + w;
+                V = V + (w * w) * cq.w;
+            }
+        }
+        r = make_float4(div_rn(Sr, W), div_rn(Sg, W), div_rn(Sb, W), div_rn(V, W * W));
+    }
+    out[p] = r;
+    if (rgb || packed) denoise_store(p, r, rgb, packed);
 }
 
 // ---- device arithmetic self-check: a/b, sqrt(a), a^32 as the kernels compute them ----------------
@@ -1674,6 +1808,36 @@ hipError_t launch_intersect(hipStream_t stream, const DScene& sc, uint32_t stack
     dim3 block(kBlock), grid((n + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(intersect_kernel, grid, block, stack_bytes(stack_depth), stream, sc, rays6, n, shadow_mode ? 1 : 0, mode, tuv, prim, blocked);
     return hipGetLastError();
+}
+
+hipError_t launch_guides(hipStream_t stream, const DScene& sc, const DCamera& cam, uint32_t flags, uint32_t stack_depth, int mode, float4* g0, float4* g1)
+{
+    const uint32_t npix = cam.width * cam.height;
+    if (npix == 0) return hipSuccess;
+    hipLaunchKernelGGL(guides_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), stack_bytes(stack_depth), stream, sc, cam, flags, mode, npix, g0, g1);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise(hipStream_t stream, const DenoiseArgs& args, uint32_t iterations, const float* film_sum, const float* film_sumsq, const uint32_t* film_n,
+                          const float4* g0, const float4* g1, uint32_t* flags, float4* ping, float4* pong, float* rgb, uint32_t* packed)
+{
+    const uint32_t npix = args.width * args.height;
+    if (npix == 0) return hipSuccess;
+    const bool last0 = iterations == 0;
+    hipLaunchKernelGGL(denoise_init_kernel, dim3((npix + 255) / 256), dim3(256), 0, stream, npix, film_sum, film_sumsq, film_n, g1, ping, flags,
+                       last0 ? rgb : nullptr, last0 ? packed : nullptr);
+    hipError_t e = hipGetLastError();
+    const dim3 grid((args.width + 63) / 64, (args.height + 3) / 4);
+    for (uint32_t i = 0; i < iterations && e == hipSuccess; ++i) {
+        DenoiseArgs a = args;
+        a.step = 1u << i;
+        const bool last = i + 1 == iterations;
+        hipLaunchKernelGGL(denoise_iter_kernel, grid, dim3(256), 0, stream, a, g0, g1, (const uint32_t*)flags, (const float4*)ping, pong,
+                           last ? rgb : nullptr, last ? packed : nullptr);
+        e = hipGetLastError();
+        std::swap(ping, pong);
+    }
+    return e;
 }
 
 }  // namespace mi355rt

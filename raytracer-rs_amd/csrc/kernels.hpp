@@ -45,6 +45,11 @@ hipError_t launch_slab(hipStream_t stream, const float* inv_rays6, const float* 
 hipError_t launch_adaptive_tiles(hipStream_t stream, const AdaptiveArgs& a, const float* film_sum, const float* film_sumsq, const uint32_t* film_n,
                                  uint8_t* out, unsigned long long* count);
 hipError_t launch_film_stat(hipStream_t stream, bool variances, size_t npix, const float* film_sum, const float* film_sumsq, const uint32_t* film_n, float* out);
+// denoised read-out: the guides of the camera cam (cam.width x cam.height pixels; flags bit 0: FIX_ROW_INDEX), mode as launch_intersect
+hipError_t launch_guides(hipStream_t stream, const DScene& sc, const DCamera& cam, uint32_t flags, uint32_t stack_depth, int mode, float4* g0, float4* g1);
+// film -> `iterations` filter iterations ping-ponging ping / pong (npix float4 each; flags: npix u32) -> rgb (npix * 3 floats) and / or packed (npix u32)
+hipError_t launch_denoise(hipStream_t stream, const DenoiseArgs& args, uint32_t iterations, const float* film_sum, const float* film_sumsq, const uint32_t* film_n,
+                          const float4* g0, const float4* g1, uint32_t* flags, float4* ping, float4* pong, float* rgb, uint32_t* packed);
 // the gather microbenchmark behind bench.py's roofline: num_cus * 8 blocks walk `steps` random nodes of `table` each
 hipError_t launch_gather_rate(hipStream_t stream, int num_cus, const void* table, uint32_t nnodes, uint32_t steps, uint32_t* sink);
 hipError_t launch_numerics(hipStream_t stream, const float* a, const float* b, uint32_t n, float* q, float* r, float* p);

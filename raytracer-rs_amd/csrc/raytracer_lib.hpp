@@ -88,6 +88,13 @@ public:
         if (mi355rt_last_counts(h_, &c) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
         return c;
     }
+    // denoised read-out (include/mi355rt.h): width*height u32 0xAARRGGBB, like get_tonemapped_pixels
+    std::vector<uint32_t> get_denoised_pixels(const mi355rt_denoise_config& cfg) const
+    {
+        std::vector<uint32_t> out((size_t)mi355rt_width(h_) * mi355rt_height(h_));
+        if (mi355rt_get_denoised_pixels(h_, &cfg, nullptr, out.data(), out.size()) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+        return out;
+    }
     mi355rt_handle* handle() const { return h_; }
 private:
     mi355rt_handle* h_;

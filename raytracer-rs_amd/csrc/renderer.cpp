@@ -1470,6 +1470,75 @@ bool Renderer::film_stat(bool variances, float* rgb)
     return true;
 }
 
+// ---- denoised read-out (include/mi355rt.h) ------------------------------------------------------------------------
+// The guides on the device for the current camera and FIX_ROW_INDEX bit: rebuilt (stream-ordered, on the main stream) only when that key changes
+bool Renderer::refresh_guides()
+{
+    const size_t npix = (size_t)cfg.width * cfg.height;
+    if (!d_guide0_) {
+        DeviceBuffer<float4> g0, g1;          // both or neither
+        HIP_TRY(g0.alloc(npix * sizeof(float4), &hbm_bytes_));
+        HIP_TRY(g1.alloc(npix * sizeof(float4), &hbm_bytes_));
+        d_guide0_ = std::move(g0); d_guide1_ = std::move(g1);
+        guides_key_.clear();
+    }
+    const DCamera cam = device_camera();
+    std::vector<float> key(cam.rot, cam.rot + 16);
+    key.insert(key.end(), cam.origin, cam.origin + 3); key.push_back(cam.max_x); key.push_back(cam.max_y);
+    key.push_back((cfg.flags & MI355RT_FLAG_FIX_ROW_INDEX) ? 1.0f : 0.0f);
+    if (key == guides_key_) return true;
+    guides_key_.clear();
+    HIP_TRY(launch_guides(stream_, dscene_, cam, cfg.flags & MI355RT_FLAG_FIX_ROW_INDEX, traversal_rows(), mode_ == kModeConfirm ? 0 : mode_ == kModeOctreeWalk ? 1 : 2,
+                          d_guide0_.get(), d_guide1_.get()));
+    guides_key_ = key;
+    return true;
+}
+
+bool Renderer::get_guides(float* depth, float* normal3, float* albedo3, uint32_t* prim)
+{
+    if (!bind()) return false;
+    if (!settle_speculation()) return false;
+    if (!refresh_guides()) return false;
+    const size_t npix = (size_t)cfg.width * cfg.height;
+    std::vector<float4> g0(npix), g1(npix);
+    HIP_TRY(hipMemcpyAsync(g0.data(), d_guide0_.get(), npix * sizeof(float4), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(g1.data(), d_guide1_.get(), npix * sizeof(float4), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    for (size_t p = 0; p < npix; ++p) {
+        if (depth) depth[p] = g0[p].w;
+        if (normal3) { normal3[3 * p] = g0[p].x; normal3[3 * p + 1] = g0[p].y; normal3[3 * p + 2] = g0[p].z; }
+        if (albedo3) { albedo3[3 * p] = g1[p].x; albedo3[3 * p + 1] = g1[p].y; albedo3[3 * p + 2] = g1[p].z; }
+        if (prim) std::memcpy(&prim[p], &g1[p].w, 4);
+    }
+    return true;
+}
+
+bool Renderer::get_denoised(const mi355rt_denoise_config& dc, float* rgb, uint32_t* packed)
+{
+    if (!bind()) return false;
+    if (!settle_speculation()) return false;
+    const size_t npix = (size_t)cfg.width * cfg.height;
+    if (!d_dn_ping_) {                        // all five or none
+        DeviceBuffer<float4> ping, pong; DeviceBuffer<uint32_t> flags, pk; DeviceBuffer<float> out;
+        HIP_TRY(ping.alloc(npix * sizeof(float4), &hbm_bytes_));
+        HIP_TRY(pong.alloc(npix * sizeof(float4), &hbm_bytes_));
+        HIP_TRY(flags.alloc(npix * 4, &hbm_bytes_));
+        HIP_TRY(out.alloc(npix * 12, &hbm_bytes_));
+        HIP_TRY(pk.alloc(npix * 4, &hbm_bytes_));
+        d_dn_ping_ = std::move(ping); d_dn_pong_ = std::move(pong); d_dn_flags_ = std::move(flags); d_dn_rgb_ = std::move(out); d_dn_packed_ = std::move(pk);
+    }
+    if (!refresh_guides()) return false;
+    DenoiseArgs a{};
+    a.width = cfg.width; a.height = cfg.height; a.step = 1u; a.normal_power_log2 = dc.normal_power_log2;
+    a.sigma_luminance = dc.sigma_luminance; a.sigma_depth = dc.sigma_depth; a.sigma_albedo = dc.sigma_albedo;
+    HIP_TRY(launch_denoise(stream_, a, dc.iterations, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_guide0_.get(), d_guide1_.get(), d_dn_flags_.get(),
+                           d_dn_ping_.get(), d_dn_pong_.get(), rgb ? d_dn_rgb_.get() : nullptr, packed ? d_dn_packed_.get() : nullptr));
+    if (rgb) HIP_TRY(hipMemcpyAsync(rgb, d_dn_rgb_.get(), npix * 12, hipMemcpyDeviceToHost, stream_));
+    if (packed) HIP_TRY(hipMemcpyAsync(packed, d_dn_packed_.get(), npix * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    return true;
+}
+
 bool Renderer::debug_sample(uint32_t pixel, uint32_t sampleno, float* color3, float* node_L, size_t nodes)
 {
     if (!bind()) return false;

@@ -56,6 +56,9 @@ public:
     bool debug_gather_rate(uint32_t table_nodes, uint32_t steps, double out[3]);
     bool debug_slab(const float* inv_rays6, const float* cubes6, size_t n, uint8_t* hit, float* tmin);
     bool film_stat(bool variances, float* rgb);
+    // denoised read-out; the caller has checked the arguments (a whole image on one device, a valid config)
+    bool get_guides(float* depth, float* normal3, float* albedo3, uint32_t* prim);
+    bool get_denoised(const mi355rt_denoise_config& dc, float* rgb, uint32_t* packed);
     void speculation_stats(uint64_t out[2]) const { out[0] = spec_launched_; out[1] = spec_adopted_; }
     bool debug_numerics(const float* a, const float* b, size_t n, float* q, float* r, float* p);
     bool debug_sample(uint32_t pixel, uint32_t sampleno, float* color3, float* node_L, size_t nodes);
@@ -139,6 +142,14 @@ private:
     bool adaptive_verdict(const mi355rt_adaptive_config& ac, uint32_t& tiles, uint64_t& pixels);    // d_tile_active_ <- the verdict of the current film
     DeviceBuffer<uint8_t> d_tile_active_;                               // adaptive sampling: one byte per tile (DPass::tile_active)
     DeviceBuffer<unsigned long long> d_tile_count_;                     // (owned pixels of the active tiles << 32) + active tiles
+    // Denoised read-out, allocated on first use: the guides (g0 = (normal, t), g1 = (albedo, prim bits)) for the camera and row-index
+    // flag of guides_key_, and the per-call buffers of the filter
+    bool refresh_guides();
+    DeviceBuffer<float4> d_guide0_, d_guide1_;
+    std::vector<float> guides_key_;      // rot, origin, max_x, max_y, FIX_ROW_INDEX bit of the guides on the device; empty: none
+    DeviceBuffer<float4> d_dn_ping_, d_dn_pong_;
+    DeviceBuffer<uint32_t> d_dn_flags_, d_dn_packed_;
+    DeviceBuffer<float> d_dn_rgb_;
     void describe_pass(DPass& ps, const Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t row_wrap, uint32_t npix, size_t nsamples, uint32_t chunk,
                        bool explicit_sample, uint32_t epixel, uint32_t esample) const;
     bool begin_call();
