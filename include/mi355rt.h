@@ -60,6 +60,10 @@ extern "C" {
  * is faster on large scenes.  Falls back to the host build when the device tree would be deeper than the traversal stack or the
  * scene fits one leaf; mi355rt_accel_stats out[6] then reports the host build's time and mi355rt_last_error says why. */
 #define MI355RT_FLAG_DEVICE_LBVH 64u
+/* Create-time: the handle keeps a DIRECT FILM next to the film (the sum of every sample's root light term), read with
+ * mi355rt_film_get_direct and used by mi355rt_get_denoised_pixels_split (see there).  12 bytes per pixel more device
+ * memory; without the flag every kernel, buffer and result of the handle is what it is without this feature. */
+#define MI355RT_FLAG_DIRECT_FILM 128u
 
 typedef struct mi355rt_handle mi355rt_handle;
 
@@ -270,6 +274,37 @@ void mi355rt_denoise_default_config(mi355rt_denoise_config* cfg);
 /* rgb: npix*3 floats, packed: npix u32 (either may be NULL, not both); npix >= width*height.  An invalid config returns MI355RT_E_INVALID,
  * names the field in mi355rt_last_error and writes nothing. */
 int mi355rt_get_denoised_pixels(mi355rt_handle* h, const mi355rt_denoise_config* cfg, float* rgb, uint32_t* packed, size_t npix);
+/* ---- direct film and split read-out (MI355RT_FLAG_DIRECT_FILM; no reference counterpart).  Almost all of a film's noise is in
+ * the bounce tree; the light arriving at the primary hit straight from the lights has none beyond pixel jitter, yet it carries the shadow
+ * edges, the highlights and the texture detail that the filter above blurs.  A handle created with the flag therefore keeps that part of
+ * the film apart, and a second denoised read-out filters only what is left.
+ *
+ * DIRECT FILM.  direct[width*height*3], f32, zero at creation.  Whenever a sample is added to a pixel's film (PixelData::add_sample,
+ * film.rs:20-24) the pixel gets direct = direct + L0, in the same place and in the same sample order.  L0 is the root node's light sum of
+ * the sample, the first term of its colour L0 + (...) * 0.5 (mod.rs:146-175 with mod.rs:211-254: the node_L[0] of mi355rt_debug_sample); it
+ * is (0, 0, 0) for a primary miss, for a hit the octree semantics drop and for every sample that writes no light term.  So direct[p] is the
+ * sequential f32 sum over the pixel's samples of node_L[0], bit for bit.  It is cleared wherever the film is cleared (mi355rt_film_clear,
+ * which the reference's loop calls after every camera move); a pixel whose film is not written (an inactive tile of mi355rt_render_adaptive,
+ * a row the handle does not own) keeps its direct sum.
+ *
+ * mi355rt_film_get_direct returns the sums, width*height*3 floats.  It follows mi355rt_film_get: queued work and a speculative 50-row frame
+ * are settled first, a striped handle returns zero for the rows it does not own, a device group gathers its members' rows.  A handle
+ * without the flag: MI355RT_E_INVALID, mi355rt_last_error names MI355RT_FLAG_DIRECT_FILM, nothing is written.
+ *
+ * SPLIT READ-OUT.  mi355rt_get_denoised_pixels_split takes the arguments, the validation and the side-effect rules of
+ * mi355rt_get_denoised_pixels (device groups and striped handles: MI355RT_E_INVALID) and also refuses a handle without the flag.  From the
+ * film (n, s[3], q[3]) and the direct sums d[3], fn = (float)n, everything f32, unfused, in this order:
+ *     n == 0 : the pixel is EMPTY: never a tap, and its output is the film mean as it stands
+ *     inv = 1.0f / fn;  c = s * inv;  cd = d * inv;  ci = c - cd                 per channel
+ *     var exactly as FILTER defines it from s and q: the variance of the TOTAL.  (Evaluated on the CPU, a second variance of the indirect
+ *     samples alone bought nothing — tone-mapped RMSE 0.01197 against 0.01193 at 8 spp, 0.00690 against 0.00692 at 32 — so the film keeps one
+ *     more sum per pixel, not two.)
+ *     the `iterations` a-trous iterations of FILTER on (ci, var), unchanged: the luminance term is now on ci, var' = V / (W*W) as there
+ *     rgb = cd + ci' per channel; packed = that value mapped as mi355rt_get_tonemapped_pixels maps a film mean
+ * iterations = 0 returns exactly mi355rt_film_get_pixels and mi355rt_get_tonemapped_pixels (not cd + (c - cd)).
+ * Device memory: the guides and the filter's buffers of mi355rt_get_denoised_pixels, shared with it; nothing more. */
+int mi355rt_film_get_direct(mi355rt_handle* h, float* sum_rgb);
+int mi355rt_get_denoised_pixels_split(mi355rt_handle* h, const mi355rt_denoise_config* cfg, float* rgb, uint32_t* packed, size_t npix);
 /* the guide buffers above, width*height entries each (normal3, albedo3: 3 floats per pixel); any pointer may be NULL */
 int mi355rt_get_guides(mi355rt_handle* h, float* depth, float* normal3, float* albedo3, uint32_t* prim, size_t npix);
 
@@ -307,8 +342,9 @@ int mi355rt_camera_get_ray(const mi355rt_handle* h, uint32_t u, uint32_t v, floa
 /* Re-seed: afterwards the handle renders what a handle created with this seed renders (the per-sample hash key AND
  * the 65 536-entry direction table are functions of the seed; only its low 32 bits are used).  The film is kept. */
 int mi355rt_set_seed(mi355rt_handle* h, uint64_t seed);
-/* Run-time flags (FIX_ROW_INDEX, COUNT_STEPS, TIME_KERNELS).  MI355RT_FLAG_OCTREE_SEMANTICS is fixed at creation:
- * pass the bit as it was created, a call that would change it fails with MI355RT_E_INVALID and changes nothing. */
+/* Run-time flags (FIX_ROW_INDEX, COUNT_STEPS, TIME_KERNELS).  The create-time flags (OCTREE_SEMANTICS, TRUE_CLOSEST_HIT, GROUP_SHARES_DEVICE,
+ * DEVICE_LBVH, DIRECT_FILM) are fixed at creation: pass the bits as they were created, a call that would change one fails with
+ * MI355RT_E_INVALID and changes nothing. */
 int mi355rt_set_flags(mi355rt_handle* h, uint32_t flags);
 /* Number of concurrent frame slices mi355rt_render splits its rows into (1..8, default 3, or the
  * environment variable MI355RT_SLICES).  Each slice runs its wavefront passes on its own HIP stream, so the

@@ -34,6 +34,7 @@ FLAG_OCTREE_SEMANTICS = 8
 FLAG_GROUP_SHARES_DEVICE = 16
 FLAG_TRUE_CLOSEST_HIT = 32
 FLAG_DEVICE_LBVH = 64
+FLAG_DIRECT_FILM = 128
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI355RT_LIB") or os.path.join(_HERE, "libmi355rt.so")     # MI355RT_LIB: an A/B build of the library
@@ -132,6 +133,8 @@ ABI = [
     ("mi355rt_adaptive_tile_mask", C.c_int, [_H, C.POINTER(AdaptiveConfig), C.POINTER(C.c_uint8), C.c_size_t]),
     ("mi355rt_denoise_default_config", None, [C.POINTER(DenoiseConfig)]),
     ("mi355rt_get_denoised_pixels", C.c_int, [_H, C.POINTER(DenoiseConfig), _F, _U, C.c_size_t]),
+    ("mi355rt_film_get_direct", C.c_int, [_H, _F]),
+    ("mi355rt_get_denoised_pixels_split", C.c_int, [_H, C.POINTER(DenoiseConfig), _F, _U, C.c_size_t]),
     ("mi355rt_get_guides", C.c_int, [_H, _F, _F, _F, _U, C.c_size_t]),
     ("mi355rt_get_tonemapped_pixels", C.c_int, [_H, _U, C.c_size_t]),
     ("mi355rt_tonemap_owned_rows_device", C.c_int, [_H, C.c_void_p, C.c_size_t]),
@@ -290,6 +293,12 @@ class Film:
         self._rt._check(lib().mi355rt_film_get(self._rt._h, _fp(s), _fp(q), _up(c)))
         return s, q, c
 
+    def direct_sums(self):
+        """direct[n,3]: per pixel, the sum of its samples' root light terms (a handle created with FLAG_DIRECT_FILM; mi355rt_film_get_direct)"""
+        d = np.zeros((self._rt.width * self._rt.height, 3), np.float32)
+        self._rt._check(lib().mi355rt_film_get_direct(self._rt._h, _fp(d)))
+        return d
+
     def get_pixels(self):
         out = np.zeros((self._rt.width * self._rt.height, 3), np.float32)
         self._rt._check(lib().mi355rt_film_get_pixels(self._rt._h, _fp(out)))
@@ -380,15 +389,16 @@ class RayTracer:
         assert rc == int(out.sum())
         return out
 
-    def get_denoised_pixels(self, rgb=True, packed=True, **cfg):
+    def get_denoised_pixels(self, rgb=True, packed=True, split=False, **cfg):
         """The denoised read-out of the film (include/mi355rt.h, mi355rt_get_denoised_pixels).  Fields not given keep
-        mi355rt_denoise_default_config's values.  Returns (rgb float32[npix, 3] or None, packed uint32[npix] or None)."""
+        mi355rt_denoise_default_config's values.  Returns (rgb float32[npix, 3] or None, packed uint32[npix] or None).
+        split=True (a handle created with FLAG_DIRECT_FILM): mi355rt_get_denoised_pixels_split, which filters the indirect part only."""
         c = denoise_config(**cfg)
         n = self.width * self.height
         out_rgb = np.zeros((n, 3), np.float32) if rgb else None
         out_packed = np.zeros(n, np.uint32) if packed else None
-        self._check(lib().mi355rt_get_denoised_pixels(self._h, C.byref(c), _fp(out_rgb) if rgb else None,
-                                                      _up(out_packed) if packed else None, n))
+        fn = lib().mi355rt_get_denoised_pixels_split if split else lib().mi355rt_get_denoised_pixels
+        self._check(fn(self._h, C.byref(c), _fp(out_rgb) if rgb else None, _up(out_packed) if packed else None, n))
         return out_rgb, out_packed
 
     def guides(self):

@@ -225,6 +225,14 @@ int mi355rt_get_denoised_pixels(mi355rt_handle* h, const mi355rt_denoise_config*
     return h->r->get_denoised(*cfg, rgb, packed) ? MI355RT_OK : MI355RT_E_HIP;
 }
 
+int mi355rt_get_denoised_pixels_split(mi355rt_handle* h, const mi355rt_denoise_config* cfg, float* rgb, uint32_t* packed, size_t npix)
+{
+    if (!denoise_handle_ok(h, npix) || !denoise_config_ok(h, cfg)) return MI355RT_E_INVALID;
+    if (!rgb && !packed) { h->r->last_error = "denoise: rgb and packed are both NULL"; return MI355RT_E_INVALID; }
+    if (!h->r->has_direct_film()) { h->r->last_error = "denoise: the split read-out needs a handle created with MI355RT_FLAG_DIRECT_FILM"; return MI355RT_E_INVALID; }
+    return h->r->get_denoised(*cfg, rgb, packed, true) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
 int mi355rt_get_guides(mi355rt_handle* h, float* depth, float* normal3, float* albedo3, uint32_t* prim, size_t npix)
 {
     if (!denoise_handle_ok(h, npix)) return MI355RT_E_INVALID;
@@ -267,6 +275,14 @@ int mi355rt_film_get(mi355rt_handle* h, float* sum_rgb, float* sumsq_rgb, uint32
 {
     if (!h) return MI355RT_E_INVALID;
     return h->g->film_get(sum_rgb, sumsq_rgb, n) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_film_get_direct(mi355rt_handle* h, float* sum_rgb)
+{
+    if (!h) return MI355RT_E_INVALID;
+    if (!sum_rgb) { h->r->last_error = "mi355rt_film_get_direct: null output"; return MI355RT_E_INVALID; }
+    if (!h->r->has_direct_film()) { h->r->last_error = "mi355rt_film_get_direct: the handle was not created with MI355RT_FLAG_DIRECT_FILM"; return MI355RT_E_INVALID; }
+    return h->g->film_get_direct(sum_rgb) ? MI355RT_OK : MI355RT_E_HIP;
 }
 
 int mi355rt_film_clear(mi355rt_handle* h)

@@ -7,7 +7,8 @@
 // rows, mi355rt_config.device_count), --out file.ppm | file.png, --fix-row-index, and adaptive sampling in place of --spp:
 // --adaptive REL (mi355rt_render_adaptive with rel_error REL) with --abs-floor F, --min-spp N, --max-spp N, --batch N (defaults:
 // mi355rt_adaptive_default_config), and --denoise: --out receives the denoised read-out of the film (mi355rt_get_denoised_pixels,
-// mi355rt_denoise_default_config) instead of get_tonemapped_pixels.
+// mi355rt_denoise_default_config) instead of get_tonemapped_pixels; --denoise-split: the handle keeps a direct film (MI355RT_FLAG_DIRECT_FILM)
+// and --out receives the split read-out (mi355rt_get_denoised_pixels_split), which filters the indirect part only.
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -67,7 +68,7 @@ int main(int argc, char** argv)
     size_t frame_iterations = 0, spp = 0, seed = 1, gpus = 1;
     bool have_iterations = false, fix_row = false, share_device = false, device_lbvh = false;
     std::string out;
-    bool adaptive = false, denoise = false;
+    bool adaptive = false, denoise = false, denoise_split = false;
     mi355rt_adaptive_config acfg;
     mi355rt_adaptive_default_config(&acfg);
     auto parse_float = [](const char* s, float& out) { if (!s || !*s) return false; char* end = nullptr; const float f = std::strtof(s, &end); if (*end != '\0' || !std::isfinite(f)) return false; out = f; return true; };
@@ -88,6 +89,7 @@ int main(int argc, char** argv)
         else if (a == "--fix-row-index") fix_row = true;
         else if (a == "--device-lbvh") device_lbvh = true;
         else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-split") denoise_split = true;
         else if (a == "--adaptive") { float f; if (parse_float(take(), f)) { acfg.rel_error = f; adaptive = true; } }
         else if (a == "--abs-floor") { float f; if (parse_float(take(), f)) acfg.abs_floor = f; }
         else if (a == "--min-spp") { size_t t; if (parse_usize(take(), t)) acfg.min_spp = (uint32_t)t; }
@@ -96,7 +98,7 @@ int main(int argc, char** argv)
         else if (a == "-h" || a == "--help") {
             std::printf("raytracer-rs (MI355X) 0.1.0\nusage: raytracer [-f COLLADA_FILENAME] [-m MAX_TRIS] [-i FRAME_ITERATIONS] [--width W] [--height H]\n"
                         "                 [--spp N] [--seed S] [--gpus N] [--out image.ppm|image.png] [--fix-row-index] [--device-lbvh]\n"
-                        "                 [--adaptive REL [--abs-floor F] [--min-spp N] [--max-spp N] [--batch N]] [--denoise]\n");
+                        "                 [--adaptive REL [--abs-floor F] [--min-spp N] [--max-spp N] [--batch N]] [--denoise | --denoise-split]\n");
             return 0;
         }
     }
@@ -109,6 +111,7 @@ int main(int argc, char** argv)
         cfg.seed = seed;
         if (fix_row) cfg.flags |= MI355RT_FLAG_FIX_ROW_INDEX;
         if (device_lbvh) cfg.flags |= MI355RT_FLAG_DEVICE_LBVH;             // BVH built on the GPU (Morton order) instead of the host's SAH build
+        if (denoise_split) cfg.flags |= MI355RT_FLAG_DIRECT_FILM;
         cfg.device_count = (uint32_t)gpus;
         if (share_device) cfg.flags |= MI355RT_FLAG_GROUP_SHARES_DEVICE;      // testing: the whole group on one GPU
         if (gpus > 1) std::printf("rendering on %zu GPUs (rows dealt in stripes of %u)\n", gpus, cfg.stripe_rows);
@@ -138,10 +141,10 @@ int main(int argc, char** argv)
             std::printf("%s\n", stats.stats(num_primary_rays).c_str());  // main.rs:213
         }
         std::printf("%s\n\n\n", stats.mean_stats().c_str());             // main.rs:216
-        if (denoise) {                                                    // the denoised read-out of the film the loop left (default config)
+        if (denoise || denoise_split) {                                   // the denoised read-out of the film the loop left (default config)
             mi355rt_denoise_config dcfg;
             mi355rt_denoise_default_config(&dcfg);
-            ldr = rt.get_denoised_pixels(dcfg);
+            ldr = denoise_split ? rt.get_denoised_pixels_split(dcfg) : rt.get_denoised_pixels(dcfg);
         }
         if (!out.empty()) {
             const bool png = out.size() > 4 && out.compare(out.size() - 4, 4, ".png") == 0;

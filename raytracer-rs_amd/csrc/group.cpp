@@ -139,6 +139,19 @@ bool DeviceGroup::film_get(float* sum, float* sumsq, uint32_t* n)
     return true;
 }
 
+bool DeviceGroup::film_get_direct(float* sum)
+{
+    error_.clear();
+    if (devs_.size() == 1) return primary()->film_get_direct(sum);
+    const uint32_t w = primary()->cfg.width; const size_t npix = (size_t)w * primary()->cfg.height;
+    std::vector<float> t(npix * 3);
+    for (size_t i = 0; i < devs_.size(); ++i) {
+        if (!devs_[i]->film_get_direct(t.data())) return fail_from(i);
+        for (uint32_t r : devs_[i]->owned_rows) std::memcpy(sum + (size_t)r * w * 3, t.data() + (size_t)r * w * 3, (size_t)w * 12);
+    }
+    return true;
+}
+
 bool DeviceGroup::film_stat(bool variances, float* rgb)
 {
     error_.clear();

@@ -25,6 +25,7 @@ public:
     bool last_counts(mi355rt_ray_counts& out);
     bool get_tonemapped(uint32_t* out, size_t n);
     bool film_get(float* sum, float* sumsq, uint32_t* n);
+    bool film_get_direct(float* sum);
     bool film_stat(bool variances, float* rgb);
     bool film_clear();
     void camera_move_rel(float x, float y, float z);

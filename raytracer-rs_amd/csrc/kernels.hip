@@ -1106,10 +1106,12 @@ __device__ f3 node_radiance(const float* __restrict__ L, const DPass& ps, uint32
 // pixel and few samples most lanes of a group have nothing to load.  The launcher picks the group size from
 // the samples per pixel of the pass (21-spp passes of a 1080p frame: 1 / 2 / 4 / 8 / 16 lanes -> 0.22 / 0.21 /
 // 0.25 / 0.31 / 0.55 ms).
-template <uint32_t kResolveLanes>
+// DIRECT (MI355RT_FLAG_DIRECT_FILM): the pixel's direct film (film_direct, beside film_sum) takes the root node's light sum L0 =
+// node_radiance<0> of every sample — the first term of the sample's colour — through the same exchange, so it is added in sample order too.
+template <uint32_t kResolveLanes, bool DIRECT>
 __global__ __launch_bounds__(256) void resolve_kernel(DPass ps, uint32_t width, uint32_t nlights, const float* __restrict__ slot_L,
                                                      const uint32_t* __restrict__ sample_slot,
-                                                     float* film_sum, float* film_sumsq, uint32_t* film_n, float* debug_color, uint32_t* ctrl)
+                                                     float* film_sum, float* film_sumsq, uint32_t* film_n, float* debug_color, uint32_t* ctrl, float* film_direct)
 {
     // last kernel of a pass: leave the pass's work cursors zeroed for the next one (960 words; a 20 MiB memset otherwise)
     if (ctrl != nullptr && blockIdx.x == 0)
@@ -1121,12 +1123,13 @@ __global__ __launch_bounds__(256) void resolve_kernel(DPass ps, uint32_t width, 
     const uint32_t p = live ? gid / kResolveLanes : ps.npix - 1u;        // surplus groups of the last block shadow the last pixel
     const uint32_t spp = ps.nsamples / ps.npix;
     const uint32_t pixel = ps.use_explicit ? ps.explicit_pixel : pass_pixel(ps, width, p);
-    f3 sum = mk3(0, 0, 0), sumsq = mk3(0, 0, 0);
+    f3 sum = mk3(0, 0, 0), sumsq = mk3(0, 0, 0), direct = mk3(0, 0, 0);
     uint32_t n = 0;
     if (!ps.use_explicit) {
         sum = mk3(film_sum[3ull * pixel], film_sum[3ull * pixel + 1], film_sum[3ull * pixel + 2]);
         sumsq = mk3(film_sumsq[3ull * pixel], film_sumsq[3ull * pixel + 1], film_sumsq[3ull * pixel + 2]);
         n = film_n[pixel];
+        if constexpr (DIRECT) direct = mk3(film_direct[3ull * pixel], film_direct[3ull * pixel + 1], film_direct[3ull * pixel + 2]);
     }
     const int group_lane0 = lane_id() & ~(int)(kResolveLanes - 1u);
     // every sample of a pixel in a culled block is a miss: no slot to look up (the primary shade launch wrote none)
@@ -1144,14 +1147,19 @@ __global__ __launch_bounds__(256) void resolve_kernel(DPass ps, uint32_t width, 
             case 2: c = node_radiance<2>(L, ps, nlights, 0, 0); break;
             default: c = node_radiance<3>(L, ps, nlights, 0, 0); break;
         }
+        f3 d = mk3(0.0f, 0.0f, 0.0f);                                   // no slot: no root light term either
+        if constexpr (DIRECT) { if (sl != 0xFFFFFFFFu) d = node_radiance<0>(L, ps, nlights, 0, 0); }
 #pragma unroll
         for (uint32_t k = 0; k < kResolveLanes; ++k) {
             const f3 ck = mk3(__shfl(c.x, group_lane0 + (int)k, 64), __shfl(c.y, group_lane0 + (int)k, 64), __shfl(c.z, group_lane0 + (int)k, 64));
+            f3 dk = mk3(0.0f, 0.0f, 0.0f);
+            if constexpr (DIRECT) dk = mk3(__shfl(d.x, group_lane0 + (int)k, 64), __shfl(d.y, group_lane0 + (int)k, 64), __shfl(d.z, group_lane0 + (int)k, 64));
             if (s0 + k < spp) {
                 // PixelData::add_sample, film.rs:20-24
                 sum = add3(sum, ck);
                 sumsq = add3(sumsq, mk3(ck.x * ck.x, ck.y * ck.y, ck.z * ck.z));
                 n += 1u;
+                if constexpr (DIRECT) direct = add3(direct, dk);
                 if (ps.use_explicit && j == 0u) { debug_color[0] = ck.x; debug_color[1] = ck.y; debug_color[2] = ck.z; }
             }
         }
@@ -1160,6 +1168,7 @@ __global__ __launch_bounds__(256) void resolve_kernel(DPass ps, uint32_t width, 
         film_sum[3ull * pixel] = sum.x; film_sum[3ull * pixel + 1] = sum.y; film_sum[3ull * pixel + 2] = sum.z;
         film_sumsq[3ull * pixel] = sumsq.x; film_sumsq[3ull * pixel + 1] = sumsq.y; film_sumsq[3ull * pixel + 2] = sumsq.z;
         film_n[pixel] = n;
+        if constexpr (DIRECT) { film_direct[3ull * pixel] = direct.x; film_direct[3ull * pixel + 1] = direct.y; film_direct[3ull * pixel + 2] = direct.z; }
     }
 }
 
@@ -1178,8 +1187,9 @@ __global__ __launch_bounds__(256) void resolve_kernel(DPass ps, uint32_t width, 
 // wave — it made this kernel 3.5x slower (0.35 ms -> see profiles/r02_notes.md), evicting the BVH each time.
 __device__ __forceinline__ void phase_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
 
+template <bool DIRECT>
 __device__ __forceinline__ void resolve_chunk_1spp(const DPass& ps, uint32_t width, uint32_t nlights, uint32_t chunk, const float* slot_L, const uint32_t* sample_slot,
-                                                   float* film_sum, float* film_sumsq, uint32_t* film_n)
+                                                   float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct)
 {
     const uint32_t n = min(ps.chunk, ps.nsamples - chunk * ps.chunk);
     for (uint32_t i = (uint32_t)lane_id(); i < n; i += 64u) {
@@ -1199,14 +1209,20 @@ __device__ __forceinline__ void resolve_chunk_1spp(const DPass& ps, uint32_t wid
         ps_[0] = ps_[0] + c.x; ps_[1] = ps_[1] + c.y; ps_[2] = ps_[2] + c.z;
         pq[0] = pq[0] + c.x * c.x; pq[1] = pq[1] + c.y * c.y; pq[2] = pq[2] + c.z * c.z;
         film_n[pixel] = film_n[pixel] + 1u;
+        if constexpr (DIRECT) {
+            f3 d = mk3(0.0f, 0.0f, 0.0f);
+            if (sl != 0xFFFFFFFFu) d = node_radiance<0>(L, ps, nlights, 0, 0);
+            float* pd = film_direct + 3ull * pixel;
+            pd[0] = pd[0] + d.x; pd[1] = pd[1] + d.y; pd[2] = pd[2] + d.z;
+        }
     }
 }
 
 constexpr int kFusedBlocks = 1;                // blocks per CU the fused 50-row kernel is compiled for (4 blocks = 128 VGPRs)
-template <bool CONFIRM>
+template <bool CONFIRM, bool DIRECT>
 __global__ __launch_bounds__(kBlock, kFusedBlocks) void fused_pass_kernel(DScene sc, DCamera cam, DPass ps, float4* q0, float4* q1,
                                                             float4* hits, float* slot_L, uint32_t* sample_slot,
-                                                            float* film_sum, float* film_sumsq, uint32_t* film_n, DCounters* counters)
+                                                            float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct, DCounters* counters)
 {
     extern __shared__ int s_stack[];                 // max(traversal stack rows, hit-list rows) x kBlock ints
     int* stack = &s_stack[threadIdx.x];
@@ -1235,7 +1251,7 @@ __global__ __launch_bounds__(kBlock, kFusedBlocks) void fused_pass_kernel(DScene
                 phase_fence();
             }
         }
-        resolve_chunk_1spp(ps, cam.width, sc.nlights, chunk, slot_L, sample_slot, film_sum, film_sumsq, film_n);
+        resolve_chunk_1spp<DIRECT>(ps, cam.width, sc.nlights, chunk, slot_L, sample_slot, film_sum, film_sumsq, film_n, film_direct);
     }
     flush_shade_counters(counters, wave, acc_bounce, acc_shadow, acc_hits);
 }
@@ -1348,6 +1364,33 @@ __device__ __forceinline__ void denoise_store(uint32_t p, const float4 c, float*
     }
 }
 
+// The split read-out (mi355rt_get_denoised_pixels_split) filters the indirect part of the mean only: ci = c - cd with cd = d * (1 / n)
+// of the direct film d, under the TOTAL's variance.  An empty pixel keeps its mean as it stands (it is never a tap and never filtered).
+__global__ __launch_bounds__(256) void denoise_init_split_kernel(uint32_t npix, const float* __restrict__ film_sum, const float* __restrict__ film_sumsq,
+                                                                const uint32_t* __restrict__ film_n, const float* __restrict__ film_direct,
+                                                                const float4* __restrict__ g1, float4* __restrict__ col, uint32_t* __restrict__ flags)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    const uint32_t n = film_n[p];
+    const float fn = (float)n, inv = div_rn(1.0f, fn);                          // film.rs:46
+    float c[3], var = 0.0f;
+    for (int k = 0; k < 3; ++k) {
+        c[k] = film_sum[3ull * p + k] * inv;
+        if (n != 0u) { const float cd = film_direct[3ull * p + k] * inv; c[k] = c[k] - cd; }
+    }
+    if (n >= 2u) {
+        float v[3];
+        for (int k = 0; k < 3; ++k) {
+            const float s = film_sum[3ull * p + k], q = film_sumsq[3ull * p + k];
+            v[k] = div_rn(pos0(fn * q - s * s), (fn * fn) * (fn - 1.0f));
+        }
+        var = (v[0] + v[1]) + v[2];
+    }
+    col[p] = make_float4(c[0], c[1], c[2], var);
+    flags[p] = (__float_as_uint(g1[p].w) != kMiss ? kDnHit : 0u) | (n == 0u ? kDnEmpty : 0u) | (n == 1u ? kDnUnknown : 0u);
+}
+
 // film -> (c, var) and the pixel's flags; with no iteration to follow it also writes the read-out
 __global__ __launch_bounds__(256) void denoise_init_kernel(uint32_t npix, const float* __restrict__ film_sum, const float* __restrict__ film_sumsq,
                                                           const uint32_t* __restrict__ film_n, const float4* __restrict__ g1, float4* __restrict__ col,
@@ -1375,9 +1418,13 @@ __global__ __launch_bounds__(256) void denoise_init_kernel(uint32_t npix, const 
 
 // One a-trous iteration (step a.step).  A block is 64 x 4 pixels, one image row per wave: each tap of a wave is one contiguous 1 KiB load
 // per buffer.  The last iteration (rgb or packed non-null) also writes the read-out.
-__global__ __launch_bounds__(256) void denoise_iter_kernel(DenoiseArgs a, const float4* __restrict__ g0, const float4* __restrict__ g1,
-                                                          const uint32_t* __restrict__ flags, const float4* __restrict__ in, float4* __restrict__ out,
-                                                          float* __restrict__ rgb, uint32_t* __restrict__ packed)
+// SPLIT: the last iteration of the split read-out; the pixel's direct part cd = d * (1 / n) is read again (a buffer of its own would cost the same 12 bytes
+// per pixel twice) and added to the filtered indirect part before the store.
+template <bool SPLIT>
+__device__ __forceinline__ void denoise_iter_body(const DenoiseArgs& a, const float4* __restrict__ g0, const float4* __restrict__ g1,
+                                                  const uint32_t* __restrict__ flags, const float4* __restrict__ in, float4* __restrict__ out,
+                                                  const float* __restrict__ film_direct, const uint32_t* __restrict__ film_n,
+                                                  float* __restrict__ rgb, uint32_t* __restrict__ packed)
 {
     const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
     if (x >= a.width || y >= a.height) return;
@@ -1431,7 +1478,26 @@ __global__ __launch_bounds__(256) void denoise_iter_kernel(DenoiseArgs a, const 
         r = make_float4(div_rn(Sr, W), div_rn(Sg, W), div_rn(Sb, W), div_rn(V, W * W));
     }
     out[p] = r;
+    if constexpr (SPLIT) {
+        if (!(fp & kDnEmpty)) {
+            const float inv = div_rn(1.0f, (float)film_n[p]);
+            r.x = film_direct[3ull * p] * inv + r.x; r.y = film_direct[3ull * p + 1] * inv + r.y; r.z = film_direct[3ull * p + 2] * inv + r.z;
+        }
+    }
     if (rgb || packed) denoise_store(p, r, rgb, packed);
+}
+__global__ __launch_bounds__(256) void denoise_iter_kernel(DenoiseArgs a, const float4* __restrict__ g0, const float4* __restrict__ g1,
+                                                          const uint32_t* __restrict__ flags, const float4* __restrict__ in, float4* __restrict__ out,
+                                                          float* __restrict__ rgb, uint32_t* __restrict__ packed)
+{
+    denoise_iter_body<false>(a, g0, g1, flags, in, out, nullptr, nullptr, rgb, packed);
+}
+__global__ __launch_bounds__(256) void denoise_iter_split_kernel(DenoiseArgs a, const float4* __restrict__ g0, const float4* __restrict__ g1,
+                                                                const uint32_t* __restrict__ flags, const float4* __restrict__ in, float4* __restrict__ out,
+                                                                const float* __restrict__ film_direct, const uint32_t* __restrict__ film_n,
+                                                                float* __restrict__ rgb, uint32_t* __restrict__ packed)
+{
+    denoise_iter_body<true>(a, g0, g1, flags, in, out, film_direct, film_n, rgb, packed);
 }
 
 // ---- device arithmetic self-check: a/b, sqrt(a), a^32 as the kernels compute them ----------------
@@ -1669,16 +1735,21 @@ hipError_t launch_shade(hipStream_t stream, int num_cus, bool primary, bool walk
 }
 
 hipError_t launch_resolve(hipStream_t stream, const DPass& ps, uint32_t width, uint32_t nlights, const float* slot_L, const uint32_t* sample_slot,
-                          float* film_sum, float* film_sumsq, uint32_t* film_n, float* debug_color, uint32_t* ctrl)
+                          float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct, float* debug_color, uint32_t* ctrl)
 {
     const uint32_t spp = ps.npix ? ps.nsamples / ps.npix : 1u;
     const uint32_t lanes = spp <= 32u ? 2u : (spp <= 96u ? 4u : 8u);
     dim3 block(256), grid((unsigned)(((size_t)ps.npix * lanes + 255) / 256));
-#define MI355RT_RESOLVE_ARGS grid, block, 0, stream, ps, width, nlights, slot_L, sample_slot, film_sum, film_sumsq, film_n, debug_color, ctrl
-    switch (lanes) {
-        case 2: hipLaunchKernelGGL(resolve_kernel<2>, MI355RT_RESOLVE_ARGS); break;
-        case 4: hipLaunchKernelGGL(resolve_kernel<4>, MI355RT_RESOLVE_ARGS); break;
-        default: hipLaunchKernelGGL(resolve_kernel<8>, MI355RT_RESOLVE_ARGS); break;
+#define MI355RT_RESOLVE_ARGS grid, block, 0, stream, ps, width, nlights, slot_L, sample_slot, film_sum, film_sumsq, film_n, debug_color, ctrl, film_direct
+    if (film_direct != nullptr && !ps.use_explicit) switch (lanes) {          // a debug_sample pass adds to no film: the plain variant
+        case 2: hipLaunchKernelGGL((resolve_kernel<2, true>), MI355RT_RESOLVE_ARGS); break;
+        case 4: hipLaunchKernelGGL((resolve_kernel<4, true>), MI355RT_RESOLVE_ARGS); break;
+        default: hipLaunchKernelGGL((resolve_kernel<8, true>), MI355RT_RESOLVE_ARGS); break;
+    }
+    else switch (lanes) {
+        case 2: hipLaunchKernelGGL((resolve_kernel<2, false>), MI355RT_RESOLVE_ARGS); break;
+        case 4: hipLaunchKernelGGL((resolve_kernel<4, false>), MI355RT_RESOLVE_ARGS); break;
+        default: hipLaunchKernelGGL((resolve_kernel<8, false>), MI355RT_RESOLVE_ARGS); break;
     }
 #undef MI355RT_RESOLVE_ARGS
     return hipGetLastError();
@@ -1695,7 +1766,9 @@ hipError_t launch_tonemap(hipStream_t stream, const uint32_t* rows, uint32_t row
 }
 
 // ---- Film::clear (film.rs:37-41) of the rows a striped handle owns: one launch instead of three whole-film memsets ----
-__global__ __launch_bounds__(256) void film_clear_rows_kernel(const uint32_t* __restrict__ rows, uint32_t nrows, uint32_t width, float* film_sum, float* film_sumsq, uint32_t* film_n)
+// DIRECT: the direct film (MI355RT_FLAG_DIRECT_FILM) is a fourth plane of the film, cleared, saved and restored with the other three
+template <bool DIRECT>
+__device__ __forceinline__ void film_clear_rows_body(const uint32_t* __restrict__ rows, uint32_t nrows, uint32_t width, float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)nrows * width) return;
@@ -1703,11 +1776,23 @@ __global__ __launch_bounds__(256) void film_clear_rows_kernel(const uint32_t* __
     film_sum[3 * pixel] = 0.0f; film_sum[3 * pixel + 1] = 0.0f; film_sum[3 * pixel + 2] = 0.0f;
     film_sumsq[3 * pixel] = 0.0f; film_sumsq[3 * pixel + 1] = 0.0f; film_sumsq[3 * pixel + 2] = 0.0f;
     film_n[pixel] = 0u;
+    if constexpr (DIRECT) { film_direct[3 * pixel] = 0.0f; film_direct[3 * pixel + 1] = 0.0f; film_direct[3 * pixel + 2] = 0.0f; }
+}
+__global__ __launch_bounds__(256) void film_clear_rows_kernel(const uint32_t* __restrict__ rows, uint32_t nrows, uint32_t width, float* film_sum, float* film_sumsq, uint32_t* film_n)
+{
+    film_clear_rows_body<false>(rows, nrows, width, film_sum, film_sumsq, film_n, nullptr);
+}
+__global__ __launch_bounds__(256) void film_clear_rows_direct_kernel(const uint32_t* __restrict__ rows, uint32_t nrows, uint32_t width, float* film_sum, float* film_sumsq, uint32_t* film_n,
+                                                                    float* film_direct)
+{
+    film_clear_rows_body<true>(rows, nrows, width, film_sum, film_sumsq, film_n, film_direct);
 }
 // copy the film entries of `total` rows of the owned-row list (entries first, first + 1, ... cyclically) to a packed backup, or back
 // (Renderer::trace_frame_additive: the rows a speculatively launched 50-row frame is about to change)
-__global__ __launch_bounds__(256) void film_rows_copy_kernel(const uint32_t* __restrict__ rows, uint32_t first, uint32_t total, uint32_t nown, uint32_t width,
-                                                            float* film_sum, float* film_sumsq, uint32_t* film_n, float* bk_sum, float* bk_sumsq, uint32_t* bk_n, int restore)
+template <bool DIRECT>
+__device__ __forceinline__ void film_rows_copy_body(const uint32_t* __restrict__ rows, uint32_t first, uint32_t total, uint32_t nown, uint32_t width,
+                                                    float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct,
+                                                    float* bk_sum, float* bk_sumsq, uint32_t* bk_n, float* bk_direct, int restore)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)total * width) return;
@@ -1717,26 +1802,47 @@ __global__ __launch_bounds__(256) void film_rows_copy_kernel(const uint32_t* __r
         film_sum[3 * pixel] = bk_sum[3 * i]; film_sum[3 * pixel + 1] = bk_sum[3 * i + 1]; film_sum[3 * pixel + 2] = bk_sum[3 * i + 2];
         film_sumsq[3 * pixel] = bk_sumsq[3 * i]; film_sumsq[3 * pixel + 1] = bk_sumsq[3 * i + 1]; film_sumsq[3 * pixel + 2] = bk_sumsq[3 * i + 2];
         film_n[pixel] = bk_n[i];
+        if constexpr (DIRECT) { film_direct[3 * pixel] = bk_direct[3 * i]; film_direct[3 * pixel + 1] = bk_direct[3 * i + 1]; film_direct[3 * pixel + 2] = bk_direct[3 * i + 2]; }
     } else {
         bk_sum[3 * i] = film_sum[3 * pixel]; bk_sum[3 * i + 1] = film_sum[3 * pixel + 1]; bk_sum[3 * i + 2] = film_sum[3 * pixel + 2];
         bk_sumsq[3 * i] = film_sumsq[3 * pixel]; bk_sumsq[3 * i + 1] = film_sumsq[3 * pixel + 1]; bk_sumsq[3 * i + 2] = film_sumsq[3 * pixel + 2];
         bk_n[i] = film_n[pixel];
+        if constexpr (DIRECT) { bk_direct[3 * i] = film_direct[3 * pixel]; bk_direct[3 * i + 1] = film_direct[3 * pixel + 1]; bk_direct[3 * i + 2] = film_direct[3 * pixel + 2]; }
     }
 }
+__global__ __launch_bounds__(256) void film_rows_copy_kernel(const uint32_t* __restrict__ rows, uint32_t first, uint32_t total, uint32_t nown, uint32_t width,
+                                                            float* film_sum, float* film_sumsq, uint32_t* film_n, float* bk_sum, float* bk_sumsq, uint32_t* bk_n, int restore)
+{
+    film_rows_copy_body<false>(rows, first, total, nown, width, film_sum, film_sumsq, film_n, nullptr, bk_sum, bk_sumsq, bk_n, nullptr, restore);
+}
+__global__ __launch_bounds__(256) void film_rows_copy_direct_kernel(const uint32_t* __restrict__ rows, uint32_t first, uint32_t total, uint32_t nown, uint32_t width,
+                                                                   float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct,
+                                                                   float* bk_sum, float* bk_sumsq, uint32_t* bk_n, float* bk_direct, int restore)
+{
+    film_rows_copy_body<true>(rows, first, total, nown, width, film_sum, film_sumsq, film_n, film_direct, bk_sum, bk_sumsq, bk_n, bk_direct, restore);
+}
+// film_direct / bk_direct null (both or neither): a film of three planes
 hipError_t launch_film_rows_copy(hipStream_t stream, const uint32_t* rows, uint32_t first, uint32_t total, uint32_t nown, uint32_t width,
-                                 float* film_sum, float* film_sumsq, uint32_t* film_n, float* bk_sum, float* bk_sumsq, uint32_t* bk_n, bool restore)
+                                 float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct,
+                                 float* bk_sum, float* bk_sumsq, uint32_t* bk_n, float* bk_direct, bool restore)
 {
     const size_t n = (size_t)total * width;
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(film_rows_copy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, rows, first, total, nown, width, film_sum, film_sumsq, film_n, bk_sum, bk_sumsq, bk_n, restore ? 1 : 0);
+    if ((film_direct == nullptr) != (bk_direct == nullptr)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (film_direct) hipLaunchKernelGGL(film_rows_copy_direct_kernel, grid, dim3(256), 0, stream, rows, first, total, nown, width, film_sum, film_sumsq, film_n, film_direct,
+                                        bk_sum, bk_sumsq, bk_n, bk_direct, restore ? 1 : 0);
+    else hipLaunchKernelGGL(film_rows_copy_kernel, grid, dim3(256), 0, stream, rows, first, total, nown, width, film_sum, film_sumsq, film_n, bk_sum, bk_sumsq, bk_n, restore ? 1 : 0);
     return hipGetLastError();
 }
 
-hipError_t launch_film_clear_rows(hipStream_t stream, const uint32_t* rows, uint32_t nrows, uint32_t width, float* film_sum, float* film_sumsq, uint32_t* film_n)
+hipError_t launch_film_clear_rows(hipStream_t stream, const uint32_t* rows, uint32_t nrows, uint32_t width, float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct)
 {
     const size_t n = (size_t)nrows * width;
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(film_clear_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, rows, nrows, width, film_sum, film_sumsq, film_n);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (film_direct) hipLaunchKernelGGL(film_clear_rows_direct_kernel, grid, dim3(256), 0, stream, rows, nrows, width, film_sum, film_sumsq, film_n, film_direct);
+    else hipLaunchKernelGGL(film_clear_rows_kernel, grid, dim3(256), 0, stream, rows, nrows, width, film_sum, film_sumsq, film_n);
     return hipGetLastError();
 }
 
@@ -1772,7 +1878,7 @@ uint32_t fused_pass_lds_rows(uint32_t stack_depth, uint32_t max_level_nodes, uin
 
 hipError_t launch_fused_pass(hipStream_t stream, int num_cus, bool confirm, const DScene& sc, const DCamera& cam, const DPass& ps, uint32_t max_level_nodes, uint32_t records_per_sample,
                              void* q0, void* q1, void* hits, float* slot_L, uint32_t* sample_slot,
-                             float* film_sum, float* film_sumsq, uint32_t* film_n, DCounters* counters)
+                             float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct, DCounters* counters)
 {
     if (ps.nchunks == 0) return hipSuccess;
     if (ps.chunk > 64u) return hipErrorInvalidValue;          // the LDS lists hold one row of 64 entries per record of a sample
@@ -1780,10 +1886,12 @@ hipError_t launch_fused_pass(hipStream_t stream, int num_cus, bool confirm, cons
     unsigned blocks = (ps.nchunks + kWavesPerBlock - 1) / kWavesPerBlock;
     const unsigned cap = (unsigned)num_cus * 8u;
     if (blocks > cap) blocks = cap;
-    if (confirm) hipLaunchKernelGGL(fused_pass_kernel<true>, dim3(blocks), dim3(kBlock), lds, stream, sc, cam, ps, (float4*)q0, (float4*)q1,
-                                    (float4*)hits, slot_L, sample_slot, film_sum, film_sumsq, film_n, counters);
-    else hipLaunchKernelGGL(fused_pass_kernel<false>, dim3(blocks), dim3(kBlock), lds, stream, sc, cam, ps, (float4*)q0, (float4*)q1,
-                            (float4*)hits, slot_L, sample_slot, film_sum, film_sumsq, film_n, counters);
+#define MI355RT_FUSED_ARGS dim3(blocks), dim3(kBlock), lds, stream, sc, cam, ps, (float4*)q0, (float4*)q1, (float4*)hits, slot_L, sample_slot, film_sum, film_sumsq, film_n, film_direct, counters
+    if (film_direct && confirm) hipLaunchKernelGGL((fused_pass_kernel<true, true>), MI355RT_FUSED_ARGS);
+    else if (film_direct) hipLaunchKernelGGL((fused_pass_kernel<false, true>), MI355RT_FUSED_ARGS);
+    else if (confirm) hipLaunchKernelGGL((fused_pass_kernel<true, false>), MI355RT_FUSED_ARGS);
+    else hipLaunchKernelGGL((fused_pass_kernel<false, false>), MI355RT_FUSED_ARGS);
+#undef MI355RT_FUSED_ARGS
     return hipGetLastError();
 }
 
@@ -1819,12 +1927,14 @@ hipError_t launch_guides(hipStream_t stream, const DScene& sc, const DCamera& ca
 }
 
 hipError_t launch_denoise(hipStream_t stream, const DenoiseArgs& args, uint32_t iterations, const float* film_sum, const float* film_sumsq, const uint32_t* film_n,
-                          const float4* g0, const float4* g1, uint32_t* flags, float4* ping, float4* pong, float* rgb, uint32_t* packed)
+                          const float* film_direct, const float4* g0, const float4* g1, uint32_t* flags, float4* ping, float4* pong, float* rgb, uint32_t* packed)
 {
     const uint32_t npix = args.width * args.height;
     if (npix == 0) return hipSuccess;
     const bool last0 = iterations == 0;
-    hipLaunchKernelGGL(denoise_init_kernel, dim3((npix + 255) / 256), dim3(256), 0, stream, npix, film_sum, film_sumsq, film_n, g1, ping, flags,
+    const bool split = film_direct != nullptr && !last0;      // no iteration: the film mean itself, never cd + (c - cd)
+    if (split) hipLaunchKernelGGL(denoise_init_split_kernel, dim3((npix + 255) / 256), dim3(256), 0, stream, npix, film_sum, film_sumsq, film_n, film_direct, g1, ping, flags);
+    else hipLaunchKernelGGL(denoise_init_kernel, dim3((npix + 255) / 256), dim3(256), 0, stream, npix, film_sum, film_sumsq, film_n, g1, ping, flags,
                        last0 ? rgb : nullptr, last0 ? packed : nullptr);
     hipError_t e = hipGetLastError();
     const dim3 grid((args.width + 63) / 64, (args.height + 3) / 4);
@@ -1832,8 +1942,10 @@ hipError_t launch_denoise(hipStream_t stream, const DenoiseArgs& args, uint32_t 
         DenoiseArgs a = args;
         a.step = 1u << i;
         const bool last = i + 1 == iterations;
-        hipLaunchKernelGGL(denoise_iter_kernel, grid, dim3(256), 0, stream, a, g0, g1, (const uint32_t*)flags, (const float4*)ping, pong,
-                           last ? rgb : nullptr, last ? packed : nullptr);
+        if (split && last) hipLaunchKernelGGL(denoise_iter_split_kernel, grid, dim3(256), 0, stream, a, g0, g1, (const uint32_t*)flags, (const float4*)ping, pong,
+                                              film_direct, film_n, rgb, packed);
+        else hipLaunchKernelGGL(denoise_iter_kernel, grid, dim3(256), 0, stream, a, g0, g1, (const uint32_t*)flags, (const float4*)ping, pong,
+                                last ? rgb : nullptr, last ? packed : nullptr);
         e = hipGetLastError();
         std::swap(ping, pong);
     }

@@ -17,7 +17,8 @@ hipError_t launch_shade(hipStream_t stream, int num_cus, bool primary, bool walk
                         const void* in_q, const void* in_counts, const void* hits, void* out_q, void* out_counts, uint32_t* cursor,
                         float* slot_L, uint32_t* sample_slot, const uint32_t* film_n, DCounters* counters, bool raster = false);   // raster: primary round, hits through the tile bins inside the launch
 hipError_t launch_resolve(hipStream_t stream, const DPass& ps, uint32_t width, uint32_t nlights, const float* slot_L, const uint32_t* sample_slot,
-                          float* film_sum, float* film_sumsq, uint32_t* film_n, float* debug_color, uint32_t* ctrl);   // ctrl != null: zero the pass's work cursors on the way out
+                          float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct, float* debug_color, uint32_t* ctrl);   // ctrl != null: zero the pass's work cursors on the way out
+// film_direct (here and below): the handle's direct film (MI355RT_FLAG_DIRECT_FILM), null without the flag: the kernels of a three-plane film
 // one 50-row frame (1 sample per pixel) in a single launch: every wave takes a 64-sample chunk through all rounds
 bool kernels_walk_wide_nodes();      // this build's trace loops read BvhNode4 slots (MI355RT_WIDE), not BvhNode
 uint32_t fused_pass_lds_rows(uint32_t stack_depth, uint32_t max_level_nodes, uint32_t records_per_sample);
@@ -26,7 +27,7 @@ hipError_t launch_confirm(hipStream_t stream, int num_cus, bool primary, bool sh
                           const void* in_q, const void* in_counts, void* hits, uint32_t* cursor, float* slot_L, const uint32_t* film_n);
 hipError_t launch_fused_pass(hipStream_t stream, int num_cus, bool confirm, const DScene& sc, const DCamera& cam, const DPass& ps, uint32_t max_level_nodes, uint32_t records_per_sample,
                              void* q0, void* q1, void* hits, float* slot_L, uint32_t* sample_slot,
-                             float* film_sum, float* film_sumsq, uint32_t* film_n, DCounters* counters);
+                             float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct, DCounters* counters);
 // rows == null: the contiguous rows row_base .. row_base + nrows - 1
 hipError_t launch_tonemap(hipStream_t stream, const uint32_t* rows, uint32_t row_base, uint32_t nrows, uint32_t width, bool packed,
                           const float* film_sum, const uint32_t* film_n, uint32_t* out);
@@ -36,10 +37,11 @@ hipError_t launch_intersect(hipStream_t stream, const DScene& sc, uint32_t stack
 hipError_t launch_place_stripes(hipStream_t stream, const uint32_t* gathered, uint32_t* frame, uint32_t width, uint32_t height,
                                 uint32_t stripe_rows, uint32_t world, uint32_t slot_rows);
 // Film::clear restricted to the listed rows (a striped handle's own rows)
-hipError_t launch_film_clear_rows(hipStream_t stream, const uint32_t* rows, uint32_t nrows, uint32_t width, float* film_sum, float* film_sumsq, uint32_t* film_n);
+hipError_t launch_film_clear_rows(hipStream_t stream, const uint32_t* rows, uint32_t nrows, uint32_t width, float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct);
 // film entries of `total` rows of the owned-row list (cyclic from entry `first`) -> packed backup, or back
 hipError_t launch_film_rows_copy(hipStream_t stream, const uint32_t* rows, uint32_t first, uint32_t total, uint32_t nown, uint32_t width,
-                                 float* film_sum, float* film_sumsq, uint32_t* film_n, float* bk_sum, float* bk_sumsq, uint32_t* bk_n, bool restore);
+                                 float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct,
+                                 float* bk_sum, float* bk_sumsq, uint32_t* bk_n, float* bk_direct, bool restore);
 hipError_t launch_slab(hipStream_t stream, const float* inv_rays6, const float* cubes6, uint32_t n, uint8_t* hit, float* tmin);
 // adaptive sampling: out[tile] = the tile is active; *count (zeroed by the caller) += (owned pixels << 32) | 1 per active tile
 hipError_t launch_adaptive_tiles(hipStream_t stream, const AdaptiveArgs& a, const float* film_sum, const float* film_sumsq, const uint32_t* film_n,
@@ -47,9 +49,10 @@ hipError_t launch_adaptive_tiles(hipStream_t stream, const AdaptiveArgs& a, cons
 hipError_t launch_film_stat(hipStream_t stream, bool variances, size_t npix, const float* film_sum, const float* film_sumsq, const uint32_t* film_n, float* out);
 // denoised read-out: the guides of the camera cam (cam.width x cam.height pixels; flags bit 0: FIX_ROW_INDEX), mode as launch_intersect
 hipError_t launch_guides(hipStream_t stream, const DScene& sc, const DCamera& cam, uint32_t flags, uint32_t stack_depth, int mode, float4* g0, float4* g1);
-// film -> `iterations` filter iterations ping-ponging ping / pong (npix float4 each; flags: npix u32) -> rgb (npix * 3 floats) and / or packed (npix u32)
+// film -> `iterations` filter iterations ping-ponging ping / pong (npix float4 each; flags: npix u32) -> rgb (npix * 3 floats) and / or packed (npix u32);
+// film_direct non-null: the split read-out (the indirect part is filtered, the direct part added back)
 hipError_t launch_denoise(hipStream_t stream, const DenoiseArgs& args, uint32_t iterations, const float* film_sum, const float* film_sumsq, const uint32_t* film_n,
-                          const float4* g0, const float4* g1, uint32_t* flags, float4* ping, float4* pong, float* rgb, uint32_t* packed);
+                          const float* film_direct, const float4* g0, const float4* g1, uint32_t* flags, float4* ping, float4* pong, float* rgb, uint32_t* packed);
 // the gather microbenchmark behind bench.py's roofline: num_cus * 8 blocks walk `steps` random nodes of `table` each
 hipError_t launch_gather_rate(hipStream_t stream, int num_cus, const void* table, uint32_t nnodes, uint32_t steps, uint32_t* sink);
 hipError_t launch_numerics(hipStream_t stream, const float* a, const float* b, uint32_t n, float* q, float* r, float* p);

@@ -41,6 +41,13 @@ public:
         mi355rt_film_get_pixels(h_, out.data());
         return out;
     }
+    // the direct film of a handle created with MI355RT_FLAG_DIRECT_FILM (include/mi355rt.h): width*height*3 sums
+    std::vector<float> direct_sums() const
+    {
+        std::vector<float> out((size_t)mi355rt_width(h_) * mi355rt_height(h_) * 3);
+        if (mi355rt_film_get_direct(h_, out.data()) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+        return out;
+    }
 private:
     friend class RayTracer;
     mi355rt_handle* h_ = nullptr;
@@ -93,6 +100,13 @@ public:
     {
         std::vector<uint32_t> out((size_t)mi355rt_width(h_) * mi355rt_height(h_));
         if (mi355rt_get_denoised_pixels(h_, &cfg, nullptr, out.data(), out.size()) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+        return out;
+    }
+    // the same with only the indirect part filtered (a handle created with MI355RT_FLAG_DIRECT_FILM)
+    std::vector<uint32_t> get_denoised_pixels_split(const mi355rt_denoise_config& cfg) const
+    {
+        std::vector<uint32_t> out((size_t)mi355rt_width(h_) * mi355rt_height(h_));
+        if (mi355rt_get_denoised_pixels_split(h_, &cfg, nullptr, out.data(), out.size()) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
         return out;
     }
     mi355rt_handle* handle() const { return h_; }

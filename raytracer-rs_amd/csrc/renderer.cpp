@@ -98,8 +98,8 @@ bool Renderer::set_seed(uint64_t seed)
 // mi355rt_set_flags: run-time flags only; a create-time flag (the intersector) cannot be changed on a live handle
 bool Renderer::set_flags(uint32_t flags)
 {
-    constexpr uint32_t kCreateMask = MI355RT_FLAG_OCTREE_SEMANTICS | MI355RT_FLAG_TRUE_CLOSEST_HIT | MI355RT_FLAG_GROUP_SHARES_DEVICE | MI355RT_FLAG_DEVICE_LBVH;
-    if ((flags ^ cfg.flags) & kCreateMask) { last_error = "the intersector flags (OCTREE_SEMANTICS, TRUE_CLOSEST_HIT) are create-time flags: they cannot be changed with mi355rt_set_flags"; return false; }
+    constexpr uint32_t kCreateMask = MI355RT_FLAG_OCTREE_SEMANTICS | MI355RT_FLAG_TRUE_CLOSEST_HIT | MI355RT_FLAG_GROUP_SHARES_DEVICE | MI355RT_FLAG_DEVICE_LBVH | MI355RT_FLAG_DIRECT_FILM;
+    if ((flags ^ cfg.flags) & kCreateMask) { last_error = "the intersector flags (OCTREE_SEMANTICS, TRUE_CLOSEST_HIT), GROUP_SHARES_DEVICE, DEVICE_LBVH and DIRECT_FILM are create-time flags: they cannot be changed with mi355rt_set_flags"; return false; }
     if (flags != cfg.flags && !settle_speculation()) return false;
     cfg.flags = flags;
     return true;
@@ -295,6 +295,7 @@ bool Renderer::init(const SceneData& scene, std::string& err, int& code)
     // --- film (film.rs:27-35) and row lists
     const size_t npix = (size_t)cfg.width * cfg.height;
     if (!upload(d_film_sum_, nullptr, npix * 12) || !upload(d_film_sumsq_, nullptr, npix * 12) || !upload(d_film_n_, nullptr, npix * 4)) return bail();
+    if ((cfg.flags & MI355RT_FLAG_DIRECT_FILM) && !upload(d_film_direct_, nullptr, npix * 12)) return bail();     // the direct film: only with the flag
     if (!upload(d_ldr_, nullptr, npix * 4)) return bail();
     ldr_dirty_.assign(cfg.height, (uint8_t)1);
     if (hipEventCreateWithFlags(&ev_tonemap_, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ev_gather_, hipEventDisableTiming) != hipSuccess) { err = "hipEventCreate failed"; return false; }
@@ -837,7 +838,7 @@ bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32
         if (r <= cfg.recursions)
             HIP_TRY(launch_shade(st, num_cus_, r == 0, shade_walks, dscene_, cam, ps, r, in_q, in_c, sl.d_hits.get(), sl.d_queue[r & 1].get(), sl.d_chunk_counts[r & 1].get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound + kShadeCursorOffset, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_n_.get(), d_counters_.get(), fuse_primary));
     }
-    HIP_TRY(launch_resolve(st, ps, cfg.width, nlights_, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_debug_color_.get(), sl.d_ctrl.get()));
+    HIP_TRY(launch_resolve(st, ps, cfg.width, nlights_, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_film_direct_.get(), d_debug_color_.get(), sl.d_ctrl.get()));
     sl.ctrl_clean = true;
     return true;
 }
@@ -1029,22 +1030,23 @@ uint32_t Renderer::trace_frame_additive()
     const FrameWindow nxt = frame_window(current_row, cfg.height, cfg.stripe_rows, cfg.stripe_world, cfg.stripe_rank, owned_rows);
     if (!no_spec && !timed && cfg.stripe_world <= 1 && ev_call_done_ && read_stream_ && win.total <= nown && nxt.total != 0 && win.total + nxt.total <= nown) {
         const size_t bk = (size_t)50 * cfg.width;
-        if (!d_bk_sum_) {          // all five or none: the next call takes a non-null d_bk_sum_ for the whole set
-            DeviceBuffer<float> sum, sumsq; DeviceBuffer<uint32_t> n; DeviceBuffer<DCounters> dc; PinnedBuffer<DCounters> hc;
+        if (!d_bk_sum_) {          // all of them or none: the next call takes a non-null d_bk_sum_ for the whole set (a handle with a direct film: its backup plane too)
+            DeviceBuffer<float> sum, sumsq, direct; DeviceBuffer<uint32_t> n; DeviceBuffer<DCounters> dc; PinnedBuffer<DCounters> hc;
             if (sum.alloc(bk * 12, &hbm_bytes_) != hipSuccess || sumsq.alloc(bk * 12, &hbm_bytes_) != hipSuccess || n.alloc(bk * 4, &hbm_bytes_) != hipSuccess
+                || (d_film_direct_ && direct.alloc(bk * 12, &hbm_bytes_) != hipSuccess)
                 || dc.alloc(sizeof(DCounters) * kShards, &hbm_bytes_) != hipSuccess || hc.alloc(sizeof(DCounters) * kShards) != hipSuccess) {
                 (void)hipGetLastError(); return 50u * cfg.width;            // no room to speculate: the frame asked for is queued all the same
             }
-            d_bk_sum_ = std::move(sum); d_bk_sumsq_ = std::move(sumsq); d_bk_n_ = std::move(n); d_counters_spec_ = std::move(dc); h_counters_spec_ = std::move(hc);
+            d_bk_sum_ = std::move(sum); d_bk_sumsq_ = std::move(sumsq); d_bk_n_ = std::move(n); d_bk_direct_ = std::move(direct); d_counters_spec_ = std::move(dc); h_counters_spec_ = std::move(hc);
         }
-        const bool backed_up = launch_film_rows_copy(stream_, d_owned_rows_.get(), nxt.first, nxt.total, nown, cfg.width, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_bk_sum_.get(), d_bk_sumsq_.get(), d_bk_n_.get(), false) == hipSuccess;
+        const bool backed_up = launch_film_rows_copy(stream_, d_owned_rows_.get(), nxt.first, nxt.total, nown, cfg.width, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_film_direct_.get(), d_bk_sum_.get(), d_bk_sumsq_.get(), d_bk_n_.get(), d_bk_direct_.get(), false) == hipSuccess;
         bool ok = backed_up
                   && hipMemsetAsync(d_counters_spec_.get(), 0, sizeof(DCounters) * kShards, stream_) == hipSuccess
                   && launch_fused_window(nxt.first, nxt.total, cam, d_counters_spec_.get())
                   && hipMemcpyAsync(h_counters_spec_.get(), d_counters_spec_.get(), sizeof(DCounters) * kShards, hipMemcpyDeviceToHost, stream_) == hipSuccess
                   && hipEventRecord(ev_spec_done_, stream_) == hipSuccess;
         if (!ok) { (void)hipGetLastError(); HIP_TRY(hipStreamSynchronize(stream_));        // what was queued of it ran; put the rows back (if they were saved) and go on without
-                   if (backed_up) (void)launch_film_rows_copy(stream_, d_owned_rows_.get(), nxt.first, nxt.total, nown, cfg.width, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_bk_sum_.get(), d_bk_sumsq_.get(), d_bk_n_.get(), true); }
+                   if (backed_up) (void)launch_film_rows_copy(stream_, d_owned_rows_.get(), nxt.first, nxt.total, nown, cfg.width, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_film_direct_.get(), d_bk_sum_.get(), d_bk_sumsq_.get(), d_bk_n_.get(), d_bk_direct_.get(), true); }
         else { spec_.valid = true; spec_.row = current_row; spec_.first = nxt.first; spec_.total = nxt.total; spec_.next_row = nxt.next_row; spec_.cam_key = cam_key; spec_.seed = cfg.seed; spec_.flags = cfg.flags; ++spec_launched_; }
     }
     return 50u * cfg.width;
@@ -1063,7 +1065,7 @@ bool Renderer::launch_fused_window(uint32_t first, uint32_t total, const DCamera
     describe_pass(ps, sl, d_owned_rows_.get(), first, nown, (uint32_t)nsamples, nsamples, fchunk, false, 0, 0);
     if (ps.nchunks > sl.count_entries || (size_t)ps.nchunks * ps.region > sl.queue_records) { last_error = "internal: fused pass does not fit the pass buffers"; return false; }
     hipError_t e = launch_fused_pass(stream_, num_cus_, mode_ == kModeConfirm, dscene_, cam, ps, max_level_nodes_, records_per_sample_, sl.d_queue[0].get(), sl.d_queue[1].get(),
-                                     sl.d_hits.get(), sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), dcounters);
+                                     sl.d_hits.get(), sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_film_direct_.get(), dcounters);
     if (e != hipSuccess) return fail(e, "fused pass launch");
     return true;
 }
@@ -1074,7 +1076,7 @@ bool Renderer::settle_speculation()
     if (!spec_.valid) return true;
     spec_.valid = false;
     if (!bind()) return false;
-    HIP_TRY(launch_film_rows_copy(stream_, d_owned_rows_.get(), spec_.first, spec_.total, (uint32_t)owned_rows.size(), cfg.width, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_bk_sum_.get(), d_bk_sumsq_.get(), d_bk_n_.get(), true));
+    HIP_TRY(launch_film_rows_copy(stream_, d_owned_rows_.get(), spec_.first, spec_.total, (uint32_t)owned_rows.size(), cfg.width, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_film_direct_.get(), d_bk_sum_.get(), d_bk_sumsq_.get(), d_bk_n_.get(), d_bk_direct_.get(), true));
     return true;
 }
 
@@ -1350,6 +1352,17 @@ bool Renderer::film_get(float* sum, float* sumsq, uint32_t* n)
     return true;
 }
 
+// mi355rt_film_get_direct: the caller has checked the flag
+bool Renderer::film_get_direct(float* sum)
+{
+    if (!bind()) return false;
+    if (!d_film_direct_) { last_error = "internal: no direct film"; return false; }
+    if (!settle_speculation()) return false;
+    HIP_TRY(hipStreamSynchronize(stream_));
+    HIP_TRY(hipMemcpy(sum, d_film_direct_.get(), (size_t)cfg.width * cfg.height * 12, hipMemcpyDeviceToHost));
+    return true;
+}
+
 bool Renderer::film_clear()
 {
     if (!bind()) return false;
@@ -1359,12 +1372,13 @@ bool Renderer::film_clear()
     if (cfg.stripe_world > 1) {
         // a striped handle only ever writes its own rows (the others stay as created: zero): one launch over them instead of three
         // whole-film memsets — 20 us of a 3.3 ms frame on one rank of eight
-        HIP_TRY(launch_film_clear_rows(stream_, d_owned_rows_.get(), (uint32_t)owned_rows.size(), cfg.width, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get()));
+        HIP_TRY(launch_film_clear_rows(stream_, d_owned_rows_.get(), (uint32_t)owned_rows.size(), cfg.width, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_film_direct_.get()));
         return true;
     }
     HIP_TRY(hipMemsetAsync(d_film_sum_.get(), 0, npix * 12, stream_));
     HIP_TRY(hipMemsetAsync(d_film_sumsq_.get(), 0, npix * 12, stream_));
     HIP_TRY(hipMemsetAsync(d_film_n_.get(), 0, npix * 4, stream_));
+    if (d_film_direct_) HIP_TRY(hipMemsetAsync(d_film_direct_.get(), 0, npix * 12, stream_));
     return true;            // stream-ordered: every later call on this handle starts on the same stream
 }
 
@@ -1513,9 +1527,10 @@ bool Renderer::get_guides(float* depth, float* normal3, float* albedo3, uint32_t
     return true;
 }
 
-bool Renderer::get_denoised(const mi355rt_denoise_config& dc, float* rgb, uint32_t* packed)
+bool Renderer::get_denoised(const mi355rt_denoise_config& dc, float* rgb, uint32_t* packed, bool split)
 {
     if (!bind()) return false;
+    if (split && !d_film_direct_) { last_error = "internal: no direct film"; return false; }
     if (!settle_speculation()) return false;
     const size_t npix = (size_t)cfg.width * cfg.height;
     if (!d_dn_ping_) {                        // all five or none
@@ -1531,7 +1546,8 @@ bool Renderer::get_denoised(const mi355rt_denoise_config& dc, float* rgb, uint32
     DenoiseArgs a{};
     a.width = cfg.width; a.height = cfg.height; a.step = 1u; a.normal_power_log2 = dc.normal_power_log2;
     a.sigma_luminance = dc.sigma_luminance; a.sigma_depth = dc.sigma_depth; a.sigma_albedo = dc.sigma_albedo;
-    HIP_TRY(launch_denoise(stream_, a, dc.iterations, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_guide0_.get(), d_guide1_.get(), d_dn_flags_.get(),
+    HIP_TRY(launch_denoise(stream_, a, dc.iterations, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), split ? d_film_direct_.get() : nullptr,
+                           d_guide0_.get(), d_guide1_.get(), d_dn_flags_.get(),
                            d_dn_ping_.get(), d_dn_pong_.get(), rgb ? d_dn_rgb_.get() : nullptr, packed ? d_dn_packed_.get() : nullptr));
     if (rgb) HIP_TRY(hipMemcpyAsync(rgb, d_dn_rgb_.get(), npix * 12, hipMemcpyDeviceToHost, stream_));
     if (packed) HIP_TRY(hipMemcpyAsync(packed, d_dn_packed_.get(), npix * 4, hipMemcpyDeviceToHost, stream_));

@@ -31,6 +31,7 @@ public:
     bool tonemap_owned_rows_device(uint32_t* device_out, size_t n, hipStream_t caller_stream = nullptr);
     bool last_counts(mi355rt_ray_counts& out);
     bool film_get(float* sum, float* sumsq, uint32_t* n);
+    bool film_get_direct(float* sum);                                   // the direct film (MI355RT_FLAG_DIRECT_FILM), width * height * 3 floats
     bool set_seed(uint64_t seed);
     bool set_flags(uint32_t flags);
     bool film_clear();                                                  // film.rs:37-41
@@ -58,7 +59,8 @@ public:
     bool film_stat(bool variances, float* rgb);
     // denoised read-out; the caller has checked the arguments (a whole image on one device, a valid config)
     bool get_guides(float* depth, float* normal3, float* albedo3, uint32_t* prim);
-    bool get_denoised(const mi355rt_denoise_config& dc, float* rgb, uint32_t* packed);
+    bool get_denoised(const mi355rt_denoise_config& dc, float* rgb, uint32_t* packed, bool split = false);   // split: the indirect part is filtered
+    bool has_direct_film() const { return (cfg.flags & MI355RT_FLAG_DIRECT_FILM) != 0; }
     void speculation_stats(uint64_t out[2]) const { out[0] = spec_launched_; out[1] = spec_adopted_; }
     bool debug_numerics(const float* a, const float* b, size_t n, float* q, float* r, float* p);
     bool debug_sample(uint32_t pixel, uint32_t sampleno, float* color3, float* node_L, size_t nodes);
@@ -181,6 +183,7 @@ private:
 
     DScene dscene_{};
     DeviceBuffer<float> d_film_sum_, d_film_sumsq_; DeviceBuffer<uint32_t> d_film_n_;
+    DeviceBuffer<float> d_film_direct_;  // MI355RT_FLAG_DIRECT_FILM: per pixel, the sum of its samples' root light terms (null without the flag)
     DeviceBuffer<uint32_t> d_owned_rows_, d_all_rows_, d_tmp_rows_;
     DeviceBuffer<uint32_t> d_ldr_;
     PinnedBuffer<uint32_t> h_ldr_;       // host mirror of d_ldr_ (get_tonemapped_pixels)
@@ -200,6 +203,7 @@ private:
     struct Speculation { bool valid = false; uint32_t row = 0, first = 0, total = 0, next_row = 0; std::vector<float> cam_key; uint64_t seed = 0; uint32_t flags = 0; } spec_;
     DeviceBuffer<DCounters> d_counters_spec_; PinnedBuffer<DCounters> h_counters_spec_;
     DeviceBuffer<float> d_bk_sum_, d_bk_sumsq_; DeviceBuffer<uint32_t> d_bk_n_;
+    DeviceBuffer<float> d_bk_direct_;    // with d_film_direct_ only
     hipStream_t read_stream_ = nullptr;
     hipEvent_t ev_call_done_ = nullptr, ev_spec_done_ = nullptr;      // behind the kernel (and the counters' copy) of the frame last asked for / of the speculative one
     bool call_done_valid_ = false;        // ev_call_done_ marks the last 50-row frame: read-outs wait for it, not for the stream

@@ -103,3 +103,28 @@ def denoise(s, q, n, guides, width, height, iterations, normal_power_log2, sigma
         c, var = iterate(c, var, empty, unknown, hit, normal, depth, albedo, width, height, 1 << i, normal_power_log2,
                          sigma_luminance, sigma_depth, sigma_albedo)
     return c, pack(c)
+
+
+def denoise_split(s, q, n, d, guides, width, height, iterations, normal_power_log2, sigma_luminance, sigma_depth, sigma_albedo):
+    """(rgb, packed) of the split read-out (mi355rt_get_denoised_pixels_split): d float32[npix, 3] is the direct film
+    (RayTracer.film.direct_sums()); the indirect part (s - d) / n is filtered under the total's variance and d / n is added back"""
+    npix = width * height
+    c, var = film_inputs(s, q, n)
+    assert c.shape[0] == npix
+    if iterations == 0:
+        return c, pack(c)                                                     # the film mean itself, not cd + (c - cd)
+    d = _f32(d, (-1, 3))
+    n = np.asarray(n).reshape(-1)
+    prim = np.asarray(guides["prim"]).reshape(-1)
+    assert prim.dtype == np.uint32, prim.dtype
+    normal = _f32(guides["normal"], (-1, 3)); albedo = _f32(guides["albedo"], (-1, 3)); depth = _f32(guides["depth"], (-1,))
+    empty, unknown, hit = n == 0, n == 1, prim != np.uint32(MISS)
+    with np.errstate(all="ignore"):
+        cd = d * (F(1) / n.astype(np.float32)[:, None])
+        ci = np.where(empty[:, None], c, c - cd).astype(np.float32)            # an empty pixel keeps its mean as it stands
+    for i in range(iterations):
+        ci, var = iterate(ci, var, empty, unknown, hit, normal, depth, albedo, width, height, 1 << i, normal_power_log2,
+                          sigma_luminance, sigma_depth, sigma_albedo)
+    with np.errstate(all="ignore"):
+        out = np.where(empty[:, None], ci, cd + ci).astype(np.float32)
+    return out, pack(out)

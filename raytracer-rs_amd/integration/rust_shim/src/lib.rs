@@ -37,6 +37,10 @@ pub const DEFAULT_TRIANGLES_PER_LEAF: usize = 70;
     seed: u64, device: i32, stripe_rows: u32, stripe_rank: u32, stripe_world: u32, samples_per_pass: u32,
     device_count: u32,      // > 1: the handle drives that many GPUs of this process (rows dealt in stripes, gathered on the first)
 }
+/// create-time flag (declared for a caller that sets cfg.flags itself; this shim sets none): the handle keeps a direct film, the sum of
+/// every sample's root light term, which the two direct-film entries below read
+pub const MI355RT_FLAG_DIRECT_FILM: u32 = 128;
+#[allow(dead_code)] #[repr(C)] pub struct mi355rt_denoise_config { pub iterations: u32, pub normal_power_log2: u32, pub sigma_luminance: f32, pub sigma_depth: f32, pub sigma_albedo: f32 }
 extern "C" {
     fn mi355rt_default_config(cfg: *mut mi355rt_config);
     fn mi355rt_create(scene: *const mi355rt_scene_desc, cfg: *const mi355rt_config, out: *mut *mut mi355rt_handle) -> c_int;
@@ -45,6 +49,8 @@ extern "C" {
     fn mi355rt_trace_frame_additive(h: *mut mi355rt_handle) -> u32;
     fn mi355rt_get_tonemapped_pixels(h: *mut mi355rt_handle, out: *mut u32, n: usize) -> c_int;
     fn mi355rt_film_clear(h: *mut mi355rt_handle) -> c_int;
+    fn mi355rt_film_get_direct(h: *mut mi355rt_handle, sum_rgb: *mut f32) -> c_int;
+    fn mi355rt_get_denoised_pixels_split(h: *mut mi355rt_handle, cfg: *const mi355rt_denoise_config, rgb: *mut f32, packed: *mut u32, npix: usize) -> c_int;
     fn mi355rt_camera_move_rel(h: *mut mi355rt_handle, x: f32, y: f32, z: f32) -> c_int;
     fn mi355rt_camera_add_x_angle(h: *mut mi355rt_handle, radians: f32) -> c_int;
     fn mi355rt_camera_add_y_angle(h: *mut mi355rt_handle, radians: f32) -> c_int;

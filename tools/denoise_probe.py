@@ -10,8 +10,12 @@ Prints one JSON line per measurement:
   sweep       one field of the default config varied at a time, at 8 and 16 spp: RMSE of the denoised image; `best` lines name the winner
   dropin      the drop-in loop at 1024x768 (trace_frame_additive + a read-out per step): ms per step with get_tonemapped_pixels and with
               the denoised read-out (which settles the speculative next frame every step)
+  --split      a second handle of the same seed created with FLAG_DIRECT_FILM renders the same films; every `spp` line gains
+              render_ms_direct_film (against render_ms: what keeping the direct film costs), split_ms_cached (the split read-out, guides
+              cached) and rmse_split / rmse_tm_split beside the raw and denoised columns, and the drop-in loop runs once more on a handle
+              with the flag (`dropin_direct_film` lines: get_tonemapped_pixels and the split read-out)
 Timings are wall-clock medians of --reps calls after one warm-up call.
-usage: tools/denoise_probe.py [--width 1920 --height 1080] [--reps 5] [--ref-spp 1024] [--skip-sweep] [--skip-dropin]"""
+usage: tools/denoise_probe.py [--width 1920 --height 1080] [--reps 5] [--ref-spp 1024] [--skip-sweep] [--skip-dropin] [--split]"""
 import argparse
 import json
 import os
@@ -32,6 +36,7 @@ def main():
     ap.add_argument("--ref-spp", type=int, default=1024)
     ap.add_argument("--skip-sweep", action="store_true")
     ap.add_argument("--skip-dropin", action="store_true")
+    ap.add_argument("--split", action="store_true")
     a = ap.parse_args()
     import __graft_entry__ as ge
     pkg = ge.load_package()
@@ -53,6 +58,7 @@ def main():
     ref_rt.close()
 
     rt = pkg.create_raytracer_from_arrays(scene, pkg.DEFAULT_TRIANGLES_PER_LEAF, w, h, seed=1)
+    rs = pkg.create_raytracer_from_arrays(scene, pkg.DEFAULT_TRIANGLES_PER_LEAF, w, h, seed=1, flags=pkg.FLAG_DIRECT_FILM) if a.split else None
 
     def errors(p):
         p = np.asarray(p, np.float64)
@@ -68,7 +74,7 @@ def main():
                 ts.append(dt)
         return float(np.median(ts))
 
-    def render_ms(spp):
+    def render_ms(spp, rt=rt):
         def before(_):
             rt.film.clear(); rt.synchronize()
         return median_ms(lambda: rt.render(spp), before)
@@ -91,6 +97,12 @@ def main():
         den = errors(den_rgb)
         row = dict(what="spp", spp=spp, render_ms=round(ms_r, 3), denoise_ms_cached=round(ms_cached, 3), denoise_ms_cold=round(ms_cold, 3),
                    rmse_raw=raw[0], rmse_denoised=den[0], rmse_tm_raw=raw[1], rmse_tm_denoised=den[1])
+        if rs is not None:
+            ms_rs = render_ms(spp, rs)             # the same film, and the direct film beside it
+            rs.get_denoised_pixels(split=True, rgb=False)
+            ms_split = median_ms(lambda: rs.get_denoised_pixels(split=True, rgb=False))
+            spl = errors(rs.get_denoised_pixels(split=True, packed=False)[0])
+            row.update(render_ms_direct_film=round(ms_rs, 3), split_ms_cached=round(ms_split, 3), rmse_split=spl[0], rmse_tm_split=spl[1])
         rows.append(row)
         emit(**row)
     ms_per_spp = rows[-1]["render_ms"] / 64.0
@@ -115,21 +127,27 @@ def main():
                     emit(what="sweep", spp=spp, field=field, value=v, rmse_denoised=e[0], rmse_tm_denoised=e[1])
                 emit(what="best", spp=spp, field=field, value=min(res)[1], rmse_tm_denoised=min(res)[0])
     rt.close()
+    if rs is not None:
+        rs.close()
 
     if not a.skip_dropin:
-        d = pkg.create_raytracer_from_arrays(scene, pkg.DEFAULT_TRIANGLES_PER_LEAF, 1024, 768, seed=1)
         out = np.empty(1024 * 768, np.uint32)
-        for label, read in (("tonemapped", lambda: d.get_tonemapped_pixels(out)), ("denoised", lambda: d.get_denoised_pixels(rgb=False)),
-                            ("tonemapped", lambda: d.get_tonemapped_pixels(out)), ("denoised", lambda: d.get_denoised_pixels(rgb=False))):
-            for _ in range(20):
-                d.trace_frame_additive(); read()
-            steps = 200
-            t = time.perf_counter()
-            for _ in range(steps):
-                d.trace_frame_additive(); read()
-            d.synchronize()
-            emit(what="dropin", readout=label, ms_per_step=round((time.perf_counter() - t) * 1e3 / steps, 4), speculation=d.debug_speculation())
-        d.close()
+        handles = [("", 0)] + ([("_direct_film", pkg.FLAG_DIRECT_FILM)] if a.split else [])      # --split: the same loop on a handle with the flag
+        for suffix, flags in handles:
+            d = pkg.create_raytracer_from_arrays(scene, pkg.DEFAULT_TRIANGLES_PER_LEAF, 1024, 768, seed=1, flags=flags)
+            reads = [("tonemapped", lambda: d.get_tonemapped_pixels(out)), ("denoised", lambda: d.get_denoised_pixels(rgb=False))]
+            if flags:
+                reads[1] = ("split", lambda: d.get_denoised_pixels(split=True, rgb=False))
+            for label, read in reads + reads:
+                for _ in range(20):
+                    d.trace_frame_additive(); read()
+                steps = 200
+                t = time.perf_counter()
+                for _ in range(steps):
+                    d.trace_frame_additive(); read()
+                d.synchronize()
+                emit(what="dropin" + suffix, readout=label, ms_per_step=round((time.perf_counter() - t) * 1e3 / steps, 4), speculation=d.debug_speculation())
+            d.close()
 
 
 if __name__ == "__main__":
