@@ -27,7 +27,7 @@ extern "C" {
 #define MI355RT_OK            0
 #define MI355RT_E_INVALID    -1   /* bad argument */
 #define MI355RT_E_NO_DEVICE  -2   /* no HIP device / HIP runtime error */
-#define MI355RT_E_LOAD       -3   /* scene load error (SceneLoadError, loaders/mod.rs:20-25) */
+#define MI355RT_E_LOAD       -3   /* scene load error (SceneLoadError, loaders/mod.rs:20-25); film file error (mi355rt_film_load / _save / _file_info) */
 #define MI355RT_E_HIP        -4   /* HIP runtime error after creation */
 
 /* DEFAULT_TRIANGLES_PER_LEAF, oct_tree_intersector.rs:12 / lib.rs:7 */
@@ -329,6 +329,53 @@ int mi355rt_film_get(mi355rt_handle* h, float* sum_rgb, float* sumsq_rgb, uint32
 int mi355rt_film_clear(mi355rt_handle* h);                                   /* Film::clear, film.rs:37-41 */
 int mi355rt_film_get_pixels(mi355rt_handle* h, float* rgb);                  /* Film::get_pixels, film.rs:43-47 */
 int mi355rt_film_get_estimated_variances(mi355rt_handle* h, float* rgb);     /* film.rs:51-67 */
+
+/* ---- film set, add, save and load: resume and combine renders (no reference counterpart).  The film (n, sum, sumsq, and direct
+ * with MI355RT_FLAG_DIRECT_FILM) is all a progressive render accumulates, and sample s of a call is numbered film_n + s (see mi355rt_render_adaptive
+ * above), so a film that is put back is a complete checkpoint: a render continued from it equals, bit for bit, one that was never interrupted.
+ *
+ * SET AND ADD.  The planes are whole images in the layout of mi355rt_film_get / mi355rt_film_get_direct: sum_rgb, sumsq_rgb and direct_rgb hold
+ * width*height*3 floats, n holds width*height counts.  npix must equal width*height; sum_rgb, sumsq_rgb and n are required; direct_rgb must be
+ * non-NULL exactly when the handle has MI355RT_FLAG_DIRECT_FILM.  A violation returns MI355RT_E_INVALID, names the argument in mi355rt_last_error
+ * and leaves the film untouched.  The values are data: they are not validated.
+ *     set : the film's entries become the input's, bits unchanged (a NaN keeps its payload, -0.0 its sign)
+ *     add : per pixel and channel s' = s + a, q' = q + b, d' = d + e, each ONE f32 addition with the handle's value on the left, and n' = n + m in
+ *           u32 (an overflow of n is the caller's business: not checked)
+ * Only the rows the handle owns (mi355rt_owned_row_list: (row / stripe_rows) % stripe_world == stripe_rank) are written; the input's other rows are
+ * ignored, so on a striped handle every other row stays zero, as mi355rt_film_clear, mi355rt_film_get and the tone-mapper expect.  A device group
+ * (config.device_count > 1) hands the planes to each member, which takes its own rows: mi355rt_film_get afterwards returns what one handle would.
+ * A queued mi355rt_render_async and a speculative 50-row frame are settled first (the frame's rows are given back BEFORE the film is written; the
+ * other order would overwrite the new film), every row is marked changed for mi355rt_get_tonemapped_pixels, and nothing else of the handle changes:
+ * camera, seed, flags, mi355rt_current_row, the last counters, the denoiser's guides and the culling caches stay.  The call returns once the
+ * caller's arrays may be reused; later calls on the handle are ordered behind it.  The device staging (28 bytes per pixel, 40 with a direct plane)
+ * is temporary: mi355rt_hbm_allocated_bytes is the same before and after.
+ *
+ * FILM FILE, version 1, little-endian: a 64-byte header, then the planes, nothing else.
+ *     header: magic "MI355FLM" (8 bytes) | u32 version = 1 | u32 width | u32 height | u32 planes (bit 0: a direct plane is present; other bits 0)
+ *             | u64 seed (low 32 bits used) | u32 flags (the handle's config.flags at save) | zeros up to byte 64
+ *     planes: n (u32 x npix) | sum (f32 x 3 npix) | sumsq (f32 x 3 npix) | direct (f32 x 3 npix, only with bit 0 of `planes`);  npix = width*height
+ * The file's length must be exactly 64 + npix * 28 (40 with a direct plane) bytes.
+ * mi355rt_film_save writes what mi355rt_film_get and mi355rt_film_get_direct return (a striped handle: zeros in the rows it does not own; a device
+ * group: its gathered film).  A file that cannot be written: MI355RT_E_LOAD.
+ * mi355rt_film_load reads and checks the WHOLE file before it touches the device, then sets (add == 0) or adds (add != 0) its planes as above.
+ * It returns MI355RT_E_LOAD, names the reason in mi355rt_last_error and leaves the film untouched for: a file that cannot be read, bad magic or
+ * version, unknown `planes` bits, a width or height that differs from the handle's, a wrong file length, a MI355RT_FLAG_FIX_ROW_INDEX bit in the
+ * header's flags that differs from the handle's current flag (the pixel -> ray mapping differs), and a file without a direct plane for a handle with
+ * MI355RT_FLAG_DIRECT_FILM.  A file WITH a direct plane loads into a handle without the flag: the plane is skipped (the header said it was there).
+ * Neither the camera nor the scene is checked: that the film belongs to this view is the caller's word.
+ * mi355rt_film_file_info is HOST code (no device, no handle): out = version, width, height, planes, seed low, seed high, flags, 0.  It makes the
+ * file's own checks (magic, version, planes bits, non-zero size, length), returns MI355RT_E_LOAD for them and leaves the reason in
+ * mi355rt_last_error(NULL).
+ *
+ * RECIPES.  Resume: save; later create a handle with the same scene, camera, seed and flags, load, render on.  Stripes to the denoiser: add every
+ * rank's mi355rt_film_get (zero outside its rows, so 0 + x is exact) into one unstriped handle, which then serves mi355rt_get_denoised_pixels.
+ * Disjoint sample ranges of one seed: a worker sets zero sums with n = offset and renders k samples, its film then holds samples offset ..
+ * offset + k - 1; the caller subtracts offset from its n before merging. */
+int mi355rt_film_set(mi355rt_handle* h, const float* sum_rgb, const float* sumsq_rgb, const uint32_t* n, const float* direct_rgb, size_t npix);
+int mi355rt_film_add(mi355rt_handle* h, const float* sum_rgb, const float* sumsq_rgb, const uint32_t* n, const float* direct_rgb, size_t npix);
+int mi355rt_film_save(mi355rt_handle* h, const char* path);
+int mi355rt_film_load(mi355rt_handle* h, const char* path, int add);
+int mi355rt_film_file_info(const char* path, uint32_t out[8]);
 
 /* Camera, camera.rs:63-78 (the `pub camera` field of RayTracer, mod.rs:38). */
 int mi355rt_camera_move_rel(mi355rt_handle* h, float x, float y, float z);

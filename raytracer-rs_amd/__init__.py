@@ -143,6 +143,11 @@ ABI = [
     ("mi355rt_owned_row_list", C.c_int, [_H, _U, C.c_size_t]),
     ("mi355rt_film_get", C.c_int, [_H, _F, _F, _U]),
     ("mi355rt_film_clear", C.c_int, [_H]),
+    ("mi355rt_film_set", C.c_int, [_H, _F, _F, _U, _F, C.c_size_t]),
+    ("mi355rt_film_add", C.c_int, [_H, _F, _F, _U, _F, C.c_size_t]),
+    ("mi355rt_film_save", C.c_int, [_H, C.c_char_p]),
+    ("mi355rt_film_load", C.c_int, [_H, C.c_char_p, C.c_int]),
+    ("mi355rt_film_file_info", C.c_int, [C.c_char_p, _U]),
     ("mi355rt_film_get_pixels", C.c_int, [_H, _F]),
     ("mi355rt_film_get_estimated_variances", C.c_int, [_H, _F]),
     ("mi355rt_camera_move_rel", C.c_int, [_H, C.c_float, C.c_float, C.c_float]),
@@ -298,6 +303,30 @@ class Film:
         d = np.zeros((self._rt.width * self._rt.height, 3), np.float32)
         self._rt._check(lib().mi355rt_film_get_direct(self._rt._h, _fp(d)))
         return d
+
+    def _put(self, fn, sum, sumsq, n, direct):
+        s = np.ascontiguousarray(sum, np.float32); q = np.ascontiguousarray(sumsq, np.float32); c = np.ascontiguousarray(n, np.uint32)
+        d = None if direct is None else np.ascontiguousarray(direct, np.float32)
+        if s.size != 3 * c.size or q.size != 3 * c.size or (d is not None and d.size != 3 * c.size):
+            raise ValueError("film planes: sum, sumsq and direct hold 3 floats per entry of n")
+        self._rt._check(fn(self._rt._h, _fp(s), _fp(q), _up(c), None if d is None else _fp(d), c.size))
+
+    def set(self, sum, sumsq, n, direct=None):
+        """mi355rt_film_set: the film becomes these planes (the layout of pixel_datas() / direct_sums()), bits unchanged, on the rows the handle
+        owns.  direct: required exactly when the handle was created with FLAG_DIRECT_FILM."""
+        self._put(lib().mi355rt_film_set, sum, sumsq, n, direct)
+
+    def add(self, sum, sumsq, n, direct=None):
+        """mi355rt_film_add: film = film + planes, one f32 addition per value (u32 for n), on the rows the handle owns"""
+        self._put(lib().mi355rt_film_add, sum, sumsq, n, direct)
+
+    def save(self, path):
+        """mi355rt_film_save: the film as a film file (include/mi355rt.h; raytracer_rs_amd.film_io reads and writes the same format)"""
+        self._rt._check(lib().mi355rt_film_save(self._rt._h, os.fsencode(path)))
+
+    def load(self, path, add=False):
+        """mi355rt_film_load: set (or, add=True, add) the planes of a film file; the file is checked whole before the film is touched"""
+        self._rt._check(lib().mi355rt_film_load(self._rt._h, os.fsencode(path), 1 if add else 0))
 
     def get_pixels(self):
         out = np.zeros((self._rt.width * self._rt.height, 3), np.float32)
@@ -617,6 +646,15 @@ def create_raytracer_from_arrays(scene, triangles_per_leaf, width, height, **cfg
     h = C.c_void_p()
     code = lib().mi355rt_create(C.byref(sd), C.byref(cfg), C.byref(h))
     return _finish(code, h, keep)
+
+
+def film_file_info(path):
+    """mi355rt_film_file_info (host code, no device): dict(version, width, height, planes, seed, flags) of a film file; raises RuntimeError
+    with the library's reason for a malformed file"""
+    out = (C.c_uint32 * 8)()
+    if lib().mi355rt_film_file_info(os.fsencode(path), out) != 0:
+        raise RuntimeError((lib().mi355rt_last_error(None) or b"").decode() or "mi355rt_film_file_info failed")
+    return dict(version=int(out[0]), width=int(out[1]), height=int(out[2]), planes=int(out[3]), seed=int(out[4]) | int(out[5]) << 32, flags=int(out[6]))
 
 
 def debug_light_map(tri_verts, light, pad, res):

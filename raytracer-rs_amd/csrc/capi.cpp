@@ -1,8 +1,10 @@
 // capi.cpp — the extern "C" surface declared in include/mi355rt.h.
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <memory>
 #include <string>
+#include <vector>
 #include "lightmap.hpp"
 #include "../../include/mi355rt.h"
 #include "group.hpp"
@@ -77,6 +79,59 @@ bool denoise_config_ok(mi355rt_handle* h, const mi355rt_denoise_config* c)
     if (!e) return true;
     h->r->last_error = e;
     return false;
+}
+// the checks of mi355rt_film_set / mi355rt_film_add (include/mi355rt.h); on failure the handle's last_error names the argument
+bool film_put_args_ok(mi355rt_handle* h, const char* fn, const float* sum, const float* sumsq, const uint32_t* n, const float* direct, size_t npix)
+{
+    if (!h) return false;
+    const char* e = nullptr;
+    if (npix != (size_t)h->r->cfg.width * h->r->cfg.height) e = "npix must equal width * height";
+    else if (!sum) e = "sum_rgb is NULL";
+    else if (!sumsq) e = "sumsq_rgb is NULL";
+    else if (!n) e = "n is NULL";
+    else if (direct && !h->r->has_direct_film()) e = "direct_rgb given, but the handle was not created with MI355RT_FLAG_DIRECT_FILM";
+    else if (!direct && h->r->has_direct_film()) e = "direct_rgb is NULL, but the handle was created with MI355RT_FLAG_DIRECT_FILM";
+    if (!e) return true;
+    h->r->last_error = std::string(fn) + ": " + e;
+    return false;
+}
+
+// ---- film files (include/mi355rt.h, "FILM FILE"): a 64-byte little-endian header, then the planes n, sum, sumsq [, direct]
+constexpr size_t kFilmHeaderBytes = 64;
+constexpr char kFilmMagic[9] = "MI355FLM";
+struct FilmFileHeader { uint32_t version, width, height, planes; uint64_t seed; uint32_t flags; };
+uint32_t get_le32(const unsigned char* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+void put_le32(unsigned char* p, uint32_t v) { p[0] = (unsigned char)v; p[1] = (unsigned char)(v >> 8); p[2] = (unsigned char)(v >> 16); p[3] = (unsigned char)(v >> 24); }
+uint64_t film_plane_bytes(const FilmFileHeader& f) { return (uint64_t)f.width * f.height * ((f.planes & 1u) ? 40u : 28u); }
+
+// Reads and checks the header and the file's length; with `planes` also the planes (file order).  False: err names the reason.
+bool read_film_file(const char* path, FilmFileHeader& f, std::vector<unsigned char>* planes, std::string& err)
+{
+    const std::string where = std::string("film file ") + path + ": ";
+    FILE* fp = std::fopen(path, "rb");
+    if (!fp) { err = where + "cannot open"; return false; }
+    unsigned char hd[kFilmHeaderBytes];
+    bool ok = false;
+    do {
+        if (std::fread(hd, 1, kFilmHeaderBytes, fp) != kFilmHeaderBytes) { err = where + "wrong file length: shorter than the 64-byte header"; break; }
+        if (std::memcmp(hd, kFilmMagic, 8) != 0) { err = where + "bad magic (not a film file)"; break; }
+        f.version = get_le32(hd + 8); f.width = get_le32(hd + 12); f.height = get_le32(hd + 16); f.planes = get_le32(hd + 20);
+        f.seed = (uint64_t)get_le32(hd + 24) | (uint64_t)get_le32(hd + 28) << 32; f.flags = get_le32(hd + 32);
+        if (f.version != 1u) { err = where + "unsupported version " + std::to_string(f.version); break; }
+        if (f.planes & ~1u) { err = where + "unknown bits in the planes field"; break; }
+        if (f.width == 0 || f.height == 0) { err = where + "width and height must be non-zero"; break; }
+        if (std::fseek(fp, 0, SEEK_END) != 0) { err = where + "cannot seek"; break; }
+        const long long len = (long long)std::ftell(fp);
+        const uint64_t want = kFilmHeaderBytes + film_plane_bytes(f);
+        if (len < 0 || (uint64_t)len != want) { err = where + "wrong file length: " + std::to_string(len) + " bytes, the header asks for " + std::to_string(want); break; }
+        if (planes) {
+            planes->resize((size_t)film_plane_bytes(f));
+            if (std::fseek(fp, (long)kFilmHeaderBytes, SEEK_SET) != 0 || std::fread(planes->data(), 1, planes->size(), fp) != planes->size()) { err = where + "read error"; break; }
+        }
+        ok = true;
+    } while (false);
+    std::fclose(fp);
+    return ok;
 }
 }  // namespace
 
@@ -289,6 +344,78 @@ int mi355rt_film_clear(mi355rt_handle* h)
 {
     if (!h) return MI355RT_E_INVALID;
     return h->g->film_clear() ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_film_set(mi355rt_handle* h, const float* sum_rgb, const float* sumsq_rgb, const uint32_t* n, const float* direct_rgb, size_t npix)
+{
+    if (!film_put_args_ok(h, "mi355rt_film_set", sum_rgb, sumsq_rgb, n, direct_rgb, npix)) return MI355RT_E_INVALID;
+    return h->g->film_put({ sum_rgb, sumsq_rgb, n, direct_rgb }, false) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_film_add(mi355rt_handle* h, const float* sum_rgb, const float* sumsq_rgb, const uint32_t* n, const float* direct_rgb, size_t npix)
+{
+    if (!film_put_args_ok(h, "mi355rt_film_add", sum_rgb, sumsq_rgb, n, direct_rgb, npix)) return MI355RT_E_INVALID;
+    return h->g->film_put({ sum_rgb, sumsq_rgb, n, direct_rgb }, true) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_film_save(mi355rt_handle* h, const char* path)
+{
+    if (!h) return MI355RT_E_INVALID;
+    if (!path) { h->r->last_error = "mi355rt_film_save: path is NULL"; return MI355RT_E_INVALID; }
+    const bool direct = h->r->has_direct_film();
+    const size_t npix = (size_t)h->r->cfg.width * h->r->cfg.height;
+    std::vector<uint32_t> n(npix);
+    std::vector<float> sum(npix * 3), sumsq(npix * 3), dsum(direct ? npix * 3 : 0);
+    if (!h->g->film_get(sum.data(), sumsq.data(), n.data()) || (direct && !h->g->film_get_direct(dsum.data()))) return MI355RT_E_HIP;
+    unsigned char hd[kFilmHeaderBytes] = { 0 };
+    std::memcpy(hd, kFilmMagic, 8);
+    put_le32(hd + 8, 1u); put_le32(hd + 12, h->r->cfg.width); put_le32(hd + 16, h->r->cfg.height); put_le32(hd + 20, direct ? 1u : 0u);
+    put_le32(hd + 24, (uint32_t)h->r->cfg.seed); put_le32(hd + 28, (uint32_t)(h->r->cfg.seed >> 32)); put_le32(hd + 32, h->r->cfg.flags);
+    FILE* fp = std::fopen(path, "wb");
+    bool ok = fp != nullptr;
+    ok = ok && std::fwrite(hd, 1, kFilmHeaderBytes, fp) == kFilmHeaderBytes && std::fwrite(n.data(), 4, npix, fp) == npix
+         && std::fwrite(sum.data(), 4, npix * 3, fp) == npix * 3 && std::fwrite(sumsq.data(), 4, npix * 3, fp) == npix * 3
+         && (!direct || std::fwrite(dsum.data(), 4, npix * 3, fp) == npix * 3);
+    if (fp && std::fclose(fp) != 0) ok = false;
+    if (!ok) { h->r->last_error = std::string("mi355rt_film_save: cannot write ") + path; return MI355RT_E_LOAD; }
+    return MI355RT_OK;
+}
+
+int mi355rt_film_load(mi355rt_handle* h, const char* path, int add)
+{
+    if (!h) return MI355RT_E_INVALID;
+    if (!path) { h->r->last_error = "mi355rt_film_load: path is NULL"; return MI355RT_E_INVALID; }
+    FilmFileHeader f{};
+    std::vector<unsigned char> planes;
+    std::string err;
+    const mi355rt_config& c = h->r->cfg;
+    if (read_film_file(path, f, &planes, err)) {
+        const std::string where = std::string("film file ") + path + ": ";
+        if (f.width != c.width || f.height != c.height)
+            err = where + "it is " + std::to_string(f.width) + " x " + std::to_string(f.height) + ", the handle " + std::to_string(c.width) + " x " + std::to_string(c.height) + " (width / height differ)";
+        else if ((f.flags ^ c.flags) & MI355RT_FLAG_FIX_ROW_INDEX) err = where + "its MI355RT_FLAG_FIX_ROW_INDEX bit differs from the handle's: the pixel -> ray mapping differs";
+        else if (h->r->has_direct_film() && !(f.planes & 1u)) err = where + "it has no direct plane, the handle was created with MI355RT_FLAG_DIRECT_FILM";
+    }
+    if (!err.empty()) { h->r->last_error = "mi355rt_film_load: " + err; return MI355RT_E_LOAD; }
+    static_assert(sizeof(float) == 4 && sizeof(uint32_t) == 4, "plane layout");
+    const size_t npix = (size_t)c.width * c.height;
+    // the planes in file order; a little-endian host reads them in place (planes.data() is aligned for any fundamental type)
+    const uint32_t* n = reinterpret_cast<const uint32_t*>(planes.data());
+    const float* sum = reinterpret_cast<const float*>(planes.data() + npix * 4);
+    const float* sumsq = sum + npix * 3;
+    const float* direct = h->r->has_direct_film() ? sumsq + npix * 3 : nullptr;        // a direct plane the handle has no use for is skipped
+    return h->g->film_put({ sum, sumsq, n, direct }, add != 0) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_film_file_info(const char* path, uint32_t out[8])
+{
+    if (!path || !out) return bad("mi355rt_film_file_info: null argument");
+    FilmFileHeader f{};
+    std::string err;
+    if (!read_film_file(path, f, nullptr, err)) { g_create_error = "mi355rt_film_file_info: " + err; return MI355RT_E_LOAD; }
+    out[0] = f.version; out[1] = f.width; out[2] = f.height; out[3] = f.planes;
+    out[4] = (uint32_t)f.seed; out[5] = (uint32_t)(f.seed >> 32); out[6] = f.flags; out[7] = 0u;
+    return MI355RT_OK;
 }
 
 int mi355rt_film_get_pixels(mi355rt_handle* h, float* rgb)

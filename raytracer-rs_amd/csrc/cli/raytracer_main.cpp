@@ -8,7 +8,9 @@
 // --adaptive REL (mi355rt_render_adaptive with rel_error REL) with --abs-floor F, --min-spp N, --max-spp N, --batch N (defaults:
 // mi355rt_adaptive_default_config), and --denoise: --out receives the denoised read-out of the film (mi355rt_get_denoised_pixels,
 // mi355rt_denoise_default_config) instead of get_tonemapped_pixels; --denoise-split: the handle keeps a direct film (MI355RT_FLAG_DIRECT_FILM)
-// and --out receives the split read-out (mi355rt_get_denoised_pixels_split), which filters the indirect part only.
+// and --out receives the split read-out (mi355rt_get_denoised_pixels_split), which filters the indirect part only.  Film files (mi355rt_film_load /
+// mi355rt_film_save): --load-film PATH (repeatable) adds each file to the fresh zero film before any rendering, --save-film PATH writes the film
+// after rendering and before the read-out; with --load-film and -i 0 nothing is rendered and the loaded film is read out once (a merge-only run).
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -67,7 +69,8 @@ int main(int argc, char** argv)
     size_t max_triangles = raytracer_lib::DEFAULT_TRIANGLES_PER_LEAF, width = DEFAULT_WIDTH, height = DEFAULT_HEIGHT;
     size_t frame_iterations = 0, spp = 0, seed = 1, gpus = 1;
     bool have_iterations = false, fix_row = false, share_device = false, device_lbvh = false;
-    std::string out;
+    std::string out, save_film;
+    std::vector<std::string> load_films;
     bool adaptive = false, denoise = false, denoise_split = false;
     mi355rt_adaptive_config acfg;
     mi355rt_adaptive_default_config(&acfg);
@@ -86,6 +89,8 @@ int main(int argc, char** argv)
         else if (a == "--gpus") { size_t t; if (parse_usize(take(), t) && t >= 1) gpus = t; }
         else if (a == "--share-device") share_device = true;
         else if (a == "--out") { if (v) out = take(); }
+        else if (a == "--load-film") { if (v) load_films.push_back(take()); }
+        else if (a == "--save-film") { if (v) save_film = take(); }
         else if (a == "--fix-row-index") fix_row = true;
         else if (a == "--device-lbvh") device_lbvh = true;
         else if (a == "--denoise") denoise = true;
@@ -98,7 +103,8 @@ int main(int argc, char** argv)
         else if (a == "-h" || a == "--help") {
             std::printf("raytracer-rs (MI355X) 0.1.0\nusage: raytracer [-f COLLADA_FILENAME] [-m MAX_TRIS] [-i FRAME_ITERATIONS] [--width W] [--height H]\n"
                         "                 [--spp N] [--seed S] [--gpus N] [--out image.ppm|image.png] [--fix-row-index] [--device-lbvh]\n"
-                        "                 [--adaptive REL [--abs-floor F] [--min-spp N] [--max-spp N] [--batch N]] [--denoise | --denoise-split]\n");
+                        "                 [--adaptive REL [--abs-floor F] [--min-spp N] [--max-spp N] [--batch N]] [--denoise | --denoise-split]\n"
+                        "                 [--load-film film.bin]... [--save-film film.bin]\n");
             return 0;
         }
     }
@@ -117,6 +123,7 @@ int main(int argc, char** argv)
         if (gpus > 1) std::printf("rendering on %zu GPUs (rows dealt in stripes of %u)\n", gpus, cfg.stripe_rows);
         raytracer_lib::RayTracer rt = raytracer_lib::create_raytracer_from_file(file, max_triangles, width, height, &cfg);
         std::printf("number of triangles: %u\n", mi355rt_triangle_count(rt.handle()));   // colladaloader.rs:265
+        for (const std::string& f : load_films) rt.film.load(f, true);     // the fresh film is zero: the first file is added to it like the others
         raytracer_lib::stats::Stats stats;
         std::vector<uint32_t> ldr;
         for (size_t it = 0; it < frame_iterations; ++it) {
@@ -141,6 +148,8 @@ int main(int argc, char** argv)
             std::printf("%s\n", stats.stats(num_primary_rays).c_str());  // main.rs:213
         }
         std::printf("%s\n\n\n", stats.mean_stats().c_str());             // main.rs:216
+        if (!save_film.empty()) rt.film.save(save_film);
+        if (frame_iterations == 0 && !load_films.empty()) ldr = rt.get_tonemapped_pixels();       // a merge-only run: the loaded film, read out once
         if (denoise || denoise_split) {                                   // the denoised read-out of the film the loop left (default config)
             mi355rt_denoise_config dcfg;
             mi355rt_denoise_default_config(&dcfg);

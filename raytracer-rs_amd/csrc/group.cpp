@@ -171,6 +171,12 @@ bool DeviceGroup::film_clear()
     for (size_t i = 0; i < devs_.size(); ++i) if (!devs_[i]->film_clear()) return fail_from(i);
     return true;
 }
+bool DeviceGroup::film_put(const Renderer::FilmPlanes& in, bool add)
+{
+    error_.clear();
+    for (size_t i = 0; i < devs_.size(); ++i) if (!devs_[i]->film_put(in, add)) return fail_from(i);
+    return true;
+}
 void DeviceGroup::camera_move_rel(float x, float y, float z) { for (auto& d : devs_) d->camera.move_rel(x, y, z); }
 void DeviceGroup::camera_add_x_angle(float r) { for (auto& d : devs_) d->camera.add_x_angle(r); }
 void DeviceGroup::camera_add_y_angle(float r) { for (auto& d : devs_) d->camera.add_y_angle(r); }

@@ -28,6 +28,7 @@ public:
     bool film_get_direct(float* sum);
     bool film_stat(bool variances, float* rgb);
     bool film_clear();
+    bool film_put(const Renderer::FilmPlanes& in, bool add);     // every member takes its own rows of the whole-image planes
     void camera_move_rel(float x, float y, float z);
     void camera_add_x_angle(float r);
     void camera_add_y_angle(float r);

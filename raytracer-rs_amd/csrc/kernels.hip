@@ -1846,6 +1846,49 @@ hipError_t launch_film_clear_rows(hipStream_t stream, const uint32_t* rows, uint
     return hipGetLastError();
 }
 
+// ---- mi355rt_film_set / mi355rt_film_add: staged input planes -> the film, on the rows the handle owns ----
+// One thread per f32 of a three-channel plane (i < 3 * npix): every access is one dword at consecutive addresses across the wave.  The threads
+// i < npix also serve the sample counts.  ADD: film = film + in, one f32 addition with the film's value on the left (u32 addition for n);
+// otherwise the input's bits are stored as they are (a NaN's payload too), so the planes travel as u32 there.
+template <bool ADD, bool DIRECT>
+__global__ __launch_bounds__(256) void film_merge_kernel(const float* __restrict__ in_sum, const float* __restrict__ in_sumsq, const uint32_t* __restrict__ in_n,
+                                                         const float* __restrict__ in_direct, uint32_t npix, uint32_t width,
+                                                         uint32_t stripe_rows, uint32_t stripe_world, uint32_t stripe_rank,
+                                                         float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;               // 3 * npix < 2^32: Renderer::init caps npix at 2^29
+    if (i >= 3u * npix) return;
+    auto owned = [&](uint32_t pixel) { return ((pixel / width) / stripe_rows) % stripe_world == stripe_rank; };
+    if (owned(i / 3u)) {
+        if constexpr (ADD) {
+            film_sum[i] = film_sum[i] + in_sum[i];
+            film_sumsq[i] = film_sumsq[i] + in_sumsq[i];
+            if constexpr (DIRECT) film_direct[i] = film_direct[i] + in_direct[i];
+        } else {
+            reinterpret_cast<uint32_t*>(film_sum)[i] = reinterpret_cast<const uint32_t*>(in_sum)[i];
+            reinterpret_cast<uint32_t*>(film_sumsq)[i] = reinterpret_cast<const uint32_t*>(in_sumsq)[i];
+            if constexpr (DIRECT) reinterpret_cast<uint32_t*>(film_direct)[i] = reinterpret_cast<const uint32_t*>(in_direct)[i];
+        }
+    }
+    if (i < npix && owned(i)) film_n[i] = ADD ? film_n[i] + in_n[i] : in_n[i];
+}
+
+// in_direct / film_direct null (both or neither): a film of three planes; stripe_world <= 1: every row
+hipError_t launch_film_merge(hipStream_t stream, bool add, const float* in_sum, const float* in_sumsq, const uint32_t* in_n, const float* in_direct,
+                             uint32_t npix, uint32_t width, uint32_t stripe_rows, uint32_t stripe_world, uint32_t stripe_rank,
+                             float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct)
+{
+    if (npix == 0) return hipSuccess;
+    if ((film_direct == nullptr) != (in_direct == nullptr) || width == 0 || stripe_rows == 0 || (uint64_t)npix * 3 > 0xFFFFFF00ull) return hipErrorInvalidValue;
+    if (stripe_world <= 1) { stripe_world = 1; stripe_rank = 0; }
+    const dim3 grid((3u * npix + 255u) / 256u);
+#define MI355RT_MERGE_ARGS grid, dim3(256), 0, stream, in_sum, in_sumsq, in_n, in_direct, npix, width, stripe_rows, stripe_world, stripe_rank, film_sum, film_sumsq, film_n, film_direct
+    if (add) { if (film_direct) hipLaunchKernelGGL((film_merge_kernel<true, true>), MI355RT_MERGE_ARGS); else hipLaunchKernelGGL((film_merge_kernel<true, false>), MI355RT_MERGE_ARGS); }
+    else { if (film_direct) hipLaunchKernelGGL((film_merge_kernel<false, true>), MI355RT_MERGE_ARGS); else hipLaunchKernelGGL((film_merge_kernel<false, false>), MI355RT_MERGE_ARGS); }
+#undef MI355RT_MERGE_ARGS
+    return hipGetLastError();
+}
+
 // ---- multi-GPU gather, last step on the root: packed stripes of every rank -> the full frame -----------------
 // gathered = world slots of slot_rows * width u32; slot r holds rank r's owned rows in ascending order (rows are dealt
 // in stripes of stripe_rows, stripe s to rank s % world: Renderer::init).  One thread per pixel of the frame.

@@ -42,6 +42,11 @@ hipError_t launch_film_clear_rows(hipStream_t stream, const uint32_t* rows, uint
 hipError_t launch_film_rows_copy(hipStream_t stream, const uint32_t* rows, uint32_t first, uint32_t total, uint32_t nown, uint32_t width,
                                  float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct,
                                  float* bk_sum, float* bk_sumsq, uint32_t* bk_n, float* bk_direct, bool restore);
+// mi355rt_film_set / mi355rt_film_add: the staged planes (device memory; in_sum / in_sumsq / in_direct npix * 3 floats, in_n npix) stored
+// (add == false: bits unchanged) or added (film + in) into the rows with (row / stripe_rows) % stripe_world == stripe_rank; the other rows are not written
+hipError_t launch_film_merge(hipStream_t stream, bool add, const float* in_sum, const float* in_sumsq, const uint32_t* in_n, const float* in_direct,
+                             uint32_t npix, uint32_t width, uint32_t stripe_rows, uint32_t stripe_world, uint32_t stripe_rank,
+                             float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct);
 hipError_t launch_slab(hipStream_t stream, const float* inv_rays6, const float* cubes6, uint32_t n, uint8_t* hit, float* tmin);
 // adaptive sampling: out[tile] = the tile is active; *count (zeroed by the caller) += (owned pixels << 32) | 1 per active tile
 hipError_t launch_adaptive_tiles(hipStream_t stream, const AdaptiveArgs& a, const float* film_sum, const float* film_sumsq, const uint32_t* film_n,

@@ -48,6 +48,24 @@ public:
         if (mi355rt_film_get_direct(h_, out.data()) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
         return out;
     }
+    // film set, add, save and load (include/mi355rt.h).  The planes are whole images in the layout of mi355rt_film_get; direct is
+    // non-null exactly for a handle created with MI355RT_FLAG_DIRECT_FILM; only the rows the handle owns are written.
+    void set(const float* sum_rgb, const float* sumsq_rgb, const uint32_t* n, const float* direct_rgb = nullptr)
+    {
+        if (mi355rt_film_set(h_, sum_rgb, sumsq_rgb, n, direct_rgb, (size_t)mi355rt_width(h_) * mi355rt_height(h_)) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+    }
+    void add(const float* sum_rgb, const float* sumsq_rgb, const uint32_t* n, const float* direct_rgb = nullptr)
+    {
+        if (mi355rt_film_add(h_, sum_rgb, sumsq_rgb, n, direct_rgb, (size_t)mi355rt_width(h_) * mi355rt_height(h_)) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+    }
+    void save(const std::string& path) const
+    {
+        if (mi355rt_film_save(h_, path.c_str()) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+    }
+    void load(const std::string& path, bool add = false)
+    {
+        if (mi355rt_film_load(h_, path.c_str(), add ? 1 : 0) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+    }
 private:
     friend class RayTracer;
     mi355rt_handle* h_ = nullptr;
@@ -140,6 +158,13 @@ inline RayTracer create_raytracer_from_file(const std::string& collada_filename,
                         : mi355rt_create_from_collada_file(collada_filename.c_str(), &cfg, &h);
     if (rc != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(nullptr));
     return RayTracer(h);
+}
+// header of a film file, checked without a device (mi355rt_film_file_info): version, width, height, planes, seed low, seed high, flags, 0
+inline std::vector<uint32_t> film_file_info(const std::string& path)
+{
+    std::vector<uint32_t> out(8);
+    if (mi355rt_film_file_info(path.c_str(), out.data()) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(nullptr));
+    return out;
 }
 
 namespace stats {

@@ -1382,6 +1382,33 @@ bool Renderer::film_clear()
     return true;            // stream-ordered: every later call on this handle starts on the same stream
 }
 
+// mi355rt_film_set / mi355rt_film_add: the caller's planes are staged in one temporary device buffer (n, sum, sumsq, direct: the order of a film
+// file), the merge kernel stores or adds them on the rows this handle owns, and the staging is freed again.  Everything runs on stream_: behind a
+// queued frame (render_async joins its slices there) and behind the rows a speculative frame gives back, ahead of every later call.  Nothing but
+// the film and the tone-map cache's dirty rows changes.
+bool Renderer::film_put(const FilmPlanes& in, bool add)
+{
+    if (!bind()) return false;
+    if (!in.sum || !in.sumsq || !in.n || (in.direct != nullptr) != (bool)d_film_direct_) { last_error = "internal: film_put planes do not match the film"; return false; }
+    if (!settle_speculation()) return false;
+    const size_t npix = (size_t)cfg.width * cfg.height;
+    DeviceBuffer<uint8_t> stage;
+    HIP_TRY(stage.alloc(npix * (in.direct ? 40 : 28), &hbm_bytes_));
+    uint32_t* s_n = reinterpret_cast<uint32_t*>(stage.get());
+    float* s_sum = reinterpret_cast<float*>(stage.get() + npix * 4);
+    float* s_sumsq = s_sum + npix * 3;
+    float* s_direct = in.direct ? s_sumsq + npix * 3 : nullptr;
+    HIP_TRY(hipMemcpyAsync(s_n, in.n, npix * 4, hipMemcpyHostToDevice, stream_));
+    HIP_TRY(hipMemcpyAsync(s_sum, in.sum, npix * 12, hipMemcpyHostToDevice, stream_));
+    HIP_TRY(hipMemcpyAsync(s_sumsq, in.sumsq, npix * 12, hipMemcpyHostToDevice, stream_));
+    if (in.direct) HIP_TRY(hipMemcpyAsync(s_direct, in.direct, npix * 12, hipMemcpyHostToDevice, stream_));
+    HIP_TRY(launch_film_merge(stream_, add, s_sum, s_sumsq, s_n, s_direct, (uint32_t)npix, cfg.width, cfg.stripe_rows, cfg.stripe_world, cfg.stripe_rank,
+                              d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_film_direct_.get()));
+    std::fill(ldr_dirty_.begin(), ldr_dirty_.end(), (uint8_t)1);
+    HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's arrays and the staging are free again
+    return true;
+}
+
 bool Renderer::intersect(const float* rays6, size_t n, float* tuv, uint32_t* prim, uint8_t* blocked)
 {
     if (!bind()) return false;

@@ -35,6 +35,9 @@ public:
     bool set_seed(uint64_t seed);
     bool set_flags(uint32_t flags);
     bool film_clear();                                                  // film.rs:37-41
+    // mi355rt_film_set / mi355rt_film_add: whole-image host planes -> the owned rows of the film; the caller has checked the arguments
+    struct FilmPlanes { const float* sum; const float* sumsq; const uint32_t* n; const float* direct; };
+    bool film_put(const FilmPlanes& in, bool add);
     bool intersect(const float* rays6, size_t n, float* tuv, uint32_t* prim, uint8_t* blocked);
     bool synchronize();                                                 // wait for everything queued on this handle
     // ---- multi-GPU gather of the packed u32 stripes into the root's frame.  Two transports end in the

@@ -50,6 +50,12 @@ extern "C" {
     fn mi355rt_get_tonemapped_pixels(h: *mut mi355rt_handle, out: *mut u32, n: usize) -> c_int;
     fn mi355rt_film_clear(h: *mut mi355rt_handle) -> c_int;
     fn mi355rt_film_get_direct(h: *mut mi355rt_handle, sum_rgb: *mut f32) -> c_int;
+    // film set / add / save / load (declared for a caller that checkpoints or merges renders; this shim calls none of them)
+    fn mi355rt_film_set(h: *mut mi355rt_handle, sum_rgb: *const f32, sumsq_rgb: *const f32, n: *const u32, direct_rgb: *const f32, npix: usize) -> c_int;
+    fn mi355rt_film_add(h: *mut mi355rt_handle, sum_rgb: *const f32, sumsq_rgb: *const f32, n: *const u32, direct_rgb: *const f32, npix: usize) -> c_int;
+    fn mi355rt_film_save(h: *mut mi355rt_handle, path: *const c_char) -> c_int;
+    fn mi355rt_film_load(h: *mut mi355rt_handle, path: *const c_char, add: c_int) -> c_int;
+    fn mi355rt_film_file_info(path: *const c_char, out: *mut u32) -> c_int;
     fn mi355rt_get_denoised_pixels_split(h: *mut mi355rt_handle, cfg: *const mi355rt_denoise_config, rgb: *mut f32, packed: *mut u32, npix: usize) -> c_int;
     fn mi355rt_camera_move_rel(h: *mut mi355rt_handle, x: f32, y: f32, z: f32) -> c_int;
     fn mi355rt_camera_add_x_angle(h: *mut mi355rt_handle, radians: f32) -> c_int;
