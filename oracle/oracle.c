@@ -841,6 +841,14 @@ void oracle_film_get(const oracle_t* o, float* sum3, float* sumsq3, uint32_t* n)
     if (sumsq3) memcpy(sumsq3, o->sumsq, npix * sizeof(rgb_t));
     if (n) memcpy(n, o->nsamp, npix * sizeof(uint32_t));
 }
+/* the counterpart of oracle_film_get: the film becomes these planes, bits unchanged (the values are data: any n, any float) */
+void oracle_film_set(oracle_t* o, const float* sum3, const float* sumsq3, const uint32_t* n)
+{
+    size_t npix = (size_t)o->width * o->height;
+    memcpy(o->sum, sum3, npix * sizeof(rgb_t));
+    memcpy(o->sumsq, sumsq3, npix * sizeof(rgb_t));
+    memcpy(o->nsamp, n, npix * sizeof(uint32_t));
+}
 void oracle_get_pixels(const oracle_t* o, float* rgb3)                       /* film.rs:43-47 */
 {
     size_t npix = (size_t)o->width * o->height;

@@ -42,6 +42,7 @@ def lib():
         L.oracle_intersect_mt.argtypes = [C.c_void_p, _F, C.c_uint32, C.c_int, _F, _U, C.c_uint32]
         L.oracle_film_clear.argtypes = [C.c_void_p]
         L.oracle_film_get.argtypes = [C.c_void_p, _F, _F, _U]
+        L.oracle_film_set.argtypes = [C.c_void_p, _F, _F, _U]
         L.oracle_get_pixels.argtypes = [C.c_void_p, _F]
         L.oracle_get_estimated_variances.argtypes = [C.c_void_p, _F]
         L.oracle_get_tonemapped.argtypes = [C.c_void_p, _U]
@@ -153,6 +154,14 @@ class Oracle:
         s = np.zeros((n, 3), np.float32); q = np.zeros((n, 3), np.float32); c = np.zeros(n, np.uint32)
         lib().oracle_film_get(self._h, _fp(s), _fp(q), _up(c))
         return s, q, c
+
+    def film_set(self, s, q, n):
+        """the film becomes these planes (the layout of film()), bits unchanged"""
+        npix = self.width * self.height
+        s = np.ascontiguousarray(s, np.float32); q = np.ascontiguousarray(q, np.float32); n = np.ascontiguousarray(n, np.uint32)
+        if s.size != 3 * npix or q.size != 3 * npix or n.size != npix:
+            raise ValueError("film_set: the planes of a %d x %d film hold %d counts and %d floats each" % (self.width, self.height, npix, 3 * npix))
+        lib().oracle_film_set(self._h, _fp(s), _fp(q), _up(n))
 
     def get_pixels(self):
         out = np.zeros((self.width * self.height, 3), np.float32); lib().oracle_get_pixels(self._h, _fp(out)); return out
