@@ -308,6 +308,87 @@ int mi355rt_get_denoised_pixels_split(mi355rt_handle* h, const mi355rt_denoise_c
 /* the guide buffers above, width*height entries each (normal3, albedo3: 3 floats per pixel); any pointer may be NULL */
 int mi355rt_get_guides(mi355rt_handle* h, float* depth, float* normal3, float* albedo3, uint32_t* prim, size_t npix);
 
+/* ---- display read-out: exposure, tone curves, sRGB, auto-exposure (no reference counterpart).  mi355rt_get_tonemapped_pixels is the
+ * reference's c / (1 + c) truncated to 8 bits: linear values that every viewer reads as sRGB, no exposure.  This read-out maps any of the three images
+ * the handle can produce through an exposure, one of four tone curves and one of two transfers.  It only reads, under the denoiser's rules: a queued
+ * mi355rt_render_async and a speculative 50-row frame are settled first; the film, the counters, mi355rt_current_row and the changed-row tracking of
+ * mi355rt_get_tonemapped_pixels stay as they are.  Device groups (config.device_count > 1) and striped handles (stripe_world > 1) are not supported, for
+ * every source: MI355RT_E_INVALID (add the stripes into one handle first: RECIPES below).
+ *
+ * SOURCE IMAGE.  c[p] is, per pixel, exactly the three floats the named read-out returns as `rgb`; an empty pixel therefore carries its film mean as it
+ * stands.  n[p] is the film count.  `dn` is ignored for SOURCE_FILM; for the other two NULL means mi355rt_denoise_default_config.  One call runs the
+ * denoiser at most once, also with auto_exposure.
+ *
+ * HISTOGRAM (mi355rt_display_histogram).  Per pixel: n == 0 counts in `empty`, whatever its sums.  Otherwise L = (0.2126f*c.r + 0.7152f*c.g) + 0.0722f*c.b,
+ * f32, unfused (the L of FILTER above); L NaN counts in `nan`; L <= 0 counts in `nonpositive`; otherwise, with bits(L) the float's bit pattern,
+ *     b = clamp((int)(bits(L) >> 20) - 856, 0, 255);  bins[b] += 1;  max_bits = max(max_bits, bits(L))   (unsigned)
+ * i.e. eight bins per octave, cut on the float's own exponent and top three mantissa bits, from 2^-20 to 2^12; everything below (denormals included) lands
+ * in bin 0, everything above (+inf included) in bin 255.  Every output is an integer that does not depend on the order of accumulation.
+ *
+ * AUTO-EXPOSURE (mi355rt_display_auto_exposure; HOST code, IEEE double).  N = sum of bins; lo = floor((double)low * N), hi = ceil((double)high * N).  Bin b
+ * holds the ranks [C_b, C_b + bins[b]) with C_b the running sum; kept_b = max(0, min(C_b + bins[b], hi) - max(C_b, lo)); K = sum of kept_b;
+ *     mean = (sum over b ascending of kept_b * centre_b) / K,   centre_b = (b + 856.5) / 8.0 - 127.0
+ *     *exposure = (float)((double)key * exp2(-mean));   K == 0: *exposure = 1.0f (and the call returns 0)
+ * key must be finite and > 0, and 0 <= low < high <= 1: otherwise MI355RT_E_INVALID, mi355rt_last_error(NULL) names the field and nothing is written.
+ *
+ * sRGB TABLE (mi355rt_display_srgb_thresholds; HOST code).  out[k - 1] = T[k] for k = 1..255: e = (k - 0.5) / 255, T[k] = (float)EOTF(e) in double,
+ * EOTF(e) = e / 12.92 for e <= 0.04045, else ((e + 0.055) / 1.055)^2.4.  Strictly increasing in f32 (smallest gap 3.0e-4).  The device reads this
+ * table; no powf runs there.
+ *
+ * DISPLAY MAPPING (mi355rt_get_display_pixels).  With the effective exposure E, per channel, f32, unfused, in this order:
+ *     x = c * E
+ *     CURVE_REINHARD        y = x / (1.0f + x)
+ *     CURVE_REINHARD_WHITE  y = (x * (1.0f + x / (white*white))) / (1.0f + x)
+ *     CURVE_ACES            y = (x * (2.51f*x + 0.03f)) / (x * (2.43f*x + 0.59f) + 0.14f)
+ *     CURVE_CLAMP           y = x
+ *     z = fmaxf(fminf(y, 1.0f), 0.0f)                      (a NaN becomes 1: white, as the reference has it)
+ *     TRANSFER_REFERENCE    u = (uint32_t)(z * 255.0f) & 0xFF
+ *     TRANSFER_SRGB         u = number of k in 1..255 with T[k] <= z
+ *     packed = B | G << 8 | R << 16 | 255 << 24
+ * E is config.exposure when auto_exposure == 0; otherwise the auto-exposure of the source's histogram with config.key / low / high.  *exposure_used
+ * (may be NULL) receives E either way.  With mi355rt_display_default_config the call returns exactly mi355rt_get_tonemapped_pixels; sources 1 and 2 with
+ * the other fields at their defaults return the `packed` of mi355rt_get_denoised_pixels / _split.
+ *
+ * ERRORS.  npix != width * height, an unknown source, curve or transfer, auto_exposure > 1, a bad float field (exposure is checked only when it is used,
+ * white, key, low and high always), a bad `dn`, a NULL output, SOURCE_DENOISED_SPLIT on a handle without MI355RT_FLAG_DIRECT_FILM (the message names the
+ * flag): MI355RT_E_INVALID, mi355rt_last_error names the field and nothing is written.
+ * Device memory, allocated on first use and counted in mi355rt_hbm_allocated_bytes: the histogram's 1040 bytes; with the first mi355rt_get_display_pixels
+ * also the table (1 KiB) and 4 bytes per pixel; for sources 1 and 2 the denoiser's buffers, shared with it. */
+#define MI355RT_DISPLAY_SOURCE_FILM            0u  /* the film means, mi355rt_film_get_pixels */
+#define MI355RT_DISPLAY_SOURCE_DENOISED        1u  /* rgb of mi355rt_get_denoised_pixels */
+#define MI355RT_DISPLAY_SOURCE_DENOISED_SPLIT  2u  /* rgb of mi355rt_get_denoised_pixels_split (needs MI355RT_FLAG_DIRECT_FILM) */
+#define MI355RT_CURVE_REINHARD        0u
+#define MI355RT_CURVE_REINHARD_WHITE  1u
+#define MI355RT_CURVE_ACES            2u
+#define MI355RT_CURVE_CLAMP           3u
+#define MI355RT_TRANSFER_REFERENCE    0u  /* (u8)(z * 255), truncating: what mi355rt_get_tonemapped_pixels does */
+#define MI355RT_TRANSFER_SRGB         1u
+#define MI355RT_HIST_BINS 256u
+
+typedef struct mi355rt_luminance_histogram {
+    uint32_t bins[MI355RT_HIST_BINS];
+    uint32_t empty;        /* pixels with film n == 0 */
+    uint32_t nan;          /* non-empty pixels whose L is NaN */
+    uint32_t nonpositive;  /* non-empty pixels with L <= 0 (includes -0.0 and -inf) */
+    uint32_t max_bits;     /* bit pattern of the largest L counted in bins[] (0 when none; +inf is 0x7F800000) */
+} mi355rt_luminance_histogram;
+
+typedef struct mi355rt_display_config {
+    uint32_t source, curve, transfer;
+    uint32_t auto_exposure;   /* 0: use `exposure`; 1: derive it from the source's histogram (key, low, high); `exposure` is ignored */
+    float exposure;           /* > 0, finite */
+    float white;              /* > 0, finite; read by CURVE_REINHARD_WHITE only, validated always */
+    float key, low, high;     /* key > 0 finite; 0 <= low < high <= 1 */
+} mi355rt_display_config;
+
+/* source FILM, CURVE_REINHARD, TRANSFER_REFERENCE, auto_exposure 0, exposure 1, white 4, key 0.18 (the usual middle grey), low 0, high 1 */
+void mi355rt_display_default_config(mi355rt_display_config* cfg);
+int mi355rt_display_histogram(mi355rt_handle* h, uint32_t source, const mi355rt_denoise_config* dn, mi355rt_luminance_histogram* out);
+int mi355rt_display_auto_exposure(const mi355rt_luminance_histogram* hist, float key, float low, float high, float* exposure);   /* HOST only */
+int mi355rt_display_srgb_thresholds(float out[255]);                                                                             /* HOST only */
+int mi355rt_get_display_pixels(mi355rt_handle* h, const mi355rt_display_config* cfg, const mi355rt_denoise_config* dn,
+                               uint32_t* packed, size_t npix, float* exposure_used /* may be NULL */);
+
 /* RayTracer::get_tonemapped_pixels, mod.rs:120-128: width*height u32 0xAARRGGBB (A = 255). */
 int mi355rt_get_tonemapped_pixels(mi355rt_handle* h, uint32_t* out, size_t n);
 /* Same, written to DEVICE memory on the handle's device (e.g. a buffer owned by the caller's

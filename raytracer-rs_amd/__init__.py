@@ -112,6 +112,33 @@ class DenoiseConfig(C.Structure):
                 ("sigma_luminance", C.c_float), ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float)]
 
 
+HIST_BINS = 256            # MI355RT_HIST_BINS
+DISPLAY_SOURCE_FILM, DISPLAY_SOURCE_DENOISED, DISPLAY_SOURCE_DENOISED_SPLIT = 0, 1, 2
+CURVE_REINHARD, CURVE_REINHARD_WHITE, CURVE_ACES, CURVE_CLAMP = 0, 1, 2, 3
+TRANSFER_REFERENCE, TRANSFER_SRGB = 0, 1
+
+
+class LuminanceHistogram(C.Structure):
+    _fields_ = [("bins", C.c_uint32 * HIST_BINS), ("empty", C.c_uint32), ("nan", C.c_uint32), ("nonpositive", C.c_uint32), ("max_bits", C.c_uint32)]
+
+    def as_dict(self):
+        """the layout of display.histogram(): dict(bins uint32[256], empty, nan, nonpositive, max_bits)"""
+        return dict(bins=np.array(self.bins, np.uint32), empty=int(self.empty), nan=int(self.nan), nonpositive=int(self.nonpositive), max_bits=int(self.max_bits))
+
+    @classmethod
+    def from_dict(cls, d):
+        h = cls()
+        bins = np.ascontiguousarray(d["bins"], np.uint32).reshape(HIST_BINS)
+        C.memmove(h.bins, bins.ctypes.data, HIST_BINS * 4)
+        h.empty, h.nan, h.nonpositive, h.max_bits = (int(d.get(k, 0)) for k in ("empty", "nan", "nonpositive", "max_bits"))
+        return h
+
+
+class DisplayConfig(C.Structure):
+    _fields_ = [("source", C.c_uint32), ("curve", C.c_uint32), ("transfer", C.c_uint32), ("auto_exposure", C.c_uint32),
+                ("exposure", C.c_float), ("white", C.c_float), ("key", C.c_float), ("low", C.c_float), ("high", C.c_float)]
+
+
 # every symbol include/mi355rt.h declares: (name, restype, argtypes)
 _H = C.c_void_p
 _F = C.POINTER(C.c_float)
@@ -136,6 +163,11 @@ ABI = [
     ("mi355rt_film_get_direct", C.c_int, [_H, _F]),
     ("mi355rt_get_denoised_pixels_split", C.c_int, [_H, C.POINTER(DenoiseConfig), _F, _U, C.c_size_t]),
     ("mi355rt_get_guides", C.c_int, [_H, _F, _F, _F, _U, C.c_size_t]),
+    ("mi355rt_display_default_config", None, [C.POINTER(DisplayConfig)]),
+    ("mi355rt_display_histogram", C.c_int, [_H, C.c_uint32, C.POINTER(DenoiseConfig), C.POINTER(LuminanceHistogram)]),
+    ("mi355rt_display_auto_exposure", C.c_int, [C.POINTER(LuminanceHistogram), C.c_float, C.c_float, C.c_float, _F]),
+    ("mi355rt_display_srgb_thresholds", C.c_int, [_F]),
+    ("mi355rt_get_display_pixels", C.c_int, [_H, C.POINTER(DisplayConfig), C.POINTER(DenoiseConfig), _U, C.c_size_t, _F]),
     ("mi355rt_get_tonemapped_pixels", C.c_int, [_H, _U, C.c_size_t]),
     ("mi355rt_tonemap_owned_rows_device", C.c_int, [_H, C.c_void_p, C.c_size_t]),
     ("mi355rt_tonemap_owned_rows_device_on_stream", C.c_int, [_H, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -254,6 +286,35 @@ def denoise_config(**kw):
             raise TypeError("unknown denoise config field %r" % k)
         setattr(cfg, k, v)
     return cfg
+
+
+def display_config(**kw):
+    """mi355rt_display_default_config with the given fields replaced (source, curve, transfer, auto_exposure, exposure, white, key, low, high)"""
+    cfg = DisplayConfig()
+    lib().mi355rt_display_default_config(C.byref(cfg))
+    for k, v in kw.items():
+        if not hasattr(cfg, k):
+            raise TypeError("unknown display config field %r" % k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+def display_auto_exposure(hist, key=0.18, low=0.0, high=1.0):
+    """mi355rt_display_auto_exposure (host code, no device): the exposure (numpy float32) a luminance histogram gives; hist: a LuminanceHistogram,
+    or the dict RayTracer.display_histogram() / display.histogram() return.  Raises RuntimeError naming the field for an invalid key, low or high."""
+    h = hist if isinstance(hist, LuminanceHistogram) else LuminanceHistogram.from_dict(hist)
+    out = C.c_float(0.0)
+    if lib().mi355rt_display_auto_exposure(C.byref(h), key, low, high, C.byref(out)) != 0:
+        raise RuntimeError((lib().mi355rt_last_error(None) or b"").decode() or "mi355rt_display_auto_exposure failed")
+    return np.float32(out.value)
+
+
+def display_srgb_thresholds():
+    """mi355rt_display_srgb_thresholds (host code, no device): float32[255], T[1..255] of the sRGB transfer"""
+    out = np.zeros(255, np.float32)
+    if lib().mi355rt_display_srgb_thresholds(_fp(out)) != 0:
+        raise RuntimeError((lib().mi355rt_last_error(None) or b"").decode() or "mi355rt_display_srgb_thresholds failed")
+    return out
 
 
 class Camera:
@@ -429,6 +490,26 @@ class RayTracer:
         fn = lib().mi355rt_get_denoised_pixels_split if split else lib().mi355rt_get_denoised_pixels
         self._check(fn(self._h, C.byref(c), _fp(out_rgb) if rgb else None, _up(out_packed) if packed else None, n))
         return out_rgb, out_packed
+
+    def display_histogram(self, source=0, **dn):
+        """The luminance histogram of a source image (include/mi355rt.h, mi355rt_display_histogram): dict(bins uint32[256], empty, nan, nonpositive,
+        max_bits).  source: DISPLAY_SOURCE_*; dn: denoise config fields for the denoised sources (none given: the default config)."""
+        hist = LuminanceHistogram()
+        c = denoise_config(**dn) if dn else None
+        self._check(lib().mi355rt_display_histogram(self._h, int(source), C.byref(c) if c is not None else None, C.byref(hist)))
+        return hist.as_dict()
+
+    def get_display_pixels(self, denoise=None, out=None, **cfg):
+        """The display read-out (include/mi355rt.h, mi355rt_get_display_pixels): exposure, tone curve and transfer on the film or on a denoised image.
+        cfg: display config fields (not given: mi355rt_display_default_config's values); denoise: dict of denoise config fields for sources 1 and 2
+        (None: the default config).  Returns (packed uint32[npix] 0xAARRGGBB, exposure_used as numpy float32); `out` is filled when given."""
+        c = display_config(**cfg)
+        d = denoise_config(**denoise) if denoise is not None else None
+        if out is None:
+            out = np.zeros(self.width * self.height, np.uint32)
+        used = C.c_float(0.0)
+        self._check(lib().mi355rt_get_display_pixels(self._h, C.byref(c), C.byref(d) if d is not None else None, _up(out), out.size, C.byref(used)))
+        return out, np.float32(used.value)
 
     def guides(self):
         """the denoiser's guide buffers: dict(depth float32[npix], normal float32[npix, 3], albedo float32[npix, 3], prim uint32[npix])"""

@@ -5,6 +5,7 @@
 #include <memory>
 #include <string>
 #include <vector>
+#include "display.hpp"
 #include "lightmap.hpp"
 #include "../../include/mi355rt.h"
 #include "group.hpp"
@@ -79,6 +80,47 @@ bool denoise_config_ok(mi355rt_handle* h, const mi355rt_denoise_config* c)
     if (!e) return true;
     h->r->last_error = e;
     return false;
+}
+// the checks of the display read-out (include/mi355rt.h, "ERRORS"): one device, every row; the source, and the flag the split source needs
+bool display_handle_ok(mi355rt_handle* h, uint32_t source)
+{
+    if (!h) return false;
+    const char* e = nullptr;
+    if (h->g->size() > 1) e = "display: not available on a device group (config.device_count > 1)";
+    else if (h->r->cfg.stripe_world > 1) e = "display: not available on a striped handle (stripe_world > 1): add the stripes into one handle first";
+    else if (source > MI355RT_DISPLAY_SOURCE_DENOISED_SPLIT) e = "display: unknown source";
+    else if (source == MI355RT_DISPLAY_SOURCE_DENOISED_SPLIT && !h->r->has_direct_film()) e = "display: source DENOISED_SPLIT needs a handle created with MI355RT_FLAG_DIRECT_FILM";
+    if (!e) return true;
+    h->r->last_error = e;
+    return false;
+}
+// key, low, high of the auto-exposure rule; null: fine, else the message that names the field
+const char* display_key_range_error(float key, float low, float high)
+{
+    if (!std::isfinite(key) || !(key > 0.0f)) return "display: key must be finite and > 0";
+    if (!(low >= 0.0f) || !(low < 1.0f)) return "display: low must be in [0, 1) and below high";
+    if (!(high > low) || !(high <= 1.0f)) return "display: high must be in (low, 1]";
+    return nullptr;
+}
+const char* display_config_error(const mi355rt_display_config* c)
+{
+    auto positive = [](float s) { return std::isfinite(s) && s > 0.0f; };
+    if (!c) return "display: null config";
+    if (c->curve > MI355RT_CURVE_CLAMP) return "display: unknown curve";
+    if (c->transfer > MI355RT_TRANSFER_SRGB) return "display: unknown transfer";
+    if (c->auto_exposure > 1u) return "display: auto_exposure must be 0 or 1";
+    if (!c->auto_exposure && !positive(c->exposure)) return "display: exposure must be finite and > 0";
+    if (!positive(c->white)) return "display: white must be finite and > 0";
+    return display_key_range_error(c->key, c->low, c->high);
+}
+// dn of a display entry point: ignored for the film, NULL = the default config, else validated; false: last_error names the field
+bool display_denoise_config(mi355rt_handle* h, uint32_t source, const mi355rt_denoise_config* dn, mi355rt_denoise_config& out)
+{
+    mi355rt_denoise_default_config(&out);
+    if (source == MI355RT_DISPLAY_SOURCE_FILM || !dn) return true;
+    if (!denoise_config_ok(h, dn)) return false;
+    out = *dn;
+    return true;
 }
 // the checks of mi355rt_film_set / mi355rt_film_add (include/mi355rt.h); on failure the handle's last_error names the argument
 bool film_put_args_ok(mi355rt_handle* h, const char* fn, const float* sum, const float* sumsq, const uint32_t* n, const float* direct, size_t npix)
@@ -292,6 +334,59 @@ int mi355rt_get_guides(mi355rt_handle* h, float* depth, float* normal3, float* a
 {
     if (!denoise_handle_ok(h, npix)) return MI355RT_E_INVALID;
     return h->r->get_guides(depth, normal3, albedo3, prim) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+void mi355rt_display_default_config(mi355rt_display_config* cfg)
+{
+    if (!cfg) return;
+    std::memset(cfg, 0, sizeof *cfg);
+    cfg->source = MI355RT_DISPLAY_SOURCE_FILM; cfg->curve = MI355RT_CURVE_REINHARD; cfg->transfer = MI355RT_TRANSFER_REFERENCE;
+    cfg->auto_exposure = 0u; cfg->exposure = 1.0f; cfg->white = 4.0f;
+    cfg->key = 0.18f; cfg->low = 0.0f; cfg->high = 1.0f;
+}
+
+int mi355rt_display_histogram(mi355rt_handle* h, uint32_t source, const mi355rt_denoise_config* dn, mi355rt_luminance_histogram* out)
+{
+    if (!display_handle_ok(h, source)) return MI355RT_E_INVALID;
+    if (!out) { h->r->last_error = "display: null histogram output"; return MI355RT_E_INVALID; }
+    mi355rt_denoise_config dcfg;
+    if (!display_denoise_config(h, source, dn, dcfg)) return MI355RT_E_INVALID;
+    mi355rt_luminance_histogram hist;
+    if (!h->r->display_histogram(source, dcfg, hist)) return MI355RT_E_HIP;
+    *out = hist;
+    return MI355RT_OK;
+}
+
+int mi355rt_display_auto_exposure(const mi355rt_luminance_histogram* hist, float key, float low, float high, float* exposure)
+{
+    if (!hist || !exposure) return bad("mi355rt_display_auto_exposure: null argument");
+    if (const char* e = display_key_range_error(key, low, high)) return bad(e);
+    *exposure = display_auto_exposure(*hist, key, low, high);
+    return MI355RT_OK;
+}
+
+int mi355rt_display_srgb_thresholds(float out[255])
+{
+    if (!out) return bad("mi355rt_display_srgb_thresholds: null output");
+    display_srgb_thresholds(out);
+    return MI355RT_OK;
+}
+
+int mi355rt_get_display_pixels(mi355rt_handle* h, const mi355rt_display_config* cfg, const mi355rt_denoise_config* dn, uint32_t* packed, size_t npix, float* exposure_used)
+{
+    if (!h) return MI355RT_E_INVALID;
+    if (!cfg) { h->r->last_error = "display: null config"; return MI355RT_E_INVALID; }
+    if (!display_handle_ok(h, cfg->source)) return MI355RT_E_INVALID;
+    const char* e = display_config_error(cfg);
+    if (!e && !packed) e = "display: null packed output";
+    if (!e && npix != (size_t)h->r->cfg.width * h->r->cfg.height) e = "display: npix must equal width * height";
+    if (e) { h->r->last_error = e; return MI355RT_E_INVALID; }
+    mi355rt_denoise_config dcfg;
+    if (!display_denoise_config(h, cfg->source, dn, dcfg)) return MI355RT_E_INVALID;
+    float used = 0.0f;
+    if (!h->r->get_display(*cfg, dcfg, packed, used)) return MI355RT_E_HIP;
+    if (exposure_used) *exposure_used = used;
+    return MI355RT_OK;
 }
 
 int mi355rt_get_tonemapped_pixels(mi355rt_handle* h, uint32_t* out, size_t n)

@@ -11,6 +11,9 @@
 // and --out receives the split read-out (mi355rt_get_denoised_pixels_split), which filters the indirect part only.  Film files (mi355rt_film_load /
 // mi355rt_film_save): --load-film PATH (repeatable) adds each file to the fresh zero film before any rendering, --save-film PATH writes the film
 // after rendering and before the read-out; with --load-film and -i 0 nothing is rendered and the loaded film is read out once (a merge-only run).
+// Display read-out (mi355rt_get_display_pixels, defaults: mi355rt_display_default_config): any of --exposure F, --auto-exposure, --key F,
+// --curve reinhard|reinhard-white|aces|clamp, --white F, --srgb sends the written frame through it, with the source --denoise / --denoise-split select (the
+// film without them), and prints the exposure used; --exposure together with --auto-exposure is an error.  Without them --out holds the bytes it always held.
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -74,6 +77,9 @@ int main(int argc, char** argv)
     bool adaptive = false, denoise = false, denoise_split = false;
     mi355rt_adaptive_config acfg;
     mi355rt_adaptive_default_config(&acfg);
+    bool display = false, have_exposure = false;
+    mi355rt_display_config dcfg_display;
+    mi355rt_display_default_config(&dcfg_display);
     auto parse_float = [](const char* s, float& out) { if (!s || !*s) return false; char* end = nullptr; const float f = std::strtof(s, &end); if (*end != '\0' || !std::isfinite(f)) return false; out = f; return true; };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -95,6 +101,20 @@ int main(int argc, char** argv)
         else if (a == "--device-lbvh") device_lbvh = true;
         else if (a == "--denoise") denoise = true;
         else if (a == "--denoise-split") denoise_split = true;
+        else if (a == "--exposure") { float f; if (parse_float(take(), f)) { dcfg_display.exposure = f; display = have_exposure = true; } }
+        else if (a == "--auto-exposure") { dcfg_display.auto_exposure = 1u; display = true; }
+        else if (a == "--key") { float f; if (parse_float(take(), f)) { dcfg_display.key = f; display = true; } }
+        else if (a == "--white") { float f; if (parse_float(take(), f)) { dcfg_display.white = f; display = true; } }
+        else if (a == "--srgb") { dcfg_display.transfer = MI355RT_TRANSFER_SRGB; display = true; }
+        else if (a == "--curve") {
+            const std::string c = v ? take() : "";
+            if (c == "reinhard") dcfg_display.curve = MI355RT_CURVE_REINHARD;
+            else if (c == "reinhard-white") dcfg_display.curve = MI355RT_CURVE_REINHARD_WHITE;
+            else if (c == "aces") dcfg_display.curve = MI355RT_CURVE_ACES;
+            else if (c == "clamp") dcfg_display.curve = MI355RT_CURVE_CLAMP;
+            else { std::fprintf(stderr, "Error: --curve takes reinhard, reinhard-white, aces or clamp\n"); return 1; }
+            display = true;
+        }
         else if (a == "--adaptive") { float f; if (parse_float(take(), f)) { acfg.rel_error = f; adaptive = true; } }
         else if (a == "--abs-floor") { float f; if (parse_float(take(), f)) acfg.abs_floor = f; }
         else if (a == "--min-spp") { size_t t; if (parse_usize(take(), t)) acfg.min_spp = (uint32_t)t; }
@@ -104,10 +124,12 @@ int main(int argc, char** argv)
             std::printf("raytracer-rs (MI355X) 0.1.0\nusage: raytracer [-f COLLADA_FILENAME] [-m MAX_TRIS] [-i FRAME_ITERATIONS] [--width W] [--height H]\n"
                         "                 [--spp N] [--seed S] [--gpus N] [--out image.ppm|image.png] [--fix-row-index] [--device-lbvh]\n"
                         "                 [--adaptive REL [--abs-floor F] [--min-spp N] [--max-spp N] [--batch N]] [--denoise | --denoise-split]\n"
-                        "                 [--load-film film.bin]... [--save-film film.bin]\n");
+                        "                 [--load-film film.bin]... [--save-film film.bin]\n"
+                        "                 [--exposure F | --auto-exposure [--key F]] [--curve reinhard|reinhard-white|aces|clamp] [--white F] [--srgb]\n");
             return 0;
         }
     }
+    if (have_exposure && dcfg_display.auto_exposure) { std::fprintf(stderr, "Error: --exposure and --auto-exposure exclude each other\n"); return 1; }
     std::printf("max triangles per leaf: %zu\n", max_triangles);      // main.rs:66
     if (have_iterations) std::printf("will quit after %zu frame iterations\n", frame_iterations);   // main.rs:73
     if (!have_iterations) { frame_iterations = (spp || adaptive) ? 1 : (height + 49) / 50; }   // headless: one sweep of the frame
@@ -150,7 +172,12 @@ int main(int argc, char** argv)
         std::printf("%s\n\n\n", stats.mean_stats().c_str());             // main.rs:216
         if (!save_film.empty()) rt.film.save(save_film);
         if (frame_iterations == 0 && !load_films.empty()) ldr = rt.get_tonemapped_pixels();       // a merge-only run: the loaded film, read out once
-        if (denoise || denoise_split) {                                   // the denoised read-out of the film the loop left (default config)
+        if (display) {                                                    // the display read-out of the film the loop left, of the source the denoise options select
+            dcfg_display.source = denoise_split ? MI355RT_DISPLAY_SOURCE_DENOISED_SPLIT : denoise ? MI355RT_DISPLAY_SOURCE_DENOISED : MI355RT_DISPLAY_SOURCE_FILM;
+            float used = 0.0f;
+            ldr = rt.get_display_pixels(dcfg_display, nullptr, &used);
+            std::printf("display: exposure %.9g%s\n", (double)used, dcfg_display.auto_exposure ? " (auto)" : "");
+        } else if (denoise || denoise_split) {                            // the denoised read-out of the film the loop left (default config)
             mi355rt_denoise_config dcfg;
             mi355rt_denoise_default_config(&dcfg);
             ldr = denoise_split ? rt.get_denoised_pixels_split(dcfg) : rt.get_denoised_pixels(dcfg);

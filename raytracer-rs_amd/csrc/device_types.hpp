@@ -136,6 +136,13 @@ struct DenoiseArgs {
     uint32_t normal_power_log2;
     float sigma_luminance, sigma_depth, sigma_albedo;
 };
+// Display read-out (include/mi355rt.h): the 260 words of mi355rt_luminance_histogram, the lanes of a display_hist_kernel block
+constexpr uint32_t kDisplayHistWords = 260u, kDisplayHistBlock = 1024u;
+struct DisplayArgs {
+    uint32_t curve, transfer;     // MI355RT_CURVE_*, MI355RT_TRANSFER_*
+    float exposure;               // the effective exposure E
+    float white2;                 // white * white (CURVE_REINHARD_WHITE)
+};
 
 struct DCounters {            // one set per render call, zeroed at its start
     unsigned long long bounce, shadow, primary_hits, nodes_visited, tris_tested;

@@ -1500,6 +1500,97 @@ __global__ __launch_bounds__(256) void denoise_iter_split_kernel(DenoiseArgs a, 
     denoise_iter_body<true>(a, g0, g1, flags, in, out, film_direct, film_n, rgb, packed);
 }
 
+// ---- display read-out (include/mi355rt.h) ------------------------------------------------------------------------------
+// The source image of both kernels: film != 0: img is the film's sums and c = s * (1 / n), the film mean (film.rs:46); film == 0: img is the denoiser's
+// rgb read-out on the device and c is what it holds.
+__device__ __forceinline__ void display_source(const float* __restrict__ img, const uint32_t* __restrict__ film_n, int film, uint32_t p, uint32_t& n, float c[3])
+{
+    n = film_n[p];
+    const float inv = film ? div_rn(1.0f, (float)n) : 1.0f;
+    for (int k = 0; k < 3; ++k) { const float s = img[3ull * p + k]; c[k] = film ? s * inv : s; }
+}
+
+// Luminance histogram: hist = the 260 words of mi355rt_luminance_histogram (bins[256], empty, nan, nonpositive, max_bits), zeroed by the caller.
+// A block of 1024 lanes walks the image one pixel per lane and step, keeps the 260 words in LDS (one LDS atomic per pixel: the word the pixel counts in;
+// the maximum stays in a register and takes one LDS atomic per wave at the end) and flushes its non-zero words with device-scope atomics.  The grid is
+// capped by the launcher, so that a frame costs a few thousand global atomics, not one set per 256 pixels.
+// A flat image sends every lane of a wave to one LDS word.  Measured at 1920x1080: 13.1 us against 14.0 us on a rendered film, so the
+// lanes' equal words are NOT added up within the wave first; that version took 12.0 us on the flat film and 19.2 us on the rendered one.
+__global__ __launch_bounds__(kDisplayHistBlock) void display_hist_kernel(uint32_t npix, const float* __restrict__ img, const uint32_t* __restrict__ film_n, int film,
+                                                                         uint32_t* __restrict__ hist)
+{
+    __shared__ uint32_t h[kDisplayHistWords];
+    for (uint32_t i = threadIdx.x; i < kDisplayHistWords; i += kDisplayHistBlock) h[i] = 0u;
+    __syncthreads();
+    uint32_t lmax = 0u;
+    const uint32_t stride = gridDim.x * kDisplayHistBlock;
+    for (uint32_t base = blockIdx.x * kDisplayHistBlock; base < npix; base += stride) {
+        const uint32_t p = base + threadIdx.x;
+        uint32_t word = kMiss;
+        if (p < npix) {
+            uint32_t n; float c[3];
+            display_source(img, film_n, film, p, n, c);
+            const float L = (0.2126f * c[0] + 0.7152f * c[1]) + 0.0722f * c[2];
+            if (n == 0u) word = 256u;
+            else if (L != L) word = 257u;
+            else if (L <= 0.0f) word = 258u;
+            else {
+                const uint32_t bits = __float_as_uint(L);
+                const int b = (int)(bits >> 20) - 856;
+                word = (uint32_t)(b < 0 ? 0 : b > 255 ? 255 : b);
+                lmax = bits > lmax ? bits : lmax;
+            }
+        }
+        if (word != kMiss) atomicAdd(&h[word], 1u);
+        if (base > 0xFFFFFFFFu - stride) break;          // the next base would wrap
+    }
+    for (int o = 32; o > 0; o >>= 1) { const uint32_t v = (uint32_t)__shfl_xor((int)lmax, o); lmax = v > lmax ? v : lmax; }
+    if ((threadIdx.x & 63u) == 0u && lmax != 0u) atomicMax(&h[259], lmax);
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < kDisplayHistWords; i += kDisplayHistBlock) {
+        const uint32_t v = h[i];
+        if (v == 0u) continue;
+        if (i == 259u) atomicMax(&hist[i], v); else atomicAdd(&hist[i], v);
+    }
+}
+
+// Display mapping of one channel (include/mi355rt.h, "Display mapping"): exposure, curve, clamp; f32, unfused, in the order written there
+__device__ __forceinline__ float display_curve(const DisplayArgs& a, float c)
+{
+    const float x = c * a.exposure;
+    float y;
+    switch (a.curve) {
+    case 0u: y = div_rn(x, 1.0f + x); break;
+    case 1u: y = div_rn(x * (1.0f + div_rn(x, a.white2)), 1.0f + x); break;
+    case 2u: y = div_rn(x * (2.51f * x + 0.03f), x * (2.43f * x + 0.59f) + 0.14f); break;
+    default: y = x; break;
+    }
+    return fmaxf(fminf(y, 1.0f), 0.0f);                  // NaN -> 1 (to_u8)
+}
+// One pixel per lane: source -> exposure -> curve -> transfer -> packed.  table: 256 floats, [k] = T[k] of mi355rt_display_srgb_thresholds for k = 1..255
+// ([0] is not read); the block keeps it in LDS and the sRGB code is the number of thresholds <= z, found by an 8-step binary search.
+__global__ __launch_bounds__(256) void display_pack_kernel(DisplayArgs a, uint32_t npix, const float* __restrict__ img, const uint32_t* __restrict__ film_n, int film,
+                                                          const float* __restrict__ table, uint32_t* __restrict__ packed)
+{
+    __shared__ float T[256];
+    if (a.transfer != 0u) { T[threadIdx.x] = table[threadIdx.x]; __syncthreads(); }
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    uint32_t n; float c[3];
+    display_source(img, film_n, film, p, n, c);
+    uint32_t u[3];
+    for (int k = 0; k < 3; ++k) {
+        const float z = display_curve(a, c[k]);
+        if (a.transfer == 0u) u[k] = (uint32_t)(z * 255.0f) & 0xFFu;
+        else {
+            uint32_t lo = 0u;
+            for (uint32_t step = 128u; step != 0u; step >>= 1) if (T[lo + step] <= z) lo += step;
+            u[k] = lo;
+        }
+    }
+    packed[p] = u[2] | (u[1] << 8) | (u[0] << 16) | (255u << 24);
+}
+
 // ---- device arithmetic self-check: a/b, sqrt(a), a^32 as the kernels compute them ----------------
 __global__ void numerics_kernel(const float* __restrict__ a, const float* __restrict__ b, uint32_t n, float* q, float* r, float* p)
 {
@@ -1993,6 +2084,23 @@ hipError_t launch_denoise(hipStream_t stream, const DenoiseArgs& args, uint32_t 
         std::swap(ping, pong);
     }
     return e;
+}
+
+hipError_t launch_display_hist(hipStream_t stream, int num_cus, uint32_t npix, const float* img, const uint32_t* film_n, bool film, uint32_t* hist)
+{
+    if (npix == 0) return hipSuccess;
+    const uint32_t need = (npix + kDisplayHistBlock - 1) / kDisplayHistBlock, cap = (uint32_t)(num_cus > 0 ? num_cus : 1);
+    const dim3 grid(need < cap ? need : cap);
+    hipLaunchKernelGGL(display_hist_kernel, grid, dim3(kDisplayHistBlock), 0, stream, npix, img, film_n, film ? 1 : 0, hist);
+    return hipGetLastError();
+}
+
+hipError_t launch_display_pack(hipStream_t stream, const DisplayArgs& args, uint32_t npix, const float* img, const uint32_t* film_n, bool film, const float* table,
+                               uint32_t* packed)
+{
+    if (npix == 0) return hipSuccess;
+    hipLaunchKernelGGL(display_pack_kernel, dim3((npix + 255) / 256), dim3(256), 0, stream, args, npix, img, film_n, film ? 1 : 0, table, packed);
+    return hipGetLastError();
 }
 
 }  // namespace mi355rt

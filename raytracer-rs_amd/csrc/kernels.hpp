@@ -58,6 +58,12 @@ hipError_t launch_guides(hipStream_t stream, const DScene& sc, const DCamera& ca
 // film_direct non-null: the split read-out (the indirect part is filtered, the direct part added back)
 hipError_t launch_denoise(hipStream_t stream, const DenoiseArgs& args, uint32_t iterations, const float* film_sum, const float* film_sumsq, const uint32_t* film_n,
                           const float* film_direct, const float4* g0, const float4* g1, uint32_t* flags, float4* ping, float4* pong, float* rgb, uint32_t* packed);
+// display read-out.  The source image: film == true: img = the film's sums (c = s * (1 / n)); false: img = the denoiser's rgb on the device.
+// hist: the kDisplayHistWords words of mi355rt_luminance_histogram, zeroed by the caller; at most num_cus blocks
+hipError_t launch_display_hist(hipStream_t stream, int num_cus, uint32_t npix, const float* img, const uint32_t* film_n, bool film, uint32_t* hist);
+// table: 256 floats, [k] = T[k] of mi355rt_display_srgb_thresholds (k = 1..255; [0] unused), read with TRANSFER_SRGB only
+hipError_t launch_display_pack(hipStream_t stream, const DisplayArgs& args, uint32_t npix, const float* img, const uint32_t* film_n, bool film, const float* table,
+                               uint32_t* packed);
 // the gather microbenchmark behind bench.py's roofline: num_cus * 8 blocks walk `steps` random nodes of `table` each
 hipError_t launch_gather_rate(hipStream_t stream, int num_cus, const void* table, uint32_t nnodes, uint32_t steps, uint32_t* sink);
 hipError_t launch_numerics(hipStream_t stream, const float* a, const float* b, uint32_t n, float* q, float* r, float* p);

@@ -127,6 +127,20 @@ public:
         if (mi355rt_get_denoised_pixels_split(h_, &cfg, nullptr, out.data(), out.size()) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
         return out;
     }
+    // display read-out (include/mi355rt.h): exposure, tone curve and transfer on the film or a denoised image; dn == nullptr: the
+    // default denoise config; exposure_used receives the exposure the call applied (the derived one with cfg.auto_exposure)
+    std::vector<uint32_t> get_display_pixels(const mi355rt_display_config& cfg, const mi355rt_denoise_config* dn = nullptr, float* exposure_used = nullptr) const
+    {
+        std::vector<uint32_t> out((size_t)mi355rt_width(h_) * mi355rt_height(h_));
+        if (mi355rt_get_display_pixels(h_, &cfg, dn, out.data(), out.size(), exposure_used) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+        return out;
+    }
+    mi355rt_luminance_histogram display_histogram(uint32_t source = MI355RT_DISPLAY_SOURCE_FILM, const mi355rt_denoise_config* dn = nullptr) const
+    {
+        mi355rt_luminance_histogram hist{};
+        if (mi355rt_display_histogram(h_, source, dn, &hist) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+        return hist;
+    }
     mi355rt_handle* handle() const { return h_; }
 private:
     mi355rt_handle* h_;

@@ -1,5 +1,6 @@
 // renderer.cpp — see renderer.hpp.
 #include "renderer.hpp"
+#include "display.hpp"
 #include "lightmap.hpp"
 #include <algorithm>
 #include <array>
@@ -1554,9 +1555,9 @@ bool Renderer::get_guides(float* depth, float* normal3, float* albedo3, uint32_t
     return true;
 }
 
-bool Renderer::get_denoised(const mi355rt_denoise_config& dc, float* rgb, uint32_t* packed, bool split)
+// The filter of one read-out, queued on the main stream: afterwards d_dn_rgb_ (rgb) and / or d_dn_packed_ (packed) hold its result
+bool Renderer::run_denoise(const mi355rt_denoise_config& dc, bool rgb, bool packed, bool split)
 {
-    if (!bind()) return false;
     if (split && !d_film_direct_) { last_error = "internal: no direct film"; return false; }
     if (!settle_speculation()) return false;
     const size_t npix = (size_t)cfg.width * cfg.height;
@@ -1576,9 +1577,83 @@ bool Renderer::get_denoised(const mi355rt_denoise_config& dc, float* rgb, uint32
     HIP_TRY(launch_denoise(stream_, a, dc.iterations, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), split ? d_film_direct_.get() : nullptr,
                            d_guide0_.get(), d_guide1_.get(), d_dn_flags_.get(),
                            d_dn_ping_.get(), d_dn_pong_.get(), rgb ? d_dn_rgb_.get() : nullptr, packed ? d_dn_packed_.get() : nullptr));
+    return true;
+}
+
+bool Renderer::get_denoised(const mi355rt_denoise_config& dc, float* rgb, uint32_t* packed, bool split)
+{
+    if (!bind()) return false;
+    if (!run_denoise(dc, rgb != nullptr, packed != nullptr, split)) return false;
+    const size_t npix = (size_t)cfg.width * cfg.height;
     if (rgb) HIP_TRY(hipMemcpyAsync(rgb, d_dn_rgb_.get(), npix * 12, hipMemcpyDeviceToHost, stream_));
     if (packed) HIP_TRY(hipMemcpyAsync(packed, d_dn_packed_.get(), npix * 4, hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
+    return true;
+}
+
+// ---- display read-out (include/mi355rt.h) -----------------------------------------------------------------------------
+// The source image on the device, stream-ordered: the film's sums, or the rgb read-out of the denoiser, run here (once per call)
+bool Renderer::display_source(uint32_t source, const mi355rt_denoise_config& dn, const float*& img, bool& film)
+{
+    film = source == MI355RT_DISPLAY_SOURCE_FILM;
+    if (film) {
+        if (!settle_speculation()) return false;
+        img = d_film_sum_.get();
+        return true;
+    }
+    if (!run_denoise(dn, true, false, source == MI355RT_DISPLAY_SOURCE_DENOISED_SPLIT)) return false;
+    img = d_dn_rgb_.get();
+    return true;
+}
+
+bool Renderer::display_hist_queue(const float* img, bool film, mi355rt_luminance_histogram& out)
+{
+    static_assert(sizeof(mi355rt_luminance_histogram) == kDisplayHistWords * 4, "the kernel's words are the struct");
+    if (!d_disp_hist_) HIP_TRY(d_disp_hist_.alloc(kDisplayHistWords * 4, &hbm_bytes_));
+    HIP_TRY(hipMemsetAsync(d_disp_hist_.get(), 0, kDisplayHistWords * 4, stream_));
+    HIP_TRY(launch_display_hist(stream_, num_cus_, cfg.width * cfg.height, img, d_film_n_.get(), film, d_disp_hist_.get()));
+    HIP_TRY(hipMemcpyAsync(&out, d_disp_hist_.get(), kDisplayHistWords * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    return true;
+}
+
+bool Renderer::display_histogram(uint32_t source, const mi355rt_denoise_config& dn, mi355rt_luminance_histogram& out)
+{
+    if (!bind()) return false;
+    const float* img = nullptr; bool film = true;
+    if (!display_source(source, dn, img, film)) return false;
+    return display_hist_queue(img, film, out);
+}
+
+bool Renderer::get_display(const mi355rt_display_config& dc, const mi355rt_denoise_config& dn, uint32_t* packed, float& exposure_used)
+{
+    if (!bind()) return false;
+    const size_t npix = (size_t)cfg.width * cfg.height;
+    const float* img = nullptr; bool film = true;
+    if (!display_source(dc.source, dn, img, film)) return false;
+    if (!d_disp_packed_) HIP_TRY(d_disp_packed_.alloc(npix * 4, &hbm_bytes_));
+    if (!d_disp_hist_) HIP_TRY(d_disp_hist_.alloc(kDisplayHistWords * 4, &hbm_bytes_));       // with the first call, whatever it asks for: the handle's memory
+    if (!d_disp_table_) {                                                                     // does not depend on the configs that follow
+        float t[256];
+        t[0] = 0.0f;                           // never read: the search starts above it
+        display_srgb_thresholds(t + 1);
+        DeviceBuffer<float> tab;
+        HIP_TRY(tab.alloc(sizeof t, &hbm_bytes_));
+        HIP_TRY(hipMemcpy(tab.get(), t, sizeof t, hipMemcpyHostToDevice));
+        d_disp_table_ = std::move(tab);
+    }
+    float E = dc.exposure;
+    if (dc.auto_exposure) {
+        mi355rt_luminance_histogram hist;
+        if (!display_hist_queue(img, film, hist)) return false;
+        E = display_auto_exposure(hist, dc.key, dc.low, dc.high);
+    }
+    DisplayArgs a{};
+    a.curve = dc.curve; a.transfer = dc.transfer; a.exposure = E; a.white2 = dc.white * dc.white;
+    HIP_TRY(launch_display_pack(stream_, a, (uint32_t)npix, img, d_film_n_.get(), film, d_disp_table_.get(), d_disp_packed_.get()));
+    HIP_TRY(hipMemcpyAsync(packed, d_disp_packed_.get(), npix * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    exposure_used = E;
     return true;
 }
 

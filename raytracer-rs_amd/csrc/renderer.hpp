@@ -64,6 +64,9 @@ public:
     bool get_guides(float* depth, float* normal3, float* albedo3, uint32_t* prim);
     bool get_denoised(const mi355rt_denoise_config& dc, float* rgb, uint32_t* packed, bool split = false);   // split: the indirect part is filtered
     bool has_direct_film() const { return (cfg.flags & MI355RT_FLAG_DIRECT_FILM) != 0; }
+    // display read-out; the caller has checked the arguments.  source: MI355RT_DISPLAY_SOURCE_*; dn is read for the denoised sources only
+    bool display_histogram(uint32_t source, const mi355rt_denoise_config& dn, mi355rt_luminance_histogram& out);
+    bool get_display(const mi355rt_display_config& dc, const mi355rt_denoise_config& dn, uint32_t* packed, float& exposure_used);
     void speculation_stats(uint64_t out[2]) const { out[0] = spec_launched_; out[1] = spec_adopted_; }
     bool debug_numerics(const float* a, const float* b, size_t n, float* q, float* r, float* p);
     bool debug_sample(uint32_t pixel, uint32_t sampleno, float* color3, float* node_L, size_t nodes);
@@ -155,6 +158,12 @@ private:
     DeviceBuffer<float4> d_dn_ping_, d_dn_pong_;
     DeviceBuffer<uint32_t> d_dn_flags_, d_dn_packed_;
     DeviceBuffer<float> d_dn_rgb_;
+    bool run_denoise(const mi355rt_denoise_config& dc, bool rgb, bool packed, bool split);   // the filter, queued: d_dn_rgb_ / d_dn_packed_ hold the read-out
+    // Display read-out, allocated on first use: the histogram's 260 words, the 256-entry sRGB threshold table, the packed image
+    bool display_source(uint32_t source, const mi355rt_denoise_config& dn, const float*& img, bool& film);   // queues the denoiser for sources 1 and 2
+    bool display_hist_queue(const float* img, bool film, mi355rt_luminance_histogram& out);                    // kernel + read-back, synchronous
+    DeviceBuffer<uint32_t> d_disp_hist_, d_disp_packed_;
+    DeviceBuffer<float> d_disp_table_;
     void describe_pass(DPass& ps, const Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t row_wrap, uint32_t npix, size_t nsamples, uint32_t chunk,
                        bool explicit_sample, uint32_t epixel, uint32_t esample) const;
     bool begin_call();
