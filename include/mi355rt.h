@@ -492,6 +492,59 @@ int mi355rt_intersect_rays(mi355rt_handle* h, const float* rays6, size_t n, floa
  * has 0.01 < t < 1.0 */
 int mi355rt_occluded_rays(mi355rt_handle* h, const float* rays6, size_t n, uint8_t* blocked);
 
+/* ---- caller-supplied rays: radiance along any ray, and custom cameras (no reference counterpart).  Everything above renders through one
+ * ray generator, the reference's pinhole camera (camera.rs:80-90).  These two entries open the seam one step below it: the caller brings the primary rays
+ * and the library does everything after ray generation exactly as it does for its own — the same kernels, the same bounce tree, the same arithmetic.  A
+ * sample's colour depends only on its ray, its hits and its key (pixel, sampleno): shade() reads ray.dir, never the camera.  So an orthographic, panoramic
+ * or fisheye view, depth of field, a lens-distortion model, a stereo pair or an irradiance probe is a ray generator on the caller's side
+ * (raytracer_rs_amd.cameras has four).
+ *
+ * RAYS.  rays6 = n x (pos3, dir3) f32, 4-byte aligned, used AS GIVEN: dir is not normalised (the camera's own rays have |dir| ~ 1.11), t and the
+ * specular term follow dir as they do in mi355rt_intersect_rays.  Non-finite rays are data and are handled as mi355rt_intersect_rays handles them.
+ * WHERE.  MI355RT_RAYS_HOST: every pointer of the call is host memory; the library stages it through temporary device buffers (24 bytes per ray, 8 per
+ * key, 12 / 12 / 12 / 4 per ray of the outputs asked for, 16 per ray of a pass for tuv or prim), so mi355rt_hbm_allocated_bytes is the same before and
+ * after, apart from pass buffers that grew.  MI355RT_RAYS_DEVICE: every pointer is device memory on the handle's device (a torch tensor's data_ptr), read
+ * and written in place by kernels on the handle's stream; the call is synchronous with respect to the host, like mi355rt_tonemap_owned_rows_device, and work
+ * the caller queued on other streams that produces the rays must have finished.
+ *
+ * mi355rt_trace_rays: the radiance of n arbitrary rays.  It touches no film.  keys2 = n x (pixel, sampleno), or NULL for (i, 0): the key replaces
+ * (pixel, sampleno) in every hash of the sample's bounce tree ({key0, key1, 1 + child_node, seed}, mod.rs:187 as this library seeds it) and need not be a
+ * pixel of the image; two rays with the same key draw the same random numbers.  Outputs (any pointer of `out` may be NULL, not all of them):
+ *     rgb    n x 3: the sample's radiance, compute_radiance's value (mod.rs:146-175; the color3 of mi355rt_debug_sample); (0, 0, 0) for a miss
+ *     direct n x 3: node_L[0], the root light sum (the DIRECT FILM's L0 above); (0, 0, 0) for a miss
+ *     tuv    n x 3 and prim n: exactly what mi355rt_intersect_rays returns for the same rays (tuv untouched on a miss)
+ * The call follows the read-out rules of mi355rt_debug_sample: a queued mi355rt_render_async and a speculative 50-row frame are settled first; the film, the
+ * direct film, the camera, mi355rt_current_row, the changed-row tracking of mi355rt_get_tonemapped_pixels and the denoiser's guides stay as they are.
+ * mi355rt_last_counts afterwards reports primary == n, primary_hits == the number of hits and primary_culled == 0 (no camera made the rays: nothing is
+ * culled, and the primary round walks the tree).  n == 0 succeeds and writes nothing.  Any n < 2^32 is served, in as many passes as the pass buffers need
+ * (config.samples_per_pass, when set, bounds a pass at that many images' worth of rays).  Striped handles serve it: rays belong to no row.
+ *
+ * mi355rt_render_rays: mi355rt_render with the caller's rays.  rays6[(s * npix + p) * 6] is the ray of the CALL's sample s of film pixel p (npix = width *
+ * height, p the index the film planes use); nrays must equal npix * spp.  Sample s of pixel p has the key (p, film_n[p] + s), as mi355rt_render numbers it;
+ * the samples are added to the film (and to the direct film with MI355RT_FLAG_DIRECT_FILM) in sample order.  Rows the handle does not own are neither read
+ * nor written.  Counters and `counts` are as for mi355rt_render, with primary_culled == 0.  With the camera's own rays (cameras.pinhole) the film equals
+ * mi355rt_render(spp) bit for bit; with any other rays MI355RT_FLAG_FIX_ROW_INDEX has nothing to act on.
+ * THE GUARD.  The denoiser's guides and the adaptive sampler's view of the image are built from the handle's camera, so they would be wrong for a film of
+ * other rays.  mi355rt_render_rays marks the film as holding caller-ray samples; mi355rt_film_clear and mi355rt_film_set lift the mark (mi355rt_film_add and
+ * mi355rt_film_load with add != 0 keep it).  While it is set mi355rt_get_denoised_pixels, mi355rt_get_denoised_pixels_split, the display entries with
+ * sources 1 and 2 and mi355rt_render_adaptive return MI355RT_E_INVALID with a message that names mi355rt_render_rays.  The film, variance, tone-mapped and
+ * SOURCE_FILM display read-outs and film add / save / load work as always.  mi355rt_trace_rays never sets the mark.
+ *
+ * ERRORS.  MI355RT_E_INVALID, the argument named in mi355rt_last_error, nothing written: a NULL rays6 with n > 0; `out` NULL or all of its pointers NULL;
+ * an unknown `where`; nrays != width * height * spp; spp == 0; a device group (config.device_count > 1). */
+#define MI355RT_RAYS_HOST   0u   /* every pointer of the call is host memory */
+#define MI355RT_RAYS_DEVICE 1u   /* every pointer is device memory on the handle's device (a torch tensor's data_ptr);
+                                    synchronous with respect to the host, like mi355rt_tonemap_owned_rows_device */
+typedef struct mi355rt_ray_outputs {   /* any pointer may be NULL, not all of them */
+    float*    rgb;     /* n x 3: the sample's radiance, compute_radiance's value; (0,0,0) for a miss */
+    float*    direct;  /* n x 3: node_L[0], the root light sum (the DIRECT FILM's L0) */
+    float*    tuv;     /* n x 3 and */
+    uint32_t* prim;    /* n: exactly what mi355rt_intersect_rays returns for the same rays */
+} mi355rt_ray_outputs;
+int mi355rt_trace_rays(mi355rt_handle* h, const float* rays6, const uint32_t* keys2 /* n x (pixel, sampleno); NULL: (i, 0) */,
+                       size_t n, uint32_t where, const mi355rt_ray_outputs* out);
+int mi355rt_render_rays(mi355rt_handle* h, const float* rays6, size_t nrays, uint32_t spp, uint32_t where, mi355rt_ray_counts* counts);
+
 /* SampleGenerator table, sample_generator.rs:15-24: 65 536 x 3 floats */
 int mi355rt_get_sample_table(const mi355rt_handle* h, float* out);
 /* Per-node direct-light terms of one primary sample, computed on the device by the same

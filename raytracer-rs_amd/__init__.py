@@ -139,6 +139,16 @@ class DisplayConfig(C.Structure):
                 ("exposure", C.c_float), ("white", C.c_float), ("key", C.c_float), ("low", C.c_float), ("high", C.c_float)]
 
 
+RAYS_HOST, RAYS_DEVICE = 0, 1      # MI355RT_RAYS_*: where the pointers of mi355rt_trace_rays / mi355rt_render_rays live
+
+
+class RayOutputs(C.Structure):
+    """mi355rt_ray_outputs: any pointer may be NULL, not all of them (void pointers here: host arrays or device addresses)"""
+    _fields_ = [("rgb", C.c_void_p), ("direct", C.c_void_p), ("tuv", C.c_void_p), ("prim", C.c_void_p)]
+
+
+RAY_OUTPUTS = ("rgb", "direct", "tuv", "prim")
+
 # every symbol include/mi355rt.h declares: (name, restype, argtypes)
 _H = C.c_void_p
 _F = C.POINTER(C.c_float)
@@ -193,6 +203,8 @@ ABI = [
     ("mi355rt_get_slices", C.c_uint32, [_H]),
     ("mi355rt_intersect_rays", C.c_int, [_H, _F, C.c_size_t, _F, _U]),
     ("mi355rt_occluded_rays", C.c_int, [_H, _F, C.c_size_t, C.POINTER(C.c_uint8)]),
+    ("mi355rt_trace_rays", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(RayOutputs)]),
+    ("mi355rt_render_rays", C.c_int, [_H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(RayCounts)]),
     ("mi355rt_get_sample_table", C.c_int, [_H, _F]),
     ("mi355rt_debug_sample", C.c_int, [_H, C.c_uint32, C.c_uint32, _F, _F, C.c_size_t]),
     ("mi355rt_debug_numerics", C.c_int, [_H, _F, _F, C.c_size_t, _F, _F, _F]),
@@ -253,6 +265,36 @@ def _fp(a):
 
 def _up(a):
     return a.ctypes.data_as(_U)
+
+
+def _is_tensor(a):
+    """a torch tensor (without importing torch for callers that never hand one in)"""
+    t = sys.modules.get("torch")
+    return t is not None and isinstance(a, t.Tensor)
+
+
+def _ray_array(a, name, cols, dtype, rows=None):
+    """Check one array argument of trace_rays / render_rays BEFORE any library call: a C-contiguous numpy array (host) or torch tensor on a GPU
+    (device) of exactly this dtype and shape (rows, cols); a uint32 argument may be a torch.int32 tensor holding the same bits (torch has little uint32
+    support).  Returns (address, rows, is_device)."""
+    want = np.dtype(dtype).name
+    if _is_tensor(a):
+        if a.device.type != "cuda":
+            raise ValueError("%s: a torch tensor must live on the handle's GPU (it is on %s); pass a numpy array for host memory" % (name, a.device))
+        if str(a.dtype).replace("torch.", "") not in ((want, "int32") if want == "uint32" else (want,)):
+            raise TypeError("%s: dtype must be %s, not %s" % (name, want, a.dtype))
+        shape, contiguous, addr, dev = tuple(a.shape), a.is_contiguous(), a.data_ptr(), True
+    elif isinstance(a, np.ndarray):
+        if a.dtype != np.dtype(dtype):
+            raise TypeError("%s: dtype must be %s, not %s" % (name, want, a.dtype))
+        shape, contiguous, addr, dev = a.shape, a.flags["C_CONTIGUOUS"], a.ctypes.data, False
+    else:
+        raise TypeError("%s: a numpy array or a torch tensor, not %s" % (name, type(a).__name__))
+    if len(shape) != 2 or shape[1] != cols or (rows is not None and shape[0] != rows):
+        raise ValueError("%s: shape must be (%s, %d), not %s" % (name, "n" if rows is None else rows, cols, tuple(shape)))
+    if not contiguous:
+        raise ValueError("%s: must be C-contiguous" % name)
+    return addr, shape[0], dev
 
 
 def default_config(width=1024, height=768, **kw):
@@ -604,6 +646,52 @@ class RayTracer:
         tuv = np.zeros((n, 3), np.float32); prim = np.zeros(n, np.uint32)
         self._check(lib().mi355rt_intersect_rays(self._h, _fp(rays6), n, _fp(tuv), _up(prim)))
         return tuv, prim
+
+    def trace_rays(self, rays6, keys=None, want=("rgb",)):
+        """mi355rt_trace_rays: the radiance of arbitrary rays; no film is touched.  rays6: float32 (n, 6) rows (pos3, dir3), used as given; keys: uint32
+        (n, 2) rows (pixel, sampleno) for the sample's random numbers, None: (i, 0); want: any of "rgb", "direct", "tuv", "prim".  numpy arrays are host
+        memory and the results come back as numpy arrays; torch tensors on the handle's GPU are read in place (MI355RT_RAYS_DEVICE) and the results are
+        tensors on that device.  Returns a dict name -> array: rgb, direct, tuv (n, 3) float32; prim (n,) uint32 (as a tensor: torch.int32 holding the
+        same bits, a miss is -1)."""
+        want = tuple(want)
+        if not want or any(w not in RAY_OUTPUTS for w in want) or len(set(want)) != len(want):
+            raise ValueError("want: a non-empty selection of %s without repeats, not %r" % (RAY_OUTPUTS, want))
+        addr, n, dev = _ray_array(rays6, "rays6", 6, np.float32)
+        kaddr = None
+        if keys is not None:
+            kaddr, _, kdev = _ray_array(keys, "keys", 2, np.uint32, rows=n)
+            if kdev != dev:
+                raise ValueError("keys must live where rays6 lives (both numpy arrays, or both tensors on the GPU)")
+        res, o = {}, RayOutputs()
+        if dev:
+            import torch
+            torch.cuda.current_stream(rays6.device).synchronize()           # what produced the rays has finished: the library's stream knows nothing of torch's
+            for w in want:
+                res[w] = torch.zeros((n,) if w == "prim" else (n, 3), dtype=torch.int32 if w == "prim" else torch.float32, device=rays6.device)
+                setattr(o, w, res[w].data_ptr())
+            torch.cuda.current_stream(rays6.device).synchronize()           # ... and so has the zero fill
+        else:
+            for w in want:
+                res[w] = np.zeros(n, np.uint32) if w == "prim" else np.zeros((n, 3), np.float32)
+                setattr(o, w, res[w].ctypes.data)
+        self._check(lib().mi355rt_trace_rays(self._h, addr, kaddr, n, RAYS_DEVICE if dev else RAYS_HOST, C.byref(o)))
+        return res
+
+    def render_rays(self, rays6, spp):
+        """mi355rt_render_rays: mi355rt_render with the caller's rays.  rays6: float32 (width * height * spp, 6), row s * npix + p = the ray of the call's
+        sample s of film pixel p (raytracer_rs_amd.cameras builds such arrays); a numpy array (host) or a torch tensor on the handle's GPU.  Returns
+        the call's counters.  Afterwards the film holds caller-ray samples: the denoised read-outs and render_adaptive refuse it until film.clear() /
+        film.set()."""
+        spp = int(spp)
+        if spp < 1:
+            raise ValueError("spp must be >= 1")
+        addr, n, dev = _ray_array(rays6, "rays6", 6, np.float32, rows=self.width * self.height * spp)
+        if dev:
+            import torch
+            torch.cuda.current_stream(rays6.device).synchronize()
+        rc = RayCounts()
+        self._check(lib().mi355rt_render_rays(self._h, addr, n, spp, RAYS_DEVICE if dev else RAYS_HOST, C.byref(rc)))
+        return rc
 
     def occluded_rays(self, rays6):
         rays6 = np.ascontiguousarray(rays6, np.float32).reshape(-1, 6)

@@ -138,6 +138,26 @@ bool film_put_args_ok(mi355rt_handle* h, const char* fn, const float* sum, const
     return false;
 }
 
+// the guard of the read-outs built on the camera's guides (include/mi355rt.h, "CALLER-SUPPLIED RAYS"): false while the film holds caller-ray samples
+bool camera_film_ok(mi355rt_handle* h, const char* fn)
+{
+    if (!h->r->caller_ray_film()) return true;
+    h->r->last_error = std::string(fn) + ": the film holds samples of mi355rt_render_rays, which the camera's guides and tiles do not describe; mi355rt_film_clear or mi355rt_film_set first";
+    return false;
+}
+// the checks mi355rt_trace_rays and mi355rt_render_rays share
+bool ray_call_ok(mi355rt_handle* h, const char* fn, const float* rays6, size_t n, uint32_t where)
+{
+    if (!h) return false;
+    const char* e = nullptr;
+    if (h->g->size() > 1) e = "not available on a device group (config.device_count > 1)";
+    else if (where > MI355RT_RAYS_DEVICE) e = "unknown `where` (MI355RT_RAYS_HOST or MI355RT_RAYS_DEVICE)";
+    else if (n && !rays6) e = "rays6 is NULL";
+    if (!e) return true;
+    h->r->last_error = std::string(fn) + ": " + e;
+    return false;
+}
+
 // ---- film files (include/mi355rt.h, "FILM FILE"): a 64-byte little-endian header, then the planes n, sum, sumsq [, direct]
 constexpr size_t kFilmHeaderBytes = 64;
 constexpr char kFilmMagic[9] = "MI355FLM";
@@ -289,7 +309,7 @@ void mi355rt_adaptive_default_config(mi355rt_adaptive_config* cfg)
 
 int mi355rt_render_adaptive(mi355rt_handle* h, const mi355rt_adaptive_config* cfg, mi355rt_adaptive_stats* stats)
 {
-    if (!adaptive_args_ok(h, cfg)) return MI355RT_E_INVALID;
+    if (!adaptive_args_ok(h, cfg) || !camera_film_ok(h, "mi355rt_render_adaptive")) return MI355RT_E_INVALID;
     mi355rt_adaptive_stats st{};
     const bool ok = h->r->render_adaptive(*cfg, st);
     if (stats) *stats = st;
@@ -319,6 +339,7 @@ int mi355rt_get_denoised_pixels(mi355rt_handle* h, const mi355rt_denoise_config*
 {
     if (!denoise_handle_ok(h, npix) || !denoise_config_ok(h, cfg)) return MI355RT_E_INVALID;
     if (!rgb && !packed) { h->r->last_error = "denoise: rgb and packed are both NULL"; return MI355RT_E_INVALID; }
+    if (!camera_film_ok(h, "mi355rt_get_denoised_pixels")) return MI355RT_E_INVALID;
     return h->r->get_denoised(*cfg, rgb, packed) ? MI355RT_OK : MI355RT_E_HIP;
 }
 
@@ -327,6 +348,7 @@ int mi355rt_get_denoised_pixels_split(mi355rt_handle* h, const mi355rt_denoise_c
     if (!denoise_handle_ok(h, npix) || !denoise_config_ok(h, cfg)) return MI355RT_E_INVALID;
     if (!rgb && !packed) { h->r->last_error = "denoise: rgb and packed are both NULL"; return MI355RT_E_INVALID; }
     if (!h->r->has_direct_film()) { h->r->last_error = "denoise: the split read-out needs a handle created with MI355RT_FLAG_DIRECT_FILM"; return MI355RT_E_INVALID; }
+    if (!camera_film_ok(h, "mi355rt_get_denoised_pixels_split")) return MI355RT_E_INVALID;
     return h->r->get_denoised(*cfg, rgb, packed, true) ? MI355RT_OK : MI355RT_E_HIP;
 }
 
@@ -351,6 +373,7 @@ int mi355rt_display_histogram(mi355rt_handle* h, uint32_t source, const mi355rt_
     if (!out) { h->r->last_error = "display: null histogram output"; return MI355RT_E_INVALID; }
     mi355rt_denoise_config dcfg;
     if (!display_denoise_config(h, source, dn, dcfg)) return MI355RT_E_INVALID;
+    if (source != MI355RT_DISPLAY_SOURCE_FILM && !camera_film_ok(h, "mi355rt_display_histogram")) return MI355RT_E_INVALID;
     mi355rt_luminance_histogram hist;
     if (!h->r->display_histogram(source, dcfg, hist)) return MI355RT_E_HIP;
     *out = hist;
@@ -383,6 +406,7 @@ int mi355rt_get_display_pixels(mi355rt_handle* h, const mi355rt_display_config* 
     if (e) { h->r->last_error = e; return MI355RT_E_INVALID; }
     mi355rt_denoise_config dcfg;
     if (!display_denoise_config(h, cfg->source, dn, dcfg)) return MI355RT_E_INVALID;
+    if (cfg->source != MI355RT_DISPLAY_SOURCE_FILM && !camera_film_ok(h, "mi355rt_get_display_pixels")) return MI355RT_E_INVALID;
     float used = 0.0f;
     if (!h->r->get_display(*cfg, dcfg, packed, used)) return MI355RT_E_HIP;
     if (exposure_used) *exposure_used = used;
@@ -587,6 +611,26 @@ int mi355rt_occluded_rays(mi355rt_handle* h, const float* rays6, size_t n, uint8
 {
     if (!h || (n && (!rays6 || !blocked))) return MI355RT_E_INVALID;
     return h->r->intersect(rays6, n, nullptr, nullptr, blocked) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_trace_rays(mi355rt_handle* h, const float* rays6, const uint32_t* keys2, size_t n, uint32_t where, const mi355rt_ray_outputs* out)
+{
+    if (!ray_call_ok(h, "mi355rt_trace_rays", rays6, n, where)) return MI355RT_E_INVALID;
+    if (!out || (!out->rgb && !out->direct && !out->tuv && !out->prim)) { h->r->last_error = "mi355rt_trace_rays: out is NULL or every output pointer in it is NULL"; return MI355RT_E_INVALID; }
+    if (n > 0xFFFFFFFFull) { h->r->last_error = "mi355rt_trace_rays: n must fit 32 bits"; return MI355RT_E_INVALID; }
+    return h->r->trace_rays(rays6, keys2, n, where == MI355RT_RAYS_DEVICE, *out) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_render_rays(mi355rt_handle* h, const float* rays6, size_t nrays, uint32_t spp, uint32_t where, mi355rt_ray_counts* counts)
+{
+    if (!ray_call_ok(h, "mi355rt_render_rays", rays6, nrays, where)) return MI355RT_E_INVALID;
+    const char* e = nullptr;
+    if (spp == 0) e = "mi355rt_render_rays: spp must be >= 1";
+    else if (nrays != (size_t)h->r->cfg.width * h->r->cfg.height * spp) e = "mi355rt_render_rays: nrays must equal width * height * spp";
+    if (e) { h->r->last_error = e; return MI355RT_E_INVALID; }
+    const bool ok = h->r->render_rays(rays6, spp, where == MI355RT_RAYS_DEVICE);
+    if (counts) *counts = h->r->counts;
+    return ok ? MI355RT_OK : MI355RT_E_HIP;
 }
 
 int mi355rt_get_sample_table(const mi355rt_handle* h, float* out)

@@ -14,6 +14,8 @@
 // Display read-out (mi355rt_get_display_pixels, defaults: mi355rt_display_default_config): any of --exposure F, --auto-exposure, --key F,
 // --curve reinhard|reinhard-white|aces|clamp, --white F, --srgb sends the written frame through it, with the source --denoise / --denoise-split select (the
 // film without them), and prints the exposure used; --exposure together with --auto-exposure is an error.  Without them --out holds the bytes it always held.
+// Caller-supplied rays (mi355rt_render_rays): --ortho-width W with --spp N renders the scene in parallel projection, W world units wide, through rays made
+// here (ortho_rays below: the arithmetic of raytracer_rs_amd.cameras.orthographic, so both paths write the same bytes).
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -55,6 +57,43 @@ static bool write_png(const std::string& path, const std::vector<uint32_t>& argb
     return std::fclose(f) == 0;
 }
 
+// pcg4d (Jarzynski & Olano, JCGT 2020) and the 23-bit uniform float, as csrc/device_math.hpp runs them
+static void pcg4d(uint32_t& x, uint32_t& y, uint32_t& z, uint32_t& w)
+{
+    x = x * 1664525u + 1013904223u; y = y * 1664525u + 1013904223u; z = z * 1664525u + 1013904223u; w = w * 1664525u + 1013904223u;
+    x += y * w; y += z * x; z += x * y; w += y * z;
+    x ^= x >> 16; y ^= y >> 16; z ^= z >> 16; w ^= w >> 16;
+    x += y * w; y += z * x; z += x * y; w += y * z;
+}
+static float u01(uint32_t bits) { return (float)(bits >> 9) * (1.0f / 8388608.0f); }
+
+// The rays of an orthographic view in mi355rt_render_rays layout: cameras.orthographic of the Python package, expression for expression (f32, unfused:
+// this file is compiled with -ffp-contract=off).  rot, orient: mi355rt_camera_get; film_n: the film's sample counts before the call.
+static std::vector<float> ortho_rays(const float rot[16], const float orient[16], size_t width, size_t height, size_t spp, uint32_t seed, float width_world,
+                                     const std::vector<uint32_t>& film_n)
+{
+    const size_t npix = width * height;
+    std::vector<float> rays(npix * spp * 6);
+    float origin[3], axis[3];
+    for (int k = 0; k < 3; ++k) {
+        origin[k] = 0.0f * orient[k] + 0.0f * orient[4 + k] + 0.0f * orient[8 + k] + 1.0f * orient[12 + k];
+        axis[k] = rot[8 + k] + rot[12 + k];
+    }
+    const float hw = width_world * 0.5f;
+    const float hh = hw * ((float)height / (float)width);
+    for (size_t s = 0; s < spp; ++s)
+        for (size_t p = 0; p < npix; ++p) {
+            uint32_t h0 = (uint32_t)p, h1 = film_n[p] + (uint32_t)s, h2 = 0u, h3 = seed;
+            pcg4d(h0, h1, h2, h3);
+            const float cu = (float)(uint32_t)(p % width), cv = (float)(uint32_t)(p / width);
+            const float sx = -hw + (2.0f * hw) * ((cu + u01(h0)) / (float)width);
+            const float sy = -hh + (2.0f * hh) * ((cv + u01(h1)) / (float)height);
+            float* r = &rays[(s * npix + p) * 6];
+            for (int k = 0; k < 3; ++k) { r[k] = (origin[k] + sx * rot[k]) + (-sy) * rot[4 + k]; r[3 + k] = axis[k]; }
+        }
+    return rays;
+}
+
 static bool parse_usize(const char* s, size_t& out)
 {
     if (!s || !*s) return false;
@@ -77,7 +116,8 @@ int main(int argc, char** argv)
     bool adaptive = false, denoise = false, denoise_split = false;
     mi355rt_adaptive_config acfg;
     mi355rt_adaptive_default_config(&acfg);
-    bool display = false, have_exposure = false;
+    bool display = false, have_exposure = false, ortho = false;
+    float ortho_width = 0.0f;
     mi355rt_display_config dcfg_display;
     mi355rt_display_default_config(&dcfg_display);
     auto parse_float = [](const char* s, float& out) { if (!s || !*s) return false; char* end = nullptr; const float f = std::strtof(s, &end); if (*end != '\0' || !std::isfinite(f)) return false; out = f; return true; };
@@ -115,6 +155,7 @@ int main(int argc, char** argv)
             else { std::fprintf(stderr, "Error: --curve takes reinhard, reinhard-white, aces or clamp\n"); return 1; }
             display = true;
         }
+        else if (a == "--ortho-width") { float f; if (parse_float(take(), f) && f > 0.0f) { ortho_width = f; ortho = true; } }
         else if (a == "--adaptive") { float f; if (parse_float(take(), f)) { acfg.rel_error = f; adaptive = true; } }
         else if (a == "--abs-floor") { float f; if (parse_float(take(), f)) acfg.abs_floor = f; }
         else if (a == "--min-spp") { size_t t; if (parse_usize(take(), t)) acfg.min_spp = (uint32_t)t; }
@@ -125,10 +166,12 @@ int main(int argc, char** argv)
                         "                 [--spp N] [--seed S] [--gpus N] [--out image.ppm|image.png] [--fix-row-index] [--device-lbvh]\n"
                         "                 [--adaptive REL [--abs-floor F] [--min-spp N] [--max-spp N] [--batch N]] [--denoise | --denoise-split]\n"
                         "                 [--load-film film.bin]... [--save-film film.bin]\n"
-                        "                 [--exposure F | --auto-exposure [--key F]] [--curve reinhard|reinhard-white|aces|clamp] [--white F] [--srgb]\n");
+                        "                 [--exposure F | --auto-exposure [--key F]] [--curve reinhard|reinhard-white|aces|clamp] [--white F] [--srgb]\n"
+                        "                 [--ortho-width W]   (with --spp: an orthographic view W world units wide, through mi355rt_render_rays)\n");
             return 0;
         }
     }
+    if (ortho && (!spp || adaptive || denoise || denoise_split || gpus > 1)) { std::fprintf(stderr, "Error: --ortho-width needs --spp and excludes --adaptive, --denoise, --denoise-split and --gpus\n"); return 1; }
     if (have_exposure && dcfg_display.auto_exposure) { std::fprintf(stderr, "Error: --exposure and --auto-exposure exclude each other\n"); return 1; }
     std::printf("max triangles per leaf: %zu\n", max_triangles);      // main.rs:66
     if (have_iterations) std::printf("will quit after %zu frame iterations\n", frame_iterations);   // main.rs:73
@@ -158,7 +201,14 @@ int main(int argc, char** argv)
                             st.rounds, st.tiles_active_first, st.tiles, st.tiles_active_last, (unsigned long long)st.samples_added,
                             (double)st.samples_added / ((double)mi355rt_owned_rows(rt.handle()) * (double)width), c.total_ms);
             } else if (spp) {
-                mi355rt_ray_counts c = rt.render((uint32_t)spp);
+                mi355rt_ray_counts c;
+                if (ortho) {
+                    float rot[16], orient[16], max_xy[2];
+                    mi355rt_camera_get(rt.handle(), rot, orient, max_xy);
+                    std::vector<uint32_t> film_n(width * height);
+                    if (mi355rt_film_get(rt.handle(), nullptr, nullptr, film_n.data()) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(rt.handle()));
+                    c = rt.render_rays(ortho_rays(rot, orient, width, height, spp, (uint32_t)seed, ortho_width, film_n), (uint32_t)spp);
+                } else c = rt.render((uint32_t)spp);
                 num_primary_rays = (uint32_t)c.primary;
                 std::printf("frame: %.3f ms  rays: %llu primary %llu bounce %llu shadow -> %.1f Mrays/s\n", c.total_ms,
                             (unsigned long long)c.primary, (unsigned long long)c.bounce, (unsigned long long)c.shadow,

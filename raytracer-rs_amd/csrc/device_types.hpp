@@ -119,6 +119,17 @@ struct DPass {
     // whose pixel lies in a tile whose byte is 0 is not rendered at all (no ray, no film update).  null: every pixel is active.
     const uint8_t* tile_active;
     uint32_t tiles_x;
+    // Ray-fed pass (mi355rt_trace_rays / mi355rt_render_rays): the primary rays come from ray_in, n x (pos3, dir3) as the caller laid them out,
+    // not from the camera.  Read by the RAYS instantiations of the kernels only.
+    //   ray_mode 1 (render_rays): pass sample (s, p) of film pixel `pixel` reads ray (ray_base + s) * ray_npix + pixel — ray_base is the CALL's sample number
+    //                             of the pass's sample 0, ray_npix = width * height — and its key is (pixel, film_n[pixel] + s) as in every frame
+    //   ray_mode 2 (trace_rays):  sample gi of the pass IS ray gi of ray_in (the host offsets the pointers pass by pass); key ray_keys[gi], or
+    //                             (ray_base + gi, 0) without keys — ray_base is the index of the pass's ray 0 in the call
+    // ray_hit (trace_rays with tuv or prim asked for): per sample the final hit (t, u, v, prim bits) of its primary ray, written by the primary shade launch
+    const float* ray_in;
+    const uint32_t* ray_keys;
+    float4* ray_hit;
+    uint32_t ray_mode, ray_base, ray_npix;
 };
 constexpr uint32_t kAdaptiveTile = 8;      // MI355RT_ADAPTIVE_TILE
 struct AdaptiveArgs {         // adaptive_tiles_kernel: the image, the handle's stripe ownership and the config of the call

@@ -247,10 +247,36 @@ __device__ __forceinline__ void pixel_ray(const DCamera& cam, uint32_t flags, ui
     o = mk3(cam.origin[0], cam.origin[1], cam.origin[2]);
 }
 
+// A caller's ray (DPass::ray_in, mi355rt_trace_rays / mi355rt_render_rays): 24 bytes at a 4-byte-aligned address, so neither half of it is a 16-byte
+// load.  Two 12-byte loads (global_load_dwordx3) per lane: the 64 rays of a wave are 1536 contiguous bytes, each load instruction touches its 12
+// cache lines once (6 dword loads would touch them six times), and nothing has to be repacked first.
+struct __attribute__((packed, aligned(4))) RayHalf { float x, y, z; };
+struct __attribute__((packed, aligned(4))) RayKey { uint32_t pixel, sampleno; };
+
 // pixel -> primary ray, mod.rs:93-96 + camera.rs:80-90.  gi = index of the primary sample in the pass.
+// RAYS (a ray-fed pass): the ray is the caller's, used as given; the key (pixel, sampleno) is the film's numbering (ray_mode 1:
+// mi355rt_render_rays, the pass order and film_n as below) or the caller's (ray_mode 2: mi355rt_trace_rays, sample gi IS ray gi of the pass).
+template <bool RAYS = false>
 __device__ __forceinline__ void primary_sample(const DCamera& cam, const DPass& ps, const uint32_t* __restrict__ film_n, uint32_t gi,
                                                uint32_t& pixel, uint32_t& sampleno, f3& o, f3& d)
 {
+    if constexpr (RAYS) {
+        size_t ri = gi;
+        if (ps.ray_mode == 2u) {
+            if (ps.ray_keys != nullptr) { const RayKey k = ((const RayKey*)ps.ray_keys)[gi]; pixel = k.pixel; sampleno = k.sampleno; }
+            else { pixel = ps.ray_base + gi; sampleno = 0u; }
+        } else {
+            uint32_t s, p;
+            sample_of(ps, gi, s, p);
+            pixel = pass_pixel(ps, cam.width, p);
+            sampleno = film_n[pixel] + s;
+            ri = (size_t)(ps.ray_base + s) * ps.ray_npix + pixel;       // the CALL's sample number, not the pass's
+        }
+        const RayHalf* r = (const RayHalf*)(ps.ray_in + 6ull * ri);
+        const RayHalf a = r[0], b = r[1];
+        o = mk3(a.x, a.y, a.z); d = mk3(b.x, b.y, b.z);
+        return;
+    }
     if (ps.use_explicit) { pixel = ps.explicit_pixel; sampleno = ps.explicit_sampleno; }
     else {
         uint32_t s, p;
@@ -397,7 +423,8 @@ __device__ __forceinline__ void store_blocked(float* __restrict__ slot_L, uint32
 // and every ray only records its hit; the octree confirm step (confirm_chunk) turns true closest hits into the reference
 // intersector's answers and settles the shadow predicate.  CONFIRM == false (MI355RT_FLAG_TRUE_CLOSEST_HIT): the shadow
 // predicate is decided here with the interval trick of traverse.hpp and unblocked light terms are stored directly.
-template <bool PRIMARY, bool COUNT, bool SINGLE, bool CONFIRM>
+// RAYS (PRIMARY only): a ray-fed pass — the primary rays come from DPass::ray_in, and nothing is culled (no camera made them).
+template <bool PRIMARY, bool COUNT, bool SINGLE, bool CONFIRM, bool RAYS = false>
 __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam, const DPass& ps,
                                            const float4* __restrict__ in_q, const uint2* __restrict__ in_counts,
                                            float4* __restrict__ hits, uint32_t* cursor,
@@ -467,7 +494,7 @@ __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam,
                 w_chunk = bcast_first(c); w_next = 0u;
                 if (PRIMARY) {
                     w_nrad = min(ps.chunk, ps.nsamples - w_chunk * ps.chunk);
-                    if (chunk_culled(cam, ps, w_chunk, w_nrad)) w_nrad = 0u;    // the shade kernel makes the same decision
+                    if (!RAYS && chunk_culled(cam, ps, w_chunk, w_nrad)) w_nrad = 0u;    // the shade kernel makes the same decision
                     w_nrad = bcast_first(w_nrad);
                     w_ntot = w_nrad;
                 }
@@ -490,9 +517,9 @@ __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam,
                 int start = sc.root;
                 if (PRIMARY) {
                     uint32_t pixel, sampleno;
-                    primary_sample(cam, ps, film_n, w_chunk * ps.chunk + i, pixel, sampleno, o, d);
+                    primary_sample<RAYS>(cam, ps, film_n, w_chunk * ps.chunk + i, pixel, sampleno, o, d);
                     rec = w_chunk * ps.region + i;
-                    if (!pixel_active(ps, cam.width, pixel)) start = kNodeFin;    // adaptive sampling: finished at once, a miss that was never traced
+                    if (!RAYS && !pixel_active(ps, cam.width, pixel)) start = kNodeFin;    // adaptive sampling: finished at once, a miss that was never traced
                 } else {
                     // record index in 32 bits, byte offsets in 64 (a whole 1080p x 64 spp frame in ONE pass is 531 M records of 16 B per plane);
                     // the planes of the queue are wave-uniform base pointers
@@ -558,7 +585,7 @@ __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam,
     }
 }
 
-template <bool PRIMARY, bool COUNT, bool CONFIRM>
+template <bool PRIMARY, bool COUNT, bool CONFIRM, bool RAYS = false>
 __global__ __launch_bounds__(kBlock, MI355RT_WIDE ? MI355RT_WIDE_BLOCKS : PRIMARY ? kPrimaryBlocks : 8) void trace_kernel(DScene sc, DCamera cam, DPass ps,
                                                       const float4* __restrict__ in_q, const uint2* __restrict__ in_counts,
                                                       float4* __restrict__ hits, uint32_t* cursor,
@@ -566,7 +593,7 @@ __global__ __launch_bounds__(kBlock, MI355RT_WIDE ? MI355RT_WIDE_BLOCKS : PRIMAR
                                                       DCounters* counters)
 {
     extern __shared__ int s_stack[];                 // ps.stack_depth rows of kBlock ints
-    trace_wave<PRIMARY, COUNT, false, CONFIRM>(sc, cam, ps, in_q, in_counts, hits, cursor, slot_L, film_n, counters, &s_stack[threadIdx.x], 0u, 0u, 0u);
+    trace_wave<PRIMARY, COUNT, false, CONFIRM, RAYS>(sc, cam, ps, in_q, in_counts, hits, cursor, slot_L, film_n, counters, &s_stack[threadIdx.x], 0u, 0u, 0u);
 }
 
 // ---- primary rays through the screen-space triangle bins (DCamera::tile_ofs; renderer.cpp, refresh_tile_bins) ----------------------------
@@ -628,7 +655,7 @@ __device__ __forceinline__ uint32_t raster_tile(const DScene& sc, const DCamera&
 }
 
 // ---- trace with the reference-exact octree intersector (parity path, MI355RT_FLAG_OCTREE_SEMANTICS) ----
-template <bool PRIMARY>
+template <bool PRIMARY, bool RAYS = false>
 __global__ __launch_bounds__(kBlock) void trace_octree_kernel(DScene sc, DCamera cam, DPass ps,
                                                              const float4* __restrict__ in_q, const uint2* __restrict__ in_counts,
                                                              float4* __restrict__ hits, float* __restrict__ slot_L,
@@ -645,9 +672,9 @@ __global__ __launch_bounds__(kBlock) void trace_octree_kernel(DScene sc, DCamera
             bool on = true;
             if (PRIMARY) {
                 uint32_t pixel, sampleno;
-                primary_sample(cam, ps, film_n, chunk * ps.chunk + i, pixel, sampleno, o, d);
+                primary_sample<RAYS>(cam, ps, film_n, chunk * ps.chunk + i, pixel, sampleno, o, d);
                 r = (size_t)chunk * ps.region + i;
-                on = pixel_active(ps, cam.width, pixel);          // adaptive sampling: an inactive pixel's sample is a miss that is never traced
+                on = RAYS || pixel_active(ps, cam.width, pixel);          // adaptive sampling: an inactive pixel's sample is a miss that is never traced
             } else {
                 r = record_index(ps, chunk, i, n_rad);
                 const float4 r0 = in_q[r];
@@ -842,7 +869,9 @@ __device__ __forceinline__ bool light_proves_unoccluded(const DScene& sc, uint32
 // its (zeroed) light-term slot and is shaded no further: it resolves to black like a miss (mod.rs:99-100).
 // RASTER (primary round of the wavefront kernels, tile bins built): the closest hits of the chunk's primary rays are found right here (raster_tile) and
 // handed to the shading loop through LDS (lds_hits: one float4 per sample of a chunk) — no primary trace launch, no hit flags and no hit records in HBM.
-template <bool PRIMARY, class List, bool WALK = false, bool RASTER = false>
+// RAYS (primary round of a ray-fed pass): the ray is the caller's (primary_sample<true>), no chunk is culled, and with DPass::ray_hit
+// the final hit of every sample — after the confirm walk — is kept for resolve_rays_kernel (the hit records themselves are reused by the later rounds).
+template <bool PRIMARY, class List, bool WALK = false, bool RASTER = false, bool RAYS = false>
 __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam, const DPass& ps, uint32_t level, uint32_t chunk, const List list,
                                             const float4* __restrict__ in_q, uint32_t in_nrad, uint32_t& out_nrad, uint32_t& out_nshadow,
                                             const float4* __restrict__ hits,
@@ -856,7 +885,7 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
     {
         uint32_t n_rad = PRIMARY ? min(ps.chunk, ps.nsamples - chunk * ps.chunk) : in_nrad;
         const size_t base = (size_t)chunk * ps.region;
-        if (PRIMARY && chunk_culled(cam, ps, chunk, n_rad)) {
+        if (PRIMARY && !RAYS && chunk_culled(cam, ps, chunk, n_rad)) {
             // no hit records were written for this chunk: every sample is a miss (with cached verdicts the resolve launch knows that too and reads no slot)
             if (ps.block_culled == nullptr) for (uint32_t i = (uint32_t)lane; i < n_rad; i += 64u) sample_slot[chunk * ps.chunk + i] = kMiss;
             // high half: primary samples skipped by the frustum culling (adaptive sampling: only those of active tiles — the others are not samples of the call)
@@ -886,6 +915,7 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
             // primary round: light-term slots are handed out per chunk to the samples that hit something
             // (74 % of the primary samples miss and need neither a slot nor zero-filling)
             if (PRIMARY && i < n_rad) st1<2>(&sample_slot[chunk * ps.chunk + i], valid ? chunk * ps.chunk + pos : kMiss);
+            if constexpr (RAYS) { if (ps.ray_hit != nullptr && i < n_rad && !valid) ps.ray_hit[chunk * ps.chunk + i] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kMiss)); }
         }
         if (PRIMARY) {
             // zero the slots this chunk uses: a node whose shadow ray is blocked, or that is never
@@ -914,7 +944,7 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
                 h = RASTER ? lds_hits[j + (uint32_t)lane] : ld4<2>(&hits[base + i]);
                 if (PRIMARY) {
                     slot = chunk * ps.chunk + j + (uint32_t)lane;       // == sample_slot[chunk * ps.chunk + i]
-                    primary_sample(cam, ps, film_n, chunk * ps.chunk + i, pixel, sampleno, o, d);
+                    primary_sample<RAYS>(cam, ps, film_n, chunk * ps.chunk + i, pixel, sampleno, o, d);
                 } else {
                     const float4 r0 = ld4<2>(&in_q[base + i]), r1 = ld4<2>(&in_q[ps.qstride + base + i]);
                     o = mk3(r0.x, r0.y, r0.z); d = mk3(r0.w, r1.x, r1.y);
@@ -929,6 +959,7 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
                     h = make_float4(wt, wu, wv, __uint_as_float(wprim));
                     active = wprim != kMiss;
                 }
+                if constexpr (RAYS) { if (ps.ray_hit != nullptr) ps.ray_hit[chunk * ps.chunk + i] = active ? h : make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kMiss)); }
             }
             if (WALK) dropped += (uint32_t)__popcll(__ballot(j + (uint32_t)lane < cnt && !active));
             if (active) {
@@ -1047,7 +1078,7 @@ __device__ __forceinline__ void flush_shade_counters(DCounters* counters, uint32
     }
 }
 
-template <bool PRIMARY, bool WALK, bool RASTER = false>
+template <bool PRIMARY, bool WALK, bool RASTER = false, bool RAYS = false>
 __global__ __launch_bounds__(kBlock, PRIMARY ? (WALK ? kShadePWBlocks : kShadePBlocks) : (WALK ? kShadeSWBlocks : kShadeSBlocks)) void shade_kernel(DScene sc, DCamera cam, DPass ps, uint32_t level,
                                                       const float4* __restrict__ in_q, const uint2* __restrict__ in_counts,
                                                       const float4* __restrict__ hits,
@@ -1064,7 +1095,7 @@ __global__ __launch_bounds__(kBlock, PRIMARY ? (WALK ? kShadePWBlocks : kShadePB
     PullState pull; uint32_t chunk = 0u;
     while (pull_chunk(cursor, ps.nchunks, pull, chunk, 0u, PRIMARY ? LiveLists() : live_lists(ps))) {
         uint32_t o_rad, o_sh;
-        shade_chunk<PRIMARY, LinearList, WALK, RASTER>(sc, cam, ps, level, chunk, list, in_q, PRIMARY ? 0u : in_counts[chunk].x, o_rad, o_sh, hits, out_q, out_counts, slot_L, sample_slot, film_n, counters, acc_bounce, acc_shadow, acc_hits,
+        shade_chunk<PRIMARY, LinearList, WALK, RASTER, RAYS>(sc, cam, ps, level, chunk, list, in_q, PRIMARY ? 0u : in_counts[chunk].x, o_rad, o_sh, hits, out_q, out_counts, slot_L, sample_slot, film_n, counters, acc_bounce, acc_shadow, acc_hits,
                                                        lds_hits, (RASTER && (ps.flags & 2u)) ? &acc_tris : nullptr);      // flags & 2: MI355RT_FLAG_COUNT_STEPS
         // a chunk that leaves the primary round with rays goes on the live list of its cursor: the later launches of the pass visit only those (DPass::live)
         if (PRIMARY && ps.live != nullptr && (o_rad | o_sh) != 0u && lane_id() == 0) {
@@ -1170,6 +1201,49 @@ __global__ __launch_bounds__(256) void resolve_kernel(DPass ps, uint32_t width, 
         film_n[pixel] = n;
         if constexpr (DIRECT) { film_direct[3ull * pixel] = direct.x; film_direct[3ull * pixel + 1] = direct.y; film_direct[3ull * pixel + 2] = direct.z; }
     }
+}
+
+// ---- resolve of mi355rt_trace_rays: per-ray results instead of a film ------------------------------
+// One lane per ray of the pass (sample i IS ray i): the radiance of its tree in the reference's summation order (node_radiance, as resolve_kernel
+// evaluates it), the root light sum, and the hit the primary shade launch kept in DPass::ray_hit.  Consecutive lanes read consecutive slots' entries and
+// write consecutive 12- / 4-byte results; nothing is accumulated.  Any output may be null; tuv is left untouched on a miss (mi355rt_intersect_rays).
+__global__ __launch_bounds__(256) void resolve_rays_kernel(DPass ps, uint32_t nlights, const float* __restrict__ slot_L, const uint32_t* __restrict__ sample_slot,
+                                                          float* __restrict__ rgb, float* __restrict__ direct, float* __restrict__ tuv, uint32_t* __restrict__ prim, uint32_t* ctrl)
+{
+    // last kernel of a pass: leave the pass's work cursors zeroed for the next one (resolve_kernel)
+    if (ctrl != nullptr && blockIdx.x == 0)
+        for (uint32_t i = threadIdx.x; i < kMaxRounds * kMaxCursors * 4u; i += blockDim.x)
+            ctrl[(size_t)(i / (kMaxCursors * 4u)) * kCtrlWordsPerRound + (size_t)((i / 4u) % kMaxCursors) * kCursorStride + (i % 4u) * kConfirmCursorOffset] = 0u;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ps.nsamples) return;
+    if (rgb != nullptr || direct != nullptr) {
+        const uint32_t sl = sample_slot[i];
+        const float* L = slot_L + 3ull * (size_t)sl;       // the slot's entry of plane 0; plane q is 3 * q * nslots floats further
+        f3 c = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 0.0f);          // primary miss: RGB::black(), mod.rs:100
+        if (sl != 0xFFFFFFFFu) {
+            if (rgb != nullptr) switch (ps.recursions) {
+                case 0: c = node_radiance<0>(L, ps, nlights, 0, 0); break;
+                case 1: c = node_radiance<1>(L, ps, nlights, 0, 0); break;
+                case 2: c = node_radiance<2>(L, ps, nlights, 0, 0); break;
+                default: c = node_radiance<3>(L, ps, nlights, 0, 0); break;
+            }
+            if (direct != nullptr) d = node_radiance<0>(L, ps, nlights, 0, 0);
+        }
+        if (rgb != nullptr) { rgb[3ull * i] = c.x; rgb[3ull * i + 1] = c.y; rgb[3ull * i + 2] = c.z; }
+        if (direct != nullptr) { direct[3ull * i] = d.x; direct[3ull * i + 1] = d.y; direct[3ull * i + 2] = d.z; }
+    }
+    if (ps.ray_hit != nullptr) {
+        const float4 h = ps.ray_hit[i];
+        const uint32_t p = __float_as_uint(h.w);
+        if (prim != nullptr) prim[i] = p;
+        if (tuv != nullptr && p != kMiss) { tuv[3ull * i] = h.x; tuv[3ull * i + 1] = h.y; tuv[3ull * i + 2] = h.z; }
+    }
+}
+hipError_t launch_resolve_rays(hipStream_t stream, const DPass& ps, uint32_t nlights, const float* slot_L, const uint32_t* sample_slot,
+                               float* rgb, float* direct, float* tuv, uint32_t* prim, uint32_t* ctrl)
+{
+    hipLaunchKernelGGL(resolve_rays_kernel, dim3((ps.nsamples + 255u) / 256u ? (ps.nsamples + 255u) / 256u : 1u), dim3(256), 0, stream, ps, nlights, slot_L, sample_slot, rgb, direct, tuv, prim, ctrl);
+    return hipGetLastError();
 }
 
 // ---- one 50-row frame in ONE launch (trace_frame_additive, mod.rs:80-117) ---------------------------------
@@ -1723,7 +1797,7 @@ bool kernels_walk_wide_nodes() { return MI355RT_WIDE != 0; }
 
 static size_t stack_bytes(uint32_t depth) { return (size_t)((depth ? depth : 1u) + 1u) * kBlock * sizeof(int); }   // sentinel row + one row per level (the deepest level's row doubles as the spare row above the top)
 
-template <bool P, bool C, bool F>
+template <bool P, bool C, bool F, bool R>
 static int trace_blocks_per_cu(size_t lds)
 {
     // the occupancy query costs ~0.3 ms of host time: ask once per (kernel, device, LDS size).  Device groups launch from one
@@ -1736,26 +1810,26 @@ static int trace_blocks_per_cu(size_t lds)
     auto it = cache.find({ dev, lds });
     if (it != cache.end()) return it->second;
     int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel<P, C, F>, kBlock, lds) != hipSuccess || nb < 1) nb = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, trace_kernel<P, C, F, R>, kBlock, lds) != hipSuccess || nb < 1) nb = 1;
     nb = nb > 8 ? 8 : nb;
     cache[{ dev, lds }] = nb;
     return nb;
 }
 
-template <bool P, bool C, bool F>
+template <bool P, bool C, bool F, bool R = false>
 static hipError_t launch_trace_variant(hipStream_t stream, int num_cus, const DScene& sc, const DCamera& cam, const DPass& ps,
                                        const void* in_q, const void* in_counts, void* hits, uint32_t* cursor,
                                        float* slot_L, const uint32_t* film_n, DCounters* counters)
 {
     // persistent grid: as many blocks as the chip holds; waves pull chunks from `cursor`
     const size_t lds = stack_bytes(ps.stack_depth);
-    const int per_cu = trace_blocks_per_cu<P, C, F>(lds);
+    const int per_cu = trace_blocks_per_cu<P, C, F, R>(lds);
     // tail of every cursor's chunk sequence that is handed out in parts (pull_chunk): kTailChunksPerWave chunks per WAVE
     constexpr uint32_t kTailChunksPerWave = 2;
     DPass pt = ps;
     const uint32_t waves_per_cursor = ((uint32_t)(num_cus * per_cu) * kWavesPerBlock + kMaxCursors - 1u) / kMaxCursors;
     pt.tail_chunks = kTailChunksPerWave * waves_per_cursor;
-    hipLaunchKernelGGL((trace_kernel<P, C, F>), dim3((unsigned)(num_cus * per_cu)), dim3(kBlock), lds, stream, sc, cam, pt,
+    hipLaunchKernelGGL((trace_kernel<P, C, F, R>), dim3((unsigned)(num_cus * per_cu)), dim3(kBlock), lds, stream, sc, cam, pt,
                        (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, cursor, slot_L, film_n, counters);
     return hipGetLastError();
 }
@@ -1763,9 +1837,11 @@ static hipError_t launch_trace_variant(hipStream_t stream, int num_cus, const DS
 // confirm: the octree confirm step follows (reference-default semantics); primary rays are radiance rays either way
 hipError_t launch_trace(hipStream_t stream, int num_cus, bool primary, bool count, bool confirm, const DScene& sc, const DCamera& cam, const DPass& ps,
                         const void* in_q, const void* in_counts, void* hits, uint32_t* cursor,
-                        float* slot_L, const uint32_t* film_n, DCounters* counters)
+                        float* slot_L, const uint32_t* film_n, DCounters* counters, bool rays)
 {
 #define MI355RT_TRACE_ARGS stream, num_cus, sc, cam, ps, in_q, in_counts, hits, cursor, slot_L, film_n, counters
+    if (rays && !primary) return hipErrorInvalidValue;         // only the primary round of a pass is ray-fed
+    if (rays) return count ? launch_trace_variant<true, true, true, true>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true, true>(MI355RT_TRACE_ARGS);
     if (primary) return count ? launch_trace_variant<true, true, true>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true>(MI355RT_TRACE_ARGS);
     if (confirm) return count ? launch_trace_variant<false, true, true>(MI355RT_TRACE_ARGS) : launch_trace_variant<false, false, true>(MI355RT_TRACE_ARGS);
     return count ? launch_trace_variant<false, true, false>(MI355RT_TRACE_ARGS) : launch_trace_variant<false, false, false>(MI355RT_TRACE_ARGS);
@@ -1791,22 +1867,25 @@ hipError_t launch_cull_blocks(hipStream_t stream, const DCamera& cam, const DPas
 }
 
 hipError_t launch_trace_octree(hipStream_t stream, int num_cus, bool primary, const DScene& sc, const DCamera& cam, const DPass& ps,
-                               const void* in_q, const void* in_counts, void* hits, float* slot_L, const uint32_t* film_n)
+                               const void* in_q, const void* in_counts, void* hits, float* slot_L, const uint32_t* film_n, bool rays)
 {
+    if (rays && !primary) return hipErrorInvalidValue;
     unsigned blocks = (ps.nchunks + kWavesPerBlock - 1) / kWavesPerBlock;
     const unsigned cap = (unsigned)num_cus * 4u;
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     dim3 grid(blocks), block(kBlock);
-    if (primary) hipLaunchKernelGGL((trace_octree_kernel<true>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
+    if (rays) hipLaunchKernelGGL((trace_octree_kernel<true, true>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
+    else if (primary) hipLaunchKernelGGL((trace_octree_kernel<true>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
     else hipLaunchKernelGGL((trace_octree_kernel<false>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
     return hipGetLastError();
 }
 
 hipError_t launch_shade(hipStream_t stream, int num_cus, bool primary, bool walk, const DScene& sc, const DCamera& cam, const DPass& ps, uint32_t level,
                         const void* in_q, const void* in_counts, const void* hits, void* out_q, void* out_counts, uint32_t* cursor,
-                        float* slot_L, uint32_t* sample_slot, const uint32_t* film_n, DCounters* counters, bool raster)
+                        float* slot_L, uint32_t* sample_slot, const uint32_t* film_n, DCounters* counters, bool raster, bool rays)
 {
+    if (rays && (!primary || raster)) return hipErrorInvalidValue;      // a ray-fed primary round walks the tree: no camera, no tile bins
     // raster (primary round only): the kernel finds the primary rays' closest hits itself, through the tile bins (cam.tile_ofs), and keeps them in LDS
     const size_t lds = (size_t)ps.list_cap * kWavesPerBlock * sizeof(uint32_t) + (raster ? (size_t)ps.chunk * kWavesPerBlock * sizeof(float4) : 0);
     unsigned blocks = (ps.nchunks + kWavesPerBlock - 1) / kWavesPerBlock;
@@ -1815,7 +1894,9 @@ hipError_t launch_shade(hipStream_t stream, int num_cus, bool primary, bool walk
     if (blocks < 1) blocks = 1;
     dim3 grid(blocks), block(kBlock);
 #define MI355RT_SHADE_ARGS grid, block, lds, stream, sc, cam, ps, level, (const float4*)in_q, (const uint2*)in_counts, (const float4*)hits, (float4*)out_q, (uint2*)out_counts, cursor, slot_L, sample_slot, film_n, counters
-    if (primary && raster && walk) hipLaunchKernelGGL((shade_kernel<true, true, true>), MI355RT_SHADE_ARGS);
+    if (rays && walk) hipLaunchKernelGGL((shade_kernel<true, true, false, true>), MI355RT_SHADE_ARGS);
+    else if (rays) hipLaunchKernelGGL((shade_kernel<true, false, false, true>), MI355RT_SHADE_ARGS);
+    else if (primary && raster && walk) hipLaunchKernelGGL((shade_kernel<true, true, true>), MI355RT_SHADE_ARGS);
     else if (primary && raster) hipLaunchKernelGGL((shade_kernel<true, false, true>), MI355RT_SHADE_ARGS);
     else if (primary && walk) hipLaunchKernelGGL((shade_kernel<true, true>), MI355RT_SHADE_ARGS);
     else if (primary) hipLaunchKernelGGL((shade_kernel<true, false>), MI355RT_SHADE_ARGS);

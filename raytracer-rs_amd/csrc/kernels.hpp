@@ -8,16 +8,20 @@ namespace mi355rt {
 
 hipError_t launch_trace(hipStream_t stream, int num_cus, bool primary, bool count, bool confirm, const DScene& sc, const DCamera& cam, const DPass& ps,
                         const void* in_q, const void* in_counts, void* hits, uint32_t* cursor,
-                        float* slot_L, const uint32_t* film_n, DCounters* counters);
+                        float* slot_L, const uint32_t* film_n, DCounters* counters, bool rays = false);   // rays: the primary round of a ray-fed pass (DPass::ray_in)
 // culling verdicts of the pass's pixel blocks (DPass::block_culled): out[b] = chunk b (first sample group) is culled
 hipError_t launch_cull_blocks(hipStream_t stream, const DCamera& cam, const DPass& ps, uint32_t nblocks, uint32_t* out);
 hipError_t launch_trace_octree(hipStream_t stream, int num_cus, bool primary, const DScene& sc, const DCamera& cam, const DPass& ps,
-                               const void* in_q, const void* in_counts, void* hits, float* slot_L, const uint32_t* film_n);
+                               const void* in_q, const void* in_counts, void* hits, float* slot_L, const uint32_t* film_n, bool rays = false);
 hipError_t launch_shade(hipStream_t stream, int num_cus, bool primary, bool walk, const DScene& sc, const DCamera& cam, const DPass& ps, uint32_t level,
                         const void* in_q, const void* in_counts, const void* hits, void* out_q, void* out_counts, uint32_t* cursor,
-                        float* slot_L, uint32_t* sample_slot, const uint32_t* film_n, DCounters* counters, bool raster = false);   // raster: primary round, hits through the tile bins inside the launch
+                        float* slot_L, uint32_t* sample_slot, const uint32_t* film_n, DCounters* counters, bool raster = false,   // raster: primary round, hits through the tile bins inside the launch
+                        bool rays = false);                                                                                        // rays: as launch_trace
 hipError_t launch_resolve(hipStream_t stream, const DPass& ps, uint32_t width, uint32_t nlights, const float* slot_L, const uint32_t* sample_slot,
                           float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct, float* debug_color, uint32_t* ctrl);   // ctrl != null: zero the pass's work cursors on the way out
+// mi355rt_trace_rays: per-ray results of a ray-fed pass whose sample i is ray i; rgb / direct / tuv / prim: the pass's part of the outputs, any may be null
+hipError_t launch_resolve_rays(hipStream_t stream, const DPass& ps, uint32_t nlights, const float* slot_L, const uint32_t* sample_slot,
+                               float* rgb, float* direct, float* tuv, uint32_t* prim, uint32_t* ctrl);
 // film_direct (here and below): the handle's direct film (MI355RT_FLAG_DIRECT_FILM), null without the flag: the kernels of a three-plane film
 // one 50-row frame (1 sample per pixel) in a single launch: every wave takes a 64-sample chunk through all rounds
 bool kernels_walk_wide_nodes();      // this build's trace loops read BvhNode4 slots (MI355RT_WIDE), not BvhNode

@@ -141,6 +141,22 @@ public:
         if (mi355rt_display_histogram(h_, source, dn, &hist) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
         return hist;
     }
+    // caller-supplied rays (include/mi355rt.h), host memory.  render_rays: rays6 holds width*height*spp rays, the ray of the call's
+    // sample s of film pixel p at (s * npix + p) * 6; trace_rays: the radiance (n x 3) of n arbitrary rays, keys2 (n x (pixel, sampleno)) may be null
+    mi355rt_ray_counts render_rays(const std::vector<float>& rays6, uint32_t spp)
+    {
+        mi355rt_ray_counts c{};
+        if (mi355rt_render_rays(h_, rays6.data(), rays6.size() / 6, spp, MI355RT_RAYS_HOST, &c) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+        return c;
+    }
+    std::vector<float> trace_rays(const std::vector<float>& rays6, const uint32_t* keys2 = nullptr)
+    {
+        std::vector<float> rgb(rays6.size() / 6 * 3);
+        mi355rt_ray_outputs out{};
+        out.rgb = rgb.data();
+        if (mi355rt_trace_rays(h_, rays6.data(), keys2, rays6.size() / 6, MI355RT_RAYS_HOST, &out) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+        return rgb;
+    }
     mi355rt_handle* handle() const { return h_; }
 private:
     mi355rt_handle* h_;

@@ -737,9 +737,10 @@ void Renderer::describe_pass(DPass& ps, const Slice& sl, const uint32_t* d_rows,
 // A wavefront pass: buffers, descriptor and cursors; then round by round trace (+ confirm) (+ shade); then resolve.  Every launch goes
 // to the slice's stream.
 bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t nrows, uint32_t spp, bool explicit_sample, uint32_t epixel, uint32_t esample, uint32_t row_wrap,
-                        const uint8_t* tile_active)
+                        const uint8_t* tile_active, const RayFeed* feed)
 {
-    const uint32_t npix = explicit_sample ? 1u : nrows * cfg.width;
+    const bool free_rays = feed != nullptr && feed->mode == 2u;       // mi355rt_trace_rays: the pass's samples are `count` rays, not pixels
+    const uint32_t npix = explicit_sample ? 1u : free_rays ? feed->count : nrows * cfg.width;
     const size_t nsamples = (size_t)npix * spp;
     if (nsamples == 0) return true;
     if (!ensure_pass_capacity(sl, nsamples)) return false;
@@ -747,8 +748,14 @@ bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32
     describe_pass(ps, sl, d_rows, row0, row_wrap, npix, nsamples, kChunk, explicit_sample, epixel, esample);
     ps.tile_active = tile_active; ps.tiles_x = tiles_x();
     // the tile bins of the primary rays need a pass that walks the slice's whole row list (render(); not the odd row windows of the other callers)
-    const bool whole = !explicit_sample && d_rows == sl.d_rows.get() && row0 == 0 && nrows == sl.rows.size() && row_wrap == 0xFFFFFFFFu;
-    const DCamera cam = device_camera(whole ? &ps : nullptr, whole ? &sl.rows : nullptr);
+    // (nor a ray-fed pass: its primary rays are not the camera's, so nothing that is derived from the camera — bins, culling rectangles, cached verdicts — holds)
+    const bool whole = !feed && !explicit_sample && d_rows == sl.d_rows.get() && row0 == 0 && nrows == sl.rows.size() && row_wrap == 0xFFFFFFFFu;
+    DCamera cam = device_camera(whole ? &ps : nullptr, whole ? &sl.rows : nullptr);
+    const bool rays = feed != nullptr;
+    if (rays) {
+        cam.cull_valid = 0; cam.cull_mask = nullptr; cam.tile_ofs = nullptr; cam.tile_entries = nullptr;
+        ps.ray_in = feed->rays; ps.ray_keys = feed->keys; ps.ray_hit = feed->hit; ps.ray_mode = feed->mode; ps.ray_base = feed->base; ps.ray_npix = cfg.width * cfg.height;
+    }
     // culling verdicts per pixel block, computed once per camera and layout (DPass::block_culled) instead of per launch and chunk
     ps.block_culled = nullptr; ps.cull_blocks = 0;
     // (needs chunks that hold whole pixels — the sample group divides the chunk — and sample groups that are whole numbers of chunks: then every sample of a pixel
@@ -804,9 +811,9 @@ bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32
                 HIP_TRY(hipMemcpy(d_counters_.get(), &init, sizeof init, hipMemcpyHostToDevice));
             }
             if (mode_ == kModeOctreeWalk)
-                HIP_TRY(launch_trace_octree(st, num_cus_, r == 0, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_slot_L.get(), d_film_n_.get()));
+                HIP_TRY(launch_trace_octree(st, num_cus_, r == 0, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_slot_L.get(), d_film_n_.get(), rays && r == 0));
             else
-                HIP_TRY(launch_trace(st, num_cus_, r == 0, count, mode_ == kModeConfirm, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound, sl.d_slot_L.get(), d_film_n_.get(), d_counters_.get()));
+                HIP_TRY(launch_trace(st, num_cus_, r == 0, count, mode_ == kModeConfirm, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound, sl.d_slot_L.get(), d_film_n_.get(), d_counters_.get(), rays && r == 0));
             if (timed) { HIP_TRY(hipEventRecord(ev_pool_[ev_used_ + 1], st)); ev_used_ += 2; }
             ++launches_;
         }
@@ -837,9 +844,10 @@ bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32
                         (double)c0.t_sum_end / c0.n_waves / 100.0, (double)(c0.t_first_end - c0.t_start) / 100.0, (double)(c0.t_last_end - c0.t_start) / 100.0);
         }
         if (r <= cfg.recursions)
-            HIP_TRY(launch_shade(st, num_cus_, r == 0, shade_walks, dscene_, cam, ps, r, in_q, in_c, sl.d_hits.get(), sl.d_queue[r & 1].get(), sl.d_chunk_counts[r & 1].get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound + kShadeCursorOffset, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_n_.get(), d_counters_.get(), fuse_primary));
+            HIP_TRY(launch_shade(st, num_cus_, r == 0, shade_walks, dscene_, cam, ps, r, in_q, in_c, sl.d_hits.get(), sl.d_queue[r & 1].get(), sl.d_chunk_counts[r & 1].get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound + kShadeCursorOffset, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_n_.get(), d_counters_.get(), fuse_primary, rays && r == 0));
     }
-    HIP_TRY(launch_resolve(st, ps, cfg.width, nlights_, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_film_direct_.get(), d_debug_color_.get(), sl.d_ctrl.get()));
+    if (free_rays) HIP_TRY(launch_resolve_rays(st, ps, nlights_, sl.d_slot_L.get(), sl.d_sample_slot.get(), feed->rgb, feed->direct, feed->tuv, feed->prim, sl.d_ctrl.get()));
+    else HIP_TRY(launch_resolve(st, ps, cfg.width, nlights_, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_film_direct_.get(), d_debug_color_.get(), sl.d_ctrl.get()));
     sl.ctrl_clean = true;
     return true;
 }
@@ -1091,7 +1099,7 @@ bool Renderer::render(uint32_t spp, bool wait)
 
 // The body of a frame: plan the passes of every slice (halving them while the device cannot hold their buffers) and queue them, each slice on its
 // own stream, forked behind `fork` on the main stream.  render() runs one; render_adaptive() one per round, with the round's tile mask.
-bool Renderer::enqueue_frame(uint32_t spp, hipEvent_t fork, const uint8_t* tile_active)
+bool Renderer::enqueue_frame(uint32_t spp, hipEvent_t fork, const uint8_t* tile_active, const RayFeed* feed)
 {
     const uint32_t nrows = (uint32_t)owned_rows.size();
     if (nrows && spp) {
@@ -1109,7 +1117,7 @@ bool Renderer::enqueue_frame(uint32_t spp, hipEvent_t fork, const uint8_t* tile_
         // The pass buffers (two ray queues, hit records, light terms: ~410 B per sample) are sized for the
         // largest pass.  If the device cannot hold them (another tenant, a 16 GB part), halve the pass and
         // try again; results do not depend on how samples are batched into passes.
-        struct PassDesc { uint32_t r0, nr, kk; };
+        struct PassDesc { uint32_t r0, nr, kk, s0; };          // s0: the call's sample number of the pass's first sample
         std::vector<PassDesc> plan[kMaxSlices];
         for (;;) {
             bool ok = true;
@@ -1131,7 +1139,7 @@ bool Renderer::enqueue_frame(uint32_t spp, hipEvent_t fork, const uint8_t* tile_
                 ok = ensure_pass_capacity(sl, (size_t)rows_per_pass * cfg.width * std::min(k, spp));
                 for (uint32_t done = 0; ok && done < spp; done += k)
                     for (uint32_t r0 = 0; r0 < snrows; r0 += rows_per_pass)
-                        plan[s].push_back(PassDesc{ r0, std::min(rows_per_pass, snrows - r0), std::min(k, spp - done) });
+                        plan[s].push_back(PassDesc{ r0, std::min(rows_per_pass, snrows - r0), std::min(k, spp - done), done });
             }
             if (ok) break;
             if (!alloc_failed_ || cfg.samples_per_pass || target <= ((size_t)64 << 10)) return false;
@@ -1152,7 +1160,9 @@ bool Renderer::enqueue_frame(uint32_t spp, hipEvent_t fork, const uint8_t* tile_
                 if (p >= plan[s].size()) continue;
                 any = true;
                 const PassDesc& d = plan[s][p];
-                if (!run_pass(slices_[s], slices_[s].d_rows.get(), d.r0, d.nr, d.kk, false, 0, 0, 0xFFFFFFFFu, tile_active)) return false;
+                RayFeed f{};
+                if (feed) { f = *feed; f.base = d.s0; }
+                if (!run_pass(slices_[s], slices_[s].d_rows.get(), d.r0, d.nr, d.kk, false, 0, 0, 0xFFFFFFFFu, tile_active, feed ? &f : nullptr)) return false;
             }
             if (!any) break;
         }
@@ -1370,6 +1380,7 @@ bool Renderer::film_clear()
     if (!settle_speculation()) return false;
     const size_t npix = (size_t)cfg.width * cfg.height;
     std::fill(ldr_dirty_.begin(), ldr_dirty_.end(), (uint8_t)1);     // unsampled rows read back white (NaN -> 255)
+    caller_ray_film_ = false;
     if (cfg.stripe_world > 1) {
         // a striped handle only ever writes its own rows (the others stay as created: zero): one launch over them instead of three
         // whole-film memsets — 20 us of a 3.3 ms frame on one rank of eight
@@ -1392,6 +1403,7 @@ bool Renderer::film_put(const FilmPlanes& in, bool add)
     if (!bind()) return false;
     if (!in.sum || !in.sumsq || !in.n || (in.direct != nullptr) != (bool)d_film_direct_) { last_error = "internal: film_put planes do not match the film"; return false; }
     if (!settle_speculation()) return false;
+    if (!add) caller_ray_film_ = false;                               // the film is the caller's planes now
     const size_t npix = (size_t)cfg.width * cfg.height;
     DeviceBuffer<uint8_t> stage;
     HIP_TRY(stage.alloc(npix * (in.direct ? 40 : 28), &hbm_bytes_));
@@ -1431,6 +1443,77 @@ bool Renderer::intersect(const float* rays6, size_t n, float* tuv, uint32_t* pri
     }
     HIP_TRY(hipStreamSynchronize(stream_));
     return true;
+}
+
+// ---- caller-supplied rays (include/mi355rt.h) ---------------------------------------------------------------------------
+// mi355rt_trace_rays: the rays as ray-fed passes of one sample each on slice 0 (the main stream), as many as the pass buffers need.  Host memory is staged
+// through temporary device buffers in the caller's own layout (rays, keys, and whatever outputs are asked for; tuv goes up first, a miss leaves it as it
+// was); device memory is read and written in place.  A read-out like debug_sample: no film, no camera, no row state changes.
+bool Renderer::trace_rays(const float* rays6, const uint32_t* keys2, size_t n, bool device, const mi355rt_ray_outputs& out)
+{
+    if (!begin_call()) return false;                                  // settles a speculative frame; a queued frame is ahead on the same stream
+    if (n > 0xFFFFFFFFull) { last_error = "mi355rt_trace_rays: n does not fit 32 bits"; return false; }
+    DeviceBuffer<float> s_rays, s_rgb, s_direct, s_tuv; DeviceBuffer<uint32_t> s_keys, s_prim; DeviceBuffer<float4> s_hit;
+    const float* d_rays = rays6; const uint32_t* d_keys = keys2;
+    float* d_rgb = out.rgb; float* d_direct = out.direct; float* d_tuv = out.tuv; uint32_t* d_prim = out.prim;
+    if (!device && n) {
+        HIP_TRY(s_rays.alloc(n * 24, &hbm_bytes_));
+        HIP_TRY(hipMemcpyAsync(s_rays.get(), rays6, n * 24, hipMemcpyHostToDevice, stream_));
+        d_rays = s_rays.get();
+        if (keys2) { HIP_TRY(s_keys.alloc(n * 8, &hbm_bytes_)); HIP_TRY(hipMemcpyAsync(s_keys.get(), keys2, n * 8, hipMemcpyHostToDevice, stream_)); d_keys = s_keys.get(); }
+        if (out.rgb) { HIP_TRY(s_rgb.alloc(n * 12, &hbm_bytes_)); d_rgb = s_rgb.get(); }
+        if (out.direct) { HIP_TRY(s_direct.alloc(n * 12, &hbm_bytes_)); d_direct = s_direct.get(); }
+        if (out.tuv) { HIP_TRY(s_tuv.alloc(n * 12, &hbm_bytes_)); HIP_TRY(hipMemcpyAsync(s_tuv.get(), out.tuv, n * 12, hipMemcpyHostToDevice, stream_)); d_tuv = s_tuv.get(); }
+        if (out.prim) { HIP_TRY(s_prim.alloc(n * 4, &hbm_bytes_)); d_prim = s_prim.get(); }
+    }
+    // rays per pass: what the frame's passes hold (enqueue_frame), config.samples_per_pass images' worth when that is set; halved while the device cannot hold the buffers
+    size_t per = (size_t)144 << 20;
+    if (const char* e = getenv("MI355RT_PASS_SAMPLES")) { long v = atol(e); if (v >= 1024) per = (size_t)v; }
+    if (cfg.samples_per_pass) per = std::max<size_t>(1, (size_t)cfg.samples_per_pass * cfg.width * cfg.height);
+    per = std::min(per, std::max<size_t>(n, 1));
+    Slice& sl = slices_[0];
+    while (n && !ensure_pass_capacity(sl, per)) {
+        if (!alloc_failed_ || per <= 1024) return false;
+        (void)hipGetLastError();
+        per /= 2;
+    }
+    if (n && (out.tuv || out.prim)) HIP_TRY(s_hit.alloc(per * sizeof(float4), &hbm_bytes_));
+    for (size_t at = 0; at < n; at += per) {
+        const size_t cnt = std::min(per, n - at);
+        RayFeed f{};
+        f.mode = 2u; f.rays = d_rays + 6 * at; f.keys = d_keys ? d_keys + 2 * at : nullptr; f.base = (uint32_t)at; f.count = (uint32_t)cnt; f.hit = s_hit.get();
+        f.rgb = d_rgb ? d_rgb + 3 * at : nullptr; f.direct = d_direct ? d_direct + 3 * at : nullptr; f.tuv = d_tuv ? d_tuv + 3 * at : nullptr; f.prim = d_prim ? d_prim + at : nullptr;
+        if (!run_pass(sl, nullptr, 0, 0, 1, false, 0, 0, 0xFFFFFFFFu, nullptr, &f)) return false;
+    }
+    if (!device && n) {
+        if (out.rgb) HIP_TRY(hipMemcpyAsync(out.rgb, d_rgb, n * 12, hipMemcpyDeviceToHost, stream_));
+        if (out.direct) HIP_TRY(hipMemcpyAsync(out.direct, d_direct, n * 12, hipMemcpyDeviceToHost, stream_));
+        if (out.tuv) HIP_TRY(hipMemcpyAsync(out.tuv, d_tuv, n * 12, hipMemcpyDeviceToHost, stream_));
+        if (out.prim) HIP_TRY(hipMemcpyAsync(out.prim, d_prim, n * 4, hipMemcpyDeviceToHost, stream_));
+    }
+    return end_call(n, true);                                         // waits: the staging (and the caller's buffers) are free again
+}
+
+// mi355rt_render_rays: mi355rt_render whose passes read their primary rays from the caller's buffer, indexed by the CALL's sample number (enqueue_frame hands
+// every pass its base).  Only the rays of owned rows are read, so a host buffer is staged whole but a striped handle never looks at the rest.
+bool Renderer::render_rays(const float* rays6, uint32_t spp, bool device)
+{
+    if (!begin_call()) return false;
+    const size_t nrays = (size_t)cfg.width * cfg.height * spp;
+    DeviceBuffer<float> s_rays;
+    const float* d_rays = rays6;
+    if (!device) {
+        HIP_TRY(s_rays.alloc(nrays * 24, &hbm_bytes_));
+        HIP_TRY(hipMemcpyAsync(s_rays.get(), rays6, nrays * 24, hipMemcpyHostToDevice, stream_));
+        d_rays = s_rays.get();
+    }
+    HIP_TRY(hipEventRecord(slices_[0].done, stream_));                // the other slices fork behind the upload (slice 0 runs on the main stream; its `done` event is free here)
+    RayFeed f{};
+    f.mode = 1u; f.rays = d_rays;
+    caller_ray_film_ = true;
+    if (!enqueue_frame(spp, slices_[0].done, nullptr, &f)) return false;
+    for (uint32_t r : owned_rows) ldr_dirty_[r] = 1;
+    return end_call((uint64_t)owned_rows.size() * cfg.width * spp, true);
 }
 
 bool Renderer::debug_numerics(const float* a, const float* b, size_t n, float* q, float* r, float* p)

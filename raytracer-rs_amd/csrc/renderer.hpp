@@ -39,6 +39,10 @@ public:
     struct FilmPlanes { const float* sum; const float* sumsq; const uint32_t* n; const float* direct; };
     bool film_put(const FilmPlanes& in, bool add);
     bool intersect(const float* rays6, size_t n, float* tuv, uint32_t* prim, uint8_t* blocked);
+    // caller-supplied rays; the caller has checked the arguments.  device: every pointer is device memory of this handle's device
+    bool trace_rays(const float* rays6, const uint32_t* keys2, size_t n, bool device, const mi355rt_ray_outputs& out);
+    bool render_rays(const float* rays6, uint32_t spp, bool device);
+    bool caller_ray_film() const { return caller_ray_film_; }           // the film holds samples of mi355rt_render_rays: the camera's guides do not describe it
     bool synchronize();                                                 // wait for everything queued on this handle
     // ---- multi-GPU gather of the packed u32 stripes into the root's frame.  Two transports end in the
     // same place: the in-process device group (hipMemcpyPeerAsync, csrc/group.cpp) and RCCL between processes (comm_*).
@@ -142,10 +146,15 @@ private:
     bool ensure_pass_capacity(Slice& sl, size_t nsamples);
     void free_pass_buffers();
     bool assign_slice_rows(uint32_t nslices);
+    // A ray-fed pass (DPass::ray_in ...).  mode 1: the film's pixels with the caller's rays (base: the call's sample number of the pass's first
+    // sample, set per pass by enqueue_frame); mode 2: `count` free rays, one sample each, resolved into the out pointers (device memory, the pass's part)
+    struct RayFeed { uint32_t mode; const float* rays; const uint32_t* keys; uint32_t base; uint32_t count; float4* hit; float* rgb; float* direct; float* tuv; uint32_t* prim; };
     bool run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t nrows, uint32_t spp, bool explicit_sample, uint32_t epixel, uint32_t esample, uint32_t row_wrap = 0xFFFFFFFFu,
-                  const uint8_t* tile_active = nullptr);
-    // the owned rows x spp as wavefront passes on the slices (pass planning, OOM halving), forked behind `fork` on the main stream; tile_active: DPass::tile_active
-    bool enqueue_frame(uint32_t spp, hipEvent_t fork, const uint8_t* tile_active);
+                  const uint8_t* tile_active = nullptr, const RayFeed* feed = nullptr);
+    // the owned rows x spp as wavefront passes on the slices (pass planning, OOM halving), forked behind `fork` on the main stream; tile_active: DPass::tile_active;
+    // feed (mode 1): the frame's primary rays are the caller's
+    bool enqueue_frame(uint32_t spp, hipEvent_t fork, const uint8_t* tile_active, const RayFeed* feed = nullptr);
+    bool caller_ray_film_ = false;
     bool join_slices();                                                 // the main stream waits for the slices of the call in flight
     bool adaptive_verdict(const mi355rt_adaptive_config& ac, uint32_t& tiles, uint64_t& pixels);    // d_tile_active_ <- the verdict of the current film
     DeviceBuffer<uint8_t> d_tile_active_;                               // adaptive sampling: one byte per tile (DPass::tile_active)

@@ -41,6 +41,10 @@ pub const DEFAULT_TRIANGLES_PER_LEAF: usize = 70;
 /// every sample's root light term, which the two direct-film entries below read
 pub const MI355RT_FLAG_DIRECT_FILM: u32 = 128;
 #[allow(dead_code)] #[repr(C)] pub struct mi355rt_denoise_config { pub iterations: u32, pub normal_power_log2: u32, pub sigma_luminance: f32, pub sigma_depth: f32, pub sigma_albedo: f32 }
+pub const MI355RT_RAYS_HOST: u32 = 0;
+pub const MI355RT_RAYS_DEVICE: u32 = 1;
+/// outputs of mi355rt_trace_rays: any pointer may be null, not all of them
+#[allow(dead_code)] #[repr(C)] pub struct mi355rt_ray_outputs { pub rgb: *mut f32, pub direct: *mut f32, pub tuv: *mut f32, pub prim: *mut u32 }
 extern "C" {
     fn mi355rt_default_config(cfg: *mut mi355rt_config);
     fn mi355rt_create(scene: *const mi355rt_scene_desc, cfg: *const mi355rt_config, out: *mut *mut mi355rt_handle) -> c_int;
@@ -57,6 +61,10 @@ extern "C" {
     fn mi355rt_film_load(h: *mut mi355rt_handle, path: *const c_char, add: c_int) -> c_int;
     fn mi355rt_film_file_info(path: *const c_char, out: *mut u32) -> c_int;
     fn mi355rt_get_denoised_pixels_split(h: *mut mi355rt_handle, cfg: *const mi355rt_denoise_config, rgb: *mut f32, packed: *mut u32, npix: usize) -> c_int;
+    // caller-supplied rays (declared for a caller that brings its own camera model; this shim calls neither): where_ = MI355RT_RAYS_HOST / _DEVICE,
+    // counts = a mi355rt_ray_counts or null
+    fn mi355rt_trace_rays(h: *mut mi355rt_handle, rays6: *const f32, keys2: *const u32, n: usize, where_: u32, out: *const mi355rt_ray_outputs) -> c_int;
+    fn mi355rt_render_rays(h: *mut mi355rt_handle, rays6: *const f32, nrays: usize, spp: u32, where_: u32, counts: *mut std::ffi::c_void) -> c_int;
     fn mi355rt_camera_move_rel(h: *mut mi355rt_handle, x: f32, y: f32, z: f32) -> c_int;
     fn mi355rt_camera_add_x_angle(h: *mut mi355rt_handle, radians: f32) -> c_int;
     fn mi355rt_camera_add_y_angle(h: *mut mi355rt_handle, radians: f32) -> c_int;
