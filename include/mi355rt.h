@@ -148,6 +148,8 @@ typedef struct mi355rt_ray_counts {
                               * sum of delta s_memrealtime (100 MHz) of all waves of the call's trace launches; 0 when not measured */
     uint64_t shadow_skipped; /* shadow rays (counted in `shadow`) never traced: the depth cube map around their light proves that nothing lies
                               * between the shaded point and the light, so no intersector could block them; traced shadow rays = shadow - shadow_skipped */
+    uint64_t bounce_skipped; /* reflection rays (counted in `bounce`) never traced: the direction mask of the triangle they start on proves that they
+                              * hit nothing (they contribute black, mod.rs:160-171); traced reflection rays = bounce - bounce_skipped */
 } mi355rt_ray_counts;
 
 void mi355rt_default_config(mi355rt_config* cfg);
@@ -569,6 +571,12 @@ int mi355rt_debug_speculation(const mi355rt_handle* h, uint64_t out[2]);
  * distance from `light` to any of the ntri triangles (tri_verts: ntri x 9 floats) padded by `pad`, +inf where no triangle is seen; *nearest the
  * distance to the nearest triangle.  Exists so that the bound can be checked against brute force without a GPU. */
 int mi355rt_debug_light_map(const float* tri_verts, uint32_t ntri, const float light[3], double pad, uint32_t res, float* out_dist2, double* nearest);
+/* The reflection masks the library builds per triangle (host code, no device needed): out_words receives ntri records of info[0] 32-bit words — 6 * bins^2
+ * direction bits (face-major cube map, a SET bit means "trace"), then v0.xyz and the guard's height margin as f32 bits; NULL: only info is filled.
+ * info: [0] words per triangle, [1] build ms, [2] work units, [3] clear bits, [4] minimum cosine, [5] angular pad, [6] barycentric guard margin,
+ * [7] 1 when a mask was built (0: over work_budget, or no triangles).  work_budget 0: unlimited.  On ENTRY info[4] and info[5] choose the minimum cosine and
+ * the angular pad to build with (0: the library's own; other values serve the census of the margins only — the kernels know the shipped ones). */
+int mi355rt_debug_reflect_mask(const float* tri_verts, uint32_t ntri, double pad, uint32_t bins, uint64_t work_budget, uint32_t* out_words, double info[8]);
 
 /* Test hook (host only, no device): the 4-wide tree of 48-byte nodes that experiment builds of the kernels walk (-DMI355RT_WIDE=1; bvh.hpp,
  * BvhNode4: 8-bit child boxes in a per-node frame), built from the ntri triangles like mi355rt_create builds the binary tree, then checked by a
@@ -583,6 +591,12 @@ int mi355rt_debug_wide_bvh(const float* tri_verts, uint32_t ntri, uint32_t out[8
  * build with its uploads and read-back), [7] host octree build time inside create (microseconds; 0 with
  * MI355RT_FLAG_TRUE_CLOSEST_HIT) */
 int mi355rt_accel_stats(const mi355rt_handle* h, uint32_t out[8]);
+/* The direction masks that prove reflection rays free (one per triangle, built inside create): out[0] bins per cube-face edge (0: no mask — switched off
+ * with MI355RT_NO_REFLECT_MASK, over the work budget MI355RT_REFLECT_MASK_WORK, or recursions == 0), [1] build time in ms, [2] share of clear bits, [3] bytes. */
+int mi355rt_reflect_mask_info(const mi355rt_handle* h, double out[4]);
+/* MI355RT_FLAG_COUNT_STEPS: the rays the trace launches of the last call took from their queues — primary rays that walk the tree, reflection rays and
+ * shadow rays that were actually made (bounce - bounce_skipped, shadow - shadow_skipped), counted by the trace kernels themselves. */
+int mi355rt_debug_rays_read(const mi355rt_handle* h, uint64_t* out);
 /* which builder made the BVH: out[0] 1 = the device (MI355RT_FLAG_DEVICE_LBVH served the scene), 0 = the host;
  * out[1] device time of the build kernels + sort (HIP events, microseconds; 0 for a host build) */
 int mi355rt_bvh_build_info(const mi355rt_handle* h, uint32_t out[2]);

@@ -82,12 +82,13 @@ class RayCounts(C.Structure):
         ("trace_ms", C.c_double), ("total_ms", C.c_double),
         ("trace_secondary_ms", C.c_double), ("trace_secondary_launches", C.c_uint64), ("shader_clock_mhz", C.c_double),
         ("shadow_skipped", C.c_uint64),
+        ("bounce_skipped", C.c_uint64),
     ]
 
     def as_dict(self):
         d = {name: getattr(self, name) for name, _ in self._fields_}
         d["total_rays"] = self.primary + self.bounce + self.shadow
-        d["traced_rays"] = d["total_rays"] - self.primary_culled - self.shadow_skipped
+        d["traced_rays"] = d["total_rays"] - self.primary_culled - self.shadow_skipped - self.bounce_skipped
         return d
 
 
@@ -212,6 +213,9 @@ ABI = [
     ("mi355rt_tree_nodes", C.c_uint32, [_H]),
     ("mi355rt_debug_speculation", C.c_int, [_H, C.POINTER(C.c_uint64)]),
     ("mi355rt_debug_light_map", C.c_int, [_F, C.c_uint32, _F, C.c_double, C.c_uint32, _F, C.POINTER(C.c_double)]),
+    ("mi355rt_debug_reflect_mask", C.c_int, [_F, C.c_uint32, C.c_double, C.c_uint32, C.c_uint64, _U, C.POINTER(C.c_double)]),
+    ("mi355rt_reflect_mask_info", C.c_int, [_H, C.POINTER(C.c_double)]),
+    ("mi355rt_debug_rays_read", C.c_int, [_H, C.POINTER(C.c_uint64)]),
     ("mi355rt_debug_wide_bvh", C.c_int, [_F, C.c_uint32, _U]),
     ("mi355rt_accel_stats", C.c_int, [_H, _U]),
     ("mi355rt_octree_stats", C.c_int, [_H, _U]),
@@ -731,6 +735,18 @@ class RayTracer:
         return dict(nodes=int(out[0]), leaves=int(out[1]), max_depth=int(out[2]), max_leaf=int(out[3]),
                     node_bytes=int(out[4]), tri_bytes=int(out[5]), bvh_build_ms=int(out[6]) / 1000.0, octree_build_ms=int(out[7]) / 1000.0)
 
+    def reflect_mask_info(self):
+        """the direction masks that prove reflection rays free: bins per cube-face edge (0: none), build time, share of clear bits, device bytes"""
+        out = (C.c_double * 4)()
+        self._check(lib().mi355rt_reflect_mask_info(self._h, out))
+        return dict(bins=int(out[0]), build_ms=float(out[1]), clear_share=float(out[2]), bytes=int(out[3]))
+
+    def debug_rays_read(self):
+        """FLAG_COUNT_STEPS: rays the trace launches of the last call took from their queues, counted by the trace kernels"""
+        out = C.c_uint64(0)
+        self._check(lib().mi355rt_debug_rays_read(self._h, C.byref(out)))
+        return int(out.value)
+
     def bvh_build_info(self):
         out = np.zeros(2, np.uint32)
         self._check(lib().mi355rt_bvh_build_info(self._h, _up(out)))
@@ -835,6 +851,22 @@ def debug_light_map(tri_verts, light, pad, res):
     if code != 0:
         raise RuntimeError("mi355rt_debug_light_map failed: %d" % code)
     return out, nearest.value
+
+
+def debug_reflect_mask(tri_verts, pad, bins=8, work_budget=0, min_cos=0.0, pad_angle=0.0):
+    """(words[ntri, stride] or None, info): the per-triangle direction masks the library builds for the reflection rays (host code; include/mi355rt.h).
+    info: stride, build_ms, work, clear_bits, min_cos, pad_angle, bary_margin, built"""
+    v = np.ascontiguousarray(tri_verts, np.float32).reshape(-1, 9)
+    info = (C.c_double * 8)()
+    info[4], info[5] = float(min_cos), float(pad_angle)          # 0: the library's own margins
+    stride = 6 * bins * bins // 32 + 4
+    out = np.zeros((v.shape[0], stride), np.uint32)
+    code = lib().mi355rt_debug_reflect_mask(_fp(v), v.shape[0], float(pad), int(bins), int(work_budget), _up(out), info)
+    if code != 0:
+        raise RuntimeError("mi355rt_debug_reflect_mask failed: %d" % code)
+    d = dict(stride=int(info[0]), build_ms=float(info[1]), work=int(info[2]), clear_bits=int(info[3]), min_cos=float(info[4]), pad_angle=float(info[5]),
+             bary_margin=float(info[6]), built=bool(info[7]))
+    return (out if d["built"] else None), d
 
 
 def debug_wide_bvh(tri_verts):

@@ -7,6 +7,7 @@
 #include <vector>
 #include "display.hpp"
 #include "lightmap.hpp"
+#include "reflmask.hpp"
 #include "../../include/mi355rt.h"
 #include "group.hpp"
 #include "renderer.hpp"
@@ -671,6 +672,17 @@ int mi355rt_debug_light_map(const float* tri_verts, uint32_t ntri, const float l
     if (nearest) *nearest = lm.nearest;
     return MI355RT_OK;
 }
+int mi355rt_debug_reflect_mask(const float* tri_verts, uint32_t ntri, double pad, uint32_t bins, uint64_t work_budget, uint32_t* out_words, double info[8])
+{
+    if ((ntri && !tri_verts) || !info || !(pad >= 0.0)) return MI355RT_E_INVALID;
+    mi355rt::ReflMask m;
+    const double min_cos = info[4] > 0.0 ? info[4] : mi355rt::kReflMinCos, pad_angle = info[5] > 0.0 ? info[5] : mi355rt::kReflPadAngle;     // in: the census's margins
+    const bool built = ntri != 0 && mi355rt::build_reflect_mask(tri_verts, ntri, pad, bins, work_budget ? work_budget : ~0ull, m, min_cos, pad_angle);
+    info[0] = (double)mi355rt::refl_mask_stride(bins); info[1] = m.build_ms; info[2] = (double)m.work; info[3] = (double)m.clear_bits;
+    info[4] = min_cos; info[5] = pad_angle; info[6] = (double)mi355rt::kReflBary; info[7] = built ? 1.0 : 0.0;
+    if (built && out_words) std::memcpy(out_words, m.words.data(), m.words.size() * sizeof(uint32_t));
+    return MI355RT_OK;
+}
 
 namespace {
 // bounds of every vertex below a reference of the wide tree; counts what the walk reaches and which child boxes fail to hold their subtree
@@ -752,6 +764,18 @@ int mi355rt_bvh_build_info(const mi355rt_handle* h, uint32_t out[2])
 {
     if (!h || !out) return MI355RT_E_INVALID;
     out[0] = h->r->bvh_on_device_ ? 1u : 0u; out[1] = (uint32_t)(h->r->lbvh_device_ms_ * 1000.0);
+    return MI355RT_OK;
+}
+int mi355rt_debug_rays_read(const mi355rt_handle* h, uint64_t* out)
+{
+    if (!h || !out) return MI355RT_E_INVALID;
+    *out = h->r->rays_read_;
+    return MI355RT_OK;
+}
+int mi355rt_reflect_mask_info(const mi355rt_handle* h, double out[4])
+{
+    if (!h || !out) return MI355RT_E_INVALID;
+    std::memcpy(out, h->r->reflect_mask_info_, sizeof h->r->reflect_mask_info_);
     return MI355RT_OK;
 }
 int mi355rt_octree_stats(const mi355rt_handle* h, uint32_t out[8])

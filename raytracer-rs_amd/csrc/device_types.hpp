@@ -46,6 +46,8 @@ struct DScene {
     const uint32_t* tri_home; // per triangle: the one octree leaf that lists it, or 0xFFFFFFFF when several do
     const float* light_maps;  // per light a depth cube map [6][res][res]: lower bound of the squared distance from the light to anything seen in the texel's directions (lightmap.hpp); null: none
     uint32_t light_map_res;   // texels per face edge (0: no maps)
+    const uint32_t* refl_mask; // per triangle (original order) refl_stride words: 6 * refl_bins^2 direction bits of a cube map (SET: a reflection ray that starts on the triangle in that direction is traced), then v0.xyz and the guard's height margin (reflmask.hpp); null: none
+    uint32_t refl_bins, refl_stride;
     int32_t root;
     uint32_t nlights;
     uint32_t ntri;
@@ -167,6 +169,7 @@ struct DCounters {            // one set per render call, zeroed at its start
     unsigned long long t_sum_cycles, t_sum_real;                                            // COUNT mode: summed s_memtime ticks (shader cycles) of the waves, against t_sum_end in s_memrealtime ticks
     unsigned long long visits_below[6];                                          // COUNT mode: inner-node visits with node index < 64, 128, 256, 512, 1024, 2048 (what an LDS copy of the first N nodes would serve)
     unsigned long long refills, refill_passes, refill_rays;                    // COUNT mode: refill sections entered, passes through the assignment code, rays handed out
+    unsigned long long bounce_skipped;            // reflection rays the direction mask of their triangle proved free (never made; counted in `bounce` by the host)
 };
 
 }  // namespace mi355rt

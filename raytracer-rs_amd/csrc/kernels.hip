@@ -39,6 +39,7 @@
 #include "device_math.hpp"
 #include "device_types.hpp"
 #include "kernels.hpp"
+#include "reflmask.hpp"
 #include "traverse.hpp"
 
 namespace mi355rt {
@@ -861,6 +862,39 @@ __device__ __forceinline__ bool light_proves_unoccluded(const DScene& sc, uint32
     return (l2 * 0.98011f < bound) & (l2 * 1.0002e-4f < lt.tail2);
 }
 
+// Does the reflection ray (bo, bd) that starts on triangle `prim` provably hit nothing?  The triangle's direction mask (reflmask.hpp) has a CLEAR bit for a bin of
+// the cube map around it only if every direction of the bin rises above the triangle's plane and misses every other triangle from every point of the triangle
+// the guard admits.  The guard: the hit's barycentrics h.y, h.z lie inside the triangle by kReflBary — the reference's hit point is a rounded f32 point, and half
+// of the margin covers its distance from the exact one — and the ACTUAL f32 origin bo lies above the triangle's plane by the record's height margin (measured from
+// bo - v0, so that the magnitudes stay local): hp = o + t d may lie below the plane, and a ray that starts there can hit its own triangle or a coplanar
+// neighbour, which the reference reports.  A failed guard or a set bit only means the ray is traced.  Bin arithmetic: light_proves_unoccluded's.
+// rec: the first word of the triangle's record, or kMiss when the barycentric half of the guard failed (reflection_record: worked out once per hit, while the hit
+// record is still in registers).
+__device__ __forceinline__ uint32_t reflection_record(const DScene& sc, const float4 h)
+{
+    if (sc.refl_mask == nullptr || !((h.y > kReflBary) & (h.z > kReflBary) & (h.y + h.z < 1.0f - kReflBary))) return kMiss;
+    return __float_as_uint(h.w) * sc.refl_stride;
+}
+__device__ __forceinline__ bool reflection_proves_miss(const DScene& sc, uint32_t rec_first, const f3 n, const f3 bo, const f3 bd)
+{
+    if (rec_first == kMiss) return false;
+    const float ax = fabsf(bd.x), ay = fabsf(bd.y), az = fabsf(bd.z);
+    uint32_t m; float vm, va, vb;
+    if (ax >= ay && ax >= az) { m = 0u; vm = bd.x; va = bd.y; vb = bd.z; }
+    else if (ay >= az) { m = 1u; vm = bd.y; va = bd.x; vb = bd.z; }
+    else { m = 2u; vm = bd.z; va = bd.x; vb = bd.y; }
+    const float am = fabsf(vm);
+    if (!(am > 0.0f)) return false;
+    const uint32_t B = sc.refl_bins;
+    const float fB = (float)B, u = div_rn(va, am), v = div_rn(vb, am);
+    const int i = min(max((int)((u * 0.5f + 0.5f) * fB), 0), (int)B - 1), j = min(max((int)((v * 0.5f + 0.5f) * fB), 0), (int)B - 1);
+    const uint32_t bit = ((2u * m + (vm < 0.0f ? 1u : 0u)) * B + (uint32_t)i) * B + (uint32_t)j;
+    const uint32_t* __restrict__ rec = sc.refl_mask + rec_first;
+    if ((rec[bit >> 5] >> (bit & 31u)) & 1u) return false;
+    const float4 g = *(const float4*)(rec + (sc.refl_stride - kReflGuardWords));          // v0.xyz, height margin (records are 16-byte aligned)
+    return dot3(sub3(bo, mk3(g.x, g.y, g.z)), n) > g.w;
+}
+
 // ---- shade: hit records -> light terms, shadow rays and reflection rays -----------------------------
 // Shade the hits of one chunk (one wave): see the header of this file.
 // in_nrad: radiance rays of the chunk in in_q (ignored for PRIMARY); out_nrad / out_nshadow: what was appended to out_q.
@@ -932,12 +966,12 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
             }
         }
         __builtin_amdgcn_wave_barrier();
-        uint32_t out_front = 0u, out_back = 0u, dropped = 0u, skipped = 0u;
+        uint32_t out_front = 0u, out_back = 0u, dropped = 0u, skipped = 0u, bskipped = 0u;
         for (uint32_t j = 0; j < cnt; j += 64u) {
             bool active = j + (uint32_t)lane < cnt;
             const bool in_batch = active;                      // PRIMARY: owns the light-term slot chunk * ps.chunk + j + lane, shaded or not
             f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1), hp = mk3(0, 0, 0), n = mk3(0, 0, 1);
-            uint32_t slot = 0u, node = 0u, pixel = 0u, sampleno = 0u, geom = 0u;
+            uint32_t slot = 0u, node = 0u, pixel = 0u, sampleno = 0u, geom = 0u, refl_rec = kMiss;
             float4 h = make_float4(0, 0, 0, 0);
             if (active) {
                 const uint32_t i = list[j + (uint32_t)lane];
@@ -967,6 +1001,7 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
                 const float4 nn = ((const float4*)sc.normals)[__float_as_uint(h.w)];   // calc_normal, mod.rs:198-205 (precomputed)
                 n = mk3(nn.x, nn.y, nn.z);
                 geom = __float_as_uint(nn.w);
+                if (level < ps.recursions) refl_rec = reflection_record(sc, h);
             }
             // ---- shade() set-up per light, mod.rs:214-257; the shadow ray carries the finished term
             for (uint32_t li = 0; li < sc.nlights; ++li) {
@@ -1031,13 +1066,21 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
                         bd0 = mk3(tv0.x, tv0.y, tv0.z); bo0 = add3(hp, sscale(0.00001f, bd0));   // mod.rs:192-193
                         bd1 = mk3(tv1.x, tv1.y, tv1.z); bo1 = add3(hp, sscale(0.00001f, bd1));
                     }
+                    // a reflection ray its triangle's direction mask proves free is never made: it would hit nothing and contribute black (mod.rs:160-171), and
+                    // the light terms of its subtree were zero-filled by the primary round
+                    bool make0 = active, make1 = active && two;
+                    if (sc.refl_mask != nullptr) {
+                        if (make0) make0 = !reflection_proves_miss(sc, refl_rec, n, bo0, bd0);
+                        if (make1) make1 = !reflection_proves_miss(sc, refl_rec, n, bo1, bd1);
+                        bskipped += (uint32_t)__popcll(__ballot(active && !make0)) + (uint32_t)__popcll(__ballot(active && two && !make1));
+                    }
                     // Where the batch's reflection rays go in the chunk's region: grouped by the OCTANT of their direction.  The rays of a batch start at
                     // neighbouring hit points; those that also agree in the signs of their direction make the same near / far choice at every node, so they
                     // walk the tree together for longer, and lanes of a quad that fetch the same node cost the memory pipe one access instead of four
                     // (profiles/r03_notes.md: all rays of a chunk in one octant would take 14 % off the secondary trace launches).  Eight ballots per child;
                     // the order of the records inside a region means nothing to anyone else.
                     uint32_t pos[2] = { 0u, 0u };
-                    const uint32_t key0 = active ? dir_bin(bd0) : kSortBins, key1 = (active && two) ? dir_bin(bd1) : kSortBins;
+                    const uint32_t key0 = make0 ? dir_bin(bd0) : kSortBins, key1 = make1 ? dir_bin(bd1) : kSortBins;
                     for (uint32_t b = 0; b < kSortBins; ++b) {
                         const unsigned long long m0 = __ballot(key0 == b), m1 = __ballot(key1 == b);
                         if (key0 == b) pos[0] = out_front + (uint32_t)__popcll(m0 & lanemask_lt());
@@ -1049,7 +1092,7 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
                         const f3 bo = w ? bo1 : bo0, bd = w ? bd1 : bd0;
                         const uint32_t child_node = w ? child1 : child0;
                         const uint32_t oi = pos[w];
-                        if (active && oi + out_back < ps.region + 0u) {
+                        if ((w ? make1 : make0) && oi + out_back < ps.region + 0u) {
                             const size_t r = base + oi;
                             st4<2>(&out_q[r], make_float4(bo.x, bo.y, bo.z, bd.x));
                             st4<2>(&out_q[ps.qstride + r], make_float4(bd.y, bd.z, __uint_as_float(slot), __uint_as_float(((level + 1u) << 4) | (child_node << 8))));
@@ -1062,7 +1105,7 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
         if (out_front + out_back > ps.region) { if (lane == 0) counters->overflow = 1u; out_front = 0u; out_back = 0u; }
         if (out_counts != nullptr && lane == 0) out_counts[chunk] = make_uint2(out_front, out_back);     // fused launch: null, the counts travel in registers
         out_nrad = out_front; out_nshadow = out_back;
-        acc_bounce += out_front; acc_shadow += out_back + ((unsigned long long)skipped << 32); acc_hits += cnt - dropped;     // high half of acc_shadow: shadow rays never made
+        acc_bounce += out_front + ((unsigned long long)bskipped << 32); acc_shadow += out_back + ((unsigned long long)skipped << 32); acc_hits += cnt - dropped;     // high half of acc_shadow: shadow rays never made
     }
 }
 
@@ -1070,7 +1113,8 @@ __device__ __forceinline__ void flush_shade_counters(DCounters* counters, uint32
 {
     if (lane_id() == 0) {
         DCounters* cs = &counters[wave % kShards];
-        if (acc_bounce) atomicAdd(&cs->bounce, acc_bounce);
+        if (acc_bounce & 0xFFFFFFFFull) atomicAdd(&cs->bounce, acc_bounce & 0xFFFFFFFFull);
+        if (acc_bounce >> 32) atomicAdd(&cs->bounce_skipped, acc_bounce >> 32);                   // high half of acc_bounce: reflection rays never made
         if (acc_shadow & 0xFFFFFFFFull) atomicAdd(&cs->shadow, acc_shadow & 0xFFFFFFFFull);
         if (acc_shadow >> 32) atomicAdd(&cs->shadow_skipped, acc_shadow >> 32);
         if (acc_hits & 0xFFFFFFFFull) atomicAdd(&cs->primary_hits, acc_hits & 0xFFFFFFFFull);

@@ -2,6 +2,7 @@
 #include "renderer.hpp"
 #include "display.hpp"
 #include "lightmap.hpp"
+#include "reflmask.hpp"
 #include <algorithm>
 #include <array>
 #include <chrono>
@@ -233,6 +234,26 @@ bool Renderer::init(const SceneData& scene, std::string& err, int& code)
         if (getenv("MI355RT_DEBUG_CULL")) fprintf(stderr, "[mi355rt] light maps: %zu lights, %u texels per face edge, %.1f ms\n", scene.lights.size(), light_map_res, light_map_ms_);
     }
     if (!upload(d_lights, lights.data(), lights.size() * sizeof(DLight))) return bail();
+    // Direction masks of the triangles (reflmask.hpp): reflection rays they prove free are never made.  Far occluders are padded like the lights' maps are; a
+    // build that would take more than MI355RT_REFLECT_MASK_WORK work units (tree nodes visited + cone tests; thai2 takes under 1 % of the default) is abandoned.
+    uint32_t* d_refl_mask = nullptr; uint32_t refl_bins = 0, refl_stride = 0;
+    if (ntri > 0 && cfg.recursions > 0 && !getenv("MI355RT_NO_REFLECT_MASK")) {
+        double diag2 = 0.0;
+        { float mn[3] = { 3e38f, 3e38f, 3e38f }, mx[3] = { -3e38f, -3e38f, -3e38f };
+          for (size_t i = 0; i < scene.tri_verts.size(); ++i) { const int a = (int)(i % 3); mn[a] = std::min(mn[a], scene.tri_verts[i]); mx[a] = std::max(mx[a], scene.tri_verts[i]); }
+          for (int a = 0; a < 3; ++a) diag2 += ((double)mx[a] - mn[a]) * ((double)mx[a] - mn[a]); }
+        uint64_t budget = 4000000000ull;
+        if (const char* e = getenv("MI355RT_REFLECT_MASK_WORK")) budget = std::strtoull(e, nullptr, 10);
+        ReflMask rm;
+        if (std::isfinite(diag2) && build_reflect_mask(scene.tri_verts.data(), ntri, 2e-4 * std::sqrt(diag2) + 1e-7, kReflBins, budget, rm)) {
+            if (!upload(d_refl_mask, rm.words.data(), rm.words.size() * sizeof(uint32_t))) return bail();
+            refl_bins = rm.bins; refl_stride = rm.stride;
+            reflect_mask_info_[2] = (double)rm.clear_bits / ((double)ntri * 6.0 * rm.bins * rm.bins);
+            reflect_mask_info_[3] = (double)(rm.words.size() * sizeof(uint32_t));
+        }
+        reflect_mask_info_[0] = (double)refl_bins; reflect_mask_info_[1] = rm.build_ms;
+        if (getenv("MI355RT_DEBUG_CULL")) fprintf(stderr, "[mi355rt] reflection masks: %u bins per face edge, %.1f ms, %llu work units, %.3f of the bits clear\n", refl_bins, rm.build_ms, (unsigned long long)rm.work, reflect_mask_info_[2]);
+    }
     std::vector<DTexture> tex(std::max<size_t>(scene.textures.size(), 1));
     std::vector<float> texels;
     for (size_t i = 0; i < scene.textures.size(); ++i) {
@@ -247,6 +268,7 @@ bool Renderer::init(const SceneData& scene, std::string& err, int& code)
     dscene_.lights = d_lights; dscene_.textures = d_tex; dscene_.texels = d_texels; dscene_.table = d_table;
     dscene_.root = bvh.root; dscene_.nlights = nlights_; dscene_.ntri = ntri;
     dscene_.light_maps = d_light_maps; dscene_.light_map_res = light_map_res;
+    dscene_.refl_mask = d_refl_mask; dscene_.refl_bins = refl_bins; dscene_.refl_stride = refl_stride;
     dscene_.oct_nodes = nullptr; dscene_.oct_leaf_tris = nullptr; dscene_.prim_tris = nullptr; dscene_.oct_info = nullptr; dscene_.tri_home = nullptr; dscene_.oct_single_leaf = 0u;
     std::memset(dscene_.oct_root, 0, sizeof dscene_.oct_root);
     // Intersector semantics.  Default: the reference's default intersector (OctTreeIntersector), served by
@@ -874,13 +896,15 @@ bool Renderer::fetch_counts(uint64_t primary, bool timed_call)
         const DCounters& s = shard[i];
         c.bounce += s.bounce; c.shadow += s.shadow; c.primary_hits += s.primary_hits;
         c.nodes_visited += s.nodes_visited; c.tris_tested += s.tris_tested; c.overflow |= s.overflow;
-        c.inner_execs += s.inner_execs; c.leaf_execs += s.leaf_execs; c.primary_culled += s.primary_culled; c.shadow_skipped += s.shadow_skipped;
-        c.t_sum_cycles += s.t_sum_cycles; c.t_sum_real += s.t_sum_real;
+        c.inner_execs += s.inner_execs; c.leaf_execs += s.leaf_execs; c.primary_culled += s.primary_culled; c.shadow_skipped += s.shadow_skipped; c.bounce_skipped += s.bounce_skipped;
+        c.t_sum_cycles += s.t_sum_cycles; c.t_sum_real += s.t_sum_real; c.refill_rays += s.refill_rays;
         for (int k = 0; k < 6; ++k) c.visits_below[k] += s.visits_below[k];
     }
     counts = mi355rt_ray_counts{};
-    counts.primary = primary; counts.bounce = c.bounce; counts.shadow = c.shadow + c.shadow_skipped; counts.primary_hits = c.primary_hits;
+    counts.primary = primary; counts.bounce = c.bounce + c.bounce_skipped; counts.shadow = c.shadow + c.shadow_skipped; counts.primary_hits = c.primary_hits;
     counts.shadow_skipped = c.shadow_skipped;     // shadow rays of mod.rs:226 that were never made: the light's depth map proved them free
+    counts.bounce_skipped = c.bounce_skipped;     // reflection rays of mod.rs:156-158 that were never made: their triangle's direction mask proved that they hit nothing
+    rays_read_ = c.refill_rays;                   // MI355RT_FLAG_COUNT_STEPS: what the trace launches took from their queues (mi355rt_debug_rays_read)
     counts.nodes_visited = c.nodes_visited; counts.tris_tested = c.tris_tested; counts.trace_launches = launches_;
     counts.inner_execs = c.inner_execs; counts.leaf_execs = c.leaf_execs; counts.primary_culled = c.primary_culled;
     if (getenv("MI355RT_DEBUG_UTIL") && c.nodes_visited)

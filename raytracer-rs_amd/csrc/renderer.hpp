@@ -103,6 +103,8 @@ public:
     uint32_t oct_stats_[8] = { 0 };       // the reference's octree: nodes, inner, leaves, empty, depth, triangle refs
     double build_ms_[2] = { 0.0, 0.0 };   // build times inside create (wall): BVH (host binned SAH, or the device build), octree (SAT, host)
     double light_map_ms_ = 0.0;           // build time of the lights' depth cube maps inside create
+    uint64_t rays_read_ = 0;              // MI355RT_FLAG_COUNT_STEPS: rays the trace launches of the last call took from their queues (DCounters::refill_rays)
+    double reflect_mask_info_[4] = { 0.0, 0.0, 0.0, 0.0 };   // the triangles' direction masks: bins per face edge (0: none), build ms inside create, share of clear bits, bytes on the device
     bool bvh_on_device_ = false;          // MI355RT_FLAG_DEVICE_LBVH and the device build served the scene
     bool wide_ = false;                   // the device holds the 4-wide tree (bvh.nodes4): this build's kernels walk it
     uint32_t traversal_rows() const { return (wide_ ? bvh.stack_need4 : bvh.max_depth) + 1u; }       // stack rows the trace loops need (kernels.hip, stack_bytes)
