@@ -547,6 +547,61 @@ int mi355rt_trace_rays(mi355rt_handle* h, const float* rays6, const uint32_t* ke
                        size_t n, uint32_t where, const mi355rt_ray_outputs* out);
 int mi355rt_render_rays(mi355rt_handle* h, const float* rays6, size_t nrays, uint32_t spp, uint32_t where, mi355rt_ray_counts* counts);
 
+/* ---- lens models: depth of field and orthographic views made on the device (no reference counterpart).  A handle has a LENS: the ray
+ * generator of mi355rt_render.  PINHOLE is the reference's camera and the state of every handle at creation; with it every entry launches the kernels and
+ * returns the bits it always did.  THIN and ORTHO are raytracer_rs_amd.cameras.thin_lens and .orthographic made by the kernels themselves, in registers,
+ * bit for bit: no 24-byte-per-ray buffer, and — because the library knows each pixel's centre ray — guides, so the denoised, split and display read-outs
+ * work on such a film.
+ *
+ * THE RAY OF A SAMPLE.  Sample `sampleno` of pixel p: (w0, w1, w2, w3) = pcg4d(p, sampleno, 0, seed); xi1 = u01(w0), xi2 = u01(w1) (the jitter, as always),
+ * l1 = u01(w2), l2 = u01(w3) (the lens sample; nothing else uses these words).  rot, orient, max_xy: what mi355rt_camera_get returns; origin[k] =
+ * 0 * orient[k] + 0 * orient[4 + k] + 0 * orient[8 + k] + 1 * orient[12 + k].  Every expression is f32, unfused, evaluated as written (raytracer_rs_amd/cameras.py
+ * is the statement; k = 0, 1, 2):
+ *   PINHOLE  x = p % width, y = p / width with MI355RT_FLAG_FIX_ROW_INDEX, else p / height (the reference's row)
+ *            dir_x = -max_x + (2 * max_x) * ((x + xi1) / width), dir_y = -max_y + (2 * max_y) * ((y + xi2) / height)
+ *            d[k] = dir_x * rot[k] + (-dir_y) * rot[4 + k] + 1 * rot[8 + k] + 1 * rot[12 + k],  o[k] = origin[k]
+ *   THIN     (o, d) as PINHOLE; lx = 2 * l1 - 1, ly = 2 * l2 - 1; off[k] = radius * (lx * rot[k] + ly * rot[4 + k]);
+ *            o'[k] = o[k] + off[k], d'[k] = focus * d[k] - off[k]: a point of a square lens of half-width radius, through o + focus * d, which stays sharp
+ *   ORTHO    hw = width_world * 0.5, hh = hw * (height / width); x = p % width, y = p / width (always the true row)
+ *            sx = -hw + (2 * hw) * ((x + xi1) / width), sy = -hh + (2 * hh) * ((y + xi2) / height)
+ *            o[k] = (origin[k] + sx * rot[k]) + (-sy) * rot[4 + k],  d[k] = rot[8 + k] + rot[12 + k]
+ * A THIN lens with radius 0 and focus 1 makes the pinhole's rays but is NOT folded into the pinhole path: it runs the lens kernels.
+ *
+ * mi355rt_set_lens.  Only the fields the model reads are checked: THIN needs radius finite and >= 0 and focus finite and > 0, ORTHO needs width_world finite
+ * and > 0; an unknown model is an error.  A failure returns MI355RT_E_INVALID, names the field in mi355rt_last_error and changes nothing.  Setting a lens
+ * keeps the film, as a camera move does (that the film belongs to the view stays the caller's word), and does not touch the caller-ray mark, the counters or
+ * mi355rt_current_row.  The guides' cache is keyed by (camera, FIX_ROW_INDEX bit, lens).  On a device group (config.device_count > 1) a model other than
+ * PINHOLE is refused with MI355RT_E_INVALID.
+ *
+ * WITH A LENS OTHER THAN PINHOLE
+ *   mi355rt_render, mi355rt_render_async   render through it; film and direct film accumulate as always, sample s of pixel p has key (p, film_n[p] + s); striped
+ *                                          handles render their rows.  primary_culled == 0 and the primary round walks the tree: the culling rectangles, the
+ *                                          coverage mask and the tile bins describe pinhole rays and are not used.  The ordering contract of render_async holds.
+ *   mi355rt_get_guides, mi355rt_get_denoised_pixels[_split], display sources 1 and 2
+ *                                          use the lens's guide ray: the lens ray with xi1 = xi2 = l1 = l2 = 0.5, intersected as mi355rt_intersect_rays would.
+ *                                          Everything else of GUIDES and FILTER is as written above.
+ *   mi355rt_trace_frame_additive           returns 0, and
+ *   mi355rt_render_adaptive                returns MI355RT_E_INVALID; both messages name mi355rt_set_lens (their fused launch and tile masks rest on the pinhole path).
+ *   mi355rt_camera_get_ray, mi355rt_trace_rays, mi355rt_render_rays are unaffected.
+ *
+ * mi355rt_lens_ray: HOST code — no device, no handle — the lens ray from the outputs of mi355rt_camera_get; flags: bit 0 = MI355RT_FLAG_FIX_ROW_INDEX.  The lens
+ * is validated as by mi355rt_set_lens; NULL pointers, width or height 0 or pixel >= width * height give MI355RT_E_INVALID, the argument named in
+ * mi355rt_last_error(NULL), ray6 untouched.
+ * mi355rt_lens_rays: the rays the next mi355rt_render(spp) would take under the handle's lens (PINHOLE included), in mi355rt_render_rays layout: ray
+ * (s * npix + p) has key (p, film_n[p] + s); every pixel is written, owned or not.  `where` as for mi355rt_trace_rays (HOST: staged through a temporary
+ * device buffer of 24 bytes per ray).  nrays must equal width * height * spp, spp >= 1; else MI355RT_E_INVALID and nothing is written.  A read-out by the
+ * rules of mi355rt_trace_rays: queued work is settled first, nothing of the handle changes.  Not available on a device group. */
+#define MI355RT_LENS_PINHOLE 0u   /* the reference's camera: everything as it is without a lens */
+#define MI355RT_LENS_THIN    1u   /* cameras.thin_lens(radius, focus) */
+#define MI355RT_LENS_ORTHO   2u   /* cameras.orthographic(width_world) */
+typedef struct mi355rt_lens { uint32_t model; float radius, focus, width_world; } mi355rt_lens;
+void mi355rt_lens_default(mi355rt_lens* lens);            /* PINHOLE, radius 0, focus 1, width_world 0 */
+int  mi355rt_set_lens(mi355rt_handle* h, const mi355rt_lens* lens);
+int  mi355rt_get_lens(const mi355rt_handle* h, mi355rt_lens* lens);
+int  mi355rt_lens_ray(const float rot16[16], const float orient16[16], const float max_xy[2], uint32_t width, uint32_t height, uint32_t flags,
+                      const mi355rt_lens* lens, uint32_t pixel, float xi1, float xi2, float l1, float l2, float ray6[6]);
+int  mi355rt_lens_rays(mi355rt_handle* h, uint32_t spp, uint32_t where, float* rays6, size_t nrays);
+
 /* SampleGenerator table, sample_generator.rs:15-24: 65 536 x 3 floats */
 int mi355rt_get_sample_table(const mi355rt_handle* h, float* out);
 /* Per-node direct-light terms of one primary sample, computed on the device by the same

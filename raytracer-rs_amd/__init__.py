@@ -150,6 +150,18 @@ class RayOutputs(C.Structure):
 
 RAY_OUTPUTS = ("rgb", "direct", "tuv", "prim")
 
+LENS_PINHOLE, LENS_THIN, LENS_ORTHO = 0, 1, 2      # MI355RT_LENS_*
+LENS_MODELS = {"pinhole": LENS_PINHOLE, "thin": LENS_THIN, "ortho": LENS_ORTHO}
+
+
+class Lens(C.Structure):
+    """mi355rt_lens: the ray generator of render() (include/mi355rt.h, "lens models"): model LENS_*, radius and focus (THIN), width_world (ORTHO)"""
+    _fields_ = [("model", C.c_uint32), ("radius", C.c_float), ("focus", C.c_float), ("width_world", C.c_float)]
+
+    def as_dict(self):
+        return dict(model={v: k for k, v in LENS_MODELS.items()}.get(self.model, self.model), radius=self.radius, focus=self.focus, width_world=self.width_world)
+
+
 # every symbol include/mi355rt.h declares: (name, restype, argtypes)
 _H = C.c_void_p
 _F = C.POINTER(C.c_float)
@@ -206,6 +218,11 @@ ABI = [
     ("mi355rt_occluded_rays", C.c_int, [_H, _F, C.c_size_t, C.POINTER(C.c_uint8)]),
     ("mi355rt_trace_rays", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(RayOutputs)]),
     ("mi355rt_render_rays", C.c_int, [_H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(RayCounts)]),
+    ("mi355rt_lens_default", None, [C.POINTER(Lens)]),
+    ("mi355rt_set_lens", C.c_int, [_H, C.POINTER(Lens)]),
+    ("mi355rt_get_lens", C.c_int, [_H, C.POINTER(Lens)]),
+    ("mi355rt_lens_ray", C.c_int, [_F, _F, _F, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Lens), C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, _F]),
+    ("mi355rt_lens_rays", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
     ("mi355rt_get_sample_table", C.c_int, [_H, _F]),
     ("mi355rt_debug_sample", C.c_int, [_H, C.c_uint32, C.c_uint32, _F, _F, C.c_size_t]),
     ("mi355rt_debug_numerics", C.c_int, [_H, _F, _F, C.c_size_t, _F, _F, _F]),
@@ -345,6 +362,30 @@ def display_config(**kw):
     return cfg
 
 
+def make_lens(model="pinhole", radius=None, focus=None, width_world=None):
+    """A Lens: mi355rt_lens_default with the given fields replaced; model: "pinhole", "thin", "ortho" or a LENS_* number.  Not validated here."""
+    l = Lens()
+    lib().mi355rt_lens_default(C.byref(l))
+    l.model = LENS_MODELS[model] if isinstance(model, str) else int(model)
+    for k, v in (("radius", radius), ("focus", focus), ("width_world", width_world)):
+        if v is not None:
+            setattr(l, k, v)
+    return l
+
+
+def lens_ray(cam, width, height, lens, pixel, xi1=0.5, xi2=0.5, l1=0.5, l2=0.5, flags=0):
+    """mi355rt_lens_ray (host code, no device): float32[6] (pos3, dir3), the ray of `pixel` under `lens` (a Lens, see make_lens) for the jitter
+    (xi1, xi2) and the lens sample (l1, l2); cam = (rot16, orient16, max_xy) as RayTracer.camera.matrices() returns them; flags bit 0:
+    FLAG_FIX_ROW_INDEX.  The defaults give the guide ray of the pixel.  Raises RuntimeError naming the argument for an invalid one."""
+    rot, orient, mx = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in cam)
+    if rot.size != 16 or orient.size != 16 or mx.size != 2:
+        raise ValueError("cam must be (rot16, orient16, max_xy) as RayTracer.camera.matrices() returns them")
+    out = np.zeros(6, np.float32)
+    if lib().mi355rt_lens_ray(_fp(rot), _fp(orient), _fp(mx), int(width), int(height), int(flags), C.byref(lens), int(pixel), xi1, xi2, l1, l2, _fp(out)) != 0:
+        raise RuntimeError((lib().mi355rt_last_error(None) or b"").decode() or "mi355rt_lens_ray failed")
+    return out
+
+
 def display_auto_exposure(hist, key=0.18, low=0.0, high=1.0):
     """mi355rt_display_auto_exposure (host code, no device): the exposure (numpy float32) a luminance histogram gives; hist: a LuminanceHistogram,
     or the dict RayTracer.display_histogram() / display.histogram() return.  Raises RuntimeError naming the field for an invalid key, low or high."""
@@ -449,9 +490,10 @@ class Film:
 class RayTracer:
     """raytracer/mod.rs:32-47.  Construct through create_raytracer* below."""
 
-    def __init__(self, handle, keepalive=None):
+    def __init__(self, handle, keepalive=None, device_index=0):
         self._h = C.c_void_p(handle)
         self._keep = keepalive
+        self.device_index = int(device_index)     # config.device: the HIP device of the handle (of device 0 of a group)
         L = lib()
         self.width = L.mi355rt_width(self._h)
         self.height = L.mi355rt_height(self._h)
@@ -697,6 +739,41 @@ class RayTracer:
         self._check(lib().mi355rt_render_rays(self._h, addr, n, spp, RAYS_DEVICE if dev else RAYS_HOST, C.byref(rc)))
         return rc
 
+    # --- lens models (include/mi355rt.h, "lens models")
+    def set_lens(self, model="pinhole", radius=None, focus=None, width_world=None):
+        """mi355rt_set_lens: the ray generator of render().  "thin" (radius, focus): depth of field, cameras.thin_lens made on the device; "ortho"
+        (width_world): cameras.orthographic; "pinhole": the reference's camera, the state at creation.  A Lens is accepted in place of the model name.
+        Keeps the film.  Under a lens the guides, and so the denoised and display read-outs, describe the lens's view; render_adaptive and
+        trace_frame_additive refuse.  Raises RuntimeError naming the field for an invalid lens (nothing changes then)."""
+        l = model if isinstance(model, Lens) else make_lens(model, radius, focus, width_world)
+        self._check(lib().mi355rt_set_lens(self._h, C.byref(l)))
+
+    @property
+    def lens(self):
+        """mi355rt_get_lens: the handle's Lens"""
+        l = Lens()
+        self._check(lib().mi355rt_get_lens(self._h, C.byref(l)))
+        return l
+
+    def lens_rays(self, spp, device=False):
+        """mi355rt_lens_rays: float32 (width * height * spp, 6), the rays the next render(spp) would take under the handle's lens, in render_rays layout
+        (row s * npix + p: key (p, film_n[p] + s)).  device=False: a numpy array; device=True (or a torch device): a torch tensor on the handle's GPU,
+        as render_rays accepts one — the start of a caller's own ray generator (distortion, stereo offsets) without a host array."""
+        spp = int(spp)
+        if spp < 1:
+            raise ValueError("spp must be >= 1")
+        n = self.width * self.height * spp
+        if device is False or device is None:
+            out = np.zeros((n, 6), np.float32)
+            self._check(lib().mi355rt_lens_rays(self._h, spp, RAYS_HOST, out.ctypes.data, n))
+            return out
+        import torch
+        dev = torch.device("cuda", self.device_index) if device is True else torch.device(device)
+        out = torch.zeros((n, 6), dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()           # the zero fill has finished: the library's stream knows nothing of torch's
+        self._check(lib().mi355rt_lens_rays(self._h, spp, RAYS_DEVICE, out.data_ptr(), n))
+        return out
+
     def occluded_rays(self, rays6):
         rays6 = np.ascontiguousarray(rays6, np.float32).reshape(-1, 6)
         n = rays6.shape[0]
@@ -766,10 +843,10 @@ class RayTracer:
         return lib().mi355rt_current_row(self._h)
 
 
-def _finish(code, handle, keep=None):
+def _finish(code, handle, keep=None, cfg=None):
     if code != 0:
         raise RuntimeError((lib().mi355rt_last_error(None) or b"").decode() or "mi355rt error %d" % code)
-    return RayTracer(handle.value, keep)
+    return RayTracer(handle.value, keep, cfg.device if cfg is not None else 0)
 
 
 def create_raytracer(collada_doc, triangles_per_leaf, width, height, data_dir=None, **cfg_kw):
@@ -778,7 +855,7 @@ def create_raytracer(collada_doc, triangles_per_leaf, width, height, data_dir=No
     doc = collada_doc.encode() if isinstance(collada_doc, str) else bytes(collada_doc)
     h = C.c_void_p()
     code = lib().mi355rt_create_from_collada_str(doc, len(doc), data_dir.encode() if data_dir else None, C.byref(cfg), C.byref(h))
-    return _finish(code, h)
+    return _finish(code, h, None, cfg)
 
 
 def create_raytracer_from_file(collada_filename, triangles_per_leaf, width, height, **cfg_kw):
@@ -786,14 +863,14 @@ def create_raytracer_from_file(collada_filename, triangles_per_leaf, width, heig
     cfg = default_config(width, height, triangles_per_leaf=triangles_per_leaf, **cfg_kw)
     h = C.c_void_p()
     code = lib().mi355rt_create_from_collada_file(str(collada_filename).encode(), C.byref(cfg), C.byref(h))
-    return _finish(code, h)
+    return _finish(code, h, None, cfg)
 
 
 def create_raytracer_from_scene_file(scene_filename, triangles_per_leaf, width, height, **cfg_kw):
     cfg = default_config(width, height, triangles_per_leaf=triangles_per_leaf, **cfg_kw)
     h = C.c_void_p()
     code = lib().mi355rt_create_from_scene_file(str(scene_filename).encode(), C.byref(cfg), C.byref(h))
-    return _finish(code, h)
+    return _finish(code, h, None, cfg)
 
 
 def create_raytracer_from_arrays(scene, triangles_per_leaf, width, height, **cfg_kw):
@@ -830,7 +907,7 @@ def create_raytracer_from_arrays(scene, triangles_per_leaf, width, height, **cfg
     sd.camera_fov_deg = float(scene["camera_fov"])
     h = C.c_void_p()
     code = lib().mi355rt_create(C.byref(sd), C.byref(cfg), C.byref(h))
-    return _finish(code, h, keep)
+    return _finish(code, h, keep, cfg)
 
 
 def film_file_info(path):

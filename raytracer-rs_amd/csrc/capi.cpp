@@ -10,6 +10,7 @@
 #include "reflmask.hpp"
 #include "../../include/mi355rt.h"
 #include "group.hpp"
+#include "lens.hpp"
 #include "renderer.hpp"
 
 using namespace mi355rt;
@@ -159,6 +160,30 @@ bool ray_call_ok(mi355rt_handle* h, const char* fn, const float* rays6, size_t n
     return false;
 }
 
+// the checks of a lens (include/mi355rt.h, "LENS MODELS"): only the fields the model reads; null: fine, else the message that names the field
+const char* lens_error(const mi355rt_lens* l)
+{
+    if (!l) return "lens is NULL";
+    if (l->model == MI355RT_LENS_PINHOLE) return nullptr;
+    if (l->model == MI355RT_LENS_THIN) {
+        if (!std::isfinite(l->radius) || l->radius < 0.0f) return "lens: radius must be finite and >= 0";
+        if (!std::isfinite(l->focus) || !(l->focus > 0.0f)) return "lens: focus must be finite and > 0";
+        return nullptr;
+    }
+    if (l->model == MI355RT_LENS_ORTHO) {
+        if (!std::isfinite(l->width_world) || !(l->width_world > 0.0f)) return "lens: width_world must be finite and > 0";
+        return nullptr;
+    }
+    return "lens: unknown model (MI355RT_LENS_PINHOLE, MI355RT_LENS_THIN or MI355RT_LENS_ORTHO)";
+}
+// the guard of the entries whose launches rest on the pinhole path (the fused 50-row frame, the adaptive sampler's tile masks): false under any other lens
+bool pinhole_lens_ok(mi355rt_handle* h, const char* fn)
+{
+    if (!h->r->has_lens()) return true;
+    h->r->last_error = std::string(fn) + ": not available under a lens other than MI355RT_LENS_PINHOLE; mi355rt_set_lens(PINHOLE) first";
+    return false;
+}
+
 // ---- film files (include/mi355rt.h, "FILM FILE"): a 64-byte little-endian header, then the planes n, sum, sumsq [, direct]
 constexpr size_t kFilmHeaderBytes = 64;
 constexpr char kFilmMagic[9] = "MI355FLM";
@@ -276,7 +301,11 @@ void mi355rt_destroy(mi355rt_handle* h) { delete h; }
 
 const char* mi355rt_last_error(const mi355rt_handle* h) { return h ? h->g->last_error().c_str() : g_create_error.c_str(); }
 
-uint32_t mi355rt_trace_frame_additive(mi355rt_handle* h) { return h ? h->g->trace_frame_additive() : 0u; }
+uint32_t mi355rt_trace_frame_additive(mi355rt_handle* h)
+{
+    if (!h || !pinhole_lens_ok(h, "mi355rt_trace_frame_additive")) return 0u;
+    return h->g->trace_frame_additive();
+}
 
 int mi355rt_render(mi355rt_handle* h, uint32_t spp, mi355rt_ray_counts* counts)
 {
@@ -310,7 +339,7 @@ void mi355rt_adaptive_default_config(mi355rt_adaptive_config* cfg)
 
 int mi355rt_render_adaptive(mi355rt_handle* h, const mi355rt_adaptive_config* cfg, mi355rt_adaptive_stats* stats)
 {
-    if (!adaptive_args_ok(h, cfg) || !camera_film_ok(h, "mi355rt_render_adaptive")) return MI355RT_E_INVALID;
+    if (!adaptive_args_ok(h, cfg) || !camera_film_ok(h, "mi355rt_render_adaptive") || !pinhole_lens_ok(h, "mi355rt_render_adaptive")) return MI355RT_E_INVALID;
     mi355rt_adaptive_stats st{};
     const bool ok = h->r->render_adaptive(*cfg, st);
     if (stats) *stats = st;
@@ -632,6 +661,61 @@ int mi355rt_render_rays(mi355rt_handle* h, const float* rays6, size_t nrays, uin
     const bool ok = h->r->render_rays(rays6, spp, where == MI355RT_RAYS_DEVICE);
     if (counts) *counts = h->r->counts;
     return ok ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+void mi355rt_lens_default(mi355rt_lens* lens)
+{
+    if (!lens) return;
+    lens->model = MI355RT_LENS_PINHOLE; lens->radius = 0.0f; lens->focus = 1.0f; lens->width_world = 0.0f;
+}
+
+int mi355rt_set_lens(mi355rt_handle* h, const mi355rt_lens* lens)
+{
+    if (!h) return MI355RT_E_INVALID;
+    const char* e = lens_error(lens);
+    if (!e && lens->model != MI355RT_LENS_PINHOLE && h->g->size() > 1) e = "mi355rt_set_lens: a lens other than MI355RT_LENS_PINHOLE is not available on a device group (config.device_count > 1)";
+    if (e) { h->r->last_error = e; return MI355RT_E_INVALID; }
+    return h->r->set_lens(*lens) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_get_lens(const mi355rt_handle* h, mi355rt_lens* lens)
+{
+    if (!h || !lens) return MI355RT_E_INVALID;
+    *lens = h->r->lens();
+    return MI355RT_OK;
+}
+
+int mi355rt_lens_ray(const float rot16[16], const float orient16[16], const float max_xy[2], uint32_t width, uint32_t height, uint32_t flags,
+                     const mi355rt_lens* lens, uint32_t pixel, float xi1, float xi2, float l1, float l2, float ray6[6])
+{
+    const char* e = nullptr;
+    if (!rot16) e = "mi355rt_lens_ray: rot16 is NULL";
+    else if (!orient16) e = "mi355rt_lens_ray: orient16 is NULL";
+    else if (!max_xy) e = "mi355rt_lens_ray: max_xy is NULL";
+    else if (!ray6) e = "mi355rt_lens_ray: ray6 is NULL";
+    else if (width == 0 || height == 0) e = "mi355rt_lens_ray: width and height must be non-zero";
+    else if ((uint64_t)pixel >= (uint64_t)width * height) e = "mi355rt_lens_ray: pixel must be < width * height";
+    else e = lens_error(lens);
+    if (e) return bad(e);
+    // orientation * (0, 0, 0, 1), camera.rs:88, in vecmath's operand order
+    float origin[3];
+    for (int k = 0; k < 3; ++k) origin[k] = 0.0f * orient16[k] + 0.0f * orient16[4 + k] + 0.0f * orient16[8 + k] + 1.0f * orient16[12 + k];
+    const DLens dl = lens_derive(lens->model, lens->radius, lens->focus, lens->width_world, rot16, max_xy[0], max_xy[1], width, height);
+    lens_ray(rot16, origin, max_xy[0], max_xy[1], width, height, flags, dl, pixel, xi1, xi2, l1, l2, ray6[0], ray6[1], ray6[2], ray6[3], ray6[4], ray6[5]);
+    return MI355RT_OK;
+}
+
+int mi355rt_lens_rays(mi355rt_handle* h, uint32_t spp, uint32_t where, float* rays6, size_t nrays)
+{
+    if (!h) return MI355RT_E_INVALID;
+    const char* e = nullptr;
+    if (h->g->size() > 1) e = "mi355rt_lens_rays: not available on a device group (config.device_count > 1)";
+    else if (where > MI355RT_RAYS_DEVICE) e = "mi355rt_lens_rays: unknown `where` (MI355RT_RAYS_HOST or MI355RT_RAYS_DEVICE)";
+    else if (spp == 0) e = "mi355rt_lens_rays: spp must be >= 1";
+    else if (nrays != (size_t)h->r->cfg.width * h->r->cfg.height * spp) e = "mi355rt_lens_rays: nrays must equal width * height * spp";
+    else if (!rays6) e = "mi355rt_lens_rays: rays6 is NULL";
+    if (e) { h->r->last_error = e; return MI355RT_E_INVALID; }
+    return h->r->lens_rays(spp, where == MI355RT_RAYS_DEVICE, rays6) ? MI355RT_OK : MI355RT_E_HIP;
 }
 
 int mi355rt_get_sample_table(const mi355rt_handle* h, float* out)

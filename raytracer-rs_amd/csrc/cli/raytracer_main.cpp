@@ -16,6 +16,8 @@
 // film without them), and prints the exposure used; --exposure together with --auto-exposure is an error.  Without them --out holds the bytes it always held.
 // Caller-supplied rays (mi355rt_render_rays): --ortho-width W with --spp N renders the scene in parallel projection, W world units wide, through rays made
 // here (ortho_rays below: the arithmetic of raytracer_rs_amd.cameras.orthographic, so both paths write the same bytes).
+// Lens models (mi355rt_set_lens): --lens thin --lens-radius R --focus F (depth of field) and --lens ortho --lens-width W (parallel projection), with --spp N:
+// the rays are made on the device, so --denoise, --denoise-split, the film files and the display options all apply; they exclude --adaptive, --gpus and -i.
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -120,6 +122,9 @@ int main(int argc, char** argv)
     float ortho_width = 0.0f;
     mi355rt_display_config dcfg_display;
     mi355rt_display_default_config(&dcfg_display);
+    mi355rt_lens lens;
+    mi355rt_lens_default(&lens);
+    bool have_lens = false;
     auto parse_float = [](const char* s, float& out) { if (!s || !*s) return false; char* end = nullptr; const float f = std::strtof(s, &end); if (*end != '\0' || !std::isfinite(f)) return false; out = f; return true; };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -156,6 +161,17 @@ int main(int argc, char** argv)
             display = true;
         }
         else if (a == "--ortho-width") { float f; if (parse_float(take(), f) && f > 0.0f) { ortho_width = f; ortho = true; } }
+        else if (a == "--lens") {
+            const std::string m = v ? take() : "";
+            if (m == "thin") lens.model = MI355RT_LENS_THIN;
+            else if (m == "ortho") lens.model = MI355RT_LENS_ORTHO;
+            else if (m == "pinhole") lens.model = MI355RT_LENS_PINHOLE;
+            else { std::fprintf(stderr, "Error: --lens takes pinhole, thin or ortho\n"); return 1; }
+            have_lens = lens.model != MI355RT_LENS_PINHOLE;
+        }
+        else if (a == "--lens-radius") { float f; if (parse_float(take(), f)) lens.radius = f; }
+        else if (a == "--focus") { float f; if (parse_float(take(), f)) lens.focus = f; }
+        else if (a == "--lens-width") { float f; if (parse_float(take(), f)) lens.width_world = f; }
         else if (a == "--adaptive") { float f; if (parse_float(take(), f)) { acfg.rel_error = f; adaptive = true; } }
         else if (a == "--abs-floor") { float f; if (parse_float(take(), f)) acfg.abs_floor = f; }
         else if (a == "--min-spp") { size_t t; if (parse_usize(take(), t)) acfg.min_spp = (uint32_t)t; }
@@ -167,11 +183,14 @@ int main(int argc, char** argv)
                         "                 [--adaptive REL [--abs-floor F] [--min-spp N] [--max-spp N] [--batch N]] [--denoise | --denoise-split]\n"
                         "                 [--load-film film.bin]... [--save-film film.bin]\n"
                         "                 [--exposure F | --auto-exposure [--key F]] [--curve reinhard|reinhard-white|aces|clamp] [--white F] [--srgb]\n"
-                        "                 [--ortho-width W]   (with --spp: an orthographic view W world units wide, through mi355rt_render_rays)\n");
+                        "                 [--ortho-width W]   (with --spp: an orthographic view W world units wide, through mi355rt_render_rays)\n"
+                        "                 [--lens thin --lens-radius R --focus F | --lens ortho --lens-width W]   (with --spp: depth of field / an orthographic\n"
+                        "                                     view made on the device, mi355rt_set_lens; excludes --adaptive, --gpus and -i)\n");
             return 0;
         }
     }
     if (ortho && (!spp || adaptive || denoise || denoise_split || gpus > 1)) { std::fprintf(stderr, "Error: --ortho-width needs --spp and excludes --adaptive, --denoise, --denoise-split and --gpus\n"); return 1; }
+    if (have_lens && (!spp || adaptive || gpus > 1 || have_iterations || ortho)) { std::fprintf(stderr, "Error: --lens thin / ortho needs --spp and excludes --adaptive, --gpus, -i and --ortho-width\n"); return 1; }
     if (have_exposure && dcfg_display.auto_exposure) { std::fprintf(stderr, "Error: --exposure and --auto-exposure exclude each other\n"); return 1; }
     std::printf("max triangles per leaf: %zu\n", max_triangles);      // main.rs:66
     if (have_iterations) std::printf("will quit after %zu frame iterations\n", frame_iterations);   // main.rs:73
@@ -188,6 +207,7 @@ int main(int argc, char** argv)
         if (gpus > 1) std::printf("rendering on %zu GPUs (rows dealt in stripes of %u)\n", gpus, cfg.stripe_rows);
         raytracer_lib::RayTracer rt = raytracer_lib::create_raytracer_from_file(file, max_triangles, width, height, &cfg);
         std::printf("number of triangles: %u\n", mi355rt_triangle_count(rt.handle()));   // colladaloader.rs:265
+        if (have_lens) rt.set_lens(lens);
         for (const std::string& f : load_films) rt.film.load(f, true);     // the fresh film is zero: the first file is added to it like the others
         raytracer_lib::stats::Stats stats;
         std::vector<uint32_t> ldr;

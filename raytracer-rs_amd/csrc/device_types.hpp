@@ -55,6 +55,18 @@ struct DScene {
     float oct_root[6];        // root cube of the octree (scene extents): min.xyz, max.xyz
 };
 
+// Lens model of the handle (include/mi355rt.h, mi355rt_lens; csrc/lens.hpp holds the arithmetic).  Read only by the lens instantiations of the kernels
+// (primary_sample<kFeedLensThin / kFeedLensOrtho>, guides_lens_kernel, lens_rays_kernel): a pinhole pass never looks at it.
+// hw .. my2: what the models derive from the lens and the camera alone, computed ONCE on the host (lens_derive, f32 unfused like the kernels) — a value
+// that is the same for every lane would otherwise be computed by, and live in, vector registers (no scalar float unit), in the shade kernels for the whole chunk.
+constexpr uint32_t kLensPinhole = 0u, kLensThin = 1u, kLensOrtho = 2u;
+struct DLens {
+    uint32_t model; float radius, focus, width_world;
+    float hw, hh, hw2, hh2;   // ORTHO: width_world * 0.5, hw * (height / width), 2 * hw, 2 * hh
+    float axis[3];            // ORTHO: the direction of every ray, rot row 2 + row 3
+    float mx2, my2;           // PINHOLE, THIN: 2 * max_x, 2 * max_y
+};
+
 struct DCamera {
     float rot[16];            // rotation_matrix, camera.rs:92-95
     float origin[3];          // orientation_matrix * (0,0,0,1)
@@ -74,6 +86,9 @@ struct DCamera {
     const uint2* tile_ofs;        // per tile: x = first entry, y = number of entries
     const uint2* tile_entries;    // x = triangle (index into DScene::tris), y = float bits of a lower bound of its distance from the camera
     uint32_t tile_cols, tile_rg, tile_nblocks;
+    // the lens block, last: the pinhole kernels' view of the struct is what it was.  A lens pass has cull_valid == 0 and no mask and no bins — the
+    // rectangles, the coverage mask and the tile bins describe pinhole rays.
+    DLens lens;
 };
 constexpr uint32_t kCullGrid = 1024;                       // cells per axis (32 words per row, 128 KiB)
 

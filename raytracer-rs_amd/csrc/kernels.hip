@@ -39,6 +39,7 @@
 #include "device_math.hpp"
 #include "device_types.hpp"
 #include "kernels.hpp"
+#include "lens.hpp"
 #include "reflmask.hpp"
 #include "traverse.hpp"
 
@@ -257,11 +258,15 @@ struct __attribute__((packed, aligned(4))) RayKey { uint32_t pixel, sampleno; };
 // pixel -> primary ray, mod.rs:93-96 + camera.rs:80-90.  gi = index of the primary sample in the pass.
 // RAYS (a ray-fed pass): the ray is the caller's, used as given; the key (pixel, sampleno) is the film's numbering (ray_mode 1:
 // mi355rt_render_rays, the pass order and film_n as below) or the caller's (ray_mode 2: mi355rt_trace_rays, sample gi IS ray gi of the pass).
-template <bool RAYS = false>
+// RAYS is the feed of the primary round: kFeedCamera (the pinhole camera, everything below the two branches), kFeedRays (the caller's buffer),
+// kFeedLensThin / kFeedLensOrtho (the handle's lens, cam.lens — the ray is made in registers from the camera and ALL FOUR words of the
+// jitter's hash; no buffer.  One instantiation per model: with both models behind a wave-uniform branch the primary shade kernels spilled).
+constexpr uint32_t kFeedCamera = 0u, kFeedRays = 1u, kFeedLensThin = 2u, kFeedLensOrtho = 3u;
+template <uint32_t RAYS = kFeedCamera>
 __device__ __forceinline__ void primary_sample(const DCamera& cam, const DPass& ps, const uint32_t* __restrict__ film_n, uint32_t gi,
                                                uint32_t& pixel, uint32_t& sampleno, f3& o, f3& d)
 {
-    if constexpr (RAYS) {
+    if constexpr (RAYS == kFeedRays) {
         size_t ri = gi;
         if (ps.ray_mode == 2u) {
             if (ps.ray_keys != nullptr) { const RayKey k = ((const RayKey*)ps.ray_keys)[gi]; pixel = k.pixel; sampleno = k.sampleno; }
@@ -276,6 +281,17 @@ __device__ __forceinline__ void primary_sample(const DCamera& cam, const DPass& 
         const RayHalf* r = (const RayHalf*)(ps.ray_in + 6ull * ri);
         const RayHalf a = r[0], b = r[1];
         o = mk3(a.x, a.y, a.z); d = mk3(b.x, b.y, b.z);
+        return;
+    }
+    if constexpr (RAYS == kFeedLensThin || RAYS == kFeedLensOrtho) {
+        uint32_t s, p;
+        sample_of(ps, gi, s, p);
+        pixel = pass_pixel(ps, cam.width, p);
+        sampleno = film_n[pixel] + s;
+        uint32_t h0 = pixel, h1 = sampleno, h2 = 0u, h3 = ps.seed;
+        pcg4d(h0, h1, h2, h3);
+        lens_ray<RAYS == kFeedLensThin ? kLensThin : kLensOrtho>(cam.rot, cam.origin, cam.max_x, cam.max_y, cam.width, cam.height, ps.flags, cam.lens, pixel,
+                                                                  u01(h0), u01(h1), u01(h2), u01(h3), o.x, o.y, o.z, d.x, d.y, d.z);
         return;
     }
     if (ps.use_explicit) { pixel = ps.explicit_pixel; sampleno = ps.explicit_sampleno; }
@@ -424,8 +440,9 @@ __device__ __forceinline__ void store_blocked(float* __restrict__ slot_L, uint32
 // and every ray only records its hit; the octree confirm step (confirm_chunk) turns true closest hits into the reference
 // intersector's answers and settles the shadow predicate.  CONFIRM == false (MI355RT_FLAG_TRUE_CLOSEST_HIT): the shadow
 // predicate is decided here with the interval trick of traverse.hpp and unblocked light terms are stored directly.
-// RAYS (PRIMARY only): a ray-fed pass — the primary rays come from DPass::ray_in, and nothing is culled (no camera made them).
-template <bool PRIMARY, bool COUNT, bool SINGLE, bool CONFIRM, bool RAYS = false>
+// RAYS (PRIMARY only; primary_sample): kFeedRays / kFeedLensThin, kFeedLensOrtho — the primary rays come from DPass::ray_in / from the handle's lens, and nothing is culled
+// (the culling rectangles, the mask and the cached verdicts describe the pinhole camera's rays).
+template <bool PRIMARY, bool COUNT, bool SINGLE, bool CONFIRM, uint32_t RAYS = kFeedCamera>
 __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam, const DPass& ps,
                                            const float4* __restrict__ in_q, const uint2* __restrict__ in_counts,
                                            float4* __restrict__ hits, uint32_t* cursor,
@@ -586,7 +603,7 @@ __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam,
     }
 }
 
-template <bool PRIMARY, bool COUNT, bool CONFIRM, bool RAYS = false>
+template <bool PRIMARY, bool COUNT, bool CONFIRM, uint32_t RAYS = kFeedCamera>
 __global__ __launch_bounds__(kBlock, MI355RT_WIDE ? MI355RT_WIDE_BLOCKS : PRIMARY ? kPrimaryBlocks : 8) void trace_kernel(DScene sc, DCamera cam, DPass ps,
                                                       const float4* __restrict__ in_q, const uint2* __restrict__ in_counts,
                                                       float4* __restrict__ hits, uint32_t* cursor,
@@ -656,7 +673,7 @@ __device__ __forceinline__ uint32_t raster_tile(const DScene& sc, const DCamera&
 }
 
 // ---- trace with the reference-exact octree intersector (parity path, MI355RT_FLAG_OCTREE_SEMANTICS) ----
-template <bool PRIMARY, bool RAYS = false>
+template <bool PRIMARY, uint32_t RAYS = kFeedCamera>
 __global__ __launch_bounds__(kBlock) void trace_octree_kernel(DScene sc, DCamera cam, DPass ps,
                                                              const float4* __restrict__ in_q, const uint2* __restrict__ in_counts,
                                                              float4* __restrict__ hits, float* __restrict__ slot_L,
@@ -675,7 +692,7 @@ __global__ __launch_bounds__(kBlock) void trace_octree_kernel(DScene sc, DCamera
                 uint32_t pixel, sampleno;
                 primary_sample<RAYS>(cam, ps, film_n, chunk * ps.chunk + i, pixel, sampleno, o, d);
                 r = (size_t)chunk * ps.region + i;
-                on = RAYS || pixel_active(ps, cam.width, pixel);          // adaptive sampling: an inactive pixel's sample is a miss that is never traced
+                on = RAYS != 0u || pixel_active(ps, cam.width, pixel);          // adaptive sampling: an inactive pixel's sample is a miss that is never traced
             } else {
                 r = record_index(ps, chunk, i, n_rad);
                 const float4 r0 = in_q[r];
@@ -903,9 +920,9 @@ __device__ __forceinline__ bool reflection_proves_miss(const DScene& sc, uint32_
 // its (zeroed) light-term slot and is shaded no further: it resolves to black like a miss (mod.rs:99-100).
 // RASTER (primary round of the wavefront kernels, tile bins built): the closest hits of the chunk's primary rays are found right here (raster_tile) and
 // handed to the shading loop through LDS (lds_hits: one float4 per sample of a chunk) — no primary trace launch, no hit flags and no hit records in HBM.
-// RAYS (primary round of a ray-fed pass): the ray is the caller's (primary_sample<true>), no chunk is culled, and with DPass::ray_hit
+// RAYS (primary round of a ray-fed or a lens pass): the ray is primary_sample<RAYS>'s, no chunk is culled, and (kFeedRays) with DPass::ray_hit
 // the final hit of every sample — after the confirm walk — is kept for resolve_rays_kernel (the hit records themselves are reused by the later rounds).
-template <bool PRIMARY, class List, bool WALK = false, bool RASTER = false, bool RAYS = false>
+template <bool PRIMARY, class List, bool WALK = false, bool RASTER = false, uint32_t RAYS = kFeedCamera>
 __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam, const DPass& ps, uint32_t level, uint32_t chunk, const List list,
                                             const float4* __restrict__ in_q, uint32_t in_nrad, uint32_t& out_nrad, uint32_t& out_nshadow,
                                             const float4* __restrict__ hits,
@@ -949,7 +966,7 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
             // primary round: light-term slots are handed out per chunk to the samples that hit something
             // (74 % of the primary samples miss and need neither a slot nor zero-filling)
             if (PRIMARY && i < n_rad) st1<2>(&sample_slot[chunk * ps.chunk + i], valid ? chunk * ps.chunk + pos : kMiss);
-            if constexpr (RAYS) { if (ps.ray_hit != nullptr && i < n_rad && !valid) ps.ray_hit[chunk * ps.chunk + i] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kMiss)); }
+            if constexpr (RAYS == kFeedRays) { if (ps.ray_hit != nullptr && i < n_rad && !valid) ps.ray_hit[chunk * ps.chunk + i] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kMiss)); }
         }
         if (PRIMARY) {
             // zero the slots this chunk uses: a node whose shadow ray is blocked, or that is never
@@ -993,7 +1010,7 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
                     h = make_float4(wt, wu, wv, __uint_as_float(wprim));
                     active = wprim != kMiss;
                 }
-                if constexpr (RAYS) { if (ps.ray_hit != nullptr) ps.ray_hit[chunk * ps.chunk + i] = active ? h : make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kMiss)); }
+                if constexpr (RAYS == kFeedRays) { if (ps.ray_hit != nullptr) ps.ray_hit[chunk * ps.chunk + i] = active ? h : make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kMiss)); }
             }
             if (WALK) dropped += (uint32_t)__popcll(__ballot(j + (uint32_t)lane < cnt && !active));
             if (active) {
@@ -1122,7 +1139,7 @@ __device__ __forceinline__ void flush_shade_counters(DCounters* counters, uint32
     }
 }
 
-template <bool PRIMARY, bool WALK, bool RASTER = false, bool RAYS = false>
+template <bool PRIMARY, bool WALK, bool RASTER = false, uint32_t RAYS = kFeedCamera>
 __global__ __launch_bounds__(kBlock, PRIMARY ? (WALK ? kShadePWBlocks : kShadePBlocks) : (WALK ? kShadeSWBlocks : kShadeSBlocks)) void shade_kernel(DScene sc, DCamera cam, DPass ps, uint32_t level,
                                                       const float4* __restrict__ in_q, const uint2* __restrict__ in_counts,
                                                       const float4* __restrict__ hits,
@@ -1449,13 +1466,16 @@ __global__ __launch_bounds__(kBlock) void intersect_kernel(DScene sc, const floa
 // ---- denoised read-out (include/mi355rt.h) ------------------------------------------------------------------------
 // Guides: the primary hit of each pixel's centre ray, pixel_ray(p, 0.5, 0.5) through closest_hit, as mi355rt_intersect_rays returns it.
 // g0[p] = (normal, t), g1[p] = (albedo, prim bits); a miss: zeros and prim 0xFFFFFFFF.
-__global__ __launch_bounds__(kBlock) void guides_kernel(DScene sc, DCamera cam, uint32_t flags, int mode, uint32_t npix, float4* __restrict__ g0, float4* __restrict__ g1)
+// LENS: the centre ray is the lens ray of cam.lens with xi1 = xi2 = l1 = l2 = 0.5; a kernel of its own, so that the pinhole one stays what it was.
+template <bool LENS>
+__device__ __forceinline__ void guides_body(const DScene& sc, const DCamera& cam, uint32_t flags, int mode, uint32_t npix, float4* __restrict__ g0, float4* __restrict__ g1, int* s_stack)
 {
-    extern __shared__ int s_stack[];
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= npix) return;
     f3 o, d;
-    pixel_ray(cam, flags, p, 0.5f, 0.5f, o, d);
+    if constexpr (LENS) {
+        lens_ray(cam.rot, cam.origin, cam.max_x, cam.max_y, cam.width, cam.height, flags, cam.lens, p, 0.5f, 0.5f, 0.5f, 0.5f, o.x, o.y, o.z, d.x, d.y, d.z);
+    } else pixel_ray(cam, flags, p, 0.5f, 0.5f, o, d);
     float t = 0.0f, u = 0.0f, v = 0.0f; uint32_t prim = kMiss;
     closest_hit(sc, o, d, mode, &s_stack[threadIdx.x], t, u, v, prim);
     float4 a = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kMiss)), n = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -1468,6 +1488,32 @@ __global__ __launch_bounds__(kBlock) void guides_kernel(DScene sc, DCamera cam, 
         a = make_float4(diffuse.x, diffuse.y, diffuse.z, __uint_as_float(prim));
     }
     g0[p] = n; g1[p] = a;
+}
+__global__ __launch_bounds__(kBlock) void guides_kernel(DScene sc, DCamera cam, uint32_t flags, int mode, uint32_t npix, float4* __restrict__ g0, float4* __restrict__ g1)
+{
+    extern __shared__ int s_stack[];
+    guides_body<false>(sc, cam, flags, mode, npix, g0, g1, s_stack);
+}
+__global__ __launch_bounds__(kBlock) void guides_lens_kernel(DScene sc, DCamera cam, uint32_t flags, int mode, uint32_t npix, float4* __restrict__ g0, float4* __restrict__ g1)
+{
+    extern __shared__ int s_stack[];
+    guides_body<true>(sc, cam, flags, mode, npix, g0, g1, s_stack);
+}
+
+// mi355rt_lens_rays: the rays the next render(spp) would take, in mi355rt_render_rays layout — ray s * npix + p has key (p, film_n[p] + s).
+// One lane per ray, the arithmetic of the lens branch of primary_sample (PINHOLE included: lens_ray's pinhole branch is pixel_ray), two 12-byte stores: a wave writes
+// 1536 contiguous bytes, each store instruction touches its 12 cache lines once.
+__global__ __launch_bounds__(256) void lens_rays_kernel(DCamera cam, uint32_t flags, uint32_t seed, uint32_t npix, size_t nrays, const uint32_t* __restrict__ film_n, float* __restrict__ rays6)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nrays) return;
+    const uint32_t s = (uint32_t)(i / npix), p = (uint32_t)(i - (size_t)s * npix);
+    uint32_t h0 = p, h1 = film_n[p] + s, h2 = 0u, h3 = seed;
+    pcg4d(h0, h1, h2, h3);
+    RayHalf a, b;
+    lens_ray(cam.rot, cam.origin, cam.max_x, cam.max_y, cam.width, cam.height, flags, cam.lens, p, u01(h0), u01(h1), u01(h2), u01(h3), a.x, a.y, a.z, b.x, b.y, b.z);
+    RayHalf* r = (RayHalf*)(rays6 + 6ull * i);
+    r[0] = a; r[1] = b;
 }
 
 __device__ __forceinline__ float pos0(float x) { return x > 0.0f ? x : 0.0f; }        // NaN -> 0
@@ -1841,7 +1887,7 @@ bool kernels_walk_wide_nodes() { return MI355RT_WIDE != 0; }
 
 static size_t stack_bytes(uint32_t depth) { return (size_t)((depth ? depth : 1u) + 1u) * kBlock * sizeof(int); }   // sentinel row + one row per level (the deepest level's row doubles as the spare row above the top)
 
-template <bool P, bool C, bool F, bool R>
+template <bool P, bool C, bool F, uint32_t R>
 static int trace_blocks_per_cu(size_t lds)
 {
     // the occupancy query costs ~0.3 ms of host time: ask once per (kernel, device, LDS size).  Device groups launch from one
@@ -1860,7 +1906,7 @@ static int trace_blocks_per_cu(size_t lds)
     return nb;
 }
 
-template <bool P, bool C, bool F, bool R = false>
+template <bool P, bool C, bool F, uint32_t R = 0u>
 static hipError_t launch_trace_variant(hipStream_t stream, int num_cus, const DScene& sc, const DCamera& cam, const DPass& ps,
                                        const void* in_q, const void* in_counts, void* hits, uint32_t* cursor,
                                        float* slot_L, const uint32_t* film_n, DCounters* counters)
@@ -1881,11 +1927,14 @@ static hipError_t launch_trace_variant(hipStream_t stream, int num_cus, const DS
 // confirm: the octree confirm step follows (reference-default semantics); primary rays are radiance rays either way
 hipError_t launch_trace(hipStream_t stream, int num_cus, bool primary, bool count, bool confirm, const DScene& sc, const DCamera& cam, const DPass& ps,
                         const void* in_q, const void* in_counts, void* hits, uint32_t* cursor,
-                        float* slot_L, const uint32_t* film_n, DCounters* counters, bool rays)
+                        float* slot_L, const uint32_t* film_n, DCounters* counters, uint32_t rays)
 {
 #define MI355RT_TRACE_ARGS stream, num_cus, sc, cam, ps, in_q, in_counts, hits, cursor, slot_L, film_n, counters
     if (rays && !primary) return hipErrorInvalidValue;         // only the primary round of a pass is ray-fed
-    if (rays) return count ? launch_trace_variant<true, true, true, true>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true, true>(MI355RT_TRACE_ARGS);
+    if (rays > kFeedLensOrtho) return hipErrorInvalidValue;
+    if (rays == kFeedLensThin) return count ? launch_trace_variant<true, true, true, kFeedLensThin>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true, kFeedLensThin>(MI355RT_TRACE_ARGS);
+    if (rays == kFeedLensOrtho) return count ? launch_trace_variant<true, true, true, kFeedLensOrtho>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true, kFeedLensOrtho>(MI355RT_TRACE_ARGS);
+    if (rays) return count ? launch_trace_variant<true, true, true, kFeedRays>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true, kFeedRays>(MI355RT_TRACE_ARGS);
     if (primary) return count ? launch_trace_variant<true, true, true>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true>(MI355RT_TRACE_ARGS);
     if (confirm) return count ? launch_trace_variant<false, true, true>(MI355RT_TRACE_ARGS) : launch_trace_variant<false, false, true>(MI355RT_TRACE_ARGS);
     return count ? launch_trace_variant<false, true, false>(MI355RT_TRACE_ARGS) : launch_trace_variant<false, false, false>(MI355RT_TRACE_ARGS);
@@ -1911,15 +1960,17 @@ hipError_t launch_cull_blocks(hipStream_t stream, const DCamera& cam, const DPas
 }
 
 hipError_t launch_trace_octree(hipStream_t stream, int num_cus, bool primary, const DScene& sc, const DCamera& cam, const DPass& ps,
-                               const void* in_q, const void* in_counts, void* hits, float* slot_L, const uint32_t* film_n, bool rays)
+                               const void* in_q, const void* in_counts, void* hits, float* slot_L, const uint32_t* film_n, uint32_t rays)
 {
-    if (rays && !primary) return hipErrorInvalidValue;
+    if ((rays && !primary) || rays > kFeedLensOrtho) return hipErrorInvalidValue;
     unsigned blocks = (ps.nchunks + kWavesPerBlock - 1) / kWavesPerBlock;
     const unsigned cap = (unsigned)num_cus * 4u;
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     dim3 grid(blocks), block(kBlock);
-    if (rays) hipLaunchKernelGGL((trace_octree_kernel<true, true>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
+    if (rays == kFeedLensThin) hipLaunchKernelGGL((trace_octree_kernel<true, kFeedLensThin>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
+    else if (rays == kFeedLensOrtho) hipLaunchKernelGGL((trace_octree_kernel<true, kFeedLensOrtho>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
+    else if (rays) hipLaunchKernelGGL((trace_octree_kernel<true, kFeedRays>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
     else if (primary) hipLaunchKernelGGL((trace_octree_kernel<true>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
     else hipLaunchKernelGGL((trace_octree_kernel<false>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
     return hipGetLastError();
@@ -1927,9 +1978,9 @@ hipError_t launch_trace_octree(hipStream_t stream, int num_cus, bool primary, co
 
 hipError_t launch_shade(hipStream_t stream, int num_cus, bool primary, bool walk, const DScene& sc, const DCamera& cam, const DPass& ps, uint32_t level,
                         const void* in_q, const void* in_counts, const void* hits, void* out_q, void* out_counts, uint32_t* cursor,
-                        float* slot_L, uint32_t* sample_slot, const uint32_t* film_n, DCounters* counters, bool raster, bool rays)
+                        float* slot_L, uint32_t* sample_slot, const uint32_t* film_n, DCounters* counters, bool raster, uint32_t rays)
 {
-    if (rays && (!primary || raster)) return hipErrorInvalidValue;      // a ray-fed primary round walks the tree: no camera, no tile bins
+    if ((rays && (!primary || raster)) || rays > kFeedLensOrtho) return hipErrorInvalidValue;      // a ray-fed or lens primary round walks the tree: no pinhole camera, no tile bins
     // raster (primary round only): the kernel finds the primary rays' closest hits itself, through the tile bins (cam.tile_ofs), and keeps them in LDS
     const size_t lds = (size_t)ps.list_cap * kWavesPerBlock * sizeof(uint32_t) + (raster ? (size_t)ps.chunk * kWavesPerBlock * sizeof(float4) : 0);
     unsigned blocks = (ps.nchunks + kWavesPerBlock - 1) / kWavesPerBlock;
@@ -1938,8 +1989,12 @@ hipError_t launch_shade(hipStream_t stream, int num_cus, bool primary, bool walk
     if (blocks < 1) blocks = 1;
     dim3 grid(blocks), block(kBlock);
 #define MI355RT_SHADE_ARGS grid, block, lds, stream, sc, cam, ps, level, (const float4*)in_q, (const uint2*)in_counts, (const float4*)hits, (float4*)out_q, (uint2*)out_counts, cursor, slot_L, sample_slot, film_n, counters
-    if (rays && walk) hipLaunchKernelGGL((shade_kernel<true, true, false, true>), MI355RT_SHADE_ARGS);
-    else if (rays) hipLaunchKernelGGL((shade_kernel<true, false, false, true>), MI355RT_SHADE_ARGS);
+    if (rays == kFeedLensThin && walk) hipLaunchKernelGGL((shade_kernel<true, true, false, kFeedLensThin>), MI355RT_SHADE_ARGS);
+    else if (rays == kFeedLensThin) hipLaunchKernelGGL((shade_kernel<true, false, false, kFeedLensThin>), MI355RT_SHADE_ARGS);
+    else if (rays == kFeedLensOrtho && walk) hipLaunchKernelGGL((shade_kernel<true, true, false, kFeedLensOrtho>), MI355RT_SHADE_ARGS);
+    else if (rays == kFeedLensOrtho) hipLaunchKernelGGL((shade_kernel<true, false, false, kFeedLensOrtho>), MI355RT_SHADE_ARGS);
+    else if (rays && walk) hipLaunchKernelGGL((shade_kernel<true, true, false, kFeedRays>), MI355RT_SHADE_ARGS);
+    else if (rays) hipLaunchKernelGGL((shade_kernel<true, false, false, kFeedRays>), MI355RT_SHADE_ARGS);
     else if (primary && raster && walk) hipLaunchKernelGGL((shade_kernel<true, true, true>), MI355RT_SHADE_ARGS);
     else if (primary && raster) hipLaunchKernelGGL((shade_kernel<true, false, true>), MI355RT_SHADE_ARGS);
     else if (primary && walk) hipLaunchKernelGGL((shade_kernel<true, true>), MI355RT_SHADE_ARGS);
@@ -2181,7 +2236,18 @@ hipError_t launch_guides(hipStream_t stream, const DScene& sc, const DCamera& ca
 {
     const uint32_t npix = cam.width * cam.height;
     if (npix == 0) return hipSuccess;
-    hipLaunchKernelGGL(guides_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), stack_bytes(stack_depth), stream, sc, cam, flags, mode, npix, g0, g1);
+    if (cam.lens.model != kLensPinhole) hipLaunchKernelGGL(guides_lens_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), stack_bytes(stack_depth), stream, sc, cam, flags, mode, npix, g0, g1);
+    else hipLaunchKernelGGL(guides_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), stack_bytes(stack_depth), stream, sc, cam, flags, mode, npix, g0, g1);
+    return hipGetLastError();
+}
+
+hipError_t launch_lens_rays(hipStream_t stream, const DCamera& cam, uint32_t flags, uint32_t seed, uint32_t spp, const uint32_t* film_n, float* rays6)
+{
+    const uint32_t npix = cam.width * cam.height;
+    const size_t nrays = (size_t)npix * spp;
+    if (nrays == 0) return hipSuccess;
+    if ((nrays + 255) / 256 > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lens_rays_kernel, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, stream, cam, flags, seed, npix, nrays, film_n, rays6);
     return hipGetLastError();
 }
 

@@ -8,15 +8,15 @@ namespace mi355rt {
 
 hipError_t launch_trace(hipStream_t stream, int num_cus, bool primary, bool count, bool confirm, const DScene& sc, const DCamera& cam, const DPass& ps,
                         const void* in_q, const void* in_counts, void* hits, uint32_t* cursor,
-                        float* slot_L, const uint32_t* film_n, DCounters* counters, bool rays = false);   // rays: the primary round of a ray-fed pass (DPass::ray_in)
+                        float* slot_L, const uint32_t* film_n, DCounters* counters, uint32_t rays = 0);   // rays: the feed of the primary round — 0 the pinhole camera, 1 a ray-fed pass (DPass::ray_in), 2 / 3 the handle's THIN / ORTHO lens (DCamera::lens)
 // culling verdicts of the pass's pixel blocks (DPass::block_culled): out[b] = chunk b (first sample group) is culled
 hipError_t launch_cull_blocks(hipStream_t stream, const DCamera& cam, const DPass& ps, uint32_t nblocks, uint32_t* out);
 hipError_t launch_trace_octree(hipStream_t stream, int num_cus, bool primary, const DScene& sc, const DCamera& cam, const DPass& ps,
-                               const void* in_q, const void* in_counts, void* hits, float* slot_L, const uint32_t* film_n, bool rays = false);
+                               const void* in_q, const void* in_counts, void* hits, float* slot_L, const uint32_t* film_n, uint32_t rays = 0);
 hipError_t launch_shade(hipStream_t stream, int num_cus, bool primary, bool walk, const DScene& sc, const DCamera& cam, const DPass& ps, uint32_t level,
                         const void* in_q, const void* in_counts, const void* hits, void* out_q, void* out_counts, uint32_t* cursor,
                         float* slot_L, uint32_t* sample_slot, const uint32_t* film_n, DCounters* counters, bool raster = false,   // raster: primary round, hits through the tile bins inside the launch
-                        bool rays = false);                                                                                        // rays: as launch_trace
+                        uint32_t rays = 0);                                                                                        // rays: as launch_trace
 hipError_t launch_resolve(hipStream_t stream, const DPass& ps, uint32_t width, uint32_t nlights, const float* slot_L, const uint32_t* sample_slot,
                           float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct, float* debug_color, uint32_t* ctrl);   // ctrl != null: zero the pass's work cursors on the way out
 // mi355rt_trace_rays: per-ray results of a ray-fed pass whose sample i is ray i; rgb / direct / tuv / prim: the pass's part of the outputs, any may be null
@@ -57,7 +57,9 @@ hipError_t launch_adaptive_tiles(hipStream_t stream, const AdaptiveArgs& a, cons
                                  uint8_t* out, unsigned long long* count);
 hipError_t launch_film_stat(hipStream_t stream, bool variances, size_t npix, const float* film_sum, const float* film_sumsq, const uint32_t* film_n, float* out);
 // denoised read-out: the guides of the camera cam (cam.width x cam.height pixels; flags bit 0: FIX_ROW_INDEX), mode as launch_intersect
-hipError_t launch_guides(hipStream_t stream, const DScene& sc, const DCamera& cam, uint32_t flags, uint32_t stack_depth, int mode, float4* g0, float4* g1);
+hipError_t launch_guides(hipStream_t stream, const DScene& sc, const DCamera& cam, uint32_t flags, uint32_t stack_depth, int mode, float4* g0, float4* g1);   // cam.lens: whose centre rays
+// mi355rt_lens_rays: the rays of the next render(spp) under cam.lens, width * height * spp x (pos3, dir3) in mi355rt_render_rays layout, device memory
+hipError_t launch_lens_rays(hipStream_t stream, const DCamera& cam, uint32_t flags, uint32_t seed, uint32_t spp, const uint32_t* film_n, float* rays6);
 // film -> `iterations` filter iterations ping-ponging ping / pong (npix float4 each; flags: npix u32) -> rgb (npix * 3 floats) and / or packed (npix u32);
 // film_direct non-null: the split read-out (the indirect part is filtered, the direct part added back)
 hipError_t launch_denoise(hipStream_t stream, const DenoiseArgs& args, uint32_t iterations, const float* film_sum, const float* film_sumsq, const uint32_t* film_n,

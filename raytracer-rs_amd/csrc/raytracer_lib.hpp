@@ -157,6 +157,20 @@ public:
         if (mi355rt_trace_rays(h_, rays6.data(), keys2, rays6.size() / 6, MI355RT_RAYS_HOST, &out) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
         return rgb;
     }
+    // lens models (include/mi355rt.h): the ray generator of render(); lens_rays: the width*height*spp rays of the next render(spp), host memory
+    void set_lens(const mi355rt_lens& lens) { if (mi355rt_set_lens(h_, &lens) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_)); }
+    mi355rt_lens lens() const
+    {
+        mi355rt_lens l{};
+        if (mi355rt_get_lens(h_, &l) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+        return l;
+    }
+    std::vector<float> lens_rays(uint32_t spp) const
+    {
+        std::vector<float> rays((size_t)mi355rt_width(h_) * mi355rt_height(h_) * spp * 6);
+        if (mi355rt_lens_rays(h_, spp, MI355RT_RAYS_HOST, rays.data(), rays.size() / 6) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+        return rays;
+    }
     mi355rt_handle* handle() const { return h_; }
 private:
     mi355rt_handle* h_;
@@ -188,6 +202,15 @@ inline RayTracer create_raytracer_from_file(const std::string& collada_filename,
                         : mi355rt_create_from_collada_file(collada_filename.c_str(), &cfg, &h);
     if (rc != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(nullptr));
     return RayTracer(h);
+}
+// the ray of a pixel under a lens, host code (mi355rt_lens_ray): rot16, orient16, max_xy as mi355rt_camera_get returns them; flags bit 0: FIX_ROW_INDEX
+inline std::vector<float> lens_ray(const float rot16[16], const float orient16[16], const float max_xy[2], size_t width, size_t height, uint32_t flags,
+                                   const mi355rt_lens& lens, uint32_t pixel, float xi1 = 0.5f, float xi2 = 0.5f, float l1 = 0.5f, float l2 = 0.5f)
+{
+    std::vector<float> ray(6);
+    if (mi355rt_lens_ray(rot16, orient16, max_xy, (uint32_t)width, (uint32_t)height, flags, &lens, pixel, xi1, xi2, l1, l2, ray.data()) != MI355RT_OK)
+        throw std::runtime_error(mi355rt_last_error(nullptr));
+    return ray;
 }
 // header of a film file, checked without a device (mi355rt_film_file_info): version, width, height, planes, seed low, seed high, flags, 0
 inline std::vector<uint32_t> film_file_info(const std::string& path)

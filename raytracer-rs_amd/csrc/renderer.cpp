@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "kernels.hpp"
+#include "lens.hpp"
 #include "octree.hpp"
 
 namespace mi355rt {
@@ -610,6 +611,7 @@ DCamera Renderer::device_camera(const DPass* layout, const std::vector<uint32_t>
     c.origin[0] = pos.x; c.origin[1] = pos.y; c.origin[2] = pos.z;
     c.max_x = camera.max_x(); c.max_y = camera.max_y();
     c.width = cfg.width; c.height = cfg.height;
+    c.lens = lens_derive(lens_.model, lens_.radius, lens_.focus, lens_.width_world, c.rot, c.max_x, c.max_y, cfg.width, cfg.height);
     // Screen-space bounds of the padded scene box for the primary-chunk frustum culling (kernels.hip,
     // chunk_is_culled).  dir = (dir_x, -dir_y, 1) * R3x3  =>  (dir_x, -dir_y, 1) ~ (p - origin) * R3x3^-1.
     // Valid only if every corner of the box is in front of the camera; computed in double, widened.
@@ -770,12 +772,12 @@ bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32
     describe_pass(ps, sl, d_rows, row0, row_wrap, npix, nsamples, kChunk, explicit_sample, epixel, esample);
     ps.tile_active = tile_active; ps.tiles_x = tiles_x();
     // the tile bins of the primary rays need a pass that walks the slice's whole row list (render(); not the odd row windows of the other callers)
-    // (nor a ray-fed pass: its primary rays are not the camera's, so nothing that is derived from the camera — bins, culling rectangles, cached verdicts — holds)
+    // (nor a ray-fed or a lens pass: its primary rays are not the pinhole camera's, so nothing that is derived from the camera — bins, culling rectangles, cached verdicts — holds)
     const bool whole = !feed && !explicit_sample && d_rows == sl.d_rows.get() && row0 == 0 && nrows == sl.rows.size() && row_wrap == 0xFFFFFFFFu;
     DCamera cam = device_camera(whole ? &ps : nullptr, whole ? &sl.rows : nullptr);
-    const bool rays = feed != nullptr;
-    if (rays) {
-        cam.cull_valid = 0; cam.cull_mask = nullptr; cam.tile_ofs = nullptr; cam.tile_entries = nullptr;
+    const uint32_t rays = feed == nullptr ? 0u : feed->mode != 3u ? 1u : lens_.model == MI355RT_LENS_THIN ? 2u : 3u;      // the feed of the primary round (kernels.hpp, launch_trace)
+    if (rays) { cam.cull_valid = 0; cam.cull_mask = nullptr; cam.tile_ofs = nullptr; cam.tile_entries = nullptr; }
+    if (rays == 1u) {
         ps.ray_in = feed->rays; ps.ray_keys = feed->keys; ps.ray_hit = feed->hit; ps.ray_mode = feed->mode; ps.ray_base = feed->base; ps.ray_npix = cfg.width * cfg.height;
     }
     // culling verdicts per pixel block, computed once per camera and layout (DPass::block_culled) instead of per launch and chunk
@@ -833,9 +835,9 @@ bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32
                 HIP_TRY(hipMemcpy(d_counters_.get(), &init, sizeof init, hipMemcpyHostToDevice));
             }
             if (mode_ == kModeOctreeWalk)
-                HIP_TRY(launch_trace_octree(st, num_cus_, r == 0, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_slot_L.get(), d_film_n_.get(), rays && r == 0));
+                HIP_TRY(launch_trace_octree(st, num_cus_, r == 0, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_slot_L.get(), d_film_n_.get(), r == 0 ? rays : 0u));
             else
-                HIP_TRY(launch_trace(st, num_cus_, r == 0, count, mode_ == kModeConfirm, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound, sl.d_slot_L.get(), d_film_n_.get(), d_counters_.get(), rays && r == 0));
+                HIP_TRY(launch_trace(st, num_cus_, r == 0, count, mode_ == kModeConfirm, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound, sl.d_slot_L.get(), d_film_n_.get(), d_counters_.get(), r == 0 ? rays : 0u));
             if (timed) { HIP_TRY(hipEventRecord(ev_pool_[ev_used_ + 1], st)); ev_used_ += 2; }
             ++launches_;
         }
@@ -866,7 +868,7 @@ bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32
                         (double)c0.t_sum_end / c0.n_waves / 100.0, (double)(c0.t_first_end - c0.t_start) / 100.0, (double)(c0.t_last_end - c0.t_start) / 100.0);
         }
         if (r <= cfg.recursions)
-            HIP_TRY(launch_shade(st, num_cus_, r == 0, shade_walks, dscene_, cam, ps, r, in_q, in_c, sl.d_hits.get(), sl.d_queue[r & 1].get(), sl.d_chunk_counts[r & 1].get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound + kShadeCursorOffset, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_n_.get(), d_counters_.get(), fuse_primary, rays && r == 0));
+            HIP_TRY(launch_shade(st, num_cus_, r == 0, shade_walks, dscene_, cam, ps, r, in_q, in_c, sl.d_hits.get(), sl.d_queue[r & 1].get(), sl.d_chunk_counts[r & 1].get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound + kShadeCursorOffset, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_n_.get(), d_counters_.get(), fuse_primary, r == 0 ? rays : 0u));
     }
     if (free_rays) HIP_TRY(launch_resolve_rays(st, ps, nlights_, sl.d_slot_L.get(), sl.d_sample_slot.get(), feed->rgb, feed->direct, feed->tuv, feed->prim, sl.d_ctrl.get()));
     else HIP_TRY(launch_resolve(st, ps, cfg.width, nlights_, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_film_direct_.get(), d_debug_color_.get(), sl.d_ctrl.get()));
@@ -1116,7 +1118,10 @@ bool Renderer::settle_speculation()
 bool Renderer::render(uint32_t spp, bool wait)
 {
     if (!begin_call()) return false;
-    if (!enqueue_frame(spp, ev_begin_, nullptr)) return false;
+    // a lens: the same passes, their primary round fed by the lens instantiations of the kernels — no buffer, nothing to stage, so it queues like any frame
+    RayFeed f{};
+    f.mode = 3u;
+    if (!enqueue_frame(spp, ev_begin_, nullptr, has_lens() ? &f : nullptr)) return false;
     for (uint32_t r : owned_rows) ldr_dirty_[r] = 1;
     return end_call((uint64_t)owned_rows.size() * cfg.width * spp, wait);
 }
@@ -1540,6 +1545,33 @@ bool Renderer::render_rays(const float* rays6, uint32_t spp, bool device)
     return end_call((uint64_t)owned_rows.size() * cfg.width * spp, true);
 }
 
+// ---- lens models (include/mi355rt.h) ---------------------------------------------------------------------------------------
+// The film, the caller-ray mark, the counters and current_row stay; a speculative 50-row frame was traced for the lens that is leaving and is given up.
+bool Renderer::set_lens(const mi355rt_lens& l)
+{
+    if (std::memcmp(&l, &lens_, sizeof l) == 0) return true;
+    if (!bind()) return false;
+    if (!settle_speculation()) return false;
+    lens_ = l;
+    return true;
+}
+
+// mi355rt_lens_rays: one launch on the main stream, behind whatever is queued (render_async joins its slices there).  Host memory: through a temporary
+// device buffer.  Nothing of the handle changes.
+bool Renderer::lens_rays(uint32_t spp, bool device, float* rays6)
+{
+    if (!bind()) return false;
+    if (!settle_speculation()) return false;
+    const size_t nrays = (size_t)cfg.width * cfg.height * spp;
+    DeviceBuffer<float> stage;
+    float* d = rays6;
+    if (!device) { HIP_TRY(stage.alloc(nrays * 24, &hbm_bytes_)); d = stage.get(); }
+    HIP_TRY(launch_lens_rays(stream_, device_camera(), cfg.flags, (uint32_t)cfg.seed, spp, d_film_n_.get(), d));
+    if (!device) HIP_TRY(hipMemcpyAsync(rays6, d, nrays * 24, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's buffer is complete, on whatever stream it is used next
+    return true;
+}
+
 bool Renderer::debug_numerics(const float* a, const float* b, size_t n, float* q, float* r, float* p)
 {
     if (!bind()) return false;
@@ -1620,7 +1652,7 @@ bool Renderer::film_stat(bool variances, float* rgb)
 }
 
 // ---- denoised read-out (include/mi355rt.h) ------------------------------------------------------------------------
-// The guides on the device for the current camera and FIX_ROW_INDEX bit: rebuilt (stream-ordered, on the main stream) only when that key changes
+// The guides on the device for the current camera, FIX_ROW_INDEX bit and lens: rebuilt (stream-ordered, on the main stream) only when that key changes
 bool Renderer::refresh_guides()
 {
     const size_t npix = (size_t)cfg.width * cfg.height;
@@ -1635,6 +1667,9 @@ bool Renderer::refresh_guides()
     std::vector<float> key(cam.rot, cam.rot + 16);
     key.insert(key.end(), cam.origin, cam.origin + 3); key.push_back(cam.max_x); key.push_back(cam.max_y);
     key.push_back((cfg.flags & MI355RT_FLAG_FIX_ROW_INDEX) ? 1.0f : 0.0f);
+    key.push_back((float)lens_.model);                                // the lens: its model and the fields that model reads (validated: finite)
+    key.push_back(lens_.model == MI355RT_LENS_THIN ? lens_.radius : 0.0f); key.push_back(lens_.model == MI355RT_LENS_THIN ? lens_.focus : 0.0f);
+    key.push_back(lens_.model == MI355RT_LENS_ORTHO ? lens_.width_world : 0.0f);
     if (key == guides_key_) return true;
     guides_key_.clear();
     HIP_TRY(launch_guides(stream_, dscene_, cam, cfg.flags & MI355RT_FLAG_FIX_ROW_INDEX, traversal_rows(), mode_ == kModeConfirm ? 0 : mode_ == kModeOctreeWalk ? 1 : 2,

@@ -42,6 +42,11 @@ public:
     // caller-supplied rays; the caller has checked the arguments.  device: every pointer is device memory of this handle's device
     bool trace_rays(const float* rays6, const uint32_t* keys2, size_t n, bool device, const mi355rt_ray_outputs& out);
     bool render_rays(const float* rays6, uint32_t spp, bool device);
+    // lens models; the caller has checked the arguments.  set_lens keeps the film, the caller-ray mark, the counters and current_row
+    bool set_lens(const mi355rt_lens& l);
+    const mi355rt_lens& lens() const { return lens_; }
+    bool has_lens() const { return lens_.model != MI355RT_LENS_PINHOLE; }
+    bool lens_rays(uint32_t spp, bool device, float* rays6);            // width * height * spp rays of the next render(spp); a read-out: nothing of the handle changes
     bool caller_ray_film() const { return caller_ray_film_; }           // the film holds samples of mi355rt_render_rays: the camera's guides do not describe it
     bool synchronize();                                                 // wait for everything queued on this handle
     // ---- multi-GPU gather of the packed u32 stripes into the root's frame.  Two transports end in the
@@ -149,7 +154,8 @@ private:
     void free_pass_buffers();
     bool assign_slice_rows(uint32_t nslices);
     // A ray-fed pass (DPass::ray_in ...).  mode 1: the film's pixels with the caller's rays (base: the call's sample number of the pass's first
-    // sample, set per pass by enqueue_frame); mode 2: `count` free rays, one sample each, resolved into the out pointers (device memory, the pass's part)
+    // sample, set per pass by enqueue_frame); mode 2: `count` free rays, one sample each, resolved into the out pointers (device memory, the pass's part);
+    // mode 3: no buffer at all — the film's pixels with the rays of the handle's lens, made by the kernels (DCamera::lens)
     struct RayFeed { uint32_t mode; const float* rays; const uint32_t* keys; uint32_t base; uint32_t count; float4* hit; float* rgb; float* direct; float* tuv; uint32_t* prim; };
     bool run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t nrows, uint32_t spp, bool explicit_sample, uint32_t epixel, uint32_t esample, uint32_t row_wrap = 0xFFFFFFFFu,
                   const uint8_t* tile_active = nullptr, const RayFeed* feed = nullptr);
@@ -157,6 +163,7 @@ private:
     // feed (mode 1): the frame's primary rays are the caller's
     bool enqueue_frame(uint32_t spp, hipEvent_t fork, const uint8_t* tile_active, const RayFeed* feed = nullptr);
     bool caller_ray_film_ = false;
+    mi355rt_lens lens_{ MI355RT_LENS_PINHOLE, 0.0f, 1.0f, 0.0f };    // the handle's lens; not PINHOLE: render() runs lens passes (RayFeed mode 3), the guides take its centre rays
     bool join_slices();                                                 // the main stream waits for the slices of the call in flight
     bool adaptive_verdict(const mi355rt_adaptive_config& ac, uint32_t& tiles, uint64_t& pixels);    // d_tile_active_ <- the verdict of the current film
     DeviceBuffer<uint8_t> d_tile_active_;                               // adaptive sampling: one byte per tile (DPass::tile_active)
@@ -165,7 +172,7 @@ private:
     // flag of guides_key_, and the per-call buffers of the filter
     bool refresh_guides();
     DeviceBuffer<float4> d_guide0_, d_guide1_;
-    std::vector<float> guides_key_;      // rot, origin, max_x, max_y, FIX_ROW_INDEX bit of the guides on the device; empty: none
+    std::vector<float> guides_key_;      // rot, origin, max_x, max_y, FIX_ROW_INDEX bit and the lens (model and the fields it reads) of the guides on the device; empty: none
     DeviceBuffer<float4> d_dn_ping_, d_dn_pong_;
     DeviceBuffer<uint32_t> d_dn_flags_, d_dn_packed_;
     DeviceBuffer<float> d_dn_rgb_;
