@@ -154,7 +154,12 @@ typedef struct mi355rt_ray_counts {
 
 void mi355rt_default_config(mi355rt_config* cfg);
 
-/* build_raytracer, lib.rs:29-44 (octree build replaced by a BVH build + upload). */
+/* build_raytracer, lib.rs:29-44 (octree build replaced by a BVH build + upload).
+ * Refused with MI355RT_E_INVALID, the cause in mi355rt_last_error(NULL), *out left NULL: a textured material whose tex_id is not below ntextures
+ * ("material texture id out of range"), a texture with width 0, height 0 or a NULL rgb ("empty texture").  A texture's rgb must hold width * height * 3
+ * floats: the struct carries no length, so that is the caller's word.
+ * The four create entries never let a C++ exception out: a failed allocation and the like return an error code with the exception's text, and a file
+ * whose header declares more than its data can hold (a PNG, a scene container) is refused with MI355RT_E_LOAD before anything of that size is allocated. */
 int mi355rt_create(const mi355rt_scene_desc* scene, const mi355rt_config* cfg, mi355rt_handle** out);
 /* create_raytracer(collada_doc, triangles_per_leaf, width, height), lib.rs:15-20.
  * data_dir (may be NULL) is where texture files are looked up (colladaloader.rs:146-150). */

@@ -873,10 +873,9 @@ def create_raytracer_from_scene_file(scene_filename, triangles_per_leaf, width, 
     return _finish(code, h, None, cfg)
 
 
-def create_raytracer_from_arrays(scene, triangles_per_leaf, width, height, **cfg_kw):
-    """build_raytracer (lib.rs:29-44) from parsed arrays — what a Rust shim would marshal.
-    `scene` is the dict produced by scene_io.load_scene_file()."""
-    cfg = default_config(width, height, triangles_per_leaf=triangles_per_leaf, **cfg_kw)
+def scene_desc(scene):
+    """(SceneDesc, keepalive): the parsed arrays of scene_io.load_scene_file() as mi355rt_create takes them.  A texture is a float array of shape
+    (height, width, 3); any other shape is refused here (RuntimeError), because the C struct carries no length the library could check."""
     verts = np.ascontiguousarray(scene["tri_verts"], np.float32).reshape(-1)
     geom = np.ascontiguousarray(scene["tri_geom"], np.uint32)
     nm = len(scene["mat_kind"])
@@ -895,6 +894,8 @@ def create_raytracer_from_arrays(scene, triangles_per_leaf, width, height, **cfg
     keep = [verts, geom, mats, lights, texs]
     for i, t in enumerate(scene["textures"]):
         arr = np.ascontiguousarray(t, np.float32)
+        if arr.ndim != 3 or arr.shape[2] != 3:
+            raise RuntimeError("texture size mismatch: texture %d has shape %r, not (height, width, 3)" % (i, arr.shape))
         keep.append(arr)
         texs[i].height, texs[i].width = arr.shape[0], arr.shape[1]
         texs[i].rgb = _fp(arr)
@@ -905,6 +906,14 @@ def create_raytracer_from_arrays(scene, triangles_per_leaf, width, height, **cfg
     for i in range(16):
         sd.camera_orientation[i] = float(scene["camera_matrix"][i])
     sd.camera_fov_deg = float(scene["camera_fov"])
+    return sd, keep
+
+
+def create_raytracer_from_arrays(scene, triangles_per_leaf, width, height, **cfg_kw):
+    """build_raytracer (lib.rs:29-44) from parsed arrays — what a Rust shim would marshal.
+    `scene` is the dict produced by scene_io.load_scene_file()."""
+    cfg = default_config(width, height, triangles_per_leaf=triangles_per_leaf, **cfg_kw)
+    sd, keep = scene_desc(scene)
     h = C.c_void_p()
     code = lib().mi355rt_create(C.byref(sd), C.byref(cfg), C.byref(h))
     return _finish(code, h, keep, cfg)

@@ -2,6 +2,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <exception>
 #include <memory>
 #include <string>
 #include <vector>
@@ -39,6 +40,15 @@ int finish_create(const SceneData& scene, const mi355rt_config* cfg, mi355rt_han
     return MI355RT_OK;
 }
 int bad(const char* msg) { g_create_error = msg; return MI355RT_E_INVALID; }
+// No C++ exception leaves a C entry point: what `body` throws (std::bad_alloc or std::length_error from a size a file or the caller gave)
+// becomes `code` and a message, as the reference's Err(String).
+template <class Body> int no_throw(const char* fn, int code, Body&& body)
+{
+    try { return body(); }
+    catch (const std::exception& e) { g_create_error = std::string(fn) + ": " + e.what(); }
+    catch (...) { g_create_error = std::string(fn) + ": unknown exception"; }
+    return code;
+}
 
 // the checks of mi355rt_render_adaptive / mi355rt_adaptive_tile_mask (include/mi355rt.h); on failure the handle's last_error names the field
 bool adaptive_args_ok(mi355rt_handle* h, const mi355rt_adaptive_config* c)
@@ -243,58 +253,66 @@ int mi355rt_create(const mi355rt_scene_desc* s, const mi355rt_config* cfg, mi355
     *out = nullptr;
     if ((s->ntri && (!s->tri_verts || !s->tri_geom)) || (s->nmaterials && !s->materials) || (s->nlights && !s->lights) || (s->ntextures && !s->textures))
         return bad("null array with a non-zero count");
-    SceneData sd;
-    sd.tri_verts.assign(s->tri_verts, s->tri_verts + (size_t)s->ntri * 9);
-    sd.tri_geom.assign(s->tri_geom, s->tri_geom + s->ntri);
-    for (uint32_t i = 0; i < s->nmaterials; ++i) {
-        MaterialData m;
-        m.kind = s->materials[i].kind; std::memcpy(m.rgb, s->materials[i].rgb, 12); m.tex_id = s->materials[i].tex_id;
-        if (m.kind > 1) return bad("material kind must be 0 (colour) or 1 (texture)");
-        sd.materials.push_back(m);
-    }
-    for (uint32_t i = 0; i < s->nlights; ++i) {
-        LightData l;
-        std::memcpy(l.pos, s->lights[i].pos, 12); std::memcpy(l.color, s->lights[i].color, 12);
-        sd.lights.push_back(l);
-    }
-    for (uint32_t i = 0; i < s->ntextures; ++i) {
-        TextureData t;
-        t.width = s->textures[i].width; t.height = s->textures[i].height;
-        if (!s->textures[i].rgb || !t.width || !t.height) return bad("empty texture");
-        t.rgb.assign(s->textures[i].rgb, s->textures[i].rgb + (size_t)t.width * t.height * 3);
-        sd.textures.push_back(std::move(t));
-    }
-    CameraData c;
-    std::memcpy(c.orientation, s->camera_orientation, 64); c.fov_deg = s->camera_fov_deg;
-    sd.cameras.push_back(c);
-    return finish_create(sd, cfg, out);
+    return no_throw("mi355rt_create", MI355RT_E_INVALID, [&]() -> int {
+        SceneData sd;
+        sd.tri_verts.assign(s->tri_verts, s->tri_verts + (size_t)s->ntri * 9);
+        sd.tri_geom.assign(s->tri_geom, s->tri_geom + s->ntri);
+        for (uint32_t i = 0; i < s->nmaterials; ++i) {
+            MaterialData m;
+            m.kind = s->materials[i].kind; std::memcpy(m.rgb, s->materials[i].rgb, 12); m.tex_id = s->materials[i].tex_id;
+            if (m.kind > 1) return bad("material kind must be 0 (colour) or 1 (texture)");
+            sd.materials.push_back(m);
+        }
+        for (uint32_t i = 0; i < s->nlights; ++i) {
+            LightData l;
+            std::memcpy(l.pos, s->lights[i].pos, 12); std::memcpy(l.color, s->lights[i].color, 12);
+            sd.lights.push_back(l);
+        }
+        for (uint32_t i = 0; i < s->ntextures; ++i) {
+            TextureData t;
+            t.width = s->textures[i].width; t.height = s->textures[i].height;
+            if (!s->textures[i].rgb || !t.width || !t.height) { g_create_error = "empty texture: texture " + std::to_string(i) + " has width 0, height 0 or a NULL rgb array"; return MI355RT_E_INVALID; }
+            t.rgb.assign(s->textures[i].rgb, s->textures[i].rgb + (size_t)t.width * t.height * 3);
+            sd.textures.push_back(std::move(t));
+        }
+        CameraData c;
+        std::memcpy(c.orientation, s->camera_orientation, 64); c.fov_deg = s->camera_fov_deg;
+        sd.cameras.push_back(c);
+        return finish_create(sd, cfg, out);
+    });
 }
 
 int mi355rt_create_from_collada_str(const char* doc, size_t len, const char* data_dir, const mi355rt_config* cfg, mi355rt_handle** out)
 {
     if (!doc || !cfg || !out) return bad("null argument");
     *out = nullptr;
-    SceneData sd; std::string err;
-    if (!load_collada_str(std::string(doc, len), data_dir, sd, err)) { g_create_error = err; return MI355RT_E_LOAD; }
-    return finish_create(sd, cfg, out);
+    return no_throw("mi355rt_create_from_collada_str", MI355RT_E_LOAD, [&]() -> int {
+        SceneData sd; std::string err;
+        if (!load_collada_str(std::string(doc, len), data_dir, sd, err)) { g_create_error = err; return MI355RT_E_LOAD; }
+        return finish_create(sd, cfg, out);
+    });
 }
 
 int mi355rt_create_from_collada_file(const char* path, const mi355rt_config* cfg, mi355rt_handle** out)
 {
     if (!path || !cfg || !out) return bad("null argument");
     *out = nullptr;
-    SceneData sd; std::string err;
-    if (!load_collada_file(path, sd, err)) { g_create_error = err; return MI355RT_E_LOAD; }
-    return finish_create(sd, cfg, out);
+    return no_throw("mi355rt_create_from_collada_file", MI355RT_E_LOAD, [&]() -> int {
+        SceneData sd; std::string err;
+        if (!load_collada_file(path, sd, err)) { g_create_error = err; return MI355RT_E_LOAD; }
+        return finish_create(sd, cfg, out);
+    });
 }
 
 int mi355rt_create_from_scene_file(const char* path, const mi355rt_config* cfg, mi355rt_handle** out)
 {
     if (!path || !cfg || !out) return bad("null argument");
     *out = nullptr;
-    SceneData sd; std::string err;
-    if (!read_scene_file(path, sd, err)) { g_create_error = err; return MI355RT_E_LOAD; }
-    return finish_create(sd, cfg, out);
+    return no_throw("mi355rt_create_from_scene_file", MI355RT_E_LOAD, [&]() -> int {
+        SceneData sd; std::string err;
+        if (!read_scene_file(path, sd, err)) { g_create_error = err; return MI355RT_E_LOAD; }
+        return finish_create(sd, cfg, out);
+    });
 }
 
 void mi355rt_destroy(mi355rt_handle* h) { delete h; }

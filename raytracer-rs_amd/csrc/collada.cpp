@@ -10,6 +10,7 @@
 // the detail text of the reference comes from the un-vendored `parseval` crate.
 #include <cstdlib>
 #include <cstdio>
+#include <exception>
 #include <fstream>
 #include <sstream>
 #include "scene.hpp"
@@ -382,6 +383,9 @@ bool load_collada_str(const std::string& doc, const char* data_dir, SceneData& o
     } catch (const LoadError& e) {
         err = e.msg;
         return false;
+    } catch (const std::exception& e) {     // e.g. std::bad_alloc: an Err(String) like any other, never an exception in the caller
+        err = std::string("cannot load the document: ") + e.what();
+        return false;
     }
 }
 
@@ -439,7 +443,18 @@ bool read_scene_file(const std::string& path, SceneData& s, std::string& err)
     char magic[8];
     if (!f.read(magic, 8) || std::memcmp(magic, kMagic, 8) != 0) { err = "not a scene file: " + path; return false; }
     uint32_t ntri, nmat, nlight, ntex, ncam;
-    if (!get(f, ntri) || !get(f, nmat) || !get(f, nlight) || !get(f, ntex) || !get(f, ncam)) { err = "truncated scene file"; return false; }
+    if (!get(f, ntri) || !get(f, nmat) || !get(f, nlight) || !get(f, ntex) || !get(f, ncam)) { err = "truncated scene file: the header"; return false; }
+    // Every count is checked against what is left of the file before anything is sized by it (each product below is < 2^39: no wrap).
+    f.seekg(0, std::ios::end);
+    const uint64_t len = (uint64_t)f.tellg();
+    f.seekg(28, std::ios::beg);
+    uint64_t left = len - 28;
+    auto take = [&left](uint64_t count, uint64_t each) { if (count > left / each) return false; left -= count * each; return true; };
+    if (!take(ntri, 40)) { err = "truncated scene file: the triangles"; return false; }
+    if (!take(nmat, 20)) { err = "truncated scene file: the materials"; return false; }
+    if (!take(nlight, 24)) { err = "truncated scene file: the lights"; return false; }
+    if (!take(ncam, 68)) { err = "truncated scene file: the cameras"; return false; }
+    if (!take(ntex, 12)) { err = "truncated scene file: the textures"; return false; }
     s = SceneData();
     s.tri_verts.resize((size_t)ntri * 9); s.tri_geom.resize(ntri);
     f.read(reinterpret_cast<char*>(s.tri_verts.data()), s.tri_verts.size() * sizeof(float));
@@ -451,6 +466,9 @@ bool read_scene_file(const std::string& path, SceneData& s, std::string& err)
     for (auto& t : s.textures) {
         uint32_t bytes = 0;
         get(f, t.width); get(f, t.height); get(f, bytes);
+        const uint64_t each = bytes ? 3 : 12;
+        if (t.width && (uint64_t)t.height > left / each / t.width) { err = "truncated scene file: the texels of a texture"; return false; }
+        left -= (uint64_t)t.width * t.height * each;
         t.rgb.resize((size_t)t.width * t.height * 3);
         if (bytes) {
             std::vector<unsigned char> q(t.rgb.size());

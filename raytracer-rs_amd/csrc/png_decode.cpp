@@ -42,6 +42,13 @@ bool load_png_rgb(const std::string& path, TextureData& out, std::string& err)
     if (depth != 8 || interlace != 0) { err = "Unsupported PNG (only 8-bit non-interlaced images are handled)"; return false; }
     int ch = ctype == 0 ? 1 : ctype == 2 ? 3 : ctype == 3 ? 1 : ctype == 4 ? 2 : ctype == 6 ? 4 : 0;
     if (!ch) { err = "Format error decoding Png: bad colour type"; return false; }
+    if (idat.empty()) { err = "Format error decoding Png: missing IDAT"; return false; }
+    if (ctype == 3 && plte.empty()) { err = "Format error decoding Png: missing PLTE"; return false; }
+    // The header is not believed before the data bears it out: deflate expands by less than 1032 : 1 (zlib's technical notes),
+    // so IDAT bytes that cannot inflate to the declared (w * ch + 1) * h are refused before anything of that size is allocated.
+    // Compared by division: w * ch + 1 < 2^35 and the bound < 2^64 / 8 for any file that fits in memory, so nothing here wraps.
+    const uint64_t row = (uint64_t)w * ch + 1, most = ((uint64_t)idat.size() + 1) * 1032;
+    if (h > most / row) { err = "Format error decoding Png: IDAT too short for the declared image size"; return false; }
     size_t stride = (size_t)w * ch;
     std::vector<unsigned char> raw((stride + 1) * h);
     uLongf rawlen = (uLongf)raw.size();

@@ -1,6 +1,6 @@
 """Randomised parity: random scene / size / seed / recursion setting / leaf size / semantics / camera moves / call sequence, the HIP
 path against the CPU oracle bit for bit (film sums, sums of squares, counts, packed pixels, ray counters).  Test infrastructure.
-usage: [FUZZ_WILD=1] [FUZZ_SPP=1] [FUZZ_SOUP=1] [FUZZ_BUILD=1] parity_fuzz.py [cases] [seed]   — prints one line per case, exits 1 on the first difference."""
+usage: [FUZZ_WILD=1] [FUZZ_SPP=1] [FUZZ_SOUP=1] [FUZZ_BUILD=1] [FUZZ_TEX=1] parity_fuzz.py [cases] [seed]   — prints one line per case, exits 1 on the first difference."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,6 +34,22 @@ def soup(base, rng):
     return sc
 
 
+def textured(base, rng):
+    """FUZZ_TEX=1: one to four random float textures (1..9 x 1..9, now and then 640 wide) after the scene's own, and random materials turned into
+    textured ones with a random texture id"""
+    sc = dict(base)
+    sc["textures"] = list(base["textures"])
+    for _ in range(int(rng.integers(1, 5))):
+        w = 640 if rng.random() < 0.15 else int(rng.integers(1, 10))
+        sc["textures"].append(rng.random((int(rng.integers(1, 10)), w, 3)).astype(np.float32))
+    sc["mat_kind"] = np.array(base["mat_kind"], np.uint32); sc["mat_tex"] = np.array(base["mat_tex"], np.uint32)
+    turn = rng.random(len(sc["mat_kind"])) < 0.6
+    turn[int(rng.integers(0, len(turn)))] = True
+    sc["mat_kind"][turn] = 1
+    sc["mat_tex"][turn] = rng.integers(0, len(sc["textures"]), size=int(turn.sum()))
+    return sc
+
+
 def one_case(pkg, O, scenes, rng, verbose=True):
     WILD = bool(os.environ.get("FUZZ_WILD"))
     name = rng.choice(["ico2", "4boxes", "ico3_tex", "thai2"], p=[0.35, 0.2, 0.2, 0.25])
@@ -52,6 +68,8 @@ def one_case(pkg, O, scenes, rng, verbose=True):
     sc = scenes(name)
     if os.environ.get("FUZZ_SOUP") and rng.random() < 0.6:   # FUZZ_SOUP=1: random triangle soups in front of the 4boxes camera — slivers, degenerate and duplicate
         name = "soup"; sc = soup(scenes("4boxes"), rng)        # triangles, axis-parallel ones, huge ones, sizes over four decades
+    if os.environ.get("FUZZ_TEX") and rng.random() < 0.7:    # FUZZ_TEX=1: random textures of odd shapes on random materials (the texel fetch, the texel pool's offsets)
+        name += "+tex"; sc = textured(sc, rng)
     if rng.random() < 0.35:                             # the light somewhere else: in, on or around the geometry (the lights' depth maps, the ray's tail behind the light)
         sc = dict(sc); sc["lights"] = sc["lights"].copy()
         v = sc["tri_verts"].reshape(-1, 3); lo, hi = v.min(0), v.max(0)
@@ -125,6 +143,7 @@ def one_case(pkg, O, scenes, rng, verbose=True):
         assert np.array_equal(rt.get_tonemapped_pixels(), orc.get_tonemapped_pixels()), (desc, steps)
     if verbose:
         print("ok  ", desc, steps, flush=True)
+    return desc
 
 
 def main():
