@@ -16,7 +16,7 @@ constexpr double kReflMinCos = 0.05;      // a clear bin's directions rise above
 constexpr double kReflPadAngle = 1e-3;    // angular pad (radians) around every bin and every occluder's cone
 constexpr float kReflBary = 0.02f;        // the guard: the hit's barycentrics lie inside the triangle by this much (the builder shrinks T by half of it)
 constexpr double kReflHeightUlps = 16.0;  // the guard: the ray's f32 origin lies above T's plane by this many ulps (2^-24) of T's longest edge, times longest edge / smallest height
-constexpr uint32_t kReflBins = 8;         // bins per face edge: 384 bits + the guard's 4 words = 64 B per triangle
+constexpr uint32_t kReflBins = 16;        // bins per face edge: 1536 bits + the guard's 4 words = 208 B per triangle (8: 64 B; MI355RT_REFLECT_MASK_BINS)
 constexpr uint32_t kReflGuardWords = 4;   // per triangle, behind the bits: v0.xyz (f32 bits) and the height margin
 
 struct ReflMask {

@@ -202,8 +202,10 @@ bool Renderer::init(const SceneData& scene, std::string& err, int& code)
         lights[i] = DLight{ l.pos[0], l.pos[1], l.pos[2], l.color[0], l.color[1], l.color[2], 0.0f, 0.0f };
     }
     // Depth cube maps around the lights (lightmap.hpp): shadow rays they prove free are never made.  Resolution: 512 texels per face edge, halved
-    // until the build stays under ~4 M texel updates (a scene of a few huge triangles) and the maps under 64 MiB; padded by ten times the BVH's
-    // own padding (bvh.cpp: 2e-5 of the scene diagonal), the margin the culling mask uses.
+    // until the build stays under ~4 M texel updates (a scene of a few huge triangles) and the maps under 64 MiB; MI355RT_LIGHT_MAP_RES (a power of two,
+    // 16 .. 2048) forces it.  1024 and 2048 prove a quarter and a third of the remaining shadow rays free and were measured: they do not pay on the
+    // frame (profiles/proofs_bench_ab.txt).  Padded by ten times the BVH's own padding (bvh.cpp: 2e-5 of the scene diagonal), the margin
+    // the culling mask uses.
     float* d_light_maps = nullptr; uint32_t light_map_res = 0;
     if (!scene.lights.empty() && scene.lights.size() <= 8 && ntri > 0 && !getenv("MI355RT_NO_LIGHT_MAP")) {
         const auto t_lm = std::chrono::steady_clock::now();
@@ -212,10 +214,12 @@ bool Renderer::init(const SceneData& scene, std::string& err, int& code)
           for (size_t i = 0; i < scene.tri_verts.size(); ++i) { const int a = (int)(i % 3); mn[a] = std::min(mn[a], scene.tri_verts[i]); mx[a] = std::max(mx[a], scene.tri_verts[i]); }
           for (int a = 0; a < 3; ++a) diag2 += ((double)mx[a] - mn[a]) * ((double)mx[a] - mn[a]); }
         const double pad = 2e-4 * std::sqrt(diag2) + 1e-7;
-        uint32_t res = 512;
+        uint32_t res = 512, forced = 0;
+        if (const char* e = getenv("MI355RT_LIGHT_MAP_RES")) { const long v = atol(e); if (v >= 16 && v <= 2048 && (v & (v - 1)) == 0) forced = (uint32_t)v; }
         while (res > 16 && (size_t)6 * res * res * 4 * scene.lights.size() > ((size_t)64 << 20)) res /= 2;
         const uint64_t work_cap = 4ull << 20;
-        for (const LightData& l : scene.lights) while (res > 16 && light_map_work(scene.tri_verts.data(), ntri, l.pos, res) > work_cap) res /= 2;
+        for (const LightData& l : scene.lights) while (!forced && res > 16 && light_map_work(scene.tri_verts.data(), ntri, l.pos, res) > work_cap) res /= 2;
+        if (forced) res = forced;
         std::vector<float> all; all.reserve((size_t)6 * res * res * scene.lights.size());
         bool finite = true;
         for (size_t i = 0; i < scene.lights.size() && finite; ++i) {
@@ -246,7 +250,9 @@ bool Renderer::init(const SceneData& scene, std::string& err, int& code)
         uint64_t budget = 4000000000ull;
         if (const char* e = getenv("MI355RT_REFLECT_MASK_WORK")) budget = std::strtoull(e, nullptr, 10);
         ReflMask rm;
-        if (std::isfinite(diag2) && build_reflect_mask(scene.tri_verts.data(), ntri, 2e-4 * std::sqrt(diag2) + 1e-7, kReflBins, budget, rm)) {
+        uint32_t bins = kReflBins;
+        if (const char* e = getenv("MI355RT_REFLECT_MASK_BINS")) { const int v = atoi(e); if (v == 8 || v == 16) bins = (uint32_t)v; }     // 8: the 64-byte records of the first masks
+        if (std::isfinite(diag2) && build_reflect_mask(scene.tri_verts.data(), ntri, 2e-4 * std::sqrt(diag2) + 1e-7, bins, budget, rm)) {
             if (!upload(d_refl_mask, rm.words.data(), rm.words.size() * sizeof(uint32_t))) return bail();
             refl_bins = rm.bins; refl_stride = rm.stride;
             reflect_mask_info_[2] = (double)rm.clear_bits / ((double)ntri * 6.0 * rm.bins * rm.bins);
