@@ -226,7 +226,8 @@ typedef struct mi355rt_adaptive_stats {
 /* min 16, max 64, batch 16, max_rounds 0, rel_error 0.05, abs_floor 0.02 (measured choice: DESIGN.md §3c) */
 void mi355rt_adaptive_default_config(mi355rt_adaptive_config* cfg);
 /* Rounds as above until no tile is active (or max_rounds).  An invalid config returns MI355RT_E_INVALID, names the field in
- * mi355rt_last_error and leaves the film untouched.  stats may be NULL. */
+ * mi355rt_last_error and leaves the film untouched.  stats may be NULL.  Under a lens other than MI355RT_LENS_PINHOLE this entry is refused; the same loop
+ * built from mi355rt_adaptive_tile_mask and mi355rt_render_tiles (`refine`, see RENDER TILES below) runs under any lens. */
 int mi355rt_render_adaptive(mi355rt_handle* h, const mi355rt_adaptive_config* cfg, mi355rt_adaptive_stats* stats);
 /* The verdict the next round would use, without rendering: out[ty * tiles_x + tx] = 1 if the tile is active, else 0
  * (tiles_x = ceil(width / MI355RT_ADAPTIVE_TILE), ntiles >= tiles_x * ceil(height / MI355RT_ADAPTIVE_TILE)).
@@ -587,6 +588,8 @@ int mi355rt_render_rays(mi355rt_handle* h, const float* rays6, size_t nrays, uin
  *                                          Everything else of GUIDES and FILTER is as written above.
  *   mi355rt_trace_frame_additive           returns 0, and
  *   mi355rt_render_adaptive                returns MI355RT_E_INVALID; both messages name mi355rt_set_lens (their fused launch and tile masks rest on the pinhole path).
+ *   mi355rt_adaptive_tile_mask, mi355rt_render_tiles
+ *                                          work under every lens (RENDER TILES below): the verdict only reads the film, and masked lens passes honour the tile mask.
  *   mi355rt_camera_get_ray, mi355rt_trace_rays, mi355rt_render_rays are unaffected.
  *
  * mi355rt_lens_ray: HOST code — no device, no handle — the lens ray from the outputs of mi355rt_camera_get; flags: bit 0 = MI355RT_FLAG_FIX_ROW_INDEX.  The lens
@@ -606,6 +609,38 @@ int  mi355rt_get_lens(const mi355rt_handle* h, mi355rt_lens* lens);
 int  mi355rt_lens_ray(const float rot16[16], const float orient16[16], const float max_xy[2], uint32_t width, uint32_t height, uint32_t flags,
                       const mi355rt_lens* lens, uint32_t pixel, float xi1, float xi2, float l1, float l2, float ray6[6]);
 int  mi355rt_lens_rays(mi355rt_handle* h, uint32_t spp, uint32_t where, float* rays6, size_t nrays);
+
+/* ---- RENDER TILES: samples into the tiles of a caller's mask, under any lens (no reference counterpart).
+ * One round of the adaptive sampler with the verdict supplied by the caller: a crop, a region of interest, tiles farmed out to several handles and merged
+ * with mi355rt_film_add — or, from mi355rt_adaptive_tile_mask (which only reads the film and works under any lens) and this call, the adaptive loop run on the
+ * caller's side, which under a lens is adaptive depth of field (raytracer_rs_amd/adaptive.py: refine; csrc/raytracer_lib.hpp: RayTracer::refine).
+ *
+ * TILES AND MASK.  The tiles are the image-aligned MI355RT_ADAPTIVE_TILE x MI355RT_ADAPTIVE_TILE tiles of the adaptive section; tile_mask[ty * tiles_x + tx] != 0
+ * selects tile (tx, ty); ntiles must equal tiles_x * tiles_y exactly (tiles_x = ceil(width / MI355RT_ADAPTIVE_TILE), tiles_y likewise from the height).
+ *
+ * THE CALL adds exactly spp samples to every owned pixel of every selected tile.  Sample s of pixel p has the key (p, film_n[p] + s), as mi355rt_render numbers
+ * it; the samples go into the film — and into the direct film with MI355RT_FLAG_DIRECT_FILM — in sample order.  No bit of any other pixel's film or direct
+ * film changes, and no ray of any kind is traced for a pixel outside the selected tiles.  Every pixel therefore ends with the bits of a uniform render of its
+ * own sample count.
+ *
+ * LENS.  Works under MI355RT_LENS_PINHOLE, THIN and ORTHO.  Under the pinhole it uses the tile bins, the culling and the cached verdicts exactly as a round of
+ * mi355rt_render_adaptive does; under a lens it runs lens passes as mi355rt_render does (the primary round walks the tree, nothing is culled).
+ *
+ * COUNTERS (counts may be NULL; mi355rt_last_counts gives the same).  primary == spp * (owned pixels in selected tiles); every other counter counts the added
+ * samples only.  primary_culled follows the adaptive round's rule under the pinhole (culled samples of selected tiles) and is 0 under a lens.
+ *
+ * AROUND THE CALL.  Synchronous like mi355rt_render; a queued mi355rt_render_async and a speculative 50-row frame are settled first.  The touched rows are
+ * marked changed for mi355rt_get_tonemapped_pixels.  Camera, lens, seed, mi355rt_current_row, the guides and the caller-ray mark are untouched; an existing
+ * caller-ray mark is ignored, as mi355rt_render ignores it.  Striped handles render their owned pixels of the selected tiles.  An all-zero mask succeeds,
+ * renders nothing and reports zero counters.
+ *
+ * WHERE.  MI355RT_RAYS_HOST: the mask is host memory and is copied into a handle-owned device buffer of ntiles bytes (allocated on first use, shared with the
+ * adaptive sampler's verdict, counted in mi355rt_hbm_allocated_bytes).  MI355RT_RAYS_DEVICE: the mask is device memory on the handle's device (a torch uint8
+ * tensor's data_ptr); it is read in place — and copied back once, ntiles bytes, for the sample count — and must not change during the call.
+ *
+ * ERRORS.  MI355RT_E_INVALID, the argument named in mi355rt_last_error and nothing changed, for: tile_mask NULL; ntiles != tiles_x * tiles_y; spp == 0; an
+ * unknown `where`; a device group (config.device_count > 1). */
+int  mi355rt_render_tiles(mi355rt_handle* h, const uint8_t* tile_mask, size_t ntiles, uint32_t spp, uint32_t where, mi355rt_ray_counts* counts);
 
 /* SampleGenerator table, sample_generator.rs:15-24: 65 536 x 3 floats */
 int mi355rt_get_sample_table(const mi355rt_handle* h, float* out);

@@ -223,6 +223,7 @@ ABI = [
     ("mi355rt_get_lens", C.c_int, [_H, C.POINTER(Lens)]),
     ("mi355rt_lens_ray", C.c_int, [_F, _F, _F, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Lens), C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, _F]),
     ("mi355rt_lens_rays", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
+    ("mi355rt_render_tiles", C.c_int, [_H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(RayCounts)]),
     ("mi355rt_get_sample_table", C.c_int, [_H, _F]),
     ("mi355rt_debug_sample", C.c_int, [_H, C.c_uint32, C.c_uint32, _F, _F, C.c_size_t]),
     ("mi355rt_debug_numerics", C.c_int, [_H, _F, _F, C.c_size_t, _F, _F, _F]),
@@ -566,6 +567,37 @@ class RayTracer:
             self._check(rc)
         assert rc == int(out.sum())
         return out
+
+    def render_tiles(self, mask, spp):
+        """mi355rt_render_tiles: spp samples into the tiles of `mask`, under whatever lens the handle has.  mask: uint8[tiles_y, tiles_x] or flat — a numpy
+        array (host), or a torch uint8 tensor on the handle's GPU, which is read in place.  Non-zero selects a tile.  Returns the call's counters."""
+        tx = (self.width + ADAPTIVE_TILE - 1) // ADAPTIVE_TILE
+        ty = (self.height + ADAPTIVE_TILE - 1) // ADAPTIVE_TILE
+        if _is_tensor(mask):
+            if mask.device.type != "cuda":
+                raise ValueError("mask: a torch tensor must live on the handle's GPU (it is on %s); pass a numpy array for host memory" % (mask.device,))
+            if mask.device.index not in (None, self.device_index):
+                raise ValueError("mask: the tensor lives on GPU %d, the handle on GPU %d" % (mask.device.index, self.device_index))
+            if str(mask.dtype) != "torch.uint8":
+                raise TypeError("mask: dtype must be uint8, not %s" % (mask.dtype,))
+            if not mask.is_contiguous():
+                raise ValueError("mask: must be C-contiguous")
+            shape, addr, where, keep = tuple(mask.shape), mask.data_ptr(), RAYS_DEVICE, mask
+        else:
+            keep = np.ascontiguousarray(mask)
+            if keep.dtype != np.uint8:
+                raise TypeError("mask: dtype must be uint8, not %s" % keep.dtype)
+            shape, addr, where = keep.shape, keep.ctypes.data, RAYS_HOST
+        if shape not in ((ty, tx), (ty * tx,)):
+            raise ValueError("mask: shape must be (%d, %d) or (%d,), not %s" % (ty, tx, ty * tx, tuple(shape)))
+        rc = RayCounts()
+        self._check(lib().mi355rt_render_tiles(self._h, C.c_void_p(addr), ty * tx, int(spp), where, C.byref(rc)))
+        return rc
+
+    def refine(self, **cfg):
+        """The adaptive loop on the caller's side (adaptive.refine): adaptive_tile_mask, then render_tiles, until no tile is active — under any lens."""
+        from . import adaptive
+        return adaptive.refine(self, **cfg)
 
     def get_denoised_pixels(self, rgb=True, packed=True, split=False, **cfg):
         """The denoised read-out of the film (include/mi355rt.h, mi355rt_get_denoised_pixels).  Fields not given keep

@@ -45,3 +45,42 @@ def pixel_tiles(width, height):
     tx = (width + TILE - 1) // TILE
     y, x = np.mgrid[0:height, 0:width]
     return (y // TILE) * tx + x // TILE
+
+
+def region_mask(width, height, x0, y0, x1, y1):
+    """uint8[tiles_y, tiles_x]: 1 for the tiles the half-open pixel rectangle [x0, x1) x [y0, y1) touches, clipped to the image; an empty rectangle
+    gives an all-zero mask (the mask of RayTracer.render_tiles: a crop or a region of interest)"""
+    tx, ty = (width + TILE - 1) // TILE, (height + TILE - 1) // TILE
+    out = np.zeros((ty, tx), np.uint8)
+    x0, y0, x1, y1 = max(int(x0), 0), max(int(y0), 0), min(int(x1), width), min(int(y1), height)
+    if x0 < x1 and y0 < y1:
+        out[y0 // TILE:(y1 - 1) // TILE + 1, x0 // TILE:(x1 - 1) // TILE + 1] = 1
+    return out
+
+
+def refine(rt, **cfg):
+    """The loop of mi355rt_render_adaptive run on the caller's side, from two calls that work under any lens (include/mi355rt.h, RENDER TILES): take the
+    verdict with rt.adaptive_tile_mask(**cfg); stop when no tile is active or max_rounds rounds have run; otherwise rt.render_tiles(mask, batch_spp).
+    Under the pinhole the film and the stats are render_adaptive's bit for bit; under a lens this is adaptive depth of field.  Fields not given keep
+    mi355rt_adaptive_default_config's values.  Returns the keys of AdaptiveStats (rounds, tiles, tiles_active_first, tiles_active_last, samples_added —
+    the sum of the calls' primary) and the rounds' summed primary, bounce, shadow and primary_hits."""
+    from . import adaptive_config
+    c = adaptive_config(**cfg)
+    batch_spp, max_rounds = int(c.batch_spp), int(c.max_rounds)
+    tx = (rt.width + TILE - 1) // TILE
+    tile_rows = {int(r) // TILE for r in rt.owned_rows()}
+    out = dict(rounds=0, tiles=len(tile_rows) * tx, tiles_active_first=0, tiles_active_last=0, samples_added=0, primary=0, bounce=0, shadow=0, primary_hits=0)
+    while True:
+        mask = rt.adaptive_tile_mask(**cfg)
+        active = int(np.count_nonzero(mask))
+        if out["rounds"] == 0:
+            out["tiles_active_first"] = active
+        out["tiles_active_last"] = active
+        if active == 0 or (max_rounds and out["rounds"] >= max_rounds):
+            break
+        rc = rt.render_tiles(mask, batch_spp)
+        out["rounds"] += 1
+        for k in ("primary", "bounce", "shadow", "primary_hits"):
+            out[k] += int(getattr(rc, k))
+    out["samples_added"] = out["primary"]
+    return out

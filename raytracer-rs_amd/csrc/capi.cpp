@@ -364,6 +364,21 @@ int mi355rt_render_adaptive(mi355rt_handle* h, const mi355rt_adaptive_config* cf
     return ok ? MI355RT_OK : MI355RT_E_HIP;
 }
 
+int mi355rt_render_tiles(mi355rt_handle* h, const uint8_t* tile_mask, size_t ntiles, uint32_t spp, uint32_t where, mi355rt_ray_counts* counts)
+{
+    if (!h) return MI355RT_E_INVALID;
+    const char* e = nullptr;
+    if (h->g->size() > 1) e = "mi355rt_render_tiles: not available on a device group (config.device_count > 1)";
+    else if (!tile_mask) e = "mi355rt_render_tiles: tile_mask is NULL";
+    else if (ntiles != (size_t)h->r->tiles_x() * h->r->tiles_y()) e = "mi355rt_render_tiles: ntiles must equal tiles_x * tiles_y";
+    else if (spp == 0) e = "mi355rt_render_tiles: spp must be >= 1";
+    else if (where > MI355RT_RAYS_DEVICE) e = "mi355rt_render_tiles: unknown `where` (MI355RT_RAYS_HOST or MI355RT_RAYS_DEVICE)";
+    if (e) { h->r->last_error = e; return MI355RT_E_INVALID; }
+    const bool ok = h->r->render_tiles(tile_mask, spp, where == MI355RT_RAYS_DEVICE);
+    if (counts) *counts = h->r->counts;
+    return ok ? MI355RT_OK : MI355RT_E_HIP;
+}
+
 int mi355rt_adaptive_tile_mask(mi355rt_handle* h, const mi355rt_adaptive_config* cfg, uint8_t* out, size_t ntiles)
 {
     if (!adaptive_args_ok(h, cfg)) return MI355RT_E_INVALID;

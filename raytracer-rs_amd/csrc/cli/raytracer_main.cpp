@@ -18,6 +18,10 @@
 // here (ortho_rays below: the arithmetic of raytracer_rs_amd.cameras.orthographic, so both paths write the same bytes).
 // Lens models (mi355rt_set_lens): --lens thin --lens-radius R --focus F (depth of field) and --lens ortho --lens-width W (parallel projection), with --spp N:
 // the rays are made on the device, so --denoise, --denoise-split, the film files and the display options all apply; they exclude --adaptive, --gpus and -i.
+// Tiles (mi355rt_render_tiles): --region X0,Y0,X1,Y1 with --spp N renders only the tiles the half-open pixel rectangle touches; --refine REL runs the adaptive
+// loop on this side (RayTracer::refine: mi355rt_adaptive_tile_mask, then mi355rt_render_tiles) with --abs-floor, --min-spp, --max-spp and --batch as --adaptive
+// takes them, and prints the line --adaptive prints.  Both work with --lens (--refine is adaptive sampling's way under a lens) and exclude --gpus, -i and --adaptive;
+// --refine excludes --spp.
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -124,7 +128,8 @@ int main(int argc, char** argv)
     mi355rt_display_default_config(&dcfg_display);
     mi355rt_lens lens;
     mi355rt_lens_default(&lens);
-    bool have_lens = false;
+    bool have_lens = false, have_region = false, refine = false;
+    long long region[4] = { 0, 0, 0, 0 };
     auto parse_float = [](const char* s, float& out) { if (!s || !*s) return false; char* end = nullptr; const float f = std::strtof(s, &end); if (*end != '\0' || !std::isfinite(f)) return false; out = f; return true; };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -172,6 +177,13 @@ int main(int argc, char** argv)
         else if (a == "--lens-radius") { float f; if (parse_float(take(), f)) lens.radius = f; }
         else if (a == "--focus") { float f; if (parse_float(take(), f)) lens.focus = f; }
         else if (a == "--lens-width") { float f; if (parse_float(take(), f)) lens.width_world = f; }
+        else if (a == "--refine") { float f; if (parse_float(take(), f)) { acfg.rel_error = f; refine = true; } }
+        else if (a == "--region") {
+            const char* r = take();
+            char tail = 0;
+            if (!r || std::sscanf(r, "%lld,%lld,%lld,%lld%c", &region[0], &region[1], &region[2], &region[3], &tail) != 4) { std::fprintf(stderr, "Error: --region takes X0,Y0,X1,Y1\n"); return 1; }
+            have_region = true;
+        }
         else if (a == "--adaptive") { float f; if (parse_float(take(), f)) { acfg.rel_error = f; adaptive = true; } }
         else if (a == "--abs-floor") { float f; if (parse_float(take(), f)) acfg.abs_floor = f; }
         else if (a == "--min-spp") { size_t t; if (parse_usize(take(), t)) acfg.min_spp = (uint32_t)t; }
@@ -185,16 +197,38 @@ int main(int argc, char** argv)
                         "                 [--exposure F | --auto-exposure [--key F]] [--curve reinhard|reinhard-white|aces|clamp] [--white F] [--srgb]\n"
                         "                 [--ortho-width W]   (with --spp: an orthographic view W world units wide, through mi355rt_render_rays)\n"
                         "                 [--lens thin --lens-radius R --focus F | --lens ortho --lens-width W]   (with --spp: depth of field / an orthographic\n"
-                        "                                     view made on the device, mi355rt_set_lens; excludes --adaptive, --gpus and -i)\n");
+                        "                                     view made on the device, mi355rt_set_lens; excludes --adaptive, --gpus and -i; adaptive sampling\n"
+                        "                                     under a lens: --refine)\n"
+                        "                 [--region X0,Y0,X1,Y1]   (with --spp: only the tiles the pixel rectangle touches, mi355rt_render_tiles; allowed with --lens;\n"
+                        "                                     excludes --gpus, -i and --adaptive)\n"
+                        "                 [--refine REL [--abs-floor F] [--min-spp N] [--max-spp N] [--batch N]]   (the adaptive loop from mi355rt_adaptive_tile_mask and\n"
+                        "                                     mi355rt_render_tiles: the way to sample adaptively under --lens; excludes --spp, --gpus, -i and --adaptive)\n");
             return 0;
         }
     }
     if (ortho && (!spp || adaptive || denoise || denoise_split || gpus > 1)) { std::fprintf(stderr, "Error: --ortho-width needs --spp and excludes --adaptive, --denoise, --denoise-split and --gpus\n"); return 1; }
-    if (have_lens && (!spp || adaptive || gpus > 1 || have_iterations || ortho)) { std::fprintf(stderr, "Error: --lens thin / ortho needs --spp and excludes --adaptive, --gpus, -i and --ortho-width\n"); return 1; }
+    // the option given together with --region / --refine that it excludes (null: none)
+    auto excluded_by_tiles = [&](bool with_spp) -> const char* {
+        if (with_spp && spp) return "--spp";
+        if (gpus > 1) return "--gpus";
+        if (have_iterations) return "-i";
+        if (adaptive) return "--adaptive";
+        if (ortho) return "--ortho-width";
+        return nullptr;
+    };
+    if (have_region) {
+        const char* x = refine ? "--refine" : excluded_by_tiles(false);
+        if (x) { std::fprintf(stderr, "Error: --region excludes %s\n", x); return 1; }
+        if (!spp) { std::fprintf(stderr, "Error: --region needs --spp\n"); return 1; }
+    }
+    if (refine) {
+        if (const char* x = excluded_by_tiles(true)) { std::fprintf(stderr, "Error: --refine excludes %s\n", x); return 1; }
+    }
+    if (have_lens && ((!spp && !refine) || adaptive || gpus > 1 || have_iterations || ortho)) { std::fprintf(stderr, "Error: --lens thin / ortho needs --spp or --refine and excludes --adaptive, --gpus, -i and --ortho-width\n"); return 1; }
     if (have_exposure && dcfg_display.auto_exposure) { std::fprintf(stderr, "Error: --exposure and --auto-exposure exclude each other\n"); return 1; }
     std::printf("max triangles per leaf: %zu\n", max_triangles);      // main.rs:66
     if (have_iterations) std::printf("will quit after %zu frame iterations\n", frame_iterations);   // main.rs:73
-    if (!have_iterations) { frame_iterations = (spp || adaptive) ? 1 : (height + 49) / 50; }   // headless: one sweep of the frame
+    if (!have_iterations) { frame_iterations = (spp || adaptive || refine) ? 1 : (height + 49) / 50; }   // headless: one sweep of the frame
 
     try {
         mi355rt_config cfg = raytracer_lib::make_config(max_triangles, width, height);
@@ -220,9 +254,17 @@ int main(int argc, char** argv)
                 std::printf("adaptive: %u rounds, %u of %u tiles active at the first verdict, %u at the last, %llu samples added (%.2f per owned pixel)  %.3f ms\n",
                             st.rounds, st.tiles_active_first, st.tiles, st.tiles_active_last, (unsigned long long)st.samples_added,
                             (double)st.samples_added / ((double)mi355rt_owned_rows(rt.handle()) * (double)width), c.total_ms);
+            } else if (refine) {
+                mi355rt_ray_counts c{};
+                const mi355rt_adaptive_stats st = rt.refine(acfg, &c);
+                num_primary_rays = (uint32_t)c.primary;
+                std::printf("adaptive: %u rounds, %u of %u tiles active at the first verdict, %u at the last, %llu samples added (%.2f per owned pixel)  %.3f ms\n",
+                            st.rounds, st.tiles_active_first, st.tiles, st.tiles_active_last, (unsigned long long)st.samples_added,
+                            (double)st.samples_added / ((double)mi355rt_owned_rows(rt.handle()) * (double)width), c.total_ms);
             } else if (spp) {
                 mi355rt_ray_counts c;
-                if (ortho) {
+                if (have_region) c = rt.render_tiles(rt.region_mask(region[0], region[1], region[2], region[3]), (uint32_t)spp);
+                else if (ortho) {
                     float rot[16], orient[16], max_xy[2];
                     mi355rt_camera_get(rt.handle(), rot, orient, max_xy);
                     std::vector<uint32_t> film_n(width * height);

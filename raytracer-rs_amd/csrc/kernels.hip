@@ -261,7 +261,15 @@ struct __attribute__((packed, aligned(4))) RayKey { uint32_t pixel, sampleno; };
 // RAYS is the feed of the primary round: kFeedCamera (the pinhole camera, everything below the two branches), kFeedRays (the caller's buffer),
 // kFeedLensThin / kFeedLensOrtho (the handle's lens, cam.lens — the ray is made in registers from the camera and ALL FOUR words of the
 // jitter's hash; no buffer.  One instantiation per model: with both models behind a wave-uniform branch the primary shade kernels spilled).
-constexpr uint32_t kFeedCamera = 0u, kFeedRays = 1u, kFeedLensThin = 2u, kFeedLensOrtho = 3u;
+// kFeedLensThinMasked / kFeedLensOrthoMasked (mi355rt_render_tiles under a lens): the lens feeds of a pass with a tile mask (DPass::tile_active).  Instantiations of
+// their own beside the unmasked ones: taught the mask in place, the THIN shade kernel without the confirm walk spilled (profiles/tiles_kernel_resources.txt), and an
+// unmasked frame under a lens launches exactly what it launched before.
+constexpr uint32_t kFeedCamera = 0u, kFeedRays = 1u, kFeedLensThin = 2u, kFeedLensOrtho = 3u, kFeedLensThinMasked = 4u, kFeedLensOrthoMasked = 5u;
+template <uint32_t RAYS> constexpr bool kFeedLens = RAYS >= kFeedLensThin;
+template <uint32_t RAYS> constexpr bool kFeedThin = RAYS == kFeedLensThin || RAYS == kFeedLensThinMasked;
+// The feeds whose primary round honours the tile mask: the pinhole camera and the masked lens feeds, whose samples are pixels of the film.  Never the caller's rays.
+// Tested with `if constexpr`, so that an instantiation holds only its own feed's code.
+template <uint32_t RAYS> constexpr bool kFeedMasked = RAYS == kFeedCamera || RAYS == kFeedLensThinMasked || RAYS == kFeedLensOrthoMasked;
 template <uint32_t RAYS = kFeedCamera>
 __device__ __forceinline__ void primary_sample(const DCamera& cam, const DPass& ps, const uint32_t* __restrict__ film_n, uint32_t gi,
                                                uint32_t& pixel, uint32_t& sampleno, f3& o, f3& d)
@@ -283,14 +291,14 @@ __device__ __forceinline__ void primary_sample(const DCamera& cam, const DPass& 
         o = mk3(a.x, a.y, a.z); d = mk3(b.x, b.y, b.z);
         return;
     }
-    if constexpr (RAYS == kFeedLensThin || RAYS == kFeedLensOrtho) {
+    if constexpr (kFeedLens<RAYS>) {
         uint32_t s, p;
         sample_of(ps, gi, s, p);
         pixel = pass_pixel(ps, cam.width, p);
         sampleno = film_n[pixel] + s;
         uint32_t h0 = pixel, h1 = sampleno, h2 = 0u, h3 = ps.seed;
         pcg4d(h0, h1, h2, h3);
-        lens_ray<RAYS == kFeedLensThin ? kLensThin : kLensOrtho>(cam.rot, cam.origin, cam.max_x, cam.max_y, cam.width, cam.height, ps.flags, cam.lens, pixel,
+        lens_ray<kFeedThin<RAYS> ? kLensThin : kLensOrtho>(cam.rot, cam.origin, cam.max_x, cam.max_y, cam.width, cam.height, ps.flags, cam.lens, pixel,
                                                                   u01(h0), u01(h1), u01(h2), u01(h3), o.x, o.y, o.z, d.x, d.y, d.z);
         return;
     }
@@ -389,9 +397,13 @@ __device__ __forceinline__ uint32_t chunk_active_samples(const DCamera& cam, con
 
 // the verdict, cached per pixel block of the pass when the host had it computed (DPass::block_culled), else computed here.  A chunk without a sample
 // in an active tile (adaptive sampling) is treated as culled by every launch: no rays, no slots, never on a live list.
+// RAYS: a masked lens feed (kFeedLensThinMasked, kFeedLensOrthoMasked) has the tile part only — nothing that describes the pinhole camera's rays holds under a lens (cam.cull_valid is 0 and
+// ps.block_culled null there anyway).
+template <uint32_t RAYS = kFeedCamera>
 __device__ __forceinline__ bool chunk_culled(const DCamera& cam, const DPass& ps, uint32_t chunk, uint32_t n)
 {
     if (ps.tile_active != nullptr && chunk_active_samples(cam, ps, chunk, n) == 0u) return true;
+    if constexpr (RAYS != kFeedCamera) return false;
     if (ps.block_culled != nullptr) return ((const_u1_ptr)(uintptr_t)ps.block_culled)[chunk % ps.cull_blocks] != 0u;
     return chunk_is_culled(cam, ps, chunk, n);
 }
@@ -441,7 +453,8 @@ __device__ __forceinline__ void store_blocked(float* __restrict__ slot_L, uint32
 // intersector's answers and settles the shadow predicate.  CONFIRM == false (MI355RT_FLAG_TRUE_CLOSEST_HIT): the shadow
 // predicate is decided here with the interval trick of traverse.hpp and unblocked light terms are stored directly.
 // RAYS (PRIMARY only; primary_sample): kFeedRays / kFeedLensThin, kFeedLensOrtho — the primary rays come from DPass::ray_in / from the handle's lens, and nothing is culled
-// (the culling rectangles, the mask and the cached verdicts describe the pinhole camera's rays).
+// (the culling rectangles, the mask and the cached verdicts describe the pinhole camera's rays).  The tile mask (DPass::tile_active) describes pixels, not rays: the lens
+// feeds honour it like the pinhole feed (kFeedMasked) — a chunk without an active sample hands out no ray, an inactive pixel's lane is finished at once.
 template <bool PRIMARY, bool COUNT, bool SINGLE, bool CONFIRM, uint32_t RAYS = kFeedCamera>
 __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam, const DPass& ps,
                                            const float4* __restrict__ in_q, const uint2* __restrict__ in_counts,
@@ -512,7 +525,7 @@ __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam,
                 w_chunk = bcast_first(c); w_next = 0u;
                 if (PRIMARY) {
                     w_nrad = min(ps.chunk, ps.nsamples - w_chunk * ps.chunk);
-                    if (!RAYS && chunk_culled(cam, ps, w_chunk, w_nrad)) w_nrad = 0u;    // the shade kernel makes the same decision
+                    if constexpr (kFeedMasked<RAYS>) { if (chunk_culled<RAYS>(cam, ps, w_chunk, w_nrad)) w_nrad = 0u; }    // the shade kernel makes the same decision
                     w_nrad = bcast_first(w_nrad);
                     w_ntot = w_nrad;
                 }
@@ -537,7 +550,7 @@ __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam,
                     uint32_t pixel, sampleno;
                     primary_sample<RAYS>(cam, ps, film_n, w_chunk * ps.chunk + i, pixel, sampleno, o, d);
                     rec = w_chunk * ps.region + i;
-                    if (!RAYS && !pixel_active(ps, cam.width, pixel)) start = kNodeFin;    // adaptive sampling: finished at once, a miss that was never traced
+                    if constexpr (kFeedMasked<RAYS>) { if (!pixel_active(ps, cam.width, pixel)) start = kNodeFin; }    // adaptive sampling: finished at once, a miss that was never traced
                 } else {
                     // record index in 32 bits, byte offsets in 64 (a whole 1080p x 64 spp frame in ONE pass is 531 M records of 16 B per plane);
                     // the planes of the queue are wave-uniform base pointers
@@ -557,6 +570,8 @@ __device__ __forceinline__ void trace_wave(const DScene& sc, const DCamera& cam,
                 }
                 ray_init(rs, o, d, shadow, start);
             }
+            // instrumented lens builds: a masked-out lane took no ray (MI355RT_FLAG_COUNT_STEPS; mi355rt_debug_rays_read counts rays, not lanes)
+            if constexpr (COUNT && PRIMARY && kFeedLens<RAYS> && kFeedMasked<RAYS>) acc_rr -= (uint32_t)__popcll(__ballot(rs.node == kNodeFin) & idle);
             w_next += min((uint32_t)__popcll(idle), avail);
             idle = __ballot(rs.node == kNodeIdle);
         }
@@ -692,7 +707,7 @@ __global__ __launch_bounds__(kBlock) void trace_octree_kernel(DScene sc, DCamera
                 uint32_t pixel, sampleno;
                 primary_sample<RAYS>(cam, ps, film_n, chunk * ps.chunk + i, pixel, sampleno, o, d);
                 r = (size_t)chunk * ps.region + i;
-                on = RAYS != 0u || pixel_active(ps, cam.width, pixel);          // adaptive sampling: an inactive pixel's sample is a miss that is never traced
+                if constexpr (kFeedMasked<RAYS>) on = pixel_active(ps, cam.width, pixel);          // adaptive sampling: an inactive pixel's sample is a miss that is never traced
             } else {
                 r = record_index(ps, chunk, i, n_rad);
                 const float4 r0 = in_q[r];
@@ -920,7 +935,9 @@ __device__ __forceinline__ bool reflection_proves_miss(const DScene& sc, uint32_
 // its (zeroed) light-term slot and is shaded no further: it resolves to black like a miss (mod.rs:99-100).
 // RASTER (primary round of the wavefront kernels, tile bins built): the closest hits of the chunk's primary rays are found right here (raster_tile) and
 // handed to the shading loop through LDS (lds_hits: one float4 per sample of a chunk) — no primary trace launch, no hit flags and no hit records in HBM.
-// RAYS (primary round of a ray-fed or a lens pass): the ray is primary_sample<RAYS>'s, no chunk is culled, and (kFeedRays) with DPass::ray_hit
+// RAYS (primary round of a ray-fed or a lens pass): the ray is primary_sample<RAYS>'s, no chunk is culled (a lens pass with a tile mask, §3j: a chunk
+// without an active sample was not traced and an inactive pixel's sample is a miss whose hit record is never read — the mask is tested per lane in the compaction loop: as
+// an up-front chunk branch like the pinhole feed's it cost the THIN kernel without the confirm walk 12 bytes of scratch), and (kFeedRays) with DPass::ray_hit
 // the final hit of every sample — after the confirm walk — is kept for resolve_rays_kernel (the hit records themselves are reused by the later rounds).
 template <bool PRIMARY, class List, bool WALK = false, bool RASTER = false, uint32_t RAYS = kFeedCamera>
 __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam, const DPass& ps, uint32_t level, uint32_t chunk, const List list,
@@ -936,7 +953,7 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
     {
         uint32_t n_rad = PRIMARY ? min(ps.chunk, ps.nsamples - chunk * ps.chunk) : in_nrad;
         const size_t base = (size_t)chunk * ps.region;
-        if (PRIMARY && !RAYS && chunk_culled(cam, ps, chunk, n_rad)) {
+        if constexpr (PRIMARY && RAYS == kFeedCamera) if (chunk_culled(cam, ps, chunk, n_rad)) {
             // no hit records were written for this chunk: every sample is a miss (with cached verdicts the resolve launch knows that too and reads no slot)
             if (ps.block_culled == nullptr) for (uint32_t i = (uint32_t)lane; i < n_rad; i += 64u) sample_slot[chunk * ps.chunk + i] = kMiss;
             // high half: primary samples skipped by the frustum culling (adaptive sampling: only those of active tiles — the others are not samples of the call)
@@ -958,6 +975,11 @@ __device__ __forceinline__ void shade_chunk(const DScene& sc, const DCamera& cam
                 if (acc_tris) *acc_tris += (unsigned long long)tested * (unsigned long long)__popcll(__ballot(in));
                 valid = in && bprim != kMiss;
                 found = make_float4(bt, bu, bv, __uint_as_float(bprim));
+            } else if constexpr (PRIMARY && kFeedLens<RAYS> && kFeedMasked<RAYS>) {
+                // a masked lens pass: the trace launch wrote no record for a chunk without an active sample (trace_wave), so an inactive pixel's record is not read at all —
+                // its sample is a miss, marked kMiss below and counted nowhere
+                valid = false;
+                if (i < n_rad) { uint32_t s, p; sample_of(ps, chunk * ps.chunk + i, s, p); valid = pixel_active(ps, cam.width, pass_pixel(ps, cam.width, p)) && ld1<2>(&ps.hit_prim[base + i]) != kMiss; }
             } else valid = i < n_rad && ld1<2>(&ps.hit_prim[base + i]) != kMiss;
             uint32_t n_new;
             const uint32_t pos = wave_append(valid, cnt, n_new);
@@ -1931,7 +1953,9 @@ hipError_t launch_trace(hipStream_t stream, int num_cus, bool primary, bool coun
 {
 #define MI355RT_TRACE_ARGS stream, num_cus, sc, cam, ps, in_q, in_counts, hits, cursor, slot_L, film_n, counters
     if (rays && !primary) return hipErrorInvalidValue;         // only the primary round of a pass is ray-fed
-    if (rays > kFeedLensOrtho) return hipErrorInvalidValue;
+    if (rays > kFeedLensOrthoMasked) return hipErrorInvalidValue;
+    if (rays == kFeedLensThinMasked) return count ? launch_trace_variant<true, true, true, kFeedLensThinMasked>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true, kFeedLensThinMasked>(MI355RT_TRACE_ARGS);
+    if (rays == kFeedLensOrthoMasked) return count ? launch_trace_variant<true, true, true, kFeedLensOrthoMasked>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true, kFeedLensOrthoMasked>(MI355RT_TRACE_ARGS);
     if (rays == kFeedLensThin) return count ? launch_trace_variant<true, true, true, kFeedLensThin>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true, kFeedLensThin>(MI355RT_TRACE_ARGS);
     if (rays == kFeedLensOrtho) return count ? launch_trace_variant<true, true, true, kFeedLensOrtho>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true, kFeedLensOrtho>(MI355RT_TRACE_ARGS);
     if (rays) return count ? launch_trace_variant<true, true, true, kFeedRays>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true, kFeedRays>(MI355RT_TRACE_ARGS);
@@ -1962,13 +1986,15 @@ hipError_t launch_cull_blocks(hipStream_t stream, const DCamera& cam, const DPas
 hipError_t launch_trace_octree(hipStream_t stream, int num_cus, bool primary, const DScene& sc, const DCamera& cam, const DPass& ps,
                                const void* in_q, const void* in_counts, void* hits, float* slot_L, const uint32_t* film_n, uint32_t rays)
 {
-    if ((rays && !primary) || rays > kFeedLensOrtho) return hipErrorInvalidValue;
+    if ((rays && !primary) || rays > kFeedLensOrthoMasked) return hipErrorInvalidValue;
     unsigned blocks = (ps.nchunks + kWavesPerBlock - 1) / kWavesPerBlock;
     const unsigned cap = (unsigned)num_cus * 4u;
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     dim3 grid(blocks), block(kBlock);
-    if (rays == kFeedLensThin) hipLaunchKernelGGL((trace_octree_kernel<true, kFeedLensThin>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
+    if (rays == kFeedLensThinMasked) hipLaunchKernelGGL((trace_octree_kernel<true, kFeedLensThinMasked>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
+    else if (rays == kFeedLensOrthoMasked) hipLaunchKernelGGL((trace_octree_kernel<true, kFeedLensOrthoMasked>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
+    else if (rays == kFeedLensThin) hipLaunchKernelGGL((trace_octree_kernel<true, kFeedLensThin>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
     else if (rays == kFeedLensOrtho) hipLaunchKernelGGL((trace_octree_kernel<true, kFeedLensOrtho>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
     else if (rays) hipLaunchKernelGGL((trace_octree_kernel<true, kFeedRays>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
     else if (primary) hipLaunchKernelGGL((trace_octree_kernel<true>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
@@ -1980,7 +2006,7 @@ hipError_t launch_shade(hipStream_t stream, int num_cus, bool primary, bool walk
                         const void* in_q, const void* in_counts, const void* hits, void* out_q, void* out_counts, uint32_t* cursor,
                         float* slot_L, uint32_t* sample_slot, const uint32_t* film_n, DCounters* counters, bool raster, uint32_t rays)
 {
-    if ((rays && (!primary || raster)) || rays > kFeedLensOrtho) return hipErrorInvalidValue;      // a ray-fed or lens primary round walks the tree: no pinhole camera, no tile bins
+    if ((rays && (!primary || raster)) || rays > kFeedLensOrthoMasked) return hipErrorInvalidValue;      // a ray-fed or lens primary round walks the tree: no pinhole camera, no tile bins
     // raster (primary round only): the kernel finds the primary rays' closest hits itself, through the tile bins (cam.tile_ofs), and keeps them in LDS
     const size_t lds = (size_t)ps.list_cap * kWavesPerBlock * sizeof(uint32_t) + (raster ? (size_t)ps.chunk * kWavesPerBlock * sizeof(float4) : 0);
     unsigned blocks = (ps.nchunks + kWavesPerBlock - 1) / kWavesPerBlock;
@@ -1989,7 +2015,11 @@ hipError_t launch_shade(hipStream_t stream, int num_cus, bool primary, bool walk
     if (blocks < 1) blocks = 1;
     dim3 grid(blocks), block(kBlock);
 #define MI355RT_SHADE_ARGS grid, block, lds, stream, sc, cam, ps, level, (const float4*)in_q, (const uint2*)in_counts, (const float4*)hits, (float4*)out_q, (uint2*)out_counts, cursor, slot_L, sample_slot, film_n, counters
-    if (rays == kFeedLensThin && walk) hipLaunchKernelGGL((shade_kernel<true, true, false, kFeedLensThin>), MI355RT_SHADE_ARGS);
+    if (rays == kFeedLensThinMasked && walk) hipLaunchKernelGGL((shade_kernel<true, true, false, kFeedLensThinMasked>), MI355RT_SHADE_ARGS);
+    else if (rays == kFeedLensThinMasked) hipLaunchKernelGGL((shade_kernel<true, false, false, kFeedLensThinMasked>), MI355RT_SHADE_ARGS);
+    else if (rays == kFeedLensOrthoMasked && walk) hipLaunchKernelGGL((shade_kernel<true, true, false, kFeedLensOrthoMasked>), MI355RT_SHADE_ARGS);
+    else if (rays == kFeedLensOrthoMasked) hipLaunchKernelGGL((shade_kernel<true, false, false, kFeedLensOrthoMasked>), MI355RT_SHADE_ARGS);
+    else if (rays == kFeedLensThin && walk) hipLaunchKernelGGL((shade_kernel<true, true, false, kFeedLensThin>), MI355RT_SHADE_ARGS);
     else if (rays == kFeedLensThin) hipLaunchKernelGGL((shade_kernel<true, false, false, kFeedLensThin>), MI355RT_SHADE_ARGS);
     else if (rays == kFeedLensOrtho && walk) hipLaunchKernelGGL((shade_kernel<true, true, false, kFeedLensOrtho>), MI355RT_SHADE_ARGS);
     else if (rays == kFeedLensOrtho) hipLaunchKernelGGL((shade_kernel<true, false, false, kFeedLensOrtho>), MI355RT_SHADE_ARGS);

@@ -8,7 +8,7 @@ namespace mi355rt {
 
 hipError_t launch_trace(hipStream_t stream, int num_cus, bool primary, bool count, bool confirm, const DScene& sc, const DCamera& cam, const DPass& ps,
                         const void* in_q, const void* in_counts, void* hits, uint32_t* cursor,
-                        float* slot_L, const uint32_t* film_n, DCounters* counters, uint32_t rays = 0);   // rays: the feed of the primary round — 0 the pinhole camera, 1 a ray-fed pass (DPass::ray_in), 2 / 3 the handle's THIN / ORTHO lens (DCamera::lens)
+                        float* slot_L, const uint32_t* film_n, DCounters* counters, uint32_t rays = 0);   // rays: the feed of the primary round — 0 the pinhole camera, 1 a ray-fed pass (DPass::ray_in), 2 / 3 the handle's THIN / ORTHO lens (DCamera::lens), 4 / 5 the same with a tile mask (DPass::tile_active)
 // culling verdicts of the pass's pixel blocks (DPass::block_culled): out[b] = chunk b (first sample group) is culled
 hipError_t launch_cull_blocks(hipStream_t stream, const DCamera& cam, const DPass& ps, uint32_t nblocks, uint32_t* out);
 hipError_t launch_trace_octree(hipStream_t stream, int num_cus, bool primary, const DScene& sc, const DCamera& cam, const DPass& ps,

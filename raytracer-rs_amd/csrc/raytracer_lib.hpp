@@ -107,6 +107,51 @@ public:
         if (mi355rt_render_adaptive(h_, &cfg, &st) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
         return st;
     }
+    // mi355rt_render_tiles (include/mi355rt.h, RENDER TILES): spp samples into the tiles of `mask` (tiles_x * tiles_y bytes, host memory), under whatever lens the handle has
+    mi355rt_ray_counts render_tiles(const std::vector<uint8_t>& mask, uint32_t spp)
+    {
+        mi355rt_ray_counts c{};
+        if (mi355rt_render_tiles(h_, mask.data(), mask.size(), spp, MI355RT_RAYS_HOST, &c) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+        return c;
+    }
+    // the tiles a half-open pixel rectangle [x0, x1) x [y0, y1) touches, clipped to the image (the mask of render_tiles; adaptive.region_mask of the Python package)
+    std::vector<uint8_t> region_mask(long long x0, long long y0, long long x1, long long y1) const
+    {
+        const long long w = mi355rt_width(h_), h = mi355rt_height(h_), T = MI355RT_ADAPTIVE_TILE, tx = (w + T - 1) / T, ty = (h + T - 1) / T;
+        std::vector<uint8_t> m((size_t)(tx * ty), 0);
+        x0 = x0 < 0 ? 0 : x0; y0 = y0 < 0 ? 0 : y0; x1 = x1 > w ? w : x1; y1 = y1 > h ? h : y1;
+        if (x0 < x1 && y0 < y1)
+            for (long long t = y0 / T; t <= (y1 - 1) / T; ++t)
+                for (long long x = x0 / T; x <= (x1 - 1) / T; ++x) m[(size_t)(t * tx + x)] = 1;
+        return m;
+    }
+    // The loop of mi355rt_render_adaptive on the caller's side, from two calls that work under any lens: the verdict (mi355rt_adaptive_tile_mask), then render_tiles,
+    // until no tile is active or cfg.max_rounds rounds have run.  samples_added is the sum of the calls' primary; `sum` (optional) receives the rounds' summed
+    // primary, bounce, shadow, primary_hits and total_ms.
+    mi355rt_adaptive_stats refine(const mi355rt_adaptive_config& cfg, mi355rt_ray_counts* sum = nullptr)
+    {
+        const uint32_t T = MI355RT_ADAPTIVE_TILE, tx = (mi355rt_width(h_) + T - 1) / T, ty = (mi355rt_height(h_) + T - 1) / T;
+        mi355rt_adaptive_stats st{};
+        mi355rt_ray_counts total{};
+        std::vector<uint32_t> rows(mi355rt_owned_rows(h_));
+        if (!rows.empty() && mi355rt_owned_row_list(h_, rows.data(), rows.size()) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+        std::vector<uint8_t> tile_row(ty, 0), mask((size_t)tx * ty);
+        for (uint32_t r : rows) tile_row[r / T] = 1;
+        for (uint8_t t : tile_row) st.tiles += t ? tx : 0u;
+        for (;;) {
+            const int active = mi355rt_adaptive_tile_mask(h_, &cfg, mask.data(), mask.size());
+            if (active < 0) throw std::runtime_error(mi355rt_last_error(h_));
+            if (st.rounds == 0) st.tiles_active_first = (uint32_t)active;
+            st.tiles_active_last = (uint32_t)active;
+            if (active == 0 || (cfg.max_rounds && st.rounds >= cfg.max_rounds)) break;
+            const mi355rt_ray_counts c = render_tiles(mask, cfg.batch_spp);
+            ++st.rounds;
+            total.primary += c.primary; total.bounce += c.bounce; total.shadow += c.shadow; total.primary_hits += c.primary_hits; total.total_ms += c.total_ms;
+        }
+        st.samples_added = total.primary;
+        if (sum) *sum = total;
+        return st;
+    }
     mi355rt_ray_counts last_counts()
     {
         mi355rt_ray_counts c{};

@@ -781,7 +781,8 @@ bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32
     // (nor a ray-fed or a lens pass: its primary rays are not the pinhole camera's, so nothing that is derived from the camera — bins, culling rectangles, cached verdicts — holds)
     const bool whole = !feed && !explicit_sample && d_rows == sl.d_rows.get() && row0 == 0 && nrows == sl.rows.size() && row_wrap == 0xFFFFFFFFu;
     DCamera cam = device_camera(whole ? &ps : nullptr, whole ? &sl.rows : nullptr);
-    const uint32_t rays = feed == nullptr ? 0u : feed->mode != 3u ? 1u : lens_.model == MI355RT_LENS_THIN ? 2u : 3u;      // the feed of the primary round (kernels.hpp, launch_trace)
+    // the feed of the primary round (kernels.hpp, launch_trace); a lens pass with a tile mask has instantiations of its own
+    const uint32_t rays = feed == nullptr ? 0u : feed->mode != 3u ? 1u : (lens_.model == MI355RT_LENS_THIN ? 2u : 3u) + (tile_active != nullptr ? 2u : 0u);
     if (rays) { cam.cull_valid = 0; cam.cull_mask = nullptr; cam.tile_ofs = nullptr; cam.tile_entries = nullptr; }
     if (rays == 1u) {
         ps.ray_in = feed->rays; ps.ray_keys = feed->keys; ps.ray_hit = feed->hit; ps.ray_mode = feed->mode; ps.ray_base = feed->base; ps.ray_npix = cfg.width * cfg.height;
@@ -1259,6 +1260,40 @@ bool Renderer::render_adaptive(const mi355rt_adaptive_config& ac, mi355rt_adapti
     st.samples_added = added;
     for (uint32_t r : owned_rows) ldr_dirty_[r] = 1;
     return end_call(added, true);
+}
+
+// mi355rt_render_tiles (include/mi355rt.h): one round of the adaptive sampler with the caller's verdict — and, under a lens, with lens passes.  The passes are
+// laid out over ALL owned rows as for any frame (the mask only empties chunks); the sample count comes from the mask on the host.
+bool Renderer::render_tiles(const uint8_t* mask, uint32_t spp, bool device)
+{
+    if (!bind()) return false;
+    const uint32_t tx = tiles_x(), ty = tiles_y();
+    const size_t ntiles = (size_t)tx * ty;
+    std::vector<uint8_t> host;
+    const uint8_t* hm = mask;
+    if (device) { host.resize(ntiles); HIP_TRY(hipMemcpy(host.data(), mask, ntiles, hipMemcpyDeviceToHost)); hm = host.data(); }
+    // owned pixels in selected tiles, and the rows they lie in
+    std::vector<uint32_t> row_pixels(ty, 0);
+    for (uint32_t t = 0; t < ty; ++t)
+        for (uint32_t x = 0; x < tx; ++x)
+            if (hm[(size_t)t * tx + x]) row_pixels[t] += std::min(kAdaptiveTile, cfg.width - x * kAdaptiveTile);
+    uint64_t pixels = 0;
+    for (uint32_t r : owned_rows) pixels += row_pixels[r / kAdaptiveTile];
+    const uint8_t* d_mask = mask;
+    if (!device && pixels) {
+        // the device copy goes ahead of begin_call's fork event on the main stream: every slice's launches are ordered behind it
+        if (!d_tile_active_) HIP_TRY(d_tile_active_.alloc(ntiles, &hbm_bytes_));
+        HIP_TRY(hipMemcpyAsync(d_tile_active_.get(), mask, ntiles, hipMemcpyHostToDevice, stream_));
+        d_mask = d_tile_active_.get();
+    }
+    if (!begin_call()) return false;
+    if (pixels) {
+        RayFeed f{};
+        f.mode = 3u;
+        if (!enqueue_frame(spp, ev_begin_, d_mask, has_lens() ? &f : nullptr)) return false;
+        for (uint32_t r : owned_rows) if (row_pixels[r / kAdaptiveTile]) ldr_dirty_[r] = 1;
+    }
+    return end_call(pixels * spp, true);
 }
 
 // get_tonemapped_pixels, mod.rs:120-128.  The reference maps the whole film on every call although one

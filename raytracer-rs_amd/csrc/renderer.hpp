@@ -25,6 +25,9 @@ public:
     // adaptive sampling: rounds of ac.batch_spp samples in the active tiles until none is left; ac is validated by the caller
     bool render_adaptive(const mi355rt_adaptive_config& ac, mi355rt_adaptive_stats& st);
     bool adaptive_tile_mask(const mi355rt_adaptive_config& ac, uint8_t* out, uint32_t& active);     // the next round's verdict, tiles_x() * tiles_y() bytes
+    // mi355rt_render_tiles: spp samples into the tiles of the caller's mask (tiles_x() * tiles_y() bytes), under whatever lens the handle has; the caller
+    // has checked the arguments.  device: the mask is device memory of this handle's device, read in place
+    bool render_tiles(const uint8_t* mask, uint32_t spp, bool device);
     uint32_t tiles_x() const { return (cfg.width + kAdaptiveTile - 1) / kAdaptiveTile; }
     uint32_t tiles_y() const { return (cfg.height + kAdaptiveTile - 1) / kAdaptiveTile; }
     bool get_tonemapped(uint32_t* out, size_t n);                       // mod.rs:120-128
@@ -166,7 +169,7 @@ private:
     mi355rt_lens lens_{ MI355RT_LENS_PINHOLE, 0.0f, 1.0f, 0.0f };    // the handle's lens; not PINHOLE: render() runs lens passes (RayFeed mode 3), the guides take its centre rays
     bool join_slices();                                                 // the main stream waits for the slices of the call in flight
     bool adaptive_verdict(const mi355rt_adaptive_config& ac, uint32_t& tiles, uint64_t& pixels);    // d_tile_active_ <- the verdict of the current film
-    DeviceBuffer<uint8_t> d_tile_active_;                               // adaptive sampling: one byte per tile (DPass::tile_active)
+    DeviceBuffer<uint8_t> d_tile_active_;                               // adaptive sampling: one byte per tile (DPass::tile_active); render_tiles: the device copy of a host mask
     DeviceBuffer<unsigned long long> d_tile_count_;                     // (owned pixels of the active tiles << 32) + active tiles
     // Denoised read-out, allocated on first use: the guides (g0 = (normal, t), g1 = (albedo, prim bits)) for the camera and row-index
     // flag of guides_key_, and the per-call buffers of the filter
