@@ -1192,23 +1192,112 @@ __global__ __launch_bounds__(kBlock, PRIMARY ? (WALK ? kShadePWBlocks : kShadePB
 }
 
 // ---- resolve: radiance tree -> sample colour -> film ------------------------------------------
-template <int REC>
-__device__ f3 node_radiance(const float* __restrict__ L, const DPass& ps, uint32_t nlights, uint32_t level, uint32_t index)
+// The radiance of tree node (level, index) of U samples (U == 1: one sample), in the reference's order of operations for each.  sl[u]: the sample's
+// light-term slot, 0xFFFFFFFF without one (its primary ray hit nothing: black, mod.rs:100 — nothing is loaded and the fold of +0.0 terms gives +0.0).
+// The walk over the tree is the same for all samples, so the loads of one node's terms — U independent ones — are issued together and waited for once.
+template <int REC, uint32_t U>
+__device__ __forceinline__ void node_radiance(const float* __restrict__ slot_L, const uint32_t (&sl)[U], const DPass& ps, uint32_t nlights, uint32_t level, uint32_t index, f3 (&out)[U])
 {
     const uint32_t node = ps.level_first[level] + index;
-    f3 rad = mk3(0.0f, 0.0f, 0.0f);                                    // accum_color, mod.rs:211
+    f3 rad[U];
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) rad[u] = mk3(0.0f, 0.0f, 0.0f);   // accum_color, mod.rs:211
     for (uint32_t li = 0; li < nlights; ++li) {
-        const float* p = L + 3ull * ((size_t)node * nlights + li) * ps.nslots;
-        rad = add3(rad, mk3(p[0], p[1], p[2]));                         // mod.rs:254
+        f3 t[U];
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) {
+            t[u] = mk3(0.0f, 0.0f, 0.0f);
+            if (sl[u] != 0xFFFFFFFFu) {
+                const float* p = slot_L + 3ull * ((size_t)(node * nlights + li) * ps.nslots + sl[u]);   // plane node * nlights + li, the slot's entry
+                t[u] = mk3(p[0], p[1], p[2]);
+            }
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) rad[u] = add3(rad[u], t[u]);   // mod.rs:254
     }
     if constexpr (REC == 0) {
-        return rad;                                                     // mod.rs:146-148
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) out[u] = rad[u];               // mod.rs:146-148
     } else {
         const uint32_t k = ps.spread * (uint32_t)REC;                   // mod.rs:150
-        f3 sum = mk3(0.0f, 0.0f, 0.0f);
-        for (uint32_t c = 0; c < k; ++c) sum = add3(sum, node_radiance<REC - 1>(L, ps, nlights, level + 1, index * k + c));   // fold, mod.rs:173
-        const f3 sub = vscale(sum, div_rn(1.0f, (float)k));          // mod.rs:174
-        return add3(rad, sub);                                          // mod.rs:175
+        f3 sum[U];
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) sum[u] = mk3(0.0f, 0.0f, 0.0f);
+        for (uint32_t c = 0; c < k; ++c) {
+            f3 child[U];
+            node_radiance<REC - 1, U>(slot_L, sl, ps, nlights, level + 1, index * k + c, child);
+#pragma unroll
+            for (uint32_t u = 0; u < U; ++u) sum[u] = add3(sum[u], child[u]);   // fold, mod.rs:173
+        }
+        const float inv = div_rn(1.0f, (float)k);
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) out[u] = add3(rad[u], vscale(sum[u], inv));   // mod.rs:174-175
+    }
+}
+// the whole tree of each of the U samples
+template <uint32_t U>
+__device__ __forceinline__ void tree_radiance(const float* __restrict__ slot_L, const uint32_t (&sl)[U], const DPass& ps, uint32_t nlights, f3 (&c)[U])
+{
+    switch (ps.recursions) {
+        case 0: node_radiance<0, U>(slot_L, sl, ps, nlights, 0, 0, c); break;
+        case 1: node_radiance<1, U>(slot_L, sl, ps, nlights, 0, 0, c); break;
+        case 2: node_radiance<2, U>(slot_L, sl, ps, nlights, 0, 0, c); break;
+        default: node_radiance<3, U>(slot_L, sl, ps, nlights, 0, 0, c); break;
+    }
+}
+// The same for a tree of at most kFlatNodes nodes: recursions 0, recursions 1 with a spread up to 4, and the reference's own 2 / 1.  node_radiance walks the
+// tree and waits for a node's terms before it loads the next node's: for the reference's tree a chain of five round trips.  Here the light sums of ALL nodes
+// are gathered first — per light, the terms of every node of the U samples in flight together — and the tree is folded afterwards, operation for operation as
+// node_radiance folds it.  root[u]: the root node's light sum L0.
+constexpr uint32_t kFlatNodes = 5;
+template <uint32_t U>
+__device__ __forceinline__ void flat_radiance(const float* __restrict__ slot_L, const uint32_t (&sl)[U], const DPass& ps, uint32_t nlights, f3 (&c)[U], f3 (&root)[U])
+{
+    f3 rad[kFlatNodes][U];
+#pragma unroll
+    for (uint32_t q = 0; q < kFlatNodes; ++q) {
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) rad[q][u] = mk3(0.0f, 0.0f, 0.0f);   // accum_color, mod.rs:211
+    }
+    for (uint32_t li = 0; li < nlights; ++li) {
+        f3 t[kFlatNodes][U];
+#pragma unroll
+        for (uint32_t q = 0; q < kFlatNodes; ++q) {
+#pragma unroll
+            for (uint32_t u = 0; u < U; ++u) {
+                t[q][u] = mk3(0.0f, 0.0f, 0.0f);
+                if (sl[u] != 0xFFFFFFFFu && q < ps.nodes_per_sample) {
+                    const float* p = slot_L + 3ull * ((size_t)(q * nlights + li) * ps.nslots + sl[u]);
+                    t[q][u] = mk3(p[0], p[1], p[2]);
+                }
+            }
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < kFlatNodes; ++q) {
+#pragma unroll
+            for (uint32_t u = 0; u < U; ++u) rad[q][u] = add3(rad[q][u], t[q][u]);   // mod.rs:254
+        }
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) {
+        root[u] = rad[0][u];
+        if (ps.recursions == 0u) c[u] = rad[0][u];                      // mod.rs:146-148
+        else if (ps.recursions == 1u) {
+            const uint32_t k = ps.spread;                               // mod.rs:150; <= kFlatNodes - 1 children
+            f3 sum = mk3(0.0f, 0.0f, 0.0f);
+#pragma unroll
+            for (uint32_t ci = 0; ci + 1u < kFlatNodes; ++ci) if (ci < k) sum = add3(sum, rad[1u + ci][u]);   // fold, mod.rs:173
+            c[u] = add3(rad[0][u], vscale(sum, div_rn(1.0f, (float)k)));                                  // mod.rs:174-175
+        } else {
+            // recursions 2, spread 1: nodes 1 and 2 below the root, node 3 below node 1 and node 4 below node 2
+            f3 sum = mk3(0.0f, 0.0f, 0.0f);
+#pragma unroll
+            for (uint32_t ci = 0; ci < 2u; ++ci) {
+                const f3 below = add3(mk3(0.0f, 0.0f, 0.0f), rad[3u + ci][u]);
+                sum = add3(sum, add3(rad[1u + ci][u], vscale(below, div_rn(1.0f, 1.0f))));
+            }
+            c[u] = add3(rad[0][u], vscale(sum, div_rn(1.0f, 2.0f)));
+        }
     }
 }
 
@@ -1218,11 +1307,18 @@ __device__ f3 node_radiance(const float* __restrict__ L, const DPass& ps, uint32
 // With one thread per pixel, a pass with few pixels and many samples per pixel (one rank's stripes of an
 // 8-GPU frame: 512 spp) is a latency-bound loop of dependent loads on a nearly empty chip; with many lanes per
 // pixel and few samples most lanes of a group have nothing to load.  The launcher picks the group size from
-// the samples per pixel of the pass (21-spp passes of a 1080p frame: 1 / 2 / 4 / 8 / 16 lanes -> 0.22 / 0.21 /
-// 0.25 / 0.31 / 0.55 ms).
-// DIRECT (MI355RT_FLAG_DIRECT_FILM): the pixel's direct film (film_direct, beside film_sum) takes the root node's light sum L0 =
-// node_radiance<0> of every sample — the first term of the sample's colour — through the same exchange, so it is added in sample order too.
-template <uint32_t kResolveLanes, bool DIRECT>
+// the samples per pixel of the pass: 2 lanes up to 32 spp, 4 up to 96, 8 above.  Kernel time with U = 2 (profiles/reach_bench_ab.txt): the 64-spp thai2
+// 1080p frame 2 / 4 / 8 lanes -> 0.574 / 0.405 / 0.438 ms; one rank's share of eight at 512 spp 0.880 / 0.451 / 0.401 ms.
+// U: a lane takes U of its samples per turn of the loop and has the loads of all of them in flight before the exchange — a turn used to be one sample's
+// dependent round trips (slot index, then terms) with nothing in flight across turns: 0.64 ms for 2.3 GB.  Same frame, 4 lanes, flat fold (FLAT):
+// U = 1 / 2 / 3 / 4 -> 0.526 / 0.405 / 0.453 / 0.436 ms at 54 / 88 / 122 / 156 VGPRs (8 / 5 / 4 / 3 waves per SIMD); the 512-spp share, 8 lanes: 0.448 / 0.401 /
+// - / 0.418 ms.  5.7 TB/s at U = 2: what is left is the bytes.
+// FLAT: the tree has at most kFlatNodes nodes and is folded by flat_radiance (the launcher's choice; the reference's own tree is such a one).
+// DIRECT (MI355RT_FLAG_DIRECT_FILM): the pixel's direct film (film_direct, beside film_sum) takes the root node's light sum L0
+// of every sample — the first term of the sample's colour — through the same exchange, so it is added in sample order too.
+// A pixel without anything to load — in a culled block, or inactive — skips the loop: its lanes exchange with each other only.
+constexpr uint32_t kResolveU = 2;
+template <uint32_t kResolveLanes, uint32_t U, bool DIRECT, bool FLAT>
 __global__ __launch_bounds__(256) void resolve_kernel(DPass ps, uint32_t width, uint32_t nlights, const float* __restrict__ slot_L,
                                                      const uint32_t* __restrict__ sample_slot,
                                                      float* film_sum, float* film_sumsq, uint32_t* film_n, float* debug_color, uint32_t* ctrl, float* film_direct)
@@ -1248,33 +1344,46 @@ __global__ __launch_bounds__(256) void resolve_kernel(DPass ps, uint32_t width, 
     const int group_lane0 = lane_id() & ~(int)(kResolveLanes - 1u);
     // every sample of a pixel in a culled block is a miss: no slot to look up (the primary shade launch wrote none)
     const bool dead = ps.block_culled != nullptr && ps.block_culled[(uint32_t)(sample_index(ps, 0u, p) / ps.chunk) % ps.cull_blocks] != 0u;
-    // adaptive sampling: an inactive pixel's slots may be stale (a skipped chunk with a cached verdict writes none) and its film is not written at all;
-    // its lanes still run the exchange loop below with the rest of the wave
+    // adaptive sampling: an inactive pixel's slots may be stale (a skipped chunk with a cached verdict writes none) and its film is not written at all
     const bool on = ps.use_explicit || pixel_active(ps, width, pixel);
-    for (uint32_t s0 = 0; s0 < spp; s0 += kResolveLanes) {
-        const uint32_t sl = (s0 + j < spp && !dead && on) ? sample_slot[sample_index(ps, s0 + j, p)] : 0xFFFFFFFFu;
-        const float* L = slot_L + 3ull * (size_t)sl;       // the slot's entry of plane 0; plane q is 3 * q * nslots floats further
-        f3 c = mk3(0.0f, 0.0f, 0.0f);                                   // primary miss: RGB::black(), mod.rs:100
-        if (sl != 0xFFFFFFFFu) switch (ps.recursions) {
-            case 0: c = node_radiance<0>(L, ps, nlights, 0, 0); break;
-            case 1: c = node_radiance<1>(L, ps, nlights, 0, 0); break;
-            case 2: c = node_radiance<2>(L, ps, nlights, 0, 0); break;
-            default: c = node_radiance<3>(L, ps, nlights, 0, 0); break;
+    if (!ps.use_explicit && (dead || !on)) {
+        // nothing to load for this pixel, and its lanes exchange with each other only.  Every sample is black: adding +0.0 spp times is adding it once, also to
+        // a film of -0.0 (which the first add turns into +0.0).  An inactive pixel is not written below.
+        if (spp != 0u) {
+            sum = add3(sum, mk3(0.0f, 0.0f, 0.0f)); sumsq = add3(sumsq, mk3(0.0f, 0.0f, 0.0f));
+            if constexpr (DIRECT) direct = add3(direct, mk3(0.0f, 0.0f, 0.0f));
         }
-        f3 d = mk3(0.0f, 0.0f, 0.0f);                                   // no slot: no root light term either
-        if constexpr (DIRECT) { if (sl != 0xFFFFFFFFu) d = node_radiance<0>(L, ps, nlights, 0, 0); }
+        n += spp;
+    } else for (uint32_t s0 = 0; s0 < spp; s0 += kResolveLanes * U) {
+        // a turn: U samples of this lane (s0 + u * kResolveLanes + j).  All their slot indices first, then their light terms — of all nodes at once where the tree
+        // is small (flat_radiance), node by node for the U samples together otherwise (node_radiance) — and only then the exchange, which waits for them
+        uint32_t sl[U];
 #pragma unroll
-        for (uint32_t k = 0; k < kResolveLanes; ++k) {
-            const f3 ck = mk3(__shfl(c.x, group_lane0 + (int)k, 64), __shfl(c.y, group_lane0 + (int)k, 64), __shfl(c.z, group_lane0 + (int)k, 64));
-            f3 dk = mk3(0.0f, 0.0f, 0.0f);
-            if constexpr (DIRECT) dk = mk3(__shfl(d.x, group_lane0 + (int)k, 64), __shfl(d.y, group_lane0 + (int)k, 64), __shfl(d.z, group_lane0 + (int)k, 64));
-            if (s0 + k < spp) {
-                // PixelData::add_sample, film.rs:20-24
-                sum = add3(sum, ck);
-                sumsq = add3(sumsq, mk3(ck.x * ck.x, ck.y * ck.y, ck.z * ck.z));
-                n += 1u;
-                if constexpr (DIRECT) direct = add3(direct, dk);
-                if (ps.use_explicit && j == 0u) { debug_color[0] = ck.x; debug_color[1] = ck.y; debug_color[2] = ck.z; }
+        for (uint32_t u = 0; u < U; ++u) {
+            const uint32_t s = s0 + u * kResolveLanes + j;
+            sl[u] = (s < spp && !dead) ? sample_slot[sample_index(ps, s, p)] : 0xFFFFFFFFu;
+        }
+        f3 c[U], d[U];
+        if constexpr (FLAT) flat_radiance<U>(slot_L, sl, ps, nlights, c, d);
+        else {
+            tree_radiance<U>(slot_L, sl, ps, nlights, c);
+            if constexpr (DIRECT) node_radiance<0, U>(slot_L, sl, ps, nlights, 0, 0, d);   // no slot: no root light term either
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) {
+#pragma unroll
+            for (uint32_t k = 0; k < kResolveLanes; ++k) {
+                const f3 ck = mk3(__shfl(c[u].x, group_lane0 + (int)k, 64), __shfl(c[u].y, group_lane0 + (int)k, 64), __shfl(c[u].z, group_lane0 + (int)k, 64));
+                f3 dk = mk3(0.0f, 0.0f, 0.0f);
+                if constexpr (DIRECT) dk = mk3(__shfl(d[u].x, group_lane0 + (int)k, 64), __shfl(d[u].y, group_lane0 + (int)k, 64), __shfl(d[u].z, group_lane0 + (int)k, 64));
+                if (s0 + u * kResolveLanes + k < spp) {
+                    // PixelData::add_sample, film.rs:20-24
+                    sum = add3(sum, ck);
+                    sumsq = add3(sumsq, mk3(ck.x * ck.x, ck.y * ck.y, ck.z * ck.z));
+                    n += 1u;
+                    if constexpr (DIRECT) direct = add3(direct, dk);
+                    if (ps.use_explicit && j == 0u) { debug_color[0] = ck.x; debug_color[1] = ck.y; debug_color[2] = ck.z; }
+                }
             }
         }
     }
@@ -1300,20 +1409,12 @@ __global__ __launch_bounds__(256) void resolve_rays_kernel(DPass ps, uint32_t nl
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= ps.nsamples) return;
     if (rgb != nullptr || direct != nullptr) {
-        const uint32_t sl = sample_slot[i];
-        const float* L = slot_L + 3ull * (size_t)sl;       // the slot's entry of plane 0; plane q is 3 * q * nslots floats further
-        f3 c = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 0.0f);          // primary miss: RGB::black(), mod.rs:100
-        if (sl != 0xFFFFFFFFu) {
-            if (rgb != nullptr) switch (ps.recursions) {
-                case 0: c = node_radiance<0>(L, ps, nlights, 0, 0); break;
-                case 1: c = node_radiance<1>(L, ps, nlights, 0, 0); break;
-                case 2: c = node_radiance<2>(L, ps, nlights, 0, 0); break;
-                default: c = node_radiance<3>(L, ps, nlights, 0, 0); break;
-            }
-            if (direct != nullptr) d = node_radiance<0>(L, ps, nlights, 0, 0);
-        }
-        if (rgb != nullptr) { rgb[3ull * i] = c.x; rgb[3ull * i + 1] = c.y; rgb[3ull * i + 2] = c.z; }
-        if (direct != nullptr) { direct[3ull * i] = d.x; direct[3ull * i + 1] = d.y; direct[3ull * i + 2] = d.z; }
+        const uint32_t sl[1] = { sample_slot[i] };
+        f3 c[1] = { mk3(0.0f, 0.0f, 0.0f) }, d[1] = { mk3(0.0f, 0.0f, 0.0f) };          // primary miss: RGB::black(), mod.rs:100
+        if (rgb != nullptr) tree_radiance<1>(slot_L, sl, ps, nlights, c);
+        if (direct != nullptr) node_radiance<0, 1>(slot_L, sl, ps, nlights, 0, 0, d);
+        if (rgb != nullptr) { rgb[3ull * i] = c[0].x; rgb[3ull * i + 1] = c[0].y; rgb[3ull * i + 2] = c[0].z; }
+        if (direct != nullptr) { direct[3ull * i] = d[0].x; direct[3ull * i + 1] = d[0].y; direct[3ull * i + 2] = d[0].z; }
     }
     if (ps.ray_hit != nullptr) {
         const float4 h = ps.ray_hit[i];
@@ -1352,25 +1453,20 @@ __device__ __forceinline__ void resolve_chunk_1spp(const DPass& ps, uint32_t wid
     for (uint32_t i = (uint32_t)lane_id(); i < n; i += 64u) {
         const uint32_t p = chunk * ps.chunk + i;                         // 1 sample per pixel: sample index == pixel index of the pass
         const uint32_t pixel = pass_pixel(ps, width, p);
-        const uint32_t sl = sample_slot[p];
-        const float* L = slot_L + 3ull * (size_t)sl;       // the slot's entry of plane 0; plane q is 3 * q * nslots floats further
-        f3 c = mk3(0.0f, 0.0f, 0.0f);                                    // primary miss: RGB::black(), mod.rs:100
-        if (sl != 0xFFFFFFFFu) switch (ps.recursions) {
-            case 0: c = node_radiance<0>(L, ps, nlights, 0, 0); break;
-            case 1: c = node_radiance<1>(L, ps, nlights, 0, 0); break;
-            case 2: c = node_radiance<2>(L, ps, nlights, 0, 0); break;
-            default: c = node_radiance<3>(L, ps, nlights, 0, 0); break;
-        }
+        const uint32_t sl[1] = { sample_slot[p] };
+        f3 c1[1];
+        tree_radiance<1>(slot_L, sl, ps, nlights, c1);                           // primary miss: RGB::black(), mod.rs:100
+        const f3 c = c1[0];
         // PixelData::add_sample, film.rs:20-24
         float* ps_ = film_sum + 3ull * pixel; float* pq = film_sumsq + 3ull * pixel;
         ps_[0] = ps_[0] + c.x; ps_[1] = ps_[1] + c.y; ps_[2] = ps_[2] + c.z;
         pq[0] = pq[0] + c.x * c.x; pq[1] = pq[1] + c.y * c.y; pq[2] = pq[2] + c.z * c.z;
         film_n[pixel] = film_n[pixel] + 1u;
         if constexpr (DIRECT) {
-            f3 d = mk3(0.0f, 0.0f, 0.0f);
-            if (sl != 0xFFFFFFFFu) d = node_radiance<0>(L, ps, nlights, 0, 0);
+            f3 d[1];
+            node_radiance<0, 1>(slot_L, sl, ps, nlights, 0, 0, d);
             float* pd = film_direct + 3ull * pixel;
-            pd[0] = pd[0] + d.x; pd[1] = pd[1] + d.y; pd[2] = pd[2] + d.z;
+            pd[0] = pd[0] + d[0].x; pd[1] = pd[1] + d[0].y; pd[2] = pd[2] + d[0].z;
         }
     }
 }
@@ -2039,19 +2135,20 @@ hipError_t launch_resolve(hipStream_t stream, const DPass& ps, uint32_t width, u
                           float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct, float* debug_color, uint32_t* ctrl)
 {
     const uint32_t spp = ps.npix ? ps.nsamples / ps.npix : 1u;
-    const uint32_t lanes = spp <= 32u ? 2u : (spp <= 96u ? 4u : 8u);
+    const uint32_t lanes = spp <= 32u ? 2u : (spp <= 96u ? 4u : 8u);       // lanes per pixel: resolve_kernel's header
     dim3 block(256), grid((unsigned)(((size_t)ps.npix * lanes + 255) / 256));
 #define MI355RT_RESOLVE_ARGS grid, block, 0, stream, ps, width, nlights, slot_L, sample_slot, film_sum, film_sumsq, film_n, debug_color, ctrl, film_direct
-    if (film_direct != nullptr && !ps.use_explicit) switch (lanes) {          // a debug_sample pass adds to no film: the plain variant
-        case 2: hipLaunchKernelGGL((resolve_kernel<2, true>), MI355RT_RESOLVE_ARGS); break;
-        case 4: hipLaunchKernelGGL((resolve_kernel<4, true>), MI355RT_RESOLVE_ARGS); break;
-        default: hipLaunchKernelGGL((resolve_kernel<8, true>), MI355RT_RESOLVE_ARGS); break;
-    }
-    else switch (lanes) {
-        case 2: hipLaunchKernelGGL((resolve_kernel<2, false>), MI355RT_RESOLVE_ARGS); break;
-        case 4: hipLaunchKernelGGL((resolve_kernel<4, false>), MI355RT_RESOLVE_ARGS); break;
-        default: hipLaunchKernelGGL((resolve_kernel<8, false>), MI355RT_RESOLVE_ARGS); break;
-    }
+#define MI355RT_RESOLVE_LANES(DIRECT, FLAT) switch (lanes) { \
+        case 2: hipLaunchKernelGGL((resolve_kernel<2, kResolveU, DIRECT, FLAT>), MI355RT_RESOLVE_ARGS); break; \
+        case 4: hipLaunchKernelGGL((resolve_kernel<4, kResolveU, DIRECT, FLAT>), MI355RT_RESOLVE_ARGS); break; \
+        default: hipLaunchKernelGGL((resolve_kernel<8, kResolveU, DIRECT, FLAT>), MI355RT_RESOLVE_ARGS); break; }
+    const bool direct = film_direct != nullptr && !ps.use_explicit;           // a debug_sample pass adds to no film: the plain variant
+    const bool flat = ps.nodes_per_sample <= kFlatNodes;                      // flat_radiance
+    if (direct && flat) MI355RT_RESOLVE_LANES(true, true)
+    else if (direct) MI355RT_RESOLVE_LANES(true, false)
+    else if (flat) MI355RT_RESOLVE_LANES(false, true)
+    else MI355RT_RESOLVE_LANES(false, false)
+#undef MI355RT_RESOLVE_LANES
 #undef MI355RT_RESOLVE_ARGS
     return hipGetLastError();
 }
