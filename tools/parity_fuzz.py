@@ -1,6 +1,6 @@
 """Randomised parity: random scene / size / seed / recursion setting / leaf size / semantics / camera moves / call sequence, the HIP
 path against the CPU oracle bit for bit (film sums, sums of squares, counts, packed pixels, ray counters).  Test infrastructure.
-usage: [FUZZ_WILD=1] [FUZZ_SPP=1] [FUZZ_SOUP=1] [FUZZ_BUILD=1] [FUZZ_TEX=1] parity_fuzz.py [cases] [seed]   — prints one line per case, exits 1 on the first difference."""
+usage: [FUZZ_WILD=1] [FUZZ_GRAZE=1] [FUZZ_SPP=1] [FUZZ_SOUP=1] [FUZZ_BUILD=1] [FUZZ_TEX=1] parity_fuzz.py [cases] [seed]   — prints one line per case, exits 1 on the first difference."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,8 +50,56 @@ def textured(base, rng):
     return sc
 
 
+def front_margin(orc, sc, w, h):
+    """The least depth along the oracle's centre ray of the corners of the scene's bounds, padded by 1e-3 of their diagonal like the library's top boxes,
+    in diagonals.  The library keeps its screen-space structures (cull rectangles, coverage mask, tile bins, cached verdicts) while every corner of its
+    own 16 padded sub-boxes is deeper than 1e-6 diagonals (`front`, renderer.cpp device_camera): this is that test on the one box a tool can know."""
+    v = np.asarray(sc["tri_verts"], np.float64).reshape(-1, 3); lo, hi = v.min(0), v.max(0)
+    diag = float(np.linalg.norm(hi - lo)); pad = 1e-3 * diag + 1e-6
+    ray = orc.get_ray(w // 2, h // 2, 0.5 if w % 2 else 0.0, 0.5 if h % 2 else 0.0).astype(np.float64)     # dir_x = dir_y = 0 exactly
+    o, d = ray[:3], ray[3:]
+    corners = np.array([[(hi[a] + pad) if (k >> a) & 1 else (lo[a] - pad) for a in range(3)] for k in range(8)])
+    return float(((corners - o) @ d / (d @ d)).min()) / max(diag, 1e-30)
+
+
+def graze(rt, orc, sc, w, h, rng):
+    """FUZZ_GRAZE=1: after a wild move, dolly the eye (move_rel(0, 0, z), mirrored on both sides) to within a random factor 1e-1 ... 1e-6 of the scene's
+    extent of the pose where `front` switches, on a random side of it: the margin above is affine in the dolly coordinate, so one probe move gives the
+    switch, and a bisection on the margin of the camera the oracle really holds (f32 moves) closes in on it.  Returns the factor, or None when the
+    dolly axis does not cross the switch within reach."""
+    ext = float(np.ptp(np.asarray(sc["tri_verts"], np.float64).reshape(-1, 3), axis=0).max())
+    cur = np.float32(0.0)
+
+    def ahead(t):
+        nonlocal cur
+        d = np.float32(np.float32(t) - cur)
+        if d != 0:
+            rt.camera.move_rel(0.0, 0.0, float(d)); orc.camera_move_rel(0.0, 0.0, float(d)); cur = np.float32(cur + d)
+        return front_margin(orc, sc, w, h) > 1e-6
+
+    m0 = front_margin(orc, sc, w, h)
+    ahead(ext)
+    slope = (front_margin(orc, sc, w, h) - m0) / ext
+    switch = (1e-6 - m0) / slope if slope else np.inf
+    if not abs(switch) < 100.0 * ext:
+        ahead(0.0)
+        return None
+    a, b = switch - rng.uniform(0.02, 0.08) * ext, switch + rng.uniform(0.02, 0.08) * ext
+    fa, fb = ahead(a), ahead(b)
+    factor = 10.0 ** -rng.uniform(1.0, 6.0)
+    for _ in range(40):
+        mid = 0.5 * (a + b)
+        if fa == fb or abs(b - a) <= factor * ext or np.float32(mid) in (np.float32(a), np.float32(b)):
+            break
+        if ahead(mid) == fa: a = mid
+        else: b = mid
+    ahead(a if rng.random() < 0.5 else b)
+    return factor
+
+
 def one_case(pkg, O, scenes, rng, verbose=True):
     WILD = bool(os.environ.get("FUZZ_WILD"))
+    GRAZE = bool(os.environ.get("FUZZ_GRAZE"))              # FUZZ_GRAZE=1: every case starts with a wild camera move that ends next to the `front` switch
     name = rng.choice(["ico2", "4boxes", "ico3_tex", "thai2"], p=[0.35, 0.2, 0.2, 0.25])
     w, h = int(rng.integers(4, 161)), int(rng.integers(3, 121))
     if rng.random() < 0.4:                              # sizes whose wave tiles do not straddle row groups: the tile bins of the primary rays engage
@@ -93,17 +141,21 @@ def one_case(pkg, O, scenes, rng, verbose=True):
     orc = O.Oracle(sc, w, h, tris_per_leaf=tpl, recursions=rec, spread=spread, seed=seed, flags=oflags)
     desc = "%s %dx%d seed %d rec %d spread %d tpl %d sem %d flags %#x %s %s" % (name, w, h, seed, rec, spread, tpl, sem, gflags, stripes or "", extra or "")
     steps = []
-    for _ in range(int(rng.integers(1, 5)) + (1 if WILD else 0)):
+    for _ in range(int(rng.integers(1, 5)) + (1 if WILD or GRAZE else 0)):
         kind = rng.choice(["render", "frame", "move", "clear"], p=[0.4, 0.3, 0.2, 0.1])
-        if WILD and not steps:
+        if (WILD or GRAZE) and not steps:
             kind = "move"                                   # FUZZ_WILD=1: every case starts with a wild camera move
         if kind == "move":
             dx, dy, dz = (float(x) for x in rng.normal(0, 0.4, 3)); ax, ay = float(rng.normal(0, 0.2)), float(rng.normal(0, 0.2))
-            if WILD or rng.random() < 0.3:                  # a wild move: into, through or behind the geometry, looking anywhere (triangles across the eye plane:
+            wild = WILD or (GRAZE and not steps) or rng.random() < 0.3
+            if wild:                  # a wild move: into, through or behind the geometry, looking anywhere (triangles across the eye plane:
                 ext = float(np.ptp(sc["tri_verts"].reshape(-1, 3), axis=0).max())       # the screen-space structures must stand down, the tree walk answers)
                 dx, dy, dz = (float(x) for x in rng.normal(0, 0.5 * ext, 3)); ax, ay = float(rng.uniform(-3.2, 3.2)), float(rng.uniform(-1.5, 1.5))
             rt.camera.move_rel(dx, dy, dz); orc.camera_move_rel(dx, dy, dz)
             rt.camera.add_x_angle(ax); orc.camera_add_x_angle(ax); rt.camera.add_y_angle(ay); orc.camera_add_y_angle(ay)
+            if GRAZE and wild:
+                factor = graze(rt, orc, sc, w, h, rng)
+                kind = "move, no graze" if factor is None else "move, graze %.1e" % factor
             rt.film.clear(); orc.film_clear()               # what the reference's binary does after a camera move (main.rs:116-169)
         elif kind == "clear":
             rt.film.clear(); orc.film_clear()
