@@ -680,6 +680,15 @@ int mi355rt_debug_reflect_mask(const float* tri_verts, uint32_t ntri, double pad
  * exactly once, [6] child boxes that fail to contain a vertex of a triangle below them (must be 0), [7] triangles the re-pointed binary tree
  * reaches exactly once. */
 int mi355rt_debug_wide_bvh(const float* tri_verts, uint32_t ntri, uint32_t out[8]);
+/* Test hook (host only, no device, no handle): the reference's octree exactly as mi355rt_create builds it for the default intersector
+ * (csrc/octree.hpp; the same build_octree call on the ntri triangles with tris_per_leaf), in its flat form by node index.  counts[8] receives what
+ * mi355rt_octree_stats reports for that tree ([0] nodes .. [5] triangle references).  SIZE QUERY: all six arrays NULL; only counts is written.
+ * Otherwise all six are required: cubes6 holds node_cap x (min3, max3); first_child, tri_first, tri_count and parent node_cap entries (first_child
+ * >= 0: inner node with the children first_child .. first_child + 7, -1: leaf with the range tri_first, tri_count of leaf_tris; parent of the root: 0);
+ * leaf_tris leaf_cap global triangle indices, the leaves' lists in list order.  node_cap < counts[0] or leaf_cap < counts[5]: MI355RT_E_INVALID and
+ * nothing is written, not counts either.  Exists so that the build can be held to an independent statement without a GPU. */
+int mi355rt_debug_octree(const float* tri_verts, uint32_t ntri, uint32_t tris_per_leaf, uint32_t counts[8], float* cubes6, int32_t* first_child,
+                         uint32_t* tri_first, uint32_t* tri_count, uint32_t* parent, size_t node_cap, uint32_t* leaf_tris, size_t leaf_cap);
 
 /* acceleration-structure facts: out[0] nodes, [1] leaves, [2] max depth, [3] max leaf size,
  * [4] node bytes, [5] triangle bytes, [6] BVH build time inside create (wall, microseconds; host SAH build, or the device

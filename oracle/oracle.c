@@ -918,6 +918,27 @@ void oracle_octree_stats(const oracle_t* o, uint32_t* out8)
     out8[0] = o->nnodes;
     stats_rec(o, 0, 0, out8);
 }
+/* The tree itself, in node order (node index == cube index), for tests/test_octree_statement.py.  sizes[0] = nodes, sizes[1] = triangle
+ * references of all leaves, always written.  The arrays may all be NULL (size query); otherwise each holds what sizes says: cubes6 per node
+ * (min3, max3); child8 per node the 8 child indices, or eight times -1 for a leaf; leaf_first / leaf_count per node its range in leaf_tris
+ * (0, 0 for an inner node); leaf_tris the leaves' lists in node order, each in its own list order. */
+void oracle_octree_dump(const oracle_t* o, uint32_t* sizes, float* cubes6, int32_t* child8, uint32_t* leaf_first, uint32_t* leaf_count,
+                        uint32_t* leaf_tris)
+{
+    uint32_t refs = 0;
+    for (uint32_t i = 0; i < o->nnodes; ++i) if (o->nodes[i].is_leaf) refs += o->nodes[i].ntris;
+    sizes[0] = o->nnodes; sizes[1] = refs;
+    if (!cubes6 || !child8 || !leaf_first || !leaf_count || !leaf_tris) return;
+    uint32_t at = 0;
+    for (uint32_t i = 0; i < o->nnodes; ++i) {
+        const octnode_t* nd = &o->nodes[i];
+        memcpy(&cubes6[6 * i], &o->cubes[i], 6 * sizeof(float));
+        for (int k = 0; k < 8; ++k) child8[8 * i + k] = nd->is_leaf ? -1 : (int32_t)nd->child[k];
+        leaf_first[i] = nd->is_leaf ? at : 0u;
+        leaf_count[i] = nd->is_leaf ? nd->ntris : 0u;
+        if (nd->is_leaf && nd->ntris) { memcpy(&leaf_tris[at], nd->tris, nd->ntris * sizeof(uint32_t)); at += nd->ntris; }
+    }
+}
 void oracle_counters(const oracle_t* o, uint64_t* c8)
 {
     c8[0] = o->cnt.rays_primary; c8[1] = o->cnt.rays_bounce; c8[2] = o->cnt.rays_shadow; c8[3] = o->cnt.nodes_visited;

@@ -56,6 +56,7 @@ def lib():
         L.oracle_current_row.restype = C.c_uint32
         L.oracle_current_row.argtypes = [C.c_void_p]
         L.oracle_octree_stats.argtypes = [C.c_void_p, _U]
+        L.oracle_octree_dump.argtypes = [C.c_void_p, _U, _F, C.POINTER(C.c_int32), _U, _U, _U]
         L.oracle_counters.argtypes = [C.c_void_p, _U64]
         L.oracle_tree_nodes.restype = C.c_uint32
         L.oracle_tree_nodes.argtypes = [C.c_void_p]
@@ -187,6 +188,16 @@ class Oracle:
     def octree_stats(self):
         s = np.zeros(8, np.uint32); lib().oracle_octree_stats(self._h, _up(s))
         return dict(nodes=int(s[0]), inner=int(s[1]), leaves=int(s[2]), empty=int(s[3]), depth=int(s[4]), tri_refs=int(s[5]), max_leaf=int(s[6]))
+
+    def octree_dump(self):
+        """the oracle's tree by node index: dict(cubes (n, 6) f32, children (n, 8) int32 (-1: leaf), leaf_first, leaf_count (n,), leaf_tris)"""
+        sizes = np.zeros(2, np.uint32)
+        lib().oracle_octree_dump(self._h, _up(sizes), None, None, None, None, None)
+        n, refs = int(sizes[0]), int(sizes[1])
+        cubes = np.zeros((n, 6), np.float32); children = np.zeros((n, 8), np.int32)
+        first = np.zeros(n, np.uint32); count = np.zeros(n, np.uint32); tris = np.zeros(max(refs, 1), np.uint32)
+        lib().oracle_octree_dump(self._h, _up(sizes), _fp(cubes), children.ctypes.data_as(C.POINTER(C.c_int32)), _up(first), _up(count), _up(tris))
+        return dict(cubes=cubes, children=children, leaf_first=first, leaf_count=count, leaf_tris=tris[:refs])
 
     @property
     def current_row(self): return lib().oracle_current_row(self._h)

@@ -235,6 +235,7 @@ ABI = [
     ("mi355rt_reflect_mask_info", C.c_int, [_H, C.POINTER(C.c_double)]),
     ("mi355rt_debug_rays_read", C.c_int, [_H, C.POINTER(C.c_uint64)]),
     ("mi355rt_debug_wide_bvh", C.c_int, [_F, C.c_uint32, _U]),
+    ("mi355rt_debug_octree", C.c_int, [_F, C.c_uint32, C.c_uint32, _U, _F, C.POINTER(C.c_int32), _U, _U, _U, C.c_size_t, _U, C.c_size_t]),
     ("mi355rt_accel_stats", C.c_int, [_H, _U]),
     ("mi355rt_octree_stats", C.c_int, [_H, _U]),
     ("mi355rt_bvh_build_info", C.c_int, [_H, _U]),
@@ -996,6 +997,25 @@ def debug_wide_bvh(tri_verts):
         raise RuntimeError("mi355rt_debug_wide_bvh failed: %d" % code)
     keys = ("wide_nodes", "binary_nodes", "stack_need", "binary_depth", "children", "tris_once_wide", "bad_boxes", "tris_once_binary")
     return dict(zip(keys, (int(x) for x in out)))
+
+
+def debug_octree(tri_verts, tris_per_leaf):
+    """the reference's octree as mi355rt_create builds it, by node index (host code; include/mi355rt.h): dict(cubes (n, 6), first_child (n,) int32,
+    tri_first, tri_count, parent (n,), leaf_tris, stats: the dict of RayTracer.octree_stats)"""
+    v = np.ascontiguousarray(tri_verts, np.float32).reshape(-1, 9)
+    counts = np.zeros(8, np.uint32)
+    code = lib().mi355rt_debug_octree(_fp(v), v.shape[0], int(tris_per_leaf), _up(counts), None, None, None, None, None, 0, None, 0)
+    if code != 0:
+        raise RuntimeError("mi355rt_debug_octree failed: %d" % code)
+    n, refs = int(counts[0]), int(counts[5])
+    cubes = np.zeros((n, 6), np.float32); first_child = np.zeros(n, np.int32)
+    tri_first = np.zeros(n, np.uint32); tri_count = np.zeros(n, np.uint32); parent = np.zeros(n, np.uint32); leaf_tris = np.zeros(max(refs, 1), np.uint32)
+    code = lib().mi355rt_debug_octree(_fp(v), v.shape[0], int(tris_per_leaf), _up(counts), _fp(cubes), first_child.ctypes.data_as(C.POINTER(C.c_int32)),
+                                      _up(tri_first), _up(tri_count), _up(parent), n, _up(leaf_tris), refs)
+    if code != 0:
+        raise RuntimeError("mi355rt_debug_octree failed: %d" % code)
+    stats = dict(nodes=int(counts[0]), inner=int(counts[1]), leaves=int(counts[2]), empty=int(counts[3]), depth=int(counts[4]), tri_refs=int(counts[5]))
+    return dict(cubes=cubes, first_child=first_child, tri_first=tri_first, tri_count=tri_count, parent=parent, leaf_tris=leaf_tris[:refs], stats=stats)
 
 
 def comm_unique_id():

@@ -8,6 +8,7 @@
 #include <vector>
 #include "display.hpp"
 #include "lightmap.hpp"
+#include "octree.hpp"
 #include "reflmask.hpp"
 #include "../../include/mi355rt.h"
 #include "group.hpp"
@@ -865,6 +866,26 @@ int mi355rt_debug_wide_bvh(const float* tri_verts, uint32_t ntri, uint32_t out[8
         else { st.push_back(b.nodes[(size_t)r].child0); st.push_back(b.nodes[(size_t)r].child1); }
     }
     for (uint32_t c : seen2) out[7] += c == 1u ? 1u : 0u;
+    return MI355RT_OK;
+}
+
+int mi355rt_debug_octree(const float* tri_verts, uint32_t ntri, uint32_t tris_per_leaf, uint32_t counts[8], float* cubes6, int32_t* first_child,
+                         uint32_t* tri_first, uint32_t* tri_count, uint32_t* parent, size_t node_cap, uint32_t* leaf_tris, size_t leaf_cap)
+{
+    if ((ntri && !tri_verts) || !counts) return MI355RT_E_INVALID;
+    const bool query = !cubes6 && !first_child && !tri_first && !tri_count && !parent && !leaf_tris;
+    if (!query && (!cubes6 || !first_child || !tri_first || !tri_count || !parent || !leaf_tris)) return MI355RT_E_INVALID;
+    mi355rt::Octree oct;
+    mi355rt::build_octree(tri_verts, ntri, tris_per_leaf, oct);
+    if (!query && (node_cap < oct.nodes.size() || leaf_cap < oct.leaf_tris.size())) return MI355RT_E_INVALID;      // nothing is written
+    mi355rt::octree_counts(oct, counts);                                                                                // what Renderer puts into oct_stats_
+    if (query) return MI355RT_OK;
+    for (size_t i = 0; i < oct.nodes.size(); ++i) {
+        const mi355rt::OctNodeFlat& f = oct.nodes[i];
+        std::memcpy(&cubes6[6 * i], f.cmin, 3 * sizeof(float)); std::memcpy(&cubes6[6 * i + 3], f.cmax, 3 * sizeof(float));
+        first_child[i] = f.first_child; tri_first[i] = f.tri_first; tri_count[i] = f.tri_count; parent[i] = f.parent;
+    }
+    if (!oct.leaf_tris.empty()) std::memcpy(leaf_tris, oct.leaf_tris.data(), oct.leaf_tris.size() * sizeof(uint32_t));
     return MI355RT_OK;
 }
 

@@ -26,4 +26,11 @@ struct Octree {
 
 void build_octree(const float* tri_verts, uint32_t ntri, uint32_t tris_per_leaf, Octree& out);
 
+// the counters of mi355rt_octree_stats: nodes, inner, leaves, empty leaves, depth, triangle references, 0, 0
+inline void octree_counts(const Octree& o, uint32_t out[8])
+{
+    out[0] = (uint32_t)o.nodes.size(); out[1] = o.inner; out[2] = o.leaves; out[3] = o.empty_leaves;
+    out[4] = o.max_depth; out[5] = (uint32_t)o.leaf_tris.size(); out[6] = 0u; out[7] = 0u;
+}
+
 }  // namespace mi355rt

@@ -288,8 +288,7 @@ bool Renderer::init(const SceneData& scene, std::string& err, int& code)
         const auto t_oct = std::chrono::steady_clock::now();
         build_octree(scene.tri_verts.data(), ntri, cfg.triangles_per_leaf, oct);
         build_ms_[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_oct).count();
-        oct_stats_[0] = (uint32_t)oct.nodes.size(); oct_stats_[1] = oct.inner; oct_stats_[2] = oct.leaves;
-        oct_stats_[3] = oct.empty_leaves; oct_stats_[4] = oct.max_depth; oct_stats_[5] = (uint32_t)oct.leaf_tris.size();
+        octree_counts(oct, oct_stats_);
         std::vector<BvhTri> prim_tris(std::max(ntri, 1u));
         std::memset(prim_tris.data(), 0, prim_tris.size() * sizeof(BvhTri));
         for (uint32_t t = 0; t < ntri; ++t) {
