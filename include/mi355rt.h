@@ -642,6 +642,70 @@ int  mi355rt_lens_rays(mi355rt_handle* h, uint32_t spp, uint32_t where, float* r
  * unknown `where`; a device group (config.device_count > 1). */
 int  mi355rt_render_tiles(mi355rt_handle* h, const uint8_t* tile_mask, size_t ntiles, uint32_t spp, uint32_t where, mi355rt_ray_counts* counts);
 
+/* ---- FEATURE FILM: per-sample guides, coverage (alpha), denoising under any rays (no reference counterpart).
+ * The GUIDES of the denoised read-out rest on one centre ray per pixel: pinhole-sharp under a thin lens, absent for a film of mi355rt_render_rays, aliased
+ * at every edge, and silent about which share of a pixel's samples hit the scene.  The feature film accumulates the PRIMARY HIT's attributes over jittered
+ * samples, under the handle's lens or along the caller's rays, beside the film.  It is a read-side pass of its own: no trace, shade, resolve or fused
+ * launch changes, and a handle that never calls these entries allocates nothing and launches nothing new.
+ *
+ * PLANES.  Five planes over width * height pixels: n (u32), hits (u32), depth (f32), normal (3 x f32), albedo (3 x f32): 36 bytes per pixel, allocated (zeroed)
+ * on the first call that needs them and counted in mi355rt_hbm_allocated_bytes.  There is no create-time flag.
+ *
+ * mi355rt_features_render(h, spp).  For every owned pixel p and s = 0 .. spp-1, in this order: the sample's key is (p, feat_n[p] + s); its ray is the ray
+ * mi355rt_lens_rays would make for that key under the handle's current lens (PINHOLE included, and the MI355RT_FLAG_FIX_ROW_INDEX mapping): lens_ray with the
+ * four pcg4d(p, sampleno, 0, seed) words; its hit (t, u, v, prim) is what mi355rt_intersect_rays returns for that ray in the handle's intersector semantics.
+ * Then n += 1 and, ON A HIT ONLY (a miss adds nothing, not even +0.0):
+ *     hits += 1;  depth = depth + t;  normal[c] = normal[c] + N[prim][c];  albedo[c] = albedo[c] + A[c]
+ * with N and A exactly the normal and albedo GUIDES defines above; each is one f32 addition with the handle's value on the left, in sample order.  Because the
+ * keys are the film's own, a feature film and a film that both start cleared and take the same spp see the SAME RAYS: hits[p] is then the number of the
+ * film's samples that hit.
+ *
+ * mi355rt_features_render_rays(h, rays6, nrays, spp, where).  The same accumulation along caller rays; layout and `where` as in mi355rt_render_rays: ray
+ * (s * npix + p), nrays == npix * spp, HOST is staged through a temporary device buffer, DEVICE is read in place.  Keys play no part: nothing is random after
+ * the ray.  Rows the handle does not own are neither read nor written.
+ *
+ * mi355rt_features_get(h, n, hits, depth, normal3, albedo3, npix).  Any pointer may be NULL, not all of them; npix must equal width * height.  A striped
+ * handle returns zeros in the rows it does not own.  A feature film that was never allocated reads as zeros (and stays unallocated).
+ * mi355rt_features_clear(h).  Zeroes the planes (owned rows) and the view stamp below.
+ * mi355rt_features_alpha(h, alpha, npix).  alpha[p] = n == 0 ? 0.0f : (float)hits / (float)n: one IEEE division.
+ *
+ * VIEW STAMP.  The first accumulation into a cleared feature film records what made its rays: the camera (rotation, orientation, max_xy, the FIX_ROW_INDEX bit
+ * and the lens: the key of the guides cache), or "caller rays".  A later mi355rt_features_render under a different camera stamp, or a mix of camera and caller
+ * rays, returns MI355RT_E_INVALID, names mi355rt_features_clear in mi355rt_last_error and writes nothing.  mi355rt_film_clear, mi355rt_film_set, camera moves
+ * and mi355rt_set_lens do NOT touch the feature film.
+ *
+ * AROUND THE CALLS.  Synchronous like mi355rt_get_guides; a queued mi355rt_render_async and a speculative 50-row frame are settled first.  The film, the
+ * direct film, the counters of mi355rt_last_counts, mi355rt_current_row, the changed-row tracking and the caller-ray mark stay as they are.  Striped handles
+ * work on their rows.
+ *
+ * GUIDE SOURCE.  mi355rt_set_guide_source(h, MI355RT_GUIDES_CENTRE | MI355RT_GUIDES_FEATURES); CENTRE is the state at creation, and with it every entry
+ * returns the bits it returns without this section.  With FEATURES, mi355rt_get_guides, mi355rt_get_denoised_pixels, ..._split, and
+ * mi355rt_display_histogram / mi355rt_get_display_pixels with sources 1 and 2 take their guides from the feature film; per pixel, f32, unfused, in this order:
+ *     h = hits[p];  h == 0 (which includes n == 0): a miss guide (prim 0xFFFFFFFF, zeros)
+ *     fh = (float)h;  inv = 1.0f / fh
+ *     depth = dsum * inv;   m[c] = nsum[c] * inv;   albedo[c] = asum[c] * inv
+ *     len = sqrtf((m.x*m.x + m.y*m.y) + m.z*m.z)
+ *     normal[c] = len > 0 ? m[c] / len : 0.0f          (three divisions)
+ *     prim = 0                                          (the filter only asks "miss or not")
+ * The converted guides are cached in guide buffers of their own (32 bytes per pixel, allocated on first use) and rebuilt when the feature film changes.
+ * Under FEATURES: an empty feature film (never accumulated since its last clear) returns MI355RT_E_INVALID; a camera-stamped feature film whose stamp
+ * differs from the handle's current view returns MI355RT_E_INVALID and names mi355rt_features_clear; the caller-ray guard on the film is LIFTED for the
+ * denoised and display read-outs when the feature film is caller-stamped — if it is not, the read-out is refused with a message naming
+ * mi355rt_features_render_rays.  mi355rt_render_adaptive stays refused for a caller-ray film.
+ *
+ * ERRORS.  MI355RT_E_INVALID, the argument named in mi355rt_last_error and nothing written, for: a device group (config.device_count > 1); spp == 0; nrays !=
+ * width * height * spp; npix != width * height; rays6 NULL; an unknown `where` or guide source; every output pointer NULL.
+ * Film files, mi355rt_film_set / _add do not carry the feature film. */
+#define MI355RT_GUIDES_CENTRE   0u   /* one centre ray per pixel: GUIDES of the denoised read-out */
+#define MI355RT_GUIDES_FEATURES 1u   /* the feature film's means */
+int  mi355rt_features_render(mi355rt_handle* h, uint32_t spp);
+int  mi355rt_features_render_rays(mi355rt_handle* h, const float* rays6, size_t nrays, uint32_t spp, uint32_t where);
+int  mi355rt_features_get(mi355rt_handle* h, uint32_t* n, uint32_t* hits, float* depth, float* normal3, float* albedo3, size_t npix);
+int  mi355rt_features_clear(mi355rt_handle* h);
+int  mi355rt_features_alpha(mi355rt_handle* h, float* alpha, size_t npix);
+int  mi355rt_set_guide_source(mi355rt_handle* h, uint32_t source);
+uint32_t mi355rt_get_guide_source(const mi355rt_handle* h);
+
 /* SampleGenerator table, sample_generator.rs:15-24: 65 536 x 3 floats */
 int mi355rt_get_sample_table(const mi355rt_handle* h, float* out);
 /* Per-node direct-light terms of one primary sample, computed on the device by the same

@@ -154,6 +154,10 @@ LENS_PINHOLE, LENS_THIN, LENS_ORTHO = 0, 1, 2      # MI355RT_LENS_*
 LENS_MODELS = {"pinhole": LENS_PINHOLE, "thin": LENS_THIN, "ortho": LENS_ORTHO}
 
 
+GUIDES_CENTRE, GUIDES_FEATURES = 0, 1      # MI355RT_GUIDES_*: where the denoised and display read-outs take their guides from
+GUIDE_SOURCES = {"centre": GUIDES_CENTRE, "features": GUIDES_FEATURES}
+
+
 class Lens(C.Structure):
     """mi355rt_lens: the ray generator of render() (include/mi355rt.h, "lens models"): model LENS_*, radius and focus (THIN), width_world (ORTHO)"""
     _fields_ = [("model", C.c_uint32), ("radius", C.c_float), ("focus", C.c_float), ("width_world", C.c_float)]
@@ -224,6 +228,13 @@ ABI = [
     ("mi355rt_lens_ray", C.c_int, [_F, _F, _F, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Lens), C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, _F]),
     ("mi355rt_lens_rays", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
     ("mi355rt_render_tiles", C.c_int, [_H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(RayCounts)]),
+    ("mi355rt_features_render", C.c_int, [_H, C.c_uint32]),
+    ("mi355rt_features_render_rays", C.c_int, [_H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32]),
+    ("mi355rt_features_get", C.c_int, [_H, _U, _U, _F, _F, _F, C.c_size_t]),
+    ("mi355rt_features_clear", C.c_int, [_H]),
+    ("mi355rt_features_alpha", C.c_int, [_H, _F, C.c_size_t]),
+    ("mi355rt_set_guide_source", C.c_int, [_H, C.c_uint32]),
+    ("mi355rt_get_guide_source", C.c_uint32, [_H]),
     ("mi355rt_get_sample_table", C.c_int, [_H, _F]),
     ("mi355rt_debug_sample", C.c_int, [_H, C.c_uint32, C.c_uint32, _F, _F, C.c_size_t]),
     ("mi355rt_debug_numerics", C.c_int, [_H, _F, _F, C.c_size_t, _F, _F, _F]),
@@ -489,6 +500,51 @@ class Film:
         return out
 
 
+class Features:
+    """The feature film of a RayTracer (include/mi355rt.h, "FEATURE FILM"): per pixel, the primary hits' depth, normal and albedo summed
+    over jittered samples, and how many samples hit.  raytracer_rs_amd.features states the arithmetic in numpy."""
+
+    def __init__(self, rt):
+        self._rt = rt
+
+    def render(self, spp):
+        """mi355rt_features_render: spp samples per owned pixel under the handle's lens, keys (p, feat_n[p] + s): the rays a cleared film's render(spp) takes"""
+        spp = int(spp)
+        if spp < 0:
+            raise ValueError("spp must be >= 1")
+        self._rt._check(lib().mi355rt_features_render(self._rt._h, spp))
+
+    def render_rays(self, rays6, spp):
+        """mi355rt_features_render_rays: the same accumulation along the caller's rays; rays6 and spp as RayTracer.render_rays takes them (a numpy array,
+        or a torch tensor on the handle's GPU, which is read in place)"""
+        spp = int(spp)
+        if spp < 0:
+            raise ValueError("spp must be >= 1")
+        addr, n, dev = _ray_array(rays6, "rays6", 6, np.float32)
+        if dev:
+            import torch
+            torch.cuda.current_stream(rays6.device).synchronize()
+        self._rt._check(lib().mi355rt_features_render_rays(self._rt._h, addr, n, spp, RAYS_DEVICE if dev else RAYS_HOST))
+
+    def get(self):
+        """mi355rt_features_get: dict(n uint32[npix], hits uint32[npix], depth float32[npix], normal float32[npix, 3], albedo float32[npix, 3])"""
+        n = self._rt.width * self._rt.height
+        p = dict(n=np.zeros(n, np.uint32), hits=np.zeros(n, np.uint32), depth=np.zeros(n, np.float32),
+                 normal=np.zeros((n, 3), np.float32), albedo=np.zeros((n, 3), np.float32))
+        self._rt._check(lib().mi355rt_features_get(self._rt._h, _up(p["n"]), _up(p["hits"]), _fp(p["depth"]), _fp(p["normal"]), _fp(p["albedo"]), n))
+        return p
+
+    def alpha(self):
+        """mi355rt_features_alpha: float32[npix], hits / n (0 where n == 0): the share of a pixel's samples that hit the scene"""
+        out = np.zeros(self._rt.width * self._rt.height, np.float32)
+        self._rt._check(lib().mi355rt_features_alpha(self._rt._h, _fp(out), out.size))
+        return out
+
+    def clear(self):
+        """mi355rt_features_clear: zero planes (owned rows), no view stamp"""
+        self._rt._check(lib().mi355rt_features_clear(self._rt._h))
+
+
 class RayTracer:
     """raytracer/mod.rs:32-47.  Construct through create_raytracer* below."""
 
@@ -503,6 +559,7 @@ class RayTracer:
         # frees its tens of GB of pass buffers) at once instead of whenever the cycle collector runs
         self.camera = Camera(weakref.proxy(self))
         self.film = Film(weakref.proxy(self))
+        self.features = Features(weakref.proxy(self))
 
     def close(self):
         if self._h:
@@ -638,6 +695,17 @@ class RayTracer:
         g = dict(depth=np.zeros(n, np.float32), normal=np.zeros((n, 3), np.float32), albedo=np.zeros((n, 3), np.float32), prim=np.zeros(n, np.uint32))
         self._check(lib().mi355rt_get_guides(self._h, _fp(g["depth"]), _fp(g["normal"]), _fp(g["albedo"]), _up(g["prim"]), n))
         return g
+
+    def set_guide_source(self, source):
+        """mi355rt_set_guide_source: "centre" (one centre ray per pixel, the state at creation) or "features" (the feature film's means); a GUIDES_* number is
+        accepted in place of the name.  Under "features", guides() and the denoised and display read-outs take their guides from rt.features."""
+        self._check(lib().mi355rt_set_guide_source(self._h, GUIDE_SOURCES[source] if isinstance(source, str) else int(source)))
+
+    @property
+    def guide_source(self):
+        """mi355rt_get_guide_source by name: "centre" or "features" (the keys of GUIDE_SOURCES)"""
+        s = int(lib().mi355rt_get_guide_source(self._h))
+        return {v: k for k, v in GUIDE_SOURCES.items()}.get(s, s)
 
     def set_seed(self, seed):
         self._check(lib().mi355rt_set_seed(self._h, seed))

@@ -158,6 +158,53 @@ bool camera_film_ok(mi355rt_handle* h, const char* fn)
     h->r->last_error = std::string(fn) + ": the film holds samples of mi355rt_render_rays, which the camera's guides and tiles do not describe; mi355rt_film_clear or mi355rt_film_set first";
     return false;
 }
+// The guard of everything that reads guides (include/mi355rt.h, "FEATURE FILM", GUIDE SOURCE).  MI355RT_GUIDES_CENTRE: camera_film_ok for the read-outs of the
+// film (film_readout), nothing for mi355rt_get_guides — what it always was.  MI355RT_GUIDES_FEATURES: the feature film must hold samples, a camera-stamped one
+// of the handle's current view; a film of caller rays is served exactly when the feature film is caller-stamped.
+bool guides_ok(mi355rt_handle* h, const char* fn, bool film_readout)
+{
+    Renderer* r = h->r;
+    if (r->guide_source() != MI355RT_GUIDES_FEATURES) return !film_readout || camera_film_ok(h, fn);
+    std::string e;
+    if (r->feature_stamp() == Renderer::kFeatEmpty) e = "the guide source is MI355RT_GUIDES_FEATURES and the feature film is empty; mi355rt_features_render or mi355rt_features_render_rays first";
+    else if (r->feature_stamp() == Renderer::kFeatCamera && !r->feature_view_current())
+        e = "the feature film was accumulated under another camera, FIX_ROW_INDEX bit or lens than the handle has now; mi355rt_features_clear and accumulate again";
+    else if (film_readout && r->caller_ray_film() && r->feature_stamp() != Renderer::kFeatRays)
+        e = "the film holds samples of mi355rt_render_rays, which a camera's feature film does not describe; mi355rt_features_clear, then mi355rt_features_render_rays with the same rays";
+    if (e.empty()) return true;
+    r->last_error = std::string(fn) + ": " + e;
+    return false;
+}
+// the checks of mi355rt_features_render / mi355rt_features_render_rays (include/mi355rt.h, "FEATURE FILM"); on failure last_error names the argument
+bool features_call_ok(mi355rt_handle* h, const char* fn, bool rays, const float* rays6, size_t nrays, uint32_t spp, uint32_t where)
+{
+    if (!h) return false;
+    Renderer* r = h->r;
+    std::string e;
+    if (h->g->size() > 1) e = "not available on a device group (config.device_count > 1)";
+    else if (rays && where > MI355RT_RAYS_DEVICE) e = "unknown `where` (MI355RT_RAYS_HOST or MI355RT_RAYS_DEVICE)";
+    else if (spp == 0) e = "spp must be >= 1";
+    else if (rays && nrays != (size_t)r->cfg.width * r->cfg.height * spp) e = "nrays must equal width * height * spp";
+    else if (rays && !rays6) e = "rays6 is NULL";
+    else if (rays && r->feature_stamp() == Renderer::kFeatCamera) e = "the feature film holds camera samples, caller rays cannot be mixed in; mi355rt_features_clear first";
+    else if (!rays && r->feature_stamp() == Renderer::kFeatRays) e = "the feature film holds caller-ray samples, camera samples cannot be mixed in; mi355rt_features_clear first";
+    else if (!rays && r->feature_stamp() == Renderer::kFeatCamera && !r->feature_view_current())
+        e = "the feature film was accumulated under another camera, FIX_ROW_INDEX bit or lens than the handle has now; mi355rt_features_clear first";
+    if (e.empty()) return true;
+    r->last_error = std::string(fn) + ": " + e;
+    return false;
+}
+// the checks mi355rt_features_get / _alpha / _clear share: one device, a whole image
+bool features_handle_ok(mi355rt_handle* h, const char* fn, bool sized, size_t npix)
+{
+    if (!h) return false;
+    const char* e = nullptr;
+    if (h->g->size() > 1) e = "not available on a device group (config.device_count > 1)";
+    else if (sized && npix != (size_t)h->r->cfg.width * h->r->cfg.height) e = "npix must equal width * height";
+    if (!e) return true;
+    h->r->last_error = std::string(fn) + ": " + e;
+    return false;
+}
 // the checks mi355rt_trace_rays and mi355rt_render_rays share
 bool ray_call_ok(mi355rt_handle* h, const char* fn, const float* rays6, size_t n, uint32_t where)
 {
@@ -403,7 +450,7 @@ int mi355rt_get_denoised_pixels(mi355rt_handle* h, const mi355rt_denoise_config*
 {
     if (!denoise_handle_ok(h, npix) || !denoise_config_ok(h, cfg)) return MI355RT_E_INVALID;
     if (!rgb && !packed) { h->r->last_error = "denoise: rgb and packed are both NULL"; return MI355RT_E_INVALID; }
-    if (!camera_film_ok(h, "mi355rt_get_denoised_pixels")) return MI355RT_E_INVALID;
+    if (!guides_ok(h, "mi355rt_get_denoised_pixels", true)) return MI355RT_E_INVALID;
     return h->r->get_denoised(*cfg, rgb, packed) ? MI355RT_OK : MI355RT_E_HIP;
 }
 
@@ -412,15 +459,58 @@ int mi355rt_get_denoised_pixels_split(mi355rt_handle* h, const mi355rt_denoise_c
     if (!denoise_handle_ok(h, npix) || !denoise_config_ok(h, cfg)) return MI355RT_E_INVALID;
     if (!rgb && !packed) { h->r->last_error = "denoise: rgb and packed are both NULL"; return MI355RT_E_INVALID; }
     if (!h->r->has_direct_film()) { h->r->last_error = "denoise: the split read-out needs a handle created with MI355RT_FLAG_DIRECT_FILM"; return MI355RT_E_INVALID; }
-    if (!camera_film_ok(h, "mi355rt_get_denoised_pixels_split")) return MI355RT_E_INVALID;
+    if (!guides_ok(h, "mi355rt_get_denoised_pixels_split", true)) return MI355RT_E_INVALID;
     return h->r->get_denoised(*cfg, rgb, packed, true) ? MI355RT_OK : MI355RT_E_HIP;
 }
 
 int mi355rt_get_guides(mi355rt_handle* h, float* depth, float* normal3, float* albedo3, uint32_t* prim, size_t npix)
 {
     if (!denoise_handle_ok(h, npix)) return MI355RT_E_INVALID;
+    if (!guides_ok(h, "mi355rt_get_guides", false)) return MI355RT_E_INVALID;
     return h->r->get_guides(depth, normal3, albedo3, prim) ? MI355RT_OK : MI355RT_E_HIP;
 }
+
+int mi355rt_features_render(mi355rt_handle* h, uint32_t spp)
+{
+    if (!features_call_ok(h, "mi355rt_features_render", false, nullptr, 0, spp, 0u)) return MI355RT_E_INVALID;
+    return h->r->features_render(nullptr, spp, false) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_features_render_rays(mi355rt_handle* h, const float* rays6, size_t nrays, uint32_t spp, uint32_t where)
+{
+    if (!features_call_ok(h, "mi355rt_features_render_rays", true, rays6, nrays, spp, where)) return MI355RT_E_INVALID;
+    return h->r->features_render(rays6, spp, where == MI355RT_RAYS_DEVICE) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_features_get(mi355rt_handle* h, uint32_t* n, uint32_t* hits, float* depth, float* normal3, float* albedo3, size_t npix)
+{
+    if (!features_handle_ok(h, "mi355rt_features_get", true, npix)) return MI355RT_E_INVALID;
+    if (!n && !hits && !depth && !normal3 && !albedo3) { h->r->last_error = "mi355rt_features_get: every output pointer is NULL"; return MI355RT_E_INVALID; }
+    return h->r->features_get(n, hits, depth, normal3, albedo3) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_features_clear(mi355rt_handle* h)
+{
+    if (!features_handle_ok(h, "mi355rt_features_clear", false, 0)) return MI355RT_E_INVALID;
+    return h->r->features_clear() ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_features_alpha(mi355rt_handle* h, float* alpha, size_t npix)
+{
+    if (!features_handle_ok(h, "mi355rt_features_alpha", true, npix)) return MI355RT_E_INVALID;
+    if (!alpha) { h->r->last_error = "mi355rt_features_alpha: alpha is NULL"; return MI355RT_E_INVALID; }
+    return h->r->features_alpha(alpha) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_set_guide_source(mi355rt_handle* h, uint32_t source)
+{
+    if (!features_handle_ok(h, "mi355rt_set_guide_source", false, 0)) return MI355RT_E_INVALID;
+    if (source > MI355RT_GUIDES_FEATURES) { h->r->last_error = "mi355rt_set_guide_source: unknown source (MI355RT_GUIDES_CENTRE or MI355RT_GUIDES_FEATURES)"; return MI355RT_E_INVALID; }
+    h->r->set_guide_source(source);
+    return MI355RT_OK;
+}
+
+uint32_t mi355rt_get_guide_source(const mi355rt_handle* h) { return h ? h->r->guide_source() : 0u; }
 
 void mi355rt_display_default_config(mi355rt_display_config* cfg)
 {
@@ -437,7 +527,7 @@ int mi355rt_display_histogram(mi355rt_handle* h, uint32_t source, const mi355rt_
     if (!out) { h->r->last_error = "display: null histogram output"; return MI355RT_E_INVALID; }
     mi355rt_denoise_config dcfg;
     if (!display_denoise_config(h, source, dn, dcfg)) return MI355RT_E_INVALID;
-    if (source != MI355RT_DISPLAY_SOURCE_FILM && !camera_film_ok(h, "mi355rt_display_histogram")) return MI355RT_E_INVALID;
+    if (source != MI355RT_DISPLAY_SOURCE_FILM && !guides_ok(h, "mi355rt_display_histogram", true)) return MI355RT_E_INVALID;
     mi355rt_luminance_histogram hist;
     if (!h->r->display_histogram(source, dcfg, hist)) return MI355RT_E_HIP;
     *out = hist;
@@ -470,7 +560,7 @@ int mi355rt_get_display_pixels(mi355rt_handle* h, const mi355rt_display_config* 
     if (e) { h->r->last_error = e; return MI355RT_E_INVALID; }
     mi355rt_denoise_config dcfg;
     if (!display_denoise_config(h, cfg->source, dn, dcfg)) return MI355RT_E_INVALID;
-    if (cfg->source != MI355RT_DISPLAY_SOURCE_FILM && !camera_film_ok(h, "mi355rt_get_display_pixels")) return MI355RT_E_INVALID;
+    if (cfg->source != MI355RT_DISPLAY_SOURCE_FILM && !guides_ok(h, "mi355rt_get_display_pixels", true)) return MI355RT_E_INVALID;
     float used = 0.0f;
     if (!h->r->get_display(*cfg, dcfg, packed, used)) return MI355RT_E_HIP;
     if (exposure_used) *exposure_used = used;

@@ -22,6 +22,11 @@
 // loop on this side (RayTracer::refine: mi355rt_adaptive_tile_mask, then mi355rt_render_tiles) with --abs-floor, --min-spp, --max-spp and --batch as --adaptive
 // takes them, and prints the line --adaptive prints.  Both work with --lens (--refine is adaptive sampling's way under a lens) and exclude --gpus, -i and --adaptive;
 // --refine excludes --spp.
+// Feature film (mi355rt_features_render): --features N accumulates N feature samples after the render — under --ortho-width along the rays an N-sample
+// orthographic render of a cleared film takes (the render's own rays when N equals --spp), through mi355rt_features_render_rays.  --denoise-guides centre|features
+// selects where --denoise / --denoise-split and the display options take their guides from (mi355rt_set_guide_source; features needs --features, and lifts the
+// exclusion of --denoise under --ortho-width).  --alpha (needs --features and a .png --out) writes an RGBA PNG: the RGB bytes are what they would be without the
+// option, A = (uint32_t)(alpha * 255.0f + 0.5f) of mi355rt_features_alpha; the colour is premultiplied by construction, because a miss is black.
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -30,14 +35,17 @@
 #include <zlib.h>
 #include "../raytracer_lib.hpp"
 
-// 8-bit RGB PNG: one IDAT chunk, filter type 0 on every scanline
-static bool write_png(const std::string& path, const std::vector<uint32_t>& argb, size_t width, size_t height)
+// 8-bit RGB PNG (alpha == nullptr) or RGBA PNG (one alpha byte per pixel): one IDAT chunk, filter type 0 on every scanline
+static bool write_png(const std::string& path, const std::vector<uint32_t>& argb, size_t width, size_t height, const std::vector<unsigned char>* alpha = nullptr)
 {
     std::vector<unsigned char> raw;
-    raw.reserve((width * 3 + 1) * height);
+    raw.reserve((width * (alpha ? 4 : 3) + 1) * height);
     for (size_t y = 0; y < height; ++y) {
         raw.push_back(0);
-        for (size_t x = 0; x < width; ++x) { uint32_t p = argb[y * width + x]; raw.push_back((unsigned char)(p >> 16)); raw.push_back((unsigned char)(p >> 8)); raw.push_back((unsigned char)p); }
+        for (size_t x = 0; x < width; ++x) {
+            uint32_t p = argb[y * width + x]; raw.push_back((unsigned char)(p >> 16)); raw.push_back((unsigned char)(p >> 8)); raw.push_back((unsigned char)p);
+            if (alpha) raw.push_back((*alpha)[y * width + x]);
+        }
     }
     uLongf clen = compressBound((uLong)raw.size());
     std::vector<unsigned char> comp(clen);
@@ -56,7 +64,7 @@ static bool write_png(const std::string& path, const std::vector<uint32_t>& argb
     static const unsigned char sig[8] = { 0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A };
     std::fwrite(sig, 1, 8, f);
     unsigned char ihdr[13]; be32(ihdr, (uint32_t)width); be32(ihdr + 4, (uint32_t)height);
-    ihdr[8] = 8; ihdr[9] = 2; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;          // 8 bit, colour type 2 (RGB)
+    ihdr[8] = 8; ihdr[9] = alpha ? 6 : 2; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;          // 8 bit, colour type 2 (RGB) or 6 (RGBA)
     chunk("IHDR", ihdr, 13);
     chunk("IDAT", comp.data(), (uint32_t)clen);
     chunk("IEND", nullptr, 0);
@@ -130,6 +138,8 @@ int main(int argc, char** argv)
     mi355rt_lens_default(&lens);
     bool have_lens = false, have_region = false, refine = false;
     long long region[4] = { 0, 0, 0, 0 };
+    size_t features = 0;
+    bool guides_features = false, alpha = false;
     auto parse_float = [](const char* s, float& out) { if (!s || !*s) return false; char* end = nullptr; const float f = std::strtof(s, &end); if (*end != '\0' || !std::isfinite(f)) return false; out = f; return true; };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -177,6 +187,14 @@ int main(int argc, char** argv)
         else if (a == "--lens-radius") { float f; if (parse_float(take(), f)) lens.radius = f; }
         else if (a == "--focus") { float f; if (parse_float(take(), f)) lens.focus = f; }
         else if (a == "--lens-width") { float f; if (parse_float(take(), f)) lens.width_world = f; }
+        else if (a == "--features") { size_t t; if (parse_usize(take(), t)) features = t; }
+        else if (a == "--denoise-guides") {
+            const std::string g = v ? take() : "";
+            if (g == "features") guides_features = true;
+            else if (g == "centre") guides_features = false;
+            else { std::fprintf(stderr, "Error: --denoise-guides takes centre or features\n"); return 1; }
+        }
+        else if (a == "--alpha") alpha = true;
         else if (a == "--refine") { float f; if (parse_float(take(), f)) { acfg.rel_error = f; refine = true; } }
         else if (a == "--region") {
             const char* r = take();
@@ -202,11 +220,21 @@ int main(int argc, char** argv)
                         "                 [--region X0,Y0,X1,Y1]   (with --spp: only the tiles the pixel rectangle touches, mi355rt_render_tiles; allowed with --lens;\n"
                         "                                     excludes --gpus, -i and --adaptive)\n"
                         "                 [--refine REL [--abs-floor F] [--min-spp N] [--max-spp N] [--batch N]]   (the adaptive loop from mi355rt_adaptive_tile_mask and\n"
-                        "                                     mi355rt_render_tiles: the way to sample adaptively under --lens; excludes --spp, --gpus, -i and --adaptive)\n");
+                        "                                     mi355rt_render_tiles: the way to sample adaptively under --lens; excludes --spp, --gpus, -i and --adaptive)\n"
+                        "                 [--features N]   (after the render: N samples per pixel into the feature film, mi355rt_features_render: the primary hits' depth,\n"
+                        "                                     normal, albedo and coverage under the lens in force; under --ortho-width along the rays of an N-sample\n"
+                        "                                     orthographic render; excludes --gpus)\n"
+                        "                 [--denoise-guides centre|features]   (where --denoise, --denoise-split and the display options take their guides from; features\n"
+                        "                                     needs --features and allows --denoise with --ortho-width)\n"
+                        "                 [--alpha]   (needs --features and --out image.png: an RGBA PNG, A = coverage (hits / samples) * 255 rounded; the RGB bytes are\n"
+                        "                                     unchanged and PREMULTIPLIED by construction, because a sample that misses the scene is black)\n");
             return 0;
         }
     }
-    if (ortho && (!spp || adaptive || denoise || denoise_split || gpus > 1)) { std::fprintf(stderr, "Error: --ortho-width needs --spp and excludes --adaptive, --denoise, --denoise-split and --gpus\n"); return 1; }
+    if (ortho && (!spp || adaptive || ((denoise || denoise_split) && !guides_features) || gpus > 1)) { std::fprintf(stderr, "Error: --ortho-width needs --spp and excludes --adaptive, --denoise, --denoise-split and --gpus\n"); return 1; }
+    if (features && gpus > 1) { std::fprintf(stderr, "Error: --features excludes --gpus\n"); return 1; }
+    if (guides_features && !features) { std::fprintf(stderr, "Error: --denoise-guides features needs --features\n"); return 1; }
+    if (alpha && (!features || !(out.size() > 4 && out.compare(out.size() - 4, 4, ".png") == 0))) { std::fprintf(stderr, "Error: --alpha needs --features and --out image.png\n"); return 1; }
     // the option given together with --region / --refine that it excludes (null: none)
     auto excluded_by_tiles = [&](bool with_spp) -> const char* {
         if (with_spp && spp) return "--spp";
@@ -283,6 +311,17 @@ int main(int argc, char** argv)
         }
         std::printf("%s\n\n\n", stats.mean_stats().c_str());             // main.rs:216
         if (!save_film.empty()) rt.film.save(save_film);
+        std::vector<unsigned char> alpha8;
+        if (features) {                                                   // the feature film of the view the loop rendered
+            if (ortho) {
+                float rot[16], orient[16], max_xy[2];
+                mi355rt_camera_get(rt.handle(), rot, orient, max_xy);
+                rt.features.render_rays(ortho_rays(rot, orient, width, height, features, (uint32_t)seed, ortho_width, std::vector<uint32_t>(width * height, 0u)), (uint32_t)features);
+            } else rt.features.render((uint32_t)features);
+            std::printf("features: %zu samples per pixel\n", features);
+            if (guides_features) rt.set_guide_source(MI355RT_GUIDES_FEATURES);
+            if (alpha) for (float a : rt.features.alpha()) alpha8.push_back((unsigned char)(uint32_t)(a * 255.0f + 0.5f));
+        }
         if (frame_iterations == 0 && !load_films.empty()) ldr = rt.get_tonemapped_pixels();       // a merge-only run: the loaded film, read out once
         if (display) {                                                    // the display read-out of the film the loop left, of the source the denoise options select
             dcfg_display.source = denoise_split ? MI355RT_DISPLAY_SOURCE_DENOISED_SPLIT : denoise ? MI355RT_DISPLAY_SOURCE_DENOISED : MI355RT_DISPLAY_SOURCE_FILM;
@@ -297,7 +336,7 @@ int main(int argc, char** argv)
         if (!out.empty()) {
             const bool png = out.size() > 4 && out.compare(out.size() - 4, 4, ".png") == 0;
             if (png) {
-                if (!write_png(out, ldr, width, height)) { std::fprintf(stderr, "cannot write %s\n", out.c_str()); return 1; }
+                if (!write_png(out, ldr, width, height, alpha ? &alpha8 : nullptr)) { std::fprintf(stderr, "cannot write %s\n", out.c_str()); return 1; }
             } else {
                 FILE* f = std::fopen(out.c_str(), "wb");
                 if (!f) { std::fprintf(stderr, "cannot write %s\n", out.c_str()); return 1; }

@@ -90,7 +90,10 @@ struct DCamera {
     // rectangles, the coverage mask and the tile bins describe pinhole rays.
     DLens lens;
 };
-constexpr uint32_t kCullGrid = 1024;                       // cells per axis (32 words per row, 128 KiB)
+// The feature film of a handle (include/mi355rt.h "FEATURE FILM"): per pixel, the samples taken, how many of them hit, and the sums of the
+// primary hits' t, triangle normal and diffuse colour.  36 bytes per pixel, one allocation.
+struct FeaturePlanes { uint32_t* n; uint32_t* hits; float* depth; float* normal; float* albedo; };
+constexpr uint32_t kCullGrid = 1024;                      // cells per axis (32 words per row, 128 KiB)
 
 struct DPass {
     // primary-sample enumeration: thread i -> s = i / npix, p = i % npix,

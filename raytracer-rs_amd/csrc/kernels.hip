@@ -1634,6 +1634,117 @@ __global__ __launch_bounds__(256) void lens_rays_kernel(DCamera cam, uint32_t fl
     r[0] = a; r[1] = b;
 }
 
+// ---- feature film (include/mi355rt.h "FEATURE FILM") -----------------------------------------------------------------
+// One lane per owned pixel (entry i of the owned-row list: neighbouring lanes are neighbouring pixels of a row, so the rays of a wave stay as coherent as
+// the guides' are); the lane keeps the nine sums in registers and takes its spp samples in sample order: the ray in registers (RAYS: the caller's, ray
+// s * npix + p; else lens_ray of cam.lens with the four pcg4d(p, feat_n[p] + s, 0, seed) words, as lens_rays_kernel makes it), closest_hit on the lane's
+// LDS stack column as the guides take it, the normal and material fetch of guides_body, one f32 addition per value ON A HIT ONLY.
+// OCTREE: the handle walks the reference's octree directly (mode 1, the cross-check semantics): instantiations of their own, because octree_intersect keeps its
+// node stack in private memory (368 bytes of scratch in every kernel that holds it) — the kernels of the two shipped semantics hold none of it.
+template <bool RAYS, bool OCTREE>
+__device__ __forceinline__ void features_body(const DScene& sc, const DCamera& cam, uint32_t flags, uint32_t seed, int mode, const uint32_t* __restrict__ rows, uint32_t nrows,
+                                              uint32_t spp, const float* __restrict__ rays6, FeaturePlanes f, int* s_stack)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;               // nrows * width <= npix < 2^29 (Renderer::init)
+    if (i >= nrows * cam.width) return;
+    const uint32_t row = rows[i / cam.width], p = row * cam.width + i % cam.width;
+    const uint32_t npix = cam.width * cam.height;
+    const uint32_t n0 = f.n[p];
+    uint32_t hits = f.hits[p];
+    float depth = f.depth[p];
+    f3 nsum = mk3(f.normal[3ull * p], f.normal[3ull * p + 1], f.normal[3ull * p + 2]);
+    f3 asum = mk3(f.albedo[3ull * p], f.albedo[3ull * p + 1], f.albedo[3ull * p + 2]);
+    for (uint32_t s = 0; s < spp; ++s) {
+        f3 o, d;
+        if constexpr (RAYS) {
+            const RayHalf* r = (const RayHalf*)(rays6 + 6ull * ((size_t)s * npix + p));
+            const RayHalf a = r[0], b = r[1];
+            o = mk3(a.x, a.y, a.z); d = mk3(b.x, b.y, b.z);
+        } else {
+            uint32_t h0 = p, h1 = n0 + s, h2 = 0u, h3 = seed;
+            pcg4d(h0, h1, h2, h3);
+            lens_ray(cam.rot, cam.origin, cam.max_x, cam.max_y, cam.width, cam.height, flags, cam.lens, p, u01(h0), u01(h1), u01(h2), u01(h3), o.x, o.y, o.z, d.x, d.y, d.z);
+        }
+        float t = 0.0f, u = 0.0f, v = 0.0f; uint32_t prim = kMiss;
+        if constexpr (OCTREE) closest_hit(sc, o, d, 1, &s_stack[threadIdx.x], t, u, v, prim);
+        else closest_hit(sc, o, d, mode == 0 ? 0 : 2, &s_stack[threadIdx.x], t, u, v, prim);
+        if (prim != kMiss) {
+            const float4 nn = ((const float4*)sc.normals)[prim];
+            const DMaterial m = sc.materials[__float_as_uint(nn.w)];
+            f3 diffuse = mk3(m.r, m.g, m.b);
+            if (m.kind_tex & 0x80000000u) diffuse = fetch_texel(sc, m.kind_tex & 0x7FFFFFFFu, u, v);
+            hits += 1u;
+            depth = depth + t;
+            nsum.x = nsum.x + nn.x; nsum.y = nsum.y + nn.y; nsum.z = nsum.z + nn.z;
+            asum.x = asum.x + diffuse.x; asum.y = asum.y + diffuse.y; asum.z = asum.z + diffuse.z;
+        }
+    }
+    f.n[p] = n0 + spp; f.hits[p] = hits; f.depth[p] = depth;
+    f.normal[3ull * p] = nsum.x; f.normal[3ull * p + 1] = nsum.y; f.normal[3ull * p + 2] = nsum.z;
+    f.albedo[3ull * p] = asum.x; f.albedo[3ull * p + 1] = asum.y; f.albedo[3ull * p + 2] = asum.z;
+}
+// 5 blocks: the lens feed came to 98 VGPRs, two over the 96 of five waves per SIMD; bounded it fits (96, no scratch: profiles/features_kernel_resources.txt)
+__global__ __launch_bounds__(kBlock, 5) void features_kernel(DScene sc, DCamera cam, uint32_t flags, uint32_t seed, int mode, const uint32_t* __restrict__ rows, uint32_t nrows,
+                                                         uint32_t spp, FeaturePlanes f)
+{
+    extern __shared__ int s_stack[];
+    features_body<false, false>(sc, cam, flags, seed, mode, rows, nrows, spp, nullptr, f, s_stack);
+}
+__global__ __launch_bounds__(kBlock) void features_rays_kernel(DScene sc, DCamera cam, int mode, const uint32_t* __restrict__ rows, uint32_t nrows,
+                                                              uint32_t spp, const float* __restrict__ rays6, FeaturePlanes f)
+{
+    extern __shared__ int s_stack[];
+    features_body<true, false>(sc, cam, 0u, 0u, mode, rows, nrows, spp, rays6, f, s_stack);
+}
+__global__ __launch_bounds__(kBlock) void features_octree_kernel(DScene sc, DCamera cam, uint32_t flags, uint32_t seed, const uint32_t* __restrict__ rows, uint32_t nrows,
+                                                                uint32_t spp, FeaturePlanes f)
+{
+    extern __shared__ int s_stack[];
+    features_body<false, true>(sc, cam, flags, seed, 1, rows, nrows, spp, nullptr, f, s_stack);
+}
+__global__ __launch_bounds__(kBlock) void features_rays_octree_kernel(DScene sc, DCamera cam, const uint32_t* __restrict__ rows, uint32_t nrows,
+                                                                     uint32_t spp, const float* __restrict__ rays6, FeaturePlanes f)
+{
+    extern __shared__ int s_stack[];
+    features_body<true, true>(sc, cam, 0u, 0u, 1, rows, nrows, spp, rays6, f, s_stack);
+}
+// mi355rt_features_clear: the planes of the listed rows
+__global__ __launch_bounds__(256) void features_clear_kernel(const uint32_t* __restrict__ rows, uint32_t nrows, uint32_t width, FeaturePlanes f)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nrows * width) return;
+    const size_t p = (size_t)rows[i / width] * width + i % width;
+    f.n[p] = 0u; f.hits[p] = 0u; f.depth[p] = 0.0f;
+    f.normal[3 * p] = 0.0f; f.normal[3 * p + 1] = 0.0f; f.normal[3 * p + 2] = 0.0f;
+    f.albedo[3 * p] = 0.0f; f.albedo[3 * p + 1] = 0.0f; f.albedo[3 * p + 2] = 0.0f;
+}
+// MI355RT_GUIDES_FEATURES: the feature film's means in the g0 / g1 format of the guides (g0 = (normal, t), g1 = (albedo, prim bits)); the arithmetic is the
+// header's, f32 and unfused, in its order.  A pixel without a hit is a miss guide; a hit's prim is 0 (the filter only asks "miss or not").
+__global__ __launch_bounds__(256) void features_guides_kernel(uint32_t npix, FeaturePlanes f, float4* __restrict__ g0, float4* __restrict__ g1)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    const uint32_t h = f.hits[p];
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kMiss)), n = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (h != 0u) {
+        const float fh = (float)h, inv = div_rn(1.0f, fh);
+        const float mx = f.normal[3ull * p] * inv, my = f.normal[3ull * p + 1] * inv, mz = f.normal[3ull * p + 2] * inv;
+        const float len = sqrt_rn((mx * mx + my * my) + mz * mz);
+        const bool ok = len > 0.0f;
+        n = make_float4(ok ? div_rn(mx, len) : 0.0f, ok ? div_rn(my, len) : 0.0f, ok ? div_rn(mz, len) : 0.0f, f.depth[p] * inv);
+        a = make_float4(f.albedo[3ull * p] * inv, f.albedo[3ull * p + 1] * inv, f.albedo[3ull * p + 2] * inv, __uint_as_float(0u));
+    }
+    g0[p] = n; g1[p] = a;
+}
+// mi355rt_features_alpha: hits / n, one IEEE division; 0 for a pixel without samples
+__global__ __launch_bounds__(256) void features_alpha_kernel(uint32_t npix, const uint32_t* __restrict__ fn, const uint32_t* __restrict__ fhits, float* __restrict__ alpha)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    const uint32_t n = fn[p];
+    alpha[p] = n == 0u ? 0.0f : div_rn((float)fhits[p], (float)n);
+}
+
 __device__ __forceinline__ float pos0(float x) { return x > 0.0f ? x : 0.0f; }        // NaN -> 0
 
 // the read-out of one pixel: rgb (3 floats) and the packed tone-mapped value (tonemap_kernel); either may be null
@@ -2375,6 +2486,43 @@ hipError_t launch_lens_rays(hipStream_t stream, const DCamera& cam, uint32_t fla
     if (nrays == 0) return hipSuccess;
     if ((nrays + 255) / 256 > 0x7FFFFFFFull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lens_rays_kernel, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, stream, cam, flags, seed, npix, nrays, film_n, rays6);
+    return hipGetLastError();
+}
+
+hipError_t launch_features(hipStream_t stream, const DScene& sc, const DCamera& cam, uint32_t flags, uint32_t seed, uint32_t stack_depth, int mode,
+                           const uint32_t* rows, uint32_t nrows, uint32_t spp, const float* rays6, const FeaturePlanes& f)
+{
+    const uint32_t n = nrows * cam.width;
+    if (n == 0 || spp == 0) return hipSuccess;
+    const dim3 grid((n + kBlock - 1) / kBlock);
+    const size_t lds = stack_bytes(stack_depth);
+    if (mode == 1) {
+        if (rays6) hipLaunchKernelGGL(features_rays_octree_kernel, grid, dim3(kBlock), lds, stream, sc, cam, rows, nrows, spp, rays6, f);
+        else hipLaunchKernelGGL(features_octree_kernel, grid, dim3(kBlock), lds, stream, sc, cam, flags, seed, rows, nrows, spp, f);
+    } else if (rays6) hipLaunchKernelGGL(features_rays_kernel, grid, dim3(kBlock), lds, stream, sc, cam, mode, rows, nrows, spp, rays6, f);
+    else hipLaunchKernelGGL(features_kernel, grid, dim3(kBlock), lds, stream, sc, cam, flags, seed, mode, rows, nrows, spp, f);
+    return hipGetLastError();
+}
+
+hipError_t launch_features_clear(hipStream_t stream, const uint32_t* rows, uint32_t nrows, uint32_t width, const FeaturePlanes& f)
+{
+    const uint32_t n = nrows * width;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(features_clear_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, rows, nrows, width, f);
+    return hipGetLastError();
+}
+
+hipError_t launch_features_guides(hipStream_t stream, uint32_t npix, const FeaturePlanes& f, float4* g0, float4* g1)
+{
+    if (npix == 0) return hipSuccess;
+    hipLaunchKernelGGL(features_guides_kernel, dim3((npix + 255) / 256), dim3(256), 0, stream, npix, f, g0, g1);
+    return hipGetLastError();
+}
+
+hipError_t launch_features_alpha(hipStream_t stream, uint32_t npix, const FeaturePlanes& f, float* alpha)
+{
+    if (npix == 0) return hipSuccess;
+    hipLaunchKernelGGL(features_alpha_kernel, dim3((npix + 255) / 256), dim3(256), 0, stream, npix, (const uint32_t*)f.n, (const uint32_t*)f.hits, alpha);
     return hipGetLastError();
 }
 

@@ -60,6 +60,14 @@ hipError_t launch_film_stat(hipStream_t stream, bool variances, size_t npix, con
 hipError_t launch_guides(hipStream_t stream, const DScene& sc, const DCamera& cam, uint32_t flags, uint32_t stack_depth, int mode, float4* g0, float4* g1);   // cam.lens: whose centre rays
 // mi355rt_lens_rays: the rays of the next render(spp) under cam.lens, width * height * spp x (pos3, dir3) in mi355rt_render_rays layout, device memory
 hipError_t launch_lens_rays(hipStream_t stream, const DCamera& cam, uint32_t flags, uint32_t seed, uint32_t spp, const uint32_t* film_n, float* rays6);
+// feature film: spp samples of every pixel of the listed rows accumulated into f in sample order; rays6 null: the rays of cam.lens for the keys
+// (p, f.n[p] + s) (flags bit 0: FIX_ROW_INDEX), else the caller's rays in mi355rt_render_rays layout (device memory); mode as launch_intersect
+hipError_t launch_features(hipStream_t stream, const DScene& sc, const DCamera& cam, uint32_t flags, uint32_t seed, uint32_t stack_depth, int mode,
+                           const uint32_t* rows, uint32_t nrows, uint32_t spp, const float* rays6, const FeaturePlanes& f);
+hipError_t launch_features_clear(hipStream_t stream, const uint32_t* rows, uint32_t nrows, uint32_t width, const FeaturePlanes& f);
+// the feature film's means as guides (g0 = (normal, t), g1 = (albedo, prim bits): what launch_denoise reads); alpha[p] = hits / n
+hipError_t launch_features_guides(hipStream_t stream, uint32_t npix, const FeaturePlanes& f, float4* g0, float4* g1);
+hipError_t launch_features_alpha(hipStream_t stream, uint32_t npix, const FeaturePlanes& f, float* alpha);
 // film -> `iterations` filter iterations ping-ponging ping / pong (npix float4 each; flags: npix u32) -> rgb (npix * 3 floats) and / or packed (npix u32);
 // film_direct non-null: the split read-out (the indirect part is filtered, the direct part added back)
 hipError_t launch_denoise(hipStream_t stream, const DenoiseArgs& args, uint32_t iterations, const float* film_sum, const float* film_sumsq, const uint32_t* film_n,

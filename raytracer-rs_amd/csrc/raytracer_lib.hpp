@@ -71,12 +71,45 @@ private:
     mi355rt_handle* h_ = nullptr;
 };
 
+// The feature film (include/mi355rt.h "FEATURE FILM"): the primary hits' depth, normal and albedo summed over jittered samples, and coverage
+struct FeaturePlanes { std::vector<uint32_t> n, hits; std::vector<float> depth, normal, albedo; };   // npix, npix, npix, npix * 3, npix * 3
+class Features {
+public:
+    // spp samples per owned pixel under the handle's lens: the rays a cleared film's render(spp) takes
+    void render(uint32_t spp) { if (mi355rt_features_render(h_, spp) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_)); }
+    // the same along the caller's rays (host memory, the layout of RayTracer::render_rays)
+    void render_rays(const std::vector<float>& rays6, uint32_t spp)
+    {
+        if (mi355rt_features_render_rays(h_, rays6.data(), rays6.size() / 6, spp, MI355RT_RAYS_HOST) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+    }
+    FeaturePlanes get() const
+    {
+        const size_t npix = (size_t)mi355rt_width(h_) * mi355rt_height(h_);
+        FeaturePlanes p;
+        p.n.resize(npix); p.hits.resize(npix); p.depth.resize(npix); p.normal.resize(npix * 3); p.albedo.resize(npix * 3);
+        if (mi355rt_features_get(h_, p.n.data(), p.hits.data(), p.depth.data(), p.normal.data(), p.albedo.data(), npix) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+        return p;
+    }
+    // hits / n per pixel (0 where n == 0): the share of a pixel's samples that hit the scene
+    std::vector<float> alpha() const
+    {
+        std::vector<float> a((size_t)mi355rt_width(h_) * mi355rt_height(h_));
+        if (mi355rt_features_alpha(h_, a.data(), a.size()) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+        return a;
+    }
+    void clear() { if (mi355rt_features_clear(h_) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_)); }
+private:
+    friend class RayTracer;
+    mi355rt_handle* h_ = nullptr;
+};
+
 class RayTracer {         // raytracer/mod.rs:32-47
 public:
     Camera camera;
     Film film;
-    explicit RayTracer(mi355rt_handle* h) : h_(h) { camera.h_ = h; film.h_ = h; }
-    RayTracer(RayTracer&& o) noexcept : camera(o.camera), film(o.film), h_(o.h_) { o.h_ = nullptr; }
+    Features features;
+    explicit RayTracer(mi355rt_handle* h) : h_(h) { camera.h_ = h; film.h_ = h; features.h_ = h; }
+    RayTracer(RayTracer&& o) noexcept : camera(o.camera), film(o.film), features(o.features), h_(o.h_) { o.h_ = nullptr; }
     RayTracer(const RayTracer&) = delete;
     RayTracer& operator=(const RayTracer&) = delete;
     ~RayTracer() { mi355rt_destroy(h_); }
@@ -216,6 +249,9 @@ public:
         if (mi355rt_lens_rays(h_, spp, MI355RT_RAYS_HOST, rays.data(), rays.size() / 6) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
         return rays;
     }
+    // where guides(), the denoised and the display read-outs take their guides from: MI355RT_GUIDES_CENTRE (the state at creation) or MI355RT_GUIDES_FEATURES
+    void set_guide_source(uint32_t source) { if (mi355rt_set_guide_source(h_, source) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_)); }
+    uint32_t guide_source() const { return mi355rt_get_guide_source(h_); }
     mi355rt_handle* handle() const { return h_; }
 private:
     mi355rt_handle* h_;

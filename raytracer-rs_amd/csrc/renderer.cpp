@@ -1692,9 +1692,137 @@ bool Renderer::film_stat(bool variances, float* rgb)
 }
 
 // ---- denoised read-out (include/mi355rt.h) ------------------------------------------------------------------------
-// The guides on the device for the current camera, FIX_ROW_INDEX bit and lens: rebuilt (stream-ordered, on the main stream) only when that key changes
+// What a pixel's camera ray depends on: the camera, the FIX_ROW_INDEX bit and the lens.  The key of the guides cache and the camera stamp of the feature film.
+std::vector<float> Renderer::view_key()
+{
+    const DCamera cam = device_camera();
+    std::vector<float> key(cam.rot, cam.rot + 16);
+    key.insert(key.end(), cam.origin, cam.origin + 3); key.push_back(cam.max_x); key.push_back(cam.max_y);
+    key.push_back((cfg.flags & MI355RT_FLAG_FIX_ROW_INDEX) ? 1.0f : 0.0f);
+    key.push_back((float)lens_.model);                                // the lens: its model and the fields that model reads (validated: finite)
+    key.push_back(lens_.model == MI355RT_LENS_THIN ? lens_.radius : 0.0f); key.push_back(lens_.model == MI355RT_LENS_THIN ? lens_.focus : 0.0f);
+    key.push_back(lens_.model == MI355RT_LENS_ORTHO ? lens_.width_world : 0.0f);
+    return key;
+}
+
+// ---- feature film (include/mi355rt.h "FEATURE FILM") -------------------------------------------------------------------
+// Everything runs on stream_: behind a queued frame (render_async joins its slices there) and behind the rows a speculative frame gives back.  Nothing but
+// the feature film, its stamp and its version changes: no film, counter, row or dirty-row state.
+bool Renderer::ensure_features()
+{
+    if (d_features_) return true;
+    const size_t npix = (size_t)cfg.width * cfg.height;
+    DeviceBuffer<uint8_t> b;
+    HIP_TRY(b.alloc(npix * 36, &hbm_bytes_));
+    HIP_TRY(hipMemsetAsync(b.get(), 0, npix * 36, stream_));
+    d_features_ = std::move(b);
+    feat_.n = reinterpret_cast<uint32_t*>(d_features_.get());
+    feat_.hits = feat_.n + npix;
+    feat_.depth = reinterpret_cast<float*>(feat_.hits + npix);
+    feat_.normal = feat_.depth + npix;
+    feat_.albedo = feat_.normal + 3 * npix;
+    return true;
+}
+
+bool Renderer::feature_view_current() { return feat_stamp_ == kFeatCamera && feat_key_ == view_key(); }
+
+bool Renderer::features_render(const float* rays6, uint32_t spp, bool device)
+{
+    if (!bind()) return false;
+    if (!settle_speculation()) return false;
+    if (!ensure_features()) return false;
+    const size_t nrays = (size_t)cfg.width * cfg.height * spp;
+    DeviceBuffer<float> stage;
+    const float* d_rays = rays6;
+    if (rays6 && !device) {
+        HIP_TRY(stage.alloc(nrays * 24, &hbm_bytes_));
+        HIP_TRY(hipMemcpyAsync(stage.get(), rays6, nrays * 24, hipMemcpyHostToDevice, stream_));
+        d_rays = stage.get();
+    }
+    const DCamera cam = device_camera();
+    HIP_TRY(launch_features(stream_, dscene_, cam, cfg.flags & MI355RT_FLAG_FIX_ROW_INDEX, (uint32_t)cfg.seed, traversal_rows(),
+                            mode_ == kModeConfirm ? 0 : mode_ == kModeOctreeWalk ? 1 : 2, d_owned_rows_.get(), (uint32_t)owned_rows.size(), spp, d_rays, feat_));
+    if (feat_stamp_ == kFeatEmpty) {
+        feat_stamp_ = rays6 ? kFeatRays : kFeatCamera;
+        if (!rays6) feat_key_ = view_key();
+    }
+    ++feat_version_;
+    HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's rays and the staging are free again
+    return true;
+}
+
+bool Renderer::features_clear()
+{
+    if (!bind()) return false;
+    if (!settle_speculation()) return false;
+    feat_stamp_ = kFeatEmpty; feat_key_.clear();
+    ++feat_version_;
+    if (!d_features_) return true;
+    HIP_TRY(launch_features_clear(stream_, d_owned_rows_.get(), (uint32_t)owned_rows.size(), cfg.width, feat_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    return true;
+}
+
+// A feature film that was never allocated reads as the zeros it would hold
+bool Renderer::features_get(uint32_t* n, uint32_t* hits, float* depth, float* normal3, float* albedo3)
+{
+    if (!bind()) return false;
+    if (!settle_speculation()) return false;
+    const size_t npix = (size_t)cfg.width * cfg.height;
+    if (!d_features_) {
+        if (n) std::memset(n, 0, npix * 4);
+        if (hits) std::memset(hits, 0, npix * 4);
+        if (depth) std::memset(depth, 0, npix * 4);
+        if (normal3) std::memset(normal3, 0, npix * 12);
+        if (albedo3) std::memset(albedo3, 0, npix * 12);
+        return true;
+    }
+    if (n) HIP_TRY(hipMemcpyAsync(n, feat_.n, npix * 4, hipMemcpyDeviceToHost, stream_));
+    if (hits) HIP_TRY(hipMemcpyAsync(hits, feat_.hits, npix * 4, hipMemcpyDeviceToHost, stream_));
+    if (depth) HIP_TRY(hipMemcpyAsync(depth, feat_.depth, npix * 4, hipMemcpyDeviceToHost, stream_));
+    if (normal3) HIP_TRY(hipMemcpyAsync(normal3, feat_.normal, npix * 12, hipMemcpyDeviceToHost, stream_));
+    if (albedo3) HIP_TRY(hipMemcpyAsync(albedo3, feat_.albedo, npix * 12, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    return true;
+}
+
+bool Renderer::features_alpha(float* alpha)
+{
+    if (!bind()) return false;
+    if (!settle_speculation()) return false;
+    const size_t npix = (size_t)cfg.width * cfg.height;
+    if (!d_features_) { std::memset(alpha, 0, npix * 4); return true; }
+    DeviceBuffer<float> d;
+    HIP_TRY(d.alloc(npix * 4, &hbm_bytes_));
+    HIP_TRY(launch_features_alpha(stream_, (uint32_t)npix, feat_, d.get()));
+    HIP_TRY(hipMemcpyAsync(alpha, d.get(), npix * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    return true;
+}
+
+// MI355RT_GUIDES_FEATURES: the guides converted from the feature film, rebuilt (stream-ordered) only when it has changed; the caller has checked that it holds samples
+bool Renderer::refresh_feature_guides()
+{
+    const size_t npix = (size_t)cfg.width * cfg.height;
+    if (!d_features_) { last_error = "internal: no feature film"; return false; }
+    if (!d_fguide0_) {
+        DeviceBuffer<float4> g0, g1;          // both or neither
+        HIP_TRY(g0.alloc(npix * sizeof(float4), &hbm_bytes_));
+        HIP_TRY(g1.alloc(npix * sizeof(float4), &hbm_bytes_));
+        d_fguide0_ = std::move(g0); d_fguide1_ = std::move(g1);
+        fguides_version_ = feat_version_ - 1;
+    }
+    if (fguides_version_ == feat_version_) return true;
+    HIP_TRY(launch_features_guides(stream_, (uint32_t)npix, feat_, d_fguide0_.get(), d_fguide1_.get()));
+    fguides_version_ = feat_version_;
+    return true;
+}
+
+// The guides on the device for the current camera, FIX_ROW_INDEX bit and lens: rebuilt (stream-ordered, on the main stream) only when that key changes.
+// Under MI355RT_GUIDES_FEATURES: the feature film's (guide0() / guide1() name the buffers of the source in force).
 bool Renderer::refresh_guides()
 {
+    if (guide_source_ == MI355RT_GUIDES_FEATURES) return refresh_feature_guides();
     const size_t npix = (size_t)cfg.width * cfg.height;
     if (!d_guide0_) {
         DeviceBuffer<float4> g0, g1;          // both or neither
@@ -1704,12 +1832,7 @@ bool Renderer::refresh_guides()
         guides_key_.clear();
     }
     const DCamera cam = device_camera();
-    std::vector<float> key(cam.rot, cam.rot + 16);
-    key.insert(key.end(), cam.origin, cam.origin + 3); key.push_back(cam.max_x); key.push_back(cam.max_y);
-    key.push_back((cfg.flags & MI355RT_FLAG_FIX_ROW_INDEX) ? 1.0f : 0.0f);
-    key.push_back((float)lens_.model);                                // the lens: its model and the fields that model reads (validated: finite)
-    key.push_back(lens_.model == MI355RT_LENS_THIN ? lens_.radius : 0.0f); key.push_back(lens_.model == MI355RT_LENS_THIN ? lens_.focus : 0.0f);
-    key.push_back(lens_.model == MI355RT_LENS_ORTHO ? lens_.width_world : 0.0f);
+    const std::vector<float> key = view_key();
     if (key == guides_key_) return true;
     guides_key_.clear();
     HIP_TRY(launch_guides(stream_, dscene_, cam, cfg.flags & MI355RT_FLAG_FIX_ROW_INDEX, traversal_rows(), mode_ == kModeConfirm ? 0 : mode_ == kModeOctreeWalk ? 1 : 2,
@@ -1725,8 +1848,8 @@ bool Renderer::get_guides(float* depth, float* normal3, float* albedo3, uint32_t
     if (!refresh_guides()) return false;
     const size_t npix = (size_t)cfg.width * cfg.height;
     std::vector<float4> g0(npix), g1(npix);
-    HIP_TRY(hipMemcpyAsync(g0.data(), d_guide0_.get(), npix * sizeof(float4), hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipMemcpyAsync(g1.data(), d_guide1_.get(), npix * sizeof(float4), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(g0.data(), guide0(), npix * sizeof(float4), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(g1.data(), guide1(), npix * sizeof(float4), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     for (size_t p = 0; p < npix; ++p) {
         if (depth) depth[p] = g0[p].w;
@@ -1757,7 +1880,7 @@ bool Renderer::run_denoise(const mi355rt_denoise_config& dc, bool rgb, bool pack
     a.width = cfg.width; a.height = cfg.height; a.step = 1u; a.normal_power_log2 = dc.normal_power_log2;
     a.sigma_luminance = dc.sigma_luminance; a.sigma_depth = dc.sigma_depth; a.sigma_albedo = dc.sigma_albedo;
     HIP_TRY(launch_denoise(stream_, a, dc.iterations, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), split ? d_film_direct_.get() : nullptr,
-                           d_guide0_.get(), d_guide1_.get(), d_dn_flags_.get(),
+                           guide0(), guide1(), d_dn_flags_.get(),
                            d_dn_ping_.get(), d_dn_pong_.get(), rgb ? d_dn_rgb_.get() : nullptr, packed ? d_dn_packed_.get() : nullptr));
     return true;
 }

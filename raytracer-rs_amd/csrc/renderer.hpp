@@ -76,6 +76,16 @@ public:
     bool get_guides(float* depth, float* normal3, float* albedo3, uint32_t* prim);
     bool get_denoised(const mi355rt_denoise_config& dc, float* rgb, uint32_t* packed, bool split = false);   // split: the indirect part is filtered
     bool has_direct_film() const { return (cfg.flags & MI355RT_FLAG_DIRECT_FILM) != 0; }
+    // feature film; the caller has checked the arguments.  rays6 null: spp samples under the handle's lens, else along the caller's rays
+    bool features_render(const float* rays6, uint32_t spp, bool device);
+    bool features_get(uint32_t* n, uint32_t* hits, float* depth, float* normal3, float* albedo3);
+    bool features_alpha(float* alpha);
+    bool features_clear();
+    enum FeatureStamp { kFeatEmpty = 0, kFeatCamera = 1, kFeatRays = 2 };     // what made the rays of the feature film's samples
+    FeatureStamp feature_stamp() const { return feat_stamp_; }
+    bool feature_view_current();                                         // a camera-stamped feature film: its stamp is the handle's current view
+    uint32_t guide_source() const { return guide_source_; }
+    void set_guide_source(uint32_t s) { guide_source_ = s; }
     // display read-out; the caller has checked the arguments.  source: MI355RT_DISPLAY_SOURCE_*; dn is read for the denoised sources only
     bool display_histogram(uint32_t source, const mi355rt_denoise_config& dn, mi355rt_luminance_histogram& out);
     bool get_display(const mi355rt_display_config& dc, const mi355rt_denoise_config& dn, uint32_t* packed, float& exposure_used);
@@ -176,6 +186,20 @@ private:
     bool refresh_guides();
     DeviceBuffer<float4> d_guide0_, d_guide1_;
     std::vector<float> guides_key_;      // rot, origin, max_x, max_y, FIX_ROW_INDEX bit and the lens (model and the fields it reads) of the guides on the device; empty: none
+    // Feature film, allocated on first use: one buffer of 36 bytes per pixel (feat_ points into it); its view stamp; the guides converted from
+    // it (MI355RT_GUIDES_FEATURES), buffers of their own beside the centre-ray guides so that each source keeps its cache, rebuilt when feat_version_ moves on
+    bool ensure_features();
+    std::vector<float> view_key();       // the key of guides_key_ for the handle's current camera, FIX_ROW_INDEX bit and lens
+    bool refresh_feature_guides();
+    const float4* guide0() const { return guide_source_ == MI355RT_GUIDES_FEATURES ? d_fguide0_.get() : d_guide0_.get(); }
+    const float4* guide1() const { return guide_source_ == MI355RT_GUIDES_FEATURES ? d_fguide1_.get() : d_guide1_.get(); }
+    DeviceBuffer<uint8_t> d_features_;
+    FeaturePlanes feat_{};
+    FeatureStamp feat_stamp_ = kFeatEmpty;
+    std::vector<float> feat_key_;        // kFeatCamera: the view of the samples
+    uint64_t feat_version_ = 0, fguides_version_ = 0;      // fguides_version_ == feat_version_: d_fguide*_ hold the current feature film
+    DeviceBuffer<float4> d_fguide0_, d_fguide1_;
+    uint32_t guide_source_ = MI355RT_GUIDES_CENTRE;
     DeviceBuffer<float4> d_dn_ping_, d_dn_pong_;
     DeviceBuffer<uint32_t> d_dn_flags_, d_dn_packed_;
     DeviceBuffer<float> d_dn_rgb_;
