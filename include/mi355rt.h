@@ -64,6 +64,11 @@ extern "C" {
  * mi355rt_film_get_direct and used by mi355rt_get_denoised_pixels_split (see there).  12 bytes per pixel more device
  * memory; without the flag every kernel, buffer and result of the handle is what it is without this feature. */
 #define MI355RT_FLAG_DIRECT_FILM 128u
+/* Create-time: the handle keeps one LIGHT FILM per light of the scene next to the film (see LIGHT FILMS below), read with
+ * mi355rt_light_films_get and mixed without tracing by mi355rt_get_relit_pixels.  12 bytes per pixel and light more device memory; at most
+ * MI355RT_LIGHT_FILMS_MAX_LIGHTS lights, one device; without the flag every kernel, buffer and result of the handle is what it is without this feature. */
+#define MI355RT_FLAG_LIGHT_FILMS 256u
+#define MI355RT_LIGHT_FILMS_MAX_LIGHTS 8u
 
 typedef struct mi355rt_handle mi355rt_handle;
 
@@ -706,6 +711,51 @@ int  mi355rt_features_alpha(mi355rt_handle* h, float* alpha, size_t npix);
 int  mi355rt_set_guide_source(mi355rt_handle* h, uint32_t source);
 uint32_t mi355rt_get_guide_source(const mi355rt_handle* h);
 
+/* ---- LIGHT FILMS: a film per light, and relighting without tracing (no reference counterpart).
+ * A sample's colour is a sum over the scene's lights: every term of its bounce tree is (diffuse * ndl + spec) * light.color of one light (mod.rs:214-257).
+ * A handle created with MI355RT_FLAG_LIGHT_FILMS keeps, beside the film, nlights planes light[li][width * height * 3] of f32, zero at creation, owned by the
+ * handle and counted in mi355rt_hbm_allocated_bytes (12 bytes per pixel and light).  nlights == 0 is allowed (no planes).  mi355rt_create* refuses the flag
+ * with MI355RT_E_INVALID, the cause in mi355rt_last_error(NULL), for a scene of more than MI355RT_LIGHT_FILMS_MAX_LIGHTS lights and for a device group
+ * (config.device_count > 1).  mi355rt_set_flags passes the bit unchanged and cannot toggle it.
+ *
+ * STATEMENT.  The light radiance R_li of a sample is compute_radiance's value (mod.rs:146-175) with the same fold, the same order and the same 1 / k factors,
+ * where each node's light sum is (+0.0f) + term[node][li] instead of the sum over all lights: the sample's colour in a scene in which every other light's
+ * colour is (0, 0, 0).  It is (0, 0, 0) for a sample without a slot (a primary miss, or a hit the octree semantics drop).  Whenever a sample is added to a
+ * pixel's film (PixelData::add_sample), light[li] = light[li] + R_li for every li: one f32 addition with the handle's value on the left, in sample order,
+ * as the direct film takes L0.  So every entry that adds samples through the resolve (mi355rt_render, _render_async, _render_adaptive, _render_tiles,
+ * _render_rays, under any lens) adds to the light films for the same pixels and no others; an inactive tile, an unowned row or an unselected tile keeps its
+ * bits; a pixel of a culled block takes +0.0 once, as the film does.  The film itself (sum, sumsq, n, direct) is, bit for bit, the film of the same handle
+ * without the flag.  With one light, light[0] equals the film's sum.  The planes add up to the film's sum only to rounding: the film adds the lights per
+ * node before the fold, the planes after it.
+ *   mi355rt_film_clear clears the light films (owned rows).  mi355rt_film_set / _add / _load / _save and film files do NOT carry them: after a film_set
+ *   the caller restores them with the entries below, and that they match the film is the caller's word.
+ *   mi355rt_trace_frame_additive on a handle with the flag returns 0 and mi355rt_last_error names MI355RT_FLAG_LIGHT_FILMS (the fused 50-row kernel keeps
+ *   no light films).  mi355rt_debug_sample and mi355rt_trace_rays touch no light film.
+ *
+ * mi355rt_light_films_get / _set / _add: layout light_rgb[(li * npix + p) * 3 + c].  Queued work is settled first; only owned rows are written, a striped
+ * handle reads zeros elsewhere; set keeps bit patterns (a NaN's payload, -0.0); add is one f32 addition with the handle's value on the left; nothing else of
+ * the handle changes.  The staging buffer of set / add is temporary: mi355rt_hbm_allocated_bytes is the same before and after.
+ *
+ * mi355rt_get_relit_pixels: the frame under other light colours, without tracing.  weights3: nweights == nlights * 3 floats, an RGB factor per light (data,
+ * not validated).  Per pixel p and channel ch, f32 and unfused, with n the film's count:
+ *     fn = (float)n;  inv = 1.0f / fn
+ *     c[ch] = +0.0f;  for li ascending:  m = light[li][p][ch] * inv;  c[ch] = c[ch] + weights3[li * 3 + ch] * m
+ * Nothing special is done for n == 0 (NaN, white once packed, like the film's read-out).  rgb (npix * 3 floats) receives c.  packed: with display == NULL
+ * c is mapped as mi355rt_get_tonemapped_pixels maps a film mean; otherwise DISPLAY MAPPING of the display section is applied to c, display->source must be
+ * MI355RT_DISPLAY_SOURCE_FILM, and auto_exposure == 1 derives E from the HISTOGRAM of c with the film's n deciding `empty`; *exposure_used (may be NULL)
+ * receives E (1 with display == NULL).  Either of rgb and packed may be NULL, not both.  The call only reads.  A striped handle serves its rows; elsewhere
+ * its planes and n are zero.  Device memory allocated on the first call and counted in mi355rt_hbm_allocated_bytes: 16 bytes per pixel (c and packed) and 96 bytes (the weights), and
+ * with the first non-NULL display the display section's histogram and sRGB table (1040 + 1024 bytes) where that section has not allocated them yet.
+ *
+ * ERRORS.  MI355RT_E_INVALID, the argument named in mi355rt_last_error and nothing written, for: a handle without the flag (the message names
+ * MI355RT_FLAG_LIGHT_FILMS); nlights != the scene's; nweights != nlights * 3; npix != width * height; a NULL light_rgb with nlights > 0; a NULL weights3
+ * with nweights > 0; rgb and packed both NULL; a display config that mi355rt_get_display_pixels refuses, or whose source is not the film. */
+int  mi355rt_light_films_get(mi355rt_handle* h, float* light_rgb, size_t nlights, size_t npix);
+int  mi355rt_light_films_set(mi355rt_handle* h, const float* light_rgb, size_t nlights, size_t npix);
+int  mi355rt_light_films_add(mi355rt_handle* h, const float* light_rgb, size_t nlights, size_t npix);
+int  mi355rt_get_relit_pixels(mi355rt_handle* h, const float* weights3, size_t nweights, const mi355rt_display_config* display /* may be NULL */,
+                              float* rgb, uint32_t* packed, size_t npix, float* exposure_used /* may be NULL */);
+
 /* SampleGenerator table, sample_generator.rs:15-24: 65 536 x 3 floats */
 int mi355rt_get_sample_table(const mi355rt_handle* h, float* out);
 /* Per-node direct-light terms of one primary sample, computed on the device by the same
@@ -809,6 +859,7 @@ int mi355rt_comm_destroy(mi355rt_handle* h);
 uint32_t mi355rt_comm_ranks(mi355rt_handle* h);
 
 uint32_t mi355rt_width(const mi355rt_handle* h);
+uint32_t mi355rt_light_count(const mi355rt_handle* h);     /* lights of the handle's scene: nlights of the LIGHT FILMS entries */
 uint32_t mi355rt_height(const mi355rt_handle* h);
 uint32_t mi355rt_triangle_count(const mi355rt_handle* h);
 uint32_t mi355rt_current_row(const mi355rt_handle* h);

@@ -35,6 +35,8 @@ FLAG_GROUP_SHARES_DEVICE = 16
 FLAG_TRUE_CLOSEST_HIT = 32
 FLAG_DEVICE_LBVH = 64
 FLAG_DIRECT_FILM = 128
+FLAG_LIGHT_FILMS = 256        # create-time: a film per light (include/mi355rt.h, "LIGHT FILMS")
+LIGHT_FILMS_MAX_LIGHTS = 8
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI355RT_LIB") or os.path.join(_HERE, "libmi355rt.so")     # MI355RT_LIB: an A/B build of the library
@@ -233,6 +235,11 @@ ABI = [
     ("mi355rt_features_get", C.c_int, [_H, _U, _U, _F, _F, _F, C.c_size_t]),
     ("mi355rt_features_clear", C.c_int, [_H]),
     ("mi355rt_features_alpha", C.c_int, [_H, _F, C.c_size_t]),
+    ("mi355rt_light_count", C.c_uint32, [_H]),
+    ("mi355rt_light_films_get", C.c_int, [_H, _F, C.c_size_t, C.c_size_t]),
+    ("mi355rt_light_films_set", C.c_int, [_H, _F, C.c_size_t, C.c_size_t]),
+    ("mi355rt_light_films_add", C.c_int, [_H, _F, C.c_size_t, C.c_size_t]),
+    ("mi355rt_get_relit_pixels", C.c_int, [_H, _F, C.c_size_t, C.c_void_p, _F, _U, C.c_size_t, _F]),
     ("mi355rt_set_guide_source", C.c_int, [_H, C.c_uint32]),
     ("mi355rt_get_guide_source", C.c_uint32, [_H]),
     ("mi355rt_get_sample_table", C.c_int, [_H, _F]),
@@ -545,6 +552,39 @@ class Features:
         self._rt._check(lib().mi355rt_features_clear(self._rt._h))
 
 
+class LightFilms:
+    """The light films of a RayTracer created with FLAG_LIGHT_FILMS (include/mi355rt.h, "LIGHT FILMS"): per light, a plane of the film's
+    shape that holds the sum of every sample's light radiance — the sample's colour with every other light black.  Arrays are float32[nlights, npix, 3].
+    raytracer_rs_amd.relight states the relit read-out in numpy."""
+
+    def __init__(self, rt):
+        self._rt = rt
+
+    def _planes(self, a):
+        a = np.ascontiguousarray(a, np.float32)
+        nl, n = self._rt.nlights, self._rt.width * self._rt.height
+        if a.shape != (nl, n, 3):
+            raise ValueError("light films: shape must be (%d, %d, 3), not %s" % (nl, n, a.shape))
+        return a
+
+    def get(self):
+        """mi355rt_light_films_get: float32[nlights, npix, 3]"""
+        nl, n = self._rt.nlights, self._rt.width * self._rt.height
+        out = np.zeros((nl, n, 3), np.float32)
+        self._rt._check(lib().mi355rt_light_films_get(self._rt._h, _fp(out) if nl else None, nl, n))
+        return out
+
+    def set(self, a):
+        """mi355rt_light_films_set: the planes' bits as they are, on the rows the handle owns"""
+        a = self._planes(a)
+        self._rt._check(lib().mi355rt_light_films_set(self._rt._h, _fp(a) if a.size else None, a.shape[0], a.shape[1]))
+
+    def add(self, a):
+        """mi355rt_light_films_add: handle + a, one f32 addition per value, on the rows the handle owns"""
+        a = self._planes(a)
+        self._rt._check(lib().mi355rt_light_films_add(self._rt._h, _fp(a) if a.size else None, a.shape[0], a.shape[1]))
+
+
 class RayTracer:
     """raytracer/mod.rs:32-47.  Construct through create_raytracer* below."""
 
@@ -560,6 +600,8 @@ class RayTracer:
         self.camera = Camera(weakref.proxy(self))
         self.film = Film(weakref.proxy(self))
         self.features = Features(weakref.proxy(self))
+        self.nlights = int(L.mi355rt_light_count(self._h))
+        self.light_films = LightFilms(weakref.proxy(self))
 
     def close(self):
         if self._h:
@@ -688,6 +730,28 @@ class RayTracer:
         used = C.c_float(0.0)
         self._check(lib().mi355rt_get_display_pixels(self._h, C.byref(c), C.byref(d) if d is not None else None, _up(out), out.size, C.byref(used)))
         return out, np.float32(used.value)
+
+    def get_relit_pixels(self, weights, rgb=False, **display_cfg):
+        """mi355rt_get_relit_pixels (a handle created with FLAG_LIGHT_FILMS): the frame with light li's colour scaled by weights[li], mixed from the light
+        films without tracing.  weights: [nlights] scalars or [nlights, 3] RGB factors.  display_cfg: display config fields (source stays the film); none
+        given: the reference's tone map, as get_tonemapped_pixels.  Returns (packed uint32[npix], exposure_used as numpy float32), with rgb=True
+        (rgb float32[npix, 3], packed, exposure_used)."""
+        w = np.asarray(weights, np.float32)
+        if w.ndim == 1:
+            w = np.repeat(w[:, None], 3, axis=1)
+        w = np.ascontiguousarray(w, np.float32)
+        if w.ndim != 2 or w.shape[1] != 3:
+            raise ValueError("weights: shape must be (nlights,) or (nlights, 3), not %s" % (w.shape,))
+        c = display_config(**display_cfg) if display_cfg else None
+        n = self.width * self.height
+        out_rgb = np.zeros((n, 3), np.float32) if rgb else None
+        packed = np.zeros(n, np.uint32)
+        used = C.c_float(0.0)
+        self._check(lib().mi355rt_get_relit_pixels(self._h, _fp(w) if w.size else None, w.size, C.byref(c) if c is not None else None,
+                                                   _fp(out_rgb) if rgb else None, _up(packed), n, C.byref(used)))
+        if rgb:
+            return out_rgb, packed, np.float32(used.value)
+        return packed, np.float32(used.value)
 
     def guides(self):
         """the denoiser's guide buffers: dict(depth float32[npix], normal float32[npix, 3], albedo float32[npix, 3], prim uint32[npix])"""

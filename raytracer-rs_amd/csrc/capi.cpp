@@ -151,6 +151,20 @@ bool film_put_args_ok(mi355rt_handle* h, const char* fn, const float* sum, const
     return false;
 }
 
+// the checks of mi355rt_light_films_get / _set / _add (include/mi355rt.h, "LIGHT FILMS"); on failure the handle's last_error names the flag or the argument
+bool light_films_args_ok(mi355rt_handle* h, const char* fn, const float* light_rgb, size_t nlights, size_t npix)
+{
+    if (!h) return false;
+    const char* e = nullptr;
+    if (!h->r->has_light_films()) e = "the handle was not created with MI355RT_FLAG_LIGHT_FILMS";
+    else if (nlights != h->r->nlights()) e = "nlights must equal the scene's number of lights";
+    else if (npix != (size_t)h->r->cfg.width * h->r->cfg.height) e = "npix must equal width * height";
+    else if (nlights && !light_rgb) e = "light_rgb is NULL";
+    if (!e) return true;
+    h->r->last_error = std::string(fn) + ": " + e;
+    return false;
+}
+
 // the guard of the read-outs built on the camera's guides (include/mi355rt.h, "CALLER-SUPPLIED RAYS"): false while the film holds caller-ray samples
 bool camera_film_ok(mi355rt_handle* h, const char* fn)
 {
@@ -511,6 +525,43 @@ int mi355rt_set_guide_source(mi355rt_handle* h, uint32_t source)
 }
 
 uint32_t mi355rt_get_guide_source(const mi355rt_handle* h) { return h ? h->r->guide_source() : 0u; }
+
+int mi355rt_light_films_get(mi355rt_handle* h, float* light_rgb, size_t nlights, size_t npix)
+{
+    if (!light_films_args_ok(h, "mi355rt_light_films_get", light_rgb, nlights, npix)) return MI355RT_E_INVALID;
+    return h->r->light_films_get(light_rgb) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_light_films_set(mi355rt_handle* h, const float* light_rgb, size_t nlights, size_t npix)
+{
+    if (!light_films_args_ok(h, "mi355rt_light_films_set", light_rgb, nlights, npix)) return MI355RT_E_INVALID;
+    return h->r->light_films_put(light_rgb, false) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_light_films_add(mi355rt_handle* h, const float* light_rgb, size_t nlights, size_t npix)
+{
+    if (!light_films_args_ok(h, "mi355rt_light_films_add", light_rgb, nlights, npix)) return MI355RT_E_INVALID;
+    return h->r->light_films_put(light_rgb, true) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_get_relit_pixels(mi355rt_handle* h, const float* weights3, size_t nweights, const mi355rt_display_config* display,
+                             float* rgb, uint32_t* packed, size_t npix, float* exposure_used)
+{
+    if (!h) return MI355RT_E_INVALID;
+    const char* e = nullptr;
+    if (!h->r->has_light_films()) e = "the handle was not created with MI355RT_FLAG_LIGHT_FILMS";
+    else if (nweights != (size_t)h->r->nlights() * 3) e = "nweights must equal nlights * 3";
+    else if (nweights && !weights3) e = "weights3 is NULL";
+    else if (npix != (size_t)h->r->cfg.width * h->r->cfg.height) e = "npix must equal width * height";
+    else if (!rgb && !packed) e = "rgb and packed are both NULL";
+    else if (display && display->source != MI355RT_DISPLAY_SOURCE_FILM) e = "display->source must be MI355RT_DISPLAY_SOURCE_FILM: the relit image has no denoised source";
+    else if (display) e = display_config_error(display);
+    if (e) { h->r->last_error = std::string("mi355rt_get_relit_pixels: ") + e; return MI355RT_E_INVALID; }
+    float used = 1.0f;
+    if (!h->r->get_relit(weights3, display, rgb, packed, used)) return MI355RT_E_HIP;
+    if (exposure_used) *exposure_used = used;
+    return MI355RT_OK;
+}
 
 void mi355rt_display_default_config(mi355rt_display_config* cfg)
 {
@@ -1075,6 +1126,7 @@ int mi355rt_comm_destroy(mi355rt_handle* h)
 uint32_t mi355rt_comm_ranks(mi355rt_handle* h) { return h ? h->r->comm_ranks() : 0u; }
 
 uint32_t mi355rt_width(const mi355rt_handle* h) { return h ? h->r->cfg.width : 0u; }
+uint32_t mi355rt_light_count(const mi355rt_handle* h) { return h ? h->r->nlights() : 0u; }
 uint32_t mi355rt_height(const mi355rt_handle* h) { return h ? h->r->cfg.height : 0u; }
 uint32_t mi355rt_triangle_count(const mi355rt_handle* h) { return h ? h->r->ntri : 0u; }
 uint32_t mi355rt_current_row(const mi355rt_handle* h) { return h ? h->r->current_row : 0u; }

@@ -27,6 +27,8 @@
 // selects where --denoise / --denoise-split and the display options take their guides from (mi355rt_set_guide_source; features needs --features, and lifts the
 // exclusion of --denoise under --ortho-width).  --alpha (needs --features and a .png --out) writes an RGBA PNG: the RGB bytes are what they would be without the
 // option, A = (uint32_t)(alpha * 255.0f + 0.5f) of mi355rt_features_alpha; the colour is premultiplied by construction, because a miss is black.
+// Light films (MI355RT_FLAG_LIGHT_FILMS): --light-films keeps a film per light; --relight W0,W1,... writes the frame with light i scaled by Wi to --out
+// (mi355rt_get_relit_pixels, no tracing; the display options apply); --out-lights PREFIX writes PREFIX<i>.png, light i alone at weight 1.
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -140,6 +142,9 @@ int main(int argc, char** argv)
     long long region[4] = { 0, 0, 0, 0 };
     size_t features = 0;
     bool guides_features = false, alpha = false;
+    bool light_films = false, have_relight = false;
+    std::vector<float> relight;
+    std::string out_lights;
     auto parse_float = [](const char* s, float& out) { if (!s || !*s) return false; char* end = nullptr; const float f = std::strtof(s, &end); if (*end != '\0' || !std::isfinite(f)) return false; out = f; return true; };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -195,6 +200,20 @@ int main(int argc, char** argv)
             else { std::fprintf(stderr, "Error: --denoise-guides takes centre or features\n"); return 1; }
         }
         else if (a == "--alpha") alpha = true;
+        else if (a == "--light-films") light_films = true;
+        else if (a == "--out-lights") { if (v) out_lights = take(); }
+        else if (a == "--relight") {
+            const char* r = take();
+            std::string tok;
+            for (const char* c = r ? r : ""; ; ++c) {
+                if (*c != ',' && *c != '\0') { tok += *c; continue; }
+                float f;
+                if (!parse_float(tok.c_str(), f)) { std::fprintf(stderr, "Error: --relight takes W0,W1,...: one finite factor per light\n"); return 1; }
+                relight.push_back(f); tok.clear();
+                if (*c == '\0') break;
+            }
+            have_relight = true;
+        }
         else if (a == "--refine") { float f; if (parse_float(take(), f)) { acfg.rel_error = f; refine = true; } }
         else if (a == "--region") {
             const char* r = take();
@@ -227,7 +246,11 @@ int main(int argc, char** argv)
                         "                 [--denoise-guides centre|features]   (where --denoise, --denoise-split and the display options take their guides from; features\n"
                         "                                     needs --features and allows --denoise with --ortho-width)\n"
                         "                 [--alpha]   (needs --features and --out image.png: an RGBA PNG, A = coverage (hits / samples) * 255 rounded; the RGB bytes are\n"
-                        "                                     unchanged and PREMULTIPLIED by construction, because a sample that misses the scene is black)\n");
+                        "                                     unchanged and PREMULTIPLIED by construction, because a sample that misses the scene is black)\n"
+                        "                 [--light-films]   (the handle keeps a film per light, MI355RT_FLAG_LIGHT_FILMS: needs --spp, --adaptive or --refine; excludes --gpus)\n"
+                        "                 [--relight W0,W1,...]   (needs --light-films: --out receives the frame with light i's colour scaled by Wi, mixed from the light films\n"
+                        "                                     without tracing, mi355rt_get_relit_pixels; the display options apply; excludes --denoise, --denoise-split)\n"
+                        "                 [--out-lights PREFIX]   (needs --light-films: PREFIX<i>.png, light i alone at weight 1, under the same display options)\n");
             return 0;
         }
     }
@@ -235,6 +258,9 @@ int main(int argc, char** argv)
     if (features && gpus > 1) { std::fprintf(stderr, "Error: --features excludes --gpus\n"); return 1; }
     if (guides_features && !features) { std::fprintf(stderr, "Error: --denoise-guides features needs --features\n"); return 1; }
     if (alpha && (!features || !(out.size() > 4 && out.compare(out.size() - 4, 4, ".png") == 0))) { std::fprintf(stderr, "Error: --alpha needs --features and --out image.png\n"); return 1; }
+    if ((have_relight || !out_lights.empty()) && !light_films) { std::fprintf(stderr, "Error: --relight and --out-lights need --light-films\n"); return 1; }
+    if (light_films && (gpus > 1 || !(spp || adaptive || refine))) { std::fprintf(stderr, "Error: --light-films needs --spp, --adaptive or --refine and excludes --gpus\n"); return 1; }
+    if (have_relight && (denoise || denoise_split)) { std::fprintf(stderr, "Error: --relight excludes --denoise and --denoise-split\n"); return 1; }
     // the option given together with --region / --refine that it excludes (null: none)
     auto excluded_by_tiles = [&](bool with_spp) -> const char* {
         if (with_spp && spp) return "--spp";
@@ -264,6 +290,7 @@ int main(int argc, char** argv)
         if (fix_row) cfg.flags |= MI355RT_FLAG_FIX_ROW_INDEX;
         if (device_lbvh) cfg.flags |= MI355RT_FLAG_DEVICE_LBVH;             // BVH built on the GPU (Morton order) instead of the host's SAH build
         if (denoise_split) cfg.flags |= MI355RT_FLAG_DIRECT_FILM;
+        if (light_films) cfg.flags |= MI355RT_FLAG_LIGHT_FILMS;
         cfg.device_count = (uint32_t)gpus;
         if (share_device) cfg.flags |= MI355RT_FLAG_GROUP_SHARES_DEVICE;      // testing: the whole group on one GPU
         if (gpus > 1) std::printf("rendering on %zu GPUs (rows dealt in stripes of %u)\n", gpus, cfg.stripe_rows);
@@ -323,7 +350,25 @@ int main(int argc, char** argv)
             if (alpha) for (float a : rt.features.alpha()) alpha8.push_back((unsigned char)(uint32_t)(a * 255.0f + 0.5f));
         }
         if (frame_iterations == 0 && !load_films.empty()) ldr = rt.get_tonemapped_pixels();       // a merge-only run: the loaded film, read out once
-        if (display) {                                                    // the display read-out of the film the loop left, of the source the denoise options select
+        if (light_films) {
+            const size_t nl = rt.light_films.nlights();
+            std::printf("light films: %zu lights\n", nl);
+            if (have_relight && relight.size() != nl) throw std::runtime_error("--relight: " + std::to_string(relight.size()) + " factors given, the scene has " + std::to_string(nl) + " lights");
+            dcfg_display.source = MI355RT_DISPLAY_SOURCE_FILM;
+            for (size_t li = 0; !out_lights.empty() && li < nl; ++li) {    // each light alone at weight 1
+                std::vector<float> w3(nl * 3, 0.0f);
+                w3[li * 3] = w3[li * 3 + 1] = w3[li * 3 + 2] = 1.0f;
+                const std::string path = out_lights + std::to_string(li) + ".png";
+                if (!write_png(path, rt.get_relit_pixels(w3, display ? &dcfg_display : nullptr), width, height, nullptr)) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+            }
+        }
+        if (have_relight) {                                               // the relit frame instead of the film's read-out
+            std::vector<float> w3;
+            for (float f : relight) { w3.push_back(f); w3.push_back(f); w3.push_back(f); }
+            float used = 1.0f;
+            ldr = rt.get_relit_pixels(w3, display ? &dcfg_display : nullptr, nullptr, &used);
+            if (display) std::printf("display: exposure %.9g%s\n", (double)used, dcfg_display.auto_exposure ? " (auto)" : "");
+        } else if (display) {                                             // the display read-out of the film the loop left, of the source the denoise options select
             dcfg_display.source = denoise_split ? MI355RT_DISPLAY_SOURCE_DENOISED_SPLIT : denoise ? MI355RT_DISPLAY_SOURCE_DENOISED : MI355RT_DISPLAY_SOURCE_FILM;
             float used = 0.0f;
             ldr = rt.get_display_pixels(dcfg_display, nullptr, &used);

@@ -14,6 +14,7 @@ std::unique_ptr<DeviceGroup> DeviceGroup::create(const SceneData& scene, const m
     code = MI355RT_E_INVALID;
     if (n > 64) { err = "device_count > 64"; return nullptr; }
     if (n > 1 && cfg.stripe_world > 1) { err = "a device group deals the rows itself: stripe_world must be <= 1 when device_count > 1"; return nullptr; }
+    if (n > 1 && (cfg.flags & MI355RT_FLAG_LIGHT_FILMS)) { err = "MI355RT_FLAG_LIGHT_FILMS: not available on a device group (config.device_count > 1)"; return nullptr; }
     for (uint32_t i = 0; i < n; ++i) {
         mi355rt_config c = cfg;
         c.device_count = 1;

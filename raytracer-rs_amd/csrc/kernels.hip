@@ -1195,14 +1195,16 @@ __global__ __launch_bounds__(kBlock, PRIMARY ? (WALK ? kShadePWBlocks : kShadePB
 // The radiance of tree node (level, index) of U samples (U == 1: one sample), in the reference's order of operations for each.  sl[u]: the sample's
 // light-term slot, 0xFFFFFFFF without one (its primary ray hit nothing: black, mod.rs:100 — nothing is loaded and the fold of +0.0 terms gives +0.0).
 // The walk over the tree is the same for all samples, so the loads of one node's terms — U independent ones — are issued together and waited for once.
-template <int REC, uint32_t U>
-__device__ __forceinline__ void node_radiance(const float* __restrict__ slot_L, const uint32_t (&sl)[U], const DPass& ps, uint32_t nlights, uint32_t level, uint32_t index, f3 (&out)[U])
+// ONE (the light films, MI355RT_FLAG_LIGHT_FILMS): every node's light sum is (+0.0) + the term of light `only` alone.
+template <int REC, uint32_t U, bool ONE = false>
+__device__ __forceinline__ void node_radiance(const float* __restrict__ slot_L, const uint32_t (&sl)[U], const DPass& ps, uint32_t nlights, uint32_t level, uint32_t index, f3 (&out)[U],
+                                              uint32_t only = 0u)
 {
     const uint32_t node = ps.level_first[level] + index;
     f3 rad[U];
 #pragma unroll
     for (uint32_t u = 0; u < U; ++u) rad[u] = mk3(0.0f, 0.0f, 0.0f);   // accum_color, mod.rs:211
-    for (uint32_t li = 0; li < nlights; ++li) {
+    for (uint32_t li = ONE ? only : 0u; li < (ONE ? only + 1u : nlights); ++li) {
         f3 t[U];
 #pragma unroll
         for (uint32_t u = 0; u < U; ++u) {
@@ -1225,7 +1227,7 @@ __device__ __forceinline__ void node_radiance(const float* __restrict__ slot_L, 
         for (uint32_t u = 0; u < U; ++u) sum[u] = mk3(0.0f, 0.0f, 0.0f);
         for (uint32_t c = 0; c < k; ++c) {
             f3 child[U];
-            node_radiance<REC - 1, U>(slot_L, sl, ps, nlights, level + 1, index * k + c, child);
+            node_radiance<REC - 1, U, ONE>(slot_L, sl, ps, nlights, level + 1, index * k + c, child, only);
 #pragma unroll
             for (uint32_t u = 0; u < U; ++u) sum[u] = add3(sum[u], child[u]);   // fold, mod.rs:173
         }
@@ -1235,52 +1237,43 @@ __device__ __forceinline__ void node_radiance(const float* __restrict__ slot_L, 
     }
 }
 // the whole tree of each of the U samples
-template <uint32_t U>
-__device__ __forceinline__ void tree_radiance(const float* __restrict__ slot_L, const uint32_t (&sl)[U], const DPass& ps, uint32_t nlights, f3 (&c)[U])
+template <uint32_t U, bool ONE = false>
+__device__ __forceinline__ void tree_radiance(const float* __restrict__ slot_L, const uint32_t (&sl)[U], const DPass& ps, uint32_t nlights, f3 (&c)[U], uint32_t only = 0u)
 {
     switch (ps.recursions) {
-        case 0: node_radiance<0, U>(slot_L, sl, ps, nlights, 0, 0, c); break;
-        case 1: node_radiance<1, U>(slot_L, sl, ps, nlights, 0, 0, c); break;
-        case 2: node_radiance<2, U>(slot_L, sl, ps, nlights, 0, 0, c); break;
-        default: node_radiance<3, U>(slot_L, sl, ps, nlights, 0, 0, c); break;
+        case 0: node_radiance<0, U, ONE>(slot_L, sl, ps, nlights, 0, 0, c, only); break;
+        case 1: node_radiance<1, U, ONE>(slot_L, sl, ps, nlights, 0, 0, c, only); break;
+        case 2: node_radiance<2, U, ONE>(slot_L, sl, ps, nlights, 0, 0, c, only); break;
+        default: node_radiance<3, U, ONE>(slot_L, sl, ps, nlights, 0, 0, c, only); break;
     }
 }
 // The same for a tree of at most kFlatNodes nodes: recursions 0, recursions 1 with a spread up to 4, and the reference's own 2 / 1.  node_radiance walks the
 // tree and waits for a node's terms before it loads the next node's: for the reference's tree a chain of five round trips.  Here the light sums of ALL nodes
 // are gathered first — per light, the terms of every node of the U samples in flight together — and the tree is folded afterwards, operation for operation as
-// node_radiance folds it.  root[u]: the root node's light sum L0.
+// node_radiance folds it (flat_radiance, below its two parts: the loads of one light's terms, and the fold).  root[u]: the root node's light sum L0.
 constexpr uint32_t kFlatNodes = 5;
+// the terms of light li of every node of the U samples: U * nodes independent loads, issued together
 template <uint32_t U>
-__device__ __forceinline__ void flat_radiance(const float* __restrict__ slot_L, const uint32_t (&sl)[U], const DPass& ps, uint32_t nlights, f3 (&c)[U], f3 (&root)[U])
+__device__ __forceinline__ void flat_terms(const float* __restrict__ slot_L, const uint32_t (&sl)[U], const DPass& ps, uint32_t nlights, uint32_t li, f3 (&t)[kFlatNodes][U])
 {
-    f3 rad[kFlatNodes][U];
 #pragma unroll
     for (uint32_t q = 0; q < kFlatNodes; ++q) {
 #pragma unroll
-        for (uint32_t u = 0; u < U; ++u) rad[q][u] = mk3(0.0f, 0.0f, 0.0f);   // accum_color, mod.rs:211
-    }
-    for (uint32_t li = 0; li < nlights; ++li) {
-        f3 t[kFlatNodes][U];
-#pragma unroll
-        for (uint32_t q = 0; q < kFlatNodes; ++q) {
-#pragma unroll
-            for (uint32_t u = 0; u < U; ++u) {
-                t[q][u] = mk3(0.0f, 0.0f, 0.0f);
-                if (sl[u] != 0xFFFFFFFFu && q < ps.nodes_per_sample) {
-                    const float* p = slot_L + 3ull * ((size_t)(q * nlights + li) * ps.nslots + sl[u]);
-                    t[q][u] = mk3(p[0], p[1], p[2]);
-                }
+        for (uint32_t u = 0; u < U; ++u) {
+            t[q][u] = mk3(0.0f, 0.0f, 0.0f);
+            if (sl[u] != 0xFFFFFFFFu && q < ps.nodes_per_sample) {
+                const float* p = slot_L + 3ull * ((size_t)(q * nlights + li) * ps.nslots + sl[u]);
+                t[q][u] = mk3(p[0], p[1], p[2]);
             }
         }
-#pragma unroll
-        for (uint32_t q = 0; q < kFlatNodes; ++q) {
-#pragma unroll
-            for (uint32_t u = 0; u < U; ++u) rad[q][u] = add3(rad[q][u], t[q][u]);   // mod.rs:254
-        }
     }
+}
+// the fold of the nodes' light sums rad into the colour of each of the U samples
+template <uint32_t U>
+__device__ __forceinline__ void flat_fold(const f3 (&rad)[kFlatNodes][U], const DPass& ps, f3 (&c)[U])
+{
 #pragma unroll
     for (uint32_t u = 0; u < U; ++u) {
-        root[u] = rad[0][u];
         if (ps.recursions == 0u) c[u] = rad[0][u];                      // mod.rs:146-148
         else if (ps.recursions == 1u) {
             const uint32_t k = ps.spread;                               // mod.rs:150; <= kFlatNodes - 1 children
@@ -1300,6 +1293,67 @@ __device__ __forceinline__ void flat_radiance(const float* __restrict__ slot_L, 
         }
     }
 }
+template <uint32_t U>
+__device__ __forceinline__ void flat_radiance(const float* __restrict__ slot_L, const uint32_t (&sl)[U], const DPass& ps, uint32_t nlights, f3 (&c)[U], f3 (&root)[U])
+{
+    f3 rad[kFlatNodes][U];
+#pragma unroll
+    for (uint32_t q = 0; q < kFlatNodes; ++q) {
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) rad[q][u] = mk3(0.0f, 0.0f, 0.0f);   // accum_color, mod.rs:211
+    }
+    for (uint32_t li = 0; li < nlights; ++li) {
+        f3 t[kFlatNodes][U];
+        flat_terms<U>(slot_L, sl, ps, nlights, li, t);
+#pragma unroll
+        for (uint32_t q = 0; q < kFlatNodes; ++q) {
+#pragma unroll
+            for (uint32_t u = 0; u < U; ++u) rad[q][u] = add3(rad[q][u], t[q][u]);   // mod.rs:254
+        }
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) root[u] = rad[0][u];
+    flat_fold<U>(rad, ps, c);
+}
+// flat_radiance for a handle with light films (MI355RT_FLAG_LIGHT_FILMS): every term is still loaded ONCE.  Light li's terms go into the nodes'
+// light sums as above and, alone, through the same fold: r = the sample's light radiance R_li, each node's light sum being (+0.0) + its term.  The group
+// exchanges r at once and adds it, in sample order, to the pixel's running sum of light li, which lives in LDS: lacc[(li * 3 + channel) * 256] is this lane's
+// (consecutive lanes on consecutive words).  s0, spp, group_lane0: the turn, as in resolve_kernel.
+template <uint32_t kResolveLanes, uint32_t U>
+__device__ __forceinline__ void flat_radiance_lights(const float* __restrict__ slot_L, const uint32_t (&sl)[U], const DPass& ps, uint32_t nlights, f3 (&c)[U], f3 (&root)[U],
+                                                     float* lacc, int group_lane0, uint32_t s0, uint32_t spp)
+{
+    f3 rad[kFlatNodes][U];
+#pragma unroll
+    for (uint32_t q = 0; q < kFlatNodes; ++q) {
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) rad[q][u] = mk3(0.0f, 0.0f, 0.0f);
+    }
+    for (uint32_t li = 0; li < nlights; ++li) {
+        f3 t[kFlatNodes][U], r[U];
+        flat_terms<U>(slot_L, sl, ps, nlights, li, t);
+#pragma unroll
+        for (uint32_t q = 0; q < kFlatNodes; ++q) {
+#pragma unroll
+            for (uint32_t u = 0; u < U; ++u) { rad[q][u] = add3(rad[q][u], t[q][u]); t[q][u] = add3(mk3(0.0f, 0.0f, 0.0f), t[q][u]); }
+        }
+        flat_fold<U>(t, ps, r);
+        float* a = lacc + (size_t)li * 3u * 256u;
+        f3 acc = mk3(a[0], a[256], a[512]);
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) {
+#pragma unroll
+            for (uint32_t k = 0; k < kResolveLanes; ++k) {
+                const f3 rk = mk3(__shfl(r[u].x, group_lane0 + (int)k, 64), __shfl(r[u].y, group_lane0 + (int)k, 64), __shfl(r[u].z, group_lane0 + (int)k, 64));
+                if (s0 + u * kResolveLanes + k < spp) acc = add3(acc, rk);
+            }
+        }
+        a[0] = acc.x; a[256] = acc.y; a[512] = acc.z;
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < U; ++u) root[u] = rad[0][u];
+    flat_fold<U>(rad, ps, c);
+}
 
 // kResolveLanes consecutive lanes work on one pixel: lane j evaluates the radiance trees of samples j,
 // j + kResolveLanes, ... (the loads), then the values of one round are exchanged inside the wave and every
@@ -1317,11 +1371,17 @@ __device__ __forceinline__ void flat_radiance(const float* __restrict__ slot_L, 
 // DIRECT (MI355RT_FLAG_DIRECT_FILM): the pixel's direct film (film_direct, beside film_sum) takes the root node's light sum L0
 // of every sample — the first term of the sample's colour — through the same exchange, so it is added in sample order too.
 // A pixel without anything to load — in a culled block, or inactive — skips the loop: its lanes exchange with each other only.
+// LIGHTS (MI355RT_FLAG_LIGHT_FILMS): behind the film, the pixel's light films (film_lights + li * lights_stride floats, laid out like film_sum)
+// take the light radiance R_li of every sample — the tree folded with light li's terms alone — through the same exchange, in sample order.  FLAT: in the
+// same turn, from the terms the film loads anyway (flat_radiance_lights); a lane's running sums of the nlights <= kMaxLightFilms planes live in LDS (24 KiB a
+// block, no dynamically indexed registers, no scratch).  Otherwise one light at a time behind the film: the group walks its samples again per light with one
+// running sum in registers and reads the slot indices (cached) and every light term a second time.  DESIGN.md §3l has both measured.
 constexpr uint32_t kResolveU = 2;
-template <uint32_t kResolveLanes, uint32_t U, bool DIRECT, bool FLAT>
+template <uint32_t kResolveLanes, uint32_t U, bool DIRECT, bool FLAT, bool LIGHTS>
 __global__ __launch_bounds__(256) void resolve_kernel(DPass ps, uint32_t width, uint32_t nlights, const float* __restrict__ slot_L,
                                                      const uint32_t* __restrict__ sample_slot,
-                                                     float* film_sum, float* film_sumsq, uint32_t* film_n, float* debug_color, uint32_t* ctrl, float* film_direct)
+                                                     float* film_sum, float* film_sumsq, uint32_t* film_n, float* debug_color, uint32_t* ctrl, float* film_direct,
+                                                     float* film_lights, uint32_t lights_stride)
 {
     // last kernel of a pass: leave the pass's work cursors zeroed for the next one (960 words; a 20 MiB memset otherwise)
     if (ctrl != nullptr && blockIdx.x == 0)
@@ -1342,6 +1402,14 @@ __global__ __launch_bounds__(256) void resolve_kernel(DPass ps, uint32_t width, 
         if constexpr (DIRECT) direct = mk3(film_direct[3ull * pixel], film_direct[3ull * pixel + 1], film_direct[3ull * pixel + 2]);
     }
     const int group_lane0 = lane_id() & ~(int)(kResolveLanes - 1u);
+    float* lacc = nullptr;
+    if constexpr (LIGHTS && FLAT) {
+        // never launched for a debug_sample pass, nor with more than kMaxLightFilms lights (launch_resolve)
+        __shared__ float light_acc[kMaxLightFilms * 3u * 256u];
+        lacc = light_acc + threadIdx.x;
+        for (uint32_t li = 0; li < nlights; ++li)
+            for (uint32_t k = 0; k < 3u; ++k) lacc[(li * 3u + k) * 256u] = film_lights[(size_t)li * lights_stride + 3ull * pixel + k];
+    }
     // every sample of a pixel in a culled block is a miss: no slot to look up (the primary shade launch wrote none)
     const bool dead = ps.block_culled != nullptr && ps.block_culled[(uint32_t)(sample_index(ps, 0u, p) / ps.chunk) % ps.cull_blocks] != 0u;
     // adaptive sampling: an inactive pixel's slots may be stale (a skipped chunk with a cached verdict writes none) and its film is not written at all
@@ -1364,7 +1432,8 @@ __global__ __launch_bounds__(256) void resolve_kernel(DPass ps, uint32_t width, 
             sl[u] = (s < spp && !dead) ? sample_slot[sample_index(ps, s, p)] : 0xFFFFFFFFu;
         }
         f3 c[U], d[U];
-        if constexpr (FLAT) flat_radiance<U>(slot_L, sl, ps, nlights, c, d);
+        if constexpr (FLAT && LIGHTS) flat_radiance_lights<kResolveLanes, U>(slot_L, sl, ps, nlights, c, d, lacc, group_lane0, s0, spp);
+        else if constexpr (FLAT) flat_radiance<U>(slot_L, sl, ps, nlights, c, d);
         else {
             tree_radiance<U>(slot_L, sl, ps, nlights, c);
             if constexpr (DIRECT) node_radiance<0, U>(slot_L, sl, ps, nlights, 0, 0, d);   // no slot: no root light term either
@@ -1392,6 +1461,41 @@ __global__ __launch_bounds__(256) void resolve_kernel(DPass ps, uint32_t width, 
         film_sumsq[3ull * pixel] = sumsq.x; film_sumsq[3ull * pixel + 1] = sumsq.y; film_sumsq[3ull * pixel + 2] = sumsq.z;
         film_n[pixel] = n;
         if constexpr (DIRECT) { film_direct[3ull * pixel] = direct.x; film_direct[3ull * pixel + 1] = direct.y; film_direct[3ull * pixel + 2] = direct.z; }
+    }
+    if constexpr (LIGHTS && FLAT) {
+        for (uint32_t li = 0; li < nlights; ++li) {
+            float* plane = film_lights + (size_t)li * lights_stride + 3ull * pixel;
+            f3 acc = mk3(lacc[(li * 3u) * 256u], lacc[(li * 3u + 1u) * 256u], lacc[(li * 3u + 2u) * 256u]);
+            if ((dead || !on) && spp != 0u) acc = add3(acc, mk3(0.0f, 0.0f, 0.0f));      // as the film above; an inactive pixel is not written
+            if (live && on && j == 0u) { plane[0] = acc.x; plane[1] = acc.y; plane[2] = acc.z; }
+        }
+    } else if constexpr (LIGHTS) {
+        // never launched for a debug_sample pass (launch_resolve)
+        for (uint32_t li = 0; li < nlights; ++li) {
+            float* plane = film_lights + (size_t)li * lights_stride + 3ull * pixel;
+            f3 acc = mk3(plane[0], plane[1], plane[2]);
+            if (dead || !on) {
+                if (spp != 0u) acc = add3(acc, mk3(0.0f, 0.0f, 0.0f));      // as the film above; an inactive pixel is not written
+            } else for (uint32_t s0 = 0; s0 < spp; s0 += kResolveLanes * U) {
+                uint32_t sl[U];
+#pragma unroll
+                for (uint32_t u = 0; u < U; ++u) {
+                    const uint32_t s = s0 + u * kResolveLanes + j;
+                    sl[u] = s < spp ? sample_slot[sample_index(ps, s, p)] : 0xFFFFFFFFu;
+                }
+                f3 c[U];
+                tree_radiance<U, true>(slot_L, sl, ps, nlights, c, li);
+#pragma unroll
+                for (uint32_t u = 0; u < U; ++u) {
+#pragma unroll
+                    for (uint32_t k = 0; k < kResolveLanes; ++k) {
+                        const f3 ck = mk3(__shfl(c[u].x, group_lane0 + (int)k, 64), __shfl(c[u].y, group_lane0 + (int)k, 64), __shfl(c[u].z, group_lane0 + (int)k, 64));
+                        if (s0 + u * kResolveLanes + k < spp) acc = add3(acc, ck);
+                    }
+                }
+            }
+            if (live && on && j == 0u) { plane[0] = acc.x; plane[1] = acc.y; plane[2] = acc.z; }
+        }
     }
 }
 
@@ -2243,22 +2347,31 @@ hipError_t launch_shade(hipStream_t stream, int num_cus, bool primary, bool walk
 }
 
 hipError_t launch_resolve(hipStream_t stream, const DPass& ps, uint32_t width, uint32_t nlights, const float* slot_L, const uint32_t* sample_slot,
-                          float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct, float* debug_color, uint32_t* ctrl)
+                          float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct, float* debug_color, uint32_t* ctrl,
+                          float* film_lights, uint32_t lights_stride)
 {
     const uint32_t spp = ps.npix ? ps.nsamples / ps.npix : 1u;
     const uint32_t lanes = spp <= 32u ? 2u : (spp <= 96u ? 4u : 8u);       // lanes per pixel: resolve_kernel's header
     dim3 block(256), grid((unsigned)(((size_t)ps.npix * lanes + 255) / 256));
-#define MI355RT_RESOLVE_ARGS grid, block, 0, stream, ps, width, nlights, slot_L, sample_slot, film_sum, film_sumsq, film_n, debug_color, ctrl, film_direct
-#define MI355RT_RESOLVE_LANES(DIRECT, FLAT) switch (lanes) { \
-        case 2: hipLaunchKernelGGL((resolve_kernel<2, kResolveU, DIRECT, FLAT>), MI355RT_RESOLVE_ARGS); break; \
-        case 4: hipLaunchKernelGGL((resolve_kernel<4, kResolveU, DIRECT, FLAT>), MI355RT_RESOLVE_ARGS); break; \
-        default: hipLaunchKernelGGL((resolve_kernel<8, kResolveU, DIRECT, FLAT>), MI355RT_RESOLVE_ARGS); break; }
+#define MI355RT_RESOLVE_ARGS grid, block, 0, stream, ps, width, nlights, slot_L, sample_slot, film_sum, film_sumsq, film_n, debug_color, ctrl, film_direct, film_lights, lights_stride
+#define MI355RT_RESOLVE_LANES(DIRECT, FLAT, LIGHTS) switch (lanes) { \
+        case 2: hipLaunchKernelGGL((resolve_kernel<2, kResolveU, DIRECT, FLAT, LIGHTS>), MI355RT_RESOLVE_ARGS); break; \
+        case 4: hipLaunchKernelGGL((resolve_kernel<4, kResolveU, DIRECT, FLAT, LIGHTS>), MI355RT_RESOLVE_ARGS); break; \
+        default: hipLaunchKernelGGL((resolve_kernel<8, kResolveU, DIRECT, FLAT, LIGHTS>), MI355RT_RESOLVE_ARGS); break; }
     const bool direct = film_direct != nullptr && !ps.use_explicit;           // a debug_sample pass adds to no film: the plain variant
     const bool flat = ps.nodes_per_sample <= kFlatNodes;                      // flat_radiance
-    if (direct && flat) MI355RT_RESOLVE_LANES(true, true)
-    else if (direct) MI355RT_RESOLVE_LANES(true, false)
-    else if (flat) MI355RT_RESOLVE_LANES(false, true)
-    else MI355RT_RESOLVE_LANES(false, false)
+    const bool lights = film_lights != nullptr && nlights != 0u && !ps.use_explicit;     // the light films (MI355RT_FLAG_LIGHT_FILMS): variants of their own
+    if (lights && nlights > kMaxLightFilms) return hipErrorInvalidValue;                 // Renderer::init refuses such a scene with the flag
+    if (lights) {
+        if (direct && flat) MI355RT_RESOLVE_LANES(true, true, true)
+        else if (direct) MI355RT_RESOLVE_LANES(true, false, true)
+        else if (flat) MI355RT_RESOLVE_LANES(false, true, true)
+        else MI355RT_RESOLVE_LANES(false, false, true)
+    }
+    else if (direct && flat) MI355RT_RESOLVE_LANES(true, true, false)
+    else if (direct) MI355RT_RESOLVE_LANES(true, false, false)
+    else if (flat) MI355RT_RESOLVE_LANES(false, true, false)
+    else MI355RT_RESOLVE_LANES(false, false, false)
 #undef MI355RT_RESOLVE_LANES
 #undef MI355RT_RESOLVE_ARGS
     return hipGetLastError();
@@ -2395,6 +2508,75 @@ hipError_t launch_film_merge(hipStream_t stream, bool add, const float* in_sum, 
     if (add) { if (film_direct) hipLaunchKernelGGL((film_merge_kernel<true, true>), MI355RT_MERGE_ARGS); else hipLaunchKernelGGL((film_merge_kernel<true, false>), MI355RT_MERGE_ARGS); }
     else { if (film_direct) hipLaunchKernelGGL((film_merge_kernel<false, true>), MI355RT_MERGE_ARGS); else hipLaunchKernelGGL((film_merge_kernel<false, false>), MI355RT_MERGE_ARGS); }
 #undef MI355RT_MERGE_ARGS
+    return hipGetLastError();
+}
+
+// ---- light films (MI355RT_FLAG_LIGHT_FILMS): the planes' own clear, set / add and the relit read-out ----
+// Clear of the owned rows of every plane: one thread per f32 of a plane's owned rows and light (grid.y), consecutive lanes on consecutive dwords of a row.
+__global__ __launch_bounds__(256) void light_films_clear_rows_kernel(const uint32_t* __restrict__ rows, uint32_t nrows, uint32_t width, float* film_lights, uint32_t lights_stride)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t row_f = 3ull * width;
+    if (i >= (size_t)nrows * row_f) return;
+    film_lights[(size_t)blockIdx.y * lights_stride + (size_t)rows[i / row_f] * row_f + i % row_f] = 0.0f;
+}
+hipError_t launch_light_films_clear_rows(hipStream_t stream, const uint32_t* rows, uint32_t nrows, uint32_t width, uint32_t nlights, float* film_lights, uint32_t lights_stride)
+{
+    const size_t n = (size_t)nrows * width * 3;
+    if (n == 0 || nlights == 0) return hipSuccess;
+    if ((n + 255) / 256 > 0x7FFFFFFFull || nlights > 65535u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(light_films_clear_rows_kernel, dim3((unsigned)((n + 255) / 256), nlights), dim3(256), 0, stream, rows, nrows, width, film_lights, lights_stride);
+    return hipGetLastError();
+}
+
+// mi355rt_light_films_set / _add: staged planes -> the handle's, on the rows it owns; film_merge_kernel's row logic and arithmetic for nlights planes
+// (grid.y: the light).  ADD: one f32 addition with the handle's value on the left; otherwise the input's bits as they are.
+template <bool ADD>
+__global__ __launch_bounds__(256) void light_films_merge_kernel(const float* __restrict__ in, uint32_t npix, uint32_t width, uint32_t stripe_rows, uint32_t stripe_world, uint32_t stripe_rank,
+                                                                float* film_lights, uint32_t lights_stride)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;               // 3 * npix < 2^32: Renderer::init caps npix at 2^29
+    if (i >= 3u * npix || ((i / 3u / width) / stripe_rows) % stripe_world != stripe_rank) return;
+    const size_t o = (size_t)blockIdx.y * lights_stride + i;
+    if constexpr (ADD) film_lights[o] = film_lights[o] + in[o];
+    else reinterpret_cast<uint32_t*>(film_lights)[o] = reinterpret_cast<const uint32_t*>(in)[o];
+}
+// in: nlights planes of lights_stride == 3 * npix floats, like film_lights
+hipError_t launch_light_films_merge(hipStream_t stream, bool add, const float* in, uint32_t nlights, uint32_t npix, uint32_t width,
+                                    uint32_t stripe_rows, uint32_t stripe_world, uint32_t stripe_rank, float* film_lights, uint32_t lights_stride)
+{
+    if (npix == 0 || nlights == 0) return hipSuccess;
+    if (width == 0 || stripe_rows == 0 || (uint64_t)npix * 3 > 0xFFFFFF00ull || lights_stride != 3u * npix || nlights > 65535u) return hipErrorInvalidValue;
+    if (stripe_world <= 1) { stripe_world = 1; stripe_rank = 0; }
+    const dim3 grid((3u * npix + 255u) / 256u, nlights);
+    if (add) hipLaunchKernelGGL(light_films_merge_kernel<true>, grid, dim3(256), 0, stream, in, npix, width, stripe_rows, stripe_world, stripe_rank, film_lights, lights_stride);
+    else hipLaunchKernelGGL(light_films_merge_kernel<false>, grid, dim3(256), 0, stream, in, npix, width, stripe_rows, stripe_world, stripe_rank, film_lights, lights_stride);
+    return hipGetLastError();
+}
+
+// mi355rt_get_relit_pixels: one lane per pixel, c[ch] = sum over the lights, ascending, of weight[li][ch] * (light[li][p][ch] * (1 / n)), f32 and unfused as
+// include/mi355rt.h writes it.  Consecutive lanes read consecutive pixels of each plane (12-byte entries: three dword loads per lane, a wave covers 768
+// contiguous bytes) and write consecutive entries of rgb, which feeds display_hist_kernel / display_pack_kernel as a non-film image.  weights: nlights * 3 floats.
+__global__ __launch_bounds__(256) void relit_kernel(uint32_t npix, uint32_t nlights, const float* __restrict__ film_lights, uint32_t lights_stride,
+                                                    const uint32_t* __restrict__ film_n, const float* __restrict__ weights, float* __restrict__ rgb)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    const float inv = div_rn(1.0f, (float)film_n[p]);
+    float c[3] = { 0.0f, 0.0f, 0.0f };
+    for (uint32_t li = 0; li < nlights; ++li) {
+        const float* plane = film_lights + (size_t)li * lights_stride + 3ull * p;
+        for (int k = 0; k < 3; ++k) {
+            const float m = plane[k] * inv;
+            c[k] = c[k] + __fmul_rn(weights[3u * li + k], m);
+        }
+    }
+    rgb[3ull * p] = c[0]; rgb[3ull * p + 1] = c[1]; rgb[3ull * p + 2] = c[2];
+}
+hipError_t launch_relit(hipStream_t stream, uint32_t npix, uint32_t nlights, const float* film_lights, uint32_t lights_stride, const uint32_t* film_n, const float* weights, float* rgb)
+{
+    if (npix == 0) return hipSuccess;
+    hipLaunchKernelGGL(relit_kernel, dim3((npix + 255) / 256), dim3(256), 0, stream, npix, nlights, film_lights, lights_stride, film_n, weights, rgb);
     return hipGetLastError();
 }
 

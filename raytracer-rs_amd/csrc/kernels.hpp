@@ -18,7 +18,8 @@ hipError_t launch_shade(hipStream_t stream, int num_cus, bool primary, bool walk
                         float* slot_L, uint32_t* sample_slot, const uint32_t* film_n, DCounters* counters, bool raster = false,   // raster: primary round, hits through the tile bins inside the launch
                         uint32_t rays = 0);                                                                                        // rays: as launch_trace
 hipError_t launch_resolve(hipStream_t stream, const DPass& ps, uint32_t width, uint32_t nlights, const float* slot_L, const uint32_t* sample_slot,
-                          float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct, float* debug_color, uint32_t* ctrl);   // ctrl != null: zero the pass's work cursors on the way out
+                          float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct, float* debug_color, uint32_t* ctrl,    // ctrl != null: zero the pass's work cursors on the way out
+                          float* film_lights = nullptr, uint32_t lights_stride = 0);   // film_lights: the light films (below), null without MI355RT_FLAG_LIGHT_FILMS: the kernels without them
 // mi355rt_trace_rays: per-ray results of a ray-fed pass whose sample i is ray i; rgb / direct / tuv / prim: the pass's part of the outputs, any may be null
 hipError_t launch_resolve_rays(hipStream_t stream, const DPass& ps, uint32_t nlights, const float* slot_L, const uint32_t* sample_slot,
                                float* rgb, float* direct, float* tuv, uint32_t* prim, uint32_t* ctrl);
@@ -51,6 +52,14 @@ hipError_t launch_film_rows_copy(hipStream_t stream, const uint32_t* rows, uint3
 hipError_t launch_film_merge(hipStream_t stream, bool add, const float* in_sum, const float* in_sumsq, const uint32_t* in_n, const float* in_direct,
                              uint32_t npix, uint32_t width, uint32_t stripe_rows, uint32_t stripe_world, uint32_t stripe_rank,
                              float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct);
+constexpr uint32_t kMaxLightFilms = 8;      // MI355RT_LIGHT_FILMS_MAX_LIGHTS: the planes resolve_kernel keeps running sums for (LDS)
+// light films (MI355RT_FLAG_LIGHT_FILMS): nlights planes of lights_stride == 3 * width * height floats, each laid out like film_sum
+hipError_t launch_light_films_clear_rows(hipStream_t stream, const uint32_t* rows, uint32_t nrows, uint32_t width, uint32_t nlights, float* film_lights, uint32_t lights_stride);
+// mi355rt_light_films_set / _add: as launch_film_merge, `in` laid out like film_lights (device memory)
+hipError_t launch_light_films_merge(hipStream_t stream, bool add, const float* in, uint32_t nlights, uint32_t npix, uint32_t width,
+                                    uint32_t stripe_rows, uint32_t stripe_world, uint32_t stripe_rank, float* film_lights, uint32_t lights_stride);
+// mi355rt_get_relit_pixels: rgb[p] = sum over the lights of weights[li] * (light[li][p] / n[p]); weights: nlights * 3 floats on the device
+hipError_t launch_relit(hipStream_t stream, uint32_t npix, uint32_t nlights, const float* film_lights, uint32_t lights_stride, const uint32_t* film_n, const float* weights, float* rgb);
 hipError_t launch_slab(hipStream_t stream, const float* inv_rays6, const float* cubes6, uint32_t n, uint8_t* hit, float* tmin);
 // adaptive sampling: out[tile] = the tile is active; *count (zeroed by the caller) += (owned pixels << 32) | 1 per active tile
 hipError_t launch_adaptive_tiles(hipStream_t stream, const AdaptiveArgs& a, const float* film_sum, const float* film_sumsq, const uint32_t* film_n,

@@ -103,13 +103,40 @@ private:
     mi355rt_handle* h_ = nullptr;
 };
 
+// The light films of a handle created with MI355RT_FLAG_LIGHT_FILMS (include/mi355rt.h "LIGHT FILMS"): nlights planes of width * height * 3
+// sums, plane li the film of the scene with every other light black; layout [(li * npix + p) * 3 + c]
+class LightFilms {
+public:
+    size_t nlights() const { return mi355rt_light_count(h_); }
+    std::vector<float> get() const
+    {
+        const size_t npix = (size_t)mi355rt_width(h_) * mi355rt_height(h_), nl = nlights();
+        std::vector<float> a(nl * npix * 3);
+        if (mi355rt_light_films_get(h_, a.data(), nl, npix) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+        return a;
+    }
+    // the planes' bits as they are / handle + a, on the rows the handle owns
+    void set(const std::vector<float>& a) { put(a, false); }
+    void add(const std::vector<float>& a) { put(a, true); }
+private:
+    void put(const std::vector<float>& a, bool add)
+    {
+        const size_t npix = (size_t)mi355rt_width(h_) * mi355rt_height(h_), nl = nlights();
+        if (a.size() != nl * npix * 3) throw std::runtime_error("light films: nlights * width * height * 3 floats are required");
+        if ((add ? mi355rt_light_films_add : mi355rt_light_films_set)(h_, a.data(), nl, npix) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+    }
+    friend class RayTracer;
+    mi355rt_handle* h_ = nullptr;
+};
+
 class RayTracer {         // raytracer/mod.rs:32-47
 public:
     Camera camera;
     Film film;
     Features features;
-    explicit RayTracer(mi355rt_handle* h) : h_(h) { camera.h_ = h; film.h_ = h; features.h_ = h; }
-    RayTracer(RayTracer&& o) noexcept : camera(o.camera), film(o.film), features(o.features), h_(o.h_) { o.h_ = nullptr; }
+    LightFilms light_films;
+    explicit RayTracer(mi355rt_handle* h) : h_(h) { camera.h_ = h; film.h_ = h; features.h_ = h; light_films.h_ = h; }
+    RayTracer(RayTracer&& o) noexcept : camera(o.camera), film(o.film), features(o.features), light_films(o.light_films), h_(o.h_) { o.h_ = nullptr; }
     RayTracer(const RayTracer&) = delete;
     RayTracer& operator=(const RayTracer&) = delete;
     ~RayTracer() { mi355rt_destroy(h_); }
@@ -250,6 +277,18 @@ public:
         return rays;
     }
     // where guides(), the denoised and the display read-outs take their guides from: MI355RT_GUIDES_CENTRE (the state at creation) or MI355RT_GUIDES_FEATURES
+    // mi355rt_get_relit_pixels: the frame with light li's colour scaled by weights3[li * 3 + c], mixed from the light films without tracing; display null:
+    // the reference's tone map.  Returns the packed 0xAARRGGBB pixels; rgb (may be null) receives width * height * 3 floats, exposure_used the exposure applied.
+    std::vector<uint32_t> get_relit_pixels(const std::vector<float>& weights3, const mi355rt_display_config* display = nullptr, std::vector<float>* rgb = nullptr,
+                                           float* exposure_used = nullptr)
+    {
+        const size_t npix = (size_t)mi355rt_width(h_) * mi355rt_height(h_);
+        std::vector<uint32_t> packed(npix);
+        if (rgb) rgb->resize(npix * 3);
+        if (mi355rt_get_relit_pixels(h_, weights3.data(), weights3.size(), display, rgb ? rgb->data() : nullptr, packed.data(), npix, exposure_used) != MI355RT_OK)
+            throw std::runtime_error(mi355rt_last_error(h_));
+        return packed;
+    }
     void set_guide_source(uint32_t source) { if (mi355rt_set_guide_source(h_, source) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_)); }
     uint32_t guide_source() const { return mi355rt_get_guide_source(h_); }
     mi355rt_handle* handle() const { return h_; }

@@ -101,8 +101,8 @@ bool Renderer::set_seed(uint64_t seed)
 // mi355rt_set_flags: run-time flags only; a create-time flag (the intersector) cannot be changed on a live handle
 bool Renderer::set_flags(uint32_t flags)
 {
-    constexpr uint32_t kCreateMask = MI355RT_FLAG_OCTREE_SEMANTICS | MI355RT_FLAG_TRUE_CLOSEST_HIT | MI355RT_FLAG_GROUP_SHARES_DEVICE | MI355RT_FLAG_DEVICE_LBVH | MI355RT_FLAG_DIRECT_FILM;
-    if ((flags ^ cfg.flags) & kCreateMask) { last_error = "the intersector flags (OCTREE_SEMANTICS, TRUE_CLOSEST_HIT), GROUP_SHARES_DEVICE, DEVICE_LBVH and DIRECT_FILM are create-time flags: they cannot be changed with mi355rt_set_flags"; return false; }
+    constexpr uint32_t kCreateMask = MI355RT_FLAG_OCTREE_SEMANTICS | MI355RT_FLAG_TRUE_CLOSEST_HIT | MI355RT_FLAG_GROUP_SHARES_DEVICE | MI355RT_FLAG_DEVICE_LBVH | MI355RT_FLAG_DIRECT_FILM | MI355RT_FLAG_LIGHT_FILMS;
+    if ((flags ^ cfg.flags) & kCreateMask) { last_error = "the intersector flags (OCTREE_SEMANTICS, TRUE_CLOSEST_HIT), GROUP_SHARES_DEVICE, DEVICE_LBVH, DIRECT_FILM and LIGHT_FILMS are create-time flags: they cannot be changed with mi355rt_set_flags"; return false; }
     if (flags != cfg.flags && !settle_speculation()) return false;
     cfg.flags = flags;
     return true;
@@ -117,6 +117,7 @@ bool Renderer::init(const SceneData& scene, std::string& err, int& code)
     if (cfg.width == 0 || cfg.height == 0) { err = "width and height must be non-zero"; return false; }
     if ((uint64_t)cfg.width * cfg.height > 0x7FFFFFFFull / 4) { err = "image too large"; return false; }
     if (cfg.recursions > kMaxRecursions) { err = "recursions > 3 not supported"; return false; }
+    if ((cfg.flags & MI355RT_FLAG_LIGHT_FILMS) && scene.lights.size() > MI355RT_LIGHT_FILMS_MAX_LIGHTS) { err = "MI355RT_FLAG_LIGHT_FILMS: the scene has " + std::to_string(scene.lights.size()) + " lights, more than MI355RT_LIGHT_FILMS_MAX_LIGHTS (8)"; return false; }
     if (scene.cameras.empty()) { err = "scene has no camera"; return false; }     // scene.cameras[0] panics in the reference, lib.rs:39
     if (scene.tri_geom.size() * 9 != scene.tri_verts.size()) { err = "tri_verts / tri_geom size mismatch"; return false; }
     for (uint32_t g : scene.tri_geom) if (g >= scene.materials.size()) { err = "tri_geom entry out of range"; return false; }
@@ -325,6 +326,7 @@ bool Renderer::init(const SceneData& scene, std::string& err, int& code)
     const size_t npix = (size_t)cfg.width * cfg.height;
     if (!upload(d_film_sum_, nullptr, npix * 12) || !upload(d_film_sumsq_, nullptr, npix * 12) || !upload(d_film_n_, nullptr, npix * 4)) return bail();
     if ((cfg.flags & MI355RT_FLAG_DIRECT_FILM) && !upload(d_film_direct_, nullptr, npix * 12)) return bail();     // the direct film: only with the flag
+    if ((cfg.flags & MI355RT_FLAG_LIGHT_FILMS) && nlights_ && !upload(d_film_lights_, nullptr, npix * 12 * nlights_)) return bail();   // the light films: only with the flag
     if (!upload(d_ldr_, nullptr, npix * 4)) return bail();
     ldr_dirty_.assign(cfg.height, (uint8_t)1);
     if (hipEventCreateWithFlags(&ev_tonemap_, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ev_gather_, hipEventDisableTiming) != hipSuccess) { err = "hipEventCreate failed"; return false; }
@@ -877,7 +879,8 @@ bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32
             HIP_TRY(launch_shade(st, num_cus_, r == 0, shade_walks, dscene_, cam, ps, r, in_q, in_c, sl.d_hits.get(), sl.d_queue[r & 1].get(), sl.d_chunk_counts[r & 1].get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound + kShadeCursorOffset, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_n_.get(), d_counters_.get(), fuse_primary, r == 0 ? rays : 0u));
     }
     if (free_rays) HIP_TRY(launch_resolve_rays(st, ps, nlights_, sl.d_slot_L.get(), sl.d_sample_slot.get(), feed->rgb, feed->direct, feed->tuv, feed->prim, sl.d_ctrl.get()));
-    else HIP_TRY(launch_resolve(st, ps, cfg.width, nlights_, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_film_direct_.get(), d_debug_color_.get(), sl.d_ctrl.get()));
+    else HIP_TRY(launch_resolve(st, ps, cfg.width, nlights_, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_film_direct_.get(), d_debug_color_.get(), sl.d_ctrl.get(),
+                                d_film_lights_.get(), lights_stride()));
     sl.ctrl_clean = true;
     return true;
 }
@@ -1012,6 +1015,7 @@ void Renderer::mark_dirty_window(uint32_t first, uint32_t total)
 
 uint32_t Renderer::trace_frame_additive()
 {
+    if (has_light_films()) { last_error = "mi355rt_trace_frame_additive: not available on a handle created with MI355RT_FLAG_LIGHT_FILMS (the fused 50-row frame keeps no light films); mi355rt_render instead"; return 0; }
     const uint32_t nown = (uint32_t)owned_rows.size();
     const FrameWindow win = frame_window(current_row, cfg.height, cfg.stripe_rows, cfg.stripe_world, cfg.stripe_rank, owned_rows);
     // instrumented / timed / reference-exact-octree calls go through the wavefront rounds (several launches, waits for the device)
@@ -1454,12 +1458,14 @@ bool Renderer::film_clear()
         // a striped handle only ever writes its own rows (the others stay as created: zero): one launch over them instead of three
         // whole-film memsets — 20 us of a 3.3 ms frame on one rank of eight
         HIP_TRY(launch_film_clear_rows(stream_, d_owned_rows_.get(), (uint32_t)owned_rows.size(), cfg.width, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_film_direct_.get()));
+        if (d_film_lights_) HIP_TRY(launch_light_films_clear_rows(stream_, d_owned_rows_.get(), (uint32_t)owned_rows.size(), cfg.width, nlights_, d_film_lights_.get(), lights_stride()));
         return true;
     }
     HIP_TRY(hipMemsetAsync(d_film_sum_.get(), 0, npix * 12, stream_));
     HIP_TRY(hipMemsetAsync(d_film_sumsq_.get(), 0, npix * 12, stream_));
     HIP_TRY(hipMemsetAsync(d_film_n_.get(), 0, npix * 4, stream_));
     if (d_film_direct_) HIP_TRY(hipMemsetAsync(d_film_direct_.get(), 0, npix * 12, stream_));
+    if (d_film_lights_) HIP_TRY(launch_light_films_clear_rows(stream_, d_owned_rows_.get(), (uint32_t)owned_rows.size(), cfg.width, nlights_, d_film_lights_.get(), lights_stride()));
     return true;            // stream-ordered: every later call on this handle starts on the same stream
 }
 
@@ -1488,6 +1494,85 @@ bool Renderer::film_put(const FilmPlanes& in, bool add)
                               d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_film_direct_.get()));
     std::fill(ldr_dirty_.begin(), ldr_dirty_.end(), (uint8_t)1);
     HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's arrays and the staging are free again
+    return true;
+}
+
+// ---- light films (include/mi355rt.h, "LIGHT FILMS") ----
+static_assert(kMaxLightFilms == MI355RT_LIGHT_FILMS_MAX_LIGHTS, "the header's limit is the one resolve_kernel's LDS is sized for");
+bool Renderer::light_films_get(float* planes)
+{
+    if (!bind()) return false;
+    if (!settle_speculation()) return false;
+    HIP_TRY(hipStreamSynchronize(stream_));
+    if (d_film_lights_) HIP_TRY(hipMemcpy(planes, d_film_lights_.get(), (size_t)nlights_ * lights_stride() * 4, hipMemcpyDeviceToHost));
+    return true;
+}
+
+// mi355rt_light_films_set / _add: as film_put — the caller's planes staged in a temporary device buffer, stored or added on the owned rows, on stream_
+bool Renderer::light_films_put(const float* planes, bool add)
+{
+    if (!bind()) return false;
+    if (!settle_speculation()) return false;
+    if (!d_film_lights_) return true;                                 // no lights: no planes
+    const size_t bytes = (size_t)nlights_ * lights_stride() * 4;
+    DeviceBuffer<float> stage;
+    HIP_TRY(stage.alloc(bytes, &hbm_bytes_));
+    HIP_TRY(hipMemcpyAsync(stage.get(), planes, bytes, hipMemcpyHostToDevice, stream_));
+    HIP_TRY(launch_light_films_merge(stream_, add, stage.get(), nlights_, cfg.width * cfg.height, cfg.width, cfg.stripe_rows, cfg.stripe_world, cfg.stripe_rank,
+                                     d_film_lights_.get(), lights_stride()));
+    HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's array and the staging are free again
+    return true;
+}
+
+bool Renderer::ensure_display_buffers(bool hist_and_table)
+{
+    const size_t npix = (size_t)cfg.width * cfg.height;
+    if (!d_disp_packed_) HIP_TRY(d_disp_packed_.alloc(npix * 4, &hbm_bytes_));
+    if (!hist_and_table) return true;
+    if (!d_disp_hist_) HIP_TRY(d_disp_hist_.alloc(kDisplayHistWords * 4, &hbm_bytes_));
+    if (!d_disp_table_) {
+        float t[256];
+        t[0] = 0.0f;                           // never read: the search starts above it
+        display_srgb_thresholds(t + 1);
+        DeviceBuffer<float> tab;
+        HIP_TRY(tab.alloc(sizeof t, &hbm_bytes_));
+        HIP_TRY(hipMemcpy(tab.get(), t, sizeof t, hipMemcpyHostToDevice));
+        d_disp_table_ = std::move(tab);
+    }
+    return true;
+}
+
+// mi355rt_get_relit_pixels: relit_kernel writes c into d_relit_rgb_, which the display kernels read as a non-film image (the film's n decides `empty`).
+// dc == null: DISPLAY MAPPING with exposure 1, the Reinhard curve and the reference's transfer is get_tonemapped_pixels' map of c (c * 1.0f is c).
+bool Renderer::get_relit(const float* weights3, const mi355rt_display_config* dc, float* rgb, uint32_t* packed, float& exposure_used)
+{
+    if (!bind()) return false;
+    if (!settle_speculation()) return false;
+    const size_t npix = (size_t)cfg.width * cfg.height;
+    if (!d_relit_rgb_) {
+        DeviceBuffer<float> img, w;
+        HIP_TRY(img.alloc(npix * 12, &hbm_bytes_));
+        HIP_TRY(w.alloc((size_t)MI355RT_LIGHT_FILMS_MAX_LIGHTS * 12, &hbm_bytes_));
+        d_relit_rgb_ = std::move(img); d_relit_weights_ = std::move(w);
+    }
+    if (!ensure_display_buffers(dc != nullptr)) return false;
+    if (nlights_) HIP_TRY(hipMemcpyAsync(d_relit_weights_.get(), weights3, (size_t)nlights_ * 12, hipMemcpyHostToDevice, stream_));
+    HIP_TRY(launch_relit(stream_, (uint32_t)npix, nlights_, d_film_lights_.get(), lights_stride(), d_film_n_.get(), d_relit_weights_.get(), d_relit_rgb_.get()));
+    float E = dc ? dc->exposure : 1.0f;
+    if (dc && dc->auto_exposure) {
+        mi355rt_luminance_histogram hist;
+        if (!display_hist_queue(d_relit_rgb_.get(), false, hist)) return false;
+        E = display_auto_exposure(hist, dc->key, dc->low, dc->high);
+    }
+    if (packed) {
+        DisplayArgs a{};
+        a.curve = dc ? dc->curve : MI355RT_CURVE_REINHARD; a.transfer = dc ? dc->transfer : MI355RT_TRANSFER_REFERENCE; a.exposure = E; a.white2 = dc ? dc->white * dc->white : 16.0f;
+        HIP_TRY(launch_display_pack(stream_, a, (uint32_t)npix, d_relit_rgb_.get(), d_film_n_.get(), false, d_disp_table_.get(), d_disp_packed_.get()));
+        HIP_TRY(hipMemcpyAsync(packed, d_disp_packed_.get(), npix * 4, hipMemcpyDeviceToHost, stream_));
+    }
+    if (rgb) HIP_TRY(hipMemcpyAsync(rgb, d_relit_rgb_.get(), npix * 12, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    exposure_used = E;
     return true;
 }
 
@@ -1936,17 +2021,7 @@ bool Renderer::get_display(const mi355rt_display_config& dc, const mi355rt_denoi
     const size_t npix = (size_t)cfg.width * cfg.height;
     const float* img = nullptr; bool film = true;
     if (!display_source(dc.source, dn, img, film)) return false;
-    if (!d_disp_packed_) HIP_TRY(d_disp_packed_.alloc(npix * 4, &hbm_bytes_));
-    if (!d_disp_hist_) HIP_TRY(d_disp_hist_.alloc(kDisplayHistWords * 4, &hbm_bytes_));       // with the first call, whatever it asks for: the handle's memory
-    if (!d_disp_table_) {                                                                     // does not depend on the configs that follow
-        float t[256];
-        t[0] = 0.0f;                           // never read: the search starts above it
-        display_srgb_thresholds(t + 1);
-        DeviceBuffer<float> tab;
-        HIP_TRY(tab.alloc(sizeof t, &hbm_bytes_));
-        HIP_TRY(hipMemcpy(tab.get(), t, sizeof t, hipMemcpyHostToDevice));
-        d_disp_table_ = std::move(tab);
-    }
+    if (!ensure_display_buffers(true)) return false;      // with the first call, whatever it asks for: the handle's memory does not depend on the configs that follow
     float E = dc.exposure;
     if (dc.auto_exposure) {
         mi355rt_luminance_histogram hist;

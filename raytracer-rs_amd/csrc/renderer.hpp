@@ -76,6 +76,13 @@ public:
     bool get_guides(float* depth, float* normal3, float* albedo3, uint32_t* prim);
     bool get_denoised(const mi355rt_denoise_config& dc, float* rgb, uint32_t* packed, bool split = false);   // split: the indirect part is filtered
     bool has_direct_film() const { return (cfg.flags & MI355RT_FLAG_DIRECT_FILM) != 0; }
+    // light films (MI355RT_FLAG_LIGHT_FILMS); the caller has checked the flag and the arguments.  planes: nlights() * width * height * 3 floats
+    bool has_light_films() const { return (cfg.flags & MI355RT_FLAG_LIGHT_FILMS) != 0; }
+    uint32_t nlights() const { return nlights_; }
+    bool light_films_get(float* planes);
+    bool light_films_put(const float* planes, bool add);
+    // mi355rt_get_relit_pixels: weights3 nlights() * 3 floats; dc null: the reference's tone map; rgb / packed: either may be null
+    bool get_relit(const float* weights3, const mi355rt_display_config* dc, float* rgb, uint32_t* packed, float& exposure_used);
     // feature film; the caller has checked the arguments.  rays6 null: spp samples under the handle's lens, else along the caller's rays
     bool features_render(const float* rays6, uint32_t spp, bool device);
     bool features_get(uint32_t* n, uint32_t* hits, float* depth, float* normal3, float* albedo3);
@@ -241,6 +248,10 @@ private:
     DScene dscene_{};
     DeviceBuffer<float> d_film_sum_, d_film_sumsq_; DeviceBuffer<uint32_t> d_film_n_;
     DeviceBuffer<float> d_film_direct_;  // MI355RT_FLAG_DIRECT_FILM: per pixel, the sum of its samples' root light terms (null without the flag)
+    DeviceBuffer<float> d_film_lights_;  // MI355RT_FLAG_LIGHT_FILMS: nlights_ planes of width * height * 3 floats, per pixel the sum of its samples' light radiances (null without the flag or without lights)
+    uint32_t lights_stride() const { return cfg.width * cfg.height * 3u; }      // floats per plane
+    DeviceBuffer<float> d_relit_rgb_, d_relit_weights_;   // mi355rt_get_relit_pixels, allocated on first use: the relit image (12 bytes per pixel; d_disp_packed_ takes the packed one), the weights
+    bool ensure_display_buffers(bool hist_and_table);     // d_disp_packed_ [, d_disp_hist_, d_disp_table_], on first use
     DeviceBuffer<uint32_t> d_owned_rows_, d_all_rows_, d_tmp_rows_;
     DeviceBuffer<uint32_t> d_ldr_;
     PinnedBuffer<uint32_t> h_ldr_;       // host mirror of d_ldr_ (get_tonemapped_pixels)

@@ -40,6 +40,10 @@ pub const DEFAULT_TRIANGLES_PER_LEAF: usize = 70;
 /// create-time flag (declared for a caller that sets cfg.flags itself; this shim sets none): the handle keeps a direct film, the sum of
 /// every sample's root light term, which the two direct-film entries below read
 pub const MI355RT_FLAG_DIRECT_FILM: u32 = 128;
+/// create-time flag (declared for a caller that sets cfg.flags itself; this shim sets none): the handle keeps a film per light, which the
+/// light-film entries below read, write and mix; such a handle serves mi355rt_render, not mi355rt_trace_frame_additive
+pub const MI355RT_FLAG_LIGHT_FILMS: u32 = 256;
+pub const MI355RT_LIGHT_FILMS_MAX_LIGHTS: u32 = 8;
 #[allow(dead_code)] #[repr(C)] pub struct mi355rt_denoise_config { pub iterations: u32, pub normal_power_log2: u32, pub sigma_luminance: f32, pub sigma_depth: f32, pub sigma_albedo: f32 }
 pub const MI355RT_RAYS_HOST: u32 = 0;
 pub const MI355RT_RAYS_DEVICE: u32 = 1;
@@ -65,6 +69,14 @@ extern "C" {
     // counts = a mi355rt_ray_counts or null
     fn mi355rt_trace_rays(h: *mut mi355rt_handle, rays6: *const f32, keys2: *const u32, n: usize, where_: u32, out: *const mi355rt_ray_outputs) -> c_int;
     fn mi355rt_render_rays(h: *mut mi355rt_handle, rays6: *const f32, nrays: usize, spp: u32, where_: u32, counts: *mut std::ffi::c_void) -> c_int;
+    // light films (declared for a caller that relights a finished render; this shim calls none of them): light_rgb[(li * npix + p) * 3 + c];
+    // display = a mi355rt_display_config or null
+    fn mi355rt_light_count(h: *const mi355rt_handle) -> u32;
+    fn mi355rt_light_films_get(h: *mut mi355rt_handle, light_rgb: *mut f32, nlights: usize, npix: usize) -> c_int;
+    fn mi355rt_light_films_set(h: *mut mi355rt_handle, light_rgb: *const f32, nlights: usize, npix: usize) -> c_int;
+    fn mi355rt_light_films_add(h: *mut mi355rt_handle, light_rgb: *const f32, nlights: usize, npix: usize) -> c_int;
+    fn mi355rt_get_relit_pixels(h: *mut mi355rt_handle, weights3: *const f32, nweights: usize, display: *const std::ffi::c_void,
+                                rgb: *mut f32, packed: *mut u32, npix: usize, exposure_used: *mut f32) -> c_int;
     fn mi355rt_camera_move_rel(h: *mut mi355rt_handle, x: f32, y: f32, z: f32) -> c_int;
     fn mi355rt_camera_add_x_angle(h: *mut mi355rt_handle, radians: f32) -> c_int;
     fn mi355rt_camera_add_y_angle(h: *mut mi355rt_handle, radians: f32) -> c_int;
