@@ -756,6 +756,51 @@ int  mi355rt_light_films_add(mi355rt_handle* h, const float* light_rgb, size_t n
 int  mi355rt_get_relit_pixels(mi355rt_handle* h, const float* weights3, size_t nweights, const mi355rt_display_config* display /* may be NULL */,
                               float* rgb, uint32_t* packed, size_t npix, float* exposure_used /* may be NULL */);
 
+/* ---- GATHER: light arriving at caller-given points, sampled on the device (no reference counterpart).
+ * The points are a film of their own: per point n, sum, sumsq (and hits, near), accumulated in sample order.  The rays are made on the device from the
+ * renderer's own hemisphere sampler; everything about a ray after it is made is mi355rt_trace_rays.
+ *
+ * THE SAMPLE.  Sample s of point i has the key (id_i, first_sample + s); id_i = ids[i], or i with ids == NULL.
+ *     start = (uint32_t)(((uint64_t)h0 * 65535) >> 32),  h0 = word 0 of pcg4d(id_i, first_sample + s, 0xFFFFFFFE, seed)       (a hash stream of its own)
+ *     d = table[start];  while dot(d, normal) <= 0:  start = (start + 1) % 65535, d = table[start]          (reflection_ray's walk, mod.rs:187-189)
+ *     ray = (point + 0.00001f * d, d)                                                                         (mod.rs:192-193)
+ * dot(d, n) = d.x * n.x + d.y * n.y + d.z * n.z, f32, unfused, left to right.  The normal is used as given (not normalised; pass unit normals).  The walk stops
+ * after one full turn of the table: a normal no entry satisfies (zero, or so small that every product underflows) makes the sample VOID: n does not count
+ * it and nothing is added for it.  A NaN normal accepts the start entry (NaN <= 0 is false).  normals3 == NULL is SPHERE MODE: no walk, d = table[start].
+ * The ray is traced under its key as mi355rt_trace_rays traces it.
+ *
+ * PER POINT, in sample order, for every sample that is not void, with w = 1 (MI355RT_GATHER_MEAN) or w = 2.0f * dot(d, normal) (MI355RT_GATHER_COSINE) and
+ * v = w * rgb per channel (one f32 multiply, unfused):
+ *     sum += v;  sumsq += v * v;  n += 1;  hits += hit;  near += hit && t < near_distance          (t as mi355rt_intersect_rays reports it)
+ * accumulate != 0: the outputs are read, added to and written back, so gather(3) followed by gather(5, first_sample 3, accumulate) is gather(8) bit for bit;
+ * otherwise they start from 0.  mean = sum / n is the reference's bounce estimator at the point (MEAN), or irradiance / pi (COSINE: the table is uniform
+ * on the sphere, the accepted half has density 1 / (2 pi)).
+ *
+ * DIRECT (needs normals; always overwritten, never accumulated): the point-light term of shade() (mod.rs:207-261) without material and specular.  Over the
+ * lights in scene order: l = light - p, ndl = dot(normal, normalized(l)); a light with ndl < 0 is skipped; the shadow ray (p + l * 0.01f, l) is blocked by
+ * the rule of mi355rt_occluded_rays; otherwise direct += color * ndl (from +0.0f).
+ *
+ * AROUND THE CALL.  The read-out rules of mi355rt_trace_rays: a queued or speculative frame is settled first; film, direct film, light films, camera, lens,
+ * current row, caller-ray mark and guides are untouched; mi355rt_last_counts reports the rays traced (npoints * spp primary); striped handles serve it.
+ * `where` as for mi355rt_trace_rays: every pointer (points3, normals3, ids and the outputs) is host memory, staged, or device memory, used in place on the
+ * handle's stream.  Every temporary is freed by the end of the call (pass buffers that grew excepted, as for mi355rt_trace_rays).
+ *
+ * ERRORS.  MI355RT_E_INVALID, the argument named in mi355rt_last_error and nothing written, for: NULL points3 with npoints > 0; out NULL or all outputs NULL;
+ * cfg NULL; spp == 0 while n, hits, near, sum or sumsq is asked for; COSINE or direct without normals; an unknown weight or where; a NaN near_distance;
+ * npoints * spp >= 2^32; first_sample + spp overflowing 32 bits; a device group.  npoints == 0 succeeds and writes nothing.
+ *
+ * mi355rt_gather_ray: THE SAMPLE on the host, no handle: the same header the kernel compiles (csrc/gather_walk.hpp).  table3: 65536 x 3 floats
+ * (mi355rt_get_sample_table).  ray6 receives the ray; a void sample gets the harmless ray of the start entry and *valid = 0 (valid may be NULL). */
+#define MI355RT_GATHER_MEAN   0u   /* w = 1: the reference's bounce estimator (mod.rs:146-175) */
+#define MI355RT_GATHER_COSINE 1u   /* w = 2 * dot(d, normal): mean = irradiance / pi under the table's uniform hemisphere */
+typedef struct mi355rt_gather_config  { uint32_t spp, first_sample, weight, accumulate; float near_distance; } mi355rt_gather_config;
+typedef struct mi355rt_gather_outputs { uint32_t *n, *hits, *near; float *sum, *sumsq, *direct; } mi355rt_gather_outputs;  /* any may be NULL, not all */
+void mi355rt_gather_default_config(mi355rt_gather_config* cfg);   /* spp 16, first_sample 0, MEAN, accumulate 0, near_distance +inf */
+int  mi355rt_gather(mi355rt_handle* h, const float* points3, const float* normals3 /* NULL: whole sphere */, const uint32_t* ids /* NULL: i */,
+                    size_t npoints, const mi355rt_gather_config* cfg, uint32_t where, const mi355rt_gather_outputs* out);
+int  mi355rt_gather_ray(const float* table3 /* 65536 x 3 */, uint32_t seed, const float point[3], const float* normal3 /* may be NULL */,
+                        uint32_t id, uint32_t sampleno, float ray6[6], uint32_t* valid);
+
 /* SampleGenerator table, sample_generator.rs:15-24: 65 536 x 3 floats */
 int mi355rt_get_sample_table(const mi355rt_handle* h, float* out);
 /* Per-node direct-light terms of one primary sample, computed on the device by the same

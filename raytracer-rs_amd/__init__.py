@@ -152,6 +152,22 @@ class RayOutputs(C.Structure):
 
 RAY_OUTPUTS = ("rgb", "direct", "tuv", "prim")
 
+GATHER_MEAN, GATHER_COSINE = 0, 1      # MI355RT_GATHER_*
+GATHER_WEIGHTS = {"mean": GATHER_MEAN, "cosine": GATHER_COSINE}
+
+
+class GatherConfig(C.Structure):
+    """mi355rt_gather_config (include/mi355rt.h, "GATHER")"""
+    _fields_ = [("spp", C.c_uint32), ("first_sample", C.c_uint32), ("weight", C.c_uint32), ("accumulate", C.c_uint32), ("near_distance", C.c_float)]
+
+
+class GatherOutputs(C.Structure):
+    """mi355rt_gather_outputs: any pointer may be NULL, not all of them (void pointers here: host arrays or device addresses)"""
+    _fields_ = [("n", C.c_void_p), ("hits", C.c_void_p), ("near", C.c_void_p), ("sum", C.c_void_p), ("sumsq", C.c_void_p), ("direct", C.c_void_p)]
+
+
+GATHER_OUTPUTS = ("n", "hits", "near", "sum", "sumsq", "direct")
+
 LENS_PINHOLE, LENS_THIN, LENS_ORTHO = 0, 1, 2      # MI355RT_LENS_*
 LENS_MODELS = {"pinhole": LENS_PINHOLE, "thin": LENS_THIN, "ortho": LENS_ORTHO}
 
@@ -224,6 +240,9 @@ ABI = [
     ("mi355rt_occluded_rays", C.c_int, [_H, _F, C.c_size_t, C.POINTER(C.c_uint8)]),
     ("mi355rt_trace_rays", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(RayOutputs)]),
     ("mi355rt_render_rays", C.c_int, [_H, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(RayCounts)]),
+    ("mi355rt_gather_default_config", None, [C.POINTER(GatherConfig)]),
+    ("mi355rt_gather", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(GatherConfig), C.c_uint32, C.POINTER(GatherOutputs)]),
+    ("mi355rt_gather_ray", C.c_int, [_F, C.c_uint32, _F, _F, C.c_uint32, C.c_uint32, _F, _U]),
     ("mi355rt_lens_default", None, [C.POINTER(Lens)]),
     ("mi355rt_set_lens", C.c_int, [_H, C.POINTER(Lens)]),
     ("mi355rt_get_lens", C.c_int, [_H, C.POINTER(Lens)]),
@@ -336,6 +355,15 @@ def _ray_array(a, name, cols, dtype, rows=None):
     if not contiguous:
         raise ValueError("%s: must be C-contiguous" % name)
     return addr, shape[0], dev
+
+
+def _ray_vector(a, name, dtype, rows):
+    """_ray_array for a one-dimensional argument (rows,): checked as the (rows, 1) view of the same memory"""
+    if (_is_tensor(a) and a.dim() == 1 and a.is_contiguous()) or (isinstance(a, np.ndarray) and a.ndim == 1 and a.flags["C_CONTIGUOUS"]):
+        return _ray_array(a.reshape(-1, 1), name, 1, dtype, rows=rows)
+    if _is_tensor(a) or isinstance(a, np.ndarray):
+        raise ValueError("%s: shape must be (%d,) and C-contiguous, not %s" % (name, rows, tuple(a.shape)))
+    raise TypeError("%s: a numpy array or a torch tensor, not %s" % (name, type(a).__name__))
 
 
 def default_config(width=1024, height=768, **kw):
@@ -886,6 +914,57 @@ class RayTracer:
                 res[w] = np.zeros(n, np.uint32) if w == "prim" else np.zeros((n, 3), np.float32)
                 setattr(o, w, res[w].ctypes.data)
         self._check(lib().mi355rt_trace_rays(self._h, addr, kaddr, n, RAYS_DEVICE if dev else RAYS_HOST, C.byref(o)))
+        return res
+
+    def gather(self, points, normals=None, ids=None, spp=16, first_sample=0, weight="mean", near_distance=float("inf"), want=("n", "sum"), into=None):
+        """mi355rt_gather: the light arriving at caller-given points, sampled on the device with the renderer's own hemisphere sampler (raytracer_rs_amd.gather
+        is the statement).  points: float32 (n, 3); normals: float32 (n, 3) unit normals, None: the whole sphere (probes); ids: uint32 (n,) keys of the points'
+        random numbers, None: i; weight "mean" (the reference's bounce estimator) or "cosine" (mean = irradiance / pi); want: any of "n", "hits", "near", "sum",
+        "sumsq", "direct".  numpy arrays are host memory and the results numpy arrays; torch tensors on the handle's GPU are read in place and the results are
+        tensors there (uint32 as torch.int32 holding the same bits), under trace_rays' rules.  into: the dict of an earlier call; its arrays are added to and
+        returned (accumulate): gather(spp=3) then gather(spp=5, first_sample=3, into=res) is gather(spp=8) bit for bit.  `direct` is always overwritten.
+        Returns a dict name -> array.  No film, camera or lens state changes."""
+        want = tuple(want)
+        if not want or any(w not in GATHER_OUTPUTS for w in want) or len(set(want)) != len(want):
+            raise ValueError("want: a non-empty selection of %s without repeats, not %r" % (GATHER_OUTPUTS, want))
+        if weight not in GATHER_WEIGHTS:
+            raise ValueError("weight: one of %s, not %r" % (tuple(GATHER_WEIGHTS), weight))
+        addr, n, dev = _ray_array(points, "points", 3, np.float32)
+        naddr = iaddr = None
+        if normals is not None:
+            naddr, _, ndev = _ray_array(normals, "normals", 3, np.float32, rows=n)
+            if ndev != dev:
+                raise ValueError("normals must live where points live (both numpy arrays, or both tensors on the GPU)")
+        if ids is not None:
+            iaddr, _, idev = _ray_vector(ids, "ids", np.uint32, n)
+            if idev != dev:
+                raise ValueError("ids must live where points live (both numpy arrays, or both tensors on the GPU)")
+        cfg = GatherConfig()
+        lib().mi355rt_gather_default_config(C.byref(cfg))
+        cfg.spp, cfg.first_sample, cfg.weight, cfg.accumulate, cfg.near_distance = int(spp), int(first_sample), GATHER_WEIGHTS[weight], 1 if into is not None else 0, float(near_distance)
+        res, o = {}, GatherOutputs()
+        if dev:
+            import torch
+        for w in want:
+            cols = 3 if w in ("sum", "sumsq", "direct") else 1
+            if into is not None and w != "direct":
+                if w not in into:
+                    raise ValueError("into: holds no %r" % w)
+                a = into[w]
+                a_addr, _, adev = _ray_array(a, "into[%r]" % w, 3, np.float32, rows=n) if cols == 3 else _ray_vector(a, "into[%r]" % w, np.uint32, n)
+                if adev != dev:
+                    raise ValueError("into[%r] must live where points live" % w)
+            elif dev:
+                a = torch.zeros((n, 3) if cols == 3 else (n,), dtype=torch.float32 if cols == 3 else torch.int32, device=points.device)
+                a_addr = a.data_ptr()
+            else:
+                a = np.zeros((n, 3), np.float32) if cols == 3 else np.zeros(n, np.uint32)
+                a_addr = a.ctypes.data
+            res[w] = a
+            setattr(o, w, a_addr)
+        if dev:
+            torch.cuda.current_stream(points.device).synchronize()          # what produced the inputs (and the zero fill) has finished: the library's stream knows nothing of torch's
+        self._check(lib().mi355rt_gather(self._h, addr, naddr, iaddr, n, C.byref(cfg), RAYS_DEVICE if dev else RAYS_HOST, C.byref(o)))
         return res
 
     def render_rays(self, rays6, spp):

@@ -11,6 +11,7 @@
 #include "octree.hpp"
 #include "reflmask.hpp"
 #include "../../include/mi355rt.h"
+#include "gather_walk.hpp"
 #include "group.hpp"
 #include "lens.hpp"
 #include "renderer.hpp"
@@ -836,6 +837,49 @@ int mi355rt_render_rays(mi355rt_handle* h, const float* rays6, size_t nrays, uin
     const bool ok = h->r->render_rays(rays6, spp, where == MI355RT_RAYS_DEVICE);
     if (counts) *counts = h->r->counts;
     return ok ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+void mi355rt_gather_default_config(mi355rt_gather_config* cfg)
+{
+    if (!cfg) return;
+    cfg->spp = 16; cfg->first_sample = 0; cfg->weight = MI355RT_GATHER_MEAN; cfg->accumulate = 0; cfg->near_distance = INFINITY;
+}
+
+int mi355rt_gather(mi355rt_handle* h, const float* points3, const float* normals3, const uint32_t* ids, size_t npoints, const mi355rt_gather_config* cfg, uint32_t where,
+                   const mi355rt_gather_outputs* out)
+{
+    if (!h) return MI355RT_E_INVALID;
+    const char* e = nullptr;
+    const bool sampled = out && (out->n || out->hits || out->near || out->sum || out->sumsq);
+    if (h->g->size() > 1) e = "not available on a device group (config.device_count > 1)";
+    else if (where > MI355RT_RAYS_DEVICE) e = "unknown `where` (MI355RT_RAYS_HOST or MI355RT_RAYS_DEVICE)";
+    else if (!cfg) e = "cfg is NULL";
+    else if (!out || (!sampled && !out->direct)) e = "out is NULL or every output pointer in it is NULL";
+    else if (npoints && !points3) e = "points3 is NULL";
+    else if (cfg->weight > MI355RT_GATHER_COSINE) e = "unknown weight (MI355RT_GATHER_MEAN or MI355RT_GATHER_COSINE)";
+    else if (cfg->weight == MI355RT_GATHER_COSINE && !normals3) e = "weight MI355RT_GATHER_COSINE needs normals3";
+    else if (out->direct && !normals3) e = "the direct output needs normals3";
+    else if (sampled && cfg->spp == 0) e = "spp must be >= 1 when n, hits, near, sum or sumsq is asked for";
+    else if (std::isnan(cfg->near_distance)) e = "near_distance is NaN";
+    else if ((uint64_t)cfg->first_sample + cfg->spp > 0xFFFFFFFFull) e = "first_sample + spp must fit 32 bits";
+    else if (npoints > 0xFFFFFFFFull || (uint64_t)npoints * std::max(cfg->spp, 1u) >= (1ull << 32)) e = "npoints * spp must be < 2^32";
+    if (e) { h->r->last_error = std::string("mi355rt_gather: ") + e; return MI355RT_E_INVALID; }
+    if (npoints == 0) return MI355RT_OK;
+    return h->r->gather(points3, normals3, ids, npoints, *cfg, where == MI355RT_RAYS_DEVICE, *out) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_gather_ray(const float* table3, uint32_t seed, const float point[3], const float* normal3, uint32_t id, uint32_t sampleno, float ray6[6], uint32_t* valid)
+{
+    if (!table3) return bad("mi355rt_gather_ray: table3 is NULL");
+    if (!point) return bad("mi355rt_gather_ray: point is NULL");
+    if (!ray6) return bad("mi355rt_gather_ray: ray6 is NULL");
+    GatherDir d;
+    const bool ok = gather_walk([table3](uint32_t j) { GatherDir g; g.x = table3[3 * (size_t)j]; g.y = table3[3 * (size_t)j + 1]; g.z = table3[3 * (size_t)j + 2]; return g; },
+                                normal3 != nullptr, normal3 ? normal3[0] : 0.0f, normal3 ? normal3[1] : 0.0f, normal3 ? normal3[2] : 0.0f, gather_start(id, sampleno, seed), d);
+    gather_ray_from(point, d, ray6);
+    ray6[3] = d.x; ray6[4] = d.y; ray6[5] = d.z;
+    if (valid) *valid = ok ? 1u : 0u;
+    return MI355RT_OK;
 }
 
 void mi355rt_lens_default(mi355rt_lens* lens)

@@ -38,6 +38,7 @@
 #include <utility>
 #include "device_math.hpp"
 #include "device_types.hpp"
+#include "gather_walk.hpp"
 #include "kernels.hpp"
 #include "lens.hpp"
 #include "reflmask.hpp"
@@ -1738,6 +1739,122 @@ __global__ __launch_bounds__(256) void lens_rays_kernel(DCamera cam, uint32_t fl
     r[0] = a; r[1] = b;
 }
 
+// ---- gather (include/mi355rt.h "GATHER"): light arriving at caller-given points -------------------------------------------
+// A chunk is `cp` points (from point0 on) x `cs` samples (sample numbers from `first` on), laid out sample-major: entry s * cp + i, so that consecutive
+// lanes write consecutive 24-byte rays here and read consecutive 12-byte results in the reduce.
+// gather_rays_kernel: one lane per entry — the hash, the float4 table entry, the bounded walk of gather_walk.hpp (the table is 1 MB and L2-resident); the ray
+// as two 12-byte stores, the key pair, one validity byte.  A void sample keeps the start entry as its direction: a finite ray that is traced and not counted.
+__global__ __launch_bounds__(256) void gather_rays_kernel(const float4* __restrict__ table, uint32_t seed, const float* __restrict__ points, const float* __restrict__ normals,
+                                                         const uint32_t* __restrict__ ids, uint32_t point0, uint32_t cp, uint32_t cs, uint32_t first,
+                                                         float* __restrict__ rays6, uint2* __restrict__ keys, uint8_t* __restrict__ valid)
+{
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= cp * cs) return;
+    const uint32_t s = e / cp, gp = point0 + (e - s * cp);
+    const RayHalf p = *(const RayHalf*)(points + 3ull * gp);
+    RayHalf n; n.x = 0.0f; n.y = 0.0f; n.z = 0.0f;
+    if (normals != nullptr) n = *(const RayHalf*)(normals + 3ull * gp);
+    const uint32_t id = ids != nullptr ? ids[gp] : gp, sampleno = first + s;
+    GatherDir d;
+    const bool ok = gather_walk([table](uint32_t j) { const float4 t = table[j]; GatherDir g; g.x = t.x; g.y = t.y; g.z = t.z; return g; },
+                                normals != nullptr, n.x, n.y, n.z, gather_start(id, sampleno, seed), d);
+    const float pp[3] = { p.x, p.y, p.z };
+    float o[3];
+    gather_ray_from(pp, d, o);
+    RayHalf a, b;
+    a.x = o[0]; a.y = o[1]; a.z = o[2]; b.x = d.x; b.y = d.y; b.z = d.z;
+    RayHalf* r = (RayHalf*)(rays6 + 6ull * e);
+    r[0] = a; r[1] = b;
+    keys[e] = make_uint2(id, sampleno);
+    valid[e] = ok ? 1 : 0;
+}
+
+// gather_reduce_kernel: one lane per point of the chunk, its samples in order: v = w * rgb (w recomputed from the stored direction and the normal), the
+// read-modify-write of the point's outputs.  fresh: the outputs start from 0 (the first sample chunk of a call that does not accumulate).  Any output may
+// be null; rgb is read only for sum / sumsq, prim / tuv (the results of the ray-fed pass) only for hits / near.
+__global__ __launch_bounds__(256) void gather_reduce_kernel(uint32_t point0, uint32_t cp, uint32_t cs, uint32_t weight, int fresh, float near_distance,
+                                                           const float* __restrict__ normals, const float* __restrict__ rays6, const uint8_t* __restrict__ valid,
+                                                           const float* __restrict__ rgb, const float* __restrict__ tuv, const uint32_t* __restrict__ prim,
+                                                           uint32_t* out_n, uint32_t* out_hits, uint32_t* out_near, float* out_sum, float* out_sumsq)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cp) return;
+    const size_t gp = (size_t)point0 + i;
+    const bool sums = out_sum != nullptr || out_sumsq != nullptr, hitq = out_hits != nullptr || out_near != nullptr;
+    f3 nrm = mk3(0.0f, 0.0f, 0.0f);
+    if (weight == 1u) nrm = mk3(normals[3 * gp], normals[3 * gp + 1], normals[3 * gp + 2]);
+    uint32_t n = 0u, hits = 0u, near = 0u;
+    f3 sum = mk3(0.0f, 0.0f, 0.0f), sq = sum;
+    if (!fresh) {
+        if (out_n) n = out_n[gp];
+        if (out_hits) hits = out_hits[gp];
+        if (out_near) near = out_near[gp];
+        if (out_sum) sum = mk3(out_sum[3 * gp], out_sum[3 * gp + 1], out_sum[3 * gp + 2]);
+        if (out_sumsq) sq = mk3(out_sumsq[3 * gp], out_sumsq[3 * gp + 1], out_sumsq[3 * gp + 2]);
+    }
+    for (uint32_t s = 0; s < cs; ++s) {
+        const size_t e = (size_t)s * cp + i;
+        if (!valid[e]) continue;                      // a void sample: nothing is counted, nothing is added
+        n += 1u;
+        if (sums) {
+            float w = 1.0f;
+            if (weight == 1u) w = 2.0f * dot3(mk3(rays6[6 * e + 3], rays6[6 * e + 4], rays6[6 * e + 5]), nrm);
+            const f3 v = mk3(w * rgb[3 * e], w * rgb[3 * e + 1], w * rgb[3 * e + 2]);
+            sum = add3(sum, v);
+            sq = add3(sq, mk3(v.x * v.x, v.y * v.y, v.z * v.z));
+        }
+        if (hitq && prim[e] != kMiss) {
+            hits += 1u;
+            if (tuv[3 * e] < near_distance) near += 1u;
+        }
+    }
+    if (out_n) out_n[gp] = n;
+    if (out_hits) out_hits[gp] = hits;
+    if (out_near) out_near[gp] = near;
+    if (out_sum) { out_sum[3 * gp] = sum.x; out_sum[3 * gp + 1] = sum.y; out_sum[3 * gp + 2] = sum.z; }
+    if (out_sumsq) { out_sumsq[3 * gp] = sq.x; out_sumsq[3 * gp + 1] = sq.y; out_sumsq[3 * gp + 2] = sq.z; }
+}
+
+// The shadow rays of `direct`: one lane per (light, point) of the chunk, entry li * cp + i: l = light - p, the ray (p + l * 0.01f, l) of mod.rs:224-225, whether or
+// not the light lies behind the surface (gather_direct_kernel skips those).  They go through intersect_kernel's shadow mode: mi355rt_occluded_rays' rule.
+__global__ __launch_bounds__(256) void gather_shadow_rays_kernel(const DLight* __restrict__ lights, uint32_t nlights, const float* __restrict__ points, uint32_t point0, uint32_t cp,
+                                                                float* __restrict__ rays6)
+{
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= cp * nlights) return;
+    const uint32_t li = e / cp;
+    const size_t gp = (size_t)point0 + (e - li * cp);
+    const DLight lt = lights[li];
+    const f3 p = mk3(points[3 * gp], points[3 * gp + 1], points[3 * gp + 2]);
+    const f3 l = sub3(mk3(lt.px, lt.py, lt.pz), p);                        // mod.rs:215
+    const f3 o = add3(p, vscale(l, 0.01f));                                // mod.rs:224
+    RayHalf a, b;
+    a.x = o.x; a.y = o.y; a.z = o.z; b.x = l.x; b.y = l.y; b.z = l.z;
+    RayHalf* r = (RayHalf*)(rays6 + 6ull * e);
+    r[0] = a; r[1] = b;
+}
+
+// `direct` of a chunk's points: one lane per point, the lights in scene order (the sum is per point, in light order): ndl = dot(normal, normalized(light - p)),
+// mod.rs:215-218; a light with ndl < 0 is skipped, a blocked one adds nothing; else direct += color * ndl, from +0.0f.  blocked: entry li * cp + i.
+__global__ __launch_bounds__(256) void gather_direct_kernel(const DLight* __restrict__ lights, uint32_t nlights, const float* __restrict__ points, const float* __restrict__ normals,
+                                                           uint32_t point0, uint32_t cp, const uint8_t* __restrict__ blocked, float* __restrict__ direct)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cp) return;
+    const size_t gp = (size_t)point0 + i;
+    const f3 p = mk3(points[3 * gp], points[3 * gp + 1], points[3 * gp + 2]);
+    const f3 n = mk3(normals[3 * gp], normals[3 * gp + 1], normals[3 * gp + 2]);
+    f3 acc = mk3(0.0f, 0.0f, 0.0f);
+    for (uint32_t li = 0; li < nlights; ++li) {
+        const DLight lt = lights[li];
+        const float ndl = dot3(n, normalized3(sub3(mk3(lt.px, lt.py, lt.pz), p)));
+        if (ndl < 0.0f) continue;
+        if (blocked[(size_t)li * cp + i]) continue;
+        acc = add3(acc, mk3(lt.cr * ndl, lt.cg * ndl, lt.cb * ndl));
+    }
+    direct[3 * gp] = acc.x; direct[3 * gp + 1] = acc.y; direct[3 * gp + 2] = acc.z;
+}
+
 // ---- feature film (include/mi355rt.h "FEATURE FILM") -----------------------------------------------------------------
 // One lane per owned pixel (entry i of the owned-row list: neighbouring lanes are neighbouring pixels of a row, so the rays of a wave stay as coherent as
 // the guides' are); the lane keeps the nine sums in registers and takes its spp samples in sample order: the ray in registers (RAYS: the caller's, ray
@@ -2668,6 +2785,43 @@ hipError_t launch_lens_rays(hipStream_t stream, const DCamera& cam, uint32_t fla
     if (nrays == 0) return hipSuccess;
     if ((nrays + 255) / 256 > 0x7FFFFFFFull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lens_rays_kernel, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, stream, cam, flags, seed, npix, nrays, film_n, rays6);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_rays(hipStream_t stream, const DScene& sc, uint32_t seed, const float* points, const float* normals, const uint32_t* ids,
+                              uint32_t point0, uint32_t cp, uint32_t cs, uint32_t first, float* rays6, uint32_t* keys2, uint8_t* valid)
+{
+    const size_t n = (size_t)cp * cs;
+    if (n == 0) return hipSuccess;
+    if (n > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gather_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float4*)sc.table, seed, points, normals, ids, point0, cp, cs, first,
+                       rays6, (uint2*)keys2, valid);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_reduce(hipStream_t stream, uint32_t point0, uint32_t cp, uint32_t cs, uint32_t weight, bool fresh, float near_distance, const float* normals,
+                                const float* rays6, const uint8_t* valid, const float* rgb, const float* tuv, const uint32_t* prim,
+                                uint32_t* out_n, uint32_t* out_hits, uint32_t* out_near, float* out_sum, float* out_sumsq)
+{
+    if (cp == 0) return hipSuccess;
+    hipLaunchKernelGGL(gather_reduce_kernel, dim3((cp + 255u) / 256u), dim3(256), 0, stream, point0, cp, cs, weight, fresh ? 1 : 0, near_distance, normals, rays6, valid, rgb, tuv, prim,
+                       out_n, out_hits, out_near, out_sum, out_sumsq);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_shadow_rays(hipStream_t stream, const DScene& sc, const float* points, uint32_t point0, uint32_t cp, float* rays6)
+{
+    const size_t n = (size_t)cp * sc.nlights;
+    if (n == 0) return hipSuccess;
+    if (n > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gather_shadow_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, sc.lights, sc.nlights, points, point0, cp, rays6);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_direct(hipStream_t stream, const DScene& sc, const float* points, const float* normals, uint32_t point0, uint32_t cp, const uint8_t* blocked, float* direct)
+{
+    if (cp == 0) return hipSuccess;
+    hipLaunchKernelGGL(gather_direct_kernel, dim3((cp + 255u) / 256u), dim3(256), 0, stream, sc.lights, sc.nlights, points, normals, point0, cp, blocked, direct);
     return hipGetLastError();
 }
 

@@ -69,6 +69,18 @@ hipError_t launch_film_stat(hipStream_t stream, bool variances, size_t npix, con
 hipError_t launch_guides(hipStream_t stream, const DScene& sc, const DCamera& cam, uint32_t flags, uint32_t stack_depth, int mode, float4* g0, float4* g1);   // cam.lens: whose centre rays
 // mi355rt_lens_rays: the rays of the next render(spp) under cam.lens, width * height * spp x (pos3, dir3) in mi355rt_render_rays layout, device memory
 hipError_t launch_lens_rays(hipStream_t stream, const DCamera& cam, uint32_t flags, uint32_t seed, uint32_t spp, const uint32_t* film_n, float* rays6);
+// gather.  A chunk: cp points from point0 on x cs samples numbered from `first` on, entry s * cp + i; every pointer is device memory, points /
+// normals / ids / out_* the caller's whole arrays, the rest chunk buffers.  launch_gather_rays: the rays (6 floats), keys (2 words) and validity bytes of the chunk
+hipError_t launch_gather_rays(hipStream_t stream, const DScene& sc, uint32_t seed, const float* points, const float* normals, const uint32_t* ids,
+                              uint32_t point0, uint32_t cp, uint32_t cs, uint32_t first, float* rays6, uint32_t* keys2, uint8_t* valid);
+// per point the chunk's samples in order into n / hits / near / sum / sumsq (any may be null; fresh: they start from 0); weight: MI355RT_GATHER_*; rgb (read for
+// sum / sumsq) and tuv / prim (read for hits / near): the results of the chunk's ray-fed pass
+hipError_t launch_gather_reduce(hipStream_t stream, uint32_t point0, uint32_t cp, uint32_t cs, uint32_t weight, bool fresh, float near_distance, const float* normals,
+                                const float* rays6, const uint8_t* valid, const float* rgb, const float* tuv, const uint32_t* prim,
+                                uint32_t* out_n, uint32_t* out_hits, uint32_t* out_near, float* out_sum, float* out_sumsq);
+// `direct`: the shadow rays of cp points x sc.nlights lights (entry li * cp + i) for launch_intersect's shadow mode, then the sum over the lights per point
+hipError_t launch_gather_shadow_rays(hipStream_t stream, const DScene& sc, const float* points, uint32_t point0, uint32_t cp, float* rays6);
+hipError_t launch_gather_direct(hipStream_t stream, const DScene& sc, const float* points, const float* normals, uint32_t point0, uint32_t cp, const uint8_t* blocked, float* direct);
 // feature film: spp samples of every pixel of the listed rows accumulated into f in sample order; rays6 null: the rays of cam.lens for the keys
 // (p, f.n[p] + s) (flags bit 0: FIX_ROW_INDEX), else the caller's rays in mi355rt_render_rays layout (device memory); mode as launch_intersect
 hipError_t launch_features(hipStream_t stream, const DScene& sc, const DCamera& cam, uint32_t flags, uint32_t seed, uint32_t stack_depth, int mode,

@@ -262,6 +262,23 @@ public:
         if (mi355rt_trace_rays(h_, rays6.data(), keys2, rays6.size() / 6, MI355RT_RAYS_HOST, &out) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
         return rgb;
     }
+    // gather (include/mi355rt.h "GATHER"), host memory: light arriving at points3.size() / 3 points.  normals3 empty: sphere mode; ids empty: i.
+    // The result's vectors are sized for the outputs `direct` asks for beyond n, sum and sumsq; prev non-null: accumulate onto it (cfg.accumulate is set)
+    struct Gathered { std::vector<uint32_t> n; std::vector<float> sum, sumsq, direct; };
+    Gathered gather(const std::vector<float>& points3, const std::vector<float>& normals3, mi355rt_gather_config cfg, bool direct = false,
+                    const std::vector<uint32_t>& ids = {}, const Gathered* prev = nullptr)
+    {
+        const size_t np = points3.size() / 3;
+        Gathered g = prev ? *prev : Gathered{};
+        g.n.resize(np); g.sum.resize(np * 3); g.sumsq.resize(np * 3);
+        if (direct) g.direct.resize(np * 3);
+        cfg.accumulate = prev ? 1u : 0u;
+        mi355rt_gather_outputs out{};
+        out.n = g.n.data(); out.sum = g.sum.data(); out.sumsq = g.sumsq.data(); out.direct = direct ? g.direct.data() : nullptr;
+        if (mi355rt_gather(h_, points3.data(), normals3.empty() ? nullptr : normals3.data(), ids.empty() ? nullptr : ids.data(), np, &cfg, MI355RT_RAYS_HOST, &out) != MI355RT_OK)
+            throw std::runtime_error(mi355rt_last_error(h_));
+        return g;
+    }
     // lens models (include/mi355rt.h): the ray generator of render(); lens_rays: the width*height*spp rays of the next render(spp), host memory
     void set_lens(const mi355rt_lens& lens) { if (mi355rt_set_lens(h_, &lens) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_)); }
     mi355rt_lens lens() const

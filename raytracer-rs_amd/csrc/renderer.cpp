@@ -1648,6 +1648,102 @@ bool Renderer::trace_rays(const float* rays6, const uint32_t* keys2, size_t n, b
     return end_call(n, true);                                         // waits: the staging (and the caller's buffers) are free again
 }
 
+// mi355rt_gather: the points as a film of their own.  Chunks of cp points x cs samples, sized by the pass capacity as trace_rays sizes its
+// passes: gather_rays_kernel makes the chunk's rays, keys and validity bytes, the chunk runs as ONE ray-fed pass (RayFeed mode 2, exactly a pass of trace_rays),
+// gather_reduce_kernel folds its results into the points' outputs.  The sample chunks of a point range go in ascending sample order, on one stream, so every
+// point takes its samples in order.  `direct` is a launch_intersect in shadow mode between two kernels of its own.  Host memory is staged (the outputs go up
+// first when the call accumulates); every temporary is freed on return.
+bool Renderer::gather(const float* points3, const float* normals3, const uint32_t* ids, size_t npoints, const mi355rt_gather_config& gc, bool device, const mi355rt_gather_outputs& out)
+{
+    if (!begin_call()) return false;                                  // settles a speculative frame; a queued frame is ahead on the same stream
+    const bool sums = out.sum || out.sumsq, hitq = out.hits || out.near;
+    const bool sampled = sums || hitq || out.n, traced = sums || hitq;           // n alone needs the walk, not the rays' radiance
+    const size_t total = sampled ? npoints * gc.spp : 0;
+    DeviceBuffer<float> s_points, s_normals, s_sum, s_sumsq, s_direct; DeviceBuffer<uint32_t> s_ids, s_n, s_hits, s_near;
+    const float* d_points = points3; const float* d_normals = normals3; const uint32_t* d_ids = ids;
+    mi355rt_gather_outputs d = out;
+    if (!device) {
+        auto up = [&](auto& buf, const auto* src, size_t bytes, auto& dst) {
+            if (buf.alloc(bytes, &hbm_bytes_) != hipSuccess) return false;
+            dst = buf.get();
+            return hipMemcpyAsync(buf.get(), src, bytes, hipMemcpyHostToDevice, stream_) == hipSuccess;
+        };
+        auto stage = [&](auto& buf, auto*& ptr, size_t bytes, bool accumulates) {
+            if (!ptr) return true;
+            if (buf.alloc(bytes, &hbm_bytes_) != hipSuccess) return false;
+            const bool ok = !(accumulates && gc.accumulate) || hipMemcpyAsync(buf.get(), ptr, bytes, hipMemcpyHostToDevice, stream_) == hipSuccess;
+            ptr = buf.get();
+            return ok;
+        };
+        bool ok = up(s_points, points3, npoints * 12, d_points);
+        if (ok && normals3) ok = up(s_normals, normals3, npoints * 12, d_normals);
+        if (ok && ids) ok = up(s_ids, ids, npoints * 4, d_ids);
+        ok = ok && stage(s_n, d.n, npoints * 4, true) && stage(s_hits, d.hits, npoints * 4, true) && stage(s_near, d.near, npoints * 4, true)
+                && stage(s_sum, d.sum, npoints * 12, true) && stage(s_sumsq, d.sumsq, npoints * 12, true) && stage(s_direct, d.direct, npoints * 12, false);
+        if (!ok) return fail(hipGetLastError(), "mi355rt_gather: staging");
+    }
+    const int imode = mode_ == kModeConfirm ? 0 : mode_ == kModeOctreeWalk ? 1 : 2;
+    if (d.direct) {
+        // (light, point) shadow rays in chunks of at most 4 M rays
+        const size_t cpd = std::min(npoints, std::max<size_t>(1, ((size_t)4 << 20) / std::max(nlights_, 1u)));
+        DeviceBuffer<float> c_rays; DeviceBuffer<uint8_t> c_blocked;
+        if (nlights_) { HIP_TRY(c_rays.alloc(cpd * nlights_ * 24, &hbm_bytes_)); HIP_TRY(c_blocked.alloc(cpd * nlights_, &hbm_bytes_)); }
+        for (size_t p0 = 0; p0 < npoints; p0 += cpd) {
+            const uint32_t cp = (uint32_t)std::min(cpd, npoints - p0);
+            HIP_TRY(launch_gather_shadow_rays(stream_, dscene_, d_points, (uint32_t)p0, cp, c_rays.get()));
+            HIP_TRY(launch_intersect(stream_, dscene_, traversal_rows(), imode, c_rays.get(), cp * nlights_, true, nullptr, nullptr, c_blocked.get()));
+            HIP_TRY(launch_gather_direct(stream_, dscene_, d_points, d_normals, (uint32_t)p0, cp, c_blocked.get(), d.direct));
+        }
+        HIP_TRY(hipStreamSynchronize(stream_));                       // the chunk buffers go out of scope here
+    }
+    if (total) {
+        // rays per chunk: what a pass of trace_rays holds
+        size_t per = (size_t)144 << 20;
+        if (const char* e = getenv("MI355RT_PASS_SAMPLES")) { long v = atol(e); if (v >= 1024) per = (size_t)v; }
+        if (cfg.samples_per_pass) per = std::max<size_t>(1, (size_t)cfg.samples_per_pass * cfg.width * cfg.height);
+        per = std::min(per, total);
+        Slice& sl = slices_[0];
+        while (traced && !ensure_pass_capacity(sl, per)) {
+            if (!alloc_failed_ || per <= 1024) return false;
+            (void)hipGetLastError();
+            per /= 2;
+        }
+        const size_t cp_max = std::min(npoints, per), cs_max = std::max<size_t>(1, std::min<size_t>(gc.spp, per / cp_max));
+        const size_t cap = cp_max * cs_max;
+        DeviceBuffer<float> c_rays, c_rgb, c_tuv; DeviceBuffer<uint32_t> c_keys, c_prim; DeviceBuffer<uint8_t> c_valid; DeviceBuffer<float4> c_hit;
+        HIP_TRY(c_rays.alloc(cap * 24, &hbm_bytes_));
+        HIP_TRY(c_keys.alloc(cap * 8, &hbm_bytes_));
+        HIP_TRY(c_valid.alloc(cap, &hbm_bytes_));
+        if (sums) HIP_TRY(c_rgb.alloc(cap * 12, &hbm_bytes_));
+        if (hitq) { HIP_TRY(c_tuv.alloc(cap * 12, &hbm_bytes_)); HIP_TRY(c_prim.alloc(cap * 4, &hbm_bytes_)); HIP_TRY(c_hit.alloc(cap * sizeof(float4), &hbm_bytes_)); }
+        for (size_t p0 = 0; p0 < npoints; p0 += cp_max) {
+            const uint32_t cp = (uint32_t)std::min(cp_max, npoints - p0);
+            for (uint32_t s0 = 0; s0 < gc.spp; s0 += (uint32_t)cs_max) {
+                const uint32_t cs = (uint32_t)std::min<size_t>(cs_max, gc.spp - s0);
+                HIP_TRY(launch_gather_rays(stream_, dscene_, (uint32_t)cfg.seed, d_points, d_normals, d_ids, (uint32_t)p0, cp, cs, gc.first_sample + s0, c_rays.get(), c_keys.get(), c_valid.get()));
+                if (traced) {
+                    RayFeed f{};
+                    f.mode = 2u; f.rays = c_rays.get(); f.keys = c_keys.get(); f.base = 0u; f.count = cp * cs; f.hit = c_hit.get();
+                    f.rgb = c_rgb.get(); f.tuv = c_tuv.get(); f.prim = c_prim.get();
+                    if (!run_pass(sl, nullptr, 0, 0, 1, false, 0, 0, 0xFFFFFFFFu, nullptr, &f)) return false;
+                }
+                HIP_TRY(launch_gather_reduce(stream_, (uint32_t)p0, cp, cs, gc.weight, !gc.accumulate && s0 == 0, gc.near_distance, d_normals, c_rays.get(), c_valid.get(),
+                                             c_rgb.get(), c_tuv.get(), c_prim.get(), d.n, d.hits, d.near, d.sum, d.sumsq));
+            }
+        }
+        HIP_TRY(hipStreamSynchronize(stream_));                       // the chunk buffers go out of scope here
+    }
+    if (!device) {
+        if (total && out.n) HIP_TRY(hipMemcpyAsync(out.n, d.n, npoints * 4, hipMemcpyDeviceToHost, stream_));
+        if (total && out.hits) HIP_TRY(hipMemcpyAsync(out.hits, d.hits, npoints * 4, hipMemcpyDeviceToHost, stream_));
+        if (total && out.near) HIP_TRY(hipMemcpyAsync(out.near, d.near, npoints * 4, hipMemcpyDeviceToHost, stream_));
+        if (total && out.sum) HIP_TRY(hipMemcpyAsync(out.sum, d.sum, npoints * 12, hipMemcpyDeviceToHost, stream_));
+        if (total && out.sumsq) HIP_TRY(hipMemcpyAsync(out.sumsq, d.sumsq, npoints * 12, hipMemcpyDeviceToHost, stream_));
+        if (out.direct) HIP_TRY(hipMemcpyAsync(out.direct, d.direct, npoints * 12, hipMemcpyDeviceToHost, stream_));
+    }
+    return end_call(traced ? total : 0, true);                        // waits: the staging (and the caller's buffers) are free again
+}
+
 // mi355rt_render_rays: mi355rt_render whose passes read their primary rays from the caller's buffer, indexed by the CALL's sample number (enqueue_frame hands
 // every pass its base).  Only the rays of owned rows are read, so a host buffer is staged whole but a striped handle never looks at the rest.
 bool Renderer::render_rays(const float* rays6, uint32_t spp, bool device)

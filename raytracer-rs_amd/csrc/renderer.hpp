@@ -45,6 +45,8 @@ public:
     // caller-supplied rays; the caller has checked the arguments.  device: every pointer is device memory of this handle's device
     bool trace_rays(const float* rays6, const uint32_t* keys2, size_t n, bool device, const mi355rt_ray_outputs& out);
     bool render_rays(const float* rays6, uint32_t spp, bool device);
+    // gather: light arriving at npoints caller-given points; the caller has checked the arguments.  device: every pointer is device memory
+    bool gather(const float* points3, const float* normals3, const uint32_t* ids, size_t npoints, const mi355rt_gather_config& gc, bool device, const mi355rt_gather_outputs& out);
     // lens models; the caller has checked the arguments.  set_lens keeps the film, the caller-ray mark, the counters and current_row
     bool set_lens(const mi355rt_lens& l);
     const mi355rt_lens& lens() const { return lens_; }
