@@ -396,6 +396,11 @@ typedef struct mi355rt_display_config {
 
 /* source FILM, CURVE_REINHARD, TRANSFER_REFERENCE, auto_exposure 0, exposure 1, white 4, key 0.18 (the usual middle grey), low 0, high 1 */
 void mi355rt_display_default_config(mi355rt_display_config* cfg);
+/* DISPLAY MAPPING of an image that is no film (a baked atlas): npix x 3 floats of host memory -> packed 0xAARRGGBB, by the kernel and with the rules of
+ * mi355rt_get_display_pixels at the fixed exposure cfg->exposure; cfg->source is not read; cfg == NULL: exposure 1, the Reinhard curve and the reference's
+ * transfer, i.e. mi355rt_get_tonemapped_pixels' map.  Every buffer is a temporary of the call; nothing of the handle changes.  MI355RT_E_INVALID for a device
+ * group, an invalid config, auto_exposure (it reads a film source's histogram), NULL pointers with npix > 0, npix > 2^28. */
+int mi355rt_display_image(mi355rt_handle* h, const float* rgb3, size_t npix, const mi355rt_display_config* cfg /* may be NULL */, uint32_t* packed);
 int mi355rt_display_histogram(mi355rt_handle* h, uint32_t source, const mi355rt_denoise_config* dn, mi355rt_luminance_histogram* out);
 int mi355rt_display_auto_exposure(const mi355rt_luminance_histogram* hist, float key, float low, float high, float* exposure);   /* HOST only */
 int mi355rt_display_srgb_thresholds(float out[255]);                                                                             /* HOST only */
@@ -800,6 +805,62 @@ int  mi355rt_gather(mi355rt_handle* h, const float* points3, const float* normal
                     size_t npoints, const mi355rt_gather_config* cfg, uint32_t where, const mi355rt_gather_outputs* out);
 int  mi355rt_gather_ray(const float* table3 /* 65536 x 3 */, uint32_t seed, const float point[3], const float* normal3 /* may be NULL */,
                         uint32_t id, uint32_t sampleno, float ray6[6], uint32_t* valid);
+
+/* ---- BAKE: UV charts to surface points, and per-point values back into an atlas with filled borders (no reference counterpart).
+ * A lightmap bake is mi355rt_bake_texels, then mi355rt_gather at the points it lists, then mi355rt_bake_atlas.  raytracer-rs_amd/bake.py states all of it.
+ *
+ * TEXELS.  uv: ntri x 3 x 2 floats, one UV triangle (a, b, c) per scene triangle in scene order; u runs to the right and v downwards; texel (x, y) has
+ * index y * width + x and its centre at (x + 0.5, y + 0.5).  f32, unfused, in the order written:
+ *     px_k = u_k * (float)width,  py_k = v_k * (float)height;   cx = (float)x + 0.5f,  cy = (float)y + 0.5f
+ *     edge(p, q) = (px_p - cx) * (py_q - cy) - (py_p - cy) * (px_q - cx);   e0 = edge(b, c), e1 = edge(c, a), e2 = edge(a, b), s = (e0 + e1) + e2
+ *     covered <=> ((e0 >= 0 && e1 >= 0 && e2 >= 0) || (e0 <= 0 && e1 <= 0 && e2 <= 0)) && s != 0
+ *                 && floor(min px) - 1 <= x <= floor(max px) + 1 && floor(min py) - 1 <= y <= floor(max py) + 1           (THE BOX)
+ *     owner(x, y) = the LOWEST triangle index that covers the texel, 0xFFFFFFFF if none;   u = e1 / s,  v = e2 / s  (the hit record's u, v)
+ *     P = (A + u * (B - A)) + v * (C - A) per component, A B C the triangle's vertices as given at create
+ * The edge functions are relative to the centre, so edge(p, q) == -edge(q, p) exactly: two triangles that share an edge with the same UV bits never both
+ * reject a centre because of it.  Both windings count (mirrored charts).  A triangle with a NaN or infinite px or py covers nothing; triangles off the atlas are cut by it, nothing
+ * is clamped.  THE BOX holds every exactly covered centre with a texel to spare; it keeps a sliver from claiming a far centre that only the rounding of
+ * its edge functions gives it, and it is what lets the device bin the triangles.
+ * Outputs (any may be NULL, not all of them and ncovered): owner u32 [w * h]; bary f32 [w * h * 2], untouched where uncovered; and the compact lists of
+ * the covered texels in ascending texel index, which the caller sizes for w * h entries: ids (the texel index: the gather's key, so a bake does not depend on
+ * chart order or chunking), points3, normals3 (the triangle's normal as shading uses it, calc_normal mod.rs:198-205; flip != 0: negated), albedo3 (the
+ * material's diffuse colour, or its texture's texel at (u, v) as texture.rs:21-27 fetches it).  *ncovered: their length.
+ * `where` as for mi355rt_gather: every pointer but ncovered is host memory, staged, or device memory used in place on the handle's stream.
+ *
+ * ATLAS.  ids[n] (texel indices), values3[n x 3] -> atlas f32 [w * h * 3] and valid u8 [w * h] (either may be NULL, not both): the values scattered, 0
+ * elsewhere, valid 1 where scattered.  Then `dilate` times, from the PREVIOUS iteration's image: an empty texel with a non-empty 8-neighbour becomes
+ * (((v0 + v1) + v2) + ...) / (float)count over the neighbours that exist and are not empty, in the order N, W, E, S, NW, NE, SW, SE (N is y - 1), f32 with one
+ * division; its valid becomes 1 + k in iteration k = 1, 2, ..., saturating at 255.  The atlas borders do not wrap.  An empty texel that can be filled
+ * at all is filled by iteration max(w, h) - 1, so min(dilate, max(w, h) - 1) iterations are run: the result is that of `dilate` iterations.
+ *
+ * AROUND THE CALLS.  A speculative frame is settled first and a queued one runs ahead; film, direct film, light films, feature film, camera, lens, current
+ * row, caller-ray mark, guides and mi355rt_last_counts are untouched.  Every temporary is freed by the end of the call; the first mi355rt_bake_texels that
+ * asks for points3 keeps 36 bytes per triangle (A, B - A, C - A in scene order) on the device for the handle's life, counted in mi355rt_hbm_allocated_bytes.
+ * Striped handles serve both calls (a bake is no part of the image).
+ *
+ * ERRORS.  MI355RT_E_INVALID, the argument named in mi355rt_last_error and nothing written, for: a device group; an unknown `where`; width or height 0 or
+ * above 16384; uv NULL on a scene with triangles; every output NULL; ids or values3 NULL with n > 0; n > width * height; an id >= width * height; an id
+ * named twice (the order of the two would decide the texel).
+ *
+ * mi355rt_bake_texel: TEXELS for one triangle and one texel on the host, no handle: the same header the kernels compile (csrc/bake_raster.hpp).
+ * *covered: 0 or 1; bary2 = (u, v) when covered, else untouched.  mi355rt_bake_point: P of one component, (a + u * e1) + v * e2.
+ * mi355rt_bake_dilate_texel: one dilation step for the empty texel (x, y) of an image on the host; returns the count, rgb3 written when it is not 0.
+ *
+ * mi355rt_bake_auto_atlas: a chart for a mesh that has none, host only.  Two triangles per square cell of *cell texels, cells row by row from the top
+ * left, cell the largest that fits ceil(ntri / 2) cells into the atlas.  With g = gutter, L = cell - 2 g, d = max(g - 0.5, 0.5), leg = L - d, (ox, oy) the
+ * cell's corner, in texels:  even i: (ox + g, oy + g), (ox + g + leg, oy + g), (ox + g, oy + g + leg);  odd i: (ox + cell - g, oy + cell - g),
+ * (ox + cell - g - leg, oy + cell - g), (ox + cell - g, oy + cell - g - leg);  uv = texels / (float)size.  No texel is claimed twice, texels of different
+ * triangles are at least max(gutter, 1) apart (Chebyshev), of different cells 2 gutter + 1.  Refused (MI355RT_E_INVALID, mi355rt_last_error(NULL)) when
+ * L < 1 + d: a half would own no texel. */
+typedef struct mi355rt_bake_texel_outputs { uint32_t *owner; float *bary; uint32_t *ids; float *points, *normals, *albedo; } mi355rt_bake_texel_outputs;
+int  mi355rt_bake_texels(mi355rt_handle* h, const float* uv, uint32_t width, uint32_t height, uint32_t flip, uint32_t where,
+                         const mi355rt_bake_texel_outputs* out, uint32_t* ncovered /* host memory; may be NULL */);
+int  mi355rt_bake_atlas(mi355rt_handle* h, const uint32_t* ids, const float* values3, size_t n, uint32_t width, uint32_t height, uint32_t dilate, uint32_t where,
+                        float* atlas /* may be NULL */, uint8_t* valid /* may be NULL */);
+int  mi355rt_bake_texel(const float uv6[6], uint32_t width, uint32_t height, uint32_t x, uint32_t y, uint32_t* covered, float bary2[2]);
+float mi355rt_bake_point(float a, float e1, float e2, float u, float v);
+uint32_t mi355rt_bake_dilate_texel(const float* atlas3, const uint8_t* valid, uint32_t width, uint32_t height, uint32_t x, uint32_t y, float rgb3[3]);
+int  mi355rt_bake_auto_atlas(uint32_t ntri, uint32_t width, uint32_t height, uint32_t gutter, float* uv /* ntri x 6 */, uint32_t* cell /* may be NULL */);
 
 /* SampleGenerator table, sample_generator.rs:15-24: 65 536 x 3 floats */
 int mi355rt_get_sample_table(const mi355rt_handle* h, float* out);

@@ -168,6 +168,13 @@ class GatherOutputs(C.Structure):
 
 GATHER_OUTPUTS = ("n", "hits", "near", "sum", "sumsq", "direct")
 
+class BakeTexelOutputs(C.Structure):
+    """mi355rt_bake_texel_outputs: any pointer may be NULL (void pointers here: host arrays or device addresses)"""
+    _fields_ = [("owner", C.c_void_p), ("bary", C.c_void_p), ("ids", C.c_void_p), ("points", C.c_void_p), ("normals", C.c_void_p), ("albedo", C.c_void_p)]
+
+
+BAKE_TEXEL_OUTPUTS = ("owner", "bary", "ids", "points", "normals", "albedo")
+
 LENS_PINHOLE, LENS_THIN, LENS_ORTHO = 0, 1, 2      # MI355RT_LENS_*
 LENS_MODELS = {"pinhole": LENS_PINHOLE, "thin": LENS_THIN, "ortho": LENS_ORTHO}
 
@@ -213,6 +220,7 @@ ABI = [
     ("mi355rt_display_auto_exposure", C.c_int, [C.POINTER(LuminanceHistogram), C.c_float, C.c_float, C.c_float, _F]),
     ("mi355rt_display_srgb_thresholds", C.c_int, [_F]),
     ("mi355rt_get_display_pixels", C.c_int, [_H, C.POINTER(DisplayConfig), C.POINTER(DenoiseConfig), _U, C.c_size_t, _F]),
+    ("mi355rt_display_image", C.c_int, [_H, _F, C.c_size_t, C.POINTER(DisplayConfig), _U]),
     ("mi355rt_get_tonemapped_pixels", C.c_int, [_H, _U, C.c_size_t]),
     ("mi355rt_tonemap_owned_rows_device", C.c_int, [_H, C.c_void_p, C.c_size_t]),
     ("mi355rt_tonemap_owned_rows_device_on_stream", C.c_int, [_H, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -243,6 +251,12 @@ ABI = [
     ("mi355rt_gather_default_config", None, [C.POINTER(GatherConfig)]),
     ("mi355rt_gather", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(GatherConfig), C.c_uint32, C.POINTER(GatherOutputs)]),
     ("mi355rt_gather_ray", C.c_int, [_F, C.c_uint32, _F, _F, C.c_uint32, C.c_uint32, _F, _U]),
+    ("mi355rt_bake_texels", C.c_int, [_H, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(BakeTexelOutputs), _U]),
+    ("mi355rt_bake_atlas", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("mi355rt_bake_texel", C.c_int, [_F, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _U, _F]),
+    ("mi355rt_bake_point", C.c_float, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
+    ("mi355rt_bake_dilate_texel", C.c_uint32, [_F, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _F]),
+    ("mi355rt_bake_auto_atlas", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _F, _U]),
     ("mi355rt_lens_default", None, [C.POINTER(Lens)]),
     ("mi355rt_set_lens", C.c_int, [_H, C.POINTER(Lens)]),
     ("mi355rt_get_lens", C.c_int, [_H, C.POINTER(Lens)]),
@@ -759,6 +773,18 @@ class RayTracer:
         self._check(lib().mi355rt_get_display_pixels(self._h, C.byref(c), C.byref(d) if d is not None else None, _up(out), out.size, C.byref(used)))
         return out, np.float32(used.value)
 
+    def display_image(self, rgb, **cfg):
+        """mi355rt_display_image: the display mapping of an image that is no film (a baked atlas).  rgb: float32 (npix, 3), a numpy array; cfg: display config
+        fields (exposure, curve, transfer, white; auto_exposure is refused); none given: the reference's tone map, as get_tonemapped_pixels.  Returns packed
+        uint32[npix] 0xAARRGGBB."""
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        if rgb.ndim != 2 or rgb.shape[1] != 3:
+            raise ValueError("rgb: shape must be (npix, 3), not %s" % (rgb.shape,))
+        c = display_config(**cfg) if cfg else None
+        out = np.zeros(rgb.shape[0], np.uint32)
+        self._check(lib().mi355rt_display_image(self._h, _fp(rgb), rgb.shape[0], C.byref(c) if c is not None else None, _up(out)))
+        return out
+
     def get_relit_pixels(self, weights, rgb=False, **display_cfg):
         """mi355rt_get_relit_pixels (a handle created with FLAG_LIGHT_FILMS): the frame with light li's colour scaled by weights[li], mixed from the light
         films without tracing.  weights: [nlights] scalars or [nlights, 3] RGB factors.  display_cfg: display config fields (source stays the film); none
@@ -966,6 +992,104 @@ class RayTracer:
             torch.cuda.current_stream(points.device).synchronize()          # what produced the inputs (and the zero fill) has finished: the library's stream knows nothing of torch's
         self._check(lib().mi355rt_gather(self._h, addr, naddr, iaddr, n, C.byref(cfg), RAYS_DEVICE if dev else RAYS_HOST, C.byref(o)))
         return res
+
+    def bake_texels(self, uv, width, height, flip=False, want=BAKE_TEXEL_OUTPUTS):
+        """mi355rt_bake_texels: the UV charts of the scene's triangles rasterised into an atlas of width x height texels (raytracer_rs_amd.bake.texels is the
+        statement).  uv: float32 (ntri, 3, 2), one UV triangle per scene triangle, u to the right and v downwards; a numpy array (host, results numpy arrays)
+        or a torch tensor on the handle's GPU (read in place, results tensors there, uint32 as torch.int32 holding the same bits).  flip: the lists' normals
+        negated.  want: any of "owner", "bary", "ids", "points", "normals", "albedo".  Returns a dict: owner uint32 (width * height,), the lowest triangle
+        index covering the texel's centre or 0xFFFFFFFF; bary float32 (width * height, 2), 0 where uncovered; the compact lists of the covered texels in
+        ascending texel index, ids uint32 (n,) (the texel index: the key gather should sample under), points / normals / albedo float32 (n, 3); "ncovered".
+        No film, camera or lens state changes."""
+        want = tuple(want)
+        if any(w not in BAKE_TEXEL_OUTPUTS for w in want) or len(set(want)) != len(want):
+            raise ValueError("want: a selection of %s without repeats, not %r" % (BAKE_TEXEL_OUTPUTS, want))
+        width, height = int(width), int(height)
+        if not (1 <= width <= 16384 and 1 <= height <= 16384):
+            raise ValueError("width and height must be 1 .. 16384")
+        if (_is_tensor(uv) or isinstance(uv, np.ndarray)) and len(uv.shape) == 3 and tuple(uv.shape[1:]) == (3, 2):
+            if not (uv.is_contiguous() if _is_tensor(uv) else uv.flags["C_CONTIGUOUS"]):
+                raise ValueError("uv: must be C-contiguous")             # before the reshape, which would copy
+            addr, _, dev = _ray_array(uv.reshape(-1, 6), "uv", 6, np.float32, rows=int(self.triangle_count))
+        elif _is_tensor(uv) or isinstance(uv, np.ndarray):
+            raise ValueError("uv: shape must be (%d, 3, 2), not %s" % (int(self.triangle_count), tuple(uv.shape)))
+        else:
+            raise TypeError("uv: a numpy array or a torch tensor, not %s" % type(uv).__name__)
+        nt = width * height
+        shapes = {"owner": ((nt,), np.uint32), "bary": ((nt, 2), np.float32), "ids": ((nt,), np.uint32), "points": ((nt, 3), np.float32),
+                  "normals": ((nt, 3), np.float32), "albedo": ((nt, 3), np.float32)}
+        res, o = {}, BakeTexelOutputs()
+        if dev:
+            import torch
+        for w in want:
+            shape, dt = shapes[w]
+            if dev:
+                a = torch.zeros(shape, dtype=torch.float32 if dt == np.float32 else torch.int32, device=uv.device)
+                setattr(o, w, a.data_ptr())
+            else:
+                a = np.zeros(shape, dt)
+                setattr(o, w, a.ctypes.data)
+            res[w] = a
+        if dev:
+            torch.cuda.current_stream(uv.device).synchronize()          # what produced uv (and the zero fill) has finished: the library's stream knows nothing of torch's
+        n = C.c_uint32(0)
+        self._check(lib().mi355rt_bake_texels(self._h, addr, width, height, 1 if flip else 0, RAYS_DEVICE if dev else RAYS_HOST, C.byref(o), C.byref(n)))
+        for w in ("ids", "points", "normals", "albedo"):
+            if w in res:
+                res[w] = res[w][:n.value]
+        res["ncovered"] = int(n.value)
+        return res
+
+    def bake_atlas(self, ids, values, width, height, dilate=2):
+        """mi355rt_bake_atlas: per-texel values back into an image, chart borders filled (raytracer_rs_amd.bake.atlas is the statement).  ids: uint32 (n,) texel
+        indices; values: float32 (n, 3); numpy arrays or torch tensors on the handle's GPU, both alike.  dilate: iterations in which an empty texel takes the
+        mean of its non-empty 8-neighbours.  Returns (atlas float32 (width * height, 3), valid uint8 (width * height,)): valid 0 empty, 1 given, 1 + k filled
+        in iteration k.  Ids outside the atlas and repeated ids are refused with nothing written."""
+        width, height, dilate = int(width), int(height), int(dilate)
+        if not (1 <= width <= 16384 and 1 <= height <= 16384):
+            raise ValueError("width and height must be 1 .. 16384")
+        if not 0 <= dilate <= 0xFFFFFFFF:
+            raise ValueError("dilate must be 0 .. 2^32 - 1")
+        vaddr, n, dev = _ray_array(values, "values", 3, np.float32)
+        iaddr, _, idev = _ray_vector(ids, "ids", np.uint32, n)
+        if idev != dev:
+            raise ValueError("ids must live where values live (both numpy arrays, or both tensors on the GPU)")
+        nt = width * height
+        if dev:
+            import torch
+            atlas = torch.zeros((nt, 3), dtype=torch.float32, device=values.device); valid = torch.zeros(nt, dtype=torch.uint8, device=values.device)
+            aaddr, daddr = atlas.data_ptr(), valid.data_ptr()
+            torch.cuda.current_stream(values.device).synchronize()
+        else:
+            atlas = np.zeros((nt, 3), np.float32); valid = np.zeros(nt, np.uint8)
+            aaddr, daddr = atlas.ctypes.data, valid.ctypes.data
+        self._check(lib().mi355rt_bake_atlas(self._h, iaddr, vaddr, n, width, height, dilate, RAYS_DEVICE if dev else RAYS_HOST, aaddr, daddr))
+        return atlas, valid
+
+    def bake(self, uv, width, height, spp=16, weight="mean", dilate=2, first_sample=0, into=None, flip=False):
+        """A lightmap bake: bake_texels, then gather(points, normals, ids, spp, first_sample, weight, want=("n", "sum", "sumsq", "direct")) at the covered
+        texels' points under the texel index as the key, then bake_atlas of three per-texel values (raytracer_rs_amd.bake states each):
+            direct     the unshadowed point-light term
+            indirect   sum / n
+            radiance   albedo * direct + indirect (f32, elementwise): under weight "mean" what the reference's compute_radiance shows at the point without
+                       the view-dependent highlight
+        into: the dict an earlier bake of the same charts returned; its gather sums are added to, so bake(spp=3) then bake(spp=5, first_sample=3, into=...)
+        is bake(spp=8) bit for bit.  Returns dict(texels=..., gather=..., direct=, indirect=, radiance= (atlas, valid) pairs)."""
+        tex = self.bake_texels(uv, width, height, flip=flip)
+        prev = None if into is None else into["gather"]
+        g = self.gather(tex["points"], tex["normals"], tex["ids"], spp=spp, first_sample=first_sample, weight=weight, want=("n", "sum", "sumsq", "direct"), into=prev)
+        if _is_tensor(uv):
+            import torch
+            ind = g["sum"] / g["n"].to(torch.float32)[:, None]             # n as int32 bits: counts stay far below 2^31
+            rad = tex["albedo"] * g["direct"] + ind
+        else:
+            with np.errstate(all="ignore"):
+                ind = (g["sum"] / g["n"].astype(np.float32)[:, None]).astype(np.float32)
+                rad = (tex["albedo"] * g["direct"] + ind).astype(np.float32)
+        out = dict(texels=tex, gather=g)
+        for name, val in (("direct", g["direct"]), ("indirect", ind), ("radiance", rad)):
+            out[name] = self.bake_atlas(tex["ids"], val.contiguous() if _is_tensor(val) else np.ascontiguousarray(val), width, height, dilate=dilate)
+        return out
 
     def render_rays(self, rays6, spp):
         """mi355rt_render_rays: mi355rt_render with the caller's rays.  rays6: float32 (width * height * spp, 6), row s * npix + p = the ray of the call's

@@ -11,6 +11,7 @@
 #include "octree.hpp"
 #include "reflmask.hpp"
 #include "../../include/mi355rt.h"
+#include "bake_raster.hpp"
 #include "gather_walk.hpp"
 #include "group.hpp"
 #include "lens.hpp"
@@ -619,6 +620,21 @@ int mi355rt_get_display_pixels(mi355rt_handle* h, const mi355rt_display_config* 
     return MI355RT_OK;
 }
 
+int mi355rt_display_image(mi355rt_handle* h, const float* rgb3, size_t npix, const mi355rt_display_config* cfg, uint32_t* packed)
+{
+    if (!h) return MI355RT_E_INVALID;
+    const char* e = nullptr;
+    if (h->g->size() > 1) e = "not available on a device group (config.device_count > 1)";
+    else if (cfg && (e = display_config_error(cfg)) != nullptr) {}
+    else if (cfg && cfg->auto_exposure) e = "auto_exposure reads the histogram of a film source; an image takes a fixed exposure";
+    else if (npix && !rgb3) e = "rgb3 is NULL";
+    else if (npix && !packed) e = "packed is NULL";
+    else if (npix > ((size_t)1 << 28)) e = "npix must be <= 2^28";
+    if (e) { h->r->last_error = std::string("mi355rt_display_image: ") + e; return MI355RT_E_INVALID; }
+    if (npix == 0) return MI355RT_OK;
+    return h->r->display_image(rgb3, npix, cfg, packed) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
 int mi355rt_get_tonemapped_pixels(mi355rt_handle* h, uint32_t* out, size_t n)
 {
     if (!h) return MI355RT_E_INVALID;
@@ -879,6 +895,69 @@ int mi355rt_gather_ray(const float* table3, uint32_t seed, const float point[3],
     gather_ray_from(point, d, ray6);
     ray6[3] = d.x; ray6[4] = d.y; ray6[5] = d.z;
     if (valid) *valid = ok ? 1u : 0u;
+    return MI355RT_OK;
+}
+
+int mi355rt_bake_texels(mi355rt_handle* h, const float* uv, uint32_t width, uint32_t height, uint32_t flip, uint32_t where, const mi355rt_bake_texel_outputs* out, uint32_t* ncovered)
+{
+    if (!h) return MI355RT_E_INVALID;
+    const char* e = nullptr;
+    if (h->g->size() > 1) e = "not available on a device group (config.device_count > 1)";
+    else if (where > MI355RT_RAYS_DEVICE) e = "unknown `where` (MI355RT_RAYS_HOST or MI355RT_RAYS_DEVICE)";
+    else if (width == 0 || height == 0 || width > 16384u || height > 16384u) e = "width and height must be 1 .. 16384";
+    else if (!uv && h->r->ntri) e = "uv is NULL";
+    else if (!ncovered && (!out || (!out->owner && !out->bary && !out->ids && !out->points && !out->normals && !out->albedo))) e = "out is NULL or every output pointer in it is NULL, and ncovered is NULL";
+    if (e) { h->r->last_error = std::string("mi355rt_bake_texels: ") + e; return MI355RT_E_INVALID; }
+    const mi355rt_bake_texel_outputs none{};
+    return h->r->bake_texels(uv, width, height, flip != 0, where == MI355RT_RAYS_DEVICE, out ? *out : none, ncovered) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_bake_atlas(mi355rt_handle* h, const uint32_t* ids, const float* values3, size_t n, uint32_t width, uint32_t height, uint32_t dilate, uint32_t where, float* atlas, uint8_t* valid)
+{
+    if (!h) return MI355RT_E_INVALID;
+    const char* e = nullptr;
+    if (h->g->size() > 1) e = "not available on a device group (config.device_count > 1)";
+    else if (where > MI355RT_RAYS_DEVICE) e = "unknown `where` (MI355RT_RAYS_HOST or MI355RT_RAYS_DEVICE)";
+    else if (width == 0 || height == 0 || width > 16384u || height > 16384u) e = "width and height must be 1 .. 16384";
+    else if (!atlas && !valid) e = "atlas and valid are both NULL";
+    else if (n && !ids) e = "ids is NULL";
+    else if (n && !values3) e = "values3 is NULL";
+    else if (n > (size_t)width * height) e = "more ids than the atlas has texels: one is named twice";
+    if (e) { h->r->last_error = std::string("mi355rt_bake_atlas: ") + e; return MI355RT_E_INVALID; }
+    uint32_t verdict = 0;
+    if (!h->r->bake_atlas(ids, values3, (uint32_t)n, width, height, dilate, where == MI355RT_RAYS_DEVICE, atlas, valid, verdict)) return MI355RT_E_HIP;
+    if (verdict) {
+        h->r->last_error = (verdict & 1u) ? "mi355rt_bake_atlas: an id is >= width * height" : "mi355rt_bake_atlas: an id is named twice (the order of the two would decide the texel)";
+        return MI355RT_E_INVALID;
+    }
+    return MI355RT_OK;
+}
+
+int mi355rt_bake_texel(const float uv6[6], uint32_t width, uint32_t height, uint32_t x, uint32_t y, uint32_t* covered, float bary2[2])
+{
+    if (!uv6) return bad("mi355rt_bake_texel: uv6 is NULL");
+    if (!covered) return bad("mi355rt_bake_texel: covered is NULL");
+    if (width == 0 || height == 0 || width > 16384u || height > 16384u) return bad("mi355rt_bake_texel: width and height must be 1 .. 16384");
+    if (x >= width || y >= height) return bad("mi355rt_bake_texel: the texel is outside the atlas");
+    const BakeTri t = bake_tri(uv6, width, height);
+    const BakeEdges e = bake_edges(t, x, y);
+    *covered = bake_in_box(t, width, height, x, y) && bake_covered(e) ? 1u : 0u;
+    if (*covered && bary2) { bary2[0] = e.e1 / e.s; bary2[1] = e.e2 / e.s; }
+    return MI355RT_OK;
+}
+
+float mi355rt_bake_point(float a, float e1, float e2, float u, float v) { return bake_point(a, e1, e2, u, v); }
+
+uint32_t mi355rt_bake_dilate_texel(const float* atlas3, const uint8_t* valid, uint32_t width, uint32_t height, uint32_t x, uint32_t y, float rgb3[3])
+{
+    if (!atlas3 || !valid || !rgb3 || x >= width || y >= height) return 0u;
+    return bake_dilate_texel([valid](size_t i) { return valid[i] != 0; }, [atlas3](size_t i, int c) { return atlas3[3 * i + c]; }, width, height, x, y, rgb3);
+}
+
+int mi355rt_bake_auto_atlas(uint32_t ntri, uint32_t width, uint32_t height, uint32_t gutter, float* uv, uint32_t* cell)
+{
+    if (!uv) return bad("mi355rt_bake_auto_atlas: uv is NULL");
+    if (const char* why = bake_auto_atlas(ntri, width, height, gutter, uv, cell)) { g_create_error = std::string("mi355rt_bake_auto_atlas: ") + why; return MI355RT_E_INVALID; }
     return MI355RT_OK;
 }
 

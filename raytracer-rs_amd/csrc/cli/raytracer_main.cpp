@@ -29,6 +29,10 @@
 // option, A = (uint32_t)(alpha * 255.0f + 0.5f) of mi355rt_features_alpha; the colour is premultiplied by construction, because a miss is black.
 // Light films (MI355RT_FLAG_LIGHT_FILMS): --light-films keeps a film per light; --relight W0,W1,... writes the frame with light i scaled by Wi to --out
 // (mi355rt_get_relit_pixels, no tracing; the display options apply); --out-lights PREFIX writes PREFIX<i>.png, light i alone at weight 1.
+// Bake (mi355rt_bake_texels, mi355rt_gather, mi355rt_bake_atlas): --bake W,H with --spp N and --out writes a lightmap instead of a frame: the auto
+// atlas (mi355rt_bake_auto_atlas, gutter 1) of W x H texels, N gather samples per covered texel, radiance = albedo * direct + sum / n, --bake-dilate K (default 2)
+// dilation steps, packed by mi355rt_display_image under the display options (without them: the reference's tone map).  --bake-uv-out FILE also writes the UVs,
+// ntri x 6 floats, raw little-endian f32.  --auto-exposure is refused (an atlas has no film histogram), as is everything that renders or reads a frame.
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -145,6 +149,10 @@ int main(int argc, char** argv)
     bool light_films = false, have_relight = false;
     std::vector<float> relight;
     std::string out_lights;
+    bool have_bake = false;
+    unsigned long long bake_w = 0, bake_h = 0;
+    size_t bake_dilate = 2;
+    std::string bake_uv_out;
     auto parse_float = [](const char* s, float& out) { if (!s || !*s) return false; char* end = nullptr; const float f = std::strtof(s, &end); if (*end != '\0' || !std::isfinite(f)) return false; out = f; return true; };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -214,6 +222,14 @@ int main(int argc, char** argv)
             }
             have_relight = true;
         }
+        else if (a == "--bake") {
+            const char* r = take();
+            char tail = 0;
+            if (!r || std::sscanf(r, "%llu,%llu%c", &bake_w, &bake_h, &tail) != 2 || r[0] == '-') { std::fprintf(stderr, "Error: --bake takes W,H\n"); return 1; }
+            have_bake = true;
+        }
+        else if (a == "--bake-dilate") { size_t t; if (parse_usize(take(), t)) bake_dilate = t; }
+        else if (a == "--bake-uv-out") { if (v) bake_uv_out = take(); }
         else if (a == "--refine") { float f; if (parse_float(take(), f)) { acfg.rel_error = f; refine = true; } }
         else if (a == "--region") {
             const char* r = take();
@@ -250,7 +266,11 @@ int main(int argc, char** argv)
                         "                 [--light-films]   (the handle keeps a film per light, MI355RT_FLAG_LIGHT_FILMS: needs --spp, --adaptive or --refine; excludes --gpus)\n"
                         "                 [--relight W0,W1,...]   (needs --light-films: --out receives the frame with light i's colour scaled by Wi, mixed from the light films\n"
                         "                                     without tracing, mi355rt_get_relit_pixels; the display options apply; excludes --denoise, --denoise-split)\n"
-                        "                 [--out-lights PREFIX]   (needs --light-films: PREFIX<i>.png, light i alone at weight 1, under the same display options)\n");
+                        "                 [--out-lights PREFIX]   (needs --light-films: PREFIX<i>.png, light i alone at weight 1, under the same display options)\n"
+                        "                 [--bake W,H [--bake-dilate K] [--bake-uv-out FILE]]   (with --spp N and --out: a lightmap of W x H texels instead of a frame: the auto\n"
+                        "                                     atlas, N gather samples per covered texel, radiance = albedo * direct + indirect, K dilation steps (default 2),\n"
+                        "                                     packed under the display options; FILE receives the UVs as raw little-endian f32; excludes --auto-exposure\n"
+                        "                                     and every option that renders or reads a frame)\n");
             return 0;
         }
     }
@@ -279,6 +299,17 @@ int main(int argc, char** argv)
         if (const char* x = excluded_by_tiles(true)) { std::fprintf(stderr, "Error: --refine excludes %s\n", x); return 1; }
     }
     if (have_lens && ((!spp && !refine) || adaptive || gpus > 1 || have_iterations || ortho)) { std::fprintf(stderr, "Error: --lens thin / ortho needs --spp or --refine and excludes --adaptive, --gpus, -i and --ortho-width\n"); return 1; }
+    if (have_bake) {
+        if (dcfg_display.auto_exposure) { std::fprintf(stderr, "Error: --bake excludes --auto-exposure (an atlas has no film histogram; give --exposure)\n"); return 1; }
+        if (!spp || out.empty()) { std::fprintf(stderr, "Error: --bake needs --spp and --out\n"); return 1; }
+        if (adaptive || refine || have_region || have_lens || ortho || have_iterations || gpus > 1 || denoise || denoise_split || features || alpha || light_films || have_relight
+            || !out_lights.empty() || !load_films.empty() || !save_film.empty()) {
+            std::fprintf(stderr, "Error: --bake writes a lightmap, not a frame: it excludes --adaptive, --refine, --region, --lens, --ortho-width, -i, --gpus, --denoise, --denoise-split, "
+                                 "--features, --alpha, --light-films, --relight, --out-lights, --load-film and --save-film\n");
+            return 1;
+        }
+        if (bake_w < 1 || bake_h < 1 || bake_w > 16384 || bake_h > 16384 || bake_dilate > 0xFFFFFFFFull) { std::fprintf(stderr, "Error: --bake W,H: 1 .. 16384 each\n"); return 1; }
+    } else if (!bake_uv_out.empty()) { std::fprintf(stderr, "Error: --bake-uv-out needs --bake\n"); return 1; }
     if (have_exposure && dcfg_display.auto_exposure) { std::fprintf(stderr, "Error: --exposure and --auto-exposure exclude each other\n"); return 1; }
     std::printf("max triangles per leaf: %zu\n", max_triangles);      // main.rs:66
     if (have_iterations) std::printf("will quit after %zu frame iterations\n", frame_iterations);   // main.rs:73
@@ -296,6 +327,50 @@ int main(int argc, char** argv)
         if (gpus > 1) std::printf("rendering on %zu GPUs (rows dealt in stripes of %u)\n", gpus, cfg.stripe_rows);
         raytracer_lib::RayTracer rt = raytracer_lib::create_raytracer_from_file(file, max_triangles, width, height, &cfg);
         std::printf("number of triangles: %u\n", mi355rt_triangle_count(rt.handle()));   // colladaloader.rs:265
+        if (have_bake) {
+            mi355rt_handle* h = rt.handle();
+            auto check = [&](int rc, bool with_handle = true) { if (rc != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(with_handle ? h : nullptr)); };
+            const uint32_t ntri = mi355rt_triangle_count(h), bw = (uint32_t)bake_w, bh = (uint32_t)bake_h;
+            const size_t nt = (size_t)bw * bh;
+            std::vector<float> uv((size_t)ntri * 6);
+            uint32_t cell = 0;
+            check(mi355rt_bake_auto_atlas(ntri, bw, bh, 1u, uv.data(), &cell), false);
+            if (!bake_uv_out.empty()) {
+                FILE* f = std::fopen(bake_uv_out.c_str(), "wb");
+                if (!f || std::fwrite(uv.data(), sizeof(float), uv.size(), f) != uv.size() || std::fclose(f) != 0) { std::fprintf(stderr, "cannot write %s\n", bake_uv_out.c_str()); return 1; }
+            }
+            std::vector<uint32_t> ids(nt), cnt(nt);
+            std::vector<float> points(nt * 3), normals(nt * 3), albedo(nt * 3), sum(nt * 3), direct(nt * 3), rad(nt * 3), atlas(nt * 3);
+            mi355rt_bake_texel_outputs to{};
+            to.ids = ids.data(); to.points = points.data(); to.normals = normals.data(); to.albedo = albedo.data();
+            uint32_t n = 0;
+            check(mi355rt_bake_texels(h, uv.data(), bw, bh, 0u, MI355RT_RAYS_HOST, &to, &n));
+            mi355rt_gather_config gc;
+            mi355rt_gather_default_config(&gc);
+            gc.spp = (uint32_t)spp;
+            mi355rt_gather_outputs go{};
+            go.n = cnt.data(); go.sum = sum.data(); go.direct = direct.data();
+            check(mi355rt_gather(h, points.data(), normals.data(), ids.data(), n, &gc, MI355RT_RAYS_HOST, &go));
+            const mi355rt_ray_counts c = rt.last_counts();
+            for (size_t k = 0; k < (size_t)n; ++k)
+                for (int a = 0; a < 3; ++a) rad[3 * k + a] = albedo[3 * k + a] * direct[3 * k + a] + sum[3 * k + a] / (float)cnt[k];      // bake.radiance: f32, unfused
+            check(mi355rt_bake_atlas(h, ids.data(), rad.data(), n, bw, bh, (uint32_t)bake_dilate, MI355RT_RAYS_HOST, atlas.data(), nullptr));
+            std::vector<uint32_t> packed(nt);
+            check(mi355rt_display_image(h, atlas.data(), nt, display ? &dcfg_display : nullptr, packed.data()));
+            std::printf("bake: %u x %u texels in cells of %u, %u covered, %zu samples each, %u dilation steps  %.3f ms\n", bw, bh, cell, n, spp, (uint32_t)bake_dilate, c.total_ms);
+            if (display) std::printf("display: exposure %.9g\n", (double)dcfg_display.exposure);
+            const bool png = out.size() > 4 && out.compare(out.size() - 4, 4, ".png") == 0;
+            if (png) {
+                if (!write_png(out, packed, bw, bh, nullptr)) { std::fprintf(stderr, "cannot write %s\n", out.c_str()); return 1; }
+            } else {
+                FILE* f = std::fopen(out.c_str(), "wb");
+                if (!f) { std::fprintf(stderr, "cannot write %s\n", out.c_str()); return 1; }
+                std::fprintf(f, "P6\n%u %u\n255\n", bw, bh);
+                for (uint32_t p : packed) { unsigned char rgb[3] = { (unsigned char)(p >> 16), (unsigned char)(p >> 8), (unsigned char)p }; std::fwrite(rgb, 1, 3, f); }
+                std::fclose(f);
+            }
+            return 0;
+        }
         if (have_lens) rt.set_lens(lens);
         for (const std::string& f : load_films) rt.film.load(f, true);     // the fresh film is zero: the first file is added to it like the others
         raytracer_lib::stats::Stats stats;

@@ -1,5 +1,6 @@
 // renderer.cpp — see renderer.hpp.
 #include "renderer.hpp"
+#include "bake.hpp"
 #include "display.hpp"
 #include "lightmap.hpp"
 #include "reflmask.hpp"
@@ -1744,6 +1745,79 @@ bool Renderer::gather(const float* points3, const float* normals3, const uint32_
     return end_call(traced ? total : 0, true);                        // waits: the staging (and the caller's buffers) are free again
 }
 
+// mi355rt_bake_texels: csrc/bake.hip does the work on device memory; this stages host memory around it.  A read-out that makes no ray: a
+// speculative frame is settled, a queued one is ahead on the same stream, and neither the counters nor any film is touched.  The points need B - A and C - A
+// with the bits of the f32 subtraction: the leaf-order triangles hold exactly those (bvh.hpp), so the first call that asks for points puts them into scene
+// order once (d_bake_tris_, 36 bytes per triangle, counted in hbm_allocated_bytes and kept for the handle's life).
+bool Renderer::bake_texels(const float* uv, uint32_t width, uint32_t height, bool flip, bool device, const mi355rt_bake_texel_outputs& out, uint32_t* ncovered)
+{
+    if (!bind() || !settle_speculation()) return false;
+    const size_t nt = (size_t)width * height;
+    if (out.points && !d_bake_tris_ && ntri) {
+        std::vector<float> t9((size_t)ntri * 9);
+        for (const BvhTri& t : bvh.tris) {
+            if (t.prim >= ntri) continue;
+            float* q = &t9[9 * (size_t)t.prim];
+            for (int a = 0; a < 3; ++a) { q[a] = t.v0[a]; q[3 + a] = t.e1[a]; q[6 + a] = t.e2[a]; }
+        }
+        if (!upload(d_bake_tris_, t9.data(), t9.size() * sizeof(float))) return false;
+    }
+    DeviceBuffer<float> s_uv, s_bary, s_points, s_normals, s_albedo; DeviceBuffer<uint32_t> s_owner, s_ids;
+    const float* d_uv = uv;
+    mi355rt_bake_texel_outputs d = out;
+    if (!device) {
+        HIP_TRY(s_uv.alloc(std::max<size_t>((size_t)ntri * 24, 4), &hbm_bytes_));
+        if (ntri) HIP_TRY(hipMemcpyAsync(s_uv.get(), uv, (size_t)ntri * 24, hipMemcpyHostToDevice, stream_));
+        d_uv = s_uv.get();
+        if (out.ids) { HIP_TRY(s_ids.alloc(nt * 4, &hbm_bytes_)); d.ids = s_ids.get(); }
+        if (out.points) { HIP_TRY(s_points.alloc(nt * 12, &hbm_bytes_)); d.points = s_points.get(); }
+        if (out.normals) { HIP_TRY(s_normals.alloc(nt * 12, &hbm_bytes_)); d.normals = s_normals.get(); }
+        if (out.albedo) { HIP_TRY(s_albedo.alloc(nt * 12, &hbm_bytes_)); d.albedo = s_albedo.get(); }
+    }
+    if (!device || !out.owner) { HIP_TRY(s_owner.alloc(nt * 4, &hbm_bytes_)); d.owner = s_owner.get(); }
+    if (!device || !out.bary) {
+        HIP_TRY(s_bary.alloc(nt * 8, &hbm_bytes_)); d.bary = s_bary.get();
+        if (out.bary) HIP_TRY(hipMemcpyAsync(s_bary.get(), out.bary, nt * 8, hipMemcpyHostToDevice, stream_));      // uncovered texels keep what the caller had
+    }
+    uint32_t n = 0;
+    HIP_TRY(bake_texels_device(stream_, dscene_, d_bake_tris_.get(), d_uv, ntri, width, height, flip, d.owner, d.bary, d.ids, d.points, d.normals, d.albedo, &n, &hbm_bytes_));
+    if (!device) {
+        if (out.owner) HIP_TRY(hipMemcpyAsync(out.owner, d.owner, nt * 4, hipMemcpyDeviceToHost, stream_));
+        if (out.bary) HIP_TRY(hipMemcpyAsync(out.bary, d.bary, nt * 8, hipMemcpyDeviceToHost, stream_));
+        if (n && out.ids) HIP_TRY(hipMemcpyAsync(out.ids, d.ids, (size_t)n * 4, hipMemcpyDeviceToHost, stream_));
+        if (n && out.points) HIP_TRY(hipMemcpyAsync(out.points, d.points, (size_t)n * 12, hipMemcpyDeviceToHost, stream_));
+        if (n && out.normals) HIP_TRY(hipMemcpyAsync(out.normals, d.normals, (size_t)n * 12, hipMemcpyDeviceToHost, stream_));
+        if (n && out.albedo) HIP_TRY(hipMemcpyAsync(out.albedo, d.albedo, (size_t)n * 12, hipMemcpyDeviceToHost, stream_));
+        HIP_TRY(hipStreamSynchronize(stream_));
+    }
+    if (ncovered) *ncovered = n;
+    return true;
+}
+
+// mi355rt_bake_atlas: the ids are checked on the device first; verdict != 0: refused, nothing written (the caller words the error)
+bool Renderer::bake_atlas(const uint32_t* ids, const float* values3, uint32_t n, uint32_t width, uint32_t height, uint32_t dilate, bool device, float* atlas, uint8_t* valid, uint32_t& verdict)
+{
+    if (!bind() || !settle_speculation()) return false;
+    const size_t nt = (size_t)width * height;
+    DeviceBuffer<uint32_t> s_ids; DeviceBuffer<float> s_values, s_atlas; DeviceBuffer<uint8_t> s_valid;
+    const uint32_t* d_ids = ids; const float* d_values = values3; float* d_atlas = atlas; uint8_t* d_valid = valid;
+    if (!device) {
+        HIP_TRY(s_ids.alloc(std::max<size_t>((size_t)n * 4, 4), &hbm_bytes_)); HIP_TRY(s_values.alloc(std::max<size_t>((size_t)n * 12, 4), &hbm_bytes_));
+        if (n) { HIP_TRY(hipMemcpyAsync(s_ids.get(), ids, (size_t)n * 4, hipMemcpyHostToDevice, stream_)); HIP_TRY(hipMemcpyAsync(s_values.get(), values3, (size_t)n * 12, hipMemcpyHostToDevice, stream_)); }
+        d_ids = s_ids.get(); d_values = s_values.get();
+    }
+    if (!device || !atlas) { HIP_TRY(s_atlas.alloc(nt * 12, &hbm_bytes_)); d_atlas = s_atlas.get(); }
+    if (!device || !valid) { HIP_TRY(s_valid.alloc(nt, &hbm_bytes_)); d_valid = s_valid.get(); }
+    HIP_TRY(bake_atlas_device(stream_, d_ids, d_values, n, width, height, dilate, d_atlas, d_valid, &verdict, &hbm_bytes_));
+    if (verdict) return true;
+    if (!device) {
+        if (atlas) HIP_TRY(hipMemcpyAsync(atlas, d_atlas, nt * 12, hipMemcpyDeviceToHost, stream_));
+        if (valid) HIP_TRY(hipMemcpyAsync(valid, d_valid, nt, hipMemcpyDeviceToHost, stream_));
+        HIP_TRY(hipStreamSynchronize(stream_));
+    }
+    return true;
+}
+
 // mi355rt_render_rays: mi355rt_render whose passes read their primary rays from the caller's buffer, indexed by the CALL's sample number (enqueue_frame hands
 // every pass its base).  Only the rays of owned rows are read, so a host buffer is staged whole but a striped handle never looks at the rest.
 bool Renderer::render_rays(const float* rays6, uint32_t spp, bool device)
@@ -2130,6 +2204,28 @@ bool Renderer::get_display(const mi355rt_display_config& dc, const mi355rt_denoi
     HIP_TRY(hipMemcpyAsync(packed, d_disp_packed_.get(), npix * 4, hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     exposure_used = E;
+    return true;
+}
+
+// mi355rt_display_image: display_pack_kernel on an image that is no film (as mi355rt_get_relit_pixels feeds it), all buffers of the call's own — the
+// handle's display buffers are sized for its frame and allocated on first use, and this call must not move hbm_allocated_bytes.  The kernel reads a sample
+// count per pixel that only a film uses: a zeroed plane stands in for it.
+bool Renderer::display_image(const float* rgb3, size_t npix, const mi355rt_display_config* dc, uint32_t* packed)
+{
+    if (!bind()) return false;
+    DeviceBuffer<float> img, tab; DeviceBuffer<uint32_t> cnt, out;
+    HIP_TRY(img.alloc(npix * 12, &hbm_bytes_)); HIP_TRY(cnt.alloc(npix * 4, &hbm_bytes_)); HIP_TRY(out.alloc(npix * 4, &hbm_bytes_)); HIP_TRY(tab.alloc(256 * sizeof(float), &hbm_bytes_));
+    float t[256];
+    t[0] = 0.0f;                               // never read: the search starts above it
+    display_srgb_thresholds(t + 1);
+    HIP_TRY(hipMemcpyAsync(tab.get(), t, sizeof t, hipMemcpyHostToDevice, stream_));
+    HIP_TRY(hipMemcpyAsync(img.get(), rgb3, npix * 12, hipMemcpyHostToDevice, stream_));
+    HIP_TRY(hipMemsetAsync(cnt.get(), 0, npix * 4, stream_));
+    DisplayArgs a{};
+    a.curve = dc ? dc->curve : MI355RT_CURVE_REINHARD; a.transfer = dc ? dc->transfer : MI355RT_TRANSFER_REFERENCE; a.exposure = dc ? dc->exposure : 1.0f; a.white2 = dc ? dc->white * dc->white : 16.0f;
+    HIP_TRY(launch_display_pack(stream_, a, (uint32_t)npix, img.get(), cnt.get(), false, tab.get(), out.get()));
+    HIP_TRY(hipMemcpyAsync(packed, out.get(), npix * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
     return true;
 }
 

@@ -47,6 +47,9 @@ public:
     bool render_rays(const float* rays6, uint32_t spp, bool device);
     // gather: light arriving at npoints caller-given points; the caller has checked the arguments.  device: every pointer is device memory
     bool gather(const float* points3, const float* normals3, const uint32_t* ids, size_t npoints, const mi355rt_gather_config& gc, bool device, const mi355rt_gather_outputs& out);
+    // bake; the caller has checked the arguments.  device: every pointer but ncovered is device memory.  Neither touches films, camera, counters
+    bool bake_texels(const float* uv, uint32_t width, uint32_t height, bool flip, bool device, const mi355rt_bake_texel_outputs& out, uint32_t* ncovered);
+    bool bake_atlas(const uint32_t* ids, const float* values3, uint32_t n, uint32_t width, uint32_t height, uint32_t dilate, bool device, float* atlas, uint8_t* valid, uint32_t& verdict);
     // lens models; the caller has checked the arguments.  set_lens keeps the film, the caller-ray mark, the counters and current_row
     bool set_lens(const mi355rt_lens& l);
     const mi355rt_lens& lens() const { return lens_; }
@@ -98,6 +101,9 @@ public:
     // display read-out; the caller has checked the arguments.  source: MI355RT_DISPLAY_SOURCE_*; dn is read for the denoised sources only
     bool display_histogram(uint32_t source, const mi355rt_denoise_config& dn, mi355rt_luminance_histogram& out);
     bool get_display(const mi355rt_display_config& dc, const mi355rt_denoise_config& dn, uint32_t* packed, float& exposure_used);
+    // mi355rt_display_image: DISPLAY MAPPING of the caller's image (host memory, npix x 3 floats) with a fixed exposure; dc null: the reference's tone map.  Every
+    // buffer is a temporary: nothing of the handle changes
+    bool display_image(const float* rgb3, size_t npix, const mi355rt_display_config* dc, uint32_t* packed);
     void speculation_stats(uint64_t out[2]) const { out[0] = spec_launched_; out[1] = spec_adopted_; }
     bool debug_numerics(const float* a, const float* b, size_t n, float* q, float* r, float* p);
     bool debug_sample(uint32_t pixel, uint32_t sampleno, float* color3, float* node_L, size_t nodes);
@@ -254,6 +260,7 @@ private:
     uint32_t lights_stride() const { return cfg.width * cfg.height * 3u; }      // floats per plane
     DeviceBuffer<float> d_relit_rgb_, d_relit_weights_;   // mi355rt_get_relit_pixels, allocated on first use: the relit image (12 bytes per pixel; d_disp_packed_ takes the packed one), the weights
     bool ensure_display_buffers(bool hist_and_table);     // d_disp_packed_ [, d_disp_hist_, d_disp_table_], on first use
+    DeviceBuffer<float> d_bake_tris_;    // bake: per triangle in SCENE order (A, B - A, C - A), 36 bytes, made from bvh.tris by the first mi355rt_bake_texels that asks for points and kept
     DeviceBuffer<uint32_t> d_owned_rows_, d_all_rows_, d_tmp_rows_;
     DeviceBuffer<uint32_t> d_ldr_;
     PinnedBuffer<uint32_t> h_ldr_;       // host mirror of d_ldr_ (get_tonemapped_pixels)

@@ -2,7 +2,8 @@
 """Compile csrc/kernels.hip for gfx950 with -Rpass-analysis=kernel-resource-usage and print one line per
 kernel: VGPRs, AGPRs, SGPRs, scratch bytes, occupancy (waves per SIMD), LDS.  Optional: --isa writes the
 disassembly to /tmp/kernels.s and prints VALU / SALU / VMEM / LDS instruction counts per kernel.
-usage: tools/kernel_resources.py [--isa] [extra hipcc flags]"""
+--src=bake.hip: another kernel file of csrc/ instead, with the flags of its own Makefile rule (no -fno-slp-vectorize).
+usage: tools/kernel_resources.py [--isa] [--src=FILE] [extra hipcc flags]"""
 import os
 import re
 import subprocess
@@ -23,11 +24,16 @@ def demangle(name):
 def main():
     args = sys.argv[1:]
     isa = "--isa" in args
-    extra = [a for a in args if a != "--isa"]
-    cmd = ["/opt/rocm/bin/hipcc"] + FLAGS + extra + ["-Rpass-analysis=kernel-resource-usage", "-c", SRC, "-o", "/tmp/kernels_res.o"]
+    extra = [a for a in args if a != "--isa" and not a.startswith("--src=")]
+    src, flags = SRC, FLAGS
+    for a in args:
+        if a.startswith("--src="):
+            src = os.path.join(os.path.dirname(SRC), a[6:])
+            flags = [f for f in FLAGS if f != "-fno-slp-vectorize"]
+    cmd = ["/opt/rocm/bin/hipcc"] + flags + extra + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/tmp/kernels_res.o"]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd="/tmp")
     if isa and r.returncode == 0:
-        subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + extra + ["--save-temps", "-c", SRC, "-o", "/tmp/kernels_res2.o"], capture_output=True, text=True, cwd="/tmp")
+        subprocess.run(["/opt/rocm/bin/hipcc"] + flags + extra + ["--save-temps", "-c", src, "-o", "/tmp/kernels_res2.o"], capture_output=True, text=True, cwd="/tmp")
     if r.returncode != 0:
         print(r.stderr)
         sys.exit(1)
