@@ -53,6 +53,15 @@ template <class Body> int no_throw(const char* fn, int code, Body&& body)
     return code;
 }
 
+// What the entries that take `where` share: they serve one device, and `where` is one of its two constants.  Null: fine, else the refusal, which the caller
+// prefixes with its name.  An entry that checks `where` later, or takes none, passes MI355RT_RAYS_HOST.
+const char* single_device_ok(const mi355rt_handle* h, uint32_t where)
+{
+    if (h->g->size() > 1) return "not available on a device group (config.device_count > 1)";
+    if (where > MI355RT_RAYS_DEVICE) return "unknown `where` (MI355RT_RAYS_HOST or MI355RT_RAYS_DEVICE)";
+    return nullptr;
+}
+
 // the checks of mi355rt_render_adaptive / mi355rt_adaptive_tile_mask (include/mi355rt.h); on failure the handle's last_error names the field
 bool adaptive_args_ok(mi355rt_handle* h, const mi355rt_adaptive_config* c)
 {
@@ -197,8 +206,7 @@ bool features_call_ok(mi355rt_handle* h, const char* fn, bool rays, const float*
     if (!h) return false;
     Renderer* r = h->r;
     std::string e;
-    if (h->g->size() > 1) e = "not available on a device group (config.device_count > 1)";
-    else if (rays && where > MI355RT_RAYS_DEVICE) e = "unknown `where` (MI355RT_RAYS_HOST or MI355RT_RAYS_DEVICE)";
+    if (const char* refusal = single_device_ok(h, rays ? where : MI355RT_RAYS_HOST)) e = refusal;
     else if (spp == 0) e = "spp must be >= 1";
     else if (rays && nrays != (size_t)r->cfg.width * r->cfg.height * spp) e = "nrays must equal width * height * spp";
     else if (rays && !rays6) e = "rays6 is NULL";
@@ -226,9 +234,8 @@ bool ray_call_ok(mi355rt_handle* h, const char* fn, const float* rays6, size_t n
 {
     if (!h) return false;
     const char* e = nullptr;
-    if (h->g->size() > 1) e = "not available on a device group (config.device_count > 1)";
-    else if (where > MI355RT_RAYS_DEVICE) e = "unknown `where` (MI355RT_RAYS_HOST or MI355RT_RAYS_DEVICE)";
-    else if (n && !rays6) e = "rays6 is NULL";
+    if ((e = single_device_ok(h, where)) != nullptr) {}
+    else if(n && !rays6) e = "rays6 is NULL";
     if (!e) return true;
     h->r->last_error = std::string(fn) + ": " + e;
     return false;
@@ -432,12 +439,12 @@ int mi355rt_render_tiles(mi355rt_handle* h, const uint8_t* tile_mask, size_t nti
 {
     if (!h) return MI355RT_E_INVALID;
     const char* e = nullptr;
-    if (h->g->size() > 1) e = "mi355rt_render_tiles: not available on a device group (config.device_count > 1)";
-    else if (!tile_mask) e = "mi355rt_render_tiles: tile_mask is NULL";
-    else if (ntiles != (size_t)h->r->tiles_x() * h->r->tiles_y()) e = "mi355rt_render_tiles: ntiles must equal tiles_x * tiles_y";
-    else if (spp == 0) e = "mi355rt_render_tiles: spp must be >= 1";
-    else if (where > MI355RT_RAYS_DEVICE) e = "mi355rt_render_tiles: unknown `where` (MI355RT_RAYS_HOST or MI355RT_RAYS_DEVICE)";
-    if (e) { h->r->last_error = e; return MI355RT_E_INVALID; }
+    if ((e = single_device_ok(h, MI355RT_RAYS_HOST)) != nullptr) {}       // the group first; `where` is this entry's last check
+    else if (!tile_mask) e = "tile_mask is NULL";
+    else if (ntiles != (size_t)h->r->tiles_x() * h->r->tiles_y()) e = "ntiles must equal tiles_x * tiles_y";
+    else if (spp == 0) e = "spp must be >= 1";
+    else e = single_device_ok(h, where);
+    if (e) { h->r->last_error = std::string("mi355rt_render_tiles: ") + e; return MI355RT_E_INVALID; }
     const bool ok = h->r->render_tiles(tile_mask, spp, where == MI355RT_RAYS_DEVICE);
     if (counts) *counts = h->r->counts;
     return ok ? MI355RT_OK : MI355RT_E_HIP;
@@ -867,9 +874,8 @@ int mi355rt_gather(mi355rt_handle* h, const float* points3, const float* normals
     if (!h) return MI355RT_E_INVALID;
     const char* e = nullptr;
     const bool sampled = out && (out->n || out->hits || out->near || out->sum || out->sumsq);
-    if (h->g->size() > 1) e = "not available on a device group (config.device_count > 1)";
-    else if (where > MI355RT_RAYS_DEVICE) e = "unknown `where` (MI355RT_RAYS_HOST or MI355RT_RAYS_DEVICE)";
-    else if (!cfg) e = "cfg is NULL";
+    if ((e = single_device_ok(h, where)) != nullptr) {}
+    else if(!cfg) e = "cfg is NULL";
     else if (!out || (!sampled && !out->direct)) e = "out is NULL or every output pointer in it is NULL";
     else if (npoints && !points3) e = "points3 is NULL";
     else if (cfg->weight > MI355RT_GATHER_COSINE) e = "unknown weight (MI355RT_GATHER_MEAN or MI355RT_GATHER_COSINE)";
@@ -902,9 +908,8 @@ int mi355rt_bake_texels(mi355rt_handle* h, const float* uv, uint32_t width, uint
 {
     if (!h) return MI355RT_E_INVALID;
     const char* e = nullptr;
-    if (h->g->size() > 1) e = "not available on a device group (config.device_count > 1)";
-    else if (where > MI355RT_RAYS_DEVICE) e = "unknown `where` (MI355RT_RAYS_HOST or MI355RT_RAYS_DEVICE)";
-    else if (width == 0 || height == 0 || width > 16384u || height > 16384u) e = "width and height must be 1 .. 16384";
+    if ((e = single_device_ok(h, where)) != nullptr) {}
+    else if(width == 0 || height == 0 || width > 16384u || height > 16384u) e = "width and height must be 1 .. 16384";
     else if (!uv && h->r->ntri) e = "uv is NULL";
     else if (!ncovered && (!out || (!out->owner && !out->bary && !out->ids && !out->points && !out->normals && !out->albedo))) e = "out is NULL or every output pointer in it is NULL, and ncovered is NULL";
     if (e) { h->r->last_error = std::string("mi355rt_bake_texels: ") + e; return MI355RT_E_INVALID; }
@@ -916,9 +921,8 @@ int mi355rt_bake_atlas(mi355rt_handle* h, const uint32_t* ids, const float* valu
 {
     if (!h) return MI355RT_E_INVALID;
     const char* e = nullptr;
-    if (h->g->size() > 1) e = "not available on a device group (config.device_count > 1)";
-    else if (where > MI355RT_RAYS_DEVICE) e = "unknown `where` (MI355RT_RAYS_HOST or MI355RT_RAYS_DEVICE)";
-    else if (width == 0 || height == 0 || width > 16384u || height > 16384u) e = "width and height must be 1 .. 16384";
+    if ((e = single_device_ok(h, where)) != nullptr) {}
+    else if(width == 0 || height == 0 || width > 16384u || height > 16384u) e = "width and height must be 1 .. 16384";
     else if (!atlas && !valid) e = "atlas and valid are both NULL";
     else if (n && !ids) e = "ids is NULL";
     else if (n && !values3) e = "values3 is NULL";
@@ -1007,12 +1011,11 @@ int mi355rt_lens_rays(mi355rt_handle* h, uint32_t spp, uint32_t where, float* ra
 {
     if (!h) return MI355RT_E_INVALID;
     const char* e = nullptr;
-    if (h->g->size() > 1) e = "mi355rt_lens_rays: not available on a device group (config.device_count > 1)";
-    else if (where > MI355RT_RAYS_DEVICE) e = "mi355rt_lens_rays: unknown `where` (MI355RT_RAYS_HOST or MI355RT_RAYS_DEVICE)";
-    else if (spp == 0) e = "mi355rt_lens_rays: spp must be >= 1";
-    else if (nrays != (size_t)h->r->cfg.width * h->r->cfg.height * spp) e = "mi355rt_lens_rays: nrays must equal width * height * spp";
-    else if (!rays6) e = "mi355rt_lens_rays: rays6 is NULL";
-    if (e) { h->r->last_error = e; return MI355RT_E_INVALID; }
+    if ((e = single_device_ok(h, where)) != nullptr) {}
+    else if (spp == 0) e = "spp must be >= 1";
+    else if (nrays != (size_t)h->r->cfg.width * h->r->cfg.height * spp) e = "nrays must equal width * height * spp";
+    else if (!rays6) e = "rays6 is NULL";
+    if (e) { h->r->last_error = std::string("mi355rt_lens_rays: ") + e; return MI355RT_E_INVALID; }
     return h->r->lens_rays(spp, where == MI355RT_RAYS_DEVICE, rays6) ? MI355RT_OK : MI355RT_E_HIP;
 }
 

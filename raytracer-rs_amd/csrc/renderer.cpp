@@ -14,6 +14,7 @@
 #include "kernels.hpp"
 #include "lens.hpp"
 #include "octree.hpp"
+#include "staging.hpp"
 
 namespace mi355rt {
 
@@ -27,6 +28,17 @@ void pcg4d(uint32_t v[4])
     v[0] += v[1] * v[3]; v[1] += v[2] * v[0]; v[2] += v[0] * v[1]; v[3] += v[1] * v[2];
 }
 float u01(uint32_t bits) { return (float)(bits >> 9) * (1.0f / 8388608.0f); }
+
+// the 256-entry sRGB threshold table the display kernels search; entry 0 is never read: the search starts above it
+void display_srgb_table(float t[256]) { t[0] = 0.0f; display_srgb_thresholds(t + 1); }
+
+// DISPLAY MAPPING's arguments; dc null: the reference's tone map (the Reinhard curve, the reference's transfer)
+DisplayArgs display_args(const mi355rt_display_config* dc, float exposure)
+{
+    DisplayArgs a{};
+    a.curve = dc ? dc->curve : MI355RT_CURVE_REINHARD; a.transfer = dc ? dc->transfer : MI355RT_TRANSFER_REFERENCE; a.exposure = exposure; a.white2 = dc ? dc->white * dc->white : 16.0f;
+    return a;
+}
 }  // namespace
 
 bool Renderer::fail(hipError_t e, const char* what)
@@ -41,6 +53,9 @@ bool Renderer::bind()
     HIP_TRY(hipSetDevice(cfg.device));
     return true;
 }
+
+// what most entries start with: the handle's device is current and no speculative frame is out
+bool Renderer::quiet() { return bind() && settle_speculation(); }
 
 template <class T> bool Renderer::upload(DeviceBuffer<T>& buf, const void* src, size_t bytes)
 {
@@ -89,8 +104,7 @@ void Renderer::build_sample_table(std::vector<float>& table4)
 // mi355rt_set_seed: the handle afterwards equals one created with this seed (per-sample hash key AND direction table)
 bool Renderer::set_seed(uint64_t seed)
 {
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     cfg.seed = seed;
     std::vector<float> table4;
     build_sample_table(table4);
@@ -888,8 +902,7 @@ bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32
 
 bool Renderer::begin_call()
 {
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     call_done_valid_ = false;
     ev_used_ = 0; launches_ = 0;
     counts_pending_ = false;
@@ -1137,6 +1150,26 @@ bool Renderer::render(uint32_t spp, bool wait)
     return end_call((uint64_t)owned_rows.size() * cfg.width * spp, wait);
 }
 
+// Samples per pass, of a frame's slice as of a ray call: 144 Mi — the whole 1080p x 64 spp frame in ONE pass (55 GB of pass buffers).  Every pass costs
+// its launches' ramps and tails: 3 passes of 44 M samples 22.9 ms, 2 passes 22.2-22.6 ms, 1 pass 21.6 ms (profiles/r03_notes.md,
+// with the HBM each takes: 18.9 / 27.4 / 54.5 GB); MI355RT_PASS_SAMPLES (>= 1024) or config.samples_per_pass trade the memory back.
+size_t Renderer::pass_sample_budget() const
+{
+    if (const char* e = getenv("MI355RT_PASS_SAMPLES")) { const long v = atol(e); if (v >= 1024) return (size_t)v; }
+    return (size_t)144 << 20;
+}
+
+// The passes of mi355rt_trace_rays and mi355rt_gather, `per` rays each on slice sl: halved while the device cannot hold their buffers, down to 1024
+bool Renderer::fit_ray_pass(Slice& sl, size_t& per)
+{
+    while (!ensure_pass_capacity(sl, per)) {
+        if (!alloc_failed_ || per <= 1024) return false;
+        (void)hipGetLastError();
+        per /= 2;
+    }
+    return true;
+}
+
 // The body of a frame: plan the passes of every slice (halving them while the device cannot hold their buffers) and queue them, each slice on its
 // own stream, forked behind `fork` on the main stream.  render() runs one; render_adaptive() one per round, with the round's tile mask.
 bool Renderer::enqueue_frame(uint32_t spp, hipEvent_t fork, const uint8_t* tile_active, const RayFeed* feed)
@@ -1149,11 +1182,7 @@ bool Renderer::enqueue_frame(uint32_t spp, hipEvent_t fork, const uint8_t* tile_
         if (!slices_explicit) nsl = (uint32_t)std::min<uint64_t>(nsl, std::max<uint64_t>(1, (uint64_t)nrows * cfg.width * spp >> 25));
         nsl = std::min(nsl, (nrows + cfg.stripe_rows - 1) / cfg.stripe_rows);
         if (!assign_slice_rows(nsl)) return false;
-        // samples per pass of one slice: 144 Mi — the whole 1080p x 64 spp frame in ONE pass (55 GB of pass buffers).  Every pass costs
-        // its launches' ramps and tails: 3 passes of 44 M samples 22.9 ms, 2 passes 22.2-22.6 ms, 1 pass 21.6 ms (profiles/r03_notes.md,
-        // with the HBM each takes: 18.9 / 27.4 / 54.5 GB); MI355RT_PASS_SAMPLES or config.samples_per_pass trade the memory back.
-        size_t target = (size_t)144 << 20;
-        if (const char* e = getenv("MI355RT_PASS_SAMPLES")) { long v = atol(e); if (v >= 1024) target = (size_t)v; }
+        size_t target = pass_sample_budget();                          // per slice; config.samples_per_pass, when set, decides instead (starget below)
         // The pass buffers (two ray queues, hit records, light terms: ~410 B per sample) are sized for the
         // largest pass.  If the device cannot hold them (another tenant, a 16 GB part), halve the pass and
         // try again; results do not depend on how samples are batched into passes.
@@ -1232,8 +1261,7 @@ bool Renderer::adaptive_verdict(const mi355rt_adaptive_config& ac, uint32_t& til
 
 bool Renderer::adaptive_tile_mask(const mi355rt_adaptive_config& ac, uint8_t* out, uint32_t& active)
 {
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     uint64_t pixels = 0;
     if (!adaptive_verdict(ac, active, pixels)) return false;
     HIP_TRY(hipMemcpy(out, d_tile_active_.get(), (size_t)tiles_x() * tiles_y(), hipMemcpyDeviceToHost));
@@ -1339,8 +1367,7 @@ bool Renderer::get_tonemapped(uint32_t* out, size_t n)
 // before and after (its collective, its buffer initialisation).
 bool Renderer::tonemap_owned_rows_device(uint32_t* device_out, size_t n, hipStream_t caller_stream)
 {
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     if (n < owned_rows.size() * (size_t)cfg.width || !device_out) { last_error = "output buffer too small"; return false; }
     if (caller_stream) {
         HIP_TRY(hipEventRecord(slices_[0].done, stream_));
@@ -1405,8 +1432,7 @@ bool Renderer::gather_prepare(bool root)
 }
 bool Renderer::tonemap_to_gather_slot()
 {
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     HIP_TRY(launch_tonemap(stream_, d_owned_rows_.get(), 0, (uint32_t)owned_rows.size(), cfg.width, true, d_film_sum_.get(), d_film_n_.get(), gather_slot(cfg.stripe_rank)));
     return true;
 }
@@ -1427,8 +1453,7 @@ bool Renderer::finish_gather(uint32_t* host_out, size_t n)
 
 bool Renderer::film_get(float* sum, float* sumsq, uint32_t* n)
 {
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     const size_t npix = (size_t)cfg.width * cfg.height;
     HIP_TRY(hipStreamSynchronize(stream_));
     if (sum) HIP_TRY(hipMemcpy(sum, d_film_sum_.get(), npix * 12, hipMemcpyDeviceToHost));
@@ -1450,8 +1475,7 @@ bool Renderer::film_get_direct(float* sum)
 
 bool Renderer::film_clear()
 {
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     const size_t npix = (size_t)cfg.width * cfg.height;
     std::fill(ldr_dirty_.begin(), ldr_dirty_.end(), (uint8_t)1);     // unsampled rows read back white (NaN -> 255)
     caller_ray_film_ = false;
@@ -1470,8 +1494,8 @@ bool Renderer::film_clear()
     return true;            // stream-ordered: every later call on this handle starts on the same stream
 }
 
-// mi355rt_film_set / mi355rt_film_add: the caller's planes are staged in one temporary device buffer (n, sum, sumsq, direct: the order of a film
-// file), the merge kernel stores or adds them on the rows this handle owns, and the staging is freed again.  Everything runs on stream_: behind a
+// mi355rt_film_set / mi355rt_film_add: the caller's planes are staged (staging.hpp; n, sum, sumsq, direct: the order of a film file), the merge kernel
+// stores or adds them on the rows this handle owns, and the staging is freed again.  Everything runs on stream_: behind a
 // queued frame (render_async joins its slices there) and behind the rows a speculative frame gives back, ahead of every later call.  Nothing but
 // the film and the tone-map cache's dirty rows changes.
 bool Renderer::film_put(const FilmPlanes& in, bool add)
@@ -1481,16 +1505,12 @@ bool Renderer::film_put(const FilmPlanes& in, bool add)
     if (!settle_speculation()) return false;
     if (!add) caller_ray_film_ = false;                               // the film is the caller's planes now
     const size_t npix = (size_t)cfg.width * cfg.height;
-    DeviceBuffer<uint8_t> stage;
-    HIP_TRY(stage.alloc(npix * (in.direct ? 40 : 28), &hbm_bytes_));
-    uint32_t* s_n = reinterpret_cast<uint32_t*>(stage.get());
-    float* s_sum = reinterpret_cast<float*>(stage.get() + npix * 4);
-    float* s_sumsq = s_sum + npix * 3;
-    float* s_direct = in.direct ? s_sumsq + npix * 3 : nullptr;
-    HIP_TRY(hipMemcpyAsync(s_n, in.n, npix * 4, hipMemcpyHostToDevice, stream_));
-    HIP_TRY(hipMemcpyAsync(s_sum, in.sum, npix * 12, hipMemcpyHostToDevice, stream_));
-    HIP_TRY(hipMemcpyAsync(s_sumsq, in.sumsq, npix * 12, hipMemcpyHostToDevice, stream_));
-    if (in.direct) HIP_TRY(hipMemcpyAsync(s_direct, in.direct, npix * 12, hipMemcpyHostToDevice, stream_));
+    Staging st(stream_, &hbm_bytes_, false);
+    const uint32_t* s_n = st.in(in.n, npix);
+    const float* s_sum = st.in(in.sum, npix * 3);
+    const float* s_sumsq = st.in(in.sumsq, npix * 3);
+    const float* s_direct = st.in(in.direct, npix * 3);
+    HIP_TRY(st.error());
     HIP_TRY(launch_film_merge(stream_, add, s_sum, s_sumsq, s_n, s_direct, (uint32_t)npix, cfg.width, cfg.stripe_rows, cfg.stripe_world, cfg.stripe_rank,
                               d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_film_direct_.get()));
     std::fill(ldr_dirty_.begin(), ldr_dirty_.end(), (uint8_t)1);
@@ -1502,8 +1522,7 @@ bool Renderer::film_put(const FilmPlanes& in, bool add)
 static_assert(kMaxLightFilms == MI355RT_LIGHT_FILMS_MAX_LIGHTS, "the header's limit is the one resolve_kernel's LDS is sized for");
 bool Renderer::light_films_get(float* planes)
 {
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     HIP_TRY(hipStreamSynchronize(stream_));
     if (d_film_lights_) HIP_TRY(hipMemcpy(planes, d_film_lights_.get(), (size_t)nlights_ * lights_stride() * 4, hipMemcpyDeviceToHost));
     return true;
@@ -1512,14 +1531,12 @@ bool Renderer::light_films_get(float* planes)
 // mi355rt_light_films_set / _add: as film_put — the caller's planes staged in a temporary device buffer, stored or added on the owned rows, on stream_
 bool Renderer::light_films_put(const float* planes, bool add)
 {
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     if (!d_film_lights_) return true;                                 // no lights: no planes
-    const size_t bytes = (size_t)nlights_ * lights_stride() * 4;
-    DeviceBuffer<float> stage;
-    HIP_TRY(stage.alloc(bytes, &hbm_bytes_));
-    HIP_TRY(hipMemcpyAsync(stage.get(), planes, bytes, hipMemcpyHostToDevice, stream_));
-    HIP_TRY(launch_light_films_merge(stream_, add, stage.get(), nlights_, cfg.width * cfg.height, cfg.width, cfg.stripe_rows, cfg.stripe_world, cfg.stripe_rank,
+    Staging st(stream_, &hbm_bytes_, false);
+    const float* s_planes = st.in(planes, (size_t)nlights_ * lights_stride());
+    HIP_TRY(st.error());
+    HIP_TRY(launch_light_films_merge(stream_, add, s_planes, nlights_, cfg.width * cfg.height, cfg.width, cfg.stripe_rows, cfg.stripe_world, cfg.stripe_rank,
                                      d_film_lights_.get(), lights_stride()));
     HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's array and the staging are free again
     return true;
@@ -1533,8 +1550,7 @@ bool Renderer::ensure_display_buffers(bool hist_and_table)
     if (!d_disp_hist_) HIP_TRY(d_disp_hist_.alloc(kDisplayHistWords * 4, &hbm_bytes_));
     if (!d_disp_table_) {
         float t[256];
-        t[0] = 0.0f;                           // never read: the search starts above it
-        display_srgb_thresholds(t + 1);
+        display_srgb_table(t);
         DeviceBuffer<float> tab;
         HIP_TRY(tab.alloc(sizeof t, &hbm_bytes_));
         HIP_TRY(hipMemcpy(tab.get(), t, sizeof t, hipMemcpyHostToDevice));
@@ -1547,8 +1563,7 @@ bool Renderer::ensure_display_buffers(bool hist_and_table)
 // dc == null: DISPLAY MAPPING with exposure 1, the Reinhard curve and the reference's transfer is get_tonemapped_pixels' map of c (c * 1.0f is c).
 bool Renderer::get_relit(const float* weights3, const mi355rt_display_config* dc, float* rgb, uint32_t* packed, float& exposure_used)
 {
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     const size_t npix = (size_t)cfg.width * cfg.height;
     if (!d_relit_rgb_) {
         DeviceBuffer<float> img, w;
@@ -1566,9 +1581,7 @@ bool Renderer::get_relit(const float* weights3, const mi355rt_display_config* dc
         E = display_auto_exposure(hist, dc->key, dc->low, dc->high);
     }
     if (packed) {
-        DisplayArgs a{};
-        a.curve = dc ? dc->curve : MI355RT_CURVE_REINHARD; a.transfer = dc ? dc->transfer : MI355RT_TRANSFER_REFERENCE; a.exposure = E; a.white2 = dc ? dc->white * dc->white : 16.0f;
-        HIP_TRY(launch_display_pack(stream_, a, (uint32_t)npix, d_relit_rgb_.get(), d_film_n_.get(), false, d_disp_table_.get(), d_disp_packed_.get()));
+        HIP_TRY(launch_display_pack(stream_, display_args(dc, E), (uint32_t)npix, d_relit_rgb_.get(), d_film_n_.get(), false, d_disp_table_.get(), d_disp_packed_.get()));
         HIP_TRY(hipMemcpyAsync(packed, d_disp_packed_.get(), npix * 4, hipMemcpyDeviceToHost, stream_));
     }
     if (rgb) HIP_TRY(hipMemcpyAsync(rgb, d_relit_rgb_.get(), npix * 12, hipMemcpyDeviceToHost, stream_));
@@ -1582,56 +1595,39 @@ bool Renderer::intersect(const float* rays6, size_t n, float* tuv, uint32_t* pri
     if (!bind()) return false;
     if (n == 0) return true;
     if (n > 0x7FFFFFFFull / 24) { last_error = "too many rays in one batch"; return false; }
-    const bool shadow = blocked != nullptr;
-    DeviceBuffer<float> d_rays, d_tuv; DeviceBuffer<uint32_t> d_prim; DeviceBuffer<uint8_t> d_blocked;
-    HIP_TRY(d_rays.alloc(n * 24));
-    HIP_TRY(d_tuv.alloc(n * 12));
-    HIP_TRY(d_prim.alloc(n * 4));
-    HIP_TRY(d_blocked.alloc(n));
-    HIP_TRY(hipMemcpyAsync(d_rays.get(), rays6, n * 24, hipMemcpyHostToDevice, stream_));
-    if (!shadow) HIP_TRY(hipMemcpyAsync(d_tuv.get(), tuv, n * 12, hipMemcpyHostToDevice, stream_));   // misses stay untouched
-    HIP_TRY(launch_intersect(stream_, dscene_, traversal_rows(), mode_ == kModeConfirm ? 0 : mode_ == kModeOctreeWalk ? 1 : 2, d_rays.get(), (uint32_t)n, shadow, d_tuv.get(), d_prim.get(), d_blocked.get()));
-    if (shadow) HIP_TRY(hipMemcpyAsync(blocked, d_blocked.get(), n, hipMemcpyDeviceToHost, stream_));
-    else {
-        HIP_TRY(hipMemcpyAsync(tuv, d_tuv.get(), n * 12, hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipMemcpyAsync(prim, d_prim.get(), n * 4, hipMemcpyDeviceToHost, stream_));
-    }
+    const bool shadow = blocked != nullptr;               // then tuv and prim are null, and the kernel touches neither
+    Staging st(stream_, &hbm_bytes_, false);
+    const float* d_rays = st.in(rays6, n * 6);
+    float* d_tuv = st.out(tuv, n * 3, true);              // misses stay untouched
+    uint32_t* d_prim = st.out(prim, n);
+    uint8_t* d_blocked = st.out(blocked, n);
+    HIP_TRY(st.error());
+    HIP_TRY(launch_intersect(stream_, dscene_, traversal_rows(), (int)mode_, d_rays, (uint32_t)n, shadow, d_tuv, d_prim, d_blocked));
+    HIP_TRY(st.download());
     HIP_TRY(hipStreamSynchronize(stream_));
     return true;
 }
 
 // ---- caller-supplied rays (include/mi355rt.h) ---------------------------------------------------------------------------
 // mi355rt_trace_rays: the rays as ray-fed passes of one sample each on slice 0 (the main stream), as many as the pass buffers need.  Host memory is staged
-// through temporary device buffers in the caller's own layout (rays, keys, and whatever outputs are asked for; tuv goes up first, a miss leaves it as it
-// was); device memory is read and written in place.  A read-out like debug_sample: no film, no camera, no row state changes.
+// (staging.hpp) in the caller's own layout: rays, keys, and whatever outputs are asked for; device memory is read and written in place.  A read-out like
+// debug_sample: no film, no camera, no row state changes.
 bool Renderer::trace_rays(const float* rays6, const uint32_t* keys2, size_t n, bool device, const mi355rt_ray_outputs& out)
 {
     if (!begin_call()) return false;                                  // settles a speculative frame; a queued frame is ahead on the same stream
     if (n > 0xFFFFFFFFull) { last_error = "mi355rt_trace_rays: n does not fit 32 bits"; return false; }
-    DeviceBuffer<float> s_rays, s_rgb, s_direct, s_tuv; DeviceBuffer<uint32_t> s_keys, s_prim; DeviceBuffer<float4> s_hit;
-    const float* d_rays = rays6; const uint32_t* d_keys = keys2;
-    float* d_rgb = out.rgb; float* d_direct = out.direct; float* d_tuv = out.tuv; uint32_t* d_prim = out.prim;
-    if (!device && n) {
-        HIP_TRY(s_rays.alloc(n * 24, &hbm_bytes_));
-        HIP_TRY(hipMemcpyAsync(s_rays.get(), rays6, n * 24, hipMemcpyHostToDevice, stream_));
-        d_rays = s_rays.get();
-        if (keys2) { HIP_TRY(s_keys.alloc(n * 8, &hbm_bytes_)); HIP_TRY(hipMemcpyAsync(s_keys.get(), keys2, n * 8, hipMemcpyHostToDevice, stream_)); d_keys = s_keys.get(); }
-        if (out.rgb) { HIP_TRY(s_rgb.alloc(n * 12, &hbm_bytes_)); d_rgb = s_rgb.get(); }
-        if (out.direct) { HIP_TRY(s_direct.alloc(n * 12, &hbm_bytes_)); d_direct = s_direct.get(); }
-        if (out.tuv) { HIP_TRY(s_tuv.alloc(n * 12, &hbm_bytes_)); HIP_TRY(hipMemcpyAsync(s_tuv.get(), out.tuv, n * 12, hipMemcpyHostToDevice, stream_)); d_tuv = s_tuv.get(); }
-        if (out.prim) { HIP_TRY(s_prim.alloc(n * 4, &hbm_bytes_)); d_prim = s_prim.get(); }
-    }
+    Staging st(stream_, &hbm_bytes_, device);
+    const float* d_rays = st.in(rays6, n * 6); const uint32_t* d_keys = st.in(keys2, n * 2);
+    float* d_rgb = st.out(out.rgb, n * 3); float* d_direct = st.out(out.direct, n * 3);
+    float* d_tuv = st.out(out.tuv, n * 3, true);                      // goes up first: a miss leaves it as it was
+    uint32_t* d_prim = st.out(out.prim, n);
+    HIP_TRY(st.error());
     // rays per pass: what the frame's passes hold (enqueue_frame), config.samples_per_pass images' worth when that is set; halved while the device cannot hold the buffers
-    size_t per = (size_t)144 << 20;
-    if (const char* e = getenv("MI355RT_PASS_SAMPLES")) { long v = atol(e); if (v >= 1024) per = (size_t)v; }
-    if (cfg.samples_per_pass) per = std::max<size_t>(1, (size_t)cfg.samples_per_pass * cfg.width * cfg.height);
+    size_t per = cfg.samples_per_pass ? std::max<size_t>(1, (size_t)cfg.samples_per_pass * cfg.width * cfg.height) : pass_sample_budget();
     per = std::min(per, std::max<size_t>(n, 1));
     Slice& sl = slices_[0];
-    while (n && !ensure_pass_capacity(sl, per)) {
-        if (!alloc_failed_ || per <= 1024) return false;
-        (void)hipGetLastError();
-        per /= 2;
-    }
+    if (n && !fit_ray_pass(sl, per)) return false;
+    DeviceBuffer<float4> s_hit;
     if (n && (out.tuv || out.prim)) HIP_TRY(s_hit.alloc(per * sizeof(float4), &hbm_bytes_));
     for (size_t at = 0; at < n; at += per) {
         const size_t cnt = std::min(per, n - at);
@@ -1640,12 +1636,7 @@ bool Renderer::trace_rays(const float* rays6, const uint32_t* keys2, size_t n, b
         f.rgb = d_rgb ? d_rgb + 3 * at : nullptr; f.direct = d_direct ? d_direct + 3 * at : nullptr; f.tuv = d_tuv ? d_tuv + 3 * at : nullptr; f.prim = d_prim ? d_prim + at : nullptr;
         if (!run_pass(sl, nullptr, 0, 0, 1, false, 0, 0, 0xFFFFFFFFu, nullptr, &f)) return false;
     }
-    if (!device && n) {
-        if (out.rgb) HIP_TRY(hipMemcpyAsync(out.rgb, d_rgb, n * 12, hipMemcpyDeviceToHost, stream_));
-        if (out.direct) HIP_TRY(hipMemcpyAsync(out.direct, d_direct, n * 12, hipMemcpyDeviceToHost, stream_));
-        if (out.tuv) HIP_TRY(hipMemcpyAsync(out.tuv, d_tuv, n * 12, hipMemcpyDeviceToHost, stream_));
-        if (out.prim) HIP_TRY(hipMemcpyAsync(out.prim, d_prim, n * 4, hipMemcpyDeviceToHost, stream_));
-    }
+    HIP_TRY(st.download());
     return end_call(n, true);                                         // waits: the staging (and the caller's buffers) are free again
 }
 
@@ -1660,30 +1651,13 @@ bool Renderer::gather(const float* points3, const float* normals3, const uint32_
     const bool sums = out.sum || out.sumsq, hitq = out.hits || out.near;
     const bool sampled = sums || hitq || out.n, traced = sums || hitq;           // n alone needs the walk, not the rays' radiance
     const size_t total = sampled ? npoints * gc.spp : 0;
-    DeviceBuffer<float> s_points, s_normals, s_sum, s_sumsq, s_direct; DeviceBuffer<uint32_t> s_ids, s_n, s_hits, s_near;
-    const float* d_points = points3; const float* d_normals = normals3; const uint32_t* d_ids = ids;
-    mi355rt_gather_outputs d = out;
-    if (!device) {
-        auto up = [&](auto& buf, const auto* src, size_t bytes, auto& dst) {
-            if (buf.alloc(bytes, &hbm_bytes_) != hipSuccess) return false;
-            dst = buf.get();
-            return hipMemcpyAsync(buf.get(), src, bytes, hipMemcpyHostToDevice, stream_) == hipSuccess;
-        };
-        auto stage = [&](auto& buf, auto*& ptr, size_t bytes, bool accumulates) {
-            if (!ptr) return true;
-            if (buf.alloc(bytes, &hbm_bytes_) != hipSuccess) return false;
-            const bool ok = !(accumulates && gc.accumulate) || hipMemcpyAsync(buf.get(), ptr, bytes, hipMemcpyHostToDevice, stream_) == hipSuccess;
-            ptr = buf.get();
-            return ok;
-        };
-        bool ok = up(s_points, points3, npoints * 12, d_points);
-        if (ok && normals3) ok = up(s_normals, normals3, npoints * 12, d_normals);
-        if (ok && ids) ok = up(s_ids, ids, npoints * 4, d_ids);
-        ok = ok && stage(s_n, d.n, npoints * 4, true) && stage(s_hits, d.hits, npoints * 4, true) && stage(s_near, d.near, npoints * 4, true)
-                && stage(s_sum, d.sum, npoints * 12, true) && stage(s_sumsq, d.sumsq, npoints * 12, true) && stage(s_direct, d.direct, npoints * 12, false);
-        if (!ok) return fail(hipGetLastError(), "mi355rt_gather: staging");
-    }
-    const int imode = mode_ == kModeConfirm ? 0 : mode_ == kModeOctreeWalk ? 1 : 2;
+    Staging st(stream_, &hbm_bytes_, device);
+    const float* d_points = st.in(points3, npoints * 3); const float* d_normals = st.in(normals3, npoints * 3); const uint32_t* d_ids = st.in(ids, npoints);
+    const bool acc = gc.accumulate != 0;                              // then the sampled outputs go up first: the call adds to what they hold
+    mi355rt_gather_outputs d{};
+    d.n = st.out(out.n, npoints, acc); d.hits = st.out(out.hits, npoints, acc); d.near = st.out(out.near, npoints, acc);
+    d.sum = st.out(out.sum, npoints * 3, acc); d.sumsq = st.out(out.sumsq, npoints * 3, acc); d.direct = st.out(out.direct, npoints * 3);
+    HIP_TRY(st.error());
     if (d.direct) {
         // (light, point) shadow rays in chunks of at most 4 M rays
         const size_t cpd = std::min(npoints, std::max<size_t>(1, ((size_t)4 << 20) / std::max(nlights_, 1u)));
@@ -1692,23 +1666,17 @@ bool Renderer::gather(const float* points3, const float* normals3, const uint32_
         for (size_t p0 = 0; p0 < npoints; p0 += cpd) {
             const uint32_t cp = (uint32_t)std::min(cpd, npoints - p0);
             HIP_TRY(launch_gather_shadow_rays(stream_, dscene_, d_points, (uint32_t)p0, cp, c_rays.get()));
-            HIP_TRY(launch_intersect(stream_, dscene_, traversal_rows(), imode, c_rays.get(), cp * nlights_, true, nullptr, nullptr, c_blocked.get()));
+            HIP_TRY(launch_intersect(stream_, dscene_, traversal_rows(), (int)mode_, c_rays.get(), cp * nlights_, true, nullptr, nullptr, c_blocked.get()));
             HIP_TRY(launch_gather_direct(stream_, dscene_, d_points, d_normals, (uint32_t)p0, cp, c_blocked.get(), d.direct));
         }
         HIP_TRY(hipStreamSynchronize(stream_));                       // the chunk buffers go out of scope here
     }
     if (total) {
         // rays per chunk: what a pass of trace_rays holds
-        size_t per = (size_t)144 << 20;
-        if (const char* e = getenv("MI355RT_PASS_SAMPLES")) { long v = atol(e); if (v >= 1024) per = (size_t)v; }
-        if (cfg.samples_per_pass) per = std::max<size_t>(1, (size_t)cfg.samples_per_pass * cfg.width * cfg.height);
+        size_t per = cfg.samples_per_pass ? std::max<size_t>(1, (size_t)cfg.samples_per_pass * cfg.width * cfg.height) : pass_sample_budget();
         per = std::min(per, total);
         Slice& sl = slices_[0];
-        while (traced && !ensure_pass_capacity(sl, per)) {
-            if (!alloc_failed_ || per <= 1024) return false;
-            (void)hipGetLastError();
-            per /= 2;
-        }
+        if (traced && !fit_ray_pass(sl, per)) return false;
         const size_t cp_max = std::min(npoints, per), cs_max = std::max<size_t>(1, std::min<size_t>(gc.spp, per / cp_max));
         const size_t cap = cp_max * cs_max;
         DeviceBuffer<float> c_rays, c_rgb, c_tuv; DeviceBuffer<uint32_t> c_keys, c_prim; DeviceBuffer<uint8_t> c_valid; DeviceBuffer<float4> c_hit;
@@ -1734,14 +1702,8 @@ bool Renderer::gather(const float* points3, const float* normals3, const uint32_
         }
         HIP_TRY(hipStreamSynchronize(stream_));                       // the chunk buffers go out of scope here
     }
-    if (!device) {
-        if (total && out.n) HIP_TRY(hipMemcpyAsync(out.n, d.n, npoints * 4, hipMemcpyDeviceToHost, stream_));
-        if (total && out.hits) HIP_TRY(hipMemcpyAsync(out.hits, d.hits, npoints * 4, hipMemcpyDeviceToHost, stream_));
-        if (total && out.near) HIP_TRY(hipMemcpyAsync(out.near, d.near, npoints * 4, hipMemcpyDeviceToHost, stream_));
-        if (total && out.sum) HIP_TRY(hipMemcpyAsync(out.sum, d.sum, npoints * 12, hipMemcpyDeviceToHost, stream_));
-        if (total && out.sumsq) HIP_TRY(hipMemcpyAsync(out.sumsq, d.sumsq, npoints * 12, hipMemcpyDeviceToHost, stream_));
-        if (out.direct) HIP_TRY(hipMemcpyAsync(out.direct, d.direct, npoints * 12, hipMemcpyDeviceToHost, stream_));
-    }
+    if (!total) { st.only(out.n, 0); st.only(out.hits, 0); st.only(out.near, 0); st.only(out.sum, 0); st.only(out.sumsq, 0); }     // spp == 0: nothing was sampled, nothing to copy
+    HIP_TRY(st.download());
     return end_call(traced ? total : 0, true);                        // waits: the staging (and the caller's buffers) are free again
 }
 
@@ -1751,7 +1713,7 @@ bool Renderer::gather(const float* points3, const float* normals3, const uint32_
 // order once (d_bake_tris_, 36 bytes per triangle, counted in hbm_allocated_bytes and kept for the handle's life).
 bool Renderer::bake_texels(const float* uv, uint32_t width, uint32_t height, bool flip, bool device, const mi355rt_bake_texel_outputs& out, uint32_t* ncovered)
 {
-    if (!bind() || !settle_speculation()) return false;
+    if (!quiet()) return false;
     const size_t nt = (size_t)width * height;
     if (out.points && !d_bake_tris_ && ntri) {
         std::vector<float> t9((size_t)ntri * 9);
@@ -1762,34 +1724,18 @@ bool Renderer::bake_texels(const float* uv, uint32_t width, uint32_t height, boo
         }
         if (!upload(d_bake_tris_, t9.data(), t9.size() * sizeof(float))) return false;
     }
-    DeviceBuffer<float> s_uv, s_bary, s_points, s_normals, s_albedo; DeviceBuffer<uint32_t> s_owner, s_ids;
-    const float* d_uv = uv;
-    mi355rt_bake_texel_outputs d = out;
-    if (!device) {
-        HIP_TRY(s_uv.alloc(std::max<size_t>((size_t)ntri * 24, 4), &hbm_bytes_));
-        if (ntri) HIP_TRY(hipMemcpyAsync(s_uv.get(), uv, (size_t)ntri * 24, hipMemcpyHostToDevice, stream_));
-        d_uv = s_uv.get();
-        if (out.ids) { HIP_TRY(s_ids.alloc(nt * 4, &hbm_bytes_)); d.ids = s_ids.get(); }
-        if (out.points) { HIP_TRY(s_points.alloc(nt * 12, &hbm_bytes_)); d.points = s_points.get(); }
-        if (out.normals) { HIP_TRY(s_normals.alloc(nt * 12, &hbm_bytes_)); d.normals = s_normals.get(); }
-        if (out.albedo) { HIP_TRY(s_albedo.alloc(nt * 12, &hbm_bytes_)); d.albedo = s_albedo.get(); }
-    }
-    if (!device || !out.owner) { HIP_TRY(s_owner.alloc(nt * 4, &hbm_bytes_)); d.owner = s_owner.get(); }
-    if (!device || !out.bary) {
-        HIP_TRY(s_bary.alloc(nt * 8, &hbm_bytes_)); d.bary = s_bary.get();
-        if (out.bary) HIP_TRY(hipMemcpyAsync(s_bary.get(), out.bary, nt * 8, hipMemcpyHostToDevice, stream_));      // uncovered texels keep what the caller had
-    }
+    Staging st(stream_, &hbm_bytes_, device);
+    const float* d_uv = st.in(uv, (size_t)ntri * 6, true);            // ntri == 0: the callee still takes a pointer
+    mi355rt_bake_texel_outputs d{};
+    d.owner = st.scratch(out.owner, nt);                              // the rasteriser writes owner and bary whether or not the caller asked
+    d.bary = st.scratch(out.bary, nt * 2, true);                      // uncovered texels keep what the caller had
+    d.ids = st.out(out.ids, nt); d.points = st.out(out.points, nt * 3); d.normals = st.out(out.normals, nt * 3); d.albedo = st.out(out.albedo, nt * 3);
+    HIP_TRY(st.error());
     uint32_t n = 0;
     HIP_TRY(bake_texels_device(stream_, dscene_, d_bake_tris_.get(), d_uv, ntri, width, height, flip, d.owner, d.bary, d.ids, d.points, d.normals, d.albedo, &n, &hbm_bytes_));
-    if (!device) {
-        if (out.owner) HIP_TRY(hipMemcpyAsync(out.owner, d.owner, nt * 4, hipMemcpyDeviceToHost, stream_));
-        if (out.bary) HIP_TRY(hipMemcpyAsync(out.bary, d.bary, nt * 8, hipMemcpyDeviceToHost, stream_));
-        if (n && out.ids) HIP_TRY(hipMemcpyAsync(out.ids, d.ids, (size_t)n * 4, hipMemcpyDeviceToHost, stream_));
-        if (n && out.points) HIP_TRY(hipMemcpyAsync(out.points, d.points, (size_t)n * 12, hipMemcpyDeviceToHost, stream_));
-        if (n && out.normals) HIP_TRY(hipMemcpyAsync(out.normals, d.normals, (size_t)n * 12, hipMemcpyDeviceToHost, stream_));
-        if (n && out.albedo) HIP_TRY(hipMemcpyAsync(out.albedo, d.albedo, (size_t)n * 12, hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipStreamSynchronize(stream_));
-    }
+    st.only(out.ids, n); st.only(out.points, (size_t)n * 3); st.only(out.normals, (size_t)n * 3); st.only(out.albedo, (size_t)n * 3);     // the n covered entries
+    HIP_TRY(st.download());
+    if (!device) HIP_TRY(hipStreamSynchronize(stream_));
     if (ncovered) *ncovered = n;
     return true;
 }
@@ -1797,24 +1743,16 @@ bool Renderer::bake_texels(const float* uv, uint32_t width, uint32_t height, boo
 // mi355rt_bake_atlas: the ids are checked on the device first; verdict != 0: refused, nothing written (the caller words the error)
 bool Renderer::bake_atlas(const uint32_t* ids, const float* values3, uint32_t n, uint32_t width, uint32_t height, uint32_t dilate, bool device, float* atlas, uint8_t* valid, uint32_t& verdict)
 {
-    if (!bind() || !settle_speculation()) return false;
+    if (!quiet()) return false;
     const size_t nt = (size_t)width * height;
-    DeviceBuffer<uint32_t> s_ids; DeviceBuffer<float> s_values, s_atlas; DeviceBuffer<uint8_t> s_valid;
-    const uint32_t* d_ids = ids; const float* d_values = values3; float* d_atlas = atlas; uint8_t* d_valid = valid;
-    if (!device) {
-        HIP_TRY(s_ids.alloc(std::max<size_t>((size_t)n * 4, 4), &hbm_bytes_)); HIP_TRY(s_values.alloc(std::max<size_t>((size_t)n * 12, 4), &hbm_bytes_));
-        if (n) { HIP_TRY(hipMemcpyAsync(s_ids.get(), ids, (size_t)n * 4, hipMemcpyHostToDevice, stream_)); HIP_TRY(hipMemcpyAsync(s_values.get(), values3, (size_t)n * 12, hipMemcpyHostToDevice, stream_)); }
-        d_ids = s_ids.get(); d_values = s_values.get();
-    }
-    if (!device || !atlas) { HIP_TRY(s_atlas.alloc(nt * 12, &hbm_bytes_)); d_atlas = s_atlas.get(); }
-    if (!device || !valid) { HIP_TRY(s_valid.alloc(nt, &hbm_bytes_)); d_valid = s_valid.get(); }
+    Staging st(stream_, &hbm_bytes_, device);
+    const uint32_t* d_ids = st.in(ids, n, true); const float* d_values = st.in(values3, (size_t)n * 3, true);      // n == 0: the callee still takes pointers
+    float* d_atlas = st.scratch(atlas, nt * 3); uint8_t* d_valid = st.scratch(valid, nt);                          // the fill works on both, whichever the caller asked for
+    HIP_TRY(st.error());
     HIP_TRY(bake_atlas_device(stream_, d_ids, d_values, n, width, height, dilate, d_atlas, d_valid, &verdict, &hbm_bytes_));
-    if (verdict) return true;
-    if (!device) {
-        if (atlas) HIP_TRY(hipMemcpyAsync(atlas, d_atlas, nt * 12, hipMemcpyDeviceToHost, stream_));
-        if (valid) HIP_TRY(hipMemcpyAsync(valid, d_valid, nt, hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipStreamSynchronize(stream_));
-    }
+    if (verdict) return true;                                         // refused: nothing is copied back
+    HIP_TRY(st.download());
+    if (!device) HIP_TRY(hipStreamSynchronize(stream_));
     return true;
 }
 
@@ -1824,13 +1762,9 @@ bool Renderer::render_rays(const float* rays6, uint32_t spp, bool device)
 {
     if (!begin_call()) return false;
     const size_t nrays = (size_t)cfg.width * cfg.height * spp;
-    DeviceBuffer<float> s_rays;
-    const float* d_rays = rays6;
-    if (!device) {
-        HIP_TRY(s_rays.alloc(nrays * 24, &hbm_bytes_));
-        HIP_TRY(hipMemcpyAsync(s_rays.get(), rays6, nrays * 24, hipMemcpyHostToDevice, stream_));
-        d_rays = s_rays.get();
-    }
+    Staging st(stream_, &hbm_bytes_, device);
+    const float* d_rays = st.in(rays6, nrays * 6);
+    HIP_TRY(st.error());
     HIP_TRY(hipEventRecord(slices_[0].done, stream_));                // the other slices fork behind the upload (slice 0 runs on the main stream; its `done` event is free here)
     RayFeed f{};
     f.mode = 1u; f.rays = d_rays;
@@ -1845,8 +1779,7 @@ bool Renderer::render_rays(const float* rays6, uint32_t spp, bool device)
 bool Renderer::set_lens(const mi355rt_lens& l)
 {
     if (std::memcmp(&l, &lens_, sizeof l) == 0) return true;
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     lens_ = l;
     return true;
 }
@@ -1855,14 +1788,13 @@ bool Renderer::set_lens(const mi355rt_lens& l)
 // device buffer.  Nothing of the handle changes.
 bool Renderer::lens_rays(uint32_t spp, bool device, float* rays6)
 {
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     const size_t nrays = (size_t)cfg.width * cfg.height * spp;
-    DeviceBuffer<float> stage;
-    float* d = rays6;
-    if (!device) { HIP_TRY(stage.alloc(nrays * 24, &hbm_bytes_)); d = stage.get(); }
+    Staging st(stream_, &hbm_bytes_, device);
+    float* d = st.out(rays6, nrays * 6);
+    HIP_TRY(st.error());
     HIP_TRY(launch_lens_rays(stream_, device_camera(), cfg.flags, (uint32_t)cfg.seed, spp, d_film_n_.get(), d));
-    if (!device) HIP_TRY(hipMemcpyAsync(rays6, d, nrays * 24, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(st.download());
     HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's buffer is complete, on whatever stream it is used next
     return true;
 }
@@ -1871,15 +1803,12 @@ bool Renderer::debug_numerics(const float* a, const float* b, size_t n, float* q
 {
     if (!bind()) return false;
     if (n == 0) return true;
-    DeviceBuffer<float> buf;
-    HIP_TRY(buf.alloc(n * 4 * 5));
-    float* d = buf.get();
-    HIP_TRY(hipMemcpyAsync(d, a, n * 4, hipMemcpyHostToDevice, stream_));
-    HIP_TRY(hipMemcpyAsync(d + n, b, n * 4, hipMemcpyHostToDevice, stream_));
-    HIP_TRY(launch_numerics(stream_, d, d + n, (uint32_t)n, d + 2 * n, d + 3 * n, d + 4 * n));
-    HIP_TRY(hipMemcpyAsync(q, d + 2 * n, n * 4, hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipMemcpyAsync(r, d + 3 * n, n * 4, hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipMemcpyAsync(p, d + 4 * n, n * 4, hipMemcpyDeviceToHost, stream_));
+    Staging st(stream_, &hbm_bytes_, false);
+    const float* d_a = st.in(a, n); const float* d_b = st.in(b, n);
+    float* d_q = st.out(q, n); float* d_r = st.out(r, n); float* d_p = st.out(p, n);
+    HIP_TRY(st.error());
+    HIP_TRY(launch_numerics(stream_, d_a, d_b, (uint32_t)n, d_q, d_r, d_p));
+    HIP_TRY(st.download());
     HIP_TRY(hipStreamSynchronize(stream_));
     return true;
 }
@@ -1919,15 +1848,12 @@ bool Renderer::debug_slab(const float* inv_rays6, const float* cubes6, size_t n,
     if (!bind()) return false;
     if (n == 0) return true;
     if (n > (1u << 24)) { last_error = "too many slab tests in one batch"; return false; }
-    DeviceBuffer<float> buf; DeviceBuffer<uint8_t> dh;
-    HIP_TRY(buf.alloc(n * 4 * 13));
-    HIP_TRY(dh.alloc(n));
-    float* d = buf.get();
-    HIP_TRY(hipMemcpyAsync(d, inv_rays6, n * 24, hipMemcpyHostToDevice, stream_));
-    HIP_TRY(hipMemcpyAsync(d + 6 * n, cubes6, n * 24, hipMemcpyHostToDevice, stream_));
-    HIP_TRY(launch_slab(stream_, d, d + 6 * n, (uint32_t)n, dh.get(), d + 12 * n));
-    HIP_TRY(hipMemcpyAsync(hit, dh.get(), n, hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipMemcpyAsync(tmin, d + 12 * n, n * 4, hipMemcpyDeviceToHost, stream_));
+    Staging st(stream_, &hbm_bytes_, false);
+    const float* d_rays = st.in(inv_rays6, n * 6); const float* d_cubes = st.in(cubes6, n * 6);
+    uint8_t* d_hit = st.out(hit, n); float* d_tmin = st.out(tmin, n);
+    HIP_TRY(st.error());
+    HIP_TRY(launch_slab(stream_, d_rays, d_cubes, (uint32_t)n, d_hit, d_tmin));
+    HIP_TRY(st.download());
     HIP_TRY(hipStreamSynchronize(stream_));
     return true;
 }
@@ -1935,13 +1861,13 @@ bool Renderer::debug_slab(const float* inv_rays6, const float* cubes6, size_t n,
 // Film::get_pixels / get_estimated_variances computed on the device, downloaded as width*height*3 floats
 bool Renderer::film_stat(bool variances, float* rgb)
 {
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     const size_t npix = (size_t)cfg.width * cfg.height;
-    DeviceBuffer<float> d;
-    HIP_TRY(d.alloc(npix * 12));
-    HIP_TRY(launch_film_stat(stream_, variances, npix, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d.get()));
-    HIP_TRY(hipMemcpyAsync(rgb, d.get(), npix * 12, hipMemcpyDeviceToHost, stream_));
+    Staging st(stream_, &hbm_bytes_, false);
+    float* d = st.out(rgb, npix * 3);
+    HIP_TRY(st.error());
+    HIP_TRY(launch_film_stat(stream_, variances, npix, d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d));
+    HIP_TRY(st.download());
     HIP_TRY(hipStreamSynchronize(stream_));
     return true;
 }
@@ -1983,20 +1909,15 @@ bool Renderer::feature_view_current() { return feat_stamp_ == kFeatCamera && fea
 
 bool Renderer::features_render(const float* rays6, uint32_t spp, bool device)
 {
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     if (!ensure_features()) return false;
     const size_t nrays = (size_t)cfg.width * cfg.height * spp;
-    DeviceBuffer<float> stage;
-    const float* d_rays = rays6;
-    if (rays6 && !device) {
-        HIP_TRY(stage.alloc(nrays * 24, &hbm_bytes_));
-        HIP_TRY(hipMemcpyAsync(stage.get(), rays6, nrays * 24, hipMemcpyHostToDevice, stream_));
-        d_rays = stage.get();
-    }
+    Staging st(stream_, &hbm_bytes_, device);
+    const float* d_rays = st.in(rays6, nrays * 6);                    // null: the handle's own rays
+    HIP_TRY(st.error());
     const DCamera cam = device_camera();
     HIP_TRY(launch_features(stream_, dscene_, cam, cfg.flags & MI355RT_FLAG_FIX_ROW_INDEX, (uint32_t)cfg.seed, traversal_rows(),
-                            mode_ == kModeConfirm ? 0 : mode_ == kModeOctreeWalk ? 1 : 2, d_owned_rows_.get(), (uint32_t)owned_rows.size(), spp, d_rays, feat_));
+                            (int)mode_, d_owned_rows_.get(), (uint32_t)owned_rows.size(), spp, d_rays, feat_));
     if (feat_stamp_ == kFeatEmpty) {
         feat_stamp_ = rays6 ? kFeatRays : kFeatCamera;
         if (!rays6) feat_key_ = view_key();
@@ -2008,8 +1929,7 @@ bool Renderer::features_render(const float* rays6, uint32_t spp, bool device)
 
 bool Renderer::features_clear()
 {
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     feat_stamp_ = kFeatEmpty; feat_key_.clear();
     ++feat_version_;
     if (!d_features_) return true;
@@ -2021,8 +1941,7 @@ bool Renderer::features_clear()
 // A feature film that was never allocated reads as the zeros it would hold
 bool Renderer::features_get(uint32_t* n, uint32_t* hits, float* depth, float* normal3, float* albedo3)
 {
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     const size_t npix = (size_t)cfg.width * cfg.height;
     if (!d_features_) {
         if (n) std::memset(n, 0, npix * 4);
@@ -2043,14 +1962,14 @@ bool Renderer::features_get(uint32_t* n, uint32_t* hits, float* depth, float* no
 
 bool Renderer::features_alpha(float* alpha)
 {
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     const size_t npix = (size_t)cfg.width * cfg.height;
     if (!d_features_) { std::memset(alpha, 0, npix * 4); return true; }
-    DeviceBuffer<float> d;
-    HIP_TRY(d.alloc(npix * 4, &hbm_bytes_));
-    HIP_TRY(launch_features_alpha(stream_, (uint32_t)npix, feat_, d.get()));
-    HIP_TRY(hipMemcpyAsync(alpha, d.get(), npix * 4, hipMemcpyDeviceToHost, stream_));
+    Staging st(stream_, &hbm_bytes_, false);
+    float* d = st.out(alpha, npix);
+    HIP_TRY(st.error());
+    HIP_TRY(launch_features_alpha(stream_, (uint32_t)npix, feat_, d));
+    HIP_TRY(st.download());
     HIP_TRY(hipStreamSynchronize(stream_));
     return true;
 }
@@ -2090,7 +2009,7 @@ bool Renderer::refresh_guides()
     const std::vector<float> key = view_key();
     if (key == guides_key_) return true;
     guides_key_.clear();
-    HIP_TRY(launch_guides(stream_, dscene_, cam, cfg.flags & MI355RT_FLAG_FIX_ROW_INDEX, traversal_rows(), mode_ == kModeConfirm ? 0 : mode_ == kModeOctreeWalk ? 1 : 2,
+    HIP_TRY(launch_guides(stream_, dscene_, cam, cfg.flags & MI355RT_FLAG_FIX_ROW_INDEX, traversal_rows(), (int)mode_,
                           d_guide0_.get(), d_guide1_.get()));
     guides_key_ = key;
     return true;
@@ -2098,8 +2017,7 @@ bool Renderer::refresh_guides()
 
 bool Renderer::get_guides(float* depth, float* normal3, float* albedo3, uint32_t* prim)
 {
-    if (!bind()) return false;
-    if (!settle_speculation()) return false;
+    if (!quiet()) return false;
     if (!refresh_guides()) return false;
     const size_t npix = (size_t)cfg.width * cfg.height;
     std::vector<float4> g0(npix), g1(npix);
@@ -2198,9 +2116,7 @@ bool Renderer::get_display(const mi355rt_display_config& dc, const mi355rt_denoi
         if (!display_hist_queue(img, film, hist)) return false;
         E = display_auto_exposure(hist, dc.key, dc.low, dc.high);
     }
-    DisplayArgs a{};
-    a.curve = dc.curve; a.transfer = dc.transfer; a.exposure = E; a.white2 = dc.white * dc.white;
-    HIP_TRY(launch_display_pack(stream_, a, (uint32_t)npix, img, d_film_n_.get(), film, d_disp_table_.get(), d_disp_packed_.get()));
+    HIP_TRY(launch_display_pack(stream_, display_args(&dc, E), (uint32_t)npix, img, d_film_n_.get(), film, d_disp_table_.get(), d_disp_packed_.get()));
     HIP_TRY(hipMemcpyAsync(packed, d_disp_packed_.get(), npix * 4, hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     exposure_used = E;
@@ -2213,18 +2129,16 @@ bool Renderer::get_display(const mi355rt_display_config& dc, const mi355rt_denoi
 bool Renderer::display_image(const float* rgb3, size_t npix, const mi355rt_display_config* dc, uint32_t* packed)
 {
     if (!bind()) return false;
-    DeviceBuffer<float> img, tab; DeviceBuffer<uint32_t> cnt, out;
-    HIP_TRY(img.alloc(npix * 12, &hbm_bytes_)); HIP_TRY(cnt.alloc(npix * 4, &hbm_bytes_)); HIP_TRY(out.alloc(npix * 4, &hbm_bytes_)); HIP_TRY(tab.alloc(256 * sizeof(float), &hbm_bytes_));
     float t[256];
-    t[0] = 0.0f;                               // never read: the search starts above it
-    display_srgb_thresholds(t + 1);
-    HIP_TRY(hipMemcpyAsync(tab.get(), t, sizeof t, hipMemcpyHostToDevice, stream_));
-    HIP_TRY(hipMemcpyAsync(img.get(), rgb3, npix * 12, hipMemcpyHostToDevice, stream_));
-    HIP_TRY(hipMemsetAsync(cnt.get(), 0, npix * 4, stream_));
-    DisplayArgs a{};
-    a.curve = dc ? dc->curve : MI355RT_CURVE_REINHARD; a.transfer = dc ? dc->transfer : MI355RT_TRANSFER_REFERENCE; a.exposure = dc ? dc->exposure : 1.0f; a.white2 = dc ? dc->white * dc->white : 16.0f;
-    HIP_TRY(launch_display_pack(stream_, a, (uint32_t)npix, img.get(), cnt.get(), false, tab.get(), out.get()));
-    HIP_TRY(hipMemcpyAsync(packed, out.get(), npix * 4, hipMemcpyDeviceToHost, stream_));
+    display_srgb_table(t);
+    Staging st(stream_, &hbm_bytes_, false);
+    const float* tab = st.in(t, 256); const float* img = st.in(rgb3, npix * 3);
+    uint32_t* cnt = st.scratch<uint32_t>(nullptr, npix);
+    uint32_t* out = st.out(packed, npix);
+    HIP_TRY(st.error());
+    HIP_TRY(hipMemsetAsync(cnt, 0, npix * 4, stream_));
+    HIP_TRY(launch_display_pack(stream_, display_args(dc, dc ? dc->exposure : 1.0f), (uint32_t)npix, img, cnt, false, tab, out));
+    HIP_TRY(st.download());
     HIP_TRY(hipStreamSynchronize(stream_));
     return true;
 }

@@ -144,11 +144,13 @@ public:
     double lbvh_device_ms_ = 0.0;         // its device time (kernels + sort)
     enum Mode { kModeConfirm = 0, kModeOctreeWalk = 1, kModeTrueClosest = 2 };
     Mode mode_ = kModeConfirm;            // intersector semantics, fixed at creation
+    static_assert(kModeConfirm == 0 && kModeOctreeWalk == 1 && kModeTrueClosest == 2, "the launches take (int)mode_ (kernels.hpp, launch_intersect)");
 
 private:
     Renderer() = default;
     bool init(const SceneData& scene, std::string& err, int& code);
     bool bind();
+    bool quiet();                         // bind() and settle_speculation()
     bool fail(hipError_t e, const char* what);
     // A frame slice: an interleaved share of the owned rows with its own stream and pass buffers.  The
     // slices of one render() call run concurrently, so that the drain window at the end of one slice's
@@ -179,6 +181,8 @@ private:
         void release_pass_buffers() { for_each_pass_buffer([](auto& b) { b.reset(); }); capacity = 0; }
     };
     bool ensure_pass_capacity(Slice& sl, size_t nsamples);
+    size_t pass_sample_budget() const;                                  // samples per pass: the default or MI355RT_PASS_SAMPLES (config.samples_per_pass is the callers' matter)
+    bool fit_ray_pass(Slice& sl, size_t& per);                          // ensure_pass_capacity(sl, per), per halved while the device is out of memory
     void free_pass_buffers();
     bool assign_slice_rows(uint32_t nslices);
     // A ray-fed pass (DPass::ray_in ...).  mode 1: the film's pixels with the caller's rays (base: the call's sample number of the pass's first
