@@ -862,6 +862,65 @@ float mi355rt_bake_point(float a, float e1, float e2, float u, float v);
 uint32_t mi355rt_bake_dilate_texel(const float* atlas3, const uint8_t* valid, uint32_t width, uint32_t height, uint32_t x, uint32_t y, float rgb3[3]);
 int  mi355rt_bake_auto_atlas(uint32_t ntri, uint32_t width, uint32_t height, uint32_t gutter, float* uv /* ntri x 6 */, uint32_t* cell /* may be NULL */);
 
+/* ---- PROBES: gathered light as spherical-harmonic coefficients, and a grid lookup (no reference counterpart).
+ * A probe is a film of its own: per point n and 9 x 3 sums (and hits, near), accumulated in sample order over mi355rt_gather's SPHERE-MODE samples.  The
+ * lookup is a read-out of such a film laid out as a grid.  raytracer-rs_amd/probes.py states all of it.  Everything is f32, unfused, in the order written.
+ *
+ * THE BASIS.  Real spherical harmonics up to band 2, polynomial in the direction d = (x, y, z), which is used as given:
+ *     b_0 = c0          b_1 = c1 * y        b_2 = c1 * z                          b_3 = c1 * x        b_4 = c2 * (x * y)
+ *     b_5 = c2 * (y * z)                    b_6 = c3 * (3.0f * (z * z) - 1.0f)    b_7 = c2 * (x * z)  b_8 = c4 * (x * x - y * y)
+ *     c0 = 0.282094792f, c1 = 0.488602512f, c2 = 1.092548431f, c3 = 0.315391565f, c4 = 0.546274215f
+ *
+ * GATHER.  Sample s of point i is exactly mi355rt_gather's sphere-mode sample: key (id_i, first_sample + s), hash stream 0xFFFFFFFE, d = table[start], ray
+ * (point + 0.00001f * d, d), traced under its key as mi355rt_trace_rays traces it.  Per point, in sample order:
+ *     sh[k][c] += b_k(d) * rgb_c   (one multiply, one add);   n += 1;   hits += hit;   near += hit && t < near_distance
+ * sh is npoints x 9 x 3 floats.  accumulate != 0: the outputs are read, added to and written back, so probes_gather(3) followed by probes_gather(5,
+ * first_sample 3, accumulate) is probes_gather(8) bit for bit; otherwise they start from 0.  The radiance arriving from direction w is estimated by
+ * sum_k (4 pi / n) * sh[k] * b_k(w): the table is uniform on the sphere.
+ * Around the call mi355rt_gather's rules hold: a speculative frame is settled and a queued one runs ahead; every film, camera, lens, current row, caller-ray
+ * mark and guide is untouched; mi355rt_last_counts reports the rays (npoints * spp primary); striped handles serve it; every temporary is freed by the end of
+ * the call (pass buffers that grew excepted).  `where` as for mi355rt_gather.
+ * ERRORS.  MI355RT_E_INVALID, the argument named in mi355rt_last_error and nothing written, for: NULL points3 with npoints > 0; out NULL or all of its
+ * pointers NULL; cfg NULL; spp == 0; an unknown where; a NaN near_distance; npoints * spp >= 2^32; first_sample + spp overflowing 32 bits; a device group.
+ * npoints == 0 succeeds and writes nothing.
+ *
+ * LOOKUP of one query (p, dir) in a grid.  Probe (ix, iy, iz) has index (iz * ny + iy) * nx + ix and sits at origin_a + (float)i_a * spacing_a; n is u32 per
+ * probe, sh f32 [probe][9][3] (the sums above), usable u8 per probe (optional).  In this order:
+ *     per axis a:  g = (p_a - origin_a) / spacing_a;  g = g >= 0.0f ? g : 0.0f  (a NaN becomes 0: no index is ever made from a NaN);
+ *                  top = (float)(count_a - 1);  g = g <= top ? g : top;  i = (uint32_t)g;  if (count_a >= 2 && i > count_a - 2) i = count_a - 2;
+ *                  f = g - (float)i;  with count_a == 1: i = 0, f = 0
+ *     corner j = 0 .. 7: bit 0 is x + 1, bit 1 is y + 1, bit 2 is z + 1, the index clamped to count_a - 1;  t_j = (wx * wy) * wz with w_a = f_a for a set
+ *                  bit and 1.0f - f_a otherwise.  A corner is SKIPPED if t_j == 0, if n_j == 0, or if usable is given and usable[j] == 0; a skipped corner
+ *                  is never read into a sum, so an infinity in it cannot make a NaN out of a zero weight
+ *     over the corners used, in j order, from +0.0f:  wsum += t_j;  s_j = t_j * (12.566370614f / (float)n_j);  C[k][c] += s_j * sh_j[k][c]
+ *     MI355RT_SH_RADIANCE (from dir):         r_c = sum_k C[k][c] * b_k(dir), in k order from +0.0f
+ *     MI355RT_SH_IRRADIANCE (at normal dir):  r_c = sum_k (A_k * C[k][c]) * b_k(dir);  A_0 = 3.14159265f, A_1..A_3 = 2.09439510f, A_4..A_8 = 0.785398163f
+ *     rgb_c = r_c / wsum, ok = 1;  no corner used: rgb = 0, ok = 0
+ * Nothing is clamped: a band-2 irradiance can ring below zero, and that is data.
+ * mi355rt_probes_lookup traces nothing.  Around the call mi355rt_bake_texels' rules hold: films, camera, lens and mi355rt_last_counts are untouched, a striped
+ * handle serves it.  `where` as for mi355rt_gather: every pointer is host memory, staged, or device memory used in place on the handle's stream.
+ * ERRORS.  MI355RT_E_INVALID, the argument named in mi355rt_last_error and nothing written, for: grid NULL; a zero count; a count product of 2^31 or more; a
+ * spacing that is not finite and positive; a non-finite origin; n, sh or rgb3 NULL; points3 or dirs3 NULL with npoints > 0; an unknown mode; an unknown
+ * where; a device group.  npoints == 0 succeeds and writes nothing.
+ *
+ * Host only, no handle, the same header the kernels compile (csrc/sh9.hpp): mi355rt_sh9_basis (THE BASIS), mi355rt_probes_lookup_one (LOOKUP of one query,
+ * *ok may be NULL; the grid is checked as above, the message in mi355rt_last_error(NULL)), mi355rt_probe_grid_points (the probes' positions in index order,
+ * counts product x 3 floats). */
+#define MI355RT_SH_RADIANCE   0u
+#define MI355RT_SH_IRRADIANCE 1u
+typedef struct mi355rt_probe_config  { uint32_t spp, first_sample, accumulate; float near_distance; } mi355rt_probe_config;   /* 16 bytes */
+typedef struct mi355rt_probe_outputs { uint32_t *n, *hits, *near; float *sh; } mi355rt_probe_outputs;   /* sh: npoints x 9 x 3; any may be NULL, not all */
+typedef struct mi355rt_probe_grid    { float origin[3], spacing[3]; uint32_t counts[3]; } mi355rt_probe_grid;   /* 36 bytes */
+void mi355rt_probes_default_config(mi355rt_probe_config* cfg);   /* spp 64, first_sample 0, accumulate 0, near_distance +inf */
+int  mi355rt_probes_gather(mi355rt_handle* h, const float* points3, const uint32_t* ids /* NULL: i */, size_t npoints, const mi355rt_probe_config* cfg, uint32_t where,
+                           const mi355rt_probe_outputs* out);
+int  mi355rt_probes_lookup(mi355rt_handle* h, const mi355rt_probe_grid* grid, const uint32_t* n, const float* sh, const uint8_t* usable /* may be NULL */,
+                           const float* points3, const float* dirs3, size_t npoints, uint32_t mode, uint32_t where, float* rgb3, uint8_t* ok /* may be NULL */);
+int  mi355rt_sh9_basis(const float dir[3], float b[9]);
+int  mi355rt_probes_lookup_one(const mi355rt_probe_grid* grid, const uint32_t* n, const float* sh, const uint8_t* usable /* may be NULL */, const float point[3],
+                               const float dir[3], uint32_t mode, float rgb[3], uint32_t* ok /* may be NULL */);
+int  mi355rt_probe_grid_points(const mi355rt_probe_grid* grid, float* points3);
+
 /* SampleGenerator table, sample_generator.rs:15-24: 65 536 x 3 floats */
 int mi355rt_get_sample_table(const mi355rt_handle* h, float* out);
 /* Per-node direct-light terms of one primary sample, computed on the device by the same

@@ -175,6 +175,35 @@ class BakeTexelOutputs(C.Structure):
 
 BAKE_TEXEL_OUTPUTS = ("owner", "bary", "ids", "points", "normals", "albedo")
 
+SH_RADIANCE, SH_IRRADIANCE = 0, 1      # MI355RT_SH_*
+SH_MODES = {"radiance": SH_RADIANCE, "irradiance": SH_IRRADIANCE}
+
+
+class ProbeConfig(C.Structure):
+    """mi355rt_probe_config (include/mi355rt.h, "PROBES")"""
+    _fields_ = [("spp", C.c_uint32), ("first_sample", C.c_uint32), ("accumulate", C.c_uint32), ("near_distance", C.c_float)]
+
+
+class ProbeOutputs(C.Structure):
+    """mi355rt_probe_outputs: any pointer may be NULL, not all of them (void pointers here: host arrays or device addresses); sh is npoints x 9 x 3"""
+    _fields_ = [("n", C.c_void_p), ("hits", C.c_void_p), ("near", C.c_void_p), ("sh", C.c_void_p)]
+
+
+class ProbeGrid(C.Structure):
+    """mi355rt_probe_grid: probe (ix, iy, iz) has index (iz * ny + iy) * nx + ix and sits at origin + float(i) * spacing"""
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("counts", C.c_uint32 * 3)]
+
+    @classmethod
+    def from_dict(cls, d):
+        """from the dict raytracer_rs_amd.probes uses: origin, spacing (3 floats each), counts (3 ints)"""
+        g = cls()
+        for a in range(3):
+            g.origin[a], g.spacing[a], g.counts[a] = float(np.float32(d["origin"][a])), float(np.float32(d["spacing"][a])), int(d["counts"][a])
+        return g
+
+
+PROBE_OUTPUTS = ("n", "hits", "near", "sh")
+
 LENS_PINHOLE, LENS_THIN, LENS_ORTHO = 0, 1, 2      # MI355RT_LENS_*
 LENS_MODELS = {"pinhole": LENS_PINHOLE, "thin": LENS_THIN, "ortho": LENS_ORTHO}
 
@@ -257,6 +286,13 @@ ABI = [
     ("mi355rt_bake_point", C.c_float, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
     ("mi355rt_bake_dilate_texel", C.c_uint32, [_F, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _F]),
     ("mi355rt_bake_auto_atlas", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _F, _U]),
+    ("mi355rt_probes_default_config", None, [C.POINTER(ProbeConfig)]),
+    ("mi355rt_probes_gather", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ProbeConfig), C.c_uint32, C.POINTER(ProbeOutputs)]),
+    ("mi355rt_probes_lookup", C.c_int, [_H, C.POINTER(ProbeGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                        C.c_void_p, C.c_void_p]),
+    ("mi355rt_sh9_basis", C.c_int, [_F, _F]),
+    ("mi355rt_probes_lookup_one", C.c_int, [C.POINTER(ProbeGrid), _U, _F, C.POINTER(C.c_uint8), _F, _F, C.c_uint32, _F, _U]),
+    ("mi355rt_probe_grid_points", C.c_int, [C.POINTER(ProbeGrid), _F]),
     ("mi355rt_lens_default", None, [C.POINTER(Lens)]),
     ("mi355rt_set_lens", C.c_int, [_H, C.POINTER(Lens)]),
     ("mi355rt_get_lens", C.c_int, [_H, C.POINTER(Lens)]),
@@ -992,6 +1028,89 @@ class RayTracer:
             torch.cuda.current_stream(points.device).synchronize()          # what produced the inputs (and the zero fill) has finished: the library's stream knows nothing of torch's
         self._check(lib().mi355rt_gather(self._h, addr, naddr, iaddr, n, C.byref(cfg), RAYS_DEVICE if dev else RAYS_HOST, C.byref(o)))
         return res
+
+    @staticmethod
+    def _sh_array(a, name, rows):
+        """_ray_array for a (rows, 9, 3) float32 argument: checked as the (rows, 27) view of the same memory"""
+        if (_is_tensor(a) or isinstance(a, np.ndarray)) and len(a.shape) == 3 and tuple(a.shape) == (rows, 9, 3):
+            if not (a.is_contiguous() if _is_tensor(a) else a.flags["C_CONTIGUOUS"]):
+                raise ValueError("%s: must be C-contiguous" % name)                 # before the reshape, which would copy
+            return _ray_array(a.reshape(rows, 27), name, 27, np.float32, rows=rows)
+        if _is_tensor(a) or isinstance(a, np.ndarray):
+            raise ValueError("%s: shape must be (%d, 9, 3), not %s" % (name, rows, tuple(a.shape)))
+        raise TypeError("%s: a numpy array or a torch tensor, not %s" % (name, type(a).__name__))
+
+    def probes_gather(self, points, ids=None, spp=64, first_sample=0, near_distance=float("inf"), want=("n", "sh"), into=None):
+        """mi355rt_probes_gather: the light arriving at probes from the whole sphere, projected onto the nine real spherical harmonics up to band 2
+        (raytracer_rs_amd.probes is the statement).  The samples are gather's sphere-mode samples.  points: float32 (n, 3); ids: uint32 (n,) keys of the
+        points' random numbers, None: i; want: any of "n", "hits", "near", "sh" (float32 (n, 9, 3) sums).  numpy arrays or torch tensors on the handle's GPU,
+        under gather's rules.  into: the dict of an earlier call; its arrays are added to and returned: probes_gather(spp=3) then probes_gather(spp=5,
+        first_sample=3, into=res) is probes_gather(spp=8) bit for bit.  Returns a dict name -> array.  No film, camera or lens state changes."""
+        want = tuple(want)
+        if not want or any(w not in PROBE_OUTPUTS for w in want) or len(set(want)) != len(want):
+            raise ValueError("want: a non-empty selection of %s without repeats, not %r" % (PROBE_OUTPUTS, want))
+        addr, n, dev = _ray_array(points, "points", 3, np.float32)
+        iaddr = None
+        if ids is not None:
+            iaddr, _, idev = _ray_vector(ids, "ids", np.uint32, n)
+            if idev != dev:
+                raise ValueError("ids must live where points live (both numpy arrays, or both tensors on the GPU)")
+        cfg = ProbeConfig()
+        lib().mi355rt_probes_default_config(C.byref(cfg))
+        cfg.spp, cfg.first_sample, cfg.accumulate, cfg.near_distance = int(spp), int(first_sample), 1 if into is not None else 0, float(near_distance)
+        res, o = {}, ProbeOutputs()
+        if dev:
+            import torch
+        for w in want:
+            if into is not None:
+                if w not in into:
+                    raise ValueError("into: holds no %r" % w)
+                a = into[w]
+                a_addr, _, adev = self._sh_array(a, "into[%r]" % w, n) if w == "sh" else _ray_vector(a, "into[%r]" % w, np.uint32, n)
+                if adev != dev:
+                    raise ValueError("into[%r] must live where points live" % w)
+            elif dev:
+                a = torch.zeros((n, 9, 3) if w == "sh" else (n,), dtype=torch.float32 if w == "sh" else torch.int32, device=points.device)
+                a_addr = a.data_ptr()
+            else:
+                a = np.zeros((n, 9, 3), np.float32) if w == "sh" else np.zeros(n, np.uint32)
+                a_addr = a.ctypes.data
+            res[w] = a
+            setattr(o, w, a_addr)
+        if dev:
+            torch.cuda.current_stream(points.device).synchronize()          # what produced the inputs (and the zero fill) has finished: the library's stream knows nothing of torch's
+        self._check(lib().mi355rt_probes_gather(self._h, addr, iaddr, n, C.byref(cfg), RAYS_DEVICE if dev else RAYS_HOST, C.byref(o)))
+        return res
+
+    def probes_lookup(self, grid, res, points, dirs, mode="irradiance", usable=None, want_ok=False):
+        """mi355rt_probes_lookup: a probe grid interpolated at points and evaluated for dirs (raytracer_rs_amd.probes.lookup is the statement); traces nothing.
+        grid: dict(origin, spacing, counts) (probes.grid_over makes one); res: a dict with n uint32 (nprobes,) and sh float32 (nprobes, 9, 3) as probes_gather
+        returns them at probes.grid_points(grid); points, dirs: float32 (m, 3); mode "irradiance" (dirs are normals) or "radiance" (arriving from dirs);
+        usable: uint8 (nprobes,) or None.  numpy arrays or torch tensors on the handle's GPU, all alike.  Returns rgb float32 (m, 3), with want_ok
+        (rgb, ok uint8 (m,)): ok 0 and rgb 0 where no probe around the point could be used.  Nothing is clamped."""
+        if mode not in SH_MODES:
+            raise ValueError("mode: one of %s, not %r" % (tuple(SH_MODES), mode))
+        g = grid if isinstance(grid, ProbeGrid) else ProbeGrid.from_dict(grid)
+        nprobes = int(g.counts[0]) * int(g.counts[1]) * int(g.counts[2])
+        addr, m, dev = _ray_array(points, "points", 3, np.float32)
+        daddr, _, ddev = _ray_array(dirs, "dirs", 3, np.float32, rows=m)
+        naddr, _, ndev = _ray_vector(res["n"], 'res["n"]', np.uint32, nprobes)
+        saddr, _, sdev = self._sh_array(res["sh"], 'res["sh"]', nprobes)
+        uaddr, udev = None, dev
+        if usable is not None:
+            uaddr, _, udev = _ray_vector(usable, "usable", np.uint8, nprobes)
+        if not (ddev == ndev == sdev == udev == dev):
+            raise ValueError("dirs, res and usable must live where points live (all numpy arrays, or all tensors on the GPU)")
+        if dev:
+            import torch
+            rgb = torch.zeros((m, 3), dtype=torch.float32, device=points.device); ok = torch.zeros(m, dtype=torch.uint8, device=points.device) if want_ok else None
+            raddr, oaddr = rgb.data_ptr(), ok.data_ptr() if want_ok else None
+            torch.cuda.current_stream(points.device).synchronize()
+        else:
+            rgb = np.zeros((m, 3), np.float32); ok = np.zeros(m, np.uint8) if want_ok else None
+            raddr, oaddr = rgb.ctypes.data, ok.ctypes.data if want_ok else None
+        self._check(lib().mi355rt_probes_lookup(self._h, C.byref(g), naddr, saddr, uaddr, addr, daddr, m, SH_MODES[mode], RAYS_DEVICE if dev else RAYS_HOST, raddr, oaddr))
+        return (rgb, ok) if want_ok else rgb
 
     def bake_texels(self, uv, width, height, flip=False, want=BAKE_TEXEL_OUTPUTS):
         """mi355rt_bake_texels: the UV charts of the scene's triangles rasterised into an atlas of width x height texels (raytracer_rs_amd.bake.texels is the

@@ -16,6 +16,7 @@
 #include "group.hpp"
 #include "lens.hpp"
 #include "renderer.hpp"
+#include "sh9.hpp"
 
 using namespace mi355rt;
 
@@ -962,6 +963,106 @@ int mi355rt_bake_auto_atlas(uint32_t ntri, uint32_t width, uint32_t height, uint
 {
     if (!uv) return bad("mi355rt_bake_auto_atlas: uv is NULL");
     if (const char* why = bake_auto_atlas(ntri, width, height, gutter, uv, cell)) { g_create_error = std::string("mi355rt_bake_auto_atlas: ") + why; return MI355RT_E_INVALID; }
+    return MI355RT_OK;
+}
+
+void mi355rt_probes_default_config(mi355rt_probe_config* cfg)
+{
+    if (!cfg) return;
+    cfg->spp = 64; cfg->first_sample = 0; cfg->accumulate = 0; cfg->near_distance = INFINITY;
+}
+
+int mi355rt_probes_gather(mi355rt_handle* h, const float* points3, const uint32_t* ids, size_t npoints, const mi355rt_probe_config* cfg, uint32_t where,
+                          const mi355rt_probe_outputs* out)
+{
+    if (!h) return MI355RT_E_INVALID;
+    const char* e = nullptr;
+    if ((e = single_device_ok(h, where)) != nullptr) {}
+    else if (!cfg) e = "cfg is NULL";
+    else if (!out || (!out->n && !out->hits && !out->near && !out->sh)) e = "out is NULL or every output pointer in it is NULL";
+    else if (npoints && !points3) e = "points3 is NULL";
+    else if (cfg->spp == 0) e = "spp must be >= 1";
+    else if (std::isnan(cfg->near_distance)) e = "near_distance is NaN";
+    else if ((uint64_t)cfg->first_sample + cfg->spp > 0xFFFFFFFFull) e = "first_sample + spp must fit 32 bits";
+    else if (npoints > 0xFFFFFFFFull || (uint64_t)npoints * cfg->spp >= (1ull << 32)) e = "npoints * spp must be < 2^32";
+    if (e) { h->r->last_error = std::string("mi355rt_probes_gather: ") + e; return MI355RT_E_INVALID; }
+    if (npoints == 0) return MI355RT_OK;
+    return h->r->probes_gather(points3, ids, npoints, *cfg, where == MI355RT_RAYS_DEVICE, *out) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+namespace {
+// the checks of a probe grid (include/mi355rt.h, "PROBES"); null: fine, else the message that names the field
+const char* probe_grid_error(const mi355rt_probe_grid* g)
+{
+    if (!g) return "grid is NULL";
+    uint64_t product = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (g->counts[a] == 0) return "grid.counts: a count is 0";
+        product *= g->counts[a];
+        if (product >= (1ull << 31)) return "grid.counts: the product must be < 2^31";
+    }
+    for (int a = 0; a < 3; ++a) {
+        if (!(std::isfinite(g->spacing[a]) && g->spacing[a] > 0.0f)) return "grid.spacing must be finite and positive";
+        if (!std::isfinite(g->origin[a])) return "grid.origin must be finite";
+    }
+    return nullptr;
+}
+}  // namespace
+
+int mi355rt_probes_lookup(mi355rt_handle* h, const mi355rt_probe_grid* grid, const uint32_t* n, const float* sh, const uint8_t* usable, const float* points3, const float* dirs3,
+                          size_t npoints, uint32_t mode, uint32_t where, float* rgb3, uint8_t* ok)
+{
+    if (!h) return MI355RT_E_INVALID;
+    const char* e = nullptr;
+    if ((e = single_device_ok(h, where)) != nullptr) {}
+    else if ((e = probe_grid_error(grid)) != nullptr) {}
+    else if (!n) e = "n is NULL";
+    else if (!sh) e = "sh is NULL";
+    else if (!rgb3) e = "rgb3 is NULL";
+    else if (npoints && !points3) e = "points3 is NULL";
+    else if (npoints && !dirs3) e = "dirs3 is NULL";
+    else if (mode > MI355RT_SH_IRRADIANCE) e = "unknown mode (MI355RT_SH_RADIANCE or MI355RT_SH_IRRADIANCE)";
+    else if (npoints > 0xFFFFFFFFull) e = "npoints must fit 32 bits";
+    if (e) { h->r->last_error = std::string("mi355rt_probes_lookup: ") + e; return MI355RT_E_INVALID; }
+    if (npoints == 0) return MI355RT_OK;
+    return h->r->probes_lookup(*grid, n, sh, usable, points3, dirs3, npoints, mode, where == MI355RT_RAYS_DEVICE, rgb3, ok) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_sh9_basis(const float dir[3], float b[9])
+{
+    if (!dir) return bad("mi355rt_sh9_basis: dir is NULL");
+    if (!b) return bad("mi355rt_sh9_basis: b is NULL");
+    sh9_basis(dir[0], dir[1], dir[2], b);
+    return MI355RT_OK;
+}
+
+int mi355rt_probes_lookup_one(const mi355rt_probe_grid* grid, const uint32_t* n, const float* sh, const uint8_t* usable, const float point[3], const float dir[3], uint32_t mode,
+                              float rgb[3], uint32_t* ok)
+{
+    const char* e = probe_grid_error(grid);
+    if (!e) e = !n ? "n is NULL" : !sh ? "sh is NULL" : !point ? "point is NULL" : !dir ? "dir is NULL" : !rgb ? "rgb is NULL" : mode > MI355RT_SH_IRRADIANCE ? "unknown mode" : nullptr;
+    if (e) { g_create_error = std::string("mi355rt_probes_lookup_one: ") + e; return MI355RT_E_INVALID; }
+    ShGrid g;
+    std::memcpy(&g, grid, sizeof g);
+    const bool used = sh9_lookup(g, [n](size_t j) { return n[j]; }, [sh](size_t j, int c) { return sh[27 * j + c]; }, usable != nullptr,
+                                 [usable](size_t j) { return usable[j] != 0; }, point, dir, mode, rgb);
+    if (ok) *ok = used ? 1u : 0u;
+    return MI355RT_OK;
+}
+
+int mi355rt_probe_grid_points(const mi355rt_probe_grid* grid, float* points3)
+{
+    const char* e = probe_grid_error(grid);
+    if (!e && !points3) e = "points3 is NULL";
+    if (e) { g_create_error = std::string("mi355rt_probe_grid_points: ") + e; return MI355RT_E_INVALID; }
+    float* o = points3;
+    for (uint32_t iz = 0; iz < grid->counts[2]; ++iz)
+        for (uint32_t iy = 0; iy < grid->counts[1]; ++iy)
+            for (uint32_t ix = 0; ix < grid->counts[0]; ++ix, o += 3) {
+                o[0] = sh9_probe_pos(grid->origin[0], grid->spacing[0], ix);
+                o[1] = sh9_probe_pos(grid->origin[1], grid->spacing[1], iy);
+                o[2] = sh9_probe_pos(grid->origin[2], grid->spacing[2], iz);
+            }
     return MI355RT_OK;
 }
 

@@ -279,6 +279,30 @@ public:
             throw std::runtime_error(mi355rt_last_error(h_));
         return g;
     }
+    // probes (include/mi355rt.h "PROBES"), host memory.  probes_gather: n and the 9 x 3 SH sums of points3.size() / 3 probes; ids empty: i;
+    // prev non-null: accumulate onto it (cfg.accumulate is set).  probes_lookup: the grid `probes` was gathered on (mi355rt_probe_grid_points) interpolated at
+    // points3 and evaluated for dirs3; usable empty: every probe counts.  Returns rgb, 3 floats per query
+    struct Probes { std::vector<uint32_t> n; std::vector<float> sh; };
+    Probes probes_gather(const std::vector<float>& points3, mi355rt_probe_config cfg, const std::vector<uint32_t>& ids = {}, const Probes* prev = nullptr)
+    {
+        const size_t np = points3.size() / 3;
+        Probes p = prev ? *prev : Probes{};
+        p.n.resize(np); p.sh.resize(np * 27);
+        cfg.accumulate = prev ? 1u : 0u;
+        mi355rt_probe_outputs out{};
+        out.n = p.n.data(); out.sh = p.sh.data();
+        if (mi355rt_probes_gather(h_, points3.data(), ids.empty() ? nullptr : ids.data(), np, &cfg, MI355RT_RAYS_HOST, &out) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_));
+        return p;
+    }
+    std::vector<float> probes_lookup(const mi355rt_probe_grid& grid, const Probes& probes, const std::vector<float>& points3, const std::vector<float>& dirs3,
+                                     uint32_t mode = MI355RT_SH_IRRADIANCE, const std::vector<uint8_t>& usable = {})
+    {
+        std::vector<float> rgb(points3.size());
+        if (mi355rt_probes_lookup(h_, &grid, probes.n.data(), probes.sh.data(), usable.empty() ? nullptr : usable.data(), points3.data(), dirs3.data(), points3.size() / 3, mode,
+                                  MI355RT_RAYS_HOST, rgb.data(), nullptr) != MI355RT_OK)
+            throw std::runtime_error(mi355rt_last_error(h_));
+        return rgb;
+    }
     // lens models (include/mi355rt.h): the ray generator of render(); lens_rays: the width*height*spp rays of the next render(spp), host memory
     void set_lens(const mi355rt_lens& lens) { if (mi355rt_set_lens(h_, &lens) != MI355RT_OK) throw std::runtime_error(mi355rt_last_error(h_)); }
     mi355rt_lens lens() const

@@ -14,9 +14,12 @@
 #include "kernels.hpp"
 #include "lens.hpp"
 #include "octree.hpp"
+#include "probes.hpp"
 #include "staging.hpp"
 
 namespace mi355rt {
+
+static_assert(sizeof(ShGrid) == sizeof(mi355rt_probe_grid), "sh9.hpp's grid is the header's");
 
 namespace {
 // counter RNG, identical to the device copy in kernels.hip (pcg4d, Jarzynski & Olano 2020)
@@ -1640,6 +1643,84 @@ bool Renderer::trace_rays(const float* rays6, const uint32_t* keys2, size_t n, b
     return end_call(n, true);                                         // waits: the staging (and the caller's buffers) are free again
 }
 
+// The chunk loop mi355rt_gather and mi355rt_probes_gather share.  Rays per chunk: what a pass of trace_rays holds.  A chunk's rays, keys and validity bytes
+// are made by gather_rays_kernel, the chunk runs as ONE ray-fed pass (RayFeed mode 2, exactly a pass of trace_rays) when `traced`, and `reduce` folds its
+// results into the caller's outputs.  Everything is queued on one stream, the sample chunks of a point range in ascending sample order, so every point takes
+// its samples in order.  Waits before it returns: the chunk buffers go out of scope here.
+bool Renderer::gather_chunks(const float* d_points, const float* d_normals, const uint32_t* d_ids, size_t npoints, uint32_t spp, uint32_t first_sample, bool traced, bool want_rgb,
+                             bool want_hits, const std::function<hipError_t(const GatherChunk&)>& reduce)
+{
+    const size_t total = npoints * spp;
+    size_t per = cfg.samples_per_pass ? std::max<size_t>(1, (size_t)cfg.samples_per_pass * cfg.width * cfg.height) : pass_sample_budget();
+    per = std::min(per, total);
+    Slice& sl = slices_[0];
+    if (traced && !fit_ray_pass(sl, per)) return false;
+    const size_t cp_max = std::min(npoints, per), cs_max = std::max<size_t>(1, std::min<size_t>(spp, per / cp_max));
+    const size_t cap = cp_max * cs_max;
+    DeviceBuffer<float> c_rays, c_rgb, c_tuv; DeviceBuffer<uint32_t> c_keys, c_prim; DeviceBuffer<uint8_t> c_valid; DeviceBuffer<float4> c_hit;
+    HIP_TRY(c_rays.alloc(cap * 24, &hbm_bytes_));
+    HIP_TRY(c_keys.alloc(cap * 8, &hbm_bytes_));
+    HIP_TRY(c_valid.alloc(cap, &hbm_bytes_));
+    if (want_rgb) HIP_TRY(c_rgb.alloc(cap * 12, &hbm_bytes_));
+    if (want_hits) { HIP_TRY(c_tuv.alloc(cap * 12, &hbm_bytes_)); HIP_TRY(c_prim.alloc(cap * 4, &hbm_bytes_)); HIP_TRY(c_hit.alloc(cap * sizeof(float4), &hbm_bytes_)); }
+    for (size_t p0 = 0; p0 < npoints; p0 += cp_max) {
+        const uint32_t cp = (uint32_t)std::min(cp_max, npoints - p0);
+        for (uint32_t s0 = 0; s0 < spp; s0 += (uint32_t)cs_max) {
+            const uint32_t cs = (uint32_t)std::min<size_t>(cs_max, spp - s0);
+            HIP_TRY(launch_gather_rays(stream_, dscene_, (uint32_t)cfg.seed, d_points, d_normals, d_ids, (uint32_t)p0, cp, cs, first_sample + s0, c_rays.get(), c_keys.get(), c_valid.get()));
+            if (traced) {
+                RayFeed f{};
+                f.mode = 2u; f.rays = c_rays.get(); f.keys = c_keys.get(); f.base = 0u; f.count = cp * cs; f.hit = c_hit.get();
+                f.rgb = c_rgb.get(); f.tuv = c_tuv.get(); f.prim = c_prim.get();
+                if (!run_pass(sl, nullptr, 0, 0, 1, false, 0, 0, 0xFFFFFFFFu, nullptr, &f)) return false;
+            }
+            HIP_TRY(reduce(GatherChunk{ (uint32_t)p0, cp, s0, cs, c_rays.get(), c_valid.get(), c_rgb.get(), c_tuv.get(), c_prim.get() }));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(stream_));
+    return true;
+}
+
+// mi355rt_probes_gather: gather's sphere-mode samples (no normals: no walk, no void sample) through gather's chunk loop, with the projection
+// of csrc/probes.hip as the reduce.  Around the call everything is gather's.
+bool Renderer::probes_gather(const float* points3, const uint32_t* ids, size_t npoints, const mi355rt_probe_config& pc, bool device, const mi355rt_probe_outputs& out)
+{
+    if (!begin_call()) return false;
+    const bool hitq = out.hits || out.near, traced = out.sh || hitq;  // n alone needs no ray
+    const size_t total = npoints * pc.spp;
+    Staging st(stream_, &hbm_bytes_, device);
+    const float* d_points = st.in(points3, npoints * 3); const uint32_t* d_ids = st.in(ids, npoints);
+    const bool acc = pc.accumulate != 0;                              // then the outputs go up first: the call adds to what they hold
+    mi355rt_probe_outputs d{};
+    d.n = st.out(out.n, npoints, acc); d.hits = st.out(out.hits, npoints, acc); d.near = st.out(out.near, npoints, acc); d.sh = st.out(out.sh, npoints * 27, acc);
+    HIP_TRY(st.error());
+    if (!gather_chunks(d_points, nullptr, d_ids, npoints, pc.spp, pc.first_sample, traced, out.sh != nullptr, hitq, [&](const GatherChunk& c) {
+            return launch_probes_project(stream_, c.point0, c.cp, c.cs, !acc && c.sample0 == 0, pc.near_distance, c.rays, c.rgb, c.tuv, c.prim, d.n, d.hits, d.near, d.sh);
+        })) return false;
+    HIP_TRY(st.download());
+    return end_call(traced ? total : 0, true);                        // waits: the staging (and the caller's buffers) are free again
+}
+
+// mi355rt_probes_lookup: arithmetic on the caller's arrays, one kernel.  A read-out that makes no ray: a speculative frame is settled, a queued
+// one is ahead on the same stream, and neither the counters nor any film is touched.
+bool Renderer::probes_lookup(const mi355rt_probe_grid& grid, const uint32_t* n, const float* sh, const uint8_t* usable, const float* points3, const float* dirs3, size_t npoints,
+                             uint32_t mode, bool device, float* rgb3, uint8_t* ok)
+{
+    if (!quiet()) return false;
+    const size_t nprobes = (size_t)grid.counts[0] * grid.counts[1] * grid.counts[2];
+    ShGrid g;
+    std::memcpy(&g, &grid, sizeof g);
+    Staging st(stream_, &hbm_bytes_, device);
+    const uint32_t* d_n = st.in(n, nprobes); const float* d_sh = st.in(sh, nprobes * 27); const uint8_t* d_usable = st.in(usable, nprobes);
+    const float* d_points = st.in(points3, npoints * 3); const float* d_dirs = st.in(dirs3, npoints * 3);
+    float* d_rgb = st.out(rgb3, npoints * 3); uint8_t* d_ok = st.out(ok, npoints);
+    HIP_TRY(st.error());
+    HIP_TRY(launch_probes_lookup(stream_, g, d_n, d_sh, d_usable, d_points, d_dirs, npoints, mode, d_rgb, d_ok));
+    HIP_TRY(st.download());
+    HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's buffers are complete, on whatever stream they are used next
+    return true;
+}
+
 // mi355rt_gather: the points as a film of their own.  Chunks of cp points x cs samples, sized by the pass capacity as trace_rays sizes its
 // passes: gather_rays_kernel makes the chunk's rays, keys and validity bytes, the chunk runs as ONE ray-fed pass (RayFeed mode 2, exactly a pass of trace_rays),
 // gather_reduce_kernel folds its results into the points' outputs.  The sample chunks of a point range go in ascending sample order, on one stream, so every
@@ -1671,37 +1752,10 @@ bool Renderer::gather(const float* points3, const float* normals3, const uint32_
         }
         HIP_TRY(hipStreamSynchronize(stream_));                       // the chunk buffers go out of scope here
     }
-    if (total) {
-        // rays per chunk: what a pass of trace_rays holds
-        size_t per = cfg.samples_per_pass ? std::max<size_t>(1, (size_t)cfg.samples_per_pass * cfg.width * cfg.height) : pass_sample_budget();
-        per = std::min(per, total);
-        Slice& sl = slices_[0];
-        if (traced && !fit_ray_pass(sl, per)) return false;
-        const size_t cp_max = std::min(npoints, per), cs_max = std::max<size_t>(1, std::min<size_t>(gc.spp, per / cp_max));
-        const size_t cap = cp_max * cs_max;
-        DeviceBuffer<float> c_rays, c_rgb, c_tuv; DeviceBuffer<uint32_t> c_keys, c_prim; DeviceBuffer<uint8_t> c_valid; DeviceBuffer<float4> c_hit;
-        HIP_TRY(c_rays.alloc(cap * 24, &hbm_bytes_));
-        HIP_TRY(c_keys.alloc(cap * 8, &hbm_bytes_));
-        HIP_TRY(c_valid.alloc(cap, &hbm_bytes_));
-        if (sums) HIP_TRY(c_rgb.alloc(cap * 12, &hbm_bytes_));
-        if (hitq) { HIP_TRY(c_tuv.alloc(cap * 12, &hbm_bytes_)); HIP_TRY(c_prim.alloc(cap * 4, &hbm_bytes_)); HIP_TRY(c_hit.alloc(cap * sizeof(float4), &hbm_bytes_)); }
-        for (size_t p0 = 0; p0 < npoints; p0 += cp_max) {
-            const uint32_t cp = (uint32_t)std::min(cp_max, npoints - p0);
-            for (uint32_t s0 = 0; s0 < gc.spp; s0 += (uint32_t)cs_max) {
-                const uint32_t cs = (uint32_t)std::min<size_t>(cs_max, gc.spp - s0);
-                HIP_TRY(launch_gather_rays(stream_, dscene_, (uint32_t)cfg.seed, d_points, d_normals, d_ids, (uint32_t)p0, cp, cs, gc.first_sample + s0, c_rays.get(), c_keys.get(), c_valid.get()));
-                if (traced) {
-                    RayFeed f{};
-                    f.mode = 2u; f.rays = c_rays.get(); f.keys = c_keys.get(); f.base = 0u; f.count = cp * cs; f.hit = c_hit.get();
-                    f.rgb = c_rgb.get(); f.tuv = c_tuv.get(); f.prim = c_prim.get();
-                    if (!run_pass(sl, nullptr, 0, 0, 1, false, 0, 0, 0xFFFFFFFFu, nullptr, &f)) return false;
-                }
-                HIP_TRY(launch_gather_reduce(stream_, (uint32_t)p0, cp, cs, gc.weight, !gc.accumulate && s0 == 0, gc.near_distance, d_normals, c_rays.get(), c_valid.get(),
-                                             c_rgb.get(), c_tuv.get(), c_prim.get(), d.n, d.hits, d.near, d.sum, d.sumsq));
-            }
-        }
-        HIP_TRY(hipStreamSynchronize(stream_));                       // the chunk buffers go out of scope here
-    }
+    if (total && !gather_chunks(d_points, d_normals, d_ids, npoints, gc.spp, gc.first_sample, traced, sums, hitq, [&](const GatherChunk& c) {
+            return launch_gather_reduce(stream_, c.point0, c.cp, c.cs, gc.weight, !gc.accumulate && c.sample0 == 0, gc.near_distance, d_normals, c.rays, c.valid, c.rgb, c.tuv, c.prim,
+                                        d.n, d.hits, d.near, d.sum, d.sumsq);
+        })) return false;
     if (!total) { st.only(out.n, 0); st.only(out.hits, 0); st.only(out.near, 0); st.only(out.sum, 0); st.only(out.sumsq, 0); }     // spp == 0: nothing was sampled, nothing to copy
     HIP_TRY(st.download());
     return end_call(traced ? total : 0, true);                        // waits: the staging (and the caller's buffers) are free again

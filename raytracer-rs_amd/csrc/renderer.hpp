@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <array>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -47,6 +48,11 @@ public:
     bool render_rays(const float* rays6, uint32_t spp, bool device);
     // gather: light arriving at npoints caller-given points; the caller has checked the arguments.  device: every pointer is device memory
     bool gather(const float* points3, const float* normals3, const uint32_t* ids, size_t npoints, const mi355rt_gather_config& gc, bool device, const mi355rt_gather_outputs& out);
+    // probes; the caller has checked the arguments.  probes_gather: gather's sphere-mode samples projected onto nine SH coefficients per point;
+    // probes_lookup: a read-out of such a grid that traces nothing and touches neither films nor counters.  device: every pointer is device memory
+    bool probes_gather(const float* points3, const uint32_t* ids, size_t npoints, const mi355rt_probe_config& pc, bool device, const mi355rt_probe_outputs& out);
+    bool probes_lookup(const mi355rt_probe_grid& grid, const uint32_t* n, const float* sh, const uint8_t* usable, const float* points3, const float* dirs3, size_t npoints,
+                       uint32_t mode, bool device, float* rgb3, uint8_t* ok);
     // bake; the caller has checked the arguments.  device: every pointer but ncovered is device memory.  Neither touches films, camera, counters
     bool bake_texels(const float* uv, uint32_t width, uint32_t height, bool flip, bool device, const mi355rt_bake_texel_outputs& out, uint32_t* ncovered);
     bool bake_atlas(const uint32_t* ids, const float* values3, uint32_t n, uint32_t width, uint32_t height, uint32_t dilate, bool device, float* atlas, uint8_t* valid, uint32_t& verdict);
@@ -184,6 +190,11 @@ private:
     size_t pass_sample_budget() const;                                  // samples per pass: the default or MI355RT_PASS_SAMPLES (config.samples_per_pass is the callers' matter)
     bool fit_ray_pass(Slice& sl, size_t& per);                          // ensure_pass_capacity(sl, per), per halved while the device is out of memory
     void free_pass_buffers();
+    // The chunk loop of gather and probes_gather: the samples of npoints points in chunks of cp points x cs samples sized by the pass
+    // capacity; per chunk launch_gather_rays, one ray-fed pass when `traced`, then reduce(chunk).  The sample chunks of a point range come in ascending order.
+    struct GatherChunk { uint32_t point0, cp, sample0, cs; const float* rays; const uint8_t* valid; const float* rgb; const float* tuv; const uint32_t* prim; };
+    bool gather_chunks(const float* d_points, const float* d_normals, const uint32_t* d_ids, size_t npoints, uint32_t spp, uint32_t first_sample, bool traced, bool want_rgb,
+                       bool want_hits, const std::function<hipError_t(const GatherChunk&)>& reduce);
     bool assign_slice_rows(uint32_t nslices);
     // A ray-fed pass (DPass::ray_in ...).  mode 1: the film's pixels with the caller's rays (base: the call's sample number of the pass's first
     // sample, set per pass by enqueue_frame); mode 2: `count` free rays, one sample each, resolved into the out pointers (device memory, the pass's part);
