@@ -968,6 +968,17 @@ int mi355rt_debug_wide_bvh(const float* tri_verts, uint32_t ntri, uint32_t out[8
  * nothing is written, not counts either.  Exists so that the build can be held to an independent statement without a GPU. */
 int mi355rt_debug_octree(const float* tri_verts, uint32_t ntri, uint32_t tris_per_leaf, uint32_t counts[8], float* cubes6, int32_t* first_child,
                          uint32_t* tri_first, uint32_t* tri_count, uint32_t* parent, size_t node_cap, uint32_t* leaf_tris, size_t leaf_cap);
+/* Test hook: the binary BVH itself, word for word (csrc/bvh.hpp: BvhNode is 8 words { h0[3], child0, h1[3], child1 }, BvhTri 12 words
+ * { v0[3], prim, e1[3], geom, e2[3], pad }).  TWO SOURCES.  With a handle: the handle's host copy of the tree its kernels were given, whichever builder
+ * made it (the device build of MI355RT_FLAG_DEVICE_LBVH, or the host build); tri_verts, tri_geom and ntri are ignored.  In a library whose kernels walk
+ * the 4-wide tree the triangles are in that tree's order.  With h == NULL: host code, no device needed — the host build (build_bvh) of the ntri triangles
+ * in tri_verts (ntri x 9 floats) with tri_geom (ntri indices; NULL: all 0), exactly as mi355rt_create runs it, MI355RT_BVH_OPT included.
+ * info receives [0] nodes, [1] triangle slots, [2] root (an int32: a node index, or a leaf code when the scene is one leaf), [3] leaves, [4] max_depth,
+ * [5] max_leaf, [6] [7] 0; bounds6 (may be NULL) scene_min then scene_max.  SIZE QUERY: nodes8 and tris12 both NULL; only info and bounds6 are written.
+ * Otherwise both are required: nodes8 holds node_cap x 8 words, tris12 tri_cap x 12.  node_cap < info[0] or tri_cap < info[1]: MI355RT_E_INVALID and
+ * nothing is written, not info either.  Exists so that the tree a kernel built can be held to an independent statement, node for node. */
+int mi355rt_debug_bvh_read(const mi355rt_handle* h, const float* tri_verts, const uint32_t* tri_geom, uint32_t ntri, uint32_t info[8], float* bounds6,
+                           uint32_t* nodes8, size_t node_cap, uint32_t* tris12, size_t tri_cap);
 
 /* acceleration-structure facts: out[0] nodes, [1] leaves, [2] max depth, [3] max leaf size,
  * [4] node bytes, [5] triangle bytes, [6] BVH build time inside create (wall, microseconds; host SAH build, or the device

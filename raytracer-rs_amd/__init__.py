@@ -323,6 +323,7 @@ ABI = [
     ("mi355rt_debug_rays_read", C.c_int, [_H, C.POINTER(C.c_uint64)]),
     ("mi355rt_debug_wide_bvh", C.c_int, [_F, C.c_uint32, _U]),
     ("mi355rt_debug_octree", C.c_int, [_F, C.c_uint32, C.c_uint32, _U, _F, C.POINTER(C.c_int32), _U, _U, _U, C.c_size_t, _U, C.c_size_t]),
+    ("mi355rt_debug_bvh_read", C.c_int, [_H, _F, _U, C.c_uint32, _U, _F, _U, C.c_size_t, _U, C.c_size_t]),
     ("mi355rt_accel_stats", C.c_int, [_H, _U]),
     ("mi355rt_octree_stats", C.c_int, [_H, _U]),
     ("mi355rt_bvh_build_info", C.c_int, [_H, _U]),
@@ -1316,6 +1317,10 @@ class RayTracer:
         self._check(lib().mi355rt_bvh_build_info(self._h, _up(out)))
         return dict(on_device=bool(out[0]), device_ms=int(out[1]) / 1000.0)
 
+    def bvh_read(self):
+        """the binary BVH the handle's kernels were given, word for word, whichever builder made it (include/mi355rt.h, mi355rt_debug_bvh_read)"""
+        return _bvh_read(self._h, None, None, 0)
+
     def octree_stats(self):
         out = np.zeros(8, np.uint32)
         self._check(lib().mi355rt_octree_stats(self._h, _up(out)))
@@ -1470,6 +1475,31 @@ def debug_octree(tri_verts, tris_per_leaf):
         raise RuntimeError("mi355rt_debug_octree failed: %d" % code)
     stats = dict(nodes=int(counts[0]), inner=int(counts[1]), leaves=int(counts[2]), empty=int(counts[3]), depth=int(counts[4]), tri_refs=int(counts[5]))
     return dict(cubes=cubes, first_child=first_child, tri_first=tri_first, tri_count=tri_count, parent=parent, leaf_tris=leaf_tris[:refs], stats=stats)
+
+
+def _bvh_read(handle, verts, geom, ntri):
+    info = np.zeros(8, np.uint32); bounds = np.zeros(6, np.float32)
+    vp = _fp(verts) if verts is not None else None; gp = _up(geom) if geom is not None else None
+    code = lib().mi355rt_debug_bvh_read(handle, vp, gp, ntri, _up(info), _fp(bounds), None, 0, None, 0)
+    if code != 0:
+        raise RuntimeError("mi355rt_debug_bvh_read failed: %d" % code)
+    nn, nt = int(info[0]), int(info[1])
+    nodes = np.zeros((max(nn, 1), 8), np.uint32); tris = np.zeros((max(nt, 1), 12), np.uint32)
+    code = lib().mi355rt_debug_bvh_read(handle, vp, gp, ntri, _up(info), _fp(bounds), _up(nodes), nn, _up(tris), nt)
+    if code != 0:
+        raise RuntimeError("mi355rt_debug_bvh_read failed: %d" % code)
+    return dict(nodes=nodes[:nn], tris=tris[:nt], root=int(info[2:3].view(np.int32)[0]), leaves=int(info[3]), max_depth=int(info[4]), max_leaf=int(info[5]),
+                scene_min=bounds[:3].copy(), scene_max=bounds[3:].copy())
+
+
+def debug_bvh(tri_verts, tri_geom=None):
+    """the binary BVH the host builder makes of these triangles, as mi355rt_create would (host code, no device; include/mi355rt.h,
+    mi355rt_debug_bvh_read): dict(nodes (k, 8) uint32, tris (n, 12) uint32, root, leaves, max_depth, max_leaf, scene_min, scene_max)"""
+    v = np.ascontiguousarray(tri_verts, np.float32).reshape(-1, 9)
+    g = None if tri_geom is None else np.ascontiguousarray(tri_geom, np.uint32).reshape(-1)
+    if g is not None and g.shape[0] != v.shape[0]:
+        raise ValueError("tri_geom has %d entries for %d triangles" % (g.shape[0], v.shape[0]))
+    return _bvh_read(None, v, g, v.shape[0])
 
 
 def comm_unique_id():

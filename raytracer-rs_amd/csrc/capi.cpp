@@ -1257,6 +1257,30 @@ int mi355rt_debug_octree(const float* tri_verts, uint32_t ntri, uint32_t tris_pe
     return MI355RT_OK;
 }
 
+int mi355rt_debug_bvh_read(const mi355rt_handle* h, const float* tri_verts, const uint32_t* tri_geom, uint32_t ntri, uint32_t info[8], float* bounds6,
+                           uint32_t* nodes8, size_t node_cap, uint32_t* tris12, size_t tri_cap)
+{
+    if (!info || (!h && ntri && !tri_verts)) return MI355RT_E_INVALID;
+    const bool query = !nodes8 && !tris12;
+    if (!query && (!nodes8 || !tris12)) return MI355RT_E_INVALID;
+    mi355rt::Bvh built;
+    if (!h) {
+        std::vector<uint32_t> zeros;
+        if (!tri_geom) { zeros.assign(std::max(ntri, 1u), 0u); tri_geom = zeros.data(); }
+        mi355rt::build_bvh(tri_verts, tri_geom, ntri, built);
+    }
+    const Bvh& b = h ? h->r->bvh : built;
+    if (!query && (node_cap < b.nodes.size() || tri_cap < b.tris.size())) return MI355RT_E_INVALID;                    // nothing is written
+    info[0] = (uint32_t)b.nodes.size(); info[1] = (uint32_t)b.tris.size(); info[2] = (uint32_t)b.root; info[3] = b.leaves;
+    info[4] = b.max_depth; info[5] = b.max_leaf; info[6] = info[7] = 0u;
+    if (bounds6) { std::memcpy(bounds6, b.scene_min, 3 * sizeof(float)); std::memcpy(bounds6 + 3, b.scene_max, 3 * sizeof(float)); }
+    if (query) return MI355RT_OK;
+    static_assert(sizeof(BvhNode) == 8 * sizeof(uint32_t) && sizeof(BvhTri) == 12 * sizeof(uint32_t), "the read-out hands the structs out as words");
+    if (!b.nodes.empty()) std::memcpy(nodes8, b.nodes.data(), b.nodes.size() * sizeof(BvhNode));
+    if (!b.tris.empty()) std::memcpy(tris12, b.tris.data(), b.tris.size() * sizeof(BvhTri));
+    return MI355RT_OK;
+}
+
 int mi355rt_accel_stats(const mi355rt_handle* h, uint32_t out[8])
 {
     if (!h || !out) return MI355RT_E_INVALID;

@@ -21,7 +21,8 @@ namespace mi355rt {
 struct RayState {
     f3 o, d;
     float idx, idy, idz;   // 1/d' (approximate reciprocal; d' = d with tiny components pushed away from 0: box tests only)
-    float oidx, oidy, oidz; // -o/d'
+    float onx, ony, onz;   // -o/d' lowered by the rounding error it may carry: what the NEAR planes add
+    float ofx, ofy, ofz;   // -o/d' raised by it: what the FAR planes add (ray_init)
     uint32_t selx, sely, selz; // v_perm selectors: identity, or swap the two halves when d' < 0
     float tlimit;          // only hits with t <= tlimit can still change the result
     float t, u, v;
@@ -46,7 +47,14 @@ __device__ __forceinline__ void ray_init(RayState& s, f3 o, f3 d, bool shadow, i
     const float bz = fabsf(d.z) < deps ? __builtin_copysignf(deps, d.z) : d.z;
     const bool null_dir = !(dmax > 0.0f);
     s.idx = null_dir ? 0.0f : __builtin_amdgcn_rcpf(bx); s.idy = null_dir ? 0.0f : __builtin_amdgcn_rcpf(by); s.idz = null_dir ? 0.0f : __builtin_amdgcn_rcpf(bz);
-    s.oidx = -(o.x * s.idx); s.oidy = -(o.y * s.idy); s.oidz = -(o.z * s.idz);
+    // A plane's distance is fma(b, 1/d', -(o/d')), and o/d' is rounded: the distance is off by up to half an ulp of o/d', however near the plane is.
+    // With the origin far from the coordinate origin against the scene's size that exceeds the boxes' padding (a ray that runs IN a box face gets the
+    // rounding error itself, of either sign).  So the near planes take o/d' two ulps high and the far planes two ulps low: the box test stays
+    // conservative whatever the coordinates, at no cost in the loop.
+    const float ox = o.x * s.idx, oy = o.y * s.idy, oz = o.z * s.idz;
+    const float ex = fabsf(ox) * 0x1p-22f, ey = fabsf(oy) * 0x1p-22f, ez = fabsf(oz) * 0x1p-22f;
+    s.onx = -ox - ex; s.ony = -oy - ey; s.onz = -oz - ez;
+    s.ofx = ex - ox; s.ofy = ey - oy; s.ofz = ez - oz;
 #if MI355RT_WIDE
     // v_perm(hi, lo, sel): the dword of the four children's NEAR planes on this axis (lo bytes, or hi bytes when d' < 0); sel ^ 0x04040404 takes the far ones
     s.selx = __builtin_signbitf(bx) ? 0x07060504u : 0x03020100u;
@@ -68,17 +76,18 @@ __device__ __forceinline__ void ray_init(RayState& s, f3 o, f3 d, bool shadow, i
 // plane: no per-axis min/max.  Each plane distance is one mixed-precision fma (v_fma_mix_f32 reads the
 // half directly): t = b * (1/d) + (-o/d).  This is not the reference's (b - o) * inv and need not be:
 // boxes only steer the search; they are padded by 2e-5 of the scene diagonal and rounded outward, far
-// above the rounding difference (direction components are kept away from zero in ray_init, so 1/d is
-// finite and the fma form cannot produce inf - inf).
+// above the rounding difference of the product; the rounding of -o/d' itself, which grows with the origin's
+// distance from the coordinate origin, is covered by the two offsets of ray_init (direction components
+// are kept away from zero there, so 1/d is finite and the fma form cannot produce inf - inf).
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void slab_child(const uint4 q, const RayState& s, float& tn, float& tf)
 {
     const half2_t hx = __builtin_bit_cast(half2_t, __builtin_amdgcn_perm(q.x, q.x, s.selx));
     const half2_t hy = __builtin_bit_cast(half2_t, __builtin_amdgcn_perm(q.y, q.y, s.sely));
     const half2_t hz = __builtin_bit_cast(half2_t, __builtin_amdgcn_perm(q.z, q.z, s.selz));
-    const float nx = __builtin_fmaf((float)hx.x, s.idx, s.oidx), fx = __builtin_fmaf((float)hx.y, s.idx, s.oidx);
-    const float ny = __builtin_fmaf((float)hy.x, s.idy, s.oidy), fy = __builtin_fmaf((float)hy.y, s.idy, s.oidy);
-    const float nz = __builtin_fmaf((float)hz.x, s.idz, s.oidz), fz = __builtin_fmaf((float)hz.y, s.idz, s.oidz);
+    const float nx = __builtin_fmaf((float)hx.x, s.idx, s.onx), fx = __builtin_fmaf((float)hx.y, s.idx, s.ofx);
+    const float ny = __builtin_fmaf((float)hy.x, s.idy, s.ony), fy = __builtin_fmaf((float)hy.y, s.idy, s.ofy);
+    const float nz = __builtin_fmaf((float)hz.x, s.idz, s.onz), fz = __builtin_fmaf((float)hz.y, s.idz, s.ofz);
     tn = fmaxf(fmaxf(nx, ny), fmaxf(nz, 0.0f));
     tf = fminf(fminf(fx, fy), fminf(fz, s.tlimit));
 }
@@ -91,7 +100,8 @@ __device__ __forceinline__ float wide_byte(uint32_t w, int i) { return (float)((
 __device__ __forceinline__ void wide_children(const uint4 q0, const uint4 q1, const uint4 q2, const RayState& s, float tn[4], bool h[4], int ref[4])
 {
     const float sx = __uint_as_float((q0.w & 0xFFu) << 23) * s.idx, sy = __uint_as_float(((q0.w >> 8) & 0xFFu) << 23) * s.idy, sz = __uint_as_float(((q0.w >> 16) & 0xFFu) << 23) * s.idz;
-    const float bx = __builtin_fmaf(__uint_as_float(q0.x), s.idx, s.oidx), by = __builtin_fmaf(__uint_as_float(q0.y), s.idy, s.oidy), bz = __builtin_fmaf(__uint_as_float(q0.z), s.idz, s.oidz);
+    const float bx = __builtin_fmaf(__uint_as_float(q0.x), s.idx, s.onx), by = __builtin_fmaf(__uint_as_float(q0.y), s.idy, s.ony), bz = __builtin_fmaf(__uint_as_float(q0.z), s.idz, s.onz);
+    const float cx = __builtin_fmaf(__uint_as_float(q0.x), s.idx, s.ofx), cy = __builtin_fmaf(__uint_as_float(q0.y), s.idy, s.ofy), cz = __builtin_fmaf(__uint_as_float(q0.z), s.idz, s.ofz);   // the far planes' base
     const uint32_t nxw = __builtin_amdgcn_perm(q1.y, q1.x, s.selx), fxw = __builtin_amdgcn_perm(q1.y, q1.x, s.selx ^ 0x04040404u);
     const uint32_t nyw = __builtin_amdgcn_perm(q1.w, q1.z, s.sely), fyw = __builtin_amdgcn_perm(q1.w, q1.z, s.sely ^ 0x04040404u);
     const uint32_t nzw = __builtin_amdgcn_perm(q2.y, q2.x, s.selz), fzw = __builtin_amdgcn_perm(q2.y, q2.x, s.selz ^ 0x04040404u);
@@ -99,9 +109,9 @@ __device__ __forceinline__ void wide_children(const uint4 q0, const uint4 q1, co
     const uint32_t nb = ~(((q2.w >> 20) | ((q0.w >> 24) << 12)) << 3);             // leaf child: ~((tri_base << 3) + byte) = nb - byte
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const float nx = __builtin_fmaf(wide_byte(nxw, i), sx, bx), fx = __builtin_fmaf(wide_byte(fxw, i), sx, bx);
-        const float ny = __builtin_fmaf(wide_byte(nyw, i), sy, by), fy = __builtin_fmaf(wide_byte(fyw, i), sy, by);
-        const float nz = __builtin_fmaf(wide_byte(nzw, i), sz, bz), fz = __builtin_fmaf(wide_byte(fzw, i), sz, bz);
+        const float nx = __builtin_fmaf(wide_byte(nxw, i), sx, bx), fx = __builtin_fmaf(wide_byte(fxw, i), sx, cx);
+        const float ny = __builtin_fmaf(wide_byte(nyw, i), sy, by), fy = __builtin_fmaf(wide_byte(fyw, i), sy, cy);
+        const float nz = __builtin_fmaf(wide_byte(nzw, i), sz, bz), fz = __builtin_fmaf(wide_byte(fzw, i), sz, cz);
         tn[i] = fmaxf(fmaxf(nx, ny), fmaxf(nz, 0.0f));
         const float tf = fminf(fminf(fx, fy), fminf(fz, s.tlimit));
         h[i] = tn[i] <= tf;
