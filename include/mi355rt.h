@@ -921,6 +921,68 @@ int  mi355rt_probes_lookup_one(const mi355rt_probe_grid* grid, const uint32_t* n
                                const float dir[3], uint32_t mode, float rgb[3], uint32_t* ok /* may be NULL */);
 int  mi355rt_probe_grid_points(const mi355rt_probe_grid* grid, float* points3);
 
+/* ---- PROBE VISIBILITY: depth moments per probe, and a lookup that trusts a probe less where it does not see (no reference counterpart).
+ * Each probe also records how far it sees in each direction: a DEPTH FILM of res x res texels over an octahedral map of the sphere, per texel count (u32) and
+ * the sums of dist and dist * dist (f32), accumulated in sample order over the SAME samples as PROBES' gather.  The weighted lookup multiplies each corner's
+ * trilinear weight by a Chebyshev bound on the chance that the probe sees as far as the query.  raytracer-rs_amd/probes.py states all of it.  Everything is
+ * f32, unfused, in the order written, with + - * / sqrt, comparisons and integer conversions only.
+ *
+ * THE MAP of a direction v = (x, y, z), used as given (not normalised), to the unit square:
+ *     s = (|x| + |y|) + |z|;  px = x / s;  py = y / s;
+ *     z < 0:  (px, py) = ((1 - |py|) * sx, (1 - |px|) * sy), both right sides from the old values, sx = x >= 0 ? 1 : -1, sy likewise
+ *     u = px * 0.5f + 0.5f;  w = py * 0.5f + 0.5f
+ * THE TEXEL of a sample: per axis g = u * (float)res, made 0 where !(g >= 0), i = min((uint32_t)g, res - 1); the texel's index is iy * res + ix.
+ *
+ * GATHER_DEPTH.  The samples, keys and rays are mi355rt_probes_gather's, traced once.  Per point, in sample order, with D = depth->max_distance:
+ *     dist = hit ? (t < D ? t : D) : D   (a NaN t becomes D);   k = texel(d);   count[k] += 1;   moments[k][0] += dist;   moments[k][1] += dist * dist
+ * Every sample goes into exactly one texel.  count is npoints x res * res u32, moments npoints x res * res x 2 f32.  `out` may be NULL (the depth film alone);
+ * where it is given its sums are those of mi355rt_probes_gather on every bit.  cfg->accumulate covers the depth film as it covers `out`.  Around the call
+ * mi355rt_probes_gather's rules hold; mi355rt_last_counts reports npoints * spp primary rays.
+ * ERRORS.  Those of mi355rt_probes_gather (an `out` that is NULL is fine, one whose pointers are all NULL is not), and: depth NULL; res outside 2 .. 16;
+ * max_distance not finite, not > 0 or > 1e12; count or moments NULL.  Nothing is written.
+ *
+ * VISIBILITY of one probe for v = p_b - probe position.  In this order:
+ *     r = sqrt((x * x + y * y) + z * z);  r not a positive finite number (0, a NaN, an overflow to infinity): 1
+ *     bilinear fetch of the texel means at (u, w) = map(v), per axis without a floor:  g = u * (float)res + 0.5f;  i1 = (uint32_t)g;  f = g - (float)i1;
+ *         the two texels are i1 - 1 and i1 (signed) with weights 1 - f and f
+ *     an index pair (i, j) outside [0, res - 1]^2 wraps by the octahedral rule, the x rule first and the y rule on its result:
+ *         i < 0 -> (0, res-1-j);  i >= res -> (res-1, res-1-j);   then  j < 0 -> (res-1-i, 0);  j >= res -> (res-1-i, res-1)
+ *     the four texels in the order (dj, di) = (0,0), (0,1), (1,0), (1,1), wt = wx * wy;  a texel with wt == 0 or count == 0 is skipped and never read into a sum;
+ *         else  ws += wt;  a += wt * (m0 / (float)count);  b += wt * (m1 / (float)count)
+ *     ws == 0 (no information): 1.   mean = a / ws;  mean2 = b / ws;   r <= mean: 1
+ *     var = |mean2 - mean * mean|;  dd = r - mean;  c = var / (var + dd * dd);   the weight is (c * c) * c
+ *
+ * LOOKUP_VIS is LOOKUP of PROBES with the weight of corner j  wj = (t_j * vis) * face  in the place of t_j: in wsum += wj and in s_j = wj * (4 pi / n_j).
+ *     p_b = p + normal_bias * normal (one multiply, one add per axis); without normals p_b = p.  v = p_b - probe position.
+ *     vis = VISIBILITY(v) with MI355RT_VIS_CHEBYSHEV, else 1
+ *     face = q * q + 0.2f with MI355RT_VIS_FACING where r is a positive finite number, else 1;  q = (dot / r + 1) * 0.5f, made 0.0001f where !(q >= 0.0001f),
+ *         dot = ((-x) * nx + (-y) * ny) + (-z) * nz
+ *     The cell and the trilinear fractions come from p, not p_b.  A corner with t_j == 0, n_j == 0 or usable == 0 is skipped before anything else of it is
+ *     read, as in LOOKUP; a corner whose wj is 0 is skipped like them.  No corner used: rgb = 0, ok = 0.  Nothing is clamped.
+ * With flags 0 and normal_bias 0 the call is mi355rt_probes_lookup on every bit: (t * 1) * 1 is t.  Around the call mi355rt_probes_lookup's rules hold.
+ * ERRORS.  Those of mi355rt_probes_lookup, and: depth NULL, its res or max_distance out of range, its count or moments NULL; vc NULL; unknown flag bits; a
+ * normal_bias that is not finite; MI355RT_VIS_FACING or a non-zero normal_bias with normals3 NULL.  Nothing is written.
+ *
+ * Host only, no handle, the same header the kernels compile (csrc/oct_vis.hpp): mi355rt_oct_encode (THE MAP), mi355rt_oct_texel (THE TEXEL: ixy = (ix, iy)),
+ * mi355rt_probe_visibility_one (VISIBILITY; count and moments are the film of that one probe), mi355rt_probes_lookup_vis_one (LOOKUP_VIS of one query, *ok may
+ * be NULL); the message of a refusal is in mi355rt_last_error(NULL). */
+#define MI355RT_VIS_CHEBYSHEV 1u
+#define MI355RT_VIS_FACING    2u
+typedef struct mi355rt_probe_depth { uint32_t res; float max_distance; uint32_t* count; float* moments; } mi355rt_probe_depth;   /* 24 bytes */
+typedef struct mi355rt_probe_vis_config { uint32_t flags; float normal_bias; } mi355rt_probe_vis_config;   /* 8 bytes */
+void mi355rt_probes_vis_default_config(mi355rt_probe_vis_config* vc);   /* flags MI355RT_VIS_CHEBYSHEV | MI355RT_VIS_FACING, normal_bias 0 */
+int  mi355rt_probes_gather_depth(mi355rt_handle* h, const float* points3, const uint32_t* ids /* NULL: i */, size_t npoints, const mi355rt_probe_config* cfg, uint32_t where,
+                                 const mi355rt_probe_outputs* out /* may be NULL */, const mi355rt_probe_depth* depth);
+int  mi355rt_probes_lookup_vis(mi355rt_handle* h, const mi355rt_probe_grid* grid, const uint32_t* n, const float* sh, const uint8_t* usable /* may be NULL */,
+                               const mi355rt_probe_depth* depth, const mi355rt_probe_vis_config* vc, const float* points3, const float* dirs3,
+                               const float* normals3 /* may be NULL */, size_t npoints, uint32_t mode, uint32_t where, float* rgb3, uint8_t* ok /* may be NULL */);
+int  mi355rt_oct_encode(const float dir[3], float uv[2]);
+int  mi355rt_oct_texel(const float dir[3], uint32_t res, uint32_t ixy[2]);
+int  mi355rt_probe_visibility_one(const mi355rt_probe_depth* depth_of_one_probe, const float v[3], float* weight);
+int  mi355rt_probes_lookup_vis_one(const mi355rt_probe_grid* grid, const uint32_t* n, const float* sh, const uint8_t* usable /* may be NULL */,
+                                   const mi355rt_probe_depth* depth, const mi355rt_probe_vis_config* vc, const float point[3], const float dir[3],
+                                   const float normal[3] /* may be NULL */, uint32_t mode, float rgb[3], uint32_t* ok /* may be NULL */);
+
 /* SampleGenerator table, sample_generator.rs:15-24: 65 536 x 3 floats */
 int mi355rt_get_sample_table(const mi355rt_handle* h, float* out);
 /* Per-node direct-light terms of one primary sample, computed on the device by the same

@@ -204,6 +204,22 @@ class ProbeGrid(C.Structure):
 
 PROBE_OUTPUTS = ("n", "hits", "near", "sh")
 
+VIS_CHEBYSHEV, VIS_FACING = 1, 2      # MI355RT_VIS_*
+
+
+class ProbeDepth(C.Structure):
+    """mi355rt_probe_depth (include/mi355rt.h, "PROBE VISIBILITY"): count is nprobes x res * res uint32, moments nprobes x res * res x 2 float32 (void pointers
+    here: host arrays or device addresses)"""
+    _fields_ = [("res", C.c_uint32), ("max_distance", C.c_float), ("count", C.c_void_p), ("moments", C.c_void_p)]
+
+
+class ProbeVisConfig(C.Structure):
+    """mi355rt_probe_vis_config: flags VIS_CHEBYSHEV | VIS_FACING, normal_bias"""
+    _fields_ = [("flags", C.c_uint32), ("normal_bias", C.c_float)]
+
+
+PROBE_DEPTH_OUTPUTS = PROBE_OUTPUTS + ("count", "moments")
+
 LENS_PINHOLE, LENS_THIN, LENS_ORTHO = 0, 1, 2      # MI355RT_LENS_*
 LENS_MODELS = {"pinhole": LENS_PINHOLE, "thin": LENS_THIN, "ortho": LENS_ORTHO}
 
@@ -293,6 +309,14 @@ ABI = [
     ("mi355rt_sh9_basis", C.c_int, [_F, _F]),
     ("mi355rt_probes_lookup_one", C.c_int, [C.POINTER(ProbeGrid), _U, _F, C.POINTER(C.c_uint8), _F, _F, C.c_uint32, _F, _U]),
     ("mi355rt_probe_grid_points", C.c_int, [C.POINTER(ProbeGrid), _F]),
+    ("mi355rt_probes_vis_default_config", None, [C.POINTER(ProbeVisConfig)]),
+    ("mi355rt_probes_gather_depth", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ProbeConfig), C.c_uint32, C.POINTER(ProbeOutputs), C.POINTER(ProbeDepth)]),
+    ("mi355rt_probes_lookup_vis", C.c_int, [_H, C.POINTER(ProbeGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ProbeDepth), C.POINTER(ProbeVisConfig), C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("mi355rt_oct_encode", C.c_int, [_F, _F]),
+    ("mi355rt_oct_texel", C.c_int, [_F, C.c_uint32, _U]),
+    ("mi355rt_probe_visibility_one", C.c_int, [C.POINTER(ProbeDepth), _F, _F]),
+    ("mi355rt_probes_lookup_vis_one", C.c_int, [C.POINTER(ProbeGrid), _U, _F, C.POINTER(C.c_uint8), C.POINTER(ProbeDepth), C.POINTER(ProbeVisConfig), _F, _F, _F, C.c_uint32, _F, _U]),
     ("mi355rt_lens_default", None, [C.POINTER(Lens)]),
     ("mi355rt_set_lens", C.c_int, [_H, C.POINTER(Lens)]),
     ("mi355rt_get_lens", C.c_int, [_H, C.POINTER(Lens)]),
@@ -1111,6 +1135,130 @@ class RayTracer:
             rgb = np.zeros((m, 3), np.float32); ok = np.zeros(m, np.uint8) if want_ok else None
             raddr, oaddr = rgb.ctypes.data, ok.ctypes.data if want_ok else None
         self._check(lib().mi355rt_probes_lookup(self._h, C.byref(g), naddr, saddr, uaddr, addr, daddr, m, SH_MODES[mode], RAYS_DEVICE if dev else RAYS_HOST, raddr, oaddr))
+        return (rgb, ok) if want_ok else rgb
+
+    @staticmethod
+    def _film_array(a, name, shape, dtype):
+        """_ray_array for an argument of exactly this shape (rows, ...): checked as the (rows, rest) view of the same memory"""
+        if not (_is_tensor(a) or isinstance(a, np.ndarray)):
+            raise TypeError("%s: a numpy array or a torch tensor, not %s" % (name, type(a).__name__))
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError("%s: shape must be %s, not %s" % (name, tuple(shape), tuple(a.shape)))
+        if not (a.is_contiguous() if _is_tensor(a) else a.flags["C_CONTIGUOUS"]):
+            raise ValueError("%s: must be C-contiguous" % name)                 # before the reshape, which would copy
+        rest = int(np.prod(shape[1:], dtype=np.int64))
+        return _ray_array(a.reshape(shape[0], rest), name, rest, dtype, rows=shape[0])
+
+    def probes_gather_depth(self, points, ids=None, spp=64, first_sample=0, near_distance=float("inf"), res=8, max_distance=None,
+                            want=("n", "sh", "count", "moments"), into=None):
+        """mi355rt_probes_gather_depth: probes_gather, and from the same traced samples each probe's depth film over an octahedral map of res x res texels
+        (raytracer_rs_amd.probes.project_depth is the statement): count uint32 (n, res * res) and moments float32 (n, res * res, 2), the sums of dist and
+        dist^2 with dist = min(t, max_distance) and max_distance for a miss.  res: 2 .. 16; max_distance: finite, > 0, <= 1e12 (probes.grid_max_distance(grid)
+        is the usual choice; None: that of `into`).  want: any of "n", "hits", "near", "sh", "count", "moments"; count and moments come together.  numpy
+        arrays or torch tensors on the handle's GPU, under probes_gather's rules.  into: the dict of an earlier call with the same res and max_distance; its
+        arrays are added to and returned.  Returns a dict name -> array, with "depth_res" and "max_distance" when it holds a depth film.  No film, camera or
+        lens state changes."""
+        want = tuple(want)
+        if not want or any(w not in PROBE_DEPTH_OUTPUTS for w in want) or len(set(want)) != len(want):
+            raise ValueError("want: a non-empty selection of %s without repeats, not %r" % (PROBE_DEPTH_OUTPUTS, want))
+        if ("count" in want) != ("moments" in want):
+            raise ValueError('want: "count" and "moments" come together')
+        if "count" not in want:
+            return self.probes_gather(points, ids, spp, first_sample, near_distance, want, into)
+        res = int(res)
+        if into is not None:
+            if "depth_res" not in into or "max_distance" not in into:
+                raise ValueError("into: holds no depth film (depth_res, max_distance)")
+            if max_distance is None:
+                max_distance = into["max_distance"]
+            if int(into["depth_res"]) != res or float(np.float32(into["max_distance"])) != float(np.float32(max_distance)):
+                raise ValueError("into: its depth film has res %r and max_distance %r, not %r and %r" % (into["depth_res"], into["max_distance"], res, max_distance))
+        if max_distance is None:
+            raise ValueError("max_distance: give one (probes.grid_max_distance(grid) is the usual choice)")
+        max_distance = float(np.float32(max_distance))
+        if not 2 <= res <= 16:
+            raise ValueError("res: 2 .. 16, not %r" % res)
+        if not (np.isfinite(max_distance) and 0.0 < max_distance <= 1e12):
+            raise ValueError("max_distance: finite, > 0 and <= 1e12, not %r" % max_distance)
+        addr, n, dev = _ray_array(points, "points", 3, np.float32)
+        iaddr = None
+        if ids is not None:
+            iaddr, _, idev = _ray_vector(ids, "ids", np.uint32, n)
+            if idev != dev:
+                raise ValueError("ids must live where points live (both numpy arrays, or both tensors on the GPU)")
+        cfg = ProbeConfig()
+        lib().mi355rt_probes_default_config(C.byref(cfg))
+        cfg.spp, cfg.first_sample, cfg.accumulate, cfg.near_distance = int(spp), int(first_sample), 1 if into is not None else 0, float(near_distance)
+        shapes = {"sh": (n, 9, 3), "count": (n, res * res), "moments": (n, res * res, 2)}
+        out, o, d = {}, ProbeOutputs(), ProbeDepth(res, max_distance, None, None)
+        if dev:
+            import torch
+        for w in want:
+            shape, f32 = shapes.get(w, (n,)), w in ("sh", "moments")
+            if into is not None:
+                if w not in into:
+                    raise ValueError("into: holds no %r" % w)
+                a = into[w]
+                a_addr, _, adev = self._film_array(a, "into[%r]" % w, shape, np.float32 if f32 else np.uint32) if len(shape) > 1 else _ray_vector(a, "into[%r]" % w, np.uint32, n)
+                if adev != dev:
+                    raise ValueError("into[%r] must live where points live" % w)
+            elif dev:
+                a = torch.zeros(shape, dtype=torch.float32 if f32 else torch.int32, device=points.device)
+                a_addr = a.data_ptr()
+            else:
+                a = np.zeros(shape, np.float32 if f32 else np.uint32)
+                a_addr = a.ctypes.data
+            out[w] = a
+            setattr(d if w in ("count", "moments") else o, w, a_addr)
+        out["depth_res"], out["max_distance"] = res, max_distance
+        if dev:
+            torch.cuda.current_stream(points.device).synchronize()          # what produced the inputs (and the zero fill) has finished: the library's stream knows nothing of torch's
+        only_depth = all(w in ("count", "moments") for w in want)
+        self._check(lib().mi355rt_probes_gather_depth(self._h, addr, iaddr, n, C.byref(cfg), RAYS_DEVICE if dev else RAYS_HOST, None if only_depth else C.byref(o), C.byref(d)))
+        return out
+
+    def probes_lookup_vis(self, grid, res, points, dirs, normals=None, mode="irradiance", usable=None, chebyshev=True, facing=True, normal_bias=0.0, want_ok=False):
+        """mi355rt_probes_lookup_vis: probes_lookup with each corner's trilinear weight multiplied by the probe's visibility of the query (Chebyshev's bound on
+        its depth film) and by how much the surface faces the probe (raytracer_rs_amd.probes.lookup_vis is the statement); traces nothing.  res: the dict
+        probes_gather_depth returned at probes.grid_points(grid), with n, sh, count, moments, depth_res and max_distance.  normals: float32 (m, 3) unit normals
+        of the surface at the points, or None: then facing has no effect and normal_bias must be 0.  With chebyshev=False, facing=False and normal_bias=0 the
+        result is probes_lookup's on every bit.  numpy arrays or torch tensors on the handle's GPU, all alike.  Returns rgb float32 (m, 3), with want_ok
+        (rgb, ok uint8 (m,))."""
+        if mode not in SH_MODES:
+            raise ValueError("mode: one of %s, not %r" % (tuple(SH_MODES), mode))
+        for k in ("n", "sh", "count", "moments", "depth_res", "max_distance"):
+            if k not in res:
+                raise ValueError("res: holds no %r (probes_gather_depth returns it)" % k)
+        g = grid if isinstance(grid, ProbeGrid) else ProbeGrid.from_dict(grid)
+        nprobes = int(g.counts[0]) * int(g.counts[1]) * int(g.counts[2])
+        R = int(res["depth_res"])
+        if not 2 <= R <= 16:
+            raise ValueError('res["depth_res"]: 2 .. 16, not %r' % R)
+        addr, m, dev = _ray_array(points, "points", 3, np.float32)
+        daddr, _, ddev = _ray_array(dirs, "dirs", 3, np.float32, rows=m)
+        naddr, _, ndev = _ray_vector(res["n"], 'res["n"]', np.uint32, nprobes)
+        saddr, _, sdev = self._sh_array(res["sh"], 'res["sh"]', nprobes)
+        caddr, _, cdev = self._film_array(res["count"], 'res["count"]', (nprobes, R * R), np.uint32)
+        maddr, _, mdev = self._film_array(res["moments"], 'res["moments"]', (nprobes, R * R, 2), np.float32)
+        uaddr, udev, nraddr, nrdev = None, dev, None, dev
+        if usable is not None:
+            uaddr, _, udev = _ray_vector(usable, "usable", np.uint8, nprobes)
+        if normals is not None:
+            nraddr, _, nrdev = _ray_array(normals, "normals", 3, np.float32, rows=m)
+        if not (ddev == ndev == sdev == cdev == mdev == udev == nrdev == dev):
+            raise ValueError("dirs, normals, res and usable must live where points live (all numpy arrays, or all tensors on the GPU)")
+        d = ProbeDepth(R, float(np.float32(res["max_distance"])), caddr, maddr)
+        vc = ProbeVisConfig((VIS_CHEBYSHEV if chebyshev else 0) | (VIS_FACING if facing and normals is not None else 0), float(normal_bias))
+        if dev:
+            import torch
+            rgb = torch.zeros((m, 3), dtype=torch.float32, device=points.device); ok = torch.zeros(m, dtype=torch.uint8, device=points.device) if want_ok else None
+            raddr, oaddr = rgb.data_ptr(), ok.data_ptr() if want_ok else None
+            torch.cuda.current_stream(points.device).synchronize()
+        else:
+            rgb = np.zeros((m, 3), np.float32); ok = np.zeros(m, np.uint8) if want_ok else None
+            raddr, oaddr = rgb.ctypes.data, ok.ctypes.data if want_ok else None
+        self._check(lib().mi355rt_probes_lookup_vis(self._h, C.byref(g), naddr, saddr, uaddr, C.byref(d), C.byref(vc), addr, daddr, nraddr, m, SH_MODES[mode],
+                                                    RAYS_DEVICE if dev else RAYS_HOST, raddr, oaddr))
         return (rgb, ok) if want_ok else rgb
 
     def bake_texels(self, uv, width, height, flip=False, want=BAKE_TEXEL_OUTPUTS):

@@ -17,6 +17,7 @@
 #include "lens.hpp"
 #include "renderer.hpp"
 #include "sh9.hpp"
+#include "oct_vis.hpp"
 
 using namespace mi355rt;
 
@@ -1063,6 +1064,128 @@ int mi355rt_probe_grid_points(const mi355rt_probe_grid* grid, float* points3)
                 o[1] = sh9_probe_pos(grid->origin[1], grid->spacing[1], iy);
                 o[2] = sh9_probe_pos(grid->origin[2], grid->spacing[2], iz);
             }
+    return MI355RT_OK;
+}
+
+// ---- probe visibility (include/mi355rt.h, "PROBE VISIBILITY") ------------------------------------------------------------------------------
+namespace {
+// the checks of a depth film and of a visibility config; null: fine, else the message that names the field
+const char* probe_depth_error(const mi355rt_probe_depth* d)
+{
+    if (!d) return "depth is NULL";
+    if (d->res < kOctResMin || d->res > kOctResMax) return "depth.res must be 2 .. 16";
+    if (!(std::isfinite(d->max_distance) && d->max_distance > 0.0f && d->max_distance <= kOctMaxDistanceTop)) return "depth.max_distance must be finite, > 0 and <= 1e12";
+    if (!d->count) return "depth.count is NULL";
+    if (!d->moments) return "depth.moments is NULL";
+    return nullptr;
+}
+const char* probe_vis_error(const mi355rt_probe_vis_config* vc, bool has_normals)
+{
+    if (!vc) return "vc is NULL";
+    if (vc->flags & ~(MI355RT_VIS_CHEBYSHEV | MI355RT_VIS_FACING)) return "vc.flags: unknown bits (MI355RT_VIS_CHEBYSHEV, MI355RT_VIS_FACING)";
+    if (!std::isfinite(vc->normal_bias)) return "vc.normal_bias must be finite";
+    if (!has_normals && (vc->flags & MI355RT_VIS_FACING)) return "MI355RT_VIS_FACING needs normals3, which is NULL";
+    if (!has_normals && vc->normal_bias != 0.0f) return "a non-zero normal_bias needs normals3, which is NULL";
+    return nullptr;
+}
+}  // namespace
+
+void mi355rt_probes_vis_default_config(mi355rt_probe_vis_config* vc)
+{
+    if (!vc) return;
+    vc->flags = MI355RT_VIS_CHEBYSHEV | MI355RT_VIS_FACING; vc->normal_bias = 0.0f;
+}
+
+int mi355rt_probes_gather_depth(mi355rt_handle* h, const float* points3, const uint32_t* ids, size_t npoints, const mi355rt_probe_config* cfg, uint32_t where,
+                                const mi355rt_probe_outputs* out, const mi355rt_probe_depth* depth)
+{
+    if (!h) return MI355RT_E_INVALID;
+    const char* e = nullptr;
+    if ((e = single_device_ok(h, where)) != nullptr) {}
+    else if (!cfg) e = "cfg is NULL";
+    else if (out && !out->n && !out->hits && !out->near && !out->sh) e = "every output pointer in out is NULL (pass out as NULL for the depth film alone)";
+    else if ((e = probe_depth_error(depth)) != nullptr) {}
+    else if (npoints && !points3) e = "points3 is NULL";
+    else if (cfg->spp == 0) e = "spp must be >= 1";
+    else if (std::isnan(cfg->near_distance)) e = "near_distance is NaN";
+    else if ((uint64_t)cfg->first_sample + cfg->spp > 0xFFFFFFFFull) e = "first_sample + spp must fit 32 bits";
+    else if (npoints > 0xFFFFFFFFull || (uint64_t)npoints * cfg->spp >= (1ull << 32)) e = "npoints * spp must be < 2^32";
+    if (e) { h->r->last_error = std::string("mi355rt_probes_gather_depth: ") + e; return MI355RT_E_INVALID; }
+    if (npoints == 0) return MI355RT_OK;
+    const mi355rt_probe_outputs none{};
+    return h->r->probes_gather_depth(points3, ids, npoints, *cfg, where == MI355RT_RAYS_DEVICE, out ? *out : none, *depth) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_probes_lookup_vis(mi355rt_handle* h, const mi355rt_probe_grid* grid, const uint32_t* n, const float* sh, const uint8_t* usable, const mi355rt_probe_depth* depth,
+                              const mi355rt_probe_vis_config* vc, const float* points3, const float* dirs3, const float* normals3, size_t npoints, uint32_t mode, uint32_t where,
+                              float* rgb3, uint8_t* ok)
+{
+    if (!h) return MI355RT_E_INVALID;
+    const char* e = nullptr;
+    if ((e = single_device_ok(h, where)) != nullptr) {}
+    else if ((e = probe_grid_error(grid)) != nullptr) {}
+    else if (!n) e = "n is NULL";
+    else if (!sh) e = "sh is NULL";
+    else if ((e = probe_depth_error(depth)) != nullptr) {}
+    else if ((e = probe_vis_error(vc, normals3 != nullptr)) != nullptr) {}
+    else if (!rgb3) e = "rgb3 is NULL";
+    else if (npoints && !points3) e = "points3 is NULL";
+    else if (npoints && !dirs3) e = "dirs3 is NULL";
+    else if (mode > MI355RT_SH_IRRADIANCE) e = "unknown mode (MI355RT_SH_RADIANCE or MI355RT_SH_IRRADIANCE)";
+    else if (npoints > 0xFFFFFFFFull) e = "npoints must fit 32 bits";
+    if (e) { h->r->last_error = std::string("mi355rt_probes_lookup_vis: ") + e; return MI355RT_E_INVALID; }
+    if (npoints == 0) return MI355RT_OK;
+    return h->r->probes_lookup_vis(*grid, n, sh, usable, *depth, *vc, points3, dirs3, normals3, npoints, mode, where == MI355RT_RAYS_DEVICE, rgb3, ok) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_oct_encode(const float dir[3], float uv[2])
+{
+    if (!dir) return bad("mi355rt_oct_encode: dir is NULL");
+    if (!uv) return bad("mi355rt_oct_encode: uv is NULL");
+    oct_encode(dir[0], dir[1], dir[2], uv[0], uv[1]);
+    return MI355RT_OK;
+}
+
+int mi355rt_oct_texel(const float dir[3], uint32_t res, uint32_t ixy[2])
+{
+    if (!dir) return bad("mi355rt_oct_texel: dir is NULL");
+    if (!ixy) return bad("mi355rt_oct_texel: ixy is NULL");
+    if (res < kOctResMin || res > kOctResMax) return bad("mi355rt_oct_texel: res must be 2 .. 16");
+    const uint32_t k = oct_texel(dir[0], dir[1], dir[2], res);
+    ixy[0] = k % res; ixy[1] = k / res;
+    return MI355RT_OK;
+}
+
+int mi355rt_probe_visibility_one(const mi355rt_probe_depth* depth, const float v[3], float* weight)
+{
+    const char* e = probe_depth_error(depth);
+    if (!e) e = !v ? "v is NULL" : !weight ? "weight is NULL" : nullptr;
+    if (e) { g_create_error = std::string("mi355rt_probe_visibility_one: ") + e; return MI355RT_E_INVALID; }
+    const uint32_t* count = depth->count; const float* moments = depth->moments;
+    *weight = oct_visibility(depth->res, [count](uint32_t k) { return count[k]; }, [moments](uint32_t k, int m) { return moments[2 * (size_t)k + m]; }, v[0], v[1], v[2],
+                             oct_length(v[0], v[1], v[2]));
+    return MI355RT_OK;
+}
+
+int mi355rt_probes_lookup_vis_one(const mi355rt_probe_grid* grid, const uint32_t* n, const float* sh, const uint8_t* usable, const mi355rt_probe_depth* depth,
+                                  const mi355rt_probe_vis_config* vc, const float point[3], const float dir[3], const float normal[3], uint32_t mode, float rgb[3], uint32_t* ok)
+{
+    const char* e = probe_grid_error(grid);
+    if (!e) e = !n ? "n is NULL" : !sh ? "sh is NULL" : nullptr;
+    if (!e) e = probe_depth_error(depth);
+    if (!e) e = probe_vis_error(vc, normal != nullptr);
+    if (!e) e = !point ? "point is NULL" : !dir ? "dir is NULL" : !rgb ? "rgb is NULL" : mode > MI355RT_SH_IRRADIANCE ? "unknown mode" : nullptr;
+    if (e) { g_create_error = std::string("mi355rt_probes_lookup_vis_one: ") + e; return MI355RT_E_INVALID; }
+    ShGrid g;
+    std::memcpy(&g, grid, sizeof g);
+    const uint32_t* count = depth->count; const float* moments = depth->moments;
+    const size_t RR = (size_t)depth->res * depth->res;
+    const float zero[3] = { 0.0f, 0.0f, 0.0f };
+    const bool used = sh9_lookup_vis(g, [n](size_t j) { return n[j]; }, [sh](size_t j, int c) { return sh[27 * j + c]; }, usable != nullptr,
+                                     [usable](size_t j) { return usable[j] != 0; }, depth->res, [count, RR](size_t j, uint32_t k) { return count[j * RR + k]; },
+                                     [moments, RR](size_t j, uint32_t k, int m) { return moments[2 * (j * RR + k) + m]; }, vc->flags, vc->normal_bias, point, dir,
+                                     normal != nullptr, normal ? normal : zero, mode, rgb);
+    if (ok) *ok = used ? 1u : 0u;
     return MI355RT_OK;
 }
 

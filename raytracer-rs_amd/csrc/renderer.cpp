@@ -15,6 +15,7 @@
 #include "lens.hpp"
 #include "octree.hpp"
 #include "probes.hpp"
+#include "probes_vis.hpp"
 #include "staging.hpp"
 
 namespace mi355rt {
@@ -1716,6 +1717,61 @@ bool Renderer::probes_lookup(const mi355rt_probe_grid& grid, const uint32_t* n, 
     float* d_rgb = st.out(rgb3, npoints * 3); uint8_t* d_ok = st.out(ok, npoints);
     HIP_TRY(st.error());
     HIP_TRY(launch_probes_lookup(stream_, g, d_n, d_sh, d_usable, d_points, d_dirs, npoints, mode, d_rgb, d_ok));
+    HIP_TRY(st.download());
+    HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's buffers are complete, on whatever stream they are used next
+    return true;
+}
+
+// mi355rt_probes_gather_depth: probes_gather with a second reduce over the same traced chunk — the depth film of csrc/probes_vis.hip.  The
+// chunk temporary of its first phase (8 bytes per entry) is made when the first, largest chunk arrives and goes with the call, counted like every other.
+bool Renderer::probes_gather_depth(const float* points3, const uint32_t* ids, size_t npoints, const mi355rt_probe_config& pc, bool device, const mi355rt_probe_outputs& out,
+                                   const mi355rt_probe_depth& depth)
+{
+    if (!begin_call()) return false;
+    const size_t total = npoints * pc.spp, RR = (size_t)depth.res * depth.res;
+    Staging st(stream_, &hbm_bytes_, device);
+    const float* d_points = st.in(points3, npoints * 3); const uint32_t* d_ids = st.in(ids, npoints);
+    const bool acc = pc.accumulate != 0;                              // then the outputs go up first: the call adds to what they hold
+    mi355rt_probe_outputs d{};
+    d.n = st.out(out.n, npoints, acc); d.hits = st.out(out.hits, npoints, acc); d.near = st.out(out.near, npoints, acc); d.sh = st.out(out.sh, npoints * 27, acc);
+    uint32_t* d_count = st.out(depth.count, npoints * RR, acc); float* d_moments = st.out(depth.moments, npoints * RR * 2, acc);
+    HIP_TRY(st.error());
+    const bool project = d.n || d.hits || d.near || d.sh;
+    DeviceBuffer<uint2> bins;
+    if (!gather_chunks(d_points, nullptr, d_ids, npoints, pc.spp, pc.first_sample, true, out.sh != nullptr, true, [&](const GatherChunk& c) {
+            const bool fresh = !acc && c.sample0 == 0;
+            if (project) {
+                const hipError_t e = launch_probes_project(stream_, c.point0, c.cp, c.cs, fresh, pc.near_distance, c.rays, c.rgb, c.tuv, c.prim, d.n, d.hits, d.near, d.sh);
+                if (e != hipSuccess) return e;
+            }
+            const size_t need = (size_t)c.cp * c.cs * sizeof(uint2);
+            if (bins.bytes() < need) {
+                const hipError_t e = bins.alloc(need, &hbm_bytes_);
+                if (e != hipSuccess) return e;
+            }
+            return launch_probes_depth(stream_, c.point0, c.cp, c.cs, fresh, depth.res, depth.max_distance, c.rays, c.tuv, c.prim, bins.get(), d_count, d_moments);
+        })) return false;
+    HIP_TRY(st.download());
+    return end_call(total, true);                                     // waits: the staging (and the caller's buffers) are free again
+}
+
+// mi355rt_probes_lookup_vis: probes_lookup with the depth films among its inputs; one kernel, and probes_lookup's rules around it.
+bool Renderer::probes_lookup_vis(const mi355rt_probe_grid& grid, const uint32_t* n, const float* sh, const uint8_t* usable, const mi355rt_probe_depth& depth,
+                                 const mi355rt_probe_vis_config& vc, const float* points3, const float* dirs3, const float* normals3, size_t npoints, uint32_t mode, bool device,
+                                 float* rgb3, uint8_t* ok)
+{
+    if (!quiet()) return false;
+    const size_t nprobes = (size_t)grid.counts[0] * grid.counts[1] * grid.counts[2], RR = (size_t)depth.res * depth.res;
+    ShGrid g;
+    std::memcpy(&g, &grid, sizeof g);
+    Staging st(stream_, &hbm_bytes_, device);
+    const uint32_t* d_n = st.in(n, nprobes); const float* d_sh = st.in(sh, nprobes * 27); const uint8_t* d_usable = st.in(usable, nprobes);
+    const uint32_t* d_count = st.in((const uint32_t*)depth.count, nprobes * RR); const float* d_moments = st.in((const float*)depth.moments, nprobes * RR * 2);
+    const float* d_points = st.in(points3, npoints * 3); const float* d_dirs = st.in(dirs3, npoints * 3); const float* d_normals = st.in(normals3, npoints * 3);
+    float* d_rgb = st.out(rgb3, npoints * 3); uint8_t* d_ok = st.out(ok, npoints);
+    HIP_TRY(st.error());
+    HIP_TRY(launch_probes_lookup_vis(stream_, g, d_n, d_sh, d_usable, depth.res, d_count, d_moments, vc.flags, vc.normal_bias, d_points, d_dirs, d_normals, npoints, mode, d_rgb,
+                                     d_ok));
     HIP_TRY(st.download());
     HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's buffers are complete, on whatever stream they are used next
     return true;

@@ -53,6 +53,13 @@ public:
     bool probes_gather(const float* points3, const uint32_t* ids, size_t npoints, const mi355rt_probe_config& pc, bool device, const mi355rt_probe_outputs& out);
     bool probes_lookup(const mi355rt_probe_grid& grid, const uint32_t* n, const float* sh, const uint8_t* usable, const float* points3, const float* dirs3, size_t npoints,
                        uint32_t mode, bool device, float* rgb3, uint8_t* ok);
+    // probe visibility; the caller has checked the arguments.  probes_gather_depth: probes_gather (out may hold no pointer) with the depth film
+    // of the same traced pass; probes_lookup_vis: probes_lookup with each corner's weight multiplied by the probe's visibility and facing
+    bool probes_gather_depth(const float* points3, const uint32_t* ids, size_t npoints, const mi355rt_probe_config& pc, bool device, const mi355rt_probe_outputs& out,
+                             const mi355rt_probe_depth& depth);
+    bool probes_lookup_vis(const mi355rt_probe_grid& grid, const uint32_t* n, const float* sh, const uint8_t* usable, const mi355rt_probe_depth& depth,
+                           const mi355rt_probe_vis_config& vc, const float* points3, const float* dirs3, const float* normals3, size_t npoints, uint32_t mode, bool device,
+                           float* rgb3, uint8_t* ok);
     // bake; the caller has checked the arguments.  device: every pointer but ncovered is device memory.  Neither touches films, camera, counters
     bool bake_texels(const float* uv, uint32_t width, uint32_t height, bool flip, bool device, const mi355rt_bake_texel_outputs& out, uint32_t* ncovered);
     bool bake_atlas(const uint32_t* ids, const float* values3, uint32_t n, uint32_t width, uint32_t height, uint32_t dilate, bool device, float* atlas, uint8_t* valid, uint32_t& verdict);
