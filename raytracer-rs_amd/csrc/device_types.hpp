@@ -95,6 +95,25 @@ struct DCamera {
 struct FeaturePlanes { uint32_t* n; uint32_t* hits; float* depth; float* normal; float* albedo; };
 constexpr uint32_t kCullGrid = 1024;                      // cells per axis (32 words per row, 128 KiB)
 
+// THE FEED of a pass's primary round: where its rays come from.  The one definition — the renderer makes the value (run_pass), the launchers take it
+// (kernels.hpp, `rays`) and map it to the RAYS template argument of the wavefront kernels (variants.hpp, with_feed), which test it with `if constexpr`.
+//   kFeedCamera: the pinhole camera;  kFeedRays: the caller's buffer (DPass::ray_in);  kFeedLensThin / kFeedLensOrtho: the handle's lens
+//   (DCamera::lens, §3i);  kFeedLensThinMasked / kFeedLensOrthoMasked: the same in a pass with a tile mask (DPass::tile_active, §3j).
+constexpr uint32_t kFeedCamera = 0u, kFeedRays = 1u, kFeedLensThin = 2u, kFeedLensOrtho = 3u, kFeedLensThinMasked = 4u, kFeedLensOrthoMasked = 5u;
+template <uint32_t RAYS> constexpr bool kFeedLens = RAYS >= kFeedLensThin;
+template <uint32_t RAYS> constexpr bool kFeedThin = RAYS == kFeedLensThin || RAYS == kFeedLensThinMasked;
+// The feeds whose primary round honours the tile mask: the pinhole camera and the masked lens feeds, whose samples are pixels of the film.  Never the caller's rays.
+// Tested with `if constexpr`, so that an instantiation holds only its own feed's code.
+template <uint32_t RAYS> constexpr bool kFeedMasked = RAYS == kFeedCamera || RAYS == kFeedLensThinMasked || RAYS == kFeedLensOrthoMasked;
+// the feed of a pass under lens `model` (kLens*; host and device), masked: the pass has a tile mask.  The pinhole camera honours a mask itself.
+constexpr uint32_t lens_feed(uint32_t model, bool masked)
+{
+    return model == kLensPinhole ? kFeedCamera : model == kLensThin ? (masked ? kFeedLensThinMasked : kFeedLensThin) : (masked ? kFeedLensOrthoMasked : kFeedLensOrtho);
+}
+// Where a pass that is not the pinhole camera's takes its primary rays (Renderer::RayFeed::mode, DPass::ray_mode; DPass goes to the device by value: the numbers stay):
+// the film's pixels with the caller's rays, free rays (one sample each, results per ray), the film's pixels with the rays of the handle's lens
+constexpr uint32_t kRaysOfPixels = 1u, kRaysFree = 2u, kRaysOfLens = 3u;
+
 struct DPass {
     // primary-sample enumeration: thread i -> s = i / npix, p = i % npix,
     // row = rows[row0 + p / width], x = p % width, pixel = row * width + x
@@ -141,9 +160,9 @@ struct DPass {
     uint32_t tiles_x;
     // Ray-fed pass (mi355rt_trace_rays / mi355rt_render_rays): the primary rays come from ray_in, n x (pos3, dir3) as the caller laid them out,
     // not from the camera.  Read by the RAYS instantiations of the kernels only.
-    //   ray_mode 1 (render_rays): pass sample (s, p) of film pixel `pixel` reads ray (ray_base + s) * ray_npix + pixel — ray_base is the CALL's sample number
-    //                             of the pass's sample 0, ray_npix = width * height — and its key is (pixel, film_n[pixel] + s) as in every frame
-    //   ray_mode 2 (trace_rays):  sample gi of the pass IS ray gi of ray_in (the host offsets the pointers pass by pass); key ray_keys[gi], or
+    //   ray_mode kRaysOfPixels (render_rays): pass sample (s, p) of film pixel `pixel` reads ray (ray_base + s) * ray_npix + pixel — ray_base is the CALL's sample
+    //                             number of the pass's sample 0, ray_npix = width * height — and its key is (pixel, film_n[pixel] + s) as in every frame
+    //   ray_mode kRaysFree (trace_rays):      sample gi of the pass IS ray gi of ray_in (the host offsets the pointers pass by pass); key ray_keys[gi], or
     //                             (ray_base + gi, 0) without keys — ray_base is the index of the pass's ray 0 in the call
     // ray_hit (trace_rays with tuv or prim asked for): per sample the final hit (t, u, v, prim bits) of its primary ray, written by the primary shade launch
     const float* ray_in;

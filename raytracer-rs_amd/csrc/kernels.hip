@@ -43,6 +43,7 @@
 #include "lens.hpp"
 #include "reflmask.hpp"
 #include "traverse.hpp"
+#include "variants.hpp"
 
 namespace mi355rt {
 
@@ -257,27 +258,22 @@ struct __attribute__((packed, aligned(4))) RayHalf { float x, y, z; };
 struct __attribute__((packed, aligned(4))) RayKey { uint32_t pixel, sampleno; };
 
 // pixel -> primary ray, mod.rs:93-96 + camera.rs:80-90.  gi = index of the primary sample in the pass.
-// RAYS (a ray-fed pass): the ray is the caller's, used as given; the key (pixel, sampleno) is the film's numbering (ray_mode 1:
-// mi355rt_render_rays, the pass order and film_n as below) or the caller's (ray_mode 2: mi355rt_trace_rays, sample gi IS ray gi of the pass).
+// RAYS (a ray-fed pass): the ray is the caller's, used as given; the key (pixel, sampleno) is the film's numbering (ray_mode kRaysOfPixels:
+// mi355rt_render_rays, the pass order and film_n as below) or the caller's (ray_mode kRaysFree: mi355rt_trace_rays, sample gi IS ray gi of the pass).
 // RAYS is the feed of the primary round: kFeedCamera (the pinhole camera, everything below the two branches), kFeedRays (the caller's buffer),
 // kFeedLensThin / kFeedLensOrtho (the handle's lens, cam.lens — the ray is made in registers from the camera and ALL FOUR words of the
 // jitter's hash; no buffer.  One instantiation per model: with both models behind a wave-uniform branch the primary shade kernels spilled).
 // kFeedLensThinMasked / kFeedLensOrthoMasked (mi355rt_render_tiles under a lens): the lens feeds of a pass with a tile mask (DPass::tile_active).  Instantiations of
 // their own beside the unmasked ones: taught the mask in place, the THIN shade kernel without the confirm walk spilled (profiles/tiles_kernel_resources.txt), and an
 // unmasked frame under a lens launches exactly what it launched before.
-constexpr uint32_t kFeedCamera = 0u, kFeedRays = 1u, kFeedLensThin = 2u, kFeedLensOrtho = 3u, kFeedLensThinMasked = 4u, kFeedLensOrthoMasked = 5u;
-template <uint32_t RAYS> constexpr bool kFeedLens = RAYS >= kFeedLensThin;
-template <uint32_t RAYS> constexpr bool kFeedThin = RAYS == kFeedLensThin || RAYS == kFeedLensThinMasked;
-// The feeds whose primary round honours the tile mask: the pinhole camera and the masked lens feeds, whose samples are pixels of the film.  Never the caller's rays.
-// Tested with `if constexpr`, so that an instantiation holds only its own feed's code.
-template <uint32_t RAYS> constexpr bool kFeedMasked = RAYS == kFeedCamera || RAYS == kFeedLensThinMasked || RAYS == kFeedLensOrthoMasked;
+// (the feed constants and their predicates: device_types.hpp)
 template <uint32_t RAYS = kFeedCamera>
 __device__ __forceinline__ void primary_sample(const DCamera& cam, const DPass& ps, const uint32_t* __restrict__ film_n, uint32_t gi,
                                                uint32_t& pixel, uint32_t& sampleno, f3& o, f3& d)
 {
     if constexpr (RAYS == kFeedRays) {
         size_t ri = gi;
-        if (ps.ray_mode == 2u) {
+        if (ps.ray_mode == kRaysFree) {
             if (ps.ray_keys != nullptr) { const RayKey k = ((const RayKey*)ps.ray_keys)[gi]; pixel = k.pixel; sampleno = k.sampleno; }
             else { pixel = ps.ray_base + gi; sampleno = 0u; }
         } else {
@@ -2379,18 +2375,9 @@ hipError_t launch_trace(hipStream_t stream, int num_cus, bool primary, bool coun
                         const void* in_q, const void* in_counts, void* hits, uint32_t* cursor,
                         float* slot_L, const uint32_t* film_n, DCounters* counters, uint32_t rays)
 {
-#define MI355RT_TRACE_ARGS stream, num_cus, sc, cam, ps, in_q, in_counts, hits, cursor, slot_L, film_n, counters
-    if (rays && !primary) return hipErrorInvalidValue;         // only the primary round of a pass is ray-fed
-    if (rays > kFeedLensOrthoMasked) return hipErrorInvalidValue;
-    if (rays == kFeedLensThinMasked) return count ? launch_trace_variant<true, true, true, kFeedLensThinMasked>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true, kFeedLensThinMasked>(MI355RT_TRACE_ARGS);
-    if (rays == kFeedLensOrthoMasked) return count ? launch_trace_variant<true, true, true, kFeedLensOrthoMasked>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true, kFeedLensOrthoMasked>(MI355RT_TRACE_ARGS);
-    if (rays == kFeedLensThin) return count ? launch_trace_variant<true, true, true, kFeedLensThin>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true, kFeedLensThin>(MI355RT_TRACE_ARGS);
-    if (rays == kFeedLensOrtho) return count ? launch_trace_variant<true, true, true, kFeedLensOrtho>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true, kFeedLensOrtho>(MI355RT_TRACE_ARGS);
-    if (rays) return count ? launch_trace_variant<true, true, true, kFeedRays>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true, kFeedRays>(MI355RT_TRACE_ARGS);
-    if (primary) return count ? launch_trace_variant<true, true, true>(MI355RT_TRACE_ARGS) : launch_trace_variant<true, false, true>(MI355RT_TRACE_ARGS);
-    if (confirm) return count ? launch_trace_variant<false, true, true>(MI355RT_TRACE_ARGS) : launch_trace_variant<false, false, true>(MI355RT_TRACE_ARGS);
-    return count ? launch_trace_variant<false, true, false>(MI355RT_TRACE_ARGS) : launch_trace_variant<false, false, false>(MI355RT_TRACE_ARGS);
-#undef MI355RT_TRACE_ARGS
+    return select_trace(primary, count, confirm, rays, [&](auto P, auto C, auto F, auto R) {
+        return launch_trace_variant<P(), C(), F(), R()>(stream, num_cus, sc, cam, ps, in_q, in_counts, hits, cursor, slot_L, film_n, counters);
+    });
 }
 
 // one wave per pixel block of the pass: the culling verdict of its chunk in the first sample group (DPass::block_culled)
@@ -2414,53 +2401,31 @@ hipError_t launch_cull_blocks(hipStream_t stream, const DCamera& cam, const DPas
 hipError_t launch_trace_octree(hipStream_t stream, int num_cus, bool primary, const DScene& sc, const DCamera& cam, const DPass& ps,
                                const void* in_q, const void* in_counts, void* hits, float* slot_L, const uint32_t* film_n, uint32_t rays)
 {
-    if ((rays && !primary) || rays > kFeedLensOrthoMasked) return hipErrorInvalidValue;
     unsigned blocks = (ps.nchunks + kWavesPerBlock - 1) / kWavesPerBlock;
     const unsigned cap = (unsigned)num_cus * 4u;
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
-    dim3 grid(blocks), block(kBlock);
-    if (rays == kFeedLensThinMasked) hipLaunchKernelGGL((trace_octree_kernel<true, kFeedLensThinMasked>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
-    else if (rays == kFeedLensOrthoMasked) hipLaunchKernelGGL((trace_octree_kernel<true, kFeedLensOrthoMasked>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
-    else if (rays == kFeedLensThin) hipLaunchKernelGGL((trace_octree_kernel<true, kFeedLensThin>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
-    else if (rays == kFeedLensOrtho) hipLaunchKernelGGL((trace_octree_kernel<true, kFeedLensOrtho>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
-    else if (rays) hipLaunchKernelGGL((trace_octree_kernel<true, kFeedRays>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
-    else if (primary) hipLaunchKernelGGL((trace_octree_kernel<true>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
-    else hipLaunchKernelGGL((trace_octree_kernel<false>), grid, block, 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
-    return hipGetLastError();
+    return select_trace_octree(primary, rays, [&](auto P, auto R) {
+        hipLaunchKernelGGL((trace_octree_kernel<P(), R()>), dim3(blocks), dim3(kBlock), 0, stream, sc, cam, ps, (const float4*)in_q, (const uint2*)in_counts, (float4*)hits, slot_L, film_n);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_shade(hipStream_t stream, int num_cus, bool primary, bool walk, const DScene& sc, const DCamera& cam, const DPass& ps, uint32_t level,
                         const void* in_q, const void* in_counts, const void* hits, void* out_q, void* out_counts, uint32_t* cursor,
                         float* slot_L, uint32_t* sample_slot, const uint32_t* film_n, DCounters* counters, bool raster, uint32_t rays)
 {
-    if ((rays && (!primary || raster)) || rays > kFeedLensOrthoMasked) return hipErrorInvalidValue;      // a ray-fed or lens primary round walks the tree: no pinhole camera, no tile bins
     // raster (primary round only): the kernel finds the primary rays' closest hits itself, through the tile bins (cam.tile_ofs), and keeps them in LDS
     const size_t lds = (size_t)ps.list_cap * kWavesPerBlock * sizeof(uint32_t) + (raster ? (size_t)ps.chunk * kWavesPerBlock * sizeof(float4) : 0);
     unsigned blocks = (ps.nchunks + kWavesPerBlock - 1) / kWavesPerBlock;
     const unsigned cap = (unsigned)num_cus * (primary ? (walk ? kShadePWBlocks : kShadePBlocks) : (walk ? kShadeSWBlocks : kShadeSBlocks));    // what the chip holds at once
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
-    dim3 grid(blocks), block(kBlock);
-#define MI355RT_SHADE_ARGS grid, block, lds, stream, sc, cam, ps, level, (const float4*)in_q, (const uint2*)in_counts, (const float4*)hits, (float4*)out_q, (uint2*)out_counts, cursor, slot_L, sample_slot, film_n, counters
-    if (rays == kFeedLensThinMasked && walk) hipLaunchKernelGGL((shade_kernel<true, true, false, kFeedLensThinMasked>), MI355RT_SHADE_ARGS);
-    else if (rays == kFeedLensThinMasked) hipLaunchKernelGGL((shade_kernel<true, false, false, kFeedLensThinMasked>), MI355RT_SHADE_ARGS);
-    else if (rays == kFeedLensOrthoMasked && walk) hipLaunchKernelGGL((shade_kernel<true, true, false, kFeedLensOrthoMasked>), MI355RT_SHADE_ARGS);
-    else if (rays == kFeedLensOrthoMasked) hipLaunchKernelGGL((shade_kernel<true, false, false, kFeedLensOrthoMasked>), MI355RT_SHADE_ARGS);
-    else if (rays == kFeedLensThin && walk) hipLaunchKernelGGL((shade_kernel<true, true, false, kFeedLensThin>), MI355RT_SHADE_ARGS);
-    else if (rays == kFeedLensThin) hipLaunchKernelGGL((shade_kernel<true, false, false, kFeedLensThin>), MI355RT_SHADE_ARGS);
-    else if (rays == kFeedLensOrtho && walk) hipLaunchKernelGGL((shade_kernel<true, true, false, kFeedLensOrtho>), MI355RT_SHADE_ARGS);
-    else if (rays == kFeedLensOrtho) hipLaunchKernelGGL((shade_kernel<true, false, false, kFeedLensOrtho>), MI355RT_SHADE_ARGS);
-    else if (rays && walk) hipLaunchKernelGGL((shade_kernel<true, true, false, kFeedRays>), MI355RT_SHADE_ARGS);
-    else if (rays) hipLaunchKernelGGL((shade_kernel<true, false, false, kFeedRays>), MI355RT_SHADE_ARGS);
-    else if (primary && raster && walk) hipLaunchKernelGGL((shade_kernel<true, true, true>), MI355RT_SHADE_ARGS);
-    else if (primary && raster) hipLaunchKernelGGL((shade_kernel<true, false, true>), MI355RT_SHADE_ARGS);
-    else if (primary && walk) hipLaunchKernelGGL((shade_kernel<true, true>), MI355RT_SHADE_ARGS);
-    else if (primary) hipLaunchKernelGGL((shade_kernel<true, false>), MI355RT_SHADE_ARGS);
-    else if (walk) hipLaunchKernelGGL((shade_kernel<false, true>), MI355RT_SHADE_ARGS);
-    else hipLaunchKernelGGL((shade_kernel<false, false>), MI355RT_SHADE_ARGS);
-#undef MI355RT_SHADE_ARGS
-    return hipGetLastError();
+    return select_shade(primary, walk, raster, rays, [&](auto P, auto W, auto T, auto R) {
+        hipLaunchKernelGGL((shade_kernel<P(), W(), T(), R()>), dim3(blocks), dim3(kBlock), lds, stream, sc, cam, ps, level, (const float4*)in_q, (const uint2*)in_counts, (const float4*)hits,
+                           (float4*)out_q, (uint2*)out_counts, cursor, slot_L, sample_slot, film_n, counters);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_resolve(hipStream_t stream, const DPass& ps, uint32_t width, uint32_t nlights, const float* slot_L, const uint32_t* sample_slot,
@@ -2470,28 +2435,14 @@ hipError_t launch_resolve(hipStream_t stream, const DPass& ps, uint32_t width, u
     const uint32_t spp = ps.npix ? ps.nsamples / ps.npix : 1u;
     const uint32_t lanes = spp <= 32u ? 2u : (spp <= 96u ? 4u : 8u);       // lanes per pixel: resolve_kernel's header
     dim3 block(256), grid((unsigned)(((size_t)ps.npix * lanes + 255) / 256));
-#define MI355RT_RESOLVE_ARGS grid, block, 0, stream, ps, width, nlights, slot_L, sample_slot, film_sum, film_sumsq, film_n, debug_color, ctrl, film_direct, film_lights, lights_stride
-#define MI355RT_RESOLVE_LANES(DIRECT, FLAT, LIGHTS) switch (lanes) { \
-        case 2: hipLaunchKernelGGL((resolve_kernel<2, kResolveU, DIRECT, FLAT, LIGHTS>), MI355RT_RESOLVE_ARGS); break; \
-        case 4: hipLaunchKernelGGL((resolve_kernel<4, kResolveU, DIRECT, FLAT, LIGHTS>), MI355RT_RESOLVE_ARGS); break; \
-        default: hipLaunchKernelGGL((resolve_kernel<8, kResolveU, DIRECT, FLAT, LIGHTS>), MI355RT_RESOLVE_ARGS); break; }
     const bool direct = film_direct != nullptr && !ps.use_explicit;           // a debug_sample pass adds to no film: the plain variant
     const bool flat = ps.nodes_per_sample <= kFlatNodes;                      // flat_radiance
     const bool lights = film_lights != nullptr && nlights != 0u && !ps.use_explicit;     // the light films (MI355RT_FLAG_LIGHT_FILMS): variants of their own
-    if (lights && nlights > kMaxLightFilms) return hipErrorInvalidValue;                 // Renderer::init refuses such a scene with the flag
-    if (lights) {
-        if (direct && flat) MI355RT_RESOLVE_LANES(true, true, true)
-        else if (direct) MI355RT_RESOLVE_LANES(true, false, true)
-        else if (flat) MI355RT_RESOLVE_LANES(false, true, true)
-        else MI355RT_RESOLVE_LANES(false, false, true)
-    }
-    else if (direct && flat) MI355RT_RESOLVE_LANES(true, true, false)
-    else if (direct) MI355RT_RESOLVE_LANES(true, false, false)
-    else if (flat) MI355RT_RESOLVE_LANES(false, true, false)
-    else MI355RT_RESOLVE_LANES(false, false, false)
-#undef MI355RT_RESOLVE_LANES
-#undef MI355RT_RESOLVE_ARGS
-    return hipGetLastError();
+    return select_resolve(lanes, direct, flat, lights ? nlights : 0u, [&](auto N, auto D, auto FL, auto L) {
+        hipLaunchKernelGGL((resolve_kernel<N(), kResolveU, D(), FL(), L()>), grid, block, 0, stream, ps, width, nlights, slot_L, sample_slot, film_sum, film_sumsq, film_n, debug_color, ctrl,
+                           film_direct, film_lights, lights_stride);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_tonemap(hipStream_t stream, const uint32_t* rows, uint32_t row_base, uint32_t nrows, uint32_t width, bool packed,
@@ -2621,11 +2572,11 @@ hipError_t launch_film_merge(hipStream_t stream, bool add, const float* in_sum, 
     if ((film_direct == nullptr) != (in_direct == nullptr) || width == 0 || stripe_rows == 0 || (uint64_t)npix * 3 > 0xFFFFFF00ull) return hipErrorInvalidValue;
     if (stripe_world <= 1) { stripe_world = 1; stripe_rank = 0; }
     const dim3 grid((3u * npix + 255u) / 256u);
-#define MI355RT_MERGE_ARGS grid, dim3(256), 0, stream, in_sum, in_sumsq, in_n, in_direct, npix, width, stripe_rows, stripe_world, stripe_rank, film_sum, film_sumsq, film_n, film_direct
-    if (add) { if (film_direct) hipLaunchKernelGGL((film_merge_kernel<true, true>), MI355RT_MERGE_ARGS); else hipLaunchKernelGGL((film_merge_kernel<true, false>), MI355RT_MERGE_ARGS); }
-    else { if (film_direct) hipLaunchKernelGGL((film_merge_kernel<false, true>), MI355RT_MERGE_ARGS); else hipLaunchKernelGGL((film_merge_kernel<false, false>), MI355RT_MERGE_ARGS); }
-#undef MI355RT_MERGE_ARGS
-    return hipGetLastError();
+    return with_bool(add, [&](auto A) { return with_bool(film_direct != nullptr, [&](auto D) {
+        hipLaunchKernelGGL((film_merge_kernel<A(), D()>), grid, dim3(256), 0, stream, in_sum, in_sumsq, in_n, in_direct, npix, width, stripe_rows, stripe_world, stripe_rank,
+                           film_sum, film_sumsq, film_n, film_direct);
+        return hipGetLastError();
+    }); });
 }
 
 // ---- light films (MI355RT_FLAG_LIGHT_FILMS): the planes' own clear, set / add and the relit read-out ----
@@ -2666,9 +2617,10 @@ hipError_t launch_light_films_merge(hipStream_t stream, bool add, const float* i
     if (width == 0 || stripe_rows == 0 || (uint64_t)npix * 3 > 0xFFFFFF00ull || lights_stride != 3u * npix || nlights > 65535u) return hipErrorInvalidValue;
     if (stripe_world <= 1) { stripe_world = 1; stripe_rank = 0; }
     const dim3 grid((3u * npix + 255u) / 256u, nlights);
-    if (add) hipLaunchKernelGGL(light_films_merge_kernel<true>, grid, dim3(256), 0, stream, in, npix, width, stripe_rows, stripe_world, stripe_rank, film_lights, lights_stride);
-    else hipLaunchKernelGGL(light_films_merge_kernel<false>, grid, dim3(256), 0, stream, in, npix, width, stripe_rows, stripe_world, stripe_rank, film_lights, lights_stride);
-    return hipGetLastError();
+    return with_bool(add, [&](auto A) {
+        hipLaunchKernelGGL(light_films_merge_kernel<A()>, grid, dim3(256), 0, stream, in, npix, width, stripe_rows, stripe_world, stripe_rank, film_lights, lights_stride);
+        return hipGetLastError();
+    });
 }
 
 // mi355rt_get_relit_pixels: one lane per pixel, c[ch] = sum over the lights, ascending, of weight[li][ch] * (light[li][p][ch] * (1 / n)), f32 and unfused as
@@ -2737,13 +2689,11 @@ hipError_t launch_fused_pass(hipStream_t stream, int num_cus, bool confirm, cons
     unsigned blocks = (ps.nchunks + kWavesPerBlock - 1) / kWavesPerBlock;
     const unsigned cap = (unsigned)num_cus * 8u;
     if (blocks > cap) blocks = cap;
-#define MI355RT_FUSED_ARGS dim3(blocks), dim3(kBlock), lds, stream, sc, cam, ps, (float4*)q0, (float4*)q1, (float4*)hits, slot_L, sample_slot, film_sum, film_sumsq, film_n, film_direct, counters
-    if (film_direct && confirm) hipLaunchKernelGGL((fused_pass_kernel<true, true>), MI355RT_FUSED_ARGS);
-    else if (film_direct) hipLaunchKernelGGL((fused_pass_kernel<false, true>), MI355RT_FUSED_ARGS);
-    else if (confirm) hipLaunchKernelGGL((fused_pass_kernel<true, false>), MI355RT_FUSED_ARGS);
-    else hipLaunchKernelGGL((fused_pass_kernel<false, false>), MI355RT_FUSED_ARGS);
-#undef MI355RT_FUSED_ARGS
-    return hipGetLastError();
+    return with_bool(confirm, [&](auto C) { return with_bool(film_direct != nullptr, [&](auto D) {
+        hipLaunchKernelGGL((fused_pass_kernel<C(), D()>), dim3(blocks), dim3(kBlock), lds, stream, sc, cam, ps, (float4*)q0, (float4*)q1, (float4*)hits, slot_L, sample_slot,
+                           film_sum, film_sumsq, film_n, film_direct, counters);
+        return hipGetLastError();
+    }); });
 }
 
 // the octree confirm step of one round (reference-default semantics), between its trace and its shade launch

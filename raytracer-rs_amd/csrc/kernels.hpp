@@ -8,15 +8,15 @@ namespace mi355rt {
 
 hipError_t launch_trace(hipStream_t stream, int num_cus, bool primary, bool count, bool confirm, const DScene& sc, const DCamera& cam, const DPass& ps,
                         const void* in_q, const void* in_counts, void* hits, uint32_t* cursor,
-                        float* slot_L, const uint32_t* film_n, DCounters* counters, uint32_t rays = 0);   // rays: the feed of the primary round — 0 the pinhole camera, 1 a ray-fed pass (DPass::ray_in), 2 / 3 the handle's THIN / ORTHO lens (DCamera::lens), 4 / 5 the same with a tile mask (DPass::tile_active)
+                        float* slot_L, const uint32_t* film_n, DCounters* counters, uint32_t rays = kFeedCamera);   // rays: the feed of the primary round, a kFeed* of device_types.hpp
 // culling verdicts of the pass's pixel blocks (DPass::block_culled): out[b] = chunk b (first sample group) is culled
 hipError_t launch_cull_blocks(hipStream_t stream, const DCamera& cam, const DPass& ps, uint32_t nblocks, uint32_t* out);
 hipError_t launch_trace_octree(hipStream_t stream, int num_cus, bool primary, const DScene& sc, const DCamera& cam, const DPass& ps,
-                               const void* in_q, const void* in_counts, void* hits, float* slot_L, const uint32_t* film_n, uint32_t rays = 0);
+                               const void* in_q, const void* in_counts, void* hits, float* slot_L, const uint32_t* film_n, uint32_t rays = kFeedCamera);
 hipError_t launch_shade(hipStream_t stream, int num_cus, bool primary, bool walk, const DScene& sc, const DCamera& cam, const DPass& ps, uint32_t level,
                         const void* in_q, const void* in_counts, const void* hits, void* out_q, void* out_counts, uint32_t* cursor,
                         float* slot_L, uint32_t* sample_slot, const uint32_t* film_n, DCounters* counters, bool raster = false,   // raster: primary round, hits through the tile bins inside the launch
-                        uint32_t rays = 0);                                                                                        // rays: as launch_trace
+                        uint32_t rays = kFeedCamera);                                                                              // rays: as launch_trace
 hipError_t launch_resolve(hipStream_t stream, const DPass& ps, uint32_t width, uint32_t nlights, const float* slot_L, const uint32_t* sample_slot,
                           float* film_sum, float* film_sumsq, uint32_t* film_n, float* film_direct, float* debug_color, uint32_t* ctrl,    // ctrl != null: zero the pass's work cursors on the way out
                           float* film_lights = nullptr, uint32_t lights_stride = 0);   // film_lights: the light films (below), null without MI355RT_FLAG_LIGHT_FILMS: the kernels without them

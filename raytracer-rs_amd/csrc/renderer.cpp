@@ -745,11 +745,10 @@ bool Renderer::assign_slice_rows(uint32_t nslices)
 
 // One wavefront pass: `nrows` rows starting at d_rows[row0], spp samples per pixel.
 // Fill the pass descriptor shared by the wavefront kernels and the fused kernel.
-void Renderer::describe_pass(DPass& ps, const Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t row_wrap, uint32_t npix, size_t nsamples, uint32_t chunk,
-                             bool explicit_sample, uint32_t epixel, uint32_t esample) const
+void Renderer::describe_pass(DPass& ps, const Slice& sl, const PassRequest& rq, uint32_t npix, size_t nsamples, uint32_t chunk) const
 {
     ps = DPass{};
-    ps.rows = d_rows; ps.row0 = row0; ps.row_wrap = row_wrap; ps.npix = npix; ps.nsamples = (uint32_t)nsamples;
+    ps.rows = rq.d_rows; ps.row0 = rq.row0; ps.row_wrap = rq.row_wrap; ps.npix = npix; ps.nsamples = (uint32_t)nsamples;
     ps.spp = npix ? (uint32_t)(nsamples / npix) : 1u;
     // samples of a pixel kept together in the pass order (kernels.hip, sample_of): 2 — thai2 frame 21.1 / 20.7 / 20.7 / 20.9 / 21.5 / 21.6 ms at
     // 1 / 2 / 4 / 8 / 16 / 64, one rank's share of eight 3.27 / 3.24 / 3.30 / 3.34 / 3.40 / 3.63 ms (profiles/r03_notes.md); the largest divisor of spp <= the wish.
@@ -765,13 +764,13 @@ void Renderer::describe_pass(DPass& ps, const Slice& sl, const uint32_t* d_rows,
     ps.row_group_shift = 3; while (ps.row_group_shift > 0 && (1u << ps.row_group_shift) > cfg.stripe_rows) --ps.row_group_shift;
     // ... and of a height that divides the pass's rows when there is one (1050 rows: groups of 2, not 4 with a ragged last group): whole groups everywhere is what
     // the tile bins of the primary rays need, and costs nothing
-    if (!explicit_sample && cfg.width) { const uint32_t prow = npix / cfg.width; while (ps.row_group_shift > 0 && prow % (1u << ps.row_group_shift)) --ps.row_group_shift; }
+    if (!rq.explicit_sample && cfg.width) { const uint32_t prow = npix / cfg.width; while (ps.row_group_shift > 0 && prow % (1u << ps.row_group_shift)) --ps.row_group_shift; }
     ps.row_group = 1u << ps.row_group_shift;
     ps.seed = (uint32_t)cfg.seed; ps.flags = cfg.flags; ps.recursions = cfg.recursions; ps.spread = cfg.spread;
     ps.nodes_per_sample = nodes_per_sample;
     ps.nslots = (uint32_t)((nsamples + chunk - 1) / chunk) * chunk;
     std::memcpy(ps.level_first, level_first, sizeof ps.level_first);
-    ps.use_explicit = explicit_sample ? 1u : 0u; ps.explicit_pixel = epixel; ps.explicit_sampleno = esample;
+    ps.use_explicit = rq.explicit_sample ? 1u : 0u; ps.explicit_pixel = rq.epixel; ps.explicit_sampleno = rq.esample;
     ps.chunk = chunk; ps.nchunks = (uint32_t)((nsamples + chunk - 1) / chunk); ps.region = chunk * records_per_sample_;
     ps.hit_prim = sl.d_hit_prim.get(); ps.qstride = sl.queue_records; ps.slot_ps = (uint2*)sl.d_slot_ps.get();
     ps.stack_depth = traversal_rows(); ps.list_cap = chunk * max_level_nodes_;
@@ -779,57 +778,99 @@ void Renderer::describe_pass(DPass& ps, const Slice& sl, const uint32_t* d_rows,
     // Not with the direct octree walk: its trace launch strides over ALL chunks, and the ray counts of the chunks the shade launches no longer visit
     // are whatever an earlier pass left there.
     ps.live = nullptr; ps.live_count = nullptr; ps.live_cap = 0;
-    if (chunk == kChunk && sl.d_live && !explicit_sample && mode_ != kModeOctreeWalk) {
+    if (chunk == kChunk && sl.d_live && !rq.explicit_sample && mode_ != kModeOctreeWalk) {
         ps.live = sl.d_live.get(); ps.live_count = sl.d_ctrl.get(); ps.live_cap = (ps.nchunks + kMaxCursors - 1u) / kMaxCursors;
     }
 }
 
+// MI355RT_DEBUG_UTIL: load-balance diagnostics of one trace launch of a counting handle (debug only: synchronises).  Before the launch ...
+bool Renderer::balance_debug_reset()
+{
+    DCounters init{};
+    HIP_TRY(hipMemcpy(&init, d_counters_.get(), sizeof init, hipMemcpyDeviceToHost));
+    init.t_first_end = ~0ull; init.t_start = ~0ull; init.t_last_end = 0; init.t_sum_end = 0; init.n_waves = 0;
+    HIP_TRY(hipMemcpy(d_counters_.get(), &init, sizeof init, hipMemcpyHostToDevice));
+    return true;
+}
+// ... and after it (and the round's confirm launch)
+bool Renderer::balance_debug_report(hipStream_t st, uint32_t r)
+{
+    DCounters c0{};
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(&c0, d_counters_.get(), sizeof c0, hipMemcpyDeviceToHost));
+    {   // lane census of the launch (summed over the counter shards; cumulative over the call's launches: print differences)
+        DCounters sh[kShards], t{};
+        HIP_TRY(hipMemcpy(sh, d_counters_.get(), sizeof sh, hipMemcpyDeviceToHost));
+        for (const DCounters& x : sh) { t.lanes_inner += x.lanes_inner; t.lanes_leaf += x.lanes_leaf; t.lanes_done += x.lanes_done; t.lane_samples += x.lane_samples;
+                                        t.refills += x.refills; t.refill_passes += x.refill_passes; t.refill_rays += x.refill_rays; t.inner_execs += x.inner_execs; t.leaf_execs += x.leaf_execs; }
+        static DCounters prev{};
+        if (t.lane_samples < prev.lane_samples) prev = DCounters{};
+        const double it = (double)(t.lane_samples - prev.lane_samples);
+        if (it > 0)
+            fprintf(stderr, "[mi355rt] trace round %u census: iterations %.0f, lanes at inner %.1f / at leaf %.1f / idle-or-finished %.1f per iteration; inner execs %.2f, leaf execs %.2f per iteration; refills %llu, passes %llu, rays per refill %.1f\n",
+                    r, it, (t.lanes_inner - prev.lanes_inner) / it, (t.lanes_leaf - prev.lanes_leaf) / it, (t.lanes_done - prev.lanes_done) / it,
+                    (t.inner_execs - prev.inner_execs) / it, (t.leaf_execs - prev.leaf_execs) / it,
+                    t.refills - prev.refills, t.refill_passes - prev.refill_passes, (double)(t.refill_rays - prev.refill_rays) / std::max<double>(1.0, (double)(t.refills - prev.refills)));
+        prev = t;
+    }
+    if (c0.n_waves)
+        fprintf(stderr, "[mi355rt] trace round %u: %llu waves, mean wave busy %.1f us, first wave out of work at %.1f us, last at %.1f us\n", r, c0.n_waves,
+                (double)c0.t_sum_end / c0.n_waves / 100.0, (double)(c0.t_first_end - c0.t_start) / 100.0, (double)(c0.t_last_end - c0.t_start) / 100.0);
+    return true;
+}
+
+// Culling verdicts per pixel block, computed once per camera and layout (DPass::block_culled) instead of per launch and chunk
+// (needs chunks that hold whole pixels — the sample group divides the chunk — and sample groups that are whole numbers of chunks: then every sample of a pixel
+// lies in chunks of ONE block)
+bool Renderer::cached_cull_verdicts(Slice& sl, const DCamera& cam, DPass& ps, uint32_t nrows)
+{
+    ps.block_culled = nullptr; ps.cull_blocks = 0;
+    if (cam.cull_valid == 0 || mode_ == kModeOctreeWalk || ps.chunk % ps.sample_group != 0 || ((size_t)ps.npix * ps.sample_group) % ps.chunk != 0 || getenv("MI355RT_NO_CULL_CACHE")) return true;
+    const size_t nblocks = (size_t)ps.npix * ps.sample_group / ps.chunk;
+    std::vector<float> key(cam.rot, cam.rot + 16);
+    key.insert(key.end(), cam.origin, cam.origin + 3); key.push_back(cam.max_x); key.push_back(cam.max_y);
+    key.push_back((float)nrows); key.push_back((float)ps.chunk); key.push_back((float)ps.sample_group); key.push_back((float)ps.row_group);
+    key.push_back((float)(ps.flags & 1u)); key.push_back(cam.cull_mask ? 1.0f : 0.0f); key.push_back((float)nblocks);
+    if (nblocks * 4 > sl.d_block_culled.bytes()) {
+        HIP_TRY(hipStreamSynchronize(sl.stream));
+        if (sl.d_block_culled.alloc(nblocks * 4, &hbm_bytes_) != hipSuccess) (void)hipGetLastError();
+        sl.cull_key.clear();
+    }
+    if (sl.d_block_culled) {
+        if (key != sl.cull_key) {          // stream-ordered behind the launches that read the old verdicts
+            HIP_TRY(launch_cull_blocks(sl.stream, cam, ps, (uint32_t)nblocks, sl.d_block_culled.get()));
+            sl.cull_key = key;
+        }
+        ps.block_culled = sl.d_block_culled.get(); ps.cull_blocks = (uint32_t)nblocks;
+    }
+    return true;
+}
+
 // A wavefront pass: buffers, descriptor and cursors; then round by round trace (+ confirm) (+ shade); then resolve.  Every launch goes
 // to the slice's stream.
-bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t nrows, uint32_t spp, bool explicit_sample, uint32_t epixel, uint32_t esample, uint32_t row_wrap,
-                        const uint8_t* tile_active, const RayFeed* feed)
+bool Renderer::run_pass(Slice& sl, const PassRequest& rq)
 {
-    const bool free_rays = feed != nullptr && feed->mode == 2u;       // mi355rt_trace_rays: the pass's samples are `count` rays, not pixels
-    const uint32_t npix = explicit_sample ? 1u : free_rays ? feed->count : nrows * cfg.width;
-    const size_t nsamples = (size_t)npix * spp;
+    const RayFeed* feed = rq.feed;
+    const bool free_rays = feed != nullptr && feed->mode == kRaysFree;       // mi355rt_trace_rays: the pass's samples are `count` rays, not pixels
+    const uint32_t npix = rq.explicit_sample ? 1u : free_rays ? feed->count : rq.nrows * cfg.width;
+    const size_t nsamples = (size_t)npix * rq.spp;
     if (nsamples == 0) return true;
     if (!ensure_pass_capacity(sl, nsamples)) return false;
     DPass ps;
-    describe_pass(ps, sl, d_rows, row0, row_wrap, npix, nsamples, kChunk, explicit_sample, epixel, esample);
-    ps.tile_active = tile_active; ps.tiles_x = tiles_x();
+    describe_pass(ps, sl, rq, npix, nsamples, kChunk);
+    ps.tile_active = rq.tile_active; ps.tiles_x = tiles_x();
     // the tile bins of the primary rays need a pass that walks the slice's whole row list (render(); not the odd row windows of the other callers)
     // (nor a ray-fed or a lens pass: its primary rays are not the pinhole camera's, so nothing that is derived from the camera — bins, culling rectangles, cached verdicts — holds)
-    const bool whole = !feed && !explicit_sample && d_rows == sl.d_rows.get() && row0 == 0 && nrows == sl.rows.size() && row_wrap == 0xFFFFFFFFu;
+    const bool whole = !feed && !rq.explicit_sample && rq.d_rows == sl.d_rows.get() && rq.row0 == 0 && rq.nrows == sl.rows.size() && rq.row_wrap == kNoRowWrap;
     DCamera cam = device_camera(whole ? &ps : nullptr, whole ? &sl.rows : nullptr);
-    // the feed of the primary round (kernels.hpp, launch_trace); a lens pass with a tile mask has instantiations of its own
-    const uint32_t rays = feed == nullptr ? 0u : feed->mode != 3u ? 1u : (lens_.model == MI355RT_LENS_THIN ? 2u : 3u) + (tile_active != nullptr ? 2u : 0u);
-    if (rays) { cam.cull_valid = 0; cam.cull_mask = nullptr; cam.tile_ofs = nullptr; cam.tile_entries = nullptr; }
-    if (rays == 1u) {
+    // the feed of the primary round (device_types.hpp); a lens pass with a tile mask has instantiations of its own
+    static_assert(kLensPinhole == MI355RT_LENS_PINHOLE && kLensThin == MI355RT_LENS_THIN && kLensOrtho == MI355RT_LENS_ORTHO, "lens_feed takes mi355rt_lens::model");
+    const uint32_t rays = feed == nullptr ? kFeedCamera : feed->mode != kRaysOfLens ? kFeedRays : lens_feed(lens_.model, rq.tile_active != nullptr);
+    if (rays != kFeedCamera) { cam.cull_valid = 0; cam.cull_mask = nullptr; cam.tile_ofs = nullptr; cam.tile_entries = nullptr; }
+    if (rays == kFeedRays) {
         ps.ray_in = feed->rays; ps.ray_keys = feed->keys; ps.ray_hit = feed->hit; ps.ray_mode = feed->mode; ps.ray_base = feed->base; ps.ray_npix = cfg.width * cfg.height;
     }
-    // culling verdicts per pixel block, computed once per camera and layout (DPass::block_culled) instead of per launch and chunk
-    ps.block_culled = nullptr; ps.cull_blocks = 0;
-    // (needs chunks that hold whole pixels — the sample group divides the chunk — and sample groups that are whole numbers of chunks: then every sample of a pixel
-    // lies in chunks of ONE block)
-    if (whole && cam.cull_valid != 0 && mode_ != kModeOctreeWalk && ps.chunk % ps.sample_group == 0 && ((size_t)ps.npix * ps.sample_group) % ps.chunk == 0 && !getenv("MI355RT_NO_CULL_CACHE")) {
-        const size_t nblocks = (size_t)ps.npix * ps.sample_group / ps.chunk;
-        std::vector<float> key(cam.rot, cam.rot + 16);
-        key.insert(key.end(), cam.origin, cam.origin + 3); key.push_back(cam.max_x); key.push_back(cam.max_y);
-        key.push_back((float)nrows); key.push_back((float)ps.chunk); key.push_back((float)ps.sample_group); key.push_back((float)ps.row_group);
-        key.push_back((float)(ps.flags & 1u)); key.push_back(cam.cull_mask ? 1.0f : 0.0f); key.push_back((float)nblocks);
-        if (nblocks * 4 > sl.d_block_culled.bytes()) {
-            HIP_TRY(hipStreamSynchronize(sl.stream));
-            if (sl.d_block_culled.alloc(nblocks * 4, &hbm_bytes_) != hipSuccess) (void)hipGetLastError();
-            sl.cull_key.clear();
-        }
-        if (sl.d_block_culled) {
-            if (key != sl.cull_key) {          // stream-ordered behind the launches that read the old verdicts
-                HIP_TRY(launch_cull_blocks(sl.stream, cam, ps, (uint32_t)nblocks, sl.d_block_culled.get()));
-                sl.cull_key = key;
-            }
-            ps.block_culled = sl.d_block_culled.get(); ps.cull_blocks = (uint32_t)nblocks;
-        }
-    }
+    if (whole && !cached_cull_verdicts(sl, cam, ps, rq.nrows)) return false;
     // the work cursors: zeroed at creation and again by the resolve kernel of every pass that ran to its end
     hipStream_t st = sl.stream;
     if (!sl.ctrl_clean) HIP_TRY(hipMemsetAsync(sl.d_ctrl.get(), 0, kMaxRounds * kCtrlWordsPerRound * 4, st));
@@ -855,47 +896,20 @@ bool Renderer::run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32
                 HIP_TRY(hipEventRecord(ev_pool_[ev_used_], st));
                 ev_secondary_.resize(ev_pool_.size() / 2); ev_secondary_[ev_used_ / 2] = r > 0;
             }
-            if (balance_dbg) {       // load-balance diagnostics of this launch (debug only: synchronises)
-                DCounters init{};
-                HIP_TRY(hipMemcpy(&init, d_counters_.get(), sizeof init, hipMemcpyDeviceToHost));
-                init.t_first_end = ~0ull; init.t_start = ~0ull; init.t_last_end = 0; init.t_sum_end = 0; init.n_waves = 0;
-                HIP_TRY(hipMemcpy(d_counters_.get(), &init, sizeof init, hipMemcpyHostToDevice));
-            }
+            if (balance_dbg && !balance_debug_reset()) return false;
             if (mode_ == kModeOctreeWalk)
-                HIP_TRY(launch_trace_octree(st, num_cus_, r == 0, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_slot_L.get(), d_film_n_.get(), r == 0 ? rays : 0u));
+                HIP_TRY(launch_trace_octree(st, num_cus_, r == 0, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_slot_L.get(), d_film_n_.get(), r == 0 ? rays : kFeedCamera));
             else
-                HIP_TRY(launch_trace(st, num_cus_, r == 0, count, mode_ == kModeConfirm, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound, sl.d_slot_L.get(), d_film_n_.get(), d_counters_.get(), r == 0 ? rays : 0u));
+                HIP_TRY(launch_trace(st, num_cus_, r == 0, count, mode_ == kModeConfirm, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound, sl.d_slot_L.get(), d_film_n_.get(), d_counters_.get(), r == 0 ? rays : kFeedCamera));
             if (timed) { HIP_TRY(hipEventRecord(ev_pool_[ev_used_ + 1], st)); ev_used_ += 2; }
             ++launches_;
         }
         const bool shade_walks = confirm_here && r <= cfg.recursions;
         if (confirm_here && r != 0)         // (the primary round's shade kernel confirms its hits, and there are no shadow rays yet)
             HIP_TRY(launch_confirm(st, num_cus_, false, shade_walks, dscene_, cam, ps, in_q, in_c, sl.d_hits.get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound + kConfirmCursorOffset, sl.d_slot_L.get(), d_film_n_.get()));
-        if (balance_dbg) {
-            DCounters c0{};
-            HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(hipMemcpy(&c0, d_counters_.get(), sizeof c0, hipMemcpyDeviceToHost));
-            {   // lane census of the launch (summed over the counter shards; cumulative over the call's launches: print differences)
-                DCounters sh[kShards], t{};
-                HIP_TRY(hipMemcpy(sh, d_counters_.get(), sizeof sh, hipMemcpyDeviceToHost));
-                for (const DCounters& x : sh) { t.lanes_inner += x.lanes_inner; t.lanes_leaf += x.lanes_leaf; t.lanes_done += x.lanes_done; t.lane_samples += x.lane_samples;
-                                                t.refills += x.refills; t.refill_passes += x.refill_passes; t.refill_rays += x.refill_rays; t.inner_execs += x.inner_execs; t.leaf_execs += x.leaf_execs; }
-                static DCounters prev{};
-                if (t.lane_samples < prev.lane_samples) prev = DCounters{};
-                const double it = (double)(t.lane_samples - prev.lane_samples);
-                if (it > 0)
-                    fprintf(stderr, "[mi355rt] trace round %u census: iterations %.0f, lanes at inner %.1f / at leaf %.1f / idle-or-finished %.1f per iteration; inner execs %.2f, leaf execs %.2f per iteration; refills %llu, passes %llu, rays per refill %.1f\n",
-                            r, it, (t.lanes_inner - prev.lanes_inner) / it, (t.lanes_leaf - prev.lanes_leaf) / it, (t.lanes_done - prev.lanes_done) / it,
-                            (t.inner_execs - prev.inner_execs) / it, (t.leaf_execs - prev.leaf_execs) / it,
-                            t.refills - prev.refills, t.refill_passes - prev.refill_passes, (double)(t.refill_rays - prev.refill_rays) / std::max<double>(1.0, (double)(t.refills - prev.refills)));
-                prev = t;
-            }
-            if (c0.n_waves)
-                fprintf(stderr, "[mi355rt] trace round %u: %llu waves, mean wave busy %.1f us, first wave out of work at %.1f us, last at %.1f us\n", r, c0.n_waves,
-                        (double)c0.t_sum_end / c0.n_waves / 100.0, (double)(c0.t_first_end - c0.t_start) / 100.0, (double)(c0.t_last_end - c0.t_start) / 100.0);
-        }
+        if (balance_dbg && !balance_debug_report(st, r)) return false;
         if (r <= cfg.recursions)
-            HIP_TRY(launch_shade(st, num_cus_, r == 0, shade_walks, dscene_, cam, ps, r, in_q, in_c, sl.d_hits.get(), sl.d_queue[r & 1].get(), sl.d_chunk_counts[r & 1].get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound + kShadeCursorOffset, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_n_.get(), d_counters_.get(), fuse_primary, r == 0 ? rays : 0u));
+            HIP_TRY(launch_shade(st, num_cus_, r == 0, shade_walks, dscene_, cam, ps, r, in_q, in_c, sl.d_hits.get(), sl.d_queue[r & 1].get(), sl.d_chunk_counts[r & 1].get(), sl.d_ctrl.get() + r * kCtrlWordsPerRound + kShadeCursorOffset, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_n_.get(), d_counters_.get(), fuse_primary, r == 0 ? rays : kFeedCamera));
     }
     if (free_rays) HIP_TRY(launch_resolve_rays(st, ps, nlights_, sl.d_slot_L.get(), sl.d_sample_slot.get(), feed->rgb, feed->direct, feed->tuv, feed->prim, sl.d_ctrl.get()));
     else HIP_TRY(launch_resolve(st, ps, cfg.width, nlights_, sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_film_direct_.get(), d_debug_color_.get(), sl.d_ctrl.get(),
@@ -1042,8 +1056,9 @@ uint32_t Renderer::trace_frame_additive()
     if (wavefront) {
         if (!begin_call()) return 0;
         for (uint32_t done = 0; done < win.total; done += nown) {
-            const uint32_t n = std::min(nown, win.total - done);
-            if (!run_pass(slices_[0], d_owned_rows_.get(), (win.first + done) % nown, n, 1, false, 0, 0, nown)) return 0;
+            PassRequest rq;
+            rq.d_rows = d_owned_rows_.get(); rq.row0 = (win.first + done) % nown; rq.nrows = std::min(nown, win.total - done); rq.row_wrap = nown;
+            if (!run_pass(slices_[0], rq)) return 0;
         }
         current_row = win.next_row;
         mark_dirty_window(win.first, win.total);
@@ -1125,7 +1140,9 @@ bool Renderer::launch_fused_window(uint32_t first, uint32_t total, const DCamera
     DPass ps;
     uint32_t fchunk = 32u;                                            // samples per wave (a 4x8 pixel tile): 64 / 32 / 16 measure 0.303 / 0.266 / 0.277 ms per launch
     if (const char* e = getenv("MI355RT_FUSED_CHUNK")) { int v = atoi(e); if (v == 16 || v == 32 || v == 64) fchunk = (uint32_t)v; }   // <= 64: the LDS lists hold one row per record of a sample; >= kMinChunk: the counts arrays
-    describe_pass(ps, sl, d_owned_rows_.get(), first, nown, (uint32_t)nsamples, nsamples, fchunk, false, 0, 0);
+    PassRequest rq;
+    rq.d_rows = d_owned_rows_.get(); rq.row0 = first; rq.nrows = total; rq.row_wrap = nown;
+    describe_pass(ps, sl, rq, (uint32_t)nsamples, nsamples, fchunk);
     if (ps.nchunks > sl.count_entries || (size_t)ps.nchunks * ps.region > sl.queue_records) { last_error = "internal: fused pass does not fit the pass buffers"; return false; }
     hipError_t e = launch_fused_pass(stream_, num_cus_, mode_ == kModeConfirm, dscene_, cam, ps, max_level_nodes_, records_per_sample_, sl.d_queue[0].get(), sl.d_queue[1].get(),
                                      sl.d_hits.get(), sl.d_slot_L.get(), sl.d_sample_slot.get(), d_film_sum_.get(), d_film_sumsq_.get(), d_film_n_.get(), d_film_direct_.get(), dcounters);
@@ -1148,7 +1165,7 @@ bool Renderer::render(uint32_t spp, bool wait)
     if (!begin_call()) return false;
     // a lens: the same passes, their primary round fed by the lens instantiations of the kernels — no buffer, nothing to stage, so it queues like any frame
     RayFeed f{};
-    f.mode = 3u;
+    f.mode = kRaysOfLens;
     if (!enqueue_frame(spp, ev_begin_, nullptr, has_lens() ? &f : nullptr)) return false;
     for (uint32_t r : owned_rows) ldr_dirty_[r] = 1;
     return end_call((uint64_t)owned_rows.size() * cfg.width * spp, wait);
@@ -1235,7 +1252,9 @@ bool Renderer::enqueue_frame(uint32_t spp, hipEvent_t fork, const uint8_t* tile_
                 const PassDesc& d = plan[s][p];
                 RayFeed f{};
                 if (feed) { f = *feed; f.base = d.s0; }
-                if (!run_pass(slices_[s], slices_[s].d_rows.get(), d.r0, d.nr, d.kk, false, 0, 0, 0xFFFFFFFFu, tile_active, feed ? &f : nullptr)) return false;
+                PassRequest rq;
+                rq.d_rows = slices_[s].d_rows.get(); rq.row0 = d.r0; rq.nrows = d.nr; rq.spp = d.kk; rq.tile_active = tile_active; rq.feed = feed ? &f : nullptr;
+                if (!run_pass(slices_[s], rq)) return false;
             }
             if (!any) break;
         }
@@ -1325,7 +1344,7 @@ bool Renderer::render_tiles(const uint8_t* mask, uint32_t spp, bool device)
     if (!begin_call()) return false;
     if (pixels) {
         RayFeed f{};
-        f.mode = 3u;
+        f.mode = kRaysOfLens;
         if (!enqueue_frame(spp, ev_begin_, d_mask, has_lens() ? &f : nullptr)) return false;
         for (uint32_t r : owned_rows) if (row_pixels[r / kAdaptiveTile]) ldr_dirty_[r] = 1;
     }
@@ -1636,16 +1655,18 @@ bool Renderer::trace_rays(const float* rays6, const uint32_t* keys2, size_t n, b
     for (size_t at = 0; at < n; at += per) {
         const size_t cnt = std::min(per, n - at);
         RayFeed f{};
-        f.mode = 2u; f.rays = d_rays + 6 * at; f.keys = d_keys ? d_keys + 2 * at : nullptr; f.base = (uint32_t)at; f.count = (uint32_t)cnt; f.hit = s_hit.get();
+        f.mode = kRaysFree; f.rays = d_rays + 6 * at; f.keys = d_keys ? d_keys + 2 * at : nullptr; f.base = (uint32_t)at; f.count = (uint32_t)cnt; f.hit = s_hit.get();
         f.rgb = d_rgb ? d_rgb + 3 * at : nullptr; f.direct = d_direct ? d_direct + 3 * at : nullptr; f.tuv = d_tuv ? d_tuv + 3 * at : nullptr; f.prim = d_prim ? d_prim + at : nullptr;
-        if (!run_pass(sl, nullptr, 0, 0, 1, false, 0, 0, 0xFFFFFFFFu, nullptr, &f)) return false;
+        PassRequest rq;
+        rq.feed = &f;
+        if (!run_pass(sl, rq)) return false;
     }
     HIP_TRY(st.download());
     return end_call(n, true);                                         // waits: the staging (and the caller's buffers) are free again
 }
 
 // The chunk loop mi355rt_gather and mi355rt_probes_gather share.  Rays per chunk: what a pass of trace_rays holds.  A chunk's rays, keys and validity bytes
-// are made by gather_rays_kernel, the chunk runs as ONE ray-fed pass (RayFeed mode 2, exactly a pass of trace_rays) when `traced`, and `reduce` folds its
+// are made by gather_rays_kernel, the chunk runs as ONE ray-fed pass (RayFeed kRaysFree, exactly a pass of trace_rays) when `traced`, and `reduce` folds its
 // results into the caller's outputs.  Everything is queued on one stream, the sample chunks of a point range in ascending sample order, so every point takes
 // its samples in order.  Waits before it returns: the chunk buffers go out of scope here.
 bool Renderer::gather_chunks(const float* d_points, const float* d_normals, const uint32_t* d_ids, size_t npoints, uint32_t spp, uint32_t first_sample, bool traced, bool want_rgb,
@@ -1671,9 +1692,11 @@ bool Renderer::gather_chunks(const float* d_points, const float* d_normals, cons
             HIP_TRY(launch_gather_rays(stream_, dscene_, (uint32_t)cfg.seed, d_points, d_normals, d_ids, (uint32_t)p0, cp, cs, first_sample + s0, c_rays.get(), c_keys.get(), c_valid.get()));
             if (traced) {
                 RayFeed f{};
-                f.mode = 2u; f.rays = c_rays.get(); f.keys = c_keys.get(); f.base = 0u; f.count = cp * cs; f.hit = c_hit.get();
+                f.mode = kRaysFree; f.rays = c_rays.get(); f.keys = c_keys.get(); f.base = 0u; f.count = cp * cs; f.hit = c_hit.get();
                 f.rgb = c_rgb.get(); f.tuv = c_tuv.get(); f.prim = c_prim.get();
-                if (!run_pass(sl, nullptr, 0, 0, 1, false, 0, 0, 0xFFFFFFFFu, nullptr, &f)) return false;
+                PassRequest rq;
+                rq.feed = &f;
+                if (!run_pass(sl, rq)) return false;
             }
             HIP_TRY(reduce(GatherChunk{ (uint32_t)p0, cp, s0, cs, c_rays.get(), c_valid.get(), c_rgb.get(), c_tuv.get(), c_prim.get() }));
         }
@@ -1778,7 +1801,7 @@ bool Renderer::probes_lookup_vis(const mi355rt_probe_grid& grid, const uint32_t*
 }
 
 // mi355rt_gather: the points as a film of their own.  Chunks of cp points x cs samples, sized by the pass capacity as trace_rays sizes its
-// passes: gather_rays_kernel makes the chunk's rays, keys and validity bytes, the chunk runs as ONE ray-fed pass (RayFeed mode 2, exactly a pass of trace_rays),
+// passes: gather_rays_kernel makes the chunk's rays, keys and validity bytes, the chunk runs as ONE ray-fed pass (RayFeed kRaysFree, exactly a pass of trace_rays),
 // gather_reduce_kernel folds its results into the points' outputs.  The sample chunks of a point range go in ascending sample order, on one stream, so every
 // point takes its samples in order.  `direct` is a launch_intersect in shadow mode between two kernels of its own.  Host memory is staged (the outputs go up
 // first when the call accumulates); every temporary is freed on return.
@@ -1877,7 +1900,7 @@ bool Renderer::render_rays(const float* rays6, uint32_t spp, bool device)
     HIP_TRY(st.error());
     HIP_TRY(hipEventRecord(slices_[0].done, stream_));                // the other slices fork behind the upload (slice 0 runs on the main stream; its `done` event is free here)
     RayFeed f{};
-    f.mode = 1u; f.rays = d_rays;
+    f.mode = kRaysOfPixels; f.rays = d_rays;
     caller_ray_film_ = true;
     if (!enqueue_frame(spp, slices_[0].done, nullptr, &f)) return false;
     for (uint32_t r : owned_rows) ldr_dirty_[r] = 1;
@@ -2261,7 +2284,9 @@ bool Renderer::debug_sample(uint32_t pixel, uint32_t sampleno, float* color3, fl
     call_done_valid_ = false;
     HIP_TRY(hipMemsetAsync(d_counters_.get(), 0, sizeof(DCounters) * kShards, stream_));
     ev_used_ = 0; counts_pending_ = false;
-    if (!run_pass(slices_[0], nullptr, 0, 1, 1, true, pixel, sampleno)) return false;
+    PassRequest rq;
+    rq.nrows = 1; rq.explicit_sample = true; rq.epixel = pixel; rq.esample = sampleno;
+    if (!run_pass(slices_[0], rq)) return false;
     HIP_TRY(hipStreamSynchronize(stream_));
     const uint32_t nl = std::max(nlights_, 1u);
     std::vector<float> raw((size_t)nodes_per_sample * nl * 3);

@@ -203,17 +203,27 @@ private:
     bool gather_chunks(const float* d_points, const float* d_normals, const uint32_t* d_ids, size_t npoints, uint32_t spp, uint32_t first_sample, bool traced, bool want_rgb,
                        bool want_hits, const std::function<hipError_t(const GatherChunk&)>& reduce);
     bool assign_slice_rows(uint32_t nslices);
-    // A ray-fed pass (DPass::ray_in ...).  mode 1: the film's pixels with the caller's rays (base: the call's sample number of the pass's first
-    // sample, set per pass by enqueue_frame); mode 2: `count` free rays, one sample each, resolved into the out pointers (device memory, the pass's part);
-    // mode 3: no buffer at all — the film's pixels with the rays of the handle's lens, made by the kernels (DCamera::lens)
+    // A ray-fed pass (DPass::ray_in ...).  mode (device_types.hpp) kRaysOfPixels: the film's pixels with the caller's rays (base: the call's sample
+    // number of the pass's first sample, set per pass by enqueue_frame); kRaysFree: `count` free rays, one sample each, resolved into the out pointers (device memory,
+    // the pass's part); kRaysOfLens: no buffer at all — the film's pixels with the rays of the handle's lens, made by the kernels (DCamera::lens)
     struct RayFeed { uint32_t mode; const float* rays; const uint32_t* keys; uint32_t base; uint32_t count; float4* hit; float* rgb; float* direct; float* tuv; uint32_t* prim; };
-    bool run_pass(Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t nrows, uint32_t spp, bool explicit_sample, uint32_t epixel, uint32_t esample, uint32_t row_wrap = 0xFFFFFFFFu,
-                  const uint8_t* tile_active = nullptr, const RayFeed* feed = nullptr);
+    // What run_pass is asked for: nrows rows of the list d_rows from entry row0 on (cyclic over row_wrap entries), spp samples per pixel
+    static constexpr uint32_t kNoRowWrap = 0xFFFFFFFFu;                // DPass::row_wrap: the row list is not cyclic
+    struct PassRequest {
+        const uint32_t* d_rows = nullptr; uint32_t row0 = 0, nrows = 0, spp = 1, row_wrap = kNoRowWrap;
+        const uint8_t* tile_active = nullptr;                           // DPass::tile_active
+        const RayFeed* feed = nullptr;                                  // null: the pinhole camera
+        bool explicit_sample = false; uint32_t epixel = 0, esample = 0; // debug_sample: the pass is this one sample
+    };
+    bool run_pass(Slice& sl, const PassRequest& rq);
+    bool cached_cull_verdicts(Slice& sl, const DCamera& cam, DPass& ps, uint32_t nrows);          // run_pass: DPass::block_culled for this camera and layout
+    bool balance_debug_reset();                                                                  // run_pass, MI355RT_DEBUG_UTIL: before a trace launch,
+    bool balance_debug_report(hipStream_t st, uint32_t round);                                   // and after it (synchronises)
     // the owned rows x spp as wavefront passes on the slices (pass planning, OOM halving), forked behind `fork` on the main stream; tile_active: DPass::tile_active;
-    // feed (mode 1): the frame's primary rays are the caller's
+    // feed (kRaysOfPixels): the frame's primary rays are the caller's
     bool enqueue_frame(uint32_t spp, hipEvent_t fork, const uint8_t* tile_active, const RayFeed* feed = nullptr);
     bool caller_ray_film_ = false;
-    mi355rt_lens lens_{ MI355RT_LENS_PINHOLE, 0.0f, 1.0f, 0.0f };    // the handle's lens; not PINHOLE: render() runs lens passes (RayFeed mode 3), the guides take its centre rays
+    mi355rt_lens lens_{ MI355RT_LENS_PINHOLE, 0.0f, 1.0f, 0.0f };    // the handle's lens; not PINHOLE: render() runs lens passes (RayFeed kRaysOfLens), the guides take its centre rays
     bool join_slices();                                                 // the main stream waits for the slices of the call in flight
     bool adaptive_verdict(const mi355rt_adaptive_config& ac, uint32_t& tiles, uint64_t& pixels);    // d_tile_active_ <- the verdict of the current film
     DeviceBuffer<uint8_t> d_tile_active_;                               // adaptive sampling: one byte per tile (DPass::tile_active); render_tiles: the device copy of a host mask
@@ -246,8 +256,7 @@ private:
     bool display_hist_queue(const float* img, bool film, mi355rt_luminance_histogram& out);                    // kernel + read-back, synchronous
     DeviceBuffer<uint32_t> d_disp_hist_, d_disp_packed_;
     DeviceBuffer<float> d_disp_table_;
-    void describe_pass(DPass& ps, const Slice& sl, const uint32_t* d_rows, uint32_t row0, uint32_t row_wrap, uint32_t npix, size_t nsamples, uint32_t chunk,
-                       bool explicit_sample, uint32_t epixel, uint32_t esample) const;
+    void describe_pass(DPass& ps, const Slice& sl, const PassRequest& rq, uint32_t npix, size_t nsamples, uint32_t chunk) const;
     bool begin_call();
     bool end_call(uint64_t primary, bool wait = true);
     bool fetch_counts(uint64_t primary, bool timed_call);
