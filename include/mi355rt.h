@@ -1102,6 +1102,91 @@ uint32_t mi355rt_height(const mi355rt_handle* h);
 uint32_t mi355rt_triangle_count(const mi355rt_handle* h);
 uint32_t mi355rt_current_row(const mi355rt_handle* h);
 
+/* ---- PROBE PLACEMENT: what a probe sees around itself, where it moves, the state it gets, and a lookup that knows the moves (no reference counterpart;
+ * DESIGN.md §3q).  A probe that stands inside or against geometry is moved a fraction of a cell into free space, and what cannot be saved is marked.  A moved
+ * probe is gathered with the existing entries at grid point + offset (one f32 addition per component).  raytracer-rs_amd/probes.py states all of it.
+ * Everything is f32, unfused, in the order written, with + - * / sqrt, comparisons and integer conversions only.
+ *
+ * SURVEY.  The samples, keys and rays are mi355rt_probes_gather's (sphere mode), but only their CLOSEST HITS are taken: the rays of a chunk are traced with the
+ * launch of mi355rt_intersect_rays, no bounce and no shadow ray is made, and mi355rt_last_counts reports npoints * spp primary rays and nothing else.
+ * A sample is a HIT when its prim is not MISS and its t is a positive finite number, otherwise a miss.  A hit is a BACK hit when
+ * (d.x * N.x + d.y * N.y) + d.z * N.z > 0, d the ray's direction as given and N the normal of the hit triangle (normalised cross(v1 - v0, v2 - v0), as the
+ * feature film has it), negated with MI355RT_SURVEY_FLIP; otherwise, and with a NaN dot, a FRONT hit.  Per point, in sample order, with D = max_distance:
+ *     n += 1
+ *     back hit:   back += 1;   t < near_back.dist:  near_back = (t, d)
+ *     front hit:  front += 1;  t < near_front.dist: near_front = (t, d);   dist = t < D ? t : D;   dist > far.dist: far = (dist, d)
+ *     miss:       dist = D;    dist > far.dist: far = (D, d)
+ * A record is four floats (dist, d.x, d.y, d.z) and is replaced on a strict comparison only: of samples at the same distance the first keeps it.  An empty
+ * near record is (+inf, 0, 0, 0), an empty far (-inf, 0, 0, 0).  n, back, front are npoints u32, near_back, near_front, far npoints x 4 f32.  accumulate != 0:
+ * the six arrays are read, continued and written back, so survey(3) followed by survey(5, first_sample 3, accumulate) is survey(8) bit for bit; otherwise they
+ * start empty.  Around the call mi355rt_probes_gather's rules hold.  Device arrays of records must be 16-byte aligned.
+ * ERRORS.  Those of mi355rt_probes_gather, and: out NULL or any of its six pointers NULL; unknown flag bits; max_distance not finite, not > 0 or > 1e12; with
+ * MI355RT_RAYS_DEVICE a record array that is not 16-byte aligned.  Nothing is written.
+ *
+ * PLACE.  Per probe, from its survey, its offset (relative to its grid point; offsets NULL: zero) and the config; share = (float)back / (float)n.
+ *     n == 0:                                                    no candidate                                                  MI355RT_PLACE_UNSAMPLED
+ *     share > back_share and near_back.dist < +inf:              len = near_back.dist + 0.5f * min_front;  c_a = o_a + nb.d_a * len      MI355RT_PLACE_THROUGH
+ *     else near_front.dist < +inf and near_front.dist < min_front:
+ *         dot = (nf.x * far.x + nf.y * far.y) + nf.z * far.z;  ln = sqrt((nf.x * nf.x + nf.y * nf.y) + nf.z * nf.z);  lf likewise of far's direction
+ *         dot <= (0.5f * ln) * lf:   m = far.dist < min_front ? far.dist : min_front;  c_a = o_a + (far.d_a * m) / lf                    MI355RT_PLACE_AWAY
+ *         otherwise:                 no candidate                                                                                      MI355RT_PLACE_STAY
+ *     else an offset component != 0:  lo = sqrt((o.x * o.x + o.y * o.y) + o.z * o.z);  room = near_front.dist - min_front
+ *         near_front.dist < +inf and room < lo:  c_a = o_a + ((-o_a) * room) / lo;   otherwise c = (0, 0, 0), the whole way                MI355RT_PLACE_BACK
+ *     else:                                                      no candidate                                                  MI355RT_PLACE_REST
+ * The candidate is accepted, and becomes the new offset, only if every component satisfies |c_a| < max_offset * spacing_a or c_a == 0, where an axis with one
+ * probe has spacing 0.  A component that is not finite fails both, so an overflow or a NaN on the way refuses the candidate.  A refused candidate leaves the
+ * offset as it was and sets MI355RT_PLACE_REFUSED in the verdict, which otherwise is the branch above.
+ * STATE of a probe: n == 0: MI355RT_PROBE_UNKNOWN; share > back_share: BURIED; !(near_front.dist < max_distance) (no front hit within reach, nothing there to
+ * light): IDLE; else ACTIVE.  max_distance is the survey's.  ACTIVE and IDLE probes are usable in a lookup.
+ * mi355rt_probes_place computes new_offsets (nprobes x 3 f32; may be `offsets` itself), verdict and state (nprobes u8 each) for the nprobes = counts product
+ * probes of the grid; any of the three may be NULL, not all.  It traces nothing; mi355rt_probes_lookup's rules hold around it.  back_share 0.25 and max_offset
+ * 0.45 are the published DDGI values; min_front has no default (a fifth of the smallest spacing is the usual choice).
+ * ERRORS.  MI355RT_E_INVALID, the argument named in mi355rt_last_error and nothing written, for: a device group; an unknown where; the grid errors of
+ * mi355rt_probes_lookup; survey NULL or any of its pointers NULL; cfg NULL; back_share not in [0, 1]; max_offset not finite or < 0; min_front not finite and
+ * > 0 (when new_offsets or verdict is asked for); max_distance out of SURVEY's range (when state is asked for); all three outputs NULL; a host `offsets` that
+ * holds a non-finite value; with MI355RT_RAYS_DEVICE a record array that is not 16-byte aligned (device offsets are not inspected: they are data).
+ *
+ * LOOKUP_PLACED is LOOKUP_VIS of PROBE VISIBILITY with offsets (nprobes x 3 f32): the probe position that enters v = p_b - position is
+ * (origin_a + (float)i_a * spacing_a) + offset_a.  The cell, the fractions and the trilinear factor still come from the grid.  offsets NULL is
+ * mi355rt_probes_lookup_vis on every bit; with flags 0 no position is made, the offsets are not read, and the call is mi355rt_probes_lookup on every bit.
+ * ERRORS.  Those of mi355rt_probes_lookup_vis, and a host `offsets` that holds a non-finite value.  Offsets in device memory are not inspected: they are used
+ * as data, and a non-finite one makes the weights of its probe what the arithmetic above makes of it.
+ *
+ * Host only, no handle, the same header the kernels compile (csrc/probe_place.hpp): mi355rt_probe_place_one (PLACE and STATE of one probe: counts3 = (n, back,
+ * front), records12 = near_back, near_front, far; new_offset, verdict and state may each be NULL), mi355rt_probes_lookup_placed_one (LOOKUP_PLACED of one
+ * query); the message of a refusal is in mi355rt_last_error(NULL). */
+#define MI355RT_SURVEY_FLIP     1u
+#define MI355RT_PROBE_UNKNOWN   0u
+#define MI355RT_PROBE_BURIED    1u
+#define MI355RT_PROBE_IDLE      2u
+#define MI355RT_PROBE_ACTIVE    3u
+#define MI355RT_PLACE_UNSAMPLED 0u
+#define MI355RT_PLACE_THROUGH   1u
+#define MI355RT_PLACE_AWAY      2u
+#define MI355RT_PLACE_STAY      3u
+#define MI355RT_PLACE_BACK      4u
+#define MI355RT_PLACE_REST      5u
+#define MI355RT_PLACE_REFUSED   8u
+typedef struct mi355rt_probe_survey_config { uint32_t spp, first_sample, accumulate, flags; float max_distance; } mi355rt_probe_survey_config;   /* 20 bytes */
+typedef struct mi355rt_probe_survey { uint32_t *n, *back, *front; float *near_back, *near_front, *far; } mi355rt_probe_survey;   /* 48 bytes; records: npoints x 4 */
+typedef struct mi355rt_probe_place_config { float back_share, max_offset, min_front, max_distance; } mi355rt_probe_place_config;   /* 16 bytes */
+void mi355rt_probes_survey_default_config(mi355rt_probe_survey_config* cfg);   /* spp 64, first_sample 0, accumulate 0, flags 0; max_distance 0: to be set */
+void mi355rt_probes_place_default_config(mi355rt_probe_place_config* cfg);     /* back_share 0.25, max_offset 0.45; min_front 0 and max_distance 0: to be set */
+int  mi355rt_probes_survey(mi355rt_handle* h, const float* points3, const uint32_t* ids /* NULL: i */, size_t npoints, const mi355rt_probe_survey_config* cfg, uint32_t where,
+                           const mi355rt_probe_survey* out);
+int  mi355rt_probes_place(mi355rt_handle* h, const mi355rt_probe_grid* grid, const mi355rt_probe_survey* survey, const mi355rt_probe_place_config* cfg,
+                          const float* offsets /* may be NULL: zero */, uint32_t where, float* new_offsets /* may be NULL */, uint8_t* verdict /* may be NULL */,
+                          uint8_t* state /* may be NULL */);
+int  mi355rt_probe_place_one(const mi355rt_probe_grid* grid, const mi355rt_probe_place_config* cfg, const uint32_t counts3[3], const float records12[12],
+                             const float offset[3] /* may be NULL: zero */, float new_offset[3], uint32_t* verdict, uint32_t* state);
+int  mi355rt_probes_lookup_placed(mi355rt_handle* h, const mi355rt_probe_grid* grid, const uint32_t* n, const float* sh, const uint8_t* usable /* may be NULL */,
+                                  const mi355rt_probe_depth* depth, const mi355rt_probe_vis_config* vc, const float* offsets /* may be NULL */, const float* points3,
+                                  const float* dirs3, const float* normals3 /* may be NULL */, size_t npoints, uint32_t mode, uint32_t where, float* rgb3,
+                                  uint8_t* ok /* may be NULL */);
+int  mi355rt_probes_lookup_placed_one(const mi355rt_probe_grid* grid, const uint32_t* n, const float* sh, const uint8_t* usable /* may be NULL */,
+                                      const mi355rt_probe_depth* depth, const mi355rt_probe_vis_config* vc, const float* offsets /* may be NULL */, const float point[3],
+                                      const float dir[3], const float normal[3] /* may be NULL */, uint32_t mode, float rgb[3], uint32_t* ok /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1685,3 +1685,199 @@ class Stats:
 
 class stats:  # namespace alias: raytracer_lib::stats::Stats
     Stats = Stats
+
+
+# ---- probe placement (include/mi355rt.h, "PROBE PLACEMENT"): the structs, the symbols and the RayTracer methods --------------------------------
+SURVEY_FLIP = 1                                                 # MI355RT_SURVEY_FLIP
+PROBE_UNKNOWN, PROBE_BURIED, PROBE_IDLE, PROBE_ACTIVE = 0, 1, 2, 3      # MI355RT_PROBE_*
+PLACE_UNSAMPLED, PLACE_THROUGH, PLACE_AWAY, PLACE_STAY, PLACE_BACK, PLACE_REST, PLACE_REFUSED = 0, 1, 2, 3, 4, 5, 8      # MI355RT_PLACE_*
+PROBE_SURVEY_OUTPUTS = ("n", "back", "front", "near_back", "near_front", "far")
+PROBE_PLACE_OUTPUTS = ("offsets", "verdict", "state")
+
+
+class ProbeSurveyConfig(C.Structure):
+    """mi355rt_probe_survey_config: flags SURVEY_FLIP; max_distance finite, > 0, <= 1e12"""
+    _fields_ = [("spp", C.c_uint32), ("first_sample", C.c_uint32), ("accumulate", C.c_uint32), ("flags", C.c_uint32), ("max_distance", C.c_float)]
+
+
+class ProbeSurvey(C.Structure):
+    """mi355rt_probe_survey: n, back, front uint32 (npoints,); near_back, near_front, far float32 (npoints, 4) rows (dist, dx, dy, dz) (void pointers here:
+    host arrays or device addresses)"""
+    _fields_ = [("n", C.c_void_p), ("back", C.c_void_p), ("front", C.c_void_p), ("near_back", C.c_void_p), ("near_front", C.c_void_p), ("far", C.c_void_p)]
+
+
+class ProbePlaceConfig(C.Structure):
+    """mi355rt_probe_place_config: back_share 0.25 and max_offset 0.45 by default; min_front and max_distance are the caller's to set"""
+    _fields_ = [("back_share", C.c_float), ("max_offset", C.c_float), ("min_front", C.c_float), ("max_distance", C.c_float)]
+
+
+ABI += [
+    ("mi355rt_probes_survey_default_config", None, [C.POINTER(ProbeSurveyConfig)]),
+    ("mi355rt_probes_place_default_config", None, [C.POINTER(ProbePlaceConfig)]),
+    ("mi355rt_probes_survey", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ProbeSurveyConfig), C.c_uint32, C.POINTER(ProbeSurvey)]),
+    ("mi355rt_probes_place", C.c_int, [_H, C.POINTER(ProbeGrid), C.POINTER(ProbeSurvey), C.POINTER(ProbePlaceConfig), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("mi355rt_probe_place_one", C.c_int, [C.POINTER(ProbeGrid), C.POINTER(ProbePlaceConfig), _U, _F, _F, _F, _U, _U]),
+    ("mi355rt_probes_lookup_placed", C.c_int, [_H, C.POINTER(ProbeGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ProbeDepth), C.POINTER(ProbeVisConfig), C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("mi355rt_probes_lookup_placed_one", C.c_int, [C.POINTER(ProbeGrid), _U, _F, C.POINTER(C.c_uint8), C.POINTER(ProbeDepth), C.POINTER(ProbeVisConfig), _F, _F, _F, _F,
+                                                   C.c_uint32, _F, _U]),
+]
+
+
+def _survey_pointers(sv, nprobes, name):
+    """(ProbeSurvey, is_device) over the six arrays of a survey dict, each checked"""
+    s, devs = ProbeSurvey(), []
+    for k in PROBE_SURVEY_OUTPUTS:
+        if k not in sv:
+            raise ValueError("%s: holds no %r (probes_survey returns it)" % (name, k))
+        label = "%s[%r]" % (name, k)
+        addr, _, dev = _ray_vector(sv[k], label, np.uint32, nprobes) if k in ("n", "back", "front") else _ray_array(sv[k], label, 4, np.float32, rows=nprobes)
+        setattr(s, k, addr)
+        devs.append(dev)
+    if len(set(devs)) != 1:
+        raise ValueError("%s: its arrays must all live in one place (all numpy arrays, or all tensors on the GPU)" % name)
+    return s, devs[0]
+
+
+def _probes_survey(self, points, ids=None, spp=64, first_sample=0, max_distance=None, flip=False, into=None):
+    """mi355rt_probes_survey: what each point sees around itself, from the closest hits of probes_gather's samples (raytracer_rs_amd.probes.survey is the
+    statement): n, back, front uint32 (n,) and the records near_back, near_front, far float32 (n, 4) rows (dist, dx, dy, dz).  A back hit is one whose ray runs
+    along the hit triangle's normal (flip: against it).  max_distance: finite, > 0, <= 1e12 (None: that of `into`).  numpy arrays or torch tensors on the
+    handle's GPU, under probes_gather's rules.  into: the dict of an earlier call with the same max_distance; its arrays are continued and returned:
+    probes_survey(spp=3) then probes_survey(spp=5, first_sample=3, into=res) is probes_survey(spp=8) bit for bit.  Returns a dict name -> array, with
+    "max_distance".  Only closest hits are traced: last_counts() reports n * spp primary rays, no bounce and no shadow ray."""
+    if into is not None:
+        if "max_distance" not in into:
+            raise ValueError("into: holds no max_distance")
+        if max_distance is None:
+            max_distance = into["max_distance"]
+        if float(np.float32(into["max_distance"])) != float(np.float32(max_distance)):
+            raise ValueError("into: its survey has max_distance %r, not %r" % (into["max_distance"], max_distance))
+    if max_distance is None:
+        raise ValueError("max_distance: give one (probes.grid_max_distance(grid) is the usual choice)")
+    max_distance = float(np.float32(max_distance))
+    if not (np.isfinite(max_distance) and 0.0 < max_distance <= 1e12):
+        raise ValueError("max_distance: finite, > 0 and <= 1e12, not %r" % max_distance)
+    addr, n, dev = _ray_array(points, "points", 3, np.float32)
+    iaddr = None
+    if ids is not None:
+        iaddr, _, idev = _ray_vector(ids, "ids", np.uint32, n)
+        if idev != dev:
+            raise ValueError("ids must live where points live (both numpy arrays, or both tensors on the GPU)")
+    cfg = ProbeSurveyConfig()
+    lib().mi355rt_probes_survey_default_config(C.byref(cfg))
+    cfg.spp, cfg.first_sample, cfg.accumulate, cfg.flags, cfg.max_distance = int(spp), int(first_sample), 1 if into is not None else 0, SURVEY_FLIP if flip else 0, max_distance
+    if into is not None:
+        o, odev = _survey_pointers(into, n, "into")
+        if odev != dev:
+            raise ValueError("into must live where points live")
+        out = {k: into[k] for k in PROBE_SURVEY_OUTPUTS}
+    else:
+        out, o = {}, ProbeSurvey()
+        if dev:
+            import torch
+        for k in PROBE_SURVEY_OUTPUTS:
+            shape, f32 = ((n,), False) if k in ("n", "back", "front") else ((n, 4), True)
+            out[k] = torch.zeros(shape, dtype=torch.float32 if f32 else torch.int32, device=points.device) if dev else np.zeros(shape, np.float32 if f32 else np.uint32)
+            setattr(o, k, out[k].data_ptr() if dev else out[k].ctypes.data)
+    out["max_distance"] = max_distance
+    if dev:
+        import torch
+        torch.cuda.current_stream(points.device).synchronize()          # what produced the inputs (and the zero fill) has finished: the library's stream knows nothing of torch's
+    self._check(lib().mi355rt_probes_survey(self._h, addr, iaddr, n, C.byref(cfg), RAYS_DEVICE if dev else RAYS_HOST, C.byref(o)))
+    return out
+
+
+def _probes_place(self, grid, survey, offsets=None, back_share=0.25, max_offset=0.45, min_front=None, want=PROBE_PLACE_OUTPUTS):
+    """mi355rt_probes_place: where every probe of a grid goes and the state it gets (raytracer_rs_amd.probes.place and probes.classify are the statement);
+    traces nothing.  survey: the dict probes_survey returned at probes.grid_points(grid) + offsets; offsets: float32 (nprobes, 3) or None (zero); min_front: a
+    length, None: probes.grid_min_front(grid); want: any of "offsets" (float32 (nprobes, 3), new arrays), "verdict" (uint8, PLACE_*), "state" (uint8, PROBE_*).
+    numpy arrays or torch tensors on the handle's GPU, all alike.  Returns a tuple in the order of want."""
+    want = tuple(want)
+    if not want or any(w not in PROBE_PLACE_OUTPUTS for w in want) or len(set(want)) != len(want):
+        raise ValueError("want: a non-empty selection of %s without repeats, not %r" % (PROBE_PLACE_OUTPUTS, want))
+    g = grid if isinstance(grid, ProbeGrid) else ProbeGrid.from_dict(grid)
+    nprobes = int(g.counts[0]) * int(g.counts[1]) * int(g.counts[2])
+    s, dev = _survey_pointers(survey, nprobes, "survey")
+    oaddr = None
+    if offsets is not None:
+        oaddr, _, odev = _ray_array(offsets, "offsets", 3, np.float32, rows=nprobes)
+        if odev != dev:
+            raise ValueError("offsets must live where the survey lives (all numpy arrays, or all tensors on the GPU)")
+    if min_front is None:
+        from . import probes as _probes
+        min_front = _probes.grid_min_front(dict(origin=list(g.origin), spacing=list(g.spacing), counts=list(g.counts)))
+    cfg = ProbePlaceConfig()
+    lib().mi355rt_probes_place_default_config(C.byref(cfg))
+    cfg.back_share, cfg.max_offset, cfg.min_front, cfg.max_distance = float(back_share), float(max_offset), float(min_front), float(np.float32(survey.get("max_distance", 0.0)))
+    res, addrs = {}, dict.fromkeys(PROBE_PLACE_OUTPUTS)
+    if dev:
+        import torch
+        where = survey["n"].device
+    for w in want:
+        shape, f32 = ((nprobes, 3), True) if w == "offsets" else ((nprobes,), False)
+        res[w] = torch.zeros(shape, dtype=torch.float32 if f32 else torch.uint8, device=where) if dev else np.zeros(shape, np.float32 if f32 else np.uint8)
+        addrs[w] = res[w].data_ptr() if dev else res[w].ctypes.data
+    if dev:
+        torch.cuda.current_stream(where).synchronize()
+    self._check(lib().mi355rt_probes_place(self._h, C.byref(g), C.byref(s), C.byref(cfg), oaddr, RAYS_DEVICE if dev else RAYS_HOST, addrs["offsets"], addrs["verdict"],
+                                           addrs["state"]))
+    return tuple(res[w] for w in want)
+
+
+def _probes_lookup_placed(self, grid, res, points, dirs, normals=None, mode="irradiance", usable=None, chebyshev=True, facing=True, normal_bias=0.0, offsets=None,
+                          want_ok=False):
+    """mi355rt_probes_lookup_placed: probes_lookup_vis for probes that have moved (raytracer_rs_amd.probes.lookup_placed is the statement); traces nothing.
+    offsets: float32 (nprobes, 3), the probes' offsets from their grid points, under which `res` was gathered; None: probes_lookup_vis on every bit.  The
+    weights use the moved positions, the cell and the trilinear factor the grid.  Everything else as probes_lookup_vis."""
+    if mode not in SH_MODES:
+        raise ValueError("mode: one of %s, not %r" % (tuple(SH_MODES), mode))
+    for k in ("n", "sh", "count", "moments", "depth_res", "max_distance"):
+        if k not in res:
+            raise ValueError("res: holds no %r (probes_gather_depth returns it)" % k)
+    g = grid if isinstance(grid, ProbeGrid) else ProbeGrid.from_dict(grid)
+    nprobes = int(g.counts[0]) * int(g.counts[1]) * int(g.counts[2])
+    R = int(res["depth_res"])
+    if not 2 <= R <= 16:
+        raise ValueError('res["depth_res"]: 2 .. 16, not %r' % R)
+    addr, m, dev = _ray_array(points, "points", 3, np.float32)
+    daddr, _, ddev = _ray_array(dirs, "dirs", 3, np.float32, rows=m)
+    naddr, _, ndev = _ray_vector(res["n"], 'res["n"]', np.uint32, nprobes)
+    saddr, _, sdev = self._sh_array(res["sh"], 'res["sh"]', nprobes)
+    caddr, _, cdev = self._film_array(res["count"], 'res["count"]', (nprobes, R * R), np.uint32)
+    maddr, _, mdev = self._film_array(res["moments"], 'res["moments"]', (nprobes, R * R, 2), np.float32)
+    uaddr, udev, nraddr, nrdev, oaddr, odev = None, dev, None, dev, None, dev
+    if usable is not None:
+        uaddr, _, udev = _ray_vector(usable, "usable", np.uint8, nprobes)
+    if normals is not None:
+        nraddr, _, nrdev = _ray_array(normals, "normals", 3, np.float32, rows=m)
+    if offsets is not None:
+        oaddr, _, odev = _ray_array(offsets, "offsets", 3, np.float32, rows=nprobes)
+    if not (ddev == ndev == sdev == cdev == mdev == udev == nrdev == odev == dev):
+        raise ValueError("dirs, normals, res, usable and offsets must live where points live (all numpy arrays, or all tensors on the GPU)")
+    d = ProbeDepth(R, float(np.float32(res["max_distance"])), caddr, maddr)
+    vc = ProbeVisConfig((VIS_CHEBYSHEV if chebyshev else 0) | (VIS_FACING if facing and normals is not None else 0), float(normal_bias))
+    if dev:
+        import torch
+        rgb = torch.zeros((m, 3), dtype=torch.float32, device=points.device); ok = torch.zeros(m, dtype=torch.uint8, device=points.device) if want_ok else None
+        raddr, okaddr = rgb.data_ptr(), ok.data_ptr() if want_ok else None
+        torch.cuda.current_stream(points.device).synchronize()
+    else:
+        rgb = np.zeros((m, 3), np.float32); ok = np.zeros(m, np.uint8) if want_ok else None
+        raddr, okaddr = rgb.ctypes.data, ok.ctypes.data if want_ok else None
+    self._check(lib().mi355rt_probes_lookup_placed(self._h, C.byref(g), naddr, saddr, uaddr, C.byref(d), C.byref(vc), oaddr, addr, daddr, nraddr, m, SH_MODES[mode],
+                                                   RAYS_DEVICE if dev else RAYS_HOST, raddr, okaddr))
+    return (rgb, ok) if want_ok else rgb
+
+
+def _probes_relocate(self, grid, rounds=4, spp=64, **kw):
+    """raytracer_rs_amd.probes.relocate(self, grid, ...): rounds of probes_survey and probes_place from zero offsets, then a last survey and the states.
+    device=torch.device("cuda", i): everything stays on the GPU.  Returns dict(offsets, state, usable, points, verdict, survey)."""
+    from . import probes as _probes
+    return _probes.relocate(self, grid, rounds=rounds, spp=spp, **kw)
+
+
+RayTracer.probes_survey = _probes_survey
+RayTracer.probes_place = _probes_place
+RayTracer.probes_lookup_placed = _probes_lookup_placed
+RayTracer.probes_relocate = _probes_relocate

@@ -18,6 +18,7 @@
 #include "renderer.hpp"
 #include "sh9.hpp"
 #include "oct_vis.hpp"
+#include "probe_place.hpp"
 
 using namespace mi355rt;
 
@@ -1504,5 +1505,164 @@ uint32_t mi355rt_light_count(const mi355rt_handle* h) { return h ? h->r->nlights
 uint32_t mi355rt_height(const mi355rt_handle* h) { return h ? h->r->cfg.height : 0u; }
 uint32_t mi355rt_triangle_count(const mi355rt_handle* h) { return h ? h->r->ntri : 0u; }
 uint32_t mi355rt_current_row(const mi355rt_handle* h) { return h ? h->r->current_row : 0u; }
+
+}  // extern "C"
+
+// ---- probe placement (include/mi355rt.h, "PROBE PLACEMENT") --------------------------------------------------------------------------------
+namespace {
+const char* probe_max_distance_error(float D)
+{
+    return std::isfinite(D) && D > 0.0f && D <= kOctMaxDistanceTop ? nullptr : "max_distance must be finite, > 0 and <= 1e12";
+}
+// a survey's six arrays; device: the record arrays are read and written as float4
+const char* probe_survey_error(const mi355rt_probe_survey* s, const char* name, bool device)
+{
+    static thread_local std::string msg;
+    if (!s) { msg = std::string(name) + " is NULL"; return msg.c_str(); }
+    const void* ptrs[6] = { s->n, s->back, s->front, s->near_back, s->near_front, s->far };
+    const char* names[6] = { "n", "back", "front", "near_back", "near_front", "far" };
+    for (int k = 0; k < 6; ++k) {
+        if (!ptrs[k]) { msg = std::string(name) + "." + names[k] + " is NULL"; return msg.c_str(); }
+        if (device && k >= 3 && ((uintptr_t)ptrs[k] & 15u)) { msg = std::string(name) + "." + names[k] + " must be 16-byte aligned in device memory"; return msg.c_str(); }
+    }
+    return nullptr;
+}
+// need_move: new_offsets or verdict is asked for; need_state: state is
+const char* probe_place_error(const mi355rt_probe_place_config* c, bool need_move, bool need_state)
+{
+    if (!c) return "cfg is NULL";
+    if (!(c->back_share >= 0.0f && c->back_share <= 1.0f)) return "cfg.back_share must be in [0, 1]";
+    if (!(std::isfinite(c->max_offset) && c->max_offset >= 0.0f)) return "cfg.max_offset must be finite and >= 0";
+    if (need_move && !(std::isfinite(c->min_front) && c->min_front > 0.0f)) return "cfg.min_front must be finite and > 0";
+    if (need_state) if (const char* e = probe_max_distance_error(c->max_distance)) return e;
+    return nullptr;
+}
+bool all_finite(const float* a, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) if (!std::isfinite(a[i])) return false;
+    return true;
+}
+size_t grid_probes(const mi355rt_probe_grid* g) { return (size_t)g->counts[0] * g->counts[1] * g->counts[2]; }
+PlaceConfig place_config(const mi355rt_probe_place_config* c) { return PlaceConfig{ c->back_share, c->max_offset, c->min_front, c->max_distance }; }
+}  // namespace
+
+extern "C" {
+
+void mi355rt_probes_survey_default_config(mi355rt_probe_survey_config* cfg)
+{
+    if (!cfg) return;
+    cfg->spp = 64; cfg->first_sample = 0; cfg->accumulate = 0; cfg->flags = 0; cfg->max_distance = 0.0f;
+}
+
+void mi355rt_probes_place_default_config(mi355rt_probe_place_config* cfg)
+{
+    if (!cfg) return;
+    cfg->back_share = 0.25f; cfg->max_offset = 0.45f; cfg->min_front = 0.0f; cfg->max_distance = 0.0f;
+}
+
+int mi355rt_probes_survey(mi355rt_handle* h, const float* points3, const uint32_t* ids, size_t npoints, const mi355rt_probe_survey_config* cfg, uint32_t where,
+                          const mi355rt_probe_survey* out)
+{
+    if (!h) return MI355RT_E_INVALID;
+    const char* e = nullptr;
+    if ((e = single_device_ok(h, where)) != nullptr) {}
+    else if (!cfg) e = "cfg is NULL";
+    else if ((e = probe_survey_error(out, "out", where == MI355RT_RAYS_DEVICE)) != nullptr) {}
+    else if (npoints && !points3) e = "points3 is NULL";
+    else if (cfg->spp == 0) e = "spp must be >= 1";
+    else if (cfg->flags & ~MI355RT_SURVEY_FLIP) e = "cfg.flags: unknown bits (MI355RT_SURVEY_FLIP)";
+    else if ((e = probe_max_distance_error(cfg->max_distance)) != nullptr) {}
+    else if ((uint64_t)cfg->first_sample + cfg->spp > 0xFFFFFFFFull) e = "first_sample + spp must fit 32 bits";
+    else if (npoints > 0xFFFFFFFFull || (uint64_t)npoints * cfg->spp >= (1ull << 32)) e = "npoints * spp must be < 2^32";
+    if (e) { h->r->last_error = std::string("mi355rt_probes_survey: ") + e; return MI355RT_E_INVALID; }
+    if (npoints == 0) return MI355RT_OK;
+    return h->r->probes_survey(points3, ids, npoints, *cfg, where == MI355RT_RAYS_DEVICE, *out) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_probes_place(mi355rt_handle* h, const mi355rt_probe_grid* grid, const mi355rt_probe_survey* survey, const mi355rt_probe_place_config* cfg, const float* offsets,
+                         uint32_t where, float* new_offsets, uint8_t* verdict, uint8_t* state)
+{
+    if (!h) return MI355RT_E_INVALID;
+    const char* e = nullptr;
+    if ((e = single_device_ok(h, where)) != nullptr) {}
+    else if ((e = probe_grid_error(grid)) != nullptr) {}
+    else if ((e = probe_survey_error(survey, "survey", where == MI355RT_RAYS_DEVICE)) != nullptr) {}
+    else if (!new_offsets && !verdict && !state) e = "new_offsets, verdict and state are all NULL";
+    else if ((e = probe_place_error(cfg, new_offsets || verdict, state != nullptr)) != nullptr) {}
+    else if (offsets && where == MI355RT_RAYS_HOST && !all_finite(offsets, grid_probes(grid) * 3)) e = "offsets holds a value that is not finite";
+    if (e) { h->r->last_error = std::string("mi355rt_probes_place: ") + e; return MI355RT_E_INVALID; }
+    return h->r->probes_place(*grid, *survey, *cfg, offsets, where == MI355RT_RAYS_DEVICE, new_offsets, verdict, state) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_probe_place_one(const mi355rt_probe_grid* grid, const mi355rt_probe_place_config* cfg, const uint32_t counts3[3], const float records12[12], const float offset[3],
+                            float new_offset[3], uint32_t* verdict, uint32_t* state)
+{
+    const char* e = probe_grid_error(grid);
+    if (!e) e = !counts3 ? "counts3 is NULL" : !records12 ? "records12 is NULL" : !new_offset && !verdict && !state ? "new_offset, verdict and state are all NULL" : nullptr;
+    if (!e) e = probe_place_error(cfg, new_offset || verdict, state != nullptr);
+    if (!e && offset && !all_finite(offset, 3)) e = "offset holds a value that is not finite";
+    if (e) { g_create_error = std::string("mi355rt_probe_place_one: ") + e; return MI355RT_E_INVALID; }
+    const float* r = records12;
+    const SurveyState s{ counts3[0], counts3[1], counts3[2], { r[0], r[1], r[2], r[3] }, { r[4], r[5], r[6], r[7] }, { r[8], r[9], r[10], r[11] } };
+    const PlaceConfig pc = place_config(cfg);
+    if (state) *state = place_state(s, pc);
+    if (new_offset || verdict) {
+        const float zero[3] = { 0.0f, 0.0f, 0.0f };
+        float out[3];
+        const uint32_t v = place_one(s, offset ? offset : zero, grid->spacing, grid->counts, pc, out);
+        if (new_offset) { new_offset[0] = out[0]; new_offset[1] = out[1]; new_offset[2] = out[2]; }
+        if (verdict) *verdict = v;
+    }
+    return MI355RT_OK;
+}
+
+int mi355rt_probes_lookup_placed(mi355rt_handle* h, const mi355rt_probe_grid* grid, const uint32_t* n, const float* sh, const uint8_t* usable, const mi355rt_probe_depth* depth,
+                                 const mi355rt_probe_vis_config* vc, const float* offsets, const float* points3, const float* dirs3, const float* normals3, size_t npoints,
+                                 uint32_t mode, uint32_t where, float* rgb3, uint8_t* ok)
+{
+    if (!h) return MI355RT_E_INVALID;
+    const char* e = nullptr;
+    if ((e = single_device_ok(h, where)) != nullptr) {}
+    else if ((e = probe_grid_error(grid)) != nullptr) {}
+    else if (!n) e = "n is NULL";
+    else if (!sh) e = "sh is NULL";
+    else if ((e = probe_depth_error(depth)) != nullptr) {}
+    else if ((e = probe_vis_error(vc, normals3 != nullptr)) != nullptr) {}
+    else if (!rgb3) e = "rgb3 is NULL";
+    else if (npoints && !points3) e = "points3 is NULL";
+    else if (npoints && !dirs3) e = "dirs3 is NULL";
+    else if (mode > MI355RT_SH_IRRADIANCE) e = "unknown mode (MI355RT_SH_RADIANCE or MI355RT_SH_IRRADIANCE)";
+    else if (npoints > 0xFFFFFFFFull) e = "npoints must fit 32 bits";
+    else if (offsets && where == MI355RT_RAYS_HOST && !all_finite(offsets, grid_probes(grid) * 3)) e = "offsets holds a value that is not finite";
+    if (e) { h->r->last_error = std::string("mi355rt_probes_lookup_placed: ") + e; return MI355RT_E_INVALID; }
+    if (npoints == 0) return MI355RT_OK;
+    return h->r->probes_lookup_placed(*grid, n, sh, usable, *depth, *vc, offsets, points3, dirs3, normals3, npoints, mode, where == MI355RT_RAYS_DEVICE, rgb3, ok) ? MI355RT_OK
+                                                                                                                                                                  : MI355RT_E_HIP;
+}
+
+int mi355rt_probes_lookup_placed_one(const mi355rt_probe_grid* grid, const uint32_t* n, const float* sh, const uint8_t* usable, const mi355rt_probe_depth* depth,
+                                     const mi355rt_probe_vis_config* vc, const float* offsets, const float point[3], const float dir[3], const float normal[3], uint32_t mode,
+                                     float rgb[3], uint32_t* ok)
+{
+    const char* e = probe_grid_error(grid);
+    if (!e) e = !n ? "n is NULL" : !sh ? "sh is NULL" : nullptr;
+    if (!e) e = probe_depth_error(depth);
+    if (!e) e = probe_vis_error(vc, normal != nullptr);
+    if (!e) e = !point ? "point is NULL" : !dir ? "dir is NULL" : !rgb ? "rgb is NULL" : mode > MI355RT_SH_IRRADIANCE ? "unknown mode" : nullptr;
+    if (!e && offsets && !all_finite(offsets, grid_probes(grid) * 3)) e = "offsets holds a value that is not finite";
+    if (e) { g_create_error = std::string("mi355rt_probes_lookup_placed_one: ") + e; return MI355RT_E_INVALID; }
+    ShGrid g;
+    std::memcpy(&g, grid, sizeof g);
+    const uint32_t* count = depth->count; const float* moments = depth->moments;
+    const size_t RR = (size_t)depth->res * depth->res;
+    const float zero[3] = { 0.0f, 0.0f, 0.0f };
+    const bool used = sh9_lookup_placed(g, [n](size_t j) { return n[j]; }, [sh](size_t j, int c) { return sh[27 * j + c]; }, usable != nullptr,
+                                        [usable](size_t j) { return usable[j] != 0; }, depth->res, [count, RR](size_t j, uint32_t k) { return count[j * RR + k]; },
+                                        [moments, RR](size_t j, uint32_t k, int m) { return moments[2 * (j * RR + k) + m]; }, offsets != nullptr,
+                                        [offsets](size_t j, int a) { return offsets[3 * j + a]; }, vc->flags, vc->normal_bias, point, dir, normal != nullptr,
+                                        normal ? normal : zero, mode, rgb);
+    if (ok) *ok = used ? 1u : 0u;
+    return MI355RT_OK;
+}
 
 }  // extern "C"

@@ -16,6 +16,8 @@
 #include "octree.hpp"
 #include "probes.hpp"
 #include "probes_vis.hpp"
+#include "probes_place.hpp"
+#include "probe_place.hpp"
 #include "staging.hpp"
 
 namespace mi355rt {
@@ -2303,6 +2305,84 @@ bool Renderer::debug_sample(uint32_t pixel, uint32_t sampleno, float* color3, fl
             for (int c = 0; c < 3; ++c) acc[c] = acc[c] + raw[3 * ((size_t)nd * nl + li) + c];
         node_L[3 * nd] = acc[0]; node_L[3 * nd + 1] = acc[1]; node_L[3 * nd + 2] = acc[2];
     }
+    return true;
+}
+
+// ---- probe placement (include/mi355rt.h, "PROBE PLACEMENT") -----------------------------------------------------------------------------
+// mi355rt_probes_survey: probes_gather's samples through gather's chunk loop, but not through a pass: a ray-fed pass cannot stop after its primary round, and
+// the survey wants closest hits and no radiance.  The loop makes the chunk's rays and traces nothing (traced = false); the reduce traces them with the
+// closest-hit launch of mi355rt_intersect_rays into two chunk temporaries (tuv, prim: 16 bytes per entry, made when the first, largest chunk arrives) and
+// folds them with the survey kernel.  The counters see no bounce and no shadow ray; the call reports npoints * spp primary rays.
+bool Renderer::probes_survey(const float* points3, const uint32_t* ids, size_t npoints, const mi355rt_probe_survey_config& sc, bool device, const mi355rt_probe_survey& out)
+{
+    if (!begin_call()) return false;
+    const size_t total = npoints * sc.spp;
+    Staging st(stream_, &hbm_bytes_, device);
+    const float* d_points = st.in(points3, npoints * 3); const uint32_t* d_ids = st.in(ids, npoints);
+    const bool acc = sc.accumulate != 0;                              // then the outputs go up first: the call continues what they hold
+    uint32_t* d_n = st.out(out.n, npoints, acc); uint32_t* d_back = st.out(out.back, npoints, acc); uint32_t* d_front = st.out(out.front, npoints, acc);
+    float* d_nb = st.out(out.near_back, npoints * 4, acc); float* d_nf = st.out(out.near_front, npoints * 4, acc); float* d_far = st.out(out.far, npoints * 4, acc);
+    HIP_TRY(st.error());
+    DeviceBuffer<float> c_tuv; DeviceBuffer<uint32_t> c_prim;
+    if (!gather_chunks(d_points, nullptr, d_ids, npoints, sc.spp, sc.first_sample, false, false, false, [&](const GatherChunk& c) {
+            const size_t entries = (size_t)c.cp * c.cs;
+            if (c_prim.bytes() < entries * 4) {
+                hipError_t e = c_tuv.alloc(entries * 12, &hbm_bytes_);
+                if (e == hipSuccess) e = c_prim.alloc(entries * 4, &hbm_bytes_);
+                if (e != hipSuccess) return e;
+            }
+            const hipError_t e = launch_intersect(stream_, dscene_, traversal_rows(), (int)mode_, c.rays, (uint32_t)entries, false, c_tuv.get(), c_prim.get(), nullptr);
+            if (e != hipSuccess) return e;
+            return launch_probes_survey(stream_, c.point0, c.cp, c.cs, !acc && c.sample0 == 0, (sc.flags & MI355RT_SURVEY_FLIP) != 0, sc.max_distance, dscene_.ntri, c.rays,
+                                        c_tuv.get(), c_prim.get(), dscene_.normals, d_n, d_back, d_front, d_nb, d_nf, d_far);
+        })) return false;
+    HIP_TRY(st.download());
+    return end_call(total, true);                                     // waits: the staging (and the caller's buffers) are free again
+}
+
+// mi355rt_probes_place: arithmetic on the caller's arrays, one kernel, and probes_lookup's rules around it.
+bool Renderer::probes_place(const mi355rt_probe_grid& grid, const mi355rt_probe_survey& survey, const mi355rt_probe_place_config& pc, const float* offsets, bool device,
+                            float* new_offsets, uint8_t* verdict, uint8_t* state)
+{
+    if (!quiet()) return false;
+    const size_t nprobes = (size_t)grid.counts[0] * grid.counts[1] * grid.counts[2];
+    ShGrid g;
+    std::memcpy(&g, &grid, sizeof g);
+    Staging st(stream_, &hbm_bytes_, device);
+    const uint32_t* d_n = st.in((const uint32_t*)survey.n, nprobes); const uint32_t* d_back = st.in((const uint32_t*)survey.back, nprobes);
+    const uint32_t* d_front = st.in((const uint32_t*)survey.front, nprobes);
+    const float* d_nb = st.in((const float*)survey.near_back, nprobes * 4); const float* d_nf = st.in((const float*)survey.near_front, nprobes * 4);
+    const float* d_far = st.in((const float*)survey.far, nprobes * 4);
+    const float* d_off = st.in(offsets, nprobes * 3);
+    float* d_new = st.out(new_offsets, nprobes * 3); uint8_t* d_verdict = st.out(verdict, nprobes); uint8_t* d_state = st.out(state, nprobes);
+    HIP_TRY(st.error());
+    HIP_TRY(launch_probes_place(stream_, g, PlaceConfig{ pc.back_share, pc.max_offset, pc.min_front, pc.max_distance }, (uint32_t)nprobes, d_n, d_back, d_front, d_nb, d_nf, d_far,
+                                d_off, d_new, d_verdict, d_state));
+    HIP_TRY(st.download());
+    HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's buffers are complete, on whatever stream they are used next
+    return true;
+}
+
+// mi355rt_probes_lookup_placed: probes_lookup_vis with the probes' offsets among its inputs; one kernel, and probes_lookup's rules around it.
+bool Renderer::probes_lookup_placed(const mi355rt_probe_grid& grid, const uint32_t* n, const float* sh, const uint8_t* usable, const mi355rt_probe_depth& depth,
+                                    const mi355rt_probe_vis_config& vc, const float* offsets, const float* points3, const float* dirs3, const float* normals3, size_t npoints,
+                                    uint32_t mode, bool device, float* rgb3, uint8_t* ok)
+{
+    if (!quiet()) return false;
+    const size_t nprobes = (size_t)grid.counts[0] * grid.counts[1] * grid.counts[2], RR = (size_t)depth.res * depth.res;
+    ShGrid g;
+    std::memcpy(&g, &grid, sizeof g);
+    Staging st(stream_, &hbm_bytes_, device);
+    const uint32_t* d_n = st.in(n, nprobes); const float* d_sh = st.in(sh, nprobes * 27); const uint8_t* d_usable = st.in(usable, nprobes);
+    const uint32_t* d_count = st.in((const uint32_t*)depth.count, nprobes * RR); const float* d_moments = st.in((const float*)depth.moments, nprobes * RR * 2);
+    const float* d_off = st.in(offsets, nprobes * 3);
+    const float* d_points = st.in(points3, npoints * 3); const float* d_dirs = st.in(dirs3, npoints * 3); const float* d_normals = st.in(normals3, npoints * 3);
+    float* d_rgb = st.out(rgb3, npoints * 3); uint8_t* d_ok = st.out(ok, npoints);
+    HIP_TRY(st.error());
+    HIP_TRY(launch_probes_lookup_placed(stream_, g, d_n, d_sh, d_usable, depth.res, d_count, d_moments, d_off, vc.flags, vc.normal_bias, d_points, d_dirs, d_normals, npoints, mode,
+                                        d_rgb, d_ok));
+    HIP_TRY(st.download());
+    HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's buffers are complete, on whatever stream they are used next
     return true;
 }
 

@@ -60,6 +60,14 @@ public:
     bool probes_lookup_vis(const mi355rt_probe_grid& grid, const uint32_t* n, const float* sh, const uint8_t* usable, const mi355rt_probe_depth& depth,
                            const mi355rt_probe_vis_config& vc, const float* points3, const float* dirs3, const float* normals3, size_t npoints, uint32_t mode, bool device,
                            float* rgb3, uint8_t* ok);
+    // probe placement; the caller has checked the arguments.  probes_survey: the closest hits of probes_gather's samples reduced to counts and
+    // three records per point; probes_place: the move and the state of every probe of a grid; probes_lookup_placed: probes_lookup_vis with the probes' offsets
+    bool probes_survey(const float* points3, const uint32_t* ids, size_t npoints, const mi355rt_probe_survey_config& sc, bool device, const mi355rt_probe_survey& out);
+    bool probes_place(const mi355rt_probe_grid& grid, const mi355rt_probe_survey& survey, const mi355rt_probe_place_config& pc, const float* offsets, bool device,
+                      float* new_offsets, uint8_t* verdict, uint8_t* state);
+    bool probes_lookup_placed(const mi355rt_probe_grid& grid, const uint32_t* n, const float* sh, const uint8_t* usable, const mi355rt_probe_depth& depth,
+                              const mi355rt_probe_vis_config& vc, const float* offsets, const float* points3, const float* dirs3, const float* normals3, size_t npoints,
+                              uint32_t mode, bool device, float* rgb3, uint8_t* ok);
     // bake; the caller has checked the arguments.  device: every pointer but ncovered is device memory.  Neither touches films, camera, counters
     bool bake_texels(const float* uv, uint32_t width, uint32_t height, bool flip, bool device, const mi355rt_bake_texel_outputs& out, uint32_t* ncovered);
     bool bake_atlas(const uint32_t* ids, const float* values3, uint32_t n, uint32_t width, uint32_t height, uint32_t dilate, bool device, float* atlas, uint8_t* valid, uint32_t& verdict);

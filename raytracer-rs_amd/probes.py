@@ -391,3 +391,293 @@ def grid_max_distance(grid):
     """1.5 x the length of the grid's spacing vector: the usual max_distance of a depth film, a little more than the farthest a query can lie from a corner"""
     _, spacing, _ = _grid(grid)
     return float(_F(1.5 * float(np.sqrt((spacing.astype(np.float64) ** 2).sum()))))
+
+
+# ---- probe placement (include/mi355rt.h, "PROBE PLACEMENT"; DESIGN.md §3q) -------------------------------------------------------------------------------
+# and of RayTracer.probes_survey / probes_place / probes_lookup_placed: what a probe sees around itself, where it moves, the state it gets and the lookup that
+# knows the moves (csrc/probe_place.hpp and the kernels of csrc/probes_place.hip evaluate the same expressions):
+#
+#     survey(t, prim, d, tri_normals, npoints, max_distance, flip, prev)   counts and three records per point from the samples' closest hits
+#     place(survey, offsets, grid, back_share, max_offset, min_front)      the new offsets and a verdict per probe
+#     classify(survey, back_share), usable_states(state)                   UNKNOWN / BURIED / IDLE / ACTIVE, and the lookups' usable mask
+#     lookup_placed(..., offsets), corner_weights(...)                     lookup_vis with the probes at grid point + offset; the eight weights of a query
+#     relocate(rt, grid, rounds, spp, ...), grid_min_front(grid)           rounds of survey and place from zero offsets, then survey and classify
+MISS = 0xFFFFFFFF
+SURVEY_FLIP = 1                                                 # MI355RT_SURVEY_FLIP
+UNKNOWN, BURIED, IDLE, ACTIVE = 0, 1, 2, 3                      # MI355RT_PROBE_*
+PLACE_UNSAMPLED, PLACE_THROUGH, PLACE_AWAY, PLACE_STAY, PLACE_BACK, PLACE_REST, PLACE_REFUSED = 0, 1, 2, 3, 4, 5, 8      # MI355RT_PLACE_*
+BACK_SHARE, MAX_OFFSET = 0.25, 0.45                             # the published DDGI values
+SURVEY_KEYS = ("n", "back", "front", "near_back", "near_front", "far")
+_INF = _F(np.inf)
+
+
+def survey_empty(npoints, max_distance):
+    """the survey of npoints points without a sample: counts 0, near records (+inf, 0, 0, 0), far records (-inf, 0, 0, 0)"""
+    npts = int(npoints)
+    res = dict(n=np.zeros(npts, np.uint32), back=np.zeros(npts, np.uint32), front=np.zeros(npts, np.uint32), near_back=np.zeros((npts, 4), _F),
+               near_front=np.zeros((npts, 4), _F), far=np.zeros((npts, 4), _F), max_distance=float(_max_distance(max_distance)))
+    res["near_back"][:, 0] = np.inf; res["near_front"][:, 0] = np.inf; res["far"][:, 0] = -np.inf
+    return res
+
+
+def survey(t, prim, d, tri_normals, npoints, max_distance, flip=False, prev=None):
+    """What each point sees, from the closest hits of the samples project() takes (same sample-major layout).  t float32 and prim uint32 (spp * npoints,) as
+    intersect_rays answers (t is read where prim != MISS; a prim is MISS or a triangle index), d float32 (spp * npoints, 3) the rays' directions, used as given,
+    tri_normals float32 (ntri, 3) (features.tri_normals(scene)), negated with flip.  A sample is a hit when prim != MISS and t is a positive finite number; a hit
+    is a back hit when (dx * Nx + dy * Ny) + dz * Nz > 0, else (a NaN dot too) a front hit.  Per point, in sample order, with D = max_distance: n += 1; back hit:
+    back += 1, and (t, d) replaces near_back where t < near_back.dist; front hit: front += 1, (t, d) replaces near_front where t < near_front.dist, and
+    dist = t < D ? t : D; miss: dist = D; for a front hit or a miss (dist, d) replaces far where dist > far.dist.  Strict comparisons: the first sample of a
+    distance keeps the record.  prev: a survey to continue (None: empty); it is not written.  Returns dict(n, back, front uint32 (npoints,); near_back,
+    near_front, far float32 (npoints, 4) rows (dist, dx, dy, dz); max_distance)."""
+    D = _max_distance(max_distance)
+    npts = int(npoints)
+    d = np.ascontiguousarray(d, _F).reshape(-1, npts, 3)
+    spp = d.shape[0]
+    t = np.ascontiguousarray(t, _F).reshape(spp, npts)
+    prim = np.ascontiguousarray(prim, np.uint32).reshape(spp, npts)
+    N = np.ascontiguousarray(tri_normals, _F).reshape(-1, 3)
+    if N.shape[0] == 0:
+        N = np.zeros((1, 3), _F)                                 # a scene without triangles: every sample is a miss and no normal is used
+    res = survey_empty(npts, D)
+    if prev is not None:
+        if float(_F(prev["max_distance"])) != float(D):
+            raise ValueError("prev: its max_distance is %r, not %r" % (prev["max_distance"], float(D)))
+        for k in SURVEY_KEYS:
+            res[k] = np.array(prev[k], res[k].dtype).reshape(res[k].shape)
+    with np.errstate(all="ignore"):
+        for s in range(spp):
+            found = prim[s] != np.uint32(MISS)
+            hit = found & (t[s] > _F(0.0)) & (t[s] <= _F(3.402823466e+38))
+            nrm = N[np.where(found, prim[s], 0).astype(np.int64)]
+            if flip:
+                nrm = -nrm
+            dot = (d[s][:, 0] * nrm[:, 0] + d[s][:, 1] * nrm[:, 1]) + d[s][:, 2] * nrm[:, 2]
+            back = hit & (dot > _F(0.0))
+            front = hit & ~back
+            rec = np.concatenate([t[s][:, None], d[s]], axis=1).astype(_F)
+            res["n"] += np.uint32(1)
+            res["back"][back] += np.uint32(1)
+            res["front"][front] += np.uint32(1)
+            take = back & (t[s] < res["near_back"][:, 0])
+            res["near_back"][take] = rec[take]
+            take = front & (t[s] < res["near_front"][:, 0])
+            res["near_front"][take] = rec[take]
+            dist = np.where(front, np.where(t[s] < D, t[s], D), D).astype(_F)
+            take = ~back & (dist > res["far"][:, 0])
+            rec[:, 0] = dist
+            res["far"][take] = rec[take]
+    return res
+
+
+def _survey_arrays(sv, nprobes):
+    return tuple(np.ascontiguousarray(sv[k], np.uint32 if k in ("n", "back", "front") else _F).reshape((nprobes,) if k in ("n", "back", "front") else (nprobes, 4))
+                 for k in SURVEY_KEYS)
+
+
+def _place_config(back_share, max_offset, min_front=None):
+    bs, mo = _F(back_share), _F(max_offset)
+    if not (_F(0.0) <= bs <= _F(1.0)):
+        raise ValueError("back_share: in [0, 1], not %r" % back_share)
+    if not (np.isfinite(mo) and mo >= 0):
+        raise ValueError("max_offset: finite and >= 0, not %r" % max_offset)
+    if min_front is None:
+        return bs, mo, None
+    mf = _F(min_front)
+    if not (np.isfinite(mf) and mf > 0):
+        raise ValueError("min_front: finite and > 0, not %r" % min_front)
+    return bs, mo, mf
+
+
+def place(sv, offsets, grid, back_share=BACK_SHARE, max_offset=MAX_OFFSET, min_front=None, want_verdict=False):
+    """Where every probe of the grid goes.  sv: the survey at grid_points(grid) + offsets; offsets float32 (nprobes, 3) or None (zero); min_front: a length
+    (grid_min_front(grid) is the usual choice).  With share = (float)back / (float)n, o the probe's offset, nb / nf / far its records:
+        n == 0: no candidate (PLACE_UNSAMPLED)
+        share > back_share and nb.dist < +inf: len = nb.dist + 0.5 * min_front; c = o + nb.d * len                             (PLACE_THROUGH)
+        else nf.dist < +inf and nf.dist < min_front: dot = (nf.x * far.x + nf.y * far.y) + nf.z * far.z, ln and lf the lengths sqrt((x * x + y * y) + z * z)
+            of the two directions; dot <= (0.5 * ln) * lf: m = far.dist < min_front ? far.dist : min_front; c = o + (far.d * m) / lf        (PLACE_AWAY)
+            otherwise no candidate                                                                                              (PLACE_STAY)
+        else o != 0: lo = |o|, room = nf.dist - min_front; nf.dist < +inf and room < lo: c = o + ((-o) * room) / lo; else c = 0     (PLACE_BACK)
+        else no candidate (PLACE_REST)
+    The candidate becomes the offset only if every component has |c| < max_offset * spacing or c == 0, an axis with one probe having spacing 0; a component that
+    is not finite fails both.  A refused candidate leaves the offset and adds PLACE_REFUSED to the verdict.  Returns offsets float32 (nprobes, 3), with
+    want_verdict (offsets, verdict uint8 (nprobes,))."""
+    origin, spacing, counts = _grid(grid)
+    nprobes = counts[0] * counts[1] * counts[2]
+    if min_front is None:
+        raise ValueError("min_front: give one (probes.grid_min_front(grid) is the usual choice)")
+    bs, mo, mf = _place_config(back_share, max_offset, min_front)
+    n, back, front, nb, nf, far = _survey_arrays(sv, nprobes)
+    o = np.zeros((nprobes, 3), _F) if offsets is None else np.ascontiguousarray(offsets, _F).reshape(nprobes, 3)
+    if not np.isfinite(o).all():
+        raise ValueError("offsets: holds a value that is not finite")
+    with np.errstate(all="ignore"):
+        share = back.astype(_F) / n.astype(_F)
+        sampled = n != 0
+        through = sampled & (share > bs) & (nb[:, 0] < _INF)
+        near = sampled & ~through & (nf[:, 0] < _INF) & (nf[:, 0] < mf)
+        dot = (nf[:, 1] * far[:, 1] + nf[:, 2] * far[:, 2]) + nf[:, 3] * far[:, 3]
+        ln = np.sqrt((nf[:, 1] * nf[:, 1] + nf[:, 2] * nf[:, 2]) + nf[:, 3] * nf[:, 3]).astype(_F)
+        lf = np.sqrt((far[:, 1] * far[:, 1] + far[:, 2] * far[:, 2]) + far[:, 3] * far[:, 3]).astype(_F)
+        away = near & (dot <= (_F(0.5) * ln) * lf)
+        stay = near & ~away
+        moved = (o != _F(0.0)).any(axis=1)
+        backw = sampled & ~through & ~near & moved
+        rest = sampled & ~through & ~near & ~moved
+        length = nb[:, 0] + _F(0.5) * mf
+        c_through = o + nb[:, 1:4] * length[:, None]
+        m = np.where(far[:, 0] < mf, far[:, 0], mf).astype(_F)
+        c_away = o + (far[:, 1:4] * m[:, None]) / lf[:, None]
+        lo = np.sqrt((o[:, 0] * o[:, 0] + o[:, 1] * o[:, 1]) + o[:, 2] * o[:, 2]).astype(_F)
+        room = nf[:, 0] - mf
+        part = (nf[:, 0] < _INF) & (room < lo)
+        c_back = np.where(part[:, None], o + ((-o) * room[:, None]) / lo[:, None], _F(0.0)).astype(_F)
+        c = np.where(through[:, None], c_through, np.where(away[:, None], c_away, c_back)).astype(_F)
+        bound = np.array([mo * (_F(0.0) if counts[a] == 1 else spacing[a]) for a in range(3)], _F)
+        fits = ((np.abs(c) < bound[None, :]) | (c == _F(0.0))).all(axis=1)
+    cand = through | away | backw
+    out = np.where((cand & fits)[:, None], c, o).astype(_F)
+    verdict = np.full(nprobes, PLACE_UNSAMPLED, np.uint8)
+    for mask, code in ((through, PLACE_THROUGH), (away, PLACE_AWAY), (stay, PLACE_STAY), (backw, PLACE_BACK), (rest, PLACE_REST)):
+        verdict[mask] = code
+    verdict[cand & ~fits] |= PLACE_REFUSED
+    return (out, verdict) if want_verdict else out
+
+
+def classify(sv, back_share=BACK_SHARE):
+    """uint8 (nprobes,): UNKNOWN where n == 0; BURIED where (float)back / (float)n > back_share; IDLE where not near_front.dist < the survey's max_distance (no
+    front hit within reach: nothing there to light); ACTIVE everything else"""
+    nprobes = int(np.asarray(sv["n"]).size)
+    n, back, front, nb, nf, far = _survey_arrays(sv, nprobes)
+    bs, _, _ = _place_config(back_share, MAX_OFFSET)
+    D = _max_distance(sv["max_distance"])
+    with np.errstate(all="ignore"):
+        share = back.astype(_F) / n.astype(_F)
+        state = np.where(n == 0, UNKNOWN, np.where(share > bs, BURIED, np.where(nf[:, 0] < D, ACTIVE, IDLE)))
+    return state.astype(np.uint8)
+
+
+def usable_states(state):
+    """uint8: 1 for ACTIVE and IDLE probes, the shape of the usable= mask the lookups take (a numpy array or a torch tensor)"""
+    if isinstance(state, np.ndarray):
+        return ((state == ACTIVE) | (state == IDLE)).astype(np.uint8)
+    return ((state == ACTIVE) | (state == IDLE)).to(state.dtype)
+
+
+def grid_min_front(grid):
+    """a fifth of the smallest spacing among the axes with more than one probe (of all axes when every axis has one): the usual min_front"""
+    _, spacing, counts = _grid(grid)
+    s = [spacing[a] for a in range(3) if counts[a] > 1] or list(spacing)
+    return float(_F(0.2) * min(s))
+
+
+def _placed(grid, res, depth, points, normals, usable, chebyshev, facing, normal_bias, offsets):
+    """the corners of lookup_placed: (m, per corner (used, wj, probe))"""
+    origin, spacing, counts = _grid(grid)
+    nprobes = counts[0] * counts[1] * counts[2]
+    R = _res(depth["res"])
+    count = np.ascontiguousarray(depth["count"], np.uint32).reshape(nprobes, R * R)
+    moments = np.ascontiguousarray(depth["moments"], _F).reshape(nprobes, R * R, 2)
+    n = np.ascontiguousarray(res["n"], np.uint32).reshape(nprobes)
+    use = None if usable is None else np.ascontiguousarray(usable, np.uint8).reshape(nprobes)
+    off = None if offsets is None else np.ascontiguousarray(offsets, _F).reshape(nprobes, 3)
+    if off is not None and not np.isfinite(off).all():
+        raise ValueError("offsets: holds a value that is not finite")
+    points = np.ascontiguousarray(points, _F).reshape(-1, 3)
+    m = points.shape[0]
+    bias = _F(normal_bias)
+    if not np.isfinite(bias):
+        raise ValueError("normal_bias must be finite")
+    nrm = None if normals is None else np.ascontiguousarray(normals, _F).reshape(m, 3)
+    with np.errstate(all="ignore"):
+        pb = points if nrm is None else (points + bias * nrm).astype(_F)
+    i, f = zip(*(_axis(points[:, a], origin[a], spacing[a], counts[a]) for a in range(3)))
+    corners = []
+    with np.errstate(all="ignore"):
+        for j in range(8):
+            c, w = [], []
+            for a in range(3):
+                up = (j >> a) & 1
+                c.append(np.minimum(i[a].astype(np.int64) + 1, counts[a] - 1) if up else i[a].astype(np.int64))
+                w.append(f[a] if up else _F(1.0) - f[a])
+            t = (w[0] * w[1]) * w[2]
+            probe = (c[2] * counts[1] + c[1]) * counts[0] + c[0]
+            pos = [origin[a] + c[a].astype(np.uint32).astype(_F) * spacing[a] for a in range(3)]
+            if off is not None:
+                pos = [pos[a] + off[probe, a] for a in range(3)]
+            v = np.stack([pb[:, a] - pos[a] for a in range(3)], axis=1).astype(_F)
+            r, fine = _length(v)
+            vis = _visibility(count[probe], moments[probe], R, v, r, fine) if chebyshev else np.ones(m, _F)
+            face = np.ones(m, _F)
+            if facing and nrm is not None:
+                dot = ((-v[:, 0]) * nrm[:, 0] + (-v[:, 1]) * nrm[:, 1]) + (-v[:, 2]) * nrm[:, 2]
+                q = (dot / np.where(fine, r, _F(1.0)).astype(_F) + _F(1.0)) * _F(0.5)
+                q = np.where(q >= _F(0.0001), q, _F(0.0001)).astype(_F)
+                face = np.where(fine, q * q + _F(0.2), _F(1.0)).astype(_F)
+            wj = (t * vis) * face
+            nj = n[probe]
+            used = (t != _F(0.0)) & (nj != 0) & (wj != _F(0.0))
+            if use is not None:
+                used &= use[probe] != 0
+            corners.append((used, wj.astype(_F), probe))
+    return m, corners
+
+
+def corner_weights(grid, res, depth, points, normals=None, usable=None, chebyshev=True, facing=True, normal_bias=0.0, offsets=None):
+    """The weights lookup_placed gives the eight corners of each query: float32 (m, 8), corner j in column j, 0 for a corner that is skipped; and the corners'
+    probe indices int64 (m, 8)"""
+    m, corners = _placed(grid, res, depth, points, normals, usable, chebyshev, facing, normal_bias, offsets)
+    w = np.stack([np.where(used, wj, _F(0.0)) for used, wj, _ in corners], axis=1).astype(_F)
+    return w, np.stack([probe for _, _, probe in corners], axis=1)
+
+
+def lookup_placed(grid, res, depth, points, dirs, normals=None, mode="irradiance", usable=None, chebyshev=True, facing=True, normal_bias=0.0, offsets=None):
+    """lookup_vis() for probes that have moved: offsets float32 (nprobes, 3), and the probe position that enters v = p_b - position is
+    (origin_a + float32(i_a) * spacing_a) + offset_a.  The cell, the fractions and the trilinear factor still come from the grid.  offsets None is lookup_vis on
+    every bit; with chebyshev and facing off no position is used and it is lookup on every bit.  Returns (rgb float32 (m, 3), ok uint8 (m,))."""
+    if mode not in MODES:
+        raise ValueError("mode: one of %s, not %r" % (tuple(MODES), mode))
+    m, corners = _placed(grid, res, depth, points, normals, usable, chebyshev, facing, normal_bias, offsets)
+    nprobes = np.asarray(res["n"]).size
+    n = np.ascontiguousarray(res["n"], np.uint32).reshape(nprobes)
+    sh = np.ascontiguousarray(res["sh"], _F).reshape(nprobes, 27)
+    dirs = np.ascontiguousarray(dirs, _F).reshape(m, 3)
+    Cq = np.zeros((m, 27), _F); wsum = np.zeros(m, _F); ok = np.zeros(m, bool)
+    with np.errstate(all="ignore"):
+        for used, wj, probe in corners:
+            s = wj * (SPHERE / n[probe].astype(_F))
+            wsum = np.where(used, wsum + wj, wsum)
+            Cq = np.where(used[:, None], Cq + s[:, None] * sh[probe], Cq)
+            ok |= used
+        b = basis(dirs)
+        rr = np.zeros((m, 3), _F)
+        for k in range(9):
+            ck = Cq[:, 3 * k:3 * k + 3]
+            rr = rr + ((A[k] * ck) if mode == "irradiance" else ck) * b[:, k, None]
+        rgb = np.where(ok[:, None], rr / wsum[:, None], _F(0.0)).astype(_F)
+    return rgb, ok.astype(np.uint8)
+
+
+def relocate(rt, grid, rounds=4, spp=64, back_share=BACK_SHARE, max_offset=MAX_OFFSET, min_front=None, max_distance=None, flip=False, ids=None, device=None):
+    """Move the probes of a grid out of geometry and say what became of each.  rt: a RayTracer (anything with its probes_survey and probes_place).  From zero
+    offsets, per round r: survey at grid_points(grid) + offsets (one f32 addition per component) with the sample numbers r * spp .. r * spp + spp - 1, then
+    place; after the last round one more survey (first_sample rounds * spp) and classify.  min_front None: grid_min_front(grid); max_distance None:
+    grid_max_distance(grid).  device: a torch device of the handle's GPU — then every array is a tensor there and nothing leaves the GPU between the rounds.
+    Returns dict(offsets float32 (nprobes, 3), state uint8 (nprobes,), usable uint8 (nprobes,), points float32 (nprobes, 3), verdict uint8 (nprobes,) of the
+    last round, survey: the last survey)."""
+    min_front = grid_min_front(grid) if min_front is None else min_front
+    max_distance = grid_max_distance(grid) if max_distance is None else max_distance
+    gp = grid_points(grid)
+    offsets, verdict = np.zeros_like(gp), np.zeros(len(gp), np.uint8)
+    if device is not None:
+        import torch
+        gp, offsets, verdict = torch.from_numpy(gp).to(device), torch.from_numpy(offsets).to(device), torch.from_numpy(verdict).to(device)
+        if ids is not None and isinstance(ids, np.ndarray):
+            ids = torch.from_numpy(np.ascontiguousarray(ids, np.uint32).view(np.int32)).to(device)
+    kw = dict(back_share=back_share, max_offset=max_offset, min_front=min_front)
+    for r in range(int(rounds) + 1):
+        points = gp + offsets
+        sv = rt.probes_survey(points, ids, spp=spp, first_sample=r * int(spp), max_distance=max_distance, flip=flip)
+        if r < int(rounds):
+            offsets, verdict = rt.probes_place(grid, sv, offsets, want=("offsets", "verdict"), **kw)
+    state = rt.probes_place(grid, sv, None, want=("state",), **kw)[0]
+    return dict(offsets=offsets, state=state, usable=usable_states(state), points=points, verdict=verdict, survey=sv)
