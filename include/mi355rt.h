@@ -1187,6 +1187,54 @@ int  mi355rt_probes_lookup_placed_one(const mi355rt_probe_grid* grid, const uint
                                       const mi355rt_probe_depth* depth, const mi355rt_probe_vis_config* vc, const float* offsets /* may be NULL */, const float point[3],
                                       const float dir[3], const float normal[3] /* may be NULL */, uint32_t mode, float rgb[3], uint32_t* ok /* may be NULL */);
 
+/* ---- PROBE-LIT: the radiance along caller-given rays with the whole bounce tree replaced by one lookup in a probe volume, and that lookup at caller-given
+ * surface points.  The reference's compute_radiance (mod.rs:132-176) returns shade() + (1 / num_sub) * sum of the children's radiance: the
+ * bounce term is the UNIFORM mean of the radiance arriving over the hemisphere of the triangle normal — not cosine-weighted, not multiplied by albedo; what
+ * mi355rt_gather estimates under MI355RT_GATHER_MEAN.  For a field given as SH coefficients that mean is a zonal convolution with the band factors 1, 1/2, 0,
+ * so only coefficients 0 .. 3 of a probe are read.  raytracer-rs_amd/probe_lit.py states all of it in numpy; everything is f32, unfused, in the order written.
+ *
+ * A VOLUME is what mi355rt_probes_lookup_placed takes of a grid: grid, n, sh, optional usable, optional depth with vc, optional offsets.  With depth NULL, vc
+ * and offsets must be NULL too, and the corner weights are LOOKUP's t_j.
+ *
+ * HEMI, the hemisphere mean at a point p with normal N (used as given).  The corners, their skipping rules, wsum and the weight w_j = (t_j * vis) * face are
+ * exactly those of LOOKUP_PLACED for (p, dir = N, normal = N) (of LOOKUP without depth).  Per used corner, in j order from +0.0f:
+ *     s_j = w_j * (12.566370614f / (float)n_j);   C[k][c] += s_j * sh_j[k][c]   for k = 0 .. 3 only   (coefficients 4 .. 8 are never read)
+ *     m_c = ((C[0][c] * b_0 + (0.5f * C[1][c]) * b_1(N)) + (0.5f * C[2][c]) * b_2(N)) + (0.5f * C[3][c]) * b_3(N)     (THE BASIS; the sum from +0.0f in k order)
+ *     x_c = m_c / wsum;   indirect_c = x_c >= 0.0f ? x_c : 0.0f with MI355RT_PROBE_LIT_CLAMP (a NaN becomes 0), x_c without;   ok = 1
+ * No corner used: indirect = 0, ok = 0.  A band-1 mean can ring below zero next to a strong light: hence the clamp.
+ *
+ * SHADE, the reference's shade() (mod.rs:207-261) at a hit of ray (pos, dir) at (t, u, v) of triangle prim: P = pos + t * dir (one multiply and one add per
+ * axis); N the triangle's normal and the diffuse colour as the feature film has them.  Per light, in scene order, from +0.0f: l = light - P, ln = normalized(l),
+ * ndl = dot(N, ln); ndl < 0: skipped; the shadow ray (P + l * 0.01f, l) blocked by the rule of mi355rt_occluded_rays: skipped; otherwise
+ * refl = (2 * ndl) * N - ln, spec = pow32(dot(normalized(dir), refl)) (five squarings in f64, one rounding), light += (diffuse * ndl + spec) * colour.
+ * This is the root light sum: `direct` of mi355rt_trace_rays for the same ray, bit for bit.
+ *
+ * mi355rt_probe_lit_rays, per ray: (tuv, prim) is what mi355rt_intersect_rays gives in the handle's semantics.  A miss: rgb = light = indirect = 0, ok = 0,
+ * prim MISS, tuv untouched.  A hit: light = SHADE, (indirect, ok) = HEMI at (P, N) with N NOT flipped towards the viewer (the reference's bounce rays go to
+ * the normal's side, whichever side the ray came from), rgb_c = light_c + indirect_c.  Any output may be NULL, not all; every subset gives the same bits.
+ * Around the call mi355rt_probes_survey's rules hold: a queued or speculative frame is settled first; films, camera, lens, current row and guides are
+ * untouched; a striped handle serves it; mi355rt_last_counts reports nrays primary rays, no bounce ray — and, as for `direct` of mi355rt_gather, NO shadow
+ * ray: the shadow rays go through the launch of mi355rt_occluded_rays, which counts nothing.  shade()'s light maps are not consulted: every (hit, light) pair
+ * is traced.  The rays run in chunks of at most min(pass samples, 4 Mi / max(nlights, 1)); the chunk temporaries (16 + 25 * nlights bytes per ray) are freed
+ * by the end of the call.
+ * mi355rt_probe_lit_points: HEMI at npoints caller-given points and normals.  It traces nothing; mi355rt_probes_lookup's rules hold around it.
+ * `where` covers every pointer of a call, the volume's arrays included (the struct itself is host memory).
+ * ERRORS.  MI355RT_E_INVALID, the argument named in mi355rt_last_error and nothing written, for: a device group; an unknown where; volume NULL; everything
+ * mi355rt_probes_lookup_placed refuses of the volume's members; depth NULL with vc or offsets given; unknown flag bits; out NULL or all its pointers NULL
+ * (indirect3 NULL); NULL rays6, points3 or normals3 with a non-zero count; nrays * max(nlights, 1) >= 2^32; host offsets that hold a non-finite value.  A
+ * count of 0 succeeds and writes nothing.
+ * Host only, no handle, the same header the kernels compile (csrc/probe_lit_math.hpp): mi355rt_probe_lit_one (HEMI of one query); the message of a refusal is
+ * in mi355rt_last_error(NULL). */
+#define MI355RT_PROBE_LIT_CLAMP 1u
+typedef struct mi355rt_probe_volume { const mi355rt_probe_grid* grid; const uint32_t* n; const float* sh; const uint8_t* usable /* may be NULL */;
+    const mi355rt_probe_depth* depth /* may be NULL */; const mi355rt_probe_vis_config* vc /* NULL iff depth is */; const float* offsets /* may be NULL; NULL if depth is */; } mi355rt_probe_volume;  /* 56 bytes */
+typedef struct mi355rt_probe_lit_outputs { float *rgb, *light, *indirect, *tuv; uint32_t* prim; uint8_t* ok; } mi355rt_probe_lit_outputs;  /* 48 bytes; any may be NULL, not all */
+int  mi355rt_probe_lit_points(mi355rt_handle* h, const mi355rt_probe_volume* volume, const float* points3, const float* normals3, size_t npoints, uint32_t flags, uint32_t where,
+                              float* indirect3, uint8_t* ok /* may be NULL */);
+int  mi355rt_probe_lit_rays(mi355rt_handle* h, const mi355rt_probe_volume* volume, const float* rays6, size_t nrays, uint32_t flags, uint32_t where,
+                            const mi355rt_probe_lit_outputs* out);
+int  mi355rt_probe_lit_one(const mi355rt_probe_volume* volume, const float point[3], const float normal[3], uint32_t flags, float indirect[3], uint32_t* ok /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

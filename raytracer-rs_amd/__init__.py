@@ -1881,3 +1881,147 @@ RayTracer.probes_survey = _probes_survey
 RayTracer.probes_place = _probes_place
 RayTracer.probes_lookup_placed = _probes_lookup_placed
 RayTracer.probes_relocate = _probes_relocate
+
+
+# ---- probe-lit shading (include/mi355rt.h, "PROBE-LIT"): the structs, the symbols and the RayTracer methods -----------------------------------
+PROBE_LIT_CLAMP = 1                                             # MI355RT_PROBE_LIT_CLAMP
+PROBE_LIT_OUTPUTS = ("rgb", "light", "indirect", "tuv", "prim", "ok")
+
+
+class ProbeVolume(C.Structure):
+    """mi355rt_probe_volume: grid, n, sh, usable (may be null), depth with vc (both null, or neither), offsets (may be null; null without depth)"""
+    _fields_ = [("grid", C.POINTER(ProbeGrid)), ("n", C.c_void_p), ("sh", C.c_void_p), ("usable", C.c_void_p), ("depth", C.POINTER(ProbeDepth)),
+                ("vc", C.POINTER(ProbeVisConfig)), ("offsets", C.c_void_p)]
+
+
+class ProbeLitOutputs(C.Structure):
+    """mi355rt_probe_lit_outputs: rgb, light, indirect, tuv float32 (n, 3); prim uint32 (n,); ok uint8 (n,); any may be null, not all"""
+    _fields_ = [("rgb", C.c_void_p), ("light", C.c_void_p), ("indirect", C.c_void_p), ("tuv", C.c_void_p), ("prim", C.c_void_p), ("ok", C.c_void_p)]
+
+
+ABI += [
+    ("mi355rt_probe_lit_points", C.c_int, [_H, C.POINTER(ProbeVolume), C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("mi355rt_probe_lit_rays", C.c_int, [_H, C.POINTER(ProbeVolume), C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(ProbeLitOutputs)]),
+    ("mi355rt_probe_lit_one", C.c_int, [C.POINTER(ProbeVolume), _F, _F, C.c_uint32, _F, _U]),
+]
+
+
+def _probe_volume(self, vol):
+    """(ProbeVolume, is_device, keep) over the arrays of a probe_lit.volume dict, each checked; keep: what the struct points to"""
+    for k in ("grid", "n", "sh", "usable", "depth", "offsets", "chebyshev", "facing", "normal_bias"):
+        if k not in vol:
+            raise ValueError("volume: holds no %r (probe_lit.volume makes one)" % k)
+    g = vol["grid"] if isinstance(vol["grid"], ProbeGrid) else ProbeGrid.from_dict(vol["grid"])
+    nprobes = int(g.counts[0]) * int(g.counts[1]) * int(g.counts[2])
+    v, devs, keep = ProbeVolume(), [], [g]
+    v.grid = C.pointer(g)
+    v.n, _, dev = _ray_vector(vol["n"], 'volume["n"]', np.uint32, nprobes)
+    devs.append(dev)
+    v.sh, _, dev = self._sh_array(vol["sh"], 'volume["sh"]', nprobes)
+    devs.append(dev)
+    if vol["usable"] is not None:
+        v.usable, _, dev = _ray_vector(vol["usable"], 'volume["usable"]', np.uint8, nprobes)
+        devs.append(dev)
+    depth = vol["depth"]
+    if depth is None:
+        if vol["offsets"] is not None:
+            raise ValueError('volume["offsets"]: given without volume["depth"]')
+    else:
+        R = int(depth["res"])
+        if not 2 <= R <= 16:
+            raise ValueError('volume["depth"]["res"]: 2 .. 16, not %r' % R)
+        caddr, _, dev = self._film_array(depth["count"], 'volume["depth"]["count"]', (nprobes, R * R), np.uint32)
+        devs.append(dev)
+        maddr, _, dev = self._film_array(depth["moments"], 'volume["depth"]["moments"]', (nprobes, R * R, 2), np.float32)
+        devs.append(dev)
+        d = ProbeDepth(R, float(np.float32(depth.get("max_distance", 1.0))), caddr, maddr)
+        vc = ProbeVisConfig((VIS_CHEBYSHEV if vol["chebyshev"] else 0) | (VIS_FACING if vol["facing"] else 0), float(vol["normal_bias"]))
+        keep += [d, vc]
+        v.depth, v.vc = C.pointer(d), C.pointer(vc)
+        if vol["offsets"] is not None:
+            v.offsets, _, dev = _ray_array(vol["offsets"], 'volume["offsets"]', 3, np.float32, rows=nprobes)
+            devs.append(dev)
+    if len(set(devs)) != 1:
+        raise ValueError("volume: its arrays must all live in one place (all numpy arrays, or all tensors on the GPU)")
+    return v, devs[0], keep
+
+
+def _probe_lit_points(self, volume, points, normals, clamp=True, want_ok=False):
+    """mi355rt_probe_lit_points: the uniform mean over the hemisphere of each normal of the light a probe volume holds, at surface points
+    (raytracer_rs_amd.probe_lit.hemi is the statement): the reference's bounce term, read from the probes without tracing a ray.  volume: what
+    probe_lit.volume makes; points, normals: float32 (m, 3).  numpy arrays or torch tensors on the handle's GPU, the volume's arrays alike.  clamp: a negative
+    (or NaN) value becomes 0.  Returns indirect float32 (m, 3), with want_ok (indirect, ok uint8 (m,))."""
+    v, vdev, _keep = _probe_volume(self, volume)
+    addr, m, dev = _ray_array(points, "points", 3, np.float32)
+    naddr, _, ndev = _ray_array(normals, "normals", 3, np.float32, rows=m)
+    if not (vdev == ndev == dev):
+        raise ValueError("normals and the volume must live where points live (all numpy arrays, or all tensors on the GPU)")
+    if dev:
+        import torch
+        ind = torch.zeros((m, 3), dtype=torch.float32, device=points.device); ok = torch.zeros(m, dtype=torch.uint8, device=points.device) if want_ok else None
+        iaddr, okaddr = ind.data_ptr(), ok.data_ptr() if want_ok else None
+        torch.cuda.current_stream(points.device).synchronize()
+    else:
+        ind = np.zeros((m, 3), np.float32); ok = np.zeros(m, np.uint8) if want_ok else None
+        iaddr, okaddr = ind.ctypes.data, ok.ctypes.data if want_ok else None
+    self._check(lib().mi355rt_probe_lit_points(self._h, C.byref(v), addr, naddr, m, PROBE_LIT_CLAMP if clamp else 0, RAYS_DEVICE if dev else RAYS_HOST, iaddr, okaddr))
+    return (ind, ok) if want_ok else ind
+
+
+def _probe_lit_rays(self, volume, rays6, want=("rgb",), clamp=True, into=None):
+    """mi355rt_probe_lit_rays: the radiance along caller-given rays with the bounce tree replaced by one lookup in a probe volume
+    (raytracer_rs_amd.probe_lit.rays is the statement): closest hit, the reference's shade() there with shadow rays (`light`: trace_rays' `direct` bit for
+    bit), the hemisphere mean of the volume (`indirect`, `ok`), and their sum (`rgb`).  rays6: float32 (n, 6) rows (pos3, dir3), used as given; want: any of
+    "rgb", "light", "indirect", "tuv", "prim", "ok".  numpy arrays or torch tensors on the handle's GPU, the volume's arrays alike, under trace_rays' rules.
+    into: a dict of arrays to write into (tuv of a miss stays as it was).  Returns a dict name -> array.  No film, camera or lens state changes;
+    last_counts() reports n primary rays."""
+    want = tuple(want)
+    if not want or any(w not in PROBE_LIT_OUTPUTS for w in want) or len(set(want)) != len(want):
+        raise ValueError("want: a non-empty selection of %s without repeats, not %r" % (PROBE_LIT_OUTPUTS, want))
+    v, vdev, _keep = _probe_volume(self, volume)
+    addr, n, dev = _ray_array(rays6, "rays6", 6, np.float32)
+    if vdev != dev:
+        raise ValueError("the volume must live where rays6 lives (all numpy arrays, or all tensors on the GPU)")
+    res, o = {}, ProbeLitOutputs()
+    if dev:
+        import torch
+    for w in want:
+        shape = (n,) if w in ("prim", "ok") else (n, 3)
+        dt = np.uint32 if w == "prim" else np.uint8 if w == "ok" else np.float32
+        if into is not None and w in into:
+            res[w] = into[w]
+            a, _, adev = (_ray_vector(res[w], "into[%r]" % w, dt, n) if len(shape) == 1 else _ray_array(res[w], "into[%r]" % w, 3, dt, rows=n))
+            if adev != dev:
+                raise ValueError("into must live where rays6 lives")
+            setattr(o, w, a)
+        elif dev:
+            res[w] = torch.zeros(shape, dtype=torch.int32 if w == "prim" else torch.uint8 if w == "ok" else torch.float32, device=rays6.device)
+            setattr(o, w, res[w].data_ptr())
+        else:
+            res[w] = np.zeros(shape, dt)
+            setattr(o, w, res[w].ctypes.data)
+    if dev:
+        torch.cuda.current_stream(rays6.device).synchronize()           # what produced the inputs (and the zero fill) has finished: the library's stream knows nothing of torch's
+    self._check(lib().mi355rt_probe_lit_rays(self._h, C.byref(v), addr, n, PROBE_LIT_CLAMP if clamp else 0, RAYS_DEVICE if dev else RAYS_HOST, C.byref(o)))
+    return res
+
+
+def _render_probe_lit(self, volume, spp=1, device=None):
+    """A probe-lit frame: lens_rays(spp) under the handle's lens (layout s * npix + p), probe_lit_rays along them, probe_lit.frame_mean over each pixel's
+    samples.  It does none of render()'s bounce rounds and touches no film.  device: None — numpy arrays, the volume's too; a torch device (or True) of the
+    handle's GPU — tensors there.  Returns dict(mean, light, indirect float32 (height, width, 3); ok_share float32 (height, width): the share of a pixel's samples
+    whose lookup used a probe).  display_image(result["mean"]) puts it on the screen."""
+    from . import probe_lit as _probe_lit
+    spp = int(spp)
+    rays6 = self.lens_rays(spp, device=False if device is None else device)
+    r = self.probe_lit_rays(volume, rays6, want=("rgb", "light", "indirect", "ok"))
+    npix, h, w = self.width * self.height, self.height, self.width
+    ok = r["ok"].astype(np.float32) if device is None else r["ok"].float()
+    out = {k: _probe_lit.frame_mean(r[s], npix).reshape(h, w, 3) for k, s in (("mean", "rgb"), ("light", "light"), ("indirect", "indirect"))}
+    out["ok_share"] = _probe_lit.frame_mean(ok.reshape(-1, 1), npix).reshape(h, w)
+    return out
+
+
+RayTracer.probe_lit_points = _probe_lit_points
+RayTracer.probe_lit_rays = _probe_lit_rays
+RayTracer.render_probe_lit = _render_probe_lit

@@ -19,6 +19,7 @@
 #include "sh9.hpp"
 #include "oct_vis.hpp"
 #include "probe_place.hpp"
+#include "probe_lit_math.hpp"
 
 using namespace mi355rt;
 
@@ -1661,6 +1662,84 @@ int mi355rt_probes_lookup_placed_one(const mi355rt_probe_grid* grid, const uint3
                                         [moments, RR](size_t j, uint32_t k, int m) { return moments[2 * (j * RR + k) + m]; }, offsets != nullptr,
                                         [offsets](size_t j, int a) { return offsets[3 * j + a]; }, vc->flags, vc->normal_bias, point, dir, normal != nullptr,
                                         normal ? normal : zero, mode, rgb);
+    if (ok) *ok = used ? 1u : 0u;
+    return MI355RT_OK;
+}
+
+}  // extern "C"
+
+// ---- probe-lit shading (include/mi355rt.h, "PROBE-LIT") ------------------------------------------------------------------------------------
+namespace {
+// host: the volume's arrays are host memory, and its offsets are inspected
+const char* probe_volume_error(const mi355rt_probe_volume* v, bool host)
+{
+    if (!v) return "volume is NULL";
+    if (const char* e = probe_grid_error(v->grid)) return e;
+    if (!v->n) return "volume.n is NULL";
+    if (!v->sh) return "volume.sh is NULL";
+    if (!v->depth) {
+        if (v->vc) return "volume.vc is given without volume.depth";
+        if (v->offsets) return "volume.offsets is given without volume.depth";
+        return nullptr;
+    }
+    if (const char* e = probe_depth_error(v->depth)) return e;
+    if (const char* e = probe_vis_error(v->vc, true)) return e;
+    if (v->offsets && host && !all_finite(v->offsets, grid_probes(v->grid) * 3)) return "volume.offsets holds a value that is not finite";
+    return nullptr;
+}
+}  // namespace
+
+extern "C" {
+
+int mi355rt_probe_lit_points(mi355rt_handle* h, const mi355rt_probe_volume* volume, const float* points3, const float* normals3, size_t npoints, uint32_t flags, uint32_t where,
+                             float* indirect3, uint8_t* ok)
+{
+    if (!h) return MI355RT_E_INVALID;
+    const char* e = nullptr;
+    if ((e = single_device_ok(h, where)) != nullptr) {}
+    else if ((e = probe_volume_error(volume, where == MI355RT_RAYS_HOST)) != nullptr) {}
+    else if (flags & ~MI355RT_PROBE_LIT_CLAMP) e = "flags: unknown bits (MI355RT_PROBE_LIT_CLAMP)";
+    else if (!indirect3) e = "indirect3 is NULL";
+    else if (npoints && !points3) e = "points3 is NULL";
+    else if (npoints && !normals3) e = "normals3 is NULL";
+    else if (npoints > 0xFFFFFFFFull) e = "npoints must fit 32 bits";
+    if (e) { h->r->last_error = std::string("mi355rt_probe_lit_points: ") + e; return MI355RT_E_INVALID; }
+    if (npoints == 0) return MI355RT_OK;
+    return h->r->probe_lit_points(*volume, points3, normals3, npoints, flags, where == MI355RT_RAYS_DEVICE, indirect3, ok) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_probe_lit_rays(mi355rt_handle* h, const mi355rt_probe_volume* volume, const float* rays6, size_t nrays, uint32_t flags, uint32_t where,
+                           const mi355rt_probe_lit_outputs* out)
+{
+    if (!h) return MI355RT_E_INVALID;
+    const char* e = nullptr;
+    if ((e = single_device_ok(h, where)) != nullptr) {}
+    else if ((e = probe_volume_error(volume, where == MI355RT_RAYS_HOST)) != nullptr) {}
+    else if (flags & ~MI355RT_PROBE_LIT_CLAMP) e = "flags: unknown bits (MI355RT_PROBE_LIT_CLAMP)";
+    else if (!out || (!out->rgb && !out->light && !out->indirect && !out->tuv && !out->prim && !out->ok)) e = "out is NULL or every output pointer in it is NULL";
+    else if (nrays && !rays6) e = "rays6 is NULL";
+    else if (nrays > 0xFFFFFFFFull || (uint64_t)nrays * std::max(h->r->nlights(), 1u) >= (1ull << 32)) e = "nrays * max(nlights, 1) must be < 2^32";
+    if (e) { h->r->last_error = std::string("mi355rt_probe_lit_rays: ") + e; return MI355RT_E_INVALID; }
+    if (nrays == 0) return MI355RT_OK;
+    return h->r->probe_lit_rays(*volume, rays6, nrays, flags, where == MI355RT_RAYS_DEVICE, *out) ? MI355RT_OK : MI355RT_E_HIP;
+}
+
+int mi355rt_probe_lit_one(const mi355rt_probe_volume* volume, const float point[3], const float normal[3], uint32_t flags, float indirect[3], uint32_t* ok)
+{
+    const char* e = probe_volume_error(volume, true);
+    if (!e) e = flags & ~MI355RT_PROBE_LIT_CLAMP ? "flags: unknown bits (MI355RT_PROBE_LIT_CLAMP)" : !point ? "point is NULL" : !normal ? "normal is NULL" : !indirect ? "indirect is NULL" : nullptr;
+    if (e) { g_create_error = std::string("mi355rt_probe_lit_one: ") + e; return MI355RT_E_INVALID; }
+    ShGrid g;
+    std::memcpy(&g, volume->grid, sizeof g);
+    const uint32_t* n = volume->n; const float* sh = volume->sh; const uint8_t* usable = volume->usable; const float* offsets = volume->offsets;
+    const mi355rt_probe_depth* depth = volume->depth;
+    const uint32_t* count = depth ? depth->count : nullptr; const float* moments = depth ? depth->moments : nullptr;
+    const uint32_t R = depth ? depth->res : 0u;
+    const size_t RR = (size_t)R * R;
+    const bool used = hemi_one(g, [n](size_t j) { return n[j]; }, [sh](size_t j, int c) { return sh[27 * j + c]; }, usable != nullptr, [usable](size_t j) { return usable[j] != 0; }, R,
+                               [count, RR](size_t j, uint32_t k) { return count[j * RR + k]; }, [moments, RR](size_t j, uint32_t k, int m) { return moments[2 * (j * RR + k) + m]; },
+                               offsets != nullptr, [offsets](size_t j, int a) { return offsets[3 * j + a]; }, depth ? volume->vc->flags : 0u, depth ? volume->vc->normal_bias : 0.0f, point,
+                               normal, (flags & MI355RT_PROBE_LIT_CLAMP) != 0, indirect);
     if (ok) *ok = used ? 1u : 0u;
     return MI355RT_OK;
 }

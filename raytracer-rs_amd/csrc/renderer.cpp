@@ -18,6 +18,7 @@
 #include "probes_vis.hpp"
 #include "probes_place.hpp"
 #include "probe_place.hpp"
+#include "probe_lit.hpp"
 #include "staging.hpp"
 
 namespace mi355rt {
@@ -2384,6 +2385,79 @@ bool Renderer::probes_lookup_placed(const mi355rt_probe_grid& grid, const uint32
     HIP_TRY(st.download());
     HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's buffers are complete, on whatever stream they are used next
     return true;
+}
+
+// ---- probe-lit shading (include/mi355rt.h, "PROBE-LIT") ----------------------------------------------------------------------------------
+namespace {
+// the volume's arrays on the device: the caller's own, or staged copies
+LitVolume stage_volume(Staging& st, const mi355rt_probe_volume& vol)
+{
+    const mi355rt_probe_grid& grid = *vol.grid;
+    const size_t nprobes = (size_t)grid.counts[0] * grid.counts[1] * grid.counts[2];
+    LitVolume v{};
+    std::memcpy(&v.grid, &grid, sizeof v.grid);
+    v.n = st.in(vol.n, nprobes); v.sh = st.in(vol.sh, nprobes * 27); v.usable = st.in(vol.usable, nprobes);
+    if (vol.depth) {
+        const size_t RR = (size_t)vol.depth->res * vol.depth->res;
+        v.R = vol.depth->res;
+        v.count = st.in((const uint32_t*)vol.depth->count, nprobes * RR); v.moments = st.in((const float*)vol.depth->moments, nprobes * RR * 2);
+        v.offsets = st.in(vol.offsets, nprobes * 3);
+        v.flags = vol.vc->flags; v.normal_bias = vol.vc->normal_bias;
+    }
+    return v;
+}
+}  // namespace
+
+// mi355rt_probe_lit_points: arithmetic on the caller's arrays, one kernel, and probes_lookup's rules around it.
+bool Renderer::probe_lit_points(const mi355rt_probe_volume& vol, const float* points3, const float* normals3, size_t npoints, uint32_t flags, bool device, float* indirect3, uint8_t* ok)
+{
+    if (!quiet()) return false;
+    Staging st(stream_, &hbm_bytes_, device);
+    const LitVolume v = stage_volume(st, vol);
+    const float* d_points = st.in(points3, npoints * 3); const float* d_normals = st.in(normals3, npoints * 3);
+    float* d_ind = st.out(indirect3, npoints * 3); uint8_t* d_ok = st.out(ok, npoints);
+    HIP_TRY(st.error());
+    HIP_TRY(launch_probe_lit_points(stream_, v, (flags & MI355RT_PROBE_LIT_CLAMP) != 0, d_points, d_normals, npoints, d_ind, d_ok));
+    HIP_TRY(st.download());
+    HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's buffers are complete, on whatever stream they are used next
+    return true;
+}
+
+// mi355rt_probe_lit_rays: the rays in chunks; per chunk the closest-hit launch of mi355rt_intersect_rays into two chunk temporaries (as probes_survey takes
+// its hits), the surface kernel's shadow rays through launch_intersect in shadow mode (as gather takes `direct`), then the shade kernel.  The temporaries are
+// made at the first, largest chunk and go with the call.  The counters see no bounce and no shadow ray; the call reports nrays primary rays.
+bool Renderer::probe_lit_rays(const mi355rt_probe_volume& vol, const float* rays6, size_t nrays, uint32_t flags, bool device, const mi355rt_probe_lit_outputs& out)
+{
+    if (!begin_call()) return false;
+    Staging st(stream_, &hbm_bytes_, device);
+    const LitVolume v = stage_volume(st, vol);
+    const float* d_rays = st.in(rays6, nrays * 6);
+    LitOutputs d{};
+    d.rgb = st.out(out.rgb, nrays * 3); d.light = st.out(out.light, nrays * 3); d.indirect = st.out(out.indirect, nrays * 3);
+    d.tuv = st.out(out.tuv, nrays * 3, true);                         // goes up first: a miss leaves it as it was
+    d.prim = st.out(out.prim, nrays); d.ok = st.out(out.ok, nrays);
+    HIP_TRY(st.error());
+    const size_t nl = std::max(nlights_, 1u);
+    const size_t per = std::min(nrays, std::max<size_t>(1, std::min(pass_sample_budget(), ((size_t)4 << 20) / nl)));
+    DeviceBuffer<float> c_tuv, c_shadow; DeviceBuffer<uint32_t> c_prim; DeviceBuffer<uint8_t> c_blocked;
+    for (size_t at = 0; at < nrays; at += per) {
+        const uint32_t cn = (uint32_t)std::min(per, nrays - at);
+        if (!c_prim) {
+            HIP_TRY(c_tuv.alloc(per * 12, &hbm_bytes_)); HIP_TRY(c_prim.alloc(per * 4, &hbm_bytes_));
+            if (nlights_) { HIP_TRY(c_shadow.alloc(per * nlights_ * 24, &hbm_bytes_)); HIP_TRY(c_blocked.alloc(per * nlights_, &hbm_bytes_)); }
+        }
+        const float* r = d_rays + 6 * at;
+        HIP_TRY(launch_intersect(stream_, dscene_, traversal_rows(), (int)mode_, r, cn, false, c_tuv.get(), c_prim.get(), nullptr));
+        if (nlights_) {
+            HIP_TRY(launch_probe_lit_surface(stream_, dscene_, r, c_tuv.get(), c_prim.get(), cn, c_shadow.get()));
+            HIP_TRY(launch_intersect(stream_, dscene_, traversal_rows(), (int)mode_, c_shadow.get(), cn * nlights_, true, nullptr, nullptr, c_blocked.get()));
+        }
+        const LitOutputs o{ d.rgb ? d.rgb + 3 * at : nullptr, d.light ? d.light + 3 * at : nullptr, d.indirect ? d.indirect + 3 * at : nullptr, d.tuv ? d.tuv + 3 * at : nullptr,
+                            d.prim ? d.prim + at : nullptr, d.ok ? d.ok + at : nullptr };
+        HIP_TRY(launch_probe_lit_shade(stream_, dscene_, v, (flags & MI355RT_PROBE_LIT_CLAMP) != 0, r, c_tuv.get(), c_prim.get(), c_blocked.get(), cn, o));
+    }
+    HIP_TRY(st.download());
+    return end_call(nrays, true);                                     // waits: the staging, the chunk temporaries (and the caller's buffers) are free again
 }
 
 }  // namespace mi355rt

@@ -68,6 +68,11 @@ public:
     bool probes_lookup_placed(const mi355rt_probe_grid& grid, const uint32_t* n, const float* sh, const uint8_t* usable, const mi355rt_probe_depth& depth,
                               const mi355rt_probe_vis_config& vc, const float* offsets, const float* points3, const float* dirs3, const float* normals3, size_t npoints,
                               uint32_t mode, bool device, float* rgb3, uint8_t* ok);
+    // probe-lit shading; the caller has checked the arguments.  probe_lit_points: the hemisphere mean of a probe volume at surface points, under
+    // probes_lookup's rules; probe_lit_rays: closest hit, shade() with shadow rays and that mean along caller-given rays, under probes_survey's rules.
+    // depth, vc null: no depth films (then offsets is null too).  device: every pointer, the volume's arrays included, is device memory
+    bool probe_lit_points(const mi355rt_probe_volume& vol, const float* points3, const float* normals3, size_t npoints, uint32_t flags, bool device, float* indirect3, uint8_t* ok);
+    bool probe_lit_rays(const mi355rt_probe_volume& vol, const float* rays6, size_t nrays, uint32_t flags, bool device, const mi355rt_probe_lit_outputs& out);
     // bake; the caller has checked the arguments.  device: every pointer but ncovered is device memory.  Neither touches films, camera, counters
     bool bake_texels(const float* uv, uint32_t width, uint32_t height, bool flip, bool device, const mi355rt_bake_texel_outputs& out, uint32_t* ncovered);
     bool bake_atlas(const uint32_t* ids, const float* values3, uint32_t n, uint32_t width, uint32_t height, uint32_t dilate, bool device, float* atlas, uint8_t* valid, uint32_t& verdict);
