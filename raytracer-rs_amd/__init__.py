@@ -441,6 +441,114 @@ def _ray_vector(a, name, dtype, rows):
     raise TypeError("%s: a numpy array or a torch tensor, not %s" % (name, type(a).__name__))
 
 
+def _film_array(a, name, shape, dtype):
+    """_ray_array for an argument of exactly this shape (rows, ...): checked as the (rows, rest) view of the same memory"""
+    if not (_is_tensor(a) or isinstance(a, np.ndarray)):
+        raise TypeError("%s: a numpy array or a torch tensor, not %s" % (name, type(a).__name__))
+    if tuple(a.shape) != tuple(shape):
+        raise ValueError("%s: shape must be %s, not %s" % (name, tuple(shape), tuple(a.shape)))
+    if not (a.is_contiguous() if _is_tensor(a) else a.flags["C_CONTIGUOUS"]):
+        raise ValueError("%s: must be C-contiguous" % name)                 # before the reshape, which would copy
+    rest = int(np.prod(shape[1:], dtype=np.int64))
+    return _ray_array(a.reshape(shape[0], rest), name, rest, dtype, rows=shape[0])
+
+
+# ---- what the array-taking methods share: the checks of want / into / max_distance and the making of outputs, host or device ----
+def _check_want(want, allowed, empty_ok=False):
+    """want as a tuple: a selection of `allowed` without repeats, non-empty unless empty_ok"""
+    want = tuple(want)
+    if (not want and not empty_ok) or any(w not in allowed for w in want) or len(set(want)) != len(want):
+        raise ValueError("want: a %sselection of %s without repeats, not %r" % ("" if empty_ok else "non-empty ", allowed, want))
+    return want
+
+
+def _input_beside(a, name, dtype, rows, cols, dev, anchor, optional=True):
+    """The address of an input that goes with an anchor input: (rows, cols), or with cols None (rows,), checked, and in the anchor's place (dev: the anchor's
+    is_device; anchor: "points live").  optional: None is accepted and gives None"""
+    if a is None and optional:
+        return None
+    addr, _, adev = _ray_vector(a, name, dtype, rows) if cols is None else _ray_array(a, name, cols, dtype, rows=rows)
+    if adev != dev:
+        raise ValueError("%s must live where %s (both numpy arrays, or both tensors on the GPU)" % (name, anchor))
+    return addr
+
+
+def _device_of(a):
+    """where outputs for the input `a` go: its torch device, None for host memory"""
+    return a.device if _is_tensor(a) else None
+
+
+def _sync(device):
+    """torch's stream on `device` has finished what it was given (inputs, zero fills): the library's stream knows nothing of torch's.  None: host memory, nothing to do"""
+    if device is not None:
+        import torch
+        torch.cuda.current_stream(device).synchronize()
+
+
+def _new_output(shape, dtype, device=None):
+    """A zeroed output of dtype uint32, uint8 or float32: a numpy array, or on a torch device a tensor there (uint32 as torch.int32 holding the same bits)"""
+    if device is None:
+        return np.zeros(shape, dtype)
+    import torch
+    return torch.zeros(shape, dtype={"uint32": torch.int32, "uint8": torch.uint8, "float32": torch.float32}[np.dtype(dtype).name], device=device)
+
+
+def _address(a):
+    return a.data_ptr() if _is_tensor(a) else a.ctypes.data
+
+
+def _output(struct, field, shape, dtype, device, into=None, misplaced=None):
+    """The output `field` of a call: into[field], checked (shape, dtype, contiguous, host or device as `device` says), or with into None a new one.  Its address
+    goes into struct.field; returns the array.  misplaced: the message for an into entry in the wrong place"""
+    if into is None:
+        a = _new_output(shape, dtype, device)
+        addr = _address(a)
+    else:
+        if field not in into:
+            raise ValueError("into: holds no %r" % field)
+        a, label = into[field], "into[%r]" % field
+        if len(shape) == 1:
+            addr, _, adev = _ray_vector(a, label, dtype, shape[0])
+        elif len(shape) == 2 and shape[1] == 3:                             # rows of three: checked as gather and probe_lit_rays always did, the dtype first
+            addr, _, adev = _ray_array(a, label, 3, dtype, rows=shape[0])
+        else:
+            addr, _, adev = _film_array(a, label, shape, dtype)
+        if adev != (device is not None):
+            raise ValueError(misplaced or "into[%r] must live where points live" % field)
+    setattr(struct, field, addr)
+    return a
+
+
+def _rgb_ok(m, want_ok, device):
+    """(rgb, ok, their addresses): the float32 (m, 3) and, with want_ok, uint8 (m,) outputs of a read-out, with _sync behind the zero fills"""
+    rgb, ok = _new_output((m, 3), np.float32, device), _new_output((m,), np.uint8, device) if want_ok else None
+    _sync(device)
+    return rgb, ok, _address(rgb), _address(ok) if want_ok else None
+
+
+def _reconcile_max_distance(max_distance, into, res=None):
+    """max_distance as the f32 value the library takes: finite, > 0, <= 1e12.  into: the dict of the call that is continued (or None): it holds max_distance —
+    with res its depth film's depth_res too — which must agree; a max_distance of None takes into's"""
+    if into is not None:
+        if "max_distance" not in into or (res is not None and "depth_res" not in into):
+            raise ValueError("into: holds no depth film (depth_res, max_distance)" if res is not None else "into: holds no max_distance")
+        if max_distance is None:
+            max_distance = into["max_distance"]
+        same = float(np.float32(into["max_distance"])) == float(np.float32(max_distance))
+        if res is not None and (int(into["depth_res"]) != res or not same):
+            raise ValueError("into: its depth film has res %r and max_distance %r, not %r and %r" % (into["depth_res"], into["max_distance"], res, max_distance))
+        if not same:
+            raise ValueError("into: its survey has max_distance %r, not %r" % (into["max_distance"], max_distance))
+    if max_distance is None:
+        raise ValueError("max_distance: give one (probes.grid_max_distance(grid) is the usual choice)")
+    max_distance = float(np.float32(max_distance))
+    if res is not None and not 2 <= res <= 16:
+        raise ValueError("res: 2 .. 16, not %r" % res)
+    if not (np.isfinite(max_distance) and 0.0 < max_distance <= 1e12):
+        raise ValueError("max_distance: finite, > 0 and <= 1e12, not %r" % max_distance)
+    return max_distance
+
+
 def default_config(width=1024, height=768, **kw):
     cfg = Config()
     lib().mi355rt_default_config(C.byref(cfg))
@@ -979,27 +1087,13 @@ class RayTracer:
         memory and the results come back as numpy arrays; torch tensors on the handle's GPU are read in place (MI355RT_RAYS_DEVICE) and the results are
         tensors on that device.  Returns a dict name -> array: rgb, direct, tuv (n, 3) float32; prim (n,) uint32 (as a tensor: torch.int32 holding the
         same bits, a miss is -1)."""
-        want = tuple(want)
-        if not want or any(w not in RAY_OUTPUTS for w in want) or len(set(want)) != len(want):
-            raise ValueError("want: a non-empty selection of %s without repeats, not %r" % (RAY_OUTPUTS, want))
+        want = _check_want(want, RAY_OUTPUTS)
         addr, n, dev = _ray_array(rays6, "rays6", 6, np.float32)
-        kaddr = None
-        if keys is not None:
-            kaddr, _, kdev = _ray_array(keys, "keys", 2, np.uint32, rows=n)
-            if kdev != dev:
-                raise ValueError("keys must live where rays6 lives (both numpy arrays, or both tensors on the GPU)")
-        res, o = {}, RayOutputs()
-        if dev:
-            import torch
-            torch.cuda.current_stream(rays6.device).synchronize()           # what produced the rays has finished: the library's stream knows nothing of torch's
-            for w in want:
-                res[w] = torch.zeros((n,) if w == "prim" else (n, 3), dtype=torch.int32 if w == "prim" else torch.float32, device=rays6.device)
-                setattr(o, w, res[w].data_ptr())
-            torch.cuda.current_stream(rays6.device).synchronize()           # ... and so has the zero fill
-        else:
-            for w in want:
-                res[w] = np.zeros(n, np.uint32) if w == "prim" else np.zeros((n, 3), np.float32)
-                setattr(o, w, res[w].ctypes.data)
+        kaddr = _input_beside(keys, "keys", np.uint32, n, 2, dev, "rays6 lives")
+        o, device = RayOutputs(), _device_of(rays6)
+        _sync(device)                                                       # what produced the rays has finished
+        res = {w: _output(o, w, (n,) if w == "prim" else (n, 3), np.uint32 if w == "prim" else np.float32, device) for w in want}
+        _sync(device)                                                       # ... and so has the zero fill
         self._check(lib().mi355rt_trace_rays(self._h, addr, kaddr, n, RAYS_DEVICE if dev else RAYS_HOST, C.byref(o)))
         return res
 
@@ -1011,59 +1105,22 @@ class RayTracer:
         tensors there (uint32 as torch.int32 holding the same bits), under trace_rays' rules.  into: the dict of an earlier call; its arrays are added to and
         returned (accumulate): gather(spp=3) then gather(spp=5, first_sample=3, into=res) is gather(spp=8) bit for bit.  `direct` is always overwritten.
         Returns a dict name -> array.  No film, camera or lens state changes."""
-        want = tuple(want)
-        if not want or any(w not in GATHER_OUTPUTS for w in want) or len(set(want)) != len(want):
-            raise ValueError("want: a non-empty selection of %s without repeats, not %r" % (GATHER_OUTPUTS, want))
+        want = _check_want(want, GATHER_OUTPUTS)
         if weight not in GATHER_WEIGHTS:
             raise ValueError("weight: one of %s, not %r" % (tuple(GATHER_WEIGHTS), weight))
         addr, n, dev = _ray_array(points, "points", 3, np.float32)
-        naddr = iaddr = None
-        if normals is not None:
-            naddr, _, ndev = _ray_array(normals, "normals", 3, np.float32, rows=n)
-            if ndev != dev:
-                raise ValueError("normals must live where points live (both numpy arrays, or both tensors on the GPU)")
-        if ids is not None:
-            iaddr, _, idev = _ray_vector(ids, "ids", np.uint32, n)
-            if idev != dev:
-                raise ValueError("ids must live where points live (both numpy arrays, or both tensors on the GPU)")
+        naddr = _input_beside(normals, "normals", np.float32, n, 3, dev, "points live")
+        iaddr = _input_beside(ids, "ids", np.uint32, n, None, dev, "points live")
         cfg = GatherConfig()
         lib().mi355rt_gather_default_config(C.byref(cfg))
         cfg.spp, cfg.first_sample, cfg.weight, cfg.accumulate, cfg.near_distance = int(spp), int(first_sample), GATHER_WEIGHTS[weight], 1 if into is not None else 0, float(near_distance)
-        res, o = {}, GatherOutputs()
-        if dev:
-            import torch
+        res, o, device = {}, GatherOutputs(), _device_of(points)
         for w in want:
-            cols = 3 if w in ("sum", "sumsq", "direct") else 1
-            if into is not None and w != "direct":
-                if w not in into:
-                    raise ValueError("into: holds no %r" % w)
-                a = into[w]
-                a_addr, _, adev = _ray_array(a, "into[%r]" % w, 3, np.float32, rows=n) if cols == 3 else _ray_vector(a, "into[%r]" % w, np.uint32, n)
-                if adev != dev:
-                    raise ValueError("into[%r] must live where points live" % w)
-            elif dev:
-                a = torch.zeros((n, 3) if cols == 3 else (n,), dtype=torch.float32 if cols == 3 else torch.int32, device=points.device)
-                a_addr = a.data_ptr()
-            else:
-                a = np.zeros((n, 3), np.float32) if cols == 3 else np.zeros(n, np.uint32)
-                a_addr = a.ctypes.data
-            res[w] = a
-            setattr(o, w, a_addr)
-        if dev:
-            torch.cuda.current_stream(points.device).synchronize()          # what produced the inputs (and the zero fill) has finished: the library's stream knows nothing of torch's
+            f32 = w in ("sum", "sumsq", "direct")
+            res[w] = _output(o, w, (n, 3) if f32 else (n,), np.float32 if f32 else np.uint32, device, None if w == "direct" else into)
+        _sync(device)                                                       # what produced the inputs (and the zero fill) has finished
         self._check(lib().mi355rt_gather(self._h, addr, naddr, iaddr, n, C.byref(cfg), RAYS_DEVICE if dev else RAYS_HOST, C.byref(o)))
         return res
-
-    @staticmethod
-    def _sh_array(a, name, rows):
-        """_ray_array for a (rows, 9, 3) float32 argument: checked as the (rows, 27) view of the same memory"""
-        if (_is_tensor(a) or isinstance(a, np.ndarray)) and len(a.shape) == 3 and tuple(a.shape) == (rows, 9, 3):
-            if not (a.is_contiguous() if _is_tensor(a) else a.flags["C_CONTIGUOUS"]):
-                raise ValueError("%s: must be C-contiguous" % name)                 # before the reshape, which would copy
-            return _ray_array(a.reshape(rows, 27), name, 27, np.float32, rows=rows)
-        if _is_tensor(a) or isinstance(a, np.ndarray):
-            raise ValueError("%s: shape must be (%d, 9, 3), not %s" % (name, rows, tuple(a.shape)))
-        raise TypeError("%s: a numpy array or a torch tensor, not %s" % (name, type(a).__name__))
 
     def probes_gather(self, points, ids=None, spp=64, first_sample=0, near_distance=float("inf"), want=("n", "sh"), into=None):
         """mi355rt_probes_gather: the light arriving at probes from the whole sphere, projected onto the nine real spherical harmonics up to band 2
@@ -1071,39 +1128,15 @@ class RayTracer:
         points' random numbers, None: i; want: any of "n", "hits", "near", "sh" (float32 (n, 9, 3) sums).  numpy arrays or torch tensors on the handle's GPU,
         under gather's rules.  into: the dict of an earlier call; its arrays are added to and returned: probes_gather(spp=3) then probes_gather(spp=5,
         first_sample=3, into=res) is probes_gather(spp=8) bit for bit.  Returns a dict name -> array.  No film, camera or lens state changes."""
-        want = tuple(want)
-        if not want or any(w not in PROBE_OUTPUTS for w in want) or len(set(want)) != len(want):
-            raise ValueError("want: a non-empty selection of %s without repeats, not %r" % (PROBE_OUTPUTS, want))
+        want = _check_want(want, PROBE_OUTPUTS)
         addr, n, dev = _ray_array(points, "points", 3, np.float32)
-        iaddr = None
-        if ids is not None:
-            iaddr, _, idev = _ray_vector(ids, "ids", np.uint32, n)
-            if idev != dev:
-                raise ValueError("ids must live where points live (both numpy arrays, or both tensors on the GPU)")
+        iaddr = _input_beside(ids, "ids", np.uint32, n, None, dev, "points live")
         cfg = ProbeConfig()
         lib().mi355rt_probes_default_config(C.byref(cfg))
         cfg.spp, cfg.first_sample, cfg.accumulate, cfg.near_distance = int(spp), int(first_sample), 1 if into is not None else 0, float(near_distance)
-        res, o = {}, ProbeOutputs()
-        if dev:
-            import torch
-        for w in want:
-            if into is not None:
-                if w not in into:
-                    raise ValueError("into: holds no %r" % w)
-                a = into[w]
-                a_addr, _, adev = self._sh_array(a, "into[%r]" % w, n) if w == "sh" else _ray_vector(a, "into[%r]" % w, np.uint32, n)
-                if adev != dev:
-                    raise ValueError("into[%r] must live where points live" % w)
-            elif dev:
-                a = torch.zeros((n, 9, 3) if w == "sh" else (n,), dtype=torch.float32 if w == "sh" else torch.int32, device=points.device)
-                a_addr = a.data_ptr()
-            else:
-                a = np.zeros((n, 9, 3), np.float32) if w == "sh" else np.zeros(n, np.uint32)
-                a_addr = a.ctypes.data
-            res[w] = a
-            setattr(o, w, a_addr)
-        if dev:
-            torch.cuda.current_stream(points.device).synchronize()          # what produced the inputs (and the zero fill) has finished: the library's stream knows nothing of torch's
+        o, device = ProbeOutputs(), _device_of(points)
+        res = {w: _output(o, w, (n, 9, 3) if w == "sh" else (n,), np.float32 if w == "sh" else np.uint32, device, into) for w in want}
+        _sync(device)                                                       # what produced the inputs (and the zero fill) has finished
         self._check(lib().mi355rt_probes_gather(self._h, addr, iaddr, n, C.byref(cfg), RAYS_DEVICE if dev else RAYS_HOST, C.byref(o)))
         return res
 
@@ -1113,41 +1146,52 @@ class RayTracer:
         returns them at probes.grid_points(grid); points, dirs: float32 (m, 3); mode "irradiance" (dirs are normals) or "radiance" (arriving from dirs);
         usable: uint8 (nprobes,) or None.  numpy arrays or torch tensors on the handle's GPU, all alike.  Returns rgb float32 (m, 3), with want_ok
         (rgb, ok uint8 (m,)): ok 0 and rgb 0 where no probe around the point could be used.  Nothing is clamped."""
+        return self._lookup("probes_lookup", grid, res, points, dirs, mode, usable, want_ok)
+
+    def _lookup(self, entry, grid, res, points, dirs, mode, usable, want_ok, normals=None, weights=None, offsets=None):
+        """The one body of probes_lookup, probes_lookup_vis and probes_lookup_placed; entry names which, and the call ends in the library entry of that name.
+        weights: (chebyshev, facing, normal_bias) for the two that read depth films, which res then holds; offsets: probes_lookup_placed's."""
+        weighted, placed = weights is not None, entry == "probes_lookup_placed"
         if mode not in SH_MODES:
             raise ValueError("mode: one of %s, not %r" % (tuple(SH_MODES), mode))
+        for k in ("n", "sh", "count", "moments", "depth_res", "max_distance") if weighted else ():
+            if k not in res:
+                raise ValueError("res: holds no %r (probes_gather_depth returns it)" % k)
         g = grid if isinstance(grid, ProbeGrid) else ProbeGrid.from_dict(grid)
         nprobes = int(g.counts[0]) * int(g.counts[1]) * int(g.counts[2])
+        R = int(res["depth_res"]) if weighted else 0
+        if weighted and not 2 <= R <= 16:
+            raise ValueError('res["depth_res"]: 2 .. 16, not %r' % R)
         addr, m, dev = _ray_array(points, "points", 3, np.float32)
         daddr, _, ddev = _ray_array(dirs, "dirs", 3, np.float32, rows=m)
         naddr, _, ndev = _ray_vector(res["n"], 'res["n"]', np.uint32, nprobes)
-        saddr, _, sdev = self._sh_array(res["sh"], 'res["sh"]', nprobes)
-        uaddr, udev = None, dev
+        saddr, _, sdev = _film_array(res["sh"], 'res["sh"]', (nprobes, 9, 3), np.float32)
+        uaddr = nraddr = oaddr = None
+        devs, films = {dev, ddev, ndev, sdev}, []
+        if weighted:
+            caddr, _, cdev = _film_array(res["count"], 'res["count"]', (nprobes, R * R), np.uint32)
+            maddr, _, mdev = _film_array(res["moments"], 'res["moments"]', (nprobes, R * R, 2), np.float32)
+            devs |= {cdev, mdev}
         if usable is not None:
             uaddr, _, udev = _ray_vector(usable, "usable", np.uint8, nprobes)
-        if not (ddev == ndev == sdev == udev == dev):
-            raise ValueError("dirs, res and usable must live where points live (all numpy arrays, or all tensors on the GPU)")
-        if dev:
-            import torch
-            rgb = torch.zeros((m, 3), dtype=torch.float32, device=points.device); ok = torch.zeros(m, dtype=torch.uint8, device=points.device) if want_ok else None
-            raddr, oaddr = rgb.data_ptr(), ok.data_ptr() if want_ok else None
-            torch.cuda.current_stream(points.device).synchronize()
-        else:
-            rgb = np.zeros((m, 3), np.float32); ok = np.zeros(m, np.uint8) if want_ok else None
-            raddr, oaddr = rgb.ctypes.data, ok.ctypes.data if want_ok else None
-        self._check(lib().mi355rt_probes_lookup(self._h, C.byref(g), naddr, saddr, uaddr, addr, daddr, m, SH_MODES[mode], RAYS_DEVICE if dev else RAYS_HOST, raddr, oaddr))
+            devs.add(udev)
+        if normals is not None:
+            nraddr, _, nrdev = _ray_array(normals, "normals", 3, np.float32, rows=m)
+            devs.add(nrdev)
+        if offsets is not None:
+            oaddr, _, odev = _ray_array(offsets, "offsets", 3, np.float32, rows=nprobes)
+            devs.add(odev)
+        if len(devs) != 1:
+            names = ["dirs"] + ["normals"] * weighted + ["res", "usable"] + ["offsets"] * placed
+            raise ValueError("%s and %s must live where points live (all numpy arrays, or all tensors on the GPU)" % (", ".join(names[:-1]), names[-1]))
+        if weighted:
+            d = ProbeDepth(R, float(np.float32(res["max_distance"])), caddr, maddr)
+            vc = ProbeVisConfig((VIS_CHEBYSHEV if weights[0] else 0) | (VIS_FACING if weights[1] and normals is not None else 0), float(weights[2]))
+            films = [C.byref(d), C.byref(vc)]
+        rgb, ok, raddr, okaddr = _rgb_ok(m, want_ok, _device_of(points))
+        args = [self._h, C.byref(g), naddr, saddr, uaddr] + films + [oaddr] * placed + [addr, daddr] + [nraddr] * weighted
+        self._check(getattr(lib(), "mi355rt_" + entry)(*args, m, SH_MODES[mode], RAYS_DEVICE if dev else RAYS_HOST, raddr, okaddr))
         return (rgb, ok) if want_ok else rgb
-
-    @staticmethod
-    def _film_array(a, name, shape, dtype):
-        """_ray_array for an argument of exactly this shape (rows, ...): checked as the (rows, rest) view of the same memory"""
-        if not (_is_tensor(a) or isinstance(a, np.ndarray)):
-            raise TypeError("%s: a numpy array or a torch tensor, not %s" % (name, type(a).__name__))
-        if tuple(a.shape) != tuple(shape):
-            raise ValueError("%s: shape must be %s, not %s" % (name, tuple(shape), tuple(a.shape)))
-        if not (a.is_contiguous() if _is_tensor(a) else a.flags["C_CONTIGUOUS"]):
-            raise ValueError("%s: must be C-contiguous" % name)                 # before the reshape, which would copy
-        rest = int(np.prod(shape[1:], dtype=np.int64))
-        return _ray_array(a.reshape(shape[0], rest), name, rest, dtype, rows=shape[0])
 
     def probes_gather_depth(self, points, ids=None, spp=64, first_sample=0, near_distance=float("inf"), res=8, max_distance=None,
                             want=("n", "sh", "count", "moments"), into=None):
@@ -1158,61 +1202,23 @@ class RayTracer:
         arrays or torch tensors on the handle's GPU, under probes_gather's rules.  into: the dict of an earlier call with the same res and max_distance; its
         arrays are added to and returned.  Returns a dict name -> array, with "depth_res" and "max_distance" when it holds a depth film.  No film, camera or
         lens state changes."""
-        want = tuple(want)
-        if not want or any(w not in PROBE_DEPTH_OUTPUTS for w in want) or len(set(want)) != len(want):
-            raise ValueError("want: a non-empty selection of %s without repeats, not %r" % (PROBE_DEPTH_OUTPUTS, want))
+        want = _check_want(want, PROBE_DEPTH_OUTPUTS)
         if ("count" in want) != ("moments" in want):
             raise ValueError('want: "count" and "moments" come together')
         if "count" not in want:
             return self.probes_gather(points, ids, spp, first_sample, near_distance, want, into)
         res = int(res)
-        if into is not None:
-            if "depth_res" not in into or "max_distance" not in into:
-                raise ValueError("into: holds no depth film (depth_res, max_distance)")
-            if max_distance is None:
-                max_distance = into["max_distance"]
-            if int(into["depth_res"]) != res or float(np.float32(into["max_distance"])) != float(np.float32(max_distance)):
-                raise ValueError("into: its depth film has res %r and max_distance %r, not %r and %r" % (into["depth_res"], into["max_distance"], res, max_distance))
-        if max_distance is None:
-            raise ValueError("max_distance: give one (probes.grid_max_distance(grid) is the usual choice)")
-        max_distance = float(np.float32(max_distance))
-        if not 2 <= res <= 16:
-            raise ValueError("res: 2 .. 16, not %r" % res)
-        if not (np.isfinite(max_distance) and 0.0 < max_distance <= 1e12):
-            raise ValueError("max_distance: finite, > 0 and <= 1e12, not %r" % max_distance)
+        max_distance = _reconcile_max_distance(max_distance, into, res)
         addr, n, dev = _ray_array(points, "points", 3, np.float32)
-        iaddr = None
-        if ids is not None:
-            iaddr, _, idev = _ray_vector(ids, "ids", np.uint32, n)
-            if idev != dev:
-                raise ValueError("ids must live where points live (both numpy arrays, or both tensors on the GPU)")
+        iaddr = _input_beside(ids, "ids", np.uint32, n, None, dev, "points live")
         cfg = ProbeConfig()
         lib().mi355rt_probes_default_config(C.byref(cfg))
         cfg.spp, cfg.first_sample, cfg.accumulate, cfg.near_distance = int(spp), int(first_sample), 1 if into is not None else 0, float(near_distance)
         shapes = {"sh": (n, 9, 3), "count": (n, res * res), "moments": (n, res * res, 2)}
-        out, o, d = {}, ProbeOutputs(), ProbeDepth(res, max_distance, None, None)
-        if dev:
-            import torch
-        for w in want:
-            shape, f32 = shapes.get(w, (n,)), w in ("sh", "moments")
-            if into is not None:
-                if w not in into:
-                    raise ValueError("into: holds no %r" % w)
-                a = into[w]
-                a_addr, _, adev = self._film_array(a, "into[%r]" % w, shape, np.float32 if f32 else np.uint32) if len(shape) > 1 else _ray_vector(a, "into[%r]" % w, np.uint32, n)
-                if adev != dev:
-                    raise ValueError("into[%r] must live where points live" % w)
-            elif dev:
-                a = torch.zeros(shape, dtype=torch.float32 if f32 else torch.int32, device=points.device)
-                a_addr = a.data_ptr()
-            else:
-                a = np.zeros(shape, np.float32 if f32 else np.uint32)
-                a_addr = a.ctypes.data
-            out[w] = a
-            setattr(d if w in ("count", "moments") else o, w, a_addr)
+        o, d, device = ProbeOutputs(), ProbeDepth(res, max_distance, None, None), _device_of(points)
+        out = {w: _output(d if w in ("count", "moments") else o, w, shapes.get(w, (n,)), np.float32 if w in ("sh", "moments") else np.uint32, device, into) for w in want}
         out["depth_res"], out["max_distance"] = res, max_distance
-        if dev:
-            torch.cuda.current_stream(points.device).synchronize()          # what produced the inputs (and the zero fill) has finished: the library's stream knows nothing of torch's
+        _sync(device)                                                       # what produced the inputs (and the zero fill) has finished
         only_depth = all(w in ("count", "moments") for w in want)
         self._check(lib().mi355rt_probes_gather_depth(self._h, addr, iaddr, n, C.byref(cfg), RAYS_DEVICE if dev else RAYS_HOST, None if only_depth else C.byref(o), C.byref(d)))
         return out
@@ -1224,42 +1230,7 @@ class RayTracer:
         of the surface at the points, or None: then facing has no effect and normal_bias must be 0.  With chebyshev=False, facing=False and normal_bias=0 the
         result is probes_lookup's on every bit.  numpy arrays or torch tensors on the handle's GPU, all alike.  Returns rgb float32 (m, 3), with want_ok
         (rgb, ok uint8 (m,))."""
-        if mode not in SH_MODES:
-            raise ValueError("mode: one of %s, not %r" % (tuple(SH_MODES), mode))
-        for k in ("n", "sh", "count", "moments", "depth_res", "max_distance"):
-            if k not in res:
-                raise ValueError("res: holds no %r (probes_gather_depth returns it)" % k)
-        g = grid if isinstance(grid, ProbeGrid) else ProbeGrid.from_dict(grid)
-        nprobes = int(g.counts[0]) * int(g.counts[1]) * int(g.counts[2])
-        R = int(res["depth_res"])
-        if not 2 <= R <= 16:
-            raise ValueError('res["depth_res"]: 2 .. 16, not %r' % R)
-        addr, m, dev = _ray_array(points, "points", 3, np.float32)
-        daddr, _, ddev = _ray_array(dirs, "dirs", 3, np.float32, rows=m)
-        naddr, _, ndev = _ray_vector(res["n"], 'res["n"]', np.uint32, nprobes)
-        saddr, _, sdev = self._sh_array(res["sh"], 'res["sh"]', nprobes)
-        caddr, _, cdev = self._film_array(res["count"], 'res["count"]', (nprobes, R * R), np.uint32)
-        maddr, _, mdev = self._film_array(res["moments"], 'res["moments"]', (nprobes, R * R, 2), np.float32)
-        uaddr, udev, nraddr, nrdev = None, dev, None, dev
-        if usable is not None:
-            uaddr, _, udev = _ray_vector(usable, "usable", np.uint8, nprobes)
-        if normals is not None:
-            nraddr, _, nrdev = _ray_array(normals, "normals", 3, np.float32, rows=m)
-        if not (ddev == ndev == sdev == cdev == mdev == udev == nrdev == dev):
-            raise ValueError("dirs, normals, res and usable must live where points live (all numpy arrays, or all tensors on the GPU)")
-        d = ProbeDepth(R, float(np.float32(res["max_distance"])), caddr, maddr)
-        vc = ProbeVisConfig((VIS_CHEBYSHEV if chebyshev else 0) | (VIS_FACING if facing and normals is not None else 0), float(normal_bias))
-        if dev:
-            import torch
-            rgb = torch.zeros((m, 3), dtype=torch.float32, device=points.device); ok = torch.zeros(m, dtype=torch.uint8, device=points.device) if want_ok else None
-            raddr, oaddr = rgb.data_ptr(), ok.data_ptr() if want_ok else None
-            torch.cuda.current_stream(points.device).synchronize()
-        else:
-            rgb = np.zeros((m, 3), np.float32); ok = np.zeros(m, np.uint8) if want_ok else None
-            raddr, oaddr = rgb.ctypes.data, ok.ctypes.data if want_ok else None
-        self._check(lib().mi355rt_probes_lookup_vis(self._h, C.byref(g), naddr, saddr, uaddr, C.byref(d), C.byref(vc), addr, daddr, nraddr, m, SH_MODES[mode],
-                                                    RAYS_DEVICE if dev else RAYS_HOST, raddr, oaddr))
-        return (rgb, ok) if want_ok else rgb
+        return self._lookup("probes_lookup_vis", grid, res, points, dirs, mode, usable, want_ok, normals=normals, weights=(chebyshev, facing, normal_bias))
 
     def bake_texels(self, uv, width, height, flip=False, want=BAKE_TEXEL_OUTPUTS):
         """mi355rt_bake_texels: the UV charts of the scene's triangles rasterised into an atlas of width x height texels (raytracer_rs_amd.bake.texels is the
@@ -1269,9 +1240,7 @@ class RayTracer:
         index covering the texel's centre or 0xFFFFFFFF; bary float32 (width * height, 2), 0 where uncovered; the compact lists of the covered texels in
         ascending texel index, ids uint32 (n,) (the texel index: the key gather should sample under), points / normals / albedo float32 (n, 3); "ncovered".
         No film, camera or lens state changes."""
-        want = tuple(want)
-        if any(w not in BAKE_TEXEL_OUTPUTS for w in want) or len(set(want)) != len(want):
-            raise ValueError("want: a selection of %s without repeats, not %r" % (BAKE_TEXEL_OUTPUTS, want))
+        want = _check_want(want, BAKE_TEXEL_OUTPUTS, empty_ok=True)
         width, height = int(width), int(height)
         if not (1 <= width <= 16384 and 1 <= height <= 16384):
             raise ValueError("width and height must be 1 .. 16384")
@@ -1286,20 +1255,9 @@ class RayTracer:
         nt = width * height
         shapes = {"owner": ((nt,), np.uint32), "bary": ((nt, 2), np.float32), "ids": ((nt,), np.uint32), "points": ((nt, 3), np.float32),
                   "normals": ((nt, 3), np.float32), "albedo": ((nt, 3), np.float32)}
-        res, o = {}, BakeTexelOutputs()
-        if dev:
-            import torch
-        for w in want:
-            shape, dt = shapes[w]
-            if dev:
-                a = torch.zeros(shape, dtype=torch.float32 if dt == np.float32 else torch.int32, device=uv.device)
-                setattr(o, w, a.data_ptr())
-            else:
-                a = np.zeros(shape, dt)
-                setattr(o, w, a.ctypes.data)
-            res[w] = a
-        if dev:
-            torch.cuda.current_stream(uv.device).synchronize()          # what produced uv (and the zero fill) has finished: the library's stream knows nothing of torch's
+        o, device = BakeTexelOutputs(), _device_of(uv)
+        res = {w: _output(o, w, shapes[w][0], shapes[w][1], device) for w in want}
+        _sync(device)                                                       # what produced uv (and the zero fill) has finished
         n = C.c_uint32(0)
         self._check(lib().mi355rt_bake_texels(self._h, addr, width, height, 1 if flip else 0, RAYS_DEVICE if dev else RAYS_HOST, C.byref(o), C.byref(n)))
         for w in ("ids", "points", "normals", "albedo"):
@@ -1319,18 +1277,8 @@ class RayTracer:
         if not 0 <= dilate <= 0xFFFFFFFF:
             raise ValueError("dilate must be 0 .. 2^32 - 1")
         vaddr, n, dev = _ray_array(values, "values", 3, np.float32)
-        iaddr, _, idev = _ray_vector(ids, "ids", np.uint32, n)
-        if idev != dev:
-            raise ValueError("ids must live where values live (both numpy arrays, or both tensors on the GPU)")
-        nt = width * height
-        if dev:
-            import torch
-            atlas = torch.zeros((nt, 3), dtype=torch.float32, device=values.device); valid = torch.zeros(nt, dtype=torch.uint8, device=values.device)
-            aaddr, daddr = atlas.data_ptr(), valid.data_ptr()
-            torch.cuda.current_stream(values.device).synchronize()
-        else:
-            atlas = np.zeros((nt, 3), np.float32); valid = np.zeros(nt, np.uint8)
-            aaddr, daddr = atlas.ctypes.data, valid.ctypes.data
+        iaddr = _input_beside(ids, "ids", np.uint32, n, None, dev, "values live", optional=False)
+        atlas, valid, aaddr, daddr = _rgb_ok(width * height, True, _device_of(values))
         self._check(lib().mi355rt_bake_atlas(self._h, iaddr, vaddr, n, width, height, dilate, RAYS_DEVICE if dev else RAYS_HOST, aaddr, daddr))
         return atlas, valid
 
@@ -1399,15 +1347,13 @@ class RayTracer:
         if spp < 1:
             raise ValueError("spp must be >= 1")
         n = self.width * self.height * spp
-        if device is False or device is None:
-            out = np.zeros((n, 6), np.float32)
-            self._check(lib().mi355rt_lens_rays(self._h, spp, RAYS_HOST, out.ctypes.data, n))
-            return out
-        import torch
-        dev = torch.device("cuda", self.device_index) if device is True else torch.device(device)
-        out = torch.zeros((n, 6), dtype=torch.float32, device=dev)
-        torch.cuda.current_stream(dev).synchronize()           # the zero fill has finished: the library's stream knows nothing of torch's
-        self._check(lib().mi355rt_lens_rays(self._h, spp, RAYS_DEVICE, out.data_ptr(), n))
+        dev = None
+        if not (device is False or device is None):
+            import torch
+            dev = torch.device("cuda", self.device_index) if device is True else torch.device(device)
+        out = _new_output((n, 6), np.float32, dev)
+        _sync(dev)                                                          # the zero fill has finished
+        self._check(lib().mi355rt_lens_rays(self._h, spp, RAYS_HOST if dev is None else RAYS_DEVICE, _address(out), n))
         return out
 
     def occluded_rays(self, rays6):
@@ -1746,24 +1692,9 @@ def _probes_survey(self, points, ids=None, spp=64, first_sample=0, max_distance=
     handle's GPU, under probes_gather's rules.  into: the dict of an earlier call with the same max_distance; its arrays are continued and returned:
     probes_survey(spp=3) then probes_survey(spp=5, first_sample=3, into=res) is probes_survey(spp=8) bit for bit.  Returns a dict name -> array, with
     "max_distance".  Only closest hits are traced: last_counts() reports n * spp primary rays, no bounce and no shadow ray."""
-    if into is not None:
-        if "max_distance" not in into:
-            raise ValueError("into: holds no max_distance")
-        if max_distance is None:
-            max_distance = into["max_distance"]
-        if float(np.float32(into["max_distance"])) != float(np.float32(max_distance)):
-            raise ValueError("into: its survey has max_distance %r, not %r" % (into["max_distance"], max_distance))
-    if max_distance is None:
-        raise ValueError("max_distance: give one (probes.grid_max_distance(grid) is the usual choice)")
-    max_distance = float(np.float32(max_distance))
-    if not (np.isfinite(max_distance) and 0.0 < max_distance <= 1e12):
-        raise ValueError("max_distance: finite, > 0 and <= 1e12, not %r" % max_distance)
+    max_distance = _reconcile_max_distance(max_distance, into)
     addr, n, dev = _ray_array(points, "points", 3, np.float32)
-    iaddr = None
-    if ids is not None:
-        iaddr, _, idev = _ray_vector(ids, "ids", np.uint32, n)
-        if idev != dev:
-            raise ValueError("ids must live where points live (both numpy arrays, or both tensors on the GPU)")
+    iaddr = _input_beside(ids, "ids", np.uint32, n, None, dev, "points live")
     cfg = ProbeSurveyConfig()
     lib().mi355rt_probes_survey_default_config(C.byref(cfg))
     cfg.spp, cfg.first_sample, cfg.accumulate, cfg.flags, cfg.max_distance = int(spp), int(first_sample), 1 if into is not None else 0, SURVEY_FLIP if flip else 0, max_distance
@@ -1773,17 +1704,10 @@ def _probes_survey(self, points, ids=None, spp=64, first_sample=0, max_distance=
             raise ValueError("into must live where points live")
         out = {k: into[k] for k in PROBE_SURVEY_OUTPUTS}
     else:
-        out, o = {}, ProbeSurvey()
-        if dev:
-            import torch
-        for k in PROBE_SURVEY_OUTPUTS:
-            shape, f32 = ((n,), False) if k in ("n", "back", "front") else ((n, 4), True)
-            out[k] = torch.zeros(shape, dtype=torch.float32 if f32 else torch.int32, device=points.device) if dev else np.zeros(shape, np.float32 if f32 else np.uint32)
-            setattr(o, k, out[k].data_ptr() if dev else out[k].ctypes.data)
+        o = ProbeSurvey()
+        out = {k: _output(o, k, *(((n,), np.uint32) if k in ("n", "back", "front") else ((n, 4), np.float32)), _device_of(points)) for k in PROBE_SURVEY_OUTPUTS}
     out["max_distance"] = max_distance
-    if dev:
-        import torch
-        torch.cuda.current_stream(points.device).synchronize()          # what produced the inputs (and the zero fill) has finished: the library's stream knows nothing of torch's
+    _sync(_device_of(points))                                           # what produced the inputs (and the zero fill) has finished
     self._check(lib().mi355rt_probes_survey(self._h, addr, iaddr, n, C.byref(cfg), RAYS_DEVICE if dev else RAYS_HOST, C.byref(o)))
     return out
 
@@ -1793,9 +1717,7 @@ def _probes_place(self, grid, survey, offsets=None, back_share=0.25, max_offset=
     traces nothing.  survey: the dict probes_survey returned at probes.grid_points(grid) + offsets; offsets: float32 (nprobes, 3) or None (zero); min_front: a
     length, None: probes.grid_min_front(grid); want: any of "offsets" (float32 (nprobes, 3), new arrays), "verdict" (uint8, PLACE_*), "state" (uint8, PROBE_*).
     numpy arrays or torch tensors on the handle's GPU, all alike.  Returns a tuple in the order of want."""
-    want = tuple(want)
-    if not want or any(w not in PROBE_PLACE_OUTPUTS for w in want) or len(set(want)) != len(want):
-        raise ValueError("want: a non-empty selection of %s without repeats, not %r" % (PROBE_PLACE_OUTPUTS, want))
+    want = _check_want(want, PROBE_PLACE_OUTPUTS)
     g = grid if isinstance(grid, ProbeGrid) else ProbeGrid.from_dict(grid)
     nprobes = int(g.counts[0]) * int(g.counts[1]) * int(g.counts[2])
     s, dev = _survey_pointers(survey, nprobes, "survey")
@@ -1810,16 +1732,10 @@ def _probes_place(self, grid, survey, offsets=None, back_share=0.25, max_offset=
     cfg = ProbePlaceConfig()
     lib().mi355rt_probes_place_default_config(C.byref(cfg))
     cfg.back_share, cfg.max_offset, cfg.min_front, cfg.max_distance = float(back_share), float(max_offset), float(min_front), float(np.float32(survey.get("max_distance", 0.0)))
-    res, addrs = {}, dict.fromkeys(PROBE_PLACE_OUTPUTS)
-    if dev:
-        import torch
-        where = survey["n"].device
-    for w in want:
-        shape, f32 = ((nprobes, 3), True) if w == "offsets" else ((nprobes,), False)
-        res[w] = torch.zeros(shape, dtype=torch.float32 if f32 else torch.uint8, device=where) if dev else np.zeros(shape, np.float32 if f32 else np.uint8)
-        addrs[w] = res[w].data_ptr() if dev else res[w].ctypes.data
-    if dev:
-        torch.cuda.current_stream(where).synchronize()
+    device = _device_of(survey["n"])
+    res = {w: _new_output(*(((nprobes, 3), np.float32) if w == "offsets" else ((nprobes,), np.uint8)), device) for w in want}
+    addrs = {w: _address(res[w]) if w in res else None for w in PROBE_PLACE_OUTPUTS}
+    _sync(device)
     self._check(lib().mi355rt_probes_place(self._h, C.byref(g), C.byref(s), C.byref(cfg), oaddr, RAYS_DEVICE if dev else RAYS_HOST, addrs["offsets"], addrs["verdict"],
                                            addrs["state"]))
     return tuple(res[w] for w in want)
@@ -1830,44 +1746,7 @@ def _probes_lookup_placed(self, grid, res, points, dirs, normals=None, mode="irr
     """mi355rt_probes_lookup_placed: probes_lookup_vis for probes that have moved (raytracer_rs_amd.probes.lookup_placed is the statement); traces nothing.
     offsets: float32 (nprobes, 3), the probes' offsets from their grid points, under which `res` was gathered; None: probes_lookup_vis on every bit.  The
     weights use the moved positions, the cell and the trilinear factor the grid.  Everything else as probes_lookup_vis."""
-    if mode not in SH_MODES:
-        raise ValueError("mode: one of %s, not %r" % (tuple(SH_MODES), mode))
-    for k in ("n", "sh", "count", "moments", "depth_res", "max_distance"):
-        if k not in res:
-            raise ValueError("res: holds no %r (probes_gather_depth returns it)" % k)
-    g = grid if isinstance(grid, ProbeGrid) else ProbeGrid.from_dict(grid)
-    nprobes = int(g.counts[0]) * int(g.counts[1]) * int(g.counts[2])
-    R = int(res["depth_res"])
-    if not 2 <= R <= 16:
-        raise ValueError('res["depth_res"]: 2 .. 16, not %r' % R)
-    addr, m, dev = _ray_array(points, "points", 3, np.float32)
-    daddr, _, ddev = _ray_array(dirs, "dirs", 3, np.float32, rows=m)
-    naddr, _, ndev = _ray_vector(res["n"], 'res["n"]', np.uint32, nprobes)
-    saddr, _, sdev = self._sh_array(res["sh"], 'res["sh"]', nprobes)
-    caddr, _, cdev = self._film_array(res["count"], 'res["count"]', (nprobes, R * R), np.uint32)
-    maddr, _, mdev = self._film_array(res["moments"], 'res["moments"]', (nprobes, R * R, 2), np.float32)
-    uaddr, udev, nraddr, nrdev, oaddr, odev = None, dev, None, dev, None, dev
-    if usable is not None:
-        uaddr, _, udev = _ray_vector(usable, "usable", np.uint8, nprobes)
-    if normals is not None:
-        nraddr, _, nrdev = _ray_array(normals, "normals", 3, np.float32, rows=m)
-    if offsets is not None:
-        oaddr, _, odev = _ray_array(offsets, "offsets", 3, np.float32, rows=nprobes)
-    if not (ddev == ndev == sdev == cdev == mdev == udev == nrdev == odev == dev):
-        raise ValueError("dirs, normals, res, usable and offsets must live where points live (all numpy arrays, or all tensors on the GPU)")
-    d = ProbeDepth(R, float(np.float32(res["max_distance"])), caddr, maddr)
-    vc = ProbeVisConfig((VIS_CHEBYSHEV if chebyshev else 0) | (VIS_FACING if facing and normals is not None else 0), float(normal_bias))
-    if dev:
-        import torch
-        rgb = torch.zeros((m, 3), dtype=torch.float32, device=points.device); ok = torch.zeros(m, dtype=torch.uint8, device=points.device) if want_ok else None
-        raddr, okaddr = rgb.data_ptr(), ok.data_ptr() if want_ok else None
-        torch.cuda.current_stream(points.device).synchronize()
-    else:
-        rgb = np.zeros((m, 3), np.float32); ok = np.zeros(m, np.uint8) if want_ok else None
-        raddr, okaddr = rgb.ctypes.data, ok.ctypes.data if want_ok else None
-    self._check(lib().mi355rt_probes_lookup_placed(self._h, C.byref(g), naddr, saddr, uaddr, C.byref(d), C.byref(vc), oaddr, addr, daddr, nraddr, m, SH_MODES[mode],
-                                                   RAYS_DEVICE if dev else RAYS_HOST, raddr, okaddr))
-    return (rgb, ok) if want_ok else rgb
+    return self._lookup("probes_lookup_placed", grid, res, points, dirs, mode, usable, want_ok, normals=normals, weights=(chebyshev, facing, normal_bias), offsets=offsets)
 
 
 def _probes_relocate(self, grid, rounds=4, spp=64, **kw):
@@ -1917,7 +1796,7 @@ def _probe_volume(self, vol):
     v.grid = C.pointer(g)
     v.n, _, dev = _ray_vector(vol["n"], 'volume["n"]', np.uint32, nprobes)
     devs.append(dev)
-    v.sh, _, dev = self._sh_array(vol["sh"], 'volume["sh"]', nprobes)
+    v.sh, _, dev = _film_array(vol["sh"], 'volume["sh"]', (nprobes, 9, 3), np.float32)
     devs.append(dev)
     if vol["usable"] is not None:
         v.usable, _, dev = _ray_vector(vol["usable"], 'volume["usable"]', np.uint8, nprobes)
@@ -1930,9 +1809,9 @@ def _probe_volume(self, vol):
         R = int(depth["res"])
         if not 2 <= R <= 16:
             raise ValueError('volume["depth"]["res"]: 2 .. 16, not %r' % R)
-        caddr, _, dev = self._film_array(depth["count"], 'volume["depth"]["count"]', (nprobes, R * R), np.uint32)
+        caddr, _, dev = _film_array(depth["count"], 'volume["depth"]["count"]', (nprobes, R * R), np.uint32)
         devs.append(dev)
-        maddr, _, dev = self._film_array(depth["moments"], 'volume["depth"]["moments"]', (nprobes, R * R, 2), np.float32)
+        maddr, _, dev = _film_array(depth["moments"], 'volume["depth"]["moments"]', (nprobes, R * R, 2), np.float32)
         devs.append(dev)
         d = ProbeDepth(R, float(np.float32(depth.get("max_distance", 1.0))), caddr, maddr)
         vc = ProbeVisConfig((VIS_CHEBYSHEV if vol["chebyshev"] else 0) | (VIS_FACING if vol["facing"] else 0), float(vol["normal_bias"]))
@@ -1956,14 +1835,7 @@ def _probe_lit_points(self, volume, points, normals, clamp=True, want_ok=False):
     naddr, _, ndev = _ray_array(normals, "normals", 3, np.float32, rows=m)
     if not (vdev == ndev == dev):
         raise ValueError("normals and the volume must live where points live (all numpy arrays, or all tensors on the GPU)")
-    if dev:
-        import torch
-        ind = torch.zeros((m, 3), dtype=torch.float32, device=points.device); ok = torch.zeros(m, dtype=torch.uint8, device=points.device) if want_ok else None
-        iaddr, okaddr = ind.data_ptr(), ok.data_ptr() if want_ok else None
-        torch.cuda.current_stream(points.device).synchronize()
-    else:
-        ind = np.zeros((m, 3), np.float32); ok = np.zeros(m, np.uint8) if want_ok else None
-        iaddr, okaddr = ind.ctypes.data, ok.ctypes.data if want_ok else None
+    ind, ok, iaddr, okaddr = _rgb_ok(m, want_ok, _device_of(points))
     self._check(lib().mi355rt_probe_lit_points(self._h, C.byref(v), addr, naddr, m, PROBE_LIT_CLAMP if clamp else 0, RAYS_DEVICE if dev else RAYS_HOST, iaddr, okaddr))
     return (ind, ok) if want_ok else ind
 
@@ -1975,33 +1847,15 @@ def _probe_lit_rays(self, volume, rays6, want=("rgb",), clamp=True, into=None):
     "rgb", "light", "indirect", "tuv", "prim", "ok".  numpy arrays or torch tensors on the handle's GPU, the volume's arrays alike, under trace_rays' rules.
     into: a dict of arrays to write into (tuv of a miss stays as it was).  Returns a dict name -> array.  No film, camera or lens state changes;
     last_counts() reports n primary rays."""
-    want = tuple(want)
-    if not want or any(w not in PROBE_LIT_OUTPUTS for w in want) or len(set(want)) != len(want):
-        raise ValueError("want: a non-empty selection of %s without repeats, not %r" % (PROBE_LIT_OUTPUTS, want))
+    want = _check_want(want, PROBE_LIT_OUTPUTS)
     v, vdev, _keep = _probe_volume(self, volume)
     addr, n, dev = _ray_array(rays6, "rays6", 6, np.float32)
     if vdev != dev:
         raise ValueError("the volume must live where rays6 lives (all numpy arrays, or all tensors on the GPU)")
-    res, o = {}, ProbeLitOutputs()
-    if dev:
-        import torch
-    for w in want:
-        shape = (n,) if w in ("prim", "ok") else (n, 3)
-        dt = np.uint32 if w == "prim" else np.uint8 if w == "ok" else np.float32
-        if into is not None and w in into:
-            res[w] = into[w]
-            a, _, adev = (_ray_vector(res[w], "into[%r]" % w, dt, n) if len(shape) == 1 else _ray_array(res[w], "into[%r]" % w, 3, dt, rows=n))
-            if adev != dev:
-                raise ValueError("into must live where rays6 lives")
-            setattr(o, w, a)
-        elif dev:
-            res[w] = torch.zeros(shape, dtype=torch.int32 if w == "prim" else torch.uint8 if w == "ok" else torch.float32, device=rays6.device)
-            setattr(o, w, res[w].data_ptr())
-        else:
-            res[w] = np.zeros(shape, dt)
-            setattr(o, w, res[w].ctypes.data)
-    if dev:
-        torch.cuda.current_stream(rays6.device).synchronize()           # what produced the inputs (and the zero fill) has finished: the library's stream knows nothing of torch's
+    o, device = ProbeLitOutputs(), _device_of(rays6)
+    res = {w: _output(o, w, (n,) if w in ("prim", "ok") else (n, 3), np.uint32 if w == "prim" else np.uint8 if w == "ok" else np.float32, device,
+                      into if into is not None and w in into else None, "into must live where rays6 lives") for w in want}
+    _sync(device)                                                       # what produced the inputs (and the zero fill) has finished
     self._check(lib().mi355rt_probe_lit_rays(self._h, C.byref(v), addr, n, PROBE_LIT_CLAMP if clamp else 0, RAYS_DEVICE if dev else RAYS_HOST, C.byref(o)))
     return res
 

@@ -969,6 +969,19 @@ int mi355rt_bake_auto_atlas(uint32_t ntri, uint32_t width, uint32_t height, uint
     return MI355RT_OK;
 }
 
+namespace {
+// The sample rules of the ray-making entries (probes_gather, probes_gather_depth, probes_survey).  between: the verdict of the entry's own config checks, which
+// come after spp's and before the sizes'
+const char* probe_samples_error(uint32_t spp, uint32_t first_sample, size_t npoints, const char* between)
+{
+    if (spp == 0) return "spp must be >= 1";
+    if (between) return between;
+    if ((uint64_t)first_sample + spp > 0xFFFFFFFFull) return "first_sample + spp must fit 32 bits";
+    if (npoints > 0xFFFFFFFFull || (uint64_t)npoints * spp >= (1ull << 32)) return "npoints * spp must be < 2^32";
+    return nullptr;
+}
+}  // namespace
+
 void mi355rt_probes_default_config(mi355rt_probe_config* cfg)
 {
     if (!cfg) return;
@@ -984,10 +997,7 @@ int mi355rt_probes_gather(mi355rt_handle* h, const float* points3, const uint32_
     else if (!cfg) e = "cfg is NULL";
     else if (!out || (!out->n && !out->hits && !out->near && !out->sh)) e = "out is NULL or every output pointer in it is NULL";
     else if (npoints && !points3) e = "points3 is NULL";
-    else if (cfg->spp == 0) e = "spp must be >= 1";
-    else if (std::isnan(cfg->near_distance)) e = "near_distance is NaN";
-    else if ((uint64_t)cfg->first_sample + cfg->spp > 0xFFFFFFFFull) e = "first_sample + spp must fit 32 bits";
-    else if (npoints > 0xFFFFFFFFull || (uint64_t)npoints * cfg->spp >= (1ull << 32)) e = "npoints * spp must be < 2^32";
+    else e = probe_samples_error(cfg->spp, cfg->first_sample, npoints, std::isnan(cfg->near_distance) ? "near_distance is NaN" : nullptr);
     if (e) { h->r->last_error = std::string("mi355rt_probes_gather: ") + e; return MI355RT_E_INVALID; }
     if (npoints == 0) return MI355RT_OK;
     return h->r->probes_gather(points3, ids, npoints, *cfg, where == MI355RT_RAYS_DEVICE, *out) ? MI355RT_OK : MI355RT_E_HIP;
@@ -1010,22 +1020,71 @@ const char* probe_grid_error(const mi355rt_probe_grid* g)
     }
     return nullptr;
 }
+// defined with the entries that came with them, below
+const char* probe_depth_error(const mi355rt_probe_depth* d);
+const char* probe_vis_error(const mi355rt_probe_vis_config* vc, bool has_normals);
+bool all_finite(const float* a, size_t n);
+size_t grid_probes(const mi355rt_probe_grid* g);
+// The arguments of mi355rt_probes_lookup, _vis and _placed.  weighted: the entry has depth films and a visibility config (and normals3 may back them);
+// host: offsets (may be null) is host memory and is inspected
+const char* probes_lookup_error(const mi355rt_handle* h, uint32_t where, const mi355rt_probe_grid* grid, const uint32_t* n, const float* sh, bool weighted, const mi355rt_probe_depth* depth,
+                                const mi355rt_probe_vis_config* vc, const float* offsets, const float* points3, const float* dirs3, const float* normals3, size_t npoints, uint32_t mode,
+                                const float* rgb3)
+{
+    if (const char* e = single_device_ok(h, where)) return e;
+    if (const char* e = probe_grid_error(grid)) return e;
+    if (!n) return "n is NULL";
+    if (!sh) return "sh is NULL";
+    if (weighted) {
+        if (const char* e = probe_depth_error(depth)) return e;
+        if (const char* e = probe_vis_error(vc, normals3 != nullptr)) return e;
+    }
+    if (!rgb3) return "rgb3 is NULL";
+    if (npoints && !points3) return "points3 is NULL";
+    if (npoints && !dirs3) return "dirs3 is NULL";
+    if (mode > MI355RT_SH_IRRADIANCE) return "unknown mode (MI355RT_SH_RADIANCE or MI355RT_SH_IRRADIANCE)";
+    if (npoints > 0xFFFFFFFFull) return "npoints must fit 32 bits";
+    if (offsets && where == MI355RT_RAYS_HOST && !all_finite(offsets, grid_probes(grid) * 3)) return "offsets holds a value that is not finite";
+    return nullptr;
+}
+// The arguments of mi355rt_probes_lookup_one, _vis_one and _placed_one
+const char* probes_lookup_one_error(const mi355rt_probe_grid* grid, const uint32_t* n, const float* sh, bool weighted, const mi355rt_probe_depth* depth, const mi355rt_probe_vis_config* vc,
+                                    const float* offsets, const float* point, const float* dir, const float* normal, uint32_t mode, const float* rgb)
+{
+    if (const char* e = probe_grid_error(grid)) return e;
+    if (!n) return "n is NULL";
+    if (!sh) return "sh is NULL";
+    if (weighted) {
+        if (const char* e = probe_depth_error(depth)) return e;
+        if (const char* e = probe_vis_error(vc, normal != nullptr)) return e;
+    }
+    if (const char* e = !point ? "point is NULL" : !dir ? "dir is NULL" : !rgb ? "rgb is NULL" : mode > MI355RT_SH_IRRADIANCE ? "unknown mode" : nullptr) return e;
+    if (offsets && !all_finite(offsets, grid_probes(grid) * 3)) return "offsets holds a value that is not finite";
+    return nullptr;
+}
+// A probe volume in host memory as the statements of sh9.hpp read it: the accessors of the _one entries.  depth, offsets: may be null
+struct HostVolume {
+    ShGrid grid; const uint32_t* n; const float* sh; const uint8_t* usable; uint32_t R; size_t RR; const uint32_t* count; const float* moments; const float* offsets;
+    HostVolume(const mi355rt_probe_grid* g, const uint32_t* n, const float* sh, const uint8_t* usable, const mi355rt_probe_depth* depth, const float* offsets)
+        : n(n), sh(sh), usable(usable), R(depth ? depth->res : 0u), RR((size_t)R * R), count(depth ? depth->count : nullptr), moments(depth ? depth->moments : nullptr), offsets(offsets)
+    {
+        std::memcpy(&grid, g, sizeof grid);
+    }
+    auto n_of() const { return [p = n](size_t j) { return p[j]; }; }
+    auto sh_of() const { return [p = sh](size_t j, int c) { return p[27 * j + c]; }; }
+    auto usable_of() const { return [p = usable](size_t j) { return p[j] != 0; }; }
+    auto count_of() const { return [p = count, RR = RR](size_t j, uint32_t k) { return p[j * RR + k]; }; }
+    auto moment_of() const { return [p = moments, RR = RR](size_t j, uint32_t k, int m) { return p[2 * (j * RR + k) + m]; }; }
+    auto offset_of() const { return [p = offsets](size_t j, int a) { return p[3 * j + a]; }; }
+};
+const float kNoNormal[3] = { 0.0f, 0.0f, 0.0f };        // what a statement is handed for a normal it will not read
 }  // namespace
 
 int mi355rt_probes_lookup(mi355rt_handle* h, const mi355rt_probe_grid* grid, const uint32_t* n, const float* sh, const uint8_t* usable, const float* points3, const float* dirs3,
                           size_t npoints, uint32_t mode, uint32_t where, float* rgb3, uint8_t* ok)
 {
     if (!h) return MI355RT_E_INVALID;
-    const char* e = nullptr;
-    if ((e = single_device_ok(h, where)) != nullptr) {}
-    else if ((e = probe_grid_error(grid)) != nullptr) {}
-    else if (!n) e = "n is NULL";
-    else if (!sh) e = "sh is NULL";
-    else if (!rgb3) e = "rgb3 is NULL";
-    else if (npoints && !points3) e = "points3 is NULL";
-    else if (npoints && !dirs3) e = "dirs3 is NULL";
-    else if (mode > MI355RT_SH_IRRADIANCE) e = "unknown mode (MI355RT_SH_RADIANCE or MI355RT_SH_IRRADIANCE)";
-    else if (npoints > 0xFFFFFFFFull) e = "npoints must fit 32 bits";
+    const char* e = probes_lookup_error(h, where, grid, n, sh, false, nullptr, nullptr, nullptr, points3, dirs3, nullptr, npoints, mode, rgb3);
     if (e) { h->r->last_error = std::string("mi355rt_probes_lookup: ") + e; return MI355RT_E_INVALID; }
     if (npoints == 0) return MI355RT_OK;
     return h->r->probes_lookup(*grid, n, sh, usable, points3, dirs3, npoints, mode, where == MI355RT_RAYS_DEVICE, rgb3, ok) ? MI355RT_OK : MI355RT_E_HIP;
@@ -1042,13 +1101,10 @@ int mi355rt_sh9_basis(const float dir[3], float b[9])
 int mi355rt_probes_lookup_one(const mi355rt_probe_grid* grid, const uint32_t* n, const float* sh, const uint8_t* usable, const float point[3], const float dir[3], uint32_t mode,
                               float rgb[3], uint32_t* ok)
 {
-    const char* e = probe_grid_error(grid);
-    if (!e) e = !n ? "n is NULL" : !sh ? "sh is NULL" : !point ? "point is NULL" : !dir ? "dir is NULL" : !rgb ? "rgb is NULL" : mode > MI355RT_SH_IRRADIANCE ? "unknown mode" : nullptr;
+    const char* e = probes_lookup_one_error(grid, n, sh, false, nullptr, nullptr, nullptr, point, dir, nullptr, mode, rgb);
     if (e) { g_create_error = std::string("mi355rt_probes_lookup_one: ") + e; return MI355RT_E_INVALID; }
-    ShGrid g;
-    std::memcpy(&g, grid, sizeof g);
-    const bool used = sh9_lookup(g, [n](size_t j) { return n[j]; }, [sh](size_t j, int c) { return sh[27 * j + c]; }, usable != nullptr,
-                                 [usable](size_t j) { return usable[j] != 0; }, point, dir, mode, rgb);
+    const HostVolume v(grid, n, sh, usable, nullptr, nullptr);
+    const bool used = sh9_lookup(v.grid, v.n_of(), v.sh_of(), usable != nullptr, v.usable_of(), point, dir, mode, rgb);
     if (ok) *ok = used ? 1u : 0u;
     return MI355RT_OK;
 }
@@ -1108,10 +1164,7 @@ int mi355rt_probes_gather_depth(mi355rt_handle* h, const float* points3, const u
     else if (out && !out->n && !out->hits && !out->near && !out->sh) e = "every output pointer in out is NULL (pass out as NULL for the depth film alone)";
     else if ((e = probe_depth_error(depth)) != nullptr) {}
     else if (npoints && !points3) e = "points3 is NULL";
-    else if (cfg->spp == 0) e = "spp must be >= 1";
-    else if (std::isnan(cfg->near_distance)) e = "near_distance is NaN";
-    else if ((uint64_t)cfg->first_sample + cfg->spp > 0xFFFFFFFFull) e = "first_sample + spp must fit 32 bits";
-    else if (npoints > 0xFFFFFFFFull || (uint64_t)npoints * cfg->spp >= (1ull << 32)) e = "npoints * spp must be < 2^32";
+    else e = probe_samples_error(cfg->spp, cfg->first_sample, npoints, std::isnan(cfg->near_distance) ? "near_distance is NaN" : nullptr);
     if (e) { h->r->last_error = std::string("mi355rt_probes_gather_depth: ") + e; return MI355RT_E_INVALID; }
     if (npoints == 0) return MI355RT_OK;
     const mi355rt_probe_outputs none{};
@@ -1123,18 +1176,7 @@ int mi355rt_probes_lookup_vis(mi355rt_handle* h, const mi355rt_probe_grid* grid,
                               float* rgb3, uint8_t* ok)
 {
     if (!h) return MI355RT_E_INVALID;
-    const char* e = nullptr;
-    if ((e = single_device_ok(h, where)) != nullptr) {}
-    else if ((e = probe_grid_error(grid)) != nullptr) {}
-    else if (!n) e = "n is NULL";
-    else if (!sh) e = "sh is NULL";
-    else if ((e = probe_depth_error(depth)) != nullptr) {}
-    else if ((e = probe_vis_error(vc, normals3 != nullptr)) != nullptr) {}
-    else if (!rgb3) e = "rgb3 is NULL";
-    else if (npoints && !points3) e = "points3 is NULL";
-    else if (npoints && !dirs3) e = "dirs3 is NULL";
-    else if (mode > MI355RT_SH_IRRADIANCE) e = "unknown mode (MI355RT_SH_RADIANCE or MI355RT_SH_IRRADIANCE)";
-    else if (npoints > 0xFFFFFFFFull) e = "npoints must fit 32 bits";
+    const char* e = probes_lookup_error(h, where, grid, n, sh, true, depth, vc, nullptr, points3, dirs3, normals3, npoints, mode, rgb3);
     if (e) { h->r->last_error = std::string("mi355rt_probes_lookup_vis: ") + e; return MI355RT_E_INVALID; }
     if (npoints == 0) return MI355RT_OK;
     return h->r->probes_lookup_vis(*grid, n, sh, usable, *depth, *vc, points3, dirs3, normals3, npoints, mode, where == MI355RT_RAYS_DEVICE, rgb3, ok) ? MI355RT_OK : MI355RT_E_HIP;
@@ -1172,21 +1214,11 @@ int mi355rt_probe_visibility_one(const mi355rt_probe_depth* depth, const float v
 int mi355rt_probes_lookup_vis_one(const mi355rt_probe_grid* grid, const uint32_t* n, const float* sh, const uint8_t* usable, const mi355rt_probe_depth* depth,
                                   const mi355rt_probe_vis_config* vc, const float point[3], const float dir[3], const float normal[3], uint32_t mode, float rgb[3], uint32_t* ok)
 {
-    const char* e = probe_grid_error(grid);
-    if (!e) e = !n ? "n is NULL" : !sh ? "sh is NULL" : nullptr;
-    if (!e) e = probe_depth_error(depth);
-    if (!e) e = probe_vis_error(vc, normal != nullptr);
-    if (!e) e = !point ? "point is NULL" : !dir ? "dir is NULL" : !rgb ? "rgb is NULL" : mode > MI355RT_SH_IRRADIANCE ? "unknown mode" : nullptr;
+    const char* e = probes_lookup_one_error(grid, n, sh, true, depth, vc, nullptr, point, dir, normal, mode, rgb);
     if (e) { g_create_error = std::string("mi355rt_probes_lookup_vis_one: ") + e; return MI355RT_E_INVALID; }
-    ShGrid g;
-    std::memcpy(&g, grid, sizeof g);
-    const uint32_t* count = depth->count; const float* moments = depth->moments;
-    const size_t RR = (size_t)depth->res * depth->res;
-    const float zero[3] = { 0.0f, 0.0f, 0.0f };
-    const bool used = sh9_lookup_vis(g, [n](size_t j) { return n[j]; }, [sh](size_t j, int c) { return sh[27 * j + c]; }, usable != nullptr,
-                                     [usable](size_t j) { return usable[j] != 0; }, depth->res, [count, RR](size_t j, uint32_t k) { return count[j * RR + k]; },
-                                     [moments, RR](size_t j, uint32_t k, int m) { return moments[2 * (j * RR + k) + m]; }, vc->flags, vc->normal_bias, point, dir,
-                                     normal != nullptr, normal ? normal : zero, mode, rgb);
+    const HostVolume v(grid, n, sh, usable, depth, nullptr);
+    const bool used = sh9_lookup_vis(v.grid, v.n_of(), v.sh_of(), usable != nullptr, v.usable_of(), v.R, v.count_of(), v.moment_of(), vc->flags, vc->normal_bias, point, dir,
+                                     normal != nullptr, normal ? normal : kNoNormal, mode, rgb);
     if (ok) *ok = used ? 1u : 0u;
     return MI355RT_OK;
 }
@@ -1570,11 +1602,8 @@ int mi355rt_probes_survey(mi355rt_handle* h, const float* points3, const uint32_
     else if (!cfg) e = "cfg is NULL";
     else if ((e = probe_survey_error(out, "out", where == MI355RT_RAYS_DEVICE)) != nullptr) {}
     else if (npoints && !points3) e = "points3 is NULL";
-    else if (cfg->spp == 0) e = "spp must be >= 1";
-    else if (cfg->flags & ~MI355RT_SURVEY_FLIP) e = "cfg.flags: unknown bits (MI355RT_SURVEY_FLIP)";
-    else if ((e = probe_max_distance_error(cfg->max_distance)) != nullptr) {}
-    else if ((uint64_t)cfg->first_sample + cfg->spp > 0xFFFFFFFFull) e = "first_sample + spp must fit 32 bits";
-    else if (npoints > 0xFFFFFFFFull || (uint64_t)npoints * cfg->spp >= (1ull << 32)) e = "npoints * spp must be < 2^32";
+    else e = probe_samples_error(cfg->spp, cfg->first_sample, npoints,
+                                 cfg->flags & ~MI355RT_SURVEY_FLIP ? "cfg.flags: unknown bits (MI355RT_SURVEY_FLIP)" : probe_max_distance_error(cfg->max_distance));
     if (e) { h->r->last_error = std::string("mi355rt_probes_survey: ") + e; return MI355RT_E_INVALID; }
     if (npoints == 0) return MI355RT_OK;
     return h->r->probes_survey(points3, ids, npoints, *cfg, where == MI355RT_RAYS_DEVICE, *out) ? MI355RT_OK : MI355RT_E_HIP;
@@ -1622,19 +1651,7 @@ int mi355rt_probes_lookup_placed(mi355rt_handle* h, const mi355rt_probe_grid* gr
                                  uint32_t mode, uint32_t where, float* rgb3, uint8_t* ok)
 {
     if (!h) return MI355RT_E_INVALID;
-    const char* e = nullptr;
-    if ((e = single_device_ok(h, where)) != nullptr) {}
-    else if ((e = probe_grid_error(grid)) != nullptr) {}
-    else if (!n) e = "n is NULL";
-    else if (!sh) e = "sh is NULL";
-    else if ((e = probe_depth_error(depth)) != nullptr) {}
-    else if ((e = probe_vis_error(vc, normals3 != nullptr)) != nullptr) {}
-    else if (!rgb3) e = "rgb3 is NULL";
-    else if (npoints && !points3) e = "points3 is NULL";
-    else if (npoints && !dirs3) e = "dirs3 is NULL";
-    else if (mode > MI355RT_SH_IRRADIANCE) e = "unknown mode (MI355RT_SH_RADIANCE or MI355RT_SH_IRRADIANCE)";
-    else if (npoints > 0xFFFFFFFFull) e = "npoints must fit 32 bits";
-    else if (offsets && where == MI355RT_RAYS_HOST && !all_finite(offsets, grid_probes(grid) * 3)) e = "offsets holds a value that is not finite";
+    const char* e = probes_lookup_error(h, where, grid, n, sh, true, depth, vc, offsets, points3, dirs3, normals3, npoints, mode, rgb3);
     if (e) { h->r->last_error = std::string("mi355rt_probes_lookup_placed: ") + e; return MI355RT_E_INVALID; }
     if (npoints == 0) return MI355RT_OK;
     return h->r->probes_lookup_placed(*grid, n, sh, usable, *depth, *vc, offsets, points3, dirs3, normals3, npoints, mode, where == MI355RT_RAYS_DEVICE, rgb3, ok) ? MI355RT_OK
@@ -1645,23 +1662,11 @@ int mi355rt_probes_lookup_placed_one(const mi355rt_probe_grid* grid, const uint3
                                      const mi355rt_probe_vis_config* vc, const float* offsets, const float point[3], const float dir[3], const float normal[3], uint32_t mode,
                                      float rgb[3], uint32_t* ok)
 {
-    const char* e = probe_grid_error(grid);
-    if (!e) e = !n ? "n is NULL" : !sh ? "sh is NULL" : nullptr;
-    if (!e) e = probe_depth_error(depth);
-    if (!e) e = probe_vis_error(vc, normal != nullptr);
-    if (!e) e = !point ? "point is NULL" : !dir ? "dir is NULL" : !rgb ? "rgb is NULL" : mode > MI355RT_SH_IRRADIANCE ? "unknown mode" : nullptr;
-    if (!e && offsets && !all_finite(offsets, grid_probes(grid) * 3)) e = "offsets holds a value that is not finite";
+    const char* e = probes_lookup_one_error(grid, n, sh, true, depth, vc, offsets, point, dir, normal, mode, rgb);
     if (e) { g_create_error = std::string("mi355rt_probes_lookup_placed_one: ") + e; return MI355RT_E_INVALID; }
-    ShGrid g;
-    std::memcpy(&g, grid, sizeof g);
-    const uint32_t* count = depth->count; const float* moments = depth->moments;
-    const size_t RR = (size_t)depth->res * depth->res;
-    const float zero[3] = { 0.0f, 0.0f, 0.0f };
-    const bool used = sh9_lookup_placed(g, [n](size_t j) { return n[j]; }, [sh](size_t j, int c) { return sh[27 * j + c]; }, usable != nullptr,
-                                        [usable](size_t j) { return usable[j] != 0; }, depth->res, [count, RR](size_t j, uint32_t k) { return count[j * RR + k]; },
-                                        [moments, RR](size_t j, uint32_t k, int m) { return moments[2 * (j * RR + k) + m]; }, offsets != nullptr,
-                                        [offsets](size_t j, int a) { return offsets[3 * j + a]; }, vc->flags, vc->normal_bias, point, dir, normal != nullptr,
-                                        normal ? normal : zero, mode, rgb);
+    const HostVolume v(grid, n, sh, usable, depth, offsets);
+    const bool used = sh9_lookup_placed(v.grid, v.n_of(), v.sh_of(), usable != nullptr, v.usable_of(), v.R, v.count_of(), v.moment_of(), offsets != nullptr, v.offset_of(), vc->flags,
+                                        vc->normal_bias, point, dir, normal != nullptr, normal ? normal : kNoNormal, mode, rgb);
     if (ok) *ok = used ? 1u : 0u;
     return MI355RT_OK;
 }
@@ -1729,17 +1734,9 @@ int mi355rt_probe_lit_one(const mi355rt_probe_volume* volume, const float point[
     const char* e = probe_volume_error(volume, true);
     if (!e) e = flags & ~MI355RT_PROBE_LIT_CLAMP ? "flags: unknown bits (MI355RT_PROBE_LIT_CLAMP)" : !point ? "point is NULL" : !normal ? "normal is NULL" : !indirect ? "indirect is NULL" : nullptr;
     if (e) { g_create_error = std::string("mi355rt_probe_lit_one: ") + e; return MI355RT_E_INVALID; }
-    ShGrid g;
-    std::memcpy(&g, volume->grid, sizeof g);
-    const uint32_t* n = volume->n; const float* sh = volume->sh; const uint8_t* usable = volume->usable; const float* offsets = volume->offsets;
-    const mi355rt_probe_depth* depth = volume->depth;
-    const uint32_t* count = depth ? depth->count : nullptr; const float* moments = depth ? depth->moments : nullptr;
-    const uint32_t R = depth ? depth->res : 0u;
-    const size_t RR = (size_t)R * R;
-    const bool used = hemi_one(g, [n](size_t j) { return n[j]; }, [sh](size_t j, int c) { return sh[27 * j + c]; }, usable != nullptr, [usable](size_t j) { return usable[j] != 0; }, R,
-                               [count, RR](size_t j, uint32_t k) { return count[j * RR + k]; }, [moments, RR](size_t j, uint32_t k, int m) { return moments[2 * (j * RR + k) + m]; },
-                               offsets != nullptr, [offsets](size_t j, int a) { return offsets[3 * j + a]; }, depth ? volume->vc->flags : 0u, depth ? volume->vc->normal_bias : 0.0f, point,
-                               normal, (flags & MI355RT_PROBE_LIT_CLAMP) != 0, indirect);
+    const HostVolume v(volume->grid, volume->n, volume->sh, volume->usable, volume->depth, volume->offsets);
+    const bool used = hemi_one(v.grid, v.n_of(), v.sh_of(), v.usable != nullptr, v.usable_of(), v.R, v.count_of(), v.moment_of(), v.offsets != nullptr, v.offset_of(),
+                               volume->depth ? volume->vc->flags : 0u, volume->depth ? volume->vc->normal_bias : 0.0f, point, normal, (flags & MI355RT_PROBE_LIT_CLAMP) != 0, indirect);
     if (ok) *ok = used ? 1u : 0u;
     return MI355RT_OK;
 }

@@ -1,13 +1,12 @@
 // oct_vis.hpp — the arithmetic of probe visibility (include/mi355rt.h, "PROBE VISIBILITY"): the octahedral map of a direction, the bin of a
-// depth sample, the Chebyshev weight of one probe for one query and the weighted lookup of one query in a probe grid.  ONE statement, compiled for the host
-// (mi355rt_oct_encode, mi355rt_oct_texel, mi355rt_probe_visibility_one, mi355rt_probes_lookup_vis_one) and for the device (csrc/probes_vis.hip): f32,
-// unfused (every file that includes this is built with -ffp-contract=off), expression for expression what raytracer-rs_amd/probes.py writes in numpy.  Only
+// depth sample, and the two factors a probe's view of a query adds to its weight in a lookup: the Chebyshev weight and the facing term.  The lookup that
+// uses them is sh9_corners (sh9.hpp, which includes this file).  ONE statement, compiled for the host (mi355rt_oct_encode, mi355rt_oct_texel,
+// mi355rt_probe_visibility_one, mi355rt_probes_lookup_vis_one) and for the device (csrc/probes_vis.hip, probes_place.hip, probe_lit.hip): f32, unfused (every file that includes this is built with -ffp-contract=off), expression for expression what raytracer-rs_amd/probes.py writes in numpy.  Only
 // + - x / sqrt, comparisons and integer conversions: no floor, no pow, no transcendental function, so host and device agree on the bits.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <hip/hip_runtime.h>
-#include "sh9.hpp"
 
 namespace mi355rt {
 
@@ -99,69 +98,6 @@ __host__ __device__ __forceinline__ float oct_facing(float x, float y, float z, 
     float q = ((((-x) * nx + (-y) * ny) + (-z) * nz) / r + 1.0f) * 0.5f;
     q = q >= 0.0001f ? q : 0.0001f;
     return q * q + 0.2f;
-}
-
-// sh9_lookup with the weight of corner j  wj = (t * vis) * face  in the place of t.  The probes' helpers, the corner order and the read-out are sh9.hpp's.
-// count(probe, k) -> u32, moment(probe, k, c) -> f32; without has_nrm nrm is not read (p_b = p and face = 1).  The cell and the fractions come from p.  A corner with
-// t == 0, n == 0 or usable == 0 is skipped before anything of it is read, one whose wj is 0 like them.  Returns ok; rgb is 0 when no corner was used.
-template <class N, class Sh, class Usable, class Cnt, class Mom>
-__host__ __device__ __forceinline__ bool sh9_lookup_vis(const ShGrid& grid, N n, Sh sh, bool has_usable, Usable usable, uint32_t R, Cnt count, Mom moment, uint32_t flags,
-                                                        float normal_bias, const float* p, const float* dir, bool has_nrm, const float* nrm, uint32_t mode, float* rgb)
-{
-    uint32_t i[3]; float f[3], pb[3];
-    for (int a = 0; a < 3; ++a) {
-        sh9_axis(p[a], grid.origin[a], grid.spacing[a], grid.counts[a], i[a], f[a]);
-        pb[a] = has_nrm ? p[a] + normal_bias * nrm[a] : p[a];
-    }
-    const bool cheb = (flags & kVisChebyshev) != 0u, facing = (flags & kVisFacing) != 0u && has_nrm;
-    float C[27];
-    for (int q = 0; q < 27; ++q) C[q] = 0.0f;
-    float wsum = 0.0f;
-    bool any = false;
-    for (uint32_t j = 0; j < 8u; ++j) {
-        uint32_t c[3]; float w[3];
-        for (int a = 0; a < 3; ++a) {
-            const bool up = ((j >> a) & 1u) != 0u;
-            c[a] = up ? (i[a] + 1u <= grid.counts[a] - 1u ? i[a] + 1u : grid.counts[a] - 1u) : i[a];
-            w[a] = up ? f[a] : 1.0f - f[a];
-        }
-        const float t = (w[0] * w[1]) * w[2];
-        if (t == 0.0f) continue;
-        const size_t probe = ((size_t)c[2] * grid.counts[1] + c[1]) * grid.counts[0] + c[0];
-        const uint32_t nj = n(probe);
-        if (nj == 0u) continue;
-        if (has_usable && !usable(probe)) continue;
-        float vis = 1.0f, face = 1.0f;
-        if (cheb || facing) {
-            const float vx = pb[0] - sh9_probe_pos(grid.origin[0], grid.spacing[0], c[0]);
-            const float vy = pb[1] - sh9_probe_pos(grid.origin[1], grid.spacing[1], c[1]);
-            const float vz = pb[2] - sh9_probe_pos(grid.origin[2], grid.spacing[2], c[2]);
-            const float r = oct_length(vx, vy, vz);
-            if (cheb) vis = oct_visibility(R, [&](uint32_t k) { return count(probe, k); }, [&](uint32_t k, int m) { return moment(probe, k, m); }, vx, vy, vz, r);
-            if (facing && oct_length_fine(r)) face = oct_facing(vx, vy, vz, r, nrm[0], nrm[1], nrm[2]);
-        }
-        const float wj = (t * vis) * face;
-        if (wj == 0.0f) continue;
-        any = true;
-        wsum += wj;
-        const float s = wj * (kShSphere / (float)nj);
-        for (int q = 0; q < 27; ++q) C[q] += s * sh(probe, q);
-    }
-    if (!any) { rgb[0] = 0.0f; rgb[1] = 0.0f; rgb[2] = 0.0f; return false; }
-    float b[9];
-    sh9_basis(dir[0], dir[1], dir[2], b);
-    float r[3] = { 0.0f, 0.0f, 0.0f };
-    if (mode == kShIrradiance) {
-        for (int k = 0; k < 9; ++k) {
-            const float A = k == 0 ? kShA0 : k < 4 ? kShA1 : kShA2;
-            for (int ch = 0; ch < 3; ++ch) r[ch] += (A * C[3 * k + ch]) * b[k];
-        }
-    } else {
-        for (int k = 0; k < 9; ++k)
-            for (int ch = 0; ch < 3; ++ch) r[ch] += C[3 * k + ch] * b[k];
-    }
-    for (int ch = 0; ch < 3; ++ch) rgb[ch] = r[ch] / wsum;
-    return true;
 }
 
 }  // namespace mi355rt

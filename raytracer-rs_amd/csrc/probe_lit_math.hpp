@@ -14,67 +14,27 @@ namespace mi355rt {
 constexpr uint32_t kProbeLitClamp = 1u;                      // MI355RT_PROBE_LIT_CLAMP
 constexpr float kHemiBand1 = 0.5f;                           // the uniform hemisphere mean as a zonal convolution: band factors 1, 1/2, 0
 
-// The uniform mean over the hemisphere of nrm of the radiance field a probe grid holds, at p.  The corners, their skipping rules, wsum and the weight
-// wj = (t * vis) * face are sh9_lookup_placed's (probe_place.hpp) for dir = normal = nrm; with flags 0 nothing of the depth films or the offsets is read and
-// wj is sh9_lookup's t.  Of a used corner only coefficients 0 .. 3 are read: sh(probe, k * 3 + c) is asked for k * 3 + c < 12 only.  Returns ok; out is 0
-// when no corner was used.  clamp: a value that is not >= 0 (a NaN too) becomes +0.
+// The uniform mean over the hemisphere of nrm of the radiance field a probe grid holds, at p.  The corners are sh9_corners' (sh9.hpp) with offsets and
+// dir = normal = nrm; with flags 0 nothing of the depth films or the offsets is read and wj is t.  Of a used corner only coefficients 0 .. 3 are read:
+// sh(probe, k * 3 + c) is asked for k * 3 + c < 12 only.  The read-out is its own: band factors 1, 1/2, 0.  Returns ok; out is 0 when no corner was used.
+// clamp: a value that is not >= 0 (a NaN too) becomes +0.
 template <class N, class Sh, class Usable, class Cnt, class Mom, class Off>
 __host__ __device__ __forceinline__ bool hemi_one(const ShGrid& grid, N n, Sh sh, bool has_usable, Usable usable, uint32_t R, Cnt count, Mom moment, bool has_off, Off offset,
                                                   uint32_t flags, float normal_bias, const float* p, const float* nrm, bool clamp, float* out)
 {
-    uint32_t i[3]; float f[3], pb[3];
-    for (int a = 0; a < 3; ++a) {
-        sh9_axis(p[a], grid.origin[a], grid.spacing[a], grid.counts[a], i[a], f[a]);
-        pb[a] = p[a] + normal_bias * nrm[a];
-    }
-    const bool cheb = (flags & kVisChebyshev) != 0u, facing = (flags & kVisFacing) != 0u;
-    float C[12];
-    for (int q = 0; q < 12; ++q) C[q] = 0.0f;
-    float wsum = 0.0f;
-    bool any = false;
-    for (uint32_t j = 0; j < 8u; ++j) {
-        uint32_t c[3]; float w[3];
-        for (int a = 0; a < 3; ++a) {
-            const bool up = ((j >> a) & 1u) != 0u;
-            c[a] = up ? (i[a] + 1u <= grid.counts[a] - 1u ? i[a] + 1u : grid.counts[a] - 1u) : i[a];
-            w[a] = up ? f[a] : 1.0f - f[a];
+    return sh9_corners<12, true, true>(grid, n, sh, has_usable, usable, R, count, moment, has_off, offset, flags, normal_bias, p, true, nrm, nullptr, 0u, nullptr,
+                                       [&](bool any, const float* C, float wsum) {
+        if (!any) { out[0] = 0.0f; out[1] = 0.0f; out[2] = 0.0f; return; }
+        float b[9];
+        sh9_basis(nrm[0], nrm[1], nrm[2], b);
+        for (int ch = 0; ch < 3; ++ch) {
+            float m = 0.0f;
+            m += C[ch] * b[0];
+            for (int k = 1; k < 4; ++k) m += (kHemiBand1 * C[3 * k + ch]) * b[k];
+            const float x = m / wsum;
+            out[ch] = clamp ? (x >= 0.0f ? x : 0.0f) : x;
         }
-        const float t = (w[0] * w[1]) * w[2];
-        if (t == 0.0f) continue;
-        const size_t probe = ((size_t)c[2] * grid.counts[1] + c[1]) * grid.counts[0] + c[0];
-        const uint32_t nj = n(probe);
-        if (nj == 0u) continue;
-        if (has_usable && !usable(probe)) continue;
-        float vis = 1.0f, face = 1.0f;
-        if (cheb || facing) {
-            float pos[3];
-            for (int a = 0; a < 3; ++a) {
-                pos[a] = sh9_probe_pos(grid.origin[a], grid.spacing[a], c[a]);
-                if (has_off) pos[a] = pos[a] + offset(probe, a);
-            }
-            const float vx = pb[0] - pos[0], vy = pb[1] - pos[1], vz = pb[2] - pos[2];
-            const float r = oct_length(vx, vy, vz);
-            if (cheb) vis = oct_visibility(R, [&](uint32_t k) { return count(probe, k); }, [&](uint32_t k, int m) { return moment(probe, k, m); }, vx, vy, vz, r);
-            if (facing && oct_length_fine(r)) face = oct_facing(vx, vy, vz, r, nrm[0], nrm[1], nrm[2]);
-        }
-        const float wj = (t * vis) * face;
-        if (wj == 0.0f) continue;
-        any = true;
-        wsum += wj;
-        const float s = wj * (kShSphere / (float)nj);
-        for (int q = 0; q < 12; ++q) C[q] += s * sh(probe, q);
-    }
-    if (!any) { out[0] = 0.0f; out[1] = 0.0f; out[2] = 0.0f; return false; }
-    float b[9];
-    sh9_basis(nrm[0], nrm[1], nrm[2], b);
-    for (int ch = 0; ch < 3; ++ch) {
-        float m = 0.0f;
-        m += C[ch] * b[0];
-        for (int k = 1; k < 4; ++k) m += (kHemiBand1 * C[3 * k + ch]) * b[k];
-        const float x = m / wsum;
-        out[ch] = clamp ? (x >= 0.0f ? x : 0.0f) : x;
-    }
-    return true;
+    });
 }
 
 // the hit point of a ray (o, d) at t: one multiply and one add per axis (mod.rs:212)

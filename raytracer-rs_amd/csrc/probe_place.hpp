@@ -1,5 +1,5 @@
 // probe_place.hpp — the arithmetic of probe placement (include/mi355rt.h, "PROBE PLACEMENT"): what one sample adds to a probe's survey, where
-// a surveyed probe moves, the state it is given, and the lookup of one query in a grid whose probes have moved.  ONE statement, compiled for the host
+// a surveyed probe moves, the state it is given, and the lookup of one query in a grid whose probes have moved (sh9_corners of sh9.hpp with offsets).  ONE statement, compiled for the host
 // (mi355rt_probe_place_one, mi355rt_probes_lookup_placed_one) and for the device (csrc/probes_place.hip): f32, unfused (every file that includes this is built
 // with -ffp-contract=off), expression for expression what raytracer-rs_amd/probes.py writes in numpy.  Only + - x / sqrt, comparisons and integer conversions.
 #pragma once
@@ -99,71 +99,14 @@ __host__ __device__ __forceinline__ uint32_t place_one(const SurveyState& s, con
     return branch;
 }
 
-// sh9_lookup_vis (oct_vis.hpp) for probes that have moved: the position that enters v = p_b - position is (origin_a + (float)i_a * spacing_a) + offset_a,
-// offset(probe, a) -> f32, asked only with has_off; the cell, the fractions and the trilinear factor stay the grid's.  Without has_off this is sh9_lookup_vis
-// on every bit, with neither flag the offsets are never read and it is sh9_lookup.
+// sh9_lookup_vis (sh9.hpp) for probes that have moved: offset(probe, a) -> f32 enters the position a corner is seen from.  Without has_off this is
+// sh9_lookup_vis on every bit, with neither flag the offsets are never read and it is sh9_lookup.
 template <class N, class Sh, class Usable, class Cnt, class Mom, class Off>
 __host__ __device__ __forceinline__ bool sh9_lookup_placed(const ShGrid& grid, N n, Sh sh, bool has_usable, Usable usable, uint32_t R, Cnt count, Mom moment, bool has_off, Off offset,
                                                            uint32_t flags, float normal_bias, const float* p, const float* dir, bool has_nrm, const float* nrm, uint32_t mode,
                                                            float* rgb)
 {
-    uint32_t i[3]; float f[3], pb[3];
-    for (int a = 0; a < 3; ++a) {
-        sh9_axis(p[a], grid.origin[a], grid.spacing[a], grid.counts[a], i[a], f[a]);
-        pb[a] = has_nrm ? p[a] + normal_bias * nrm[a] : p[a];
-    }
-    const bool cheb = (flags & kVisChebyshev) != 0u, facing = (flags & kVisFacing) != 0u && has_nrm;
-    float C[27];
-    for (int q = 0; q < 27; ++q) C[q] = 0.0f;
-    float wsum = 0.0f;
-    bool any = false;
-    for (uint32_t j = 0; j < 8u; ++j) {
-        uint32_t c[3]; float w[3];
-        for (int a = 0; a < 3; ++a) {
-            const bool up = ((j >> a) & 1u) != 0u;
-            c[a] = up ? (i[a] + 1u <= grid.counts[a] - 1u ? i[a] + 1u : grid.counts[a] - 1u) : i[a];
-            w[a] = up ? f[a] : 1.0f - f[a];
-        }
-        const float t = (w[0] * w[1]) * w[2];
-        if (t == 0.0f) continue;
-        const size_t probe = ((size_t)c[2] * grid.counts[1] + c[1]) * grid.counts[0] + c[0];
-        const uint32_t nj = n(probe);
-        if (nj == 0u) continue;
-        if (has_usable && !usable(probe)) continue;
-        float vis = 1.0f, face = 1.0f;
-        if (cheb || facing) {
-            float pos[3];
-            for (int a = 0; a < 3; ++a) {
-                pos[a] = sh9_probe_pos(grid.origin[a], grid.spacing[a], c[a]);
-                if (has_off) pos[a] = pos[a] + offset(probe, a);
-            }
-            const float vx = pb[0] - pos[0], vy = pb[1] - pos[1], vz = pb[2] - pos[2];
-            const float r = oct_length(vx, vy, vz);
-            if (cheb) vis = oct_visibility(R, [&](uint32_t k) { return count(probe, k); }, [&](uint32_t k, int m) { return moment(probe, k, m); }, vx, vy, vz, r);
-            if (facing && oct_length_fine(r)) face = oct_facing(vx, vy, vz, r, nrm[0], nrm[1], nrm[2]);
-        }
-        const float wj = (t * vis) * face;
-        if (wj == 0.0f) continue;
-        any = true;
-        wsum += wj;
-        const float s = wj * (kShSphere / (float)nj);
-        for (int q = 0; q < 27; ++q) C[q] += s * sh(probe, q);
-    }
-    if (!any) { rgb[0] = 0.0f; rgb[1] = 0.0f; rgb[2] = 0.0f; return false; }
-    float b[9];
-    sh9_basis(dir[0], dir[1], dir[2], b);
-    float r[3] = { 0.0f, 0.0f, 0.0f };
-    if (mode == kShIrradiance) {
-        for (int k = 0; k < 9; ++k) {
-            const float A = k == 0 ? kShA0 : k < 4 ? kShA1 : kShA2;
-            for (int ch = 0; ch < 3; ++ch) r[ch] += (A * C[3 * k + ch]) * b[k];
-        }
-    } else {
-        for (int k = 0; k < 9; ++k)
-            for (int ch = 0; ch < 3; ++ch) r[ch] += C[3 * k + ch] * b[k];
-    }
-    for (int ch = 0; ch < 3; ++ch) rgb[ch] = r[ch] / wsum;
-    return true;
+    return sh9_corners<27, true, true>(grid, n, sh, has_usable, usable, R, count, moment, has_off, offset, flags, normal_bias, p, has_nrm, nrm, dir, mode, rgb, nullptr);
 }
 
 }  // namespace mi355rt

@@ -1,6 +1,6 @@
 // probes_vis.hip — the device side of probe visibility (include/mi355rt.h, "PROBE VISIBILITY"): the depth film of a gather chunk's traced
 // samples over an octahedral map per probe (mi355rt_probes_gather_depth), and the visibility-weighted lookup of a probe grid (mi355rt_probes_lookup_vis).  The
-// arithmetic is csrc/oct_vis.hpp, the statement raytracer-rs_amd/probes.py.
+// arithmetic is csrc/oct_vis.hpp and, for the lookup, csrc/sh9.hpp; the statement raytracer-rs_amd/probes.py.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "probes_vis.hpp"

@@ -1728,24 +1728,53 @@ bool Renderer::probes_gather(const float* points3, const uint32_t* ids, size_t n
     return end_call(traced ? total : 0, true);                        // waits: the staging (and the caller's buffers) are free again
 }
 
-// mi355rt_probes_lookup: arithmetic on the caller's arrays, one kernel.  A read-out that makes no ray: a speculative frame is settled, a queued
-// one is ahead on the same stream, and neither the counters nor any film is touched.
-bool Renderer::probes_lookup(const mi355rt_probe_grid& grid, const uint32_t* n, const float* sh, const uint8_t* usable, const float* points3, const float* dirs3, size_t npoints,
-                             uint32_t mode, bool device, float* rgb3, uint8_t* ok)
+namespace {
+// the volume's arrays on the device: the caller's own, or staged copies
+LitVolume stage_volume(Staging& st, const mi355rt_probe_volume& vol)
+{
+    const mi355rt_probe_grid& grid = *vol.grid;
+    const size_t nprobes = (size_t)grid.counts[0] * grid.counts[1] * grid.counts[2];
+    LitVolume v{};
+    std::memcpy(&v.grid, &grid, sizeof v.grid);
+    v.n = st.in(vol.n, nprobes); v.sh = st.in(vol.sh, nprobes * 27); v.usable = st.in(vol.usable, nprobes);
+    if (vol.depth) {
+        const size_t RR = (size_t)vol.depth->res * vol.depth->res;
+        v.R = vol.depth->res;
+        v.count = st.in((const uint32_t*)vol.depth->count, nprobes * RR); v.moments = st.in((const float*)vol.depth->moments, nprobes * RR * 2);
+        v.offsets = st.in(vol.offsets, nprobes * 3);
+        v.flags = vol.vc->flags; v.normal_bias = vol.vc->normal_bias;
+    }
+    return v;
+}
+}  // namespace
+
+// The read-outs of a probe grid (mi355rt_probes_lookup, _vis, _placed; mi355rt_probe_lit_points): arithmetic on the caller's arrays, one kernel.  Stages the
+// grid's arrays, the queries (dirs3, normals3 may be null) and the outputs, queues what `launch` launches, downloads and waits.  A read-out makes no ray: a
+// speculative frame is settled, a queued one is ahead on the same stream, and neither the counters nor any film is touched.
+template <class Launch>
+bool Renderer::volume_readout(const mi355rt_probe_volume& vol, const float* points3, const float* dirs3, const float* normals3, size_t npoints, bool device, float* rgb3, uint8_t* ok,
+                              Launch launch)
 {
     if (!quiet()) return false;
-    const size_t nprobes = (size_t)grid.counts[0] * grid.counts[1] * grid.counts[2];
-    ShGrid g;
-    std::memcpy(&g, &grid, sizeof g);
     Staging st(stream_, &hbm_bytes_, device);
-    const uint32_t* d_n = st.in(n, nprobes); const float* d_sh = st.in(sh, nprobes * 27); const uint8_t* d_usable = st.in(usable, nprobes);
-    const float* d_points = st.in(points3, npoints * 3); const float* d_dirs = st.in(dirs3, npoints * 3);
+    const LitVolume v = stage_volume(st, vol);
+    const float* d_points = st.in(points3, npoints * 3); const float* d_dirs = st.in(dirs3, npoints * 3); const float* d_normals = st.in(normals3, npoints * 3);
     float* d_rgb = st.out(rgb3, npoints * 3); uint8_t* d_ok = st.out(ok, npoints);
     HIP_TRY(st.error());
-    HIP_TRY(launch_probes_lookup(stream_, g, d_n, d_sh, d_usable, d_points, d_dirs, npoints, mode, d_rgb, d_ok));
+    HIP_TRY(launch(v, d_points, d_dirs, d_normals, d_rgb, d_ok));
     HIP_TRY(st.download());
     HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's buffers are complete, on whatever stream they are used next
     return true;
+}
+
+// mi355rt_probes_lookup
+bool Renderer::probes_lookup(const mi355rt_probe_grid& grid, const uint32_t* n, const float* sh, const uint8_t* usable, const float* points3, const float* dirs3, size_t npoints,
+                             uint32_t mode, bool device, float* rgb3, uint8_t* ok)
+{
+    return volume_readout({ &grid, n, sh, usable, nullptr, nullptr, nullptr }, points3, dirs3, nullptr, npoints, device, rgb3, ok,
+                          [&](const LitVolume& v, const float* p, const float* d, const float*, float* rgb, uint8_t* k) {
+                              return launch_probes_lookup(stream_, v.grid, v.n, v.sh, v.usable, p, d, npoints, mode, rgb, k);
+                          });
 }
 
 // mi355rt_probes_gather_depth: probes_gather with a second reduce over the same traced chunk — the depth film of csrc/probes_vis.hip.  The
@@ -1781,26 +1810,15 @@ bool Renderer::probes_gather_depth(const float* points3, const uint32_t* ids, si
     return end_call(total, true);                                     // waits: the staging (and the caller's buffers) are free again
 }
 
-// mi355rt_probes_lookup_vis: probes_lookup with the depth films among its inputs; one kernel, and probes_lookup's rules around it.
+// mi355rt_probes_lookup_vis: the depth films among the volume's arrays
 bool Renderer::probes_lookup_vis(const mi355rt_probe_grid& grid, const uint32_t* n, const float* sh, const uint8_t* usable, const mi355rt_probe_depth& depth,
                                  const mi355rt_probe_vis_config& vc, const float* points3, const float* dirs3, const float* normals3, size_t npoints, uint32_t mode, bool device,
                                  float* rgb3, uint8_t* ok)
 {
-    if (!quiet()) return false;
-    const size_t nprobes = (size_t)grid.counts[0] * grid.counts[1] * grid.counts[2], RR = (size_t)depth.res * depth.res;
-    ShGrid g;
-    std::memcpy(&g, &grid, sizeof g);
-    Staging st(stream_, &hbm_bytes_, device);
-    const uint32_t* d_n = st.in(n, nprobes); const float* d_sh = st.in(sh, nprobes * 27); const uint8_t* d_usable = st.in(usable, nprobes);
-    const uint32_t* d_count = st.in((const uint32_t*)depth.count, nprobes * RR); const float* d_moments = st.in((const float*)depth.moments, nprobes * RR * 2);
-    const float* d_points = st.in(points3, npoints * 3); const float* d_dirs = st.in(dirs3, npoints * 3); const float* d_normals = st.in(normals3, npoints * 3);
-    float* d_rgb = st.out(rgb3, npoints * 3); uint8_t* d_ok = st.out(ok, npoints);
-    HIP_TRY(st.error());
-    HIP_TRY(launch_probes_lookup_vis(stream_, g, d_n, d_sh, d_usable, depth.res, d_count, d_moments, vc.flags, vc.normal_bias, d_points, d_dirs, d_normals, npoints, mode, d_rgb,
-                                     d_ok));
-    HIP_TRY(st.download());
-    HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's buffers are complete, on whatever stream they are used next
-    return true;
+    return volume_readout({ &grid, n, sh, usable, &depth, &vc, nullptr }, points3, dirs3, normals3, npoints, device, rgb3, ok,
+                          [&](const LitVolume& v, const float* p, const float* d, const float* nr, float* rgb, uint8_t* k) {
+                              return launch_probes_lookup_vis(stream_, v.grid, v.n, v.sh, v.usable, v.R, v.count, v.moments, v.flags, v.normal_bias, p, d, nr, npoints, mode, rgb, k);
+                          });
 }
 
 // mi355rt_gather: the points as a film of their own.  Chunks of cp points x cs samples, sized by the pass capacity as trace_rays sizes its
@@ -2364,63 +2382,25 @@ bool Renderer::probes_place(const mi355rt_probe_grid& grid, const mi355rt_probe_
     return true;
 }
 
-// mi355rt_probes_lookup_placed: probes_lookup_vis with the probes' offsets among its inputs; one kernel, and probes_lookup's rules around it.
+// mi355rt_probes_lookup_placed: the probes' offsets among the volume's arrays too; null offsets still launch this kernel
 bool Renderer::probes_lookup_placed(const mi355rt_probe_grid& grid, const uint32_t* n, const float* sh, const uint8_t* usable, const mi355rt_probe_depth& depth,
                                     const mi355rt_probe_vis_config& vc, const float* offsets, const float* points3, const float* dirs3, const float* normals3, size_t npoints,
                                     uint32_t mode, bool device, float* rgb3, uint8_t* ok)
 {
-    if (!quiet()) return false;
-    const size_t nprobes = (size_t)grid.counts[0] * grid.counts[1] * grid.counts[2], RR = (size_t)depth.res * depth.res;
-    ShGrid g;
-    std::memcpy(&g, &grid, sizeof g);
-    Staging st(stream_, &hbm_bytes_, device);
-    const uint32_t* d_n = st.in(n, nprobes); const float* d_sh = st.in(sh, nprobes * 27); const uint8_t* d_usable = st.in(usable, nprobes);
-    const uint32_t* d_count = st.in((const uint32_t*)depth.count, nprobes * RR); const float* d_moments = st.in((const float*)depth.moments, nprobes * RR * 2);
-    const float* d_off = st.in(offsets, nprobes * 3);
-    const float* d_points = st.in(points3, npoints * 3); const float* d_dirs = st.in(dirs3, npoints * 3); const float* d_normals = st.in(normals3, npoints * 3);
-    float* d_rgb = st.out(rgb3, npoints * 3); uint8_t* d_ok = st.out(ok, npoints);
-    HIP_TRY(st.error());
-    HIP_TRY(launch_probes_lookup_placed(stream_, g, d_n, d_sh, d_usable, depth.res, d_count, d_moments, d_off, vc.flags, vc.normal_bias, d_points, d_dirs, d_normals, npoints, mode,
-                                        d_rgb, d_ok));
-    HIP_TRY(st.download());
-    HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's buffers are complete, on whatever stream they are used next
-    return true;
+    return volume_readout({ &grid, n, sh, usable, &depth, &vc, offsets }, points3, dirs3, normals3, npoints, device, rgb3, ok,
+                          [&](const LitVolume& v, const float* p, const float* d, const float* nr, float* rgb, uint8_t* k) {
+                              return launch_probes_lookup_placed(stream_, v.grid, v.n, v.sh, v.usable, v.R, v.count, v.moments, v.offsets, v.flags, v.normal_bias, p, d, nr, npoints, mode,
+                                                                 rgb, k);
+                          });
 }
 
 // ---- probe-lit shading (include/mi355rt.h, "PROBE-LIT") ----------------------------------------------------------------------------------
-namespace {
-// the volume's arrays on the device: the caller's own, or staged copies
-LitVolume stage_volume(Staging& st, const mi355rt_probe_volume& vol)
-{
-    const mi355rt_probe_grid& grid = *vol.grid;
-    const size_t nprobes = (size_t)grid.counts[0] * grid.counts[1] * grid.counts[2];
-    LitVolume v{};
-    std::memcpy(&v.grid, &grid, sizeof v.grid);
-    v.n = st.in(vol.n, nprobes); v.sh = st.in(vol.sh, nprobes * 27); v.usable = st.in(vol.usable, nprobes);
-    if (vol.depth) {
-        const size_t RR = (size_t)vol.depth->res * vol.depth->res;
-        v.R = vol.depth->res;
-        v.count = st.in((const uint32_t*)vol.depth->count, nprobes * RR); v.moments = st.in((const float*)vol.depth->moments, nprobes * RR * 2);
-        v.offsets = st.in(vol.offsets, nprobes * 3);
-        v.flags = vol.vc->flags; v.normal_bias = vol.vc->normal_bias;
-    }
-    return v;
-}
-}  // namespace
-
-// mi355rt_probe_lit_points: arithmetic on the caller's arrays, one kernel, and probes_lookup's rules around it.
+// mi355rt_probe_lit_points: the hemisphere mean as one more read-out of the volume
 bool Renderer::probe_lit_points(const mi355rt_probe_volume& vol, const float* points3, const float* normals3, size_t npoints, uint32_t flags, bool device, float* indirect3, uint8_t* ok)
 {
-    if (!quiet()) return false;
-    Staging st(stream_, &hbm_bytes_, device);
-    const LitVolume v = stage_volume(st, vol);
-    const float* d_points = st.in(points3, npoints * 3); const float* d_normals = st.in(normals3, npoints * 3);
-    float* d_ind = st.out(indirect3, npoints * 3); uint8_t* d_ok = st.out(ok, npoints);
-    HIP_TRY(st.error());
-    HIP_TRY(launch_probe_lit_points(stream_, v, (flags & MI355RT_PROBE_LIT_CLAMP) != 0, d_points, d_normals, npoints, d_ind, d_ok));
-    HIP_TRY(st.download());
-    HIP_TRY(hipStreamSynchronize(stream_));                           // the caller's buffers are complete, on whatever stream they are used next
-    return true;
+    return volume_readout(vol, points3, nullptr, normals3, npoints, device, indirect3, ok, [&](const LitVolume& v, const float* p, const float*, const float* nr, float* ind, uint8_t* k) {
+        return launch_probe_lit_points(stream_, v, (flags & MI355RT_PROBE_LIT_CLAMP) != 0, p, nr, npoints, ind, k);
+    });
 }
 
 // mi355rt_probe_lit_rays: the rays in chunks; per chunk the closest-hit launch of mi355rt_intersect_rays into two chunk temporaries (as probes_survey takes

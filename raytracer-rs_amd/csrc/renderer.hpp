@@ -178,6 +178,10 @@ private:
     bool bind();
     bool quiet();                         // bind() and settle_speculation()
     bool fail(hipError_t e, const char* what);
+    // the host path of every read-out of a probe grid: launch(volume, points, dirs, normals, rgb, ok) queues its kernel on the staged arrays
+    template <class Launch>
+    bool volume_readout(const mi355rt_probe_volume& vol, const float* points3, const float* dirs3, const float* normals3, size_t npoints, bool device, float* rgb3, uint8_t* ok,
+                        Launch launch);
     // A frame slice: an interleaved share of the owned rows with its own stream and pass buffers.  The
     // slices of one render() call run concurrently, so that the drain window at the end of one slice's
     // (persistent) trace launch is filled by the other slices' kernels.  Pixels of different slices are
